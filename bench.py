@@ -12,13 +12,17 @@ N > 1: one process per GPU, one independent locus per rank (loci are independent
 command/genotype.rs:1331-1351) -> weak scaling, no data-path collective; torch.distributed (gloo)
 only carries the barrier and the max-over-ranks of the timed region.
 
-Prints ONE JSON line on rank 0. The legs beside the timed region live in bench_legs/ (its __init__ lists them).
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the steps and prints the headline; --full adds everything
+measured or checked beside the timed region (per-stage and per-kernel figures of one more locus, rooflines, the legs of bench_legs/
+— its __init__ lists them —, the CPU baseline, the queue of distinct loci). --dump-outputs DIR writes what the last timed step
+handed its caller as DIR/<name>.npy (float64).
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -103,6 +107,14 @@ def parse_args():
                          "solvers against each other in any case)")
     ap.add_argument("--recovery-sample", type=int, default=262144,
                     help="read pairs of the extra alignment-recovery measurement (K6, outside the timed region; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: per-stage and per-kernel figures of one more locus solved call by call, "
+                         "rooflines, the legs of bench_legs/, the CPU baseline, the queue of distinct loci (the --*-sample options and "
+                         "--distinct-loci size them); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step handed its caller (the call: genotype indices, their alleles "
+                         "and log-probabilities, quality, counts; with --no-solve the genotypes kept by the prefilter) as DIR/<name>.npy, "
+                         "float64; bench_outputs, which git ignores, keeps them inside the tree")
     return ap.parse_args()
 
 
@@ -160,41 +172,49 @@ def load_loci(args, ctx, n_loci, rank, world, one_locus, first_pair, total_pairs
     params = None
     counted = args.format == "counted"
     n_chunks = (args.pairs + args.chunk - 1) // args.chunk
-    for j in range(n_loci):
-        seed_off = int(args.loci_seeds.split(",")[j]) if args.loci_seeds else (0 if one_locus else n_loci * rank + j)
-        L = synth.SynthLocus(A, total_pairs, seed=synth.SEED + seed_off)
-        params = api.resolve_params(api.default_params(), L.bg)
-        t1 = time.time()
-        loc = api.Locus(ctx, L.seqs, L.seq_off, L.counts, L.cnt_off, L.k, L.bg, params)
-        ctx.synchronize()
-        locus_setup_s += time.time() - t1
-        # generate chunk by chunk, keep totals, and allocate from the first chunk's density with head-room
-        c0 = L.reads(first_pair, min(args.chunk, args.pairs))
-        dens_b, dens_r, dens_c = c0.n_bases / c0.n_pairs, len(c0.recs) / c0.n_pairs, len(c0.cigar) / c0.n_pairs
-        head = 1.03
-        cap_bases = (int(dens_b * args.pairs * head) + 1024) // 32 * 32 + 32
-        aa = api.AllAlignments(loc, args.pairs, cap_bases, int(dens_r * args.pairs * head) + 4096,
-                               0 if counted else int(dens_c * args.pairs * head) + 65536)
-        # the chunks of the resident loci stay on the host when the queue of NON-resident loci is measured afterwards (it uploads them again)
-        keep_host = args.distinct_loci >= 2 and not one_locus and not args.no_solve and world == 1 and counted
-        host_chunks.append([c0] if keep_host else None)
-        aa.append(c0, counted=counted)
-        if j == 0:
-            totals.update(recs=len(c0.recs), cigar=len(c0.cigar), bases=c0.n_bases)
-            first = c0 if (rank == 0 and world == 1 and args.cpu_sample > 0) else None
-        for ci in range(1, n_chunks):
-            lo = ci * args.chunk
-            ch = L.reads(first_pair + lo, min(args.chunk, args.pairs - lo))
-            aa.append(ch, counted=counted)
+
+    def gen(L, ci):
+        lo = ci * args.chunk
+        return L.reads(first_pair + lo, min(args.chunk, args.pairs - lo))
+
+    # one chunk ahead: the generator (C, OpenMP; ctypes releases the GIL) makes chunk ci + 1 while chunk ci is counted and uploaded
+    with ThreadPoolExecutor(1) as ahead:
+        for j in range(n_loci):
+            seed_off = int(args.loci_seeds.split(",")[j]) if args.loci_seeds else (0 if one_locus else n_loci * rank + j)
+            L = synth.SynthLocus(A, total_pairs, seed=synth.SEED + seed_off)
+            params = api.resolve_params(api.default_params(), L.bg)
+            t1 = time.time()
+            loc = api.Locus(ctx, L.seqs, L.seq_off, L.counts, L.cnt_off, L.k, L.bg, params)
+            ctx.synchronize()
+            locus_setup_s += time.time() - t1
+            # generate chunk by chunk, keep totals, and allocate from the first chunk's density with head-room
+            c0 = gen(L, 0)
+            nxt = ahead.submit(gen, L, 1) if n_chunks > 1 else None
+            dens_b, dens_r, dens_c = c0.n_bases / c0.n_pairs, len(c0.recs) / c0.n_pairs, len(c0.cigar) / c0.n_pairs
+            head = 1.03
+            cap_bases = (int(dens_b * args.pairs * head) + 1024) // 32 * 32 + 32
+            aa = api.AllAlignments(loc, args.pairs, cap_bases, int(dens_r * args.pairs * head) + 4096,
+                                   0 if counted else int(dens_c * args.pairs * head) + 65536)
+            # the chunks of the resident loci stay on the host when the queue of NON-resident loci is measured afterwards (it uploads them again)
+            keep_host = args.full and args.distinct_loci >= 2 and not one_locus and not args.no_solve and world == 1 and counted
+            host_chunks.append([c0] if keep_host else None)
+            aa.append(c0, counted=counted)
             if j == 0:
-                totals["recs"] += len(ch.recs)
-                totals["cigar"] += len(ch.cigar)
-                totals["bases"] += ch.n_bases
-            if keep_host:
-                host_chunks[j].append(ch)
-            del ch
-        loci.append((L, loc))
-        batches.append(aa)
+                totals.update(recs=len(c0.recs), cigar=len(c0.cigar), bases=c0.n_bases)
+                first = c0 if (args.full and rank == 0 and world == 1 and args.cpu_sample > 0) else None
+            for ci in range(1, n_chunks):
+                ch = nxt.result()
+                nxt = ahead.submit(gen, L, ci + 1) if ci + 1 < n_chunks else None
+                aa.append(ch, counted=counted)
+                if j == 0:
+                    totals["recs"] += len(ch.recs)
+                    totals["cigar"] += len(ch.cigar)
+                    totals["bases"] += ch.n_bases
+                if keep_host:
+                    host_chunks[j].append(ch)
+                del ch
+            loci.append((L, loc))
+            batches.append(aa)
     return loci, batches, host_chunks, params, first, totals, locus_setup_s
 
 
@@ -223,6 +243,60 @@ def records_format_figure(args, ctx, loc, chunks, totals):
             "what": "lcty_score_reads on the same read pairs as 16-byte BAM records + CIGAR words (the kernel counts the operations: "
                     "Alignment::count_region_operations_fast, aln.rs:301-317), nothing else on the device; SURVEY 8(d)'s 12 331 B per pair, "
                     "and the same plus 4 B per CIGAR word"}
+
+
+def line_rooflines(args, aa, timers, per_step, alone_ms, beside_the_chains, totals, G, sha16):
+    """--full: the rooflines of the kernels of a step; `roofline` is the one with the most kernel time (DESIGN.md §4 for the bytes).
+    alone_ms: the kernels of the locus solved call by call after the queue (None outside the queue mode)."""
+    A = args.alleles
+    n_score, ms_score = timers["score_reads_kernel"]
+    score_ms = ms_score / max(n_score, 1)
+    layout_bytes = (totals["bases"] / 4 + totals["bases"] / 8 + 16 * totals["recs"]
+                    + (0 if args.format == "counted" else 4 * totals["cigar"]) + 8 * A * args.pairs
+                    + 8 * 4 * args.pairs)      # what the kernel's inputs/outputs occupy, excl. pair-alignment arena
+    roofs = RL.kernel_rooflines(ROOT, timers, args.steps, args.pairs, A, G, aa.n_good(), per_step, beside_the_chains)
+    # the dominant kernel of a step: the one with the most time on the MAIN stream, whose kernels run back to back and make up the
+    # step; the annealing chains of the locus before run on the side stream next to them (overlapped, never on the critical path of
+    # the queue) and are reported in roofline_all like everything else
+    dominant = max((k for k in roofs if roofs[k]["bound"] == "hbm" and k != "anneal_loop_kernel"), key=lambda k: roofs[k]["ms_per_step"])
+    if alone_ms is not None:
+        RL.attach_alone(roofs, alone_ms)
+    traffic_path = args.traffic or RL.newest(ROOT, "r*_pmc_traffic.json")
+    traffic_info = RL.attach_traffic(ROOT, roofs, traffic_path, args.pairs, A, sha16) if traffic_path else {}
+    RL.attach_sq(ROOT, roofs, sha16)
+    dom = roofs[dominant]
+    return {
+        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": dom["achieved"], "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": dom["frac"], "traffic": dom.get("traffic"),
+                     "algorithmic_bytes_per_launch": dom["bytes"], "launch_ms": dom["launch_ms"], "what": dom["what"],
+                     "traffic_fetch_raw": dom.get("traffic_fetch_raw"), "traffic_fetch_x2": dom.get("traffic_fetch_x2"),
+                     "traffic_write": dom.get("traffic_write"), "traffic_rule": dom.get("traffic_rule"), "sq": dom.get("sq"),
+                     **traffic_info},
+        "roofline_all": roofs,
+        "roofline_score_layout": {"layout_bytes_per_launch": layout_bytes,
+                                  "achieved_layout_GBs": layout_bytes / (score_ms * 1e-3) / 1e9 if score_ms else None},
+    }
+
+
+def dump_outputs(path, result, queue_mode, gts):
+    """--dump-outputs: what the last timed step handed its caller, one float64 array per file (a few KB in all). Queue mode: the call
+    of the queue's last locus (lcty_call); call by call: the genotypes the prefilter kept and, with the solver, produce_result's call."""
+    os.makedirs(path, exist_ok=True)
+    if queue_mode:
+        c = result[-1]
+        n = int(c.n_out)
+        ixs = np.array(c.ixs[:n], dtype=np.uint64)
+        arrays = {"call_ixs": ixs, "call_genotypes": gts[ixs], "call_ln_probs": np.array(c.ln_probs[:n]),
+                  "call_quality": [c.quality], "call_unexpl_reads": [c.unexpl_reads], "call_warnings": [c.warnings],
+                  "call_n_good": [c.n_good], "call_kept_after_filter": [c.kept_after_filter]}
+    else:
+        keep, res = result
+        arrays = {"prefilter_kept_ixs": keep}
+        if res is not None:
+            ixs, ln_probs, quality = res
+            arrays.update(call_ixs=ixs, call_genotypes=gts[ixs], call_ln_probs=ln_probs, call_quality=[quality])
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def main():
@@ -363,7 +437,7 @@ def main():
         quality = float(calls[-1].quality)
         greedy_chains_per_step = float(np.mean([int(c.kept_after_filter) for c in calls]))
         # per-stage wall times and iteration counts: one more locus call by call, outside the timed region
-        if rank == 0:
+        if rank == 0 and args.full:
             ctx.timing_reset()          # the queue's timers have been read: what follows are the kernels with nothing beside them
             step(7)
             ctx.synchronize()
@@ -381,32 +455,12 @@ def main():
 
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result, queue_mode, gts)
 
-    n_break = 1 if queue_mode else args.steps                  # steps behind stage_s / solved
     ms_per_step = 1e3 * elapsed / args.steps
     reads_per_s = (total_pairs if one_locus else world * args.pairs) * args.steps / elapsed
-    n_score, ms_score = timers["score_reads_kernel"]
-    n_pref, ms_pref = timers["prefilter_tile_kernel"]
-    score_ms = ms_score / max(n_score, 1)
-    pref_ms = ms_pref / max(n_pref, 1)
-    layout_bytes = (totals["bases"] / 4 + totals["bases"] / 8 + 16 * totals["recs"]
-                    + (0 if args.format == "counted" else 4 * totals["cigar"]) + 8 * A * args.pairs
-                    + 8 * 4 * args.pairs)      # what the kernel's inputs/outputs occupy, excl. pair-alignment arena
-    n_good = aa.n_good()
-    per_step = {k: v / max(n_break, 1) for k, v in solved.items()}
     sha16 = sources_sha16(ROOT)
-    # ---- rooflines of the kernels of a step; `roofline` is the one with the most kernel time (DESIGN.md §4 for the bytes) ----
-    roofs = RL.kernel_rooflines(ROOT, timers, args.steps, args.pairs, A, G, n_good, per_step, queue_mode and early_head)
-    # the dominant kernel of a step: the one with the most time on the MAIN stream, whose kernels run back to back and make up the
-    # step; the annealing chains of the locus before run on the side stream next to them (overlapped, never on the critical path of
-    # the queue) and are reported in roofline_all like everything else
-    dominant = max((k for k in roofs if roofs[k]["bound"] == "hbm" and k != "anneal_loop_kernel"), key=lambda k: roofs[k]["ms_per_step"])
-    if queue_mode:
-        RL.attach_alone(roofs, alone_ms)
-    traffic_path = args.traffic or RL.newest(ROOT, "r*_pmc_traffic.json")
-    traffic_info = RL.attach_traffic(ROOT, roofs, traffic_path, args.pairs, A, sha16) if traffic_path else {}
-    RL.attach_sq(ROOT, roofs, sha16)
-    dom = roofs[dominant]
     workload = (f"{args.pairs} synthetic 150 bp PE read pairs x {A} alleles, 1 locus per step, k=25 "
                 + ("(BASELINE.json configs[1])" if (total_pairs, A) == (1_000_000, 256) and not one_locus
                    else "(one GPU's share of BASELINE.json configs[4])" if A == 4096 else "(not a BASELINE.json configuration)"))
@@ -442,38 +496,38 @@ def main():
         "vs_baseline": None,
         "dtype": "f64",
         "data": "synthetic",
+        "full": args.full,
         "config": {"workload": workload, "read_pairs": args.pairs, "alleles": A, "genotypes": G, "k": 25,
                    "records": totals["recs"], "cigar_words": totals["cigar"],
                    "alignment_table": ("16-byte counted alignments (lcty_reads_append_counted): the caller counts the CIGAR operations"
                                        if args.format == "counted" else "16-byte BAM records + CIGAR words (lcty_reads_append)"),
                    "step": step_what, "parallelism": parallelism},
-        "reads_scored_per_s": (total_pairs if args.shard_reads else args.pairs) * n_break / max(stage_s["score_prefilter"], 1e-9),
-        "genotypes_prefiltered_per_s": G * n_break / max(stage_s["score_prefilter"], 1e-9),
-        "prefilter_genotypes_per_s_kernel": G / (pref_ms * 1e-3) if pref_ms else None,
-        "kernel_ms_per_step": ({k: r["ms_per_step"] for k, r in roofs.items()}
-                               | {"build_loc_table_kernel": timers["build_loc_table_kernel"][1] / args.steps}),
+        "kernel_ms_per_step": {name: msk / args.steps for name, (_, msk) in timers.items()},
         "solver": None if args.no_solve else {
             "scheme": "greedy:i=5k,a=1 -> anneal:i=20,a=20 -> final comparison",
             "genotypes_solved_per_s": world * (greedy_chains_per_step + 20) * args.steps / elapsed,
             "chains_per_s": world * (greedy_chains_per_step + 400) * args.steps / elapsed,
-            "per_step": per_step,
-            "call_by_call_stage_ms": {k: 1e3 * v / max(n_break, 1) for k, v in stage_s.items()},
             "quality": quality, "all_calls_equal_truth": calls_ok},
-        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": dom["achieved"], "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": dom["frac"], "traffic": dom.get("traffic"),
-                     "algorithmic_bytes_per_launch": dom["bytes"], "launch_ms": dom["launch_ms"], "what": dom["what"],
-                     "traffic_fetch_raw": dom.get("traffic_fetch_raw"), "traffic_fetch_x2": dom.get("traffic_fetch_x2"),
-                     "traffic_write": dom.get("traffic_write"), "traffic_rule": dom.get("traffic_rule"), "sq": dom.get("sq"),
-                     **traffic_info},
-        "roofline_all": roofs,
-        "roofline_score_layout": {"layout_bytes_per_launch": layout_bytes,
-                                  "achieved_layout_GBs": layout_bytes / (score_ms * 1e-3) / 1e9 if score_ms else None},
         "kernel_sources_sha16": sha16,
         "called_genotype": called, "true_genotype": truth, "kept_after_prefilter": kept,
         "setup_s": {"generate_and_upload": gen_s, "locus_create": locus_setup_s},
     }
+    n_pref, ms_pref = timers["prefilter_tile_kernel"]
+    pref_ms = ms_pref / max(n_pref, 1)
+    out["prefilter_genotypes_per_s_kernel"] = G / (pref_ms * 1e-3) if pref_ms else None
+    # the per-stage figures: the timed steps themselves call by call; in the queue mode the locus solved call by call after it (--full)
+    if args.full or not queue_mode:
+        n_break = 1 if queue_mode else args.steps                  # steps behind stage_s / solved
+        per_step = {k: v / max(n_break, 1) for k, v in solved.items()}
+        out["reads_scored_per_s"] = (total_pairs if args.shard_reads else args.pairs) * n_break / max(stage_s["score_prefilter"], 1e-9)
+        out["genotypes_prefiltered_per_s"] = G * n_break / max(stage_s["score_prefilter"], 1e-9)
+        if out["solver"] is not None:
+            out["solver"]["per_step"] = per_step
+            out["solver"]["call_by_call_stage_ms"] = {k: 1e3 * v / max(n_break, 1) for k, v in stage_s.items()}
+    if args.full:
+        out.update(line_rooflines(args, aa, timers, per_step, alone_ms if queue_mode else None, queue_mode and early_head, totals, G, sha16))
 
-    extra = world == 1
+    extra = world == 1 and args.full
     if extra:
         progress("timed region done")
         ctx.trim()          # the solver workspaces of the timed steps (160 GB) make room for the extra measurements below

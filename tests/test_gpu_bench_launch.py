@@ -62,5 +62,33 @@ def test_one_locus_sharded_over_the_ranks_through_the_whole_path(mode):
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == n and out["rccl_ranks"] == n and out["scaling"] == "strong"
     assert out["solver"] is not None and tuple(out["called_genotype"]) == tuple(out["true_genotype"])
+    # call by call, the timed steps give the per-stage figures themselves: a plain line carries them
+    assert out["reads_scored_per_s"] > 0 and out["solver"]["call_by_call_stage_ms"]["score_prefilter"] > 0
     if n > 1:
         assert out["ms_per_step_ranks"]["min"] <= out["ms_per_step_ranks"]["max"] == pytest.approx(out["ms_per_step"])
+
+
+@pytest.mark.gpu
+def test_plain_line_full_line_and_the_dumped_outputs(tmp_path):
+    """A plain run prints the headline alone; --dump-outputs writes the call of the last timed step as float64 arrays; --full adds the
+    figures beside the timed region. The same arguments give the same inputs, so both runs dump the same call."""
+    import numpy as np
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    r = run_bench(["--gpus", "1", "--dump-outputs", str(plain)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["full"] is False and out["steps"] == 2 and out["ms_per_step"] > 0 and out["dtype"] == "f64"
+    assert "roofline_all" not in out and "distinct_loci_queue" not in out and "per_step" not in out["solver"]
+    arrays = {p.name: np.load(p) for p in plain.glob("*.npy")}
+    assert {"call_ixs.npy", "call_genotypes.npy", "call_ln_probs.npy", "call_quality.npy"} <= set(arrays)
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert tuple(arrays["call_genotypes.npy"][0]) == tuple(out["called_genotype"]) == tuple(out["true_genotype"])
+    assert arrays["call_quality.npy"][0] == out["solver"]["quality"]
+    r = run_bench(["--gpus", "1", "--full", "--dump-outputs", str(full)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    out_full = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out_full["full"] is True and "roofline_all" in out_full and "call_by_call_stage_ms" in out_full["solver"]
+    assert "distinct_loci_queue" in out_full and out_full["distinct_loci_queue"]["all_calls_equal_truth"] is True
+    assert sorted(p.name for p in full.glob("*.npy")) == sorted(arrays)
+    for name, a in arrays.items():
+        np.testing.assert_allclose(np.load(full / name), a, rtol=1e-12, atol=0, err_msg=name)
