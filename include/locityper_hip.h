@@ -838,6 +838,112 @@ int32_t lcty_paf_read(const char* path, const char* const* names, uint32_t n_all
  * i < j row by row. dist[n_alleles x n_alleles]: symmetric, LCTY_NONE_U32 on the diagonal: the `dist` of lcty_call_checks, "minim-div". */
 int32_t lcty_distances_parse(const uint8_t* buf, uint64_t len, uint32_t n_alleles, uint32_t* k, uint32_t* w, uint32_t* dist);
 
+/* ---- background distributions of a sample (locityper preproc, existing alignments + a background region) ------------------------
+ * estimate_bg_distrs (src/command/preproc.rs:1157-1192) with `-a`: the alignments of ONE background interval [start, end) of one
+ * contig, read sequentially from a BAM file that holds them (a slice of the sample's BAM: no BAI fetch, no CRAM), the reference
+ * sequence of the interval +- 50 kb (BgRegion::new, preproc.rs:1357-1385) and the k-mer counts of that padded sequence (what
+ * `jellyfish query` returns for it; the caller runs jellyfish). Out of scope: mapping reads (run_mapping, 918), --similar-dataset
+ * (estimate_like, 1293), input subsampling (only the rate enters the depth fit), the region-less OpCounter::Unbounded path.
+ *
+ * lcty_bg_reads_load: IndexedReader::fetch (records of `contig` overlapping [start, end), file order) + load_alns (preproc.rs:988-1028):
+ *   flags & 3844 == 0, MAPQ >= min_mapq, clipping_rate <= max_clipping (seq/cigar.rs:944-966; first and last op that consume no
+ *   reference, a one-op CIGAR twice, over SEQ length); records whose extended CIGAR cannot be inferred from the padded sequence (an
+ *   M run starting before it or ending at or past its end, cigar.rs:446-448) are dropped and counted. Mates by read name
+ *   (group_mates, bg/insertsz.rs:25-37). Errors (LCTY_ERR_INVALID_DATA): paired and unpaired records mixed, no records, a read with
+ *   two first (second) mates, SEQ length != CIGAR query length (the reference panics), an op other than M I D S = X (H, N, P: the
+ *   reference panics in count_region_operations). Paired-end data with a technology other than Illumina -> LCTY_ERR_INVALID_INPUT.
+ * lcty_bg_estimate: estimate_bg_from_paired / _unpaired (preproc.rs:1065-1155) -> lcty_bg + the mean read length (read_len_from_alns,
+ *   1031-1037; SequencingInfo::new 304-322: out of the technology's range -> LCTY_ERR_INVALID_INPUT unless explicit_technology).
+ *   padded_seq: upper-case A/C/G/T only (JfKmerGetter::fetch refuses Ns, seq/counts.rs:326-327: LCTY_ERR_INVALID_INPUT);
+ *   kmer_counts[padded_len + 1 - k]: the counts of every k-mer of padded_seq, already clamped (KmerCounts::subregion, 234-246 takes
+ *   the interval's part). Errors as the reference: < 1000 pairs / FF-RR orientation / match probability <= 0.5 -> INVALID_DATA,
+ *   zero kept windows -> RUNTIME. Integer work on the device; fits on the host (what is exact, what is a tolerance).
+ * lcty_bg_diag: the --debug intermediates. lcty_bg_diag_sizes gives n_windows, n_records, n_pairs; hist_* need n_pairs entries,
+ *   edit_* n_records (upper bounds: n_hist / n_edit say how many were written). Any array may be NULL.
+ * lcty_bg_to_json: BgDistr::save (bg/mod.rs:147-158) as text, total_reads / file_size null; doubles in the shortest form that reads
+ *   back bit-exact; `ploidy` is bg_depth.ploidy (lcty_bg does not carry it). Two calls: out = NULL sizes it (*needed includes the final 0). */
+typedef struct lcty_bg_params {
+    int32_t  technology;          /* LCTY_TECH_* */
+    int32_t  explicit_technology; /* 1: a read length outside the technology's range is a warning, not an error (bg/mod.rs:304-322) */
+    uint32_t min_mapq;            /* 30 (preproc.rs:275) */
+    uint32_t ploidy;              /* 2 (bg/depth.rs:172) */
+    double   max_clipping;        /* 0.02 (preproc.rs:294) */
+    double   insert_pval;         /* 0.001 (bg/mod.rs:39-46) */
+    double   edit_pval;           /* 0.01 */
+    uint32_t window_size;         /* 0 = auto: clamp(round(2/3 read length), 20, 5000) (bg/windows.rs:103-109) */
+    uint32_t boundary_size;       /* 1000 */
+    double   uniq_kmer_perc;      /* 90 */
+    double   frac_windows;        /* 0.5 */
+    uint32_t min_tail_obs;        /* 100 */
+    uint32_t _pad0;
+    double   tail_var_mult;       /* 0.02 */
+    double   subsampling_rate;    /* 1.0 */
+} lcty_bg_params;
+
+typedef struct lcty_bg_reads lcty_bg_reads;
+#define LCTY_BG_REVERSE 1u          /* lcty_bg_reads_view.flags */
+#define LCTY_BG_SECOND  2u          /* ReadEnd::Second (BAM flag 0x80) */
+typedef struct lcty_bg_reads_view {
+    uint64_t n_records;           /* kept records (file order) */
+    uint64_t n_ignored;           /* failed flags / MAPQ / clipping */
+    uint64_t n_wo_cigar;          /* no extended CIGAR (outside the padded sequence) */
+    int32_t  paired;
+    uint32_t _pad0;
+    double   read_len;            /* mean query length of the first 10 000 kept records */
+    const uint32_t* pos;          /* [n] 0-based start */
+    const uint32_t* end;          /* [n] start + reference length */
+    const uint32_t* qlen;         /* [n] query length */
+    const uint8_t*  flags;        /* [n] LCTY_BG_* */
+    const uint32_t* mate;         /* [n] index of the other end of a full pair, LCTY_NONE_U32 without one */
+    const uint64_t* cigar_off;    /* [n + 1] */
+    const uint32_t* cigar;        /* raw BAM CIGAR words */
+    const uint64_t* seq_off;      /* [n + 1] base offsets, multiples of 32; bases2 / nmask as lcty_reads_host */
+    const uint32_t* bases2;
+    const uint32_t* nmask;
+} lcty_bg_reads_view;
+
+typedef struct lcty_bg_diag {
+    uint64_t n_windows, n_records, n_pairs, n_hist, n_edit;   /* n_hist / n_edit: written by lcty_bg_estimate */
+    /* per window [n_windows] (filter_windows, bg/windows.rs:44-101; count_reads, depth.rs:27-39) */
+    uint32_t* win_start; double* win_gc; double* win_kmer_frac; uint8_t* win_keep; uint32_t* win_depth /* [2 n_windows] */;
+    /* per record [n_records] (count_region_operations, seq/aln.rs:241-281; edit_distance, err_prof.rs:73-79) */
+    uint32_t* rec_counts /* [5 n_records] =, X, I, D, S */; uint32_t* rec_edit; uint32_t* rec_read_len; uint32_t* rec_middle;
+    uint32_t* rec_window /* LCTY_NONE_U32 outside */;
+    /* per pair [n_pairs]: the pairs in order of their first end, insert size and FF/RR (seq/aln.rs:223-233) */
+    uint32_t* pair_first; uint32_t* pair_second; uint32_t* pair_insert; uint8_t* pair_same_strand;
+    /* insert sizes (InsertDistr::estimate, insertsz.rs:67-143) */
+    uint32_t* hist_size; uint32_t* hist_count;               /* [n_hist] ascending size, inserts < 500 000 */
+    uint64_t orient[2];                                      /* FR/RF, FF/RR */
+    double   ins_limit, ins_mean, ins_var;                   /* 3 x q0.99, mean / variance of the inserts <= limit */
+    uint32_t ci_low, ci_high;                                /* confidence_interval(1 - insert_pval) */
+    /* error profile (ErrorProfile::estimate, err_prof.rs:152-197) */
+    uint64_t op_totals[5];
+    uint32_t* edit_edit; uint32_t* edit_len; uint64_t* edit_count;   /* [n_edit] ascending (edit, read_len) */
+    double   unif_coef;
+    /* records / pairs entering each stage: 0 loaded records, 1 pairs, 2 pairs in the histogram, 3 error-profile records,
+     * 4 of them in kept windows, 5 depth records (edit-filtered) */
+    uint64_t n_stage[6];
+    /* depth (ReadDepth::estimate, depth.rs:300-345) per GC bin */
+    uint32_t gc_nwin[LCTY_GC_BINS];
+    double   loess_mean[LCTY_GC_BINS], loess_var[LCTY_GC_BINS], blur_mean[LCTY_GC_BINS], blur_var[LCTY_GC_BINS];
+    double   nb_n[LCTY_GC_BINS], nb_p[LCTY_GC_BINS];
+    double   depth_mean, depth_var;                          /* technologies without GC bias: the one mean / variance */
+    /* timing of this call: device time of windows / counts / pairs / depth kernels (events), host fits, whole call (ms) */
+    double   kernel_ms[4], fit_ms, total_ms;
+} lcty_bg_diag;
+
+void    lcty_bg_params_default(lcty_bg_params* params);
+int32_t lcty_bg_reads_load(const char* path, const char* contig, uint32_t start, uint32_t end, uint32_t padded_start, uint32_t padded_len,
+                           const lcty_bg_params* params, lcty_bg_reads** out);
+int32_t lcty_bg_reads_view_get(const lcty_bg_reads* reads, lcty_bg_reads_view* view);
+void    lcty_bg_reads_free(lcty_bg_reads* reads);
+int32_t lcty_bg_diag_sizes(const lcty_bg_reads* reads, uint32_t region_start, uint32_t region_end, const lcty_bg_params* params,
+                           uint64_t* n_windows, uint64_t* n_records, uint64_t* n_pairs);
+int32_t lcty_bg_estimate(lcty_ctx* ctx, const lcty_bg_reads* reads, const uint8_t* padded_seq, uint32_t padded_start, uint32_t padded_len,
+                         const uint16_t* kmer_counts, uint32_t k, uint32_t region_start, uint32_t region_end, const lcty_bg_params* params,
+                         lcty_bg* out, double* read_len, lcty_bg_diag* diag /* may be NULL */);
+int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, char* out, uint64_t cap, uint64_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import Bg, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
+from .cdefs import Bg, BgParams, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -24,6 +24,13 @@ P = C.POINTER
 
 # name -> (restype, argtypes): every symbol declared in include/locityper_hip.h
 SIGNATURES = {
+    "lcty_bg_params_default": (None, [P(BgParams)]),
+    "lcty_bg_reads_load": (I32, [C.c_char_p, C.c_char_p, U32, U32, U32, U32, P(BgParams), P(VP)]),
+    "lcty_bg_reads_view_get": (I32, [VP, P(BgReadsView)]),
+    "lcty_bg_reads_free": (None, [VP]),
+    "lcty_bg_diag_sizes": (I32, [VP, U32, U32, P(BgParams), P(U64), P(U64), P(U64)]),
+    "lcty_bg_estimate": (I32, [VP, VP, VP, U32, U32, VP, U32, U32, U32, P(BgParams), P(Bg), P(D), P(BgDiag)]),
+    "lcty_bg_to_json": (I32, [P(Bg), D, U32, C.c_char_p, U64, P(U64)]),
     "lcty_last_error": (C.c_char_p, []),
     "lcty_version": (C.c_char_p, []),
     "lcty_device_count": (I32, []),

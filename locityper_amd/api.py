@@ -868,3 +868,94 @@ def counts_to_posteriors(counts, attempts):
     prob = np.zeros(len(counts), dtype=np.float32); mapq = np.zeros(len(counts), dtype=np.uint8)
     check(lib().lcty_counts_to_posteriors(counts.ctypes.data, len(counts), attempts, prob.ctypes.data, mapq.ctypes.data))
     return prob, mapq
+
+
+# ---- background distributions of a sample (lcty_bg.hip) ------------------------------------------------------------------------
+def bg_params(technology=cdefs.TECH_ILLUMINA, **kw):
+    """lcty_bg_params_default with the technology and any field given by name."""
+    p = cdefs.BgParams()
+    lib().lcty_bg_params_default(C.byref(p))
+    p.technology = technology
+    for k, val in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, val)
+    return p
+
+
+class BgReads:
+    """lcty_bg_reads_load: the records of the background interval [start, end) of `contig` that load_alns keeps, as numpy arrays."""
+
+    def __init__(self, path, contig, start, end, padded_start, padded_len, params):
+        self._h = VP()
+        check(lib().lcty_bg_reads_load(str(path).encode(), contig.encode(), start, end, padded_start, padded_len, C.byref(params), C.byref(self._h)))
+        v = cdefs.BgReadsView()
+        check(lib().lcty_bg_reads_view_get(self._h, C.byref(v)))
+        n = int(v.n_records)
+        self.n_records, self.n_ignored, self.n_wo_cigar = n, int(v.n_ignored), int(v.n_wo_cigar)
+        self.paired, self.read_len = bool(v.paired), float(v.read_len)
+
+        def arr(p, count, dt):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(dt)), (count,)).copy() if count else np.zeros(0, dtype=dt)
+        self.pos, self.end, self.qlen = arr(v.pos, n, C.c_uint32), arr(v.end, n, C.c_uint32), arr(v.qlen, n, C.c_uint32)
+        self.flags, self.mate = arr(v.flags, n, C.c_uint8), arr(v.mate, n, C.c_uint32)
+        self.cigar_off = arr(v.cigar_off, n + 1, C.c_uint64)
+        self.cigar = arr(v.cigar, int(self.cigar_off[-1]), C.c_uint32)
+        self.seq_off = arr(v.seq_off, n + 1, C.c_uint64)
+        nb = int(self.seq_off[-1])
+        self.bases2, self.nmask = arr(v.bases2, nb // 16 + 2, C.c_uint32), arr(v.nmask, nb // 32 + 1, C.c_uint32)
+
+    def close(self):
+        if self._h:
+            lib().lcty_bg_reads_free(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        self.close()
+
+
+def read_bg_bam(path, contig, start, end, padded_start, padded_len, params):
+    return BgReads(path, contig, start, end, padded_start, padded_len, params)
+
+
+def estimate_bg(ctx, reads, padded_seq, padded_start, kmer_counts, k, region_start, region_end, params, with_diag=True):
+    """lcty_bg_estimate -> (Bg, mean read length, diag dict or None). padded_seq: bytes (upper-case ACGT); kmer_counts: u16 of every
+    k-mer of padded_seq."""
+    seq = np.frombuffer(bytes(padded_seq), dtype=np.uint8)
+    cnt = np.ascontiguousarray(kmer_counts, dtype=np.uint16)
+    bg, rl = Bg(), D()
+    dg, keep = None, {}
+    if with_diag:
+        nw, nr, npairs = U64(), U64(), U64()
+        check(lib().lcty_bg_diag_sizes(reads._h, region_start, region_end, C.byref(params), C.byref(nw), C.byref(nr), C.byref(npairs)))
+        nw, nr, npairs = int(nw.value), int(nr.value), int(npairs.value)
+        dg = cdefs.BgDiag()
+        dg.n_windows, dg.n_records, dg.n_pairs = nw, nr, npairs
+        shapes = {"win_start": (nw, np.uint32), "win_gc": (nw, np.float64), "win_kmer_frac": (nw, np.float64), "win_keep": (nw, np.uint8),
+                  "win_depth": (2 * nw, np.uint32), "rec_counts": (5 * nr, np.uint32), "rec_edit": (nr, np.uint32),
+                  "rec_read_len": (nr, np.uint32), "rec_middle": (nr, np.uint32), "rec_window": (nr, np.uint32),
+                  "pair_first": (npairs, np.uint32), "pair_second": (npairs, np.uint32), "pair_insert": (npairs, np.uint32),
+                  "pair_same_strand": (npairs, np.uint8), "hist_size": (npairs, np.uint32), "hist_count": (npairs, np.uint32),
+                  "edit_edit": (nr, np.uint32), "edit_len": (nr, np.uint32), "edit_count": (nr, np.uint64)}
+        for name, (cnt_, dt) in shapes.items():
+            keep[name] = np.zeros(max(cnt_, 1), dtype=dt)
+            setattr(dg, name, keep[name].ctypes.data)
+    check(lib().lcty_bg_estimate(ctx._h, reads._h, seq.ctypes.data, padded_start, len(seq), cnt.ctypes.data, k, region_start, region_end,
+                                 C.byref(params), C.byref(bg), C.byref(rl), C.byref(dg) if dg is not None else None))
+    if dg is None:
+        return bg, float(rl.value), None
+    nw, nr, npairs, nh, ne = int(dg.n_windows), int(dg.n_records), int(dg.n_pairs), int(dg.n_hist), int(dg.n_edit)
+    sizes = {"win": nw, "rec": nr, "pair": npairs, "hist": nh, "edit": ne}
+    out = {}
+    for name, a in keep.items():
+        m = sizes[name.split("_")[0]]
+        m = 2 * m if name == "win_depth" else 5 * m if name == "rec_counts" else m
+        out[name] = a[:m].copy()
+    out["win_depth"] = out["win_depth"].reshape(-1, 2)
+    out["rec_counts"] = out["rec_counts"].reshape(-1, 5)
+    for f in ("orient", "op_totals", "n_stage", "gc_nwin", "loess_mean", "loess_var", "blur_mean", "blur_var", "nb_n", "nb_p"):
+        out[f] = np.array(getattr(dg, f)[:])
+    out["kernel_ms"] = np.array(dg.kernel_ms[:])
+    for f in ("ins_limit", "ins_mean", "ins_var", "ci_low", "ci_high", "unif_coef", "depth_mean", "depth_var", "fit_ms", "total_ms"):
+        out[f] = getattr(dg, f)
+    return bg, float(rl.value), out

@@ -76,6 +76,76 @@ class Bg(C.Structure):
     ]
 
 
+BG_REVERSE, BG_SECOND = 1, 2
+
+
+class BgParams(C.Structure):
+    """preproc's background parameters (src/command/preproc.rs:275-294, src/bg/mod.rs:39-46, src/bg/depth.rs:166-180)."""
+    _fields_ = [
+        ("technology", C.c_int32),
+        ("explicit_technology", C.c_int32),
+        ("min_mapq", C.c_uint32),
+        ("ploidy", C.c_uint32),
+        ("max_clipping", C.c_double),
+        ("insert_pval", C.c_double),
+        ("edit_pval", C.c_double),
+        ("window_size", C.c_uint32),
+        ("boundary_size", C.c_uint32),
+        ("uniq_kmer_perc", C.c_double),
+        ("frac_windows", C.c_double),
+        ("min_tail_obs", C.c_uint32),
+        ("_pad0", C.c_uint32),
+        ("tail_var_mult", C.c_double),
+        ("subsampling_rate", C.c_double),
+    ]
+
+
+class BgReadsView(C.Structure):
+    """The records of the background interval as load_alns keeps them (preproc.rs:988-1028)."""
+    _fields_ = [
+        ("n_records", C.c_uint64),
+        ("n_ignored", C.c_uint64),
+        ("n_wo_cigar", C.c_uint64),
+        ("paired", C.c_int32),
+        ("_pad0", C.c_uint32),
+        ("read_len", C.c_double),
+        ("pos", C.c_void_p),
+        ("end", C.c_void_p),
+        ("qlen", C.c_void_p),
+        ("flags", C.c_void_p),
+        ("mate", C.c_void_p),
+        ("cigar_off", C.c_void_p),
+        ("cigar", C.c_void_p),
+        ("seq_off", C.c_void_p),
+        ("bases2", C.c_void_p),
+        ("nmask", C.c_void_p),
+    ]
+
+
+class BgDiag(C.Structure):
+    """The --debug intermediates of the background estimate (lcty_bg_diag)."""
+    _fields_ = [
+        ("n_windows", C.c_uint64), ("n_records", C.c_uint64), ("n_pairs", C.c_uint64), ("n_hist", C.c_uint64), ("n_edit", C.c_uint64),
+        ("win_start", C.c_void_p), ("win_gc", C.c_void_p), ("win_kmer_frac", C.c_void_p), ("win_keep", C.c_void_p), ("win_depth", C.c_void_p),
+        ("rec_counts", C.c_void_p), ("rec_edit", C.c_void_p), ("rec_read_len", C.c_void_p), ("rec_middle", C.c_void_p), ("rec_window", C.c_void_p),
+        ("pair_first", C.c_void_p), ("pair_second", C.c_void_p), ("pair_insert", C.c_void_p), ("pair_same_strand", C.c_void_p),
+        ("hist_size", C.c_void_p), ("hist_count", C.c_void_p),
+        ("orient", C.c_uint64 * 2),
+        ("ins_limit", C.c_double), ("ins_mean", C.c_double), ("ins_var", C.c_double),
+        ("ci_low", C.c_uint32), ("ci_high", C.c_uint32),
+        ("op_totals", C.c_uint64 * 5),
+        ("edit_edit", C.c_void_p), ("edit_len", C.c_void_p), ("edit_count", C.c_void_p),
+        ("unif_coef", C.c_double),
+        ("n_stage", C.c_uint64 * 6),
+        ("gc_nwin", C.c_uint32 * GC_BINS),
+        ("loess_mean", C.c_double * GC_BINS), ("loess_var", C.c_double * GC_BINS),
+        ("blur_mean", C.c_double * GC_BINS), ("blur_var", C.c_double * GC_BINS),
+        ("nb_n", C.c_double * GC_BINS), ("nb_p", C.c_double * GC_BINS),
+        ("depth_mean", C.c_double), ("depth_var", C.c_double),
+        ("kernel_ms", C.c_double * 4), ("fit_ms", C.c_double), ("total_ms", C.c_double),
+    ]
+
+
 SOLVER_GREEDY, SOLVER_ANNEAL, SOLVER_EXACT = 0, 1, 2
 
 

@@ -9,6 +9,8 @@
 #include <dlfcn.h>
 #include <zlib.h>
 
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -885,6 +887,193 @@ int32_t lcty_distances_parse(const uint8_t* buf, uint64_t len, uint32_t n_allele
                 const uint32_t d = varint();
                 dist[static_cast<size_t>(i) * n + j] = d; dist[static_cast<size_t>(j) * n + i] = d;
             }
+    });
+}
+
+}  // extern "C"
+
+extern "C" {
+
+// ---- background reads: IndexedReader::fetch + load_alns of `preproc -a` (src/command/preproc.rs:988-1028, 1174-1192) --------------
+struct lcty_bg_reads {
+    std::vector<uint32_t> pos, end, qlen, mate; std::vector<uint8_t> flags;
+    std::vector<uint64_t> cigar_off, seq_off; std::vector<uint32_t> cigar, bases2, nmask;
+    lcty_bg_reads_view view{};
+};
+
+void lcty_bg_params_default(lcty_bg_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->technology = LCTY_TECH_ILLUMINA;
+    p->min_mapq = 30; p->max_clipping = 0.02;                          // preproc.rs:275, 294
+    p->insert_pval = 0.001; p->edit_pval = 0.01;                       // bg/mod.rs:39-46
+    p->ploidy = 2; p->window_size = 0; p->boundary_size = 1000;        // bg/depth.rs:166-180
+    p->uniq_kmer_perc = 90.0; p->frac_windows = 0.5; p->min_tail_obs = 100; p->tail_var_mult = 0.02;
+    p->subsampling_rate = 1.0;
+}
+
+int32_t lcty_bg_reads_load(const char* path, const char* contig, uint32_t start, uint32_t end, uint32_t padded_start, uint32_t padded_len,
+                           const lcty_bg_params* params, lcty_bg_reads** out) {
+    return guarded([&] {
+        if (!path || !contig || !params || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (start >= end || padded_start > start || static_cast<uint64_t>(padded_start) + padded_len < end)
+            fail(LCTY_ERR_INVALID_INPUT, "background interval [%u, %u) is not inside the padded sequence [%u, +%u)", start, end, padded_start, padded_len);
+        const std::vector<uint8_t> b = inflate_gzip(slurp(path), path);
+        size_t i = 0;
+        auto need = [&](uint64_t n) { if (n > b.size() - i) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAM", path); };
+        need(12);
+        if (memcmp(&b[0], "BAM\1", 4)) fail(LCTY_ERR_INVALID_DATA, "%s: not a BAM file", path);
+        i = 4;
+        const uint32_t l_text = rd32(&b[i]); i += 4; need(static_cast<uint64_t>(l_text) + 4); i += l_text;
+        const uint32_t n_ref = rd32(&b[i]); i += 4;
+        if (n_ref > (b.size() - i) / 8) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAM header", path);
+        int64_t tid = -1;
+        for (uint32_t r = 0; r < n_ref; r++) {
+            need(4); const uint32_t l_name = rd32(&b[i]); i += 4; need(static_cast<uint64_t>(l_name) + 4);
+            const std::string nm(reinterpret_cast<const char*>(&b[i]), l_name ? l_name - 1 : 0);
+            i += static_cast<size_t>(l_name) + 4;
+            if (tid < 0 && nm == contig) tid = r;
+        }
+        if (tid < 0) fail(LCTY_ERR_INVALID_INPUT, "%s: no reference sequence %s in the BAM header", path, contig);
+        const uint64_t padded_end = static_cast<uint64_t>(padded_start) + padded_len;
+        auto T = std::make_unique<lcty_bg_reads>();
+        T->cigar_off.push_back(0); T->seq_off.push_back(0);
+        std::vector<std::string> names;
+        uint64_t paired_counts[2] = {0, 0}, ignored = 0, wo_cigar = 0;
+        static const char NT16[] = "=ACMGRSVTWYHKDBN";
+        auto consumes_ref = [](uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; };
+        while (i < b.size()) {
+            need(4); const uint32_t block = rd32(&b[i]); i += 4; need(block);
+            if (block < 32) fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BAM record", path);
+            const uint8_t* r = &b[i];
+            i += block;
+            const int32_t ref_id = static_cast<int32_t>(rd32(r)), pos = static_cast<int32_t>(rd32(r + 4));
+            const uint32_t l_read_name = r[8], mapq = r[9], n_cigar = r[12] | (r[13] << 8), flag = r[14] | (r[15] << 8), l_seq = rd32(r + 16);
+            const size_t fixed = 32 + l_read_name + 4ull * n_cigar + (l_seq + 1) / 2 + l_seq;
+            if (fixed > block) fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BAM record", path);
+            if (ref_id != tid || pos < 0) continue;
+            const uint8_t* cg = r + 32 + l_read_name;
+            uint64_t ref_len = 0;
+            for (uint32_t k = 0; k < n_cigar; k++) { const uint32_t w = rd32(cg + 4 * k); if (consumes_ref(w & 15u)) ref_len += w >> 4; }
+            // the records IndexedReader::fetch returns: overlapping [start, end); no reference span counts as one base (bam_endpos)
+            const uint64_t rec_end = static_cast<uint64_t>(pos) + ((flag & 4u) || ref_len == 0 ? 1 : ref_len);
+            if (static_cast<uint64_t>(pos) >= end || rec_end <= start) continue;
+            // load_alns filter (preproc.rs:1006); clipping_rate / raw_clipping (seq/cigar.rs:944-966)
+            bool keep = (flag & 3844u) == 0 && mapq >= params->min_mapq;
+            if (keep) {
+                if (n_cigar == 0) fail(LCTY_ERR_INVALID_DATA, "%s: mapped record without a CIGAR", path);
+                const uint32_t first = rd32(cg), last = rd32(cg + 4ull * (n_cigar - 1));
+                const uint32_t clip = (consumes_ref(first & 15u) ? 0 : first >> 4) + (consumes_ref(last & 15u) ? 0 : last >> 4);
+                const double rate = clip == 0 ? 0.0 : static_cast<double>(clip) / static_cast<double>(l_seq);
+                keep = rate <= params->max_clipping;
+            }
+            if (!keep) { ignored++; continue; }
+            // Cigar::infer_ext_cigar (cigar.rs:434-476): an M run outside the padded sequence -> no extended CIGAR
+            uint64_t rl = 0, ql = 0;
+            bool dropped = false;
+            for (uint32_t k = 0; k < n_cigar; k++) {
+                const uint32_t w = rd32(cg + 4 * k), op = w & 15u, len = w >> 4;
+                if (op == 0 && (pos + rl < padded_start || pos + rl + len >= padded_end)) { dropped = true; break; }
+                if (consumes_ref(op)) rl += len;
+                if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ql += len;
+            }
+            if (dropped) { wo_cigar++; continue; }
+            const std::string qname(reinterpret_cast<const char*>(r + 32), l_read_name ? l_read_name - 1 : 0);
+            for (uint32_t k = 0; k < n_cigar; k++) {
+                const uint32_t op = rd32(cg + 4 * k) & 15u;
+                if (op == 3 || op == 5 || op == 6 || op > 8)
+                    fail(LCTY_ERR_INVALID_DATA, "Read %s: unsupported CIGAR operation %c in a background alignment", qname.c_str(), "MIDNSHP=X???????"[op]);
+            }
+            if (ql != l_seq) fail(LCTY_ERR_INVALID_DATA, "Failed to convert CIGAR for read \"%s\" (query length %llu, SEQ length %u)",
+                                  qname.c_str(), static_cast<unsigned long long>(ql), l_seq);
+            paired_counts[(flag & 1u) ? 1 : 0]++;
+            T->pos.push_back(static_cast<uint32_t>(pos)); T->end.push_back(static_cast<uint32_t>(pos + rl)); T->qlen.push_back(l_seq);
+            T->flags.push_back(static_cast<uint8_t>(((flag & 0x10u) ? LCTY_BG_REVERSE : 0u) | ((flag & 0x80u) ? LCTY_BG_SECOND : 0u)));
+            for (uint32_t k = 0; k < n_cigar; k++) T->cigar.push_back(rd32(cg + 4 * k));
+            T->cigar_off.push_back(T->cigar.size());
+            const uint8_t* seq = cg + 4ull * n_cigar;
+            const uint64_t base_at = T->seq_off.back();
+            const uint64_t next = (base_at + l_seq + 31) / 32 * 32;
+            T->bases2.resize(next / 16 + 2, 0); T->nmask.resize(next / 32 + 1, 0);
+            for (uint32_t k = 0; k < l_seq; k++) {
+                const uint64_t at = base_at + k;
+                uint32_t code = 0; bool other = false;
+                switch (NT16[(seq[k >> 1] >> ((~k & 1) << 2)) & 15]) {
+                    case 'A': code = 0; break; case 'C': code = 1; break; case 'G': code = 2; break; case 'T': code = 3; break; default: other = true;
+                }
+                T->bases2[at >> 4] |= code << (2 * (at & 15));
+                if (other) T->nmask[at >> 5] |= 1u << (at & 31);
+            }
+            T->seq_off.push_back(next);
+            names.push_back(qname);
+        }
+        if (paired_counts[0] > 0 && paired_counts[1] > 0) fail(LCTY_ERR_INVALID_DATA, "BAM file contains both paired and unpaired reads");
+        if (T->pos.empty()) fail(LCTY_ERR_INVALID_DATA, "BAM file contains no reads in the target region");
+        const bool paired = paired_counts[1] > 0;
+        if (paired && params->technology != LCTY_TECH_ILLUMINA) fail(LCTY_ERR_INVALID_INPUT, "Paired end reads are not supported by this technology");
+        const size_t n = T->pos.size();
+        T->bases2.resize(std::max<size_t>(T->bases2.size(), 2), 0); T->nmask.resize(std::max<size_t>(T->nmask.size(), 1), 0);
+        T->mate.assign(n, LCTY_NONE_U32);
+        if (paired) {                                       // group_mates (bg/insertsz.rs:25-37): both ends inside the loaded set
+            std::unordered_map<std::string, std::array<uint32_t, 2>> by_name;
+            by_name.reserve(n);
+            for (size_t a = 0; a < n; a++) {
+                const int e = (T->flags[a] & LCTY_BG_SECOND) ? 1 : 0;
+                auto& slot = by_name.try_emplace(names[a], std::array<uint32_t, 2>{LCTY_NONE_U32, LCTY_NONE_U32}).first->second;
+                if (slot[e] != LCTY_NONE_U32) fail(LCTY_ERR_INVALID_DATA, "Read %s has several %s mates", names[a].c_str(), e ? "second" : "first");
+                slot[e] = static_cast<uint32_t>(a);
+            }
+            for (const auto& kv : by_name)
+                if (kv.second[0] != LCTY_NONE_U32 && kv.second[1] != LCTY_NONE_U32) { T->mate[kv.second[0]] = kv.second[1]; T->mate[kv.second[1]] = kv.second[0]; }
+        }
+        double sum = 0.0;                                   // read_len_from_alns (preproc.rs:1031-1037)
+        const size_t m = std::min<size_t>(n, 10000);
+        for (size_t a = 0; a < m; a++) sum += static_cast<double>(T->qlen[a]);
+        lcty_bg_reads_view& v = T->view;
+        v.n_records = n; v.n_ignored = ignored; v.n_wo_cigar = wo_cigar; v.paired = paired ? 1 : 0;
+        v.read_len = sum / static_cast<double>(m);
+        v.pos = T->pos.data(); v.end = T->end.data(); v.qlen = T->qlen.data(); v.flags = T->flags.data(); v.mate = T->mate.data();
+        v.cigar_off = T->cigar_off.data(); v.cigar = T->cigar.data(); v.seq_off = T->seq_off.data();
+        v.bases2 = T->bases2.data(); v.nmask = T->nmask.data();
+        *out = T.release();
+    });
+}
+
+int32_t lcty_bg_reads_view_get(const lcty_bg_reads* reads, lcty_bg_reads_view* view) {
+    return guarded([&] {
+        if (!reads || !view) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        *view = reads->view;
+    });
+}
+
+void lcty_bg_reads_free(lcty_bg_reads* reads) { delete reads; }
+
+// BgDistr::save (bg/mod.rs:147-158): seq_info (349-357), insert_distr (insertsz.rs:184-193, {} single-end), error_profile
+// (err_prof.rs:308-319), bg_depth (depth.rs:387-398)
+int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, char* out, uint64_t cap, uint64_t* needed) {
+    return guarded([&] {
+        if (!bg || !needed) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        static const char* const techs[4] = {"illumina", "hifi", "pacbio", "ont"};
+        if (bg->technology < 0 || bg->technology > 3) fail(LCTY_ERR_INVALID_INPUT, "unknown technology %d", bg->technology);
+        std::string s = "{\"seq_info\":{\"read_len\":" + json_num(read_len) + ",\"technology\":\"" + techs[bg->technology]
+                      + "\",\"total_reads\":null,\"file_size\":null},\"insert_distr\":{";
+        if (bg->is_paired) s += "\"n\":" + json_num(bg->ins_n) + ",\"p\":" + json_num(bg->ins_p);
+        s += "},\"error_profile\":{";
+        static const char* const ops[5] = {"matches", "mismatches", "insertions", "deletions", "clipping"};
+        for (int k = 0; k < 5; k++) s += std::string("\"") + ops[k] + "\":" + json_num(bg->op_lnprobs[k]) + ",";
+        s += "\"alpha\":" + json_num(bg->edit_alpha) + ",\"beta\":" + json_num(bg->edit_beta) + "},\"bg_depth\":{\"ploidy\":"
+           + std::to_string(ploidy) + ",\"window\":" + std::to_string(bg->window) + ",\"neighb\":" + std::to_string(bg->neighb);
+        for (int which = 0; which < 2; which++) {
+            s += which ? ",\"p\":[" : ",\"n\":[";
+            for (int g = 0; g < LCTY_GC_BINS; g++) s += (g ? "," : "") + json_num(which ? bg->depth_p[g] : bg->depth_n[g]);
+            s += "]";
+        }
+        s += "}}";
+        *needed = s.size() + 1;
+        if (out) {
+            if (cap < s.size() + 1) fail(LCTY_ERR_INVALID_INPUT, "output buffer of %llu bytes, %zu needed", static_cast<unsigned long long>(cap), s.size() + 1);
+            memcpy(out, s.c_str(), s.size() + 1);
+        }
     });
 }
 

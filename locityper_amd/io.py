@@ -66,6 +66,15 @@ def bg_from_json(text):
     return bg, float(rl.value)
 
 
+def bg_to_json(bg, read_len, ploidy=2):
+    """BgDistr::save as text (lcty_bg_to_json): the content of PREPROC/distr.gz."""
+    need = U64()
+    check(lib().lcty_bg_to_json(C.byref(bg), float(read_len), int(ploidy), None, 0, C.byref(need)))
+    buf = C.create_string_buffer(int(need.value))
+    check(lib().lcty_bg_to_json(C.byref(bg), float(read_len), int(ploidy), buf, need.value, C.byref(need)))
+    return buf.value.decode()
+
+
 def res_to_json(call, genotypes, names, lik_mean, lik_var, distances=None, true_edit=False, weighted_dist=float("nan")):
     """Genotyping::to_json as text. genotypes[n_out][ploidy], lik_mean / lik_var[n_out] (natural log), in call.ixs order."""
     gt = np.ascontiguousarray(genotypes, dtype=np.uint16)
