@@ -496,5 +496,17 @@ void solve(const Model& m, const double* lut, uint32_t ld, Result& out) {
     out.nodes = nodes; out.out_of_nodes = out_of_nodes; out.n_free = n_free;
 }
 
+void set_limits(Model& m, uint32_t node_limit, double init_prob) {
+    m.node_limit = node_limit ? node_limit : 20ull * 1000 * 1000;
+    m.rel_gap = init_prob > 0.0 && init_prob < 1.0 ? init_prob : 0.0;
+}
+
+std::string node_limit_message(const Model& m, const Result& r) {
+    char buf[512];
+    snprintf(buf, sizeof(buf), "Exact solver: no proof of optimality within %llu nodes (%u non-trivial reads, %u of them free after fixing the dominated ones); "
+             "Model finished with non-optimal status NodeLimit", static_cast<unsigned long long>(m.node_limit), m.n, r.n_free);
+    return buf;
+}
+
 }  // namespace exact
 }  // namespace lcty

@@ -48,5 +48,10 @@ uint64_t depth_needed(const Model& m);
 // lut = the depth table [GC bins][ld] (WindowDistr::ln_prob = weight * lut[gc][depth], distr_cache.rs:34-39)
 void solve(const Model& m, const double* lut, uint32_t ld, Result& out);
 
+// the limits of the search from the solver settings (lcty_solver): node_limit 0 = 20 M nodes; init_prob in (0, 1) = the relative gap, else a proof
+void set_limits(Model& m, uint32_t node_limit, double init_prob);
+// what a search that ran out of nodes fails with (LCTY_ERR_SOLVER; the reference's Error::Solver, highs.rs:113-116)
+std::string node_limit_message(const Model& m, const Result& r);
+
 }  // namespace exact
 }  // namespace lcty

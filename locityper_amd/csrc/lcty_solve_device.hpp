@@ -183,6 +183,28 @@ struct InitPlan {
     size_t lds = 0;
 };
 
+// The record list of a chain over n_reads reads: reads per part (a multiple of 64, at least 64) and the chain's stride of records
+inline void set_rec_list(SolveView& V, uint64_t n_reads) {
+    V.seg_reads = static_cast<uint32_t>(((n_reads + INIT_SEGS - 1) / INIT_SEGS + 63) / 64 * 64);
+    if (V.seg_reads == 0) V.seg_reads = 64;
+    V.rstride = static_cast<uint64_t>(INIT_SEGS) * V.seg_reads;
+}
+// LDS of a one-chain initialisation (solve_init_kernel, given_init_kernel): the depth histogram, 256 partial sums, the part counters
+inline size_t init_chain_lds(uint32_t wstride) { return ((static_cast<size_t>(wstride) * 4 + 15) & ~static_cast<size_t>(15)) + 256 * 8 + 64; }
+
+// A solver kernel with `lds` bytes of dynamic LDS (past 48 KB the kernel has to be allowed them first), timed as `timer` (< 0: not timed)
+template <typename... P, typename... A>
+void launch_lds(lcty_ctx* ctx, int timer, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    if (lds > 48 * 1024)
+        LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    auto go = [&] { hipLaunchKernelGGL(kernel, grid, block, lds, s, args...); };
+    if (timer < 0) go();
+    else ctx->timed(timer, go, s);
+    LCTY_HIP(hipGetLastError());
+}
+
+void check_solver(const lcty_solver* solver);                              // the settings of a solver (LCTY_ERR_INVALID_INPUT / LCTY_ERR_UNSUPPORTED)
+
 // ---- launchers of lcty_solve_kernels.hip (the only way the host side starts a solver kernel) ----
 void ensure_solver_tables(lcty_reads* reads);                              // location table + compact "unmapped" column of a scored batch
 void ensure_depth_table(lcty_locus* loc, uint64_t want);                   // extended depth table of the locus, at least `want` wide

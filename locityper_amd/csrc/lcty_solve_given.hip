@@ -145,7 +145,9 @@ uint64_t xoshiro_next(uint64_t* s) {                            // xoshiro256++ 
     return result;
 }
 
-void check_solver(const lcty_solver* solver) {
+}  // namespace
+
+void lcty::check_solver(const lcty_solver* solver) {
     if (solver->kind != LCTY_SOLVER_GREEDY && solver->kind != LCTY_SOLVER_ANNEAL && solver->kind != LCTY_SOLVER_EXACT)
         fail(LCTY_ERR_INVALID_INPUT, "unknown solver kind");
     if (solver->kind == LCTY_SOLVER_ANNEAL && !(solver->init_prob > 0.0 && solver->init_prob <= 1.0))
@@ -154,6 +156,8 @@ void check_solver(const lcty_solver* solver) {
     if (solver->kind == LCTY_SOLVER_GREEDY && solver->sample_size == 0) fail(LCTY_ERR_INVALID_INPUT, "Sample size must be positive");
     if (solver->kind == LCTY_SOLVER_GREEDY && solver->sample_size > 64) fail(LCTY_ERR_UNSUPPORTED, "greedy sample size above 64");
 }
+
+namespace {
 
 // what every location that names a window adds up to: no assignment can make the window deeper (a pair in one window counts twice)
 uint64_t deepest_window(const lcty_gt_alns_view* g, std::vector<uint32_t>& reach) {
@@ -233,9 +237,7 @@ void solve_given(lcty_ctx* ctx, lcty_locus* loc, const lcty_depth_tables* T, con
     V.depth_contrib = g->depth_contrib; V.aln_contrib = g->aln_contrib;
     V.n_wk = V.n_wc = 0;                                          // weights as given: no tables
     V.n_good = static_cast<uint32_t>(R);
-    V.seg_reads = static_cast<uint32_t>(((R + INIT_SEGS - 1) / INIT_SEGS + 63) / 64 * 64);
-    if (V.seg_reads == 0) V.seg_reads = 64;
-    V.rstride = static_cast<uint64_t>(INIT_SEGS) * V.seg_reads;
+    set_rec_list(V, R);
     V.ploidy = g->n_contigs ? g->n_contigs : 1; V.attempts = 1; V.solver = *solver; V.priors = nullptr;
     V.wstride = (W + 3) & ~3u;
     if (!solver_lds_fits(V.wstride)) fail(LCTY_ERR_UNSUPPORTED, "%u windows per genotype: too many for the device solver", W);
@@ -274,11 +276,7 @@ void solve_given(lcty_ctx* ctx, lcty_locus* loc, const lcty_depth_tables* T, con
     S.gc.upload(g->window_gc, W, s); S.weight.upload(g->window_weight, W, s);
     const bool random_start = solver->kind == LCTY_SOLVER_ANNEAL || (solver->kind == LCTY_SOLVER_GREEDY && !solver->best_start);
     const GivenDev G{S.read_ixs.p, S.lp.p, S.win.p, S.gc.p, S.weight.p, static_cast<uint32_t>(R), W, seed, random_start ? 1u : 0u};
-    const size_t lds_init = ((static_cast<size_t>(V.wstride) * 4 + 15) & ~static_cast<size_t>(15)) + 256 * 8 + 64;
-    if (lds_init > 48 * 1024)
-        LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(given_init_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_init)));
-    hipLaunchKernelGGL(given_init_kernel, dim3(1), dim3(256), lds_init, s, V, G);
-    LCTY_HIP(hipGetLastError());
+    launch_lds(ctx, -1, given_init_kernel, dim3(1), dim3(256), init_chain_lds(V.wstride), s, V, G);
 
     double parts[4] = {0, 0, 0, 0}, lik = 0.0;
     if (solver->kind == LCTY_SOLVER_EXACT && nnt) {
@@ -305,8 +303,7 @@ void solve_given(lcty_ctx* ctx, lcty_locus* loc, const lcty_depth_tables* T, con
         if (g->n_contigs) m.allele_first_w.assign(g->wshifts, g->wshifts + g->n_contigs + 1);
         else { m.allele_first_w.assign(1, 2u); m.allele_first_w.push_back(W); }
         m.aln_contrib = g->aln_contrib; m.depth_contrib = g->depth_contrib;
-        m.node_limit = solver->node_limit ? solver->node_limit : 20ull * 1000 * 1000;
-        m.rel_gap = solver->init_prob > 0.0 && solver->init_prob < 1.0 ? solver->init_prob : 0.0;
+        exact::set_limits(m, solver->node_limit, solver->init_prob);
         m.gc_bins = n_rows;
         std::vector<double> lut(static_cast<size_t>(n_rows) * S.lut_depth);
         S.lut.download(lut.data(), lut.size(), s);
@@ -314,9 +311,7 @@ void solve_given(lcty_ctx* ctx, lcty_locus* loc, const lcty_depth_tables* T, con
         // (no window with a distribution gets deeper than `deepest` < the table's width: the search indexes the table for those only)
         exact::Result res;
         exact::solve(m, lut.data(), S.lut_depth, res);
-        if (res.out_of_nodes)
-            fail(LCTY_ERR_SOLVER, "Exact solver: no proof of optimality within %llu nodes (%u non-trivial reads, %u of them free after fixing the dominated ones); Model finished with non-optimal status NodeLimit",
-                 static_cast<unsigned long long>(m.node_limit), m.n, res.n_free);
+        if (res.out_of_nodes) fail(LCTY_ERR_SOLVER, "%s", exact::node_limit_message(m, res).c_str());
         memset(read_assgn, 0, sizeof(uint16_t) * R);
         for (uint32_t i = 0; i < m.n; i++) read_assgn[nt_read[i]] = res.assign[i];
         parts[0] = res.aln_lik; parts[1] = res.depth_lik; lik = res.value;

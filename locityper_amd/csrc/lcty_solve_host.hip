@@ -92,13 +92,7 @@ struct StageRunner {
         if (!reads->scored) fail(LCTY_ERR_INVALID_INPUT, "lcty_score_reads has not been called on this batch");
         if (ploidy == 0 || ploidy > MAXP) fail(LCTY_ERR_UNSUPPORTED, "the device solver handles ploidy 1..%u", MAXP);
         if (attempts == 0) fail(LCTY_ERR_INVALID_INPUT, "At least one attempt is required for each stage");
-        if (solver->kind != LCTY_SOLVER_GREEDY && solver->kind != LCTY_SOLVER_ANNEAL && solver->kind != LCTY_SOLVER_EXACT)
-            fail(LCTY_ERR_INVALID_INPUT, "unknown solver kind");
-        if (solver->kind == LCTY_SOLVER_ANNEAL && !(solver->init_prob > 0.0 && solver->init_prob <= 1.0))
-            fail(LCTY_ERR_INVALID_INPUT, "Initial probability (%g) must be within (0, 1]", solver->init_prob);
-        if (solver->kind == LCTY_SOLVER_ANNEAL && solver->anneal_steps == 0) fail(LCTY_ERR_INVALID_INPUT, "Number of annealing steps must be positive");
-        if (solver->kind == LCTY_SOLVER_GREEDY && solver->sample_size == 0) fail(LCTY_ERR_INVALID_INPUT, "Sample size must be positive");
-        if (solver->kind == LCTY_SOLVER_GREEDY && solver->sample_size > 64) fail(LCTY_ERR_UNSUPPORTED, "greedy sample size above 64");
+        check_solver(solver);
         ctx = reads->ctx; loc = reads->locus; gathered_rows = gathered;
         ctx->activate();
         stream = lane ? ctx->side_stream() : ctx->stream;
@@ -133,9 +127,7 @@ struct StageRunner {
         V.n_wk = tables ? static_cast<uint32_t>(loc->d_wk.n) : 0u; V.n_wc = tables ? static_cast<uint32_t>(loc->d_wc.n) : 0u;
         V.lut = loc->d_lut_ext.p; V.lut_depth = loc->lut_ext_depth; V.lut_shift = static_cast<uint32_t>(__builtin_ctz(loc->lut_ext_depth)); V.depth_nb = loc->d_depth_nb.p; V.n_alt = loc->prm.n_alt_cn;
         V.n_good = static_cast<uint32_t>(n_good); V.ngp = ngp;
-        V.seg_reads = static_cast<uint32_t>(((n_good + INIT_SEGS - 1) / INIT_SEGS + 63) / 64 * 64);      // the parts of a chain's record list
-        if (V.seg_reads == 0) V.seg_reads = 64;
-        V.rstride = static_cast<uint64_t>(INIT_SEGS) * V.seg_reads;
+        set_rec_list(V, n_good);                                            // the parts of a chain's record list
         V.table = reinterpret_cast<const LocCell*>(reads->d_loc_table.p); V.table_ext = reads->d_loc_ext.p; V.table_unm = reads->d_loc_unm.p;
         V.pa = reads->d_pa.p; V.row_of = nullptr;
         if (gathered) {
@@ -144,7 +136,7 @@ struct StageRunner {
         }
         V.ploidy = ploidy; V.attempts = attempts; V.solver = *solver;
         V.wstride = (2 + ploidy * loc->max_n_windows + 3) & ~3u;
-        lds_init = ((static_cast<size_t>(V.wstride) * 4 + 15) & ~static_cast<size_t>(15)) + 256 * 8 + 64;
+        lds_init = init_chain_lds(V.wstride);
         if (!solver_lds_fits(V.wstride))
             fail(LCTY_ERR_UNSUPPORTED, "%u windows per genotype: too many for the device solver", V.wstride);
 
@@ -367,8 +359,7 @@ struct StageRunner {
                 for (uint32_t q = 0; q < ploidy; q++)
                     m.allele_first_w.push_back(m.allele_first_w.back() + loc->n_windows[gids[static_cast<size_t>(c / attempts) * ploidy + q]]);
                 m.aln_contrib = V.aln_contrib; m.depth_contrib = V.depth_contrib;
-                m.node_limit = V.solver.node_limit ? V.solver.node_limit : 20ull * 1000 * 1000;
-                m.rel_gap = V.solver.init_prob > 0.0 && V.solver.init_prob < 1.0 ? V.solver.init_prob : 0.0;
+                exact::set_limits(m, V.solver.node_limit, V.solver.init_prob);
                 m.chain = c; m.trace = trace; m.gc_bins = LCTY_GC_BINS;
                 if (c == 0) m.dump_path = ctx->exact_dump_path;
                 need = std::max(need, exact::depth_needed(m));
@@ -409,9 +400,7 @@ struct StageRunner {
             if (failed) std::rethrow_exception(failed);
             for (size_t k = 0; k < gn; k++) {
                 const Held& h = held[k];
-                if (h.res.out_of_nodes)
-                    fail(LCTY_ERR_SOLVER, "Exact solver: no proof of optimality within %llu nodes (%u non-trivial reads, %u of them free after fixing the dominated ones); Model finished with non-optimal status NodeLimit",
-                         static_cast<unsigned long long>(h.model.node_limit), h.model.n, h.res.n_free);
+                if (h.res.out_of_nodes) fail(LCTY_ERR_SOLVER, "%s", exact::node_limit_message(h.model, h.res).c_str());
             }
             // the assignments back into the records (of every attempt that shares the model: same reads at the same places, only the
             // runs of further locations are laid out per chain, so only the `cur` words travel); the likelihood as ReadAssignment::likelihood sums it

@@ -821,20 +821,72 @@ __device__ __forceinline__ double pair_term(const PairGather& g, int i, uint32_t
 __device__ __forceinline__ double lut_at(const double* lut, uint32_t index) {
     return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(lut) + (index << 3));
 }
-// window state of one chain: depth (25 bit) | GC bin << 25 in LDS, weights in the chain's row of c_ww (L2)
+// Where a chain's window state lives (the layout parameter of Chain): a window's word (and half-word) in LDS, decoded into depth and GC
+// bin, and its weight.
+// Gathered: depth (25 bit) | GC bin << 25 in a word, the weight from a row of doubles — LDS (annealing) or the chain's row of c_ww (L2).
 constexpr uint32_t DEPTH_MASK = 0x1FFFFFFu;
+struct WinGathered {
+    static constexpr bool WEIGHTS_LAST = false;     // the weight is gathered next to the table entries of its window
+    uint32_t* wd;               // LDS: the chain's windows
+    const double* ww;           // window weights
+    struct Word { uint32_t word; };
+    __device__ __forceinline__ Word at(uint32_t w) const { return Word{wd[w]}; }
+    __device__ __forceinline__ uint32_t depth(Word x) const { return x.word & DEPTH_MASK; }
+    __device__ __forceinline__ uint32_t gc(Word x) const { return x.word >> 25; }
+    __device__ __forceinline__ double weight(Word x, uint32_t w) const { return ww[w]; }
+};
+// LDS tables (greedy loop, loci without explicit weights): a window is 6 bytes — depth (23 bit) | index into wk << 23 in a word, GC bin
+// | index into wc << 7 in a half-word — and its weight the product of two LDS table entries, which is how window_weight_kernel made it.
+// Every 8-byte weight gather moved a 128-byte line out of the L2; at 5 000 chains those lines were a quarter of the loop's time.
+constexpr uint32_t LW_DEPTH_BITS = 23, LW_DEPTH_MASK = (1u << LW_DEPTH_BITS) - 1u;      // nine bits for a table index
+struct WinTables {
+    static constexpr bool WEIGHTS_LAST = true;      // the products after the table gathers
+    uint32_t* wd;               // LDS: depth | wk index << 23
+    const uint16_t* wh;         // LDS: GC bin | wc index << 7
+    const double* wk; const double* wc;     // LDS
+    struct Word { uint32_t word, half; };
+    __device__ __forceinline__ Word at(uint32_t w) const { return Word{wd[w], wh[w]}; }
+    __device__ __forceinline__ uint32_t depth(Word x) const { return x.word & LW_DEPTH_MASK; }
+    __device__ __forceinline__ uint32_t gc(Word x) const { return x.half & 0x7Fu; }
+    __device__ __forceinline__ double weight(Word x, uint32_t w) const { return wk[x.word >> LW_DEPTH_BITS] * wc[x.half >> 7]; }
+};
+
+// window state of one chain
+template <typename LAYOUT>
 struct Chain {
     const SolveView* V;
-    uint32_t* wd;               // LDS: the chain's windows
-    const double* ww;           // window weights: LDS (annealing) or the chain's row of c_ww
+    LAYOUT L;
+    using Word = typename LAYOUT::Word;
     // WindowDistr::ln_prob (distr_cache.rs:34-39) through the depth table
-    __device__ __forceinline__ double wlp(uint32_t w, uint32_t g, uint32_t d) const {
-        const double weight = ww[w];
+    __device__ __forceinline__ double wlp_at(uint32_t w) const {
+        const Word x = L.at(w);
+        const double weight = L.weight(x, w);
+        const uint32_t d = L.depth(x);
         if (weight == 0.0) return 0.0;                                      // WindowDistr::TRIVIAL
         if (d >= V->lut_depth) { atomicMax(V->overflow, 1u); return 0.0; }  // every chain of the batch is repeated
-        return weight * lut_at(V->lut, g * V->lut_depth + d);
+        return weight * lut_at(V->lut, L.gc(x) * V->lut_depth + d);
     }
-    __device__ __forceinline__ double wlp_at(uint32_t w) const { return wlp(w, wd[w] >> 25, wd[w] & DEPTH_MASK); }
+    // the gathers of N windows whose depths change by c[i]: table entries at the old and the new depth, window weights
+    template <int N>
+    __device__ __forceinline__ void gather(const uint32_t (&w)[N], const int32_t* c, uint32_t* dmax, double* weight, double* vnew, double* vold) const {
+        Word x[N];
+#pragma unroll
+        for (int i = 0; i < N; i++) x[i] = L.at(w[i]);
+        const uint32_t last = V->lut_depth - 1;
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            const uint32_t d_old = L.depth(x[i]), row = L.gc(x[i]) << V->lut_shift;
+            const uint32_t d_new = static_cast<uint32_t>(static_cast<int32_t>(d_old) + c[i]);
+            if constexpr (!LAYOUT::WEIGHTS_LAST) weight[i] = L.weight(x[i], w[i]);
+            vnew[i] = lut_at(V->lut, row + min(d_new, last));
+            vold[i] = lut_at(V->lut, row + min(d_old, last));
+            dmax[i] = max(d_new, d_old);
+        }
+        if constexpr (LAYOUT::WEIGHTS_LAST) {
+#pragma unroll
+            for (int i = 0; i < N; i++) weight[i] = L.weight(x[i], w[i]);
+        }
+    }
     // depth_lik_diff (assgn.rs:259-284) = sum of atomic_depth_lik_diff (244-254) over the four windows, in two halves: `request`
     // reads the windows' depths (LDS) and ISSUES the twelve gathers (table entry at the old and the new depth, window weight);
     // `finish` uses them. Between the two a caller can issue further loads: the wait for these twelve then leaves those in flight.
@@ -848,20 +900,7 @@ struct Chain {
         g.c[1] = e21 ? 0 : -1 + e32 + e42;
         g.c[2] = (e31 | e32) ? 0 : 1 + e43;
         g.c[3] = (e41 | e42 | e43) ? 0 : 1;
-        const uint32_t w[4] = {w1, w2, w3, w4};
-        uint32_t word[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) word[i] = wd[w[i]];
-        const uint32_t last = V->lut_depth - 1;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t d_old = word[i] & DEPTH_MASK, row = (word[i] >> 25) << V->lut_shift;
-            const uint32_t d_new = static_cast<uint32_t>(static_cast<int32_t>(d_old) + g.c[i]);
-            g.weight[i] = ww[w[i]];
-            g.vnew[i] = lut_at(V->lut, row + min(d_new, last));
-            g.vold[i] = lut_at(V->lut, row + min(d_old, last));
-            g.dmax[i] = max(d_new, d_old);
-        }
+        gather<4>({w1, w2, w3, w4}, g.c, g.dmax, g.weight, g.vnew, g.vold);
     }
     __device__ __forceinline__ double finish(const DepthGather& g) const {
         uint32_t deepest = 0;
@@ -888,103 +927,7 @@ struct Chain {
     __device__ __forceinline__ void request_pair(uint32_t wa, uint32_t wb, int32_t dir, PairGather& g) const {
         const int32_t same = wb == wa;
         g.c[0] = dir * (1 + same); g.c[1] = same ? 0 : dir;
-        const uint32_t w[2] = {wa, wb};
-        uint32_t word[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) word[i] = wd[w[i]];
-        const uint32_t last = V->lut_depth - 1;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const uint32_t d_old = word[i] & DEPTH_MASK, row = (word[i] >> 25) << V->lut_shift;
-            const uint32_t d_new = static_cast<uint32_t>(static_cast<int32_t>(d_old) + g.c[i]);
-            g.weight[i] = ww[w[i]];
-            g.vnew[i] = lut_at(V->lut, row + min(d_new, last));
-            g.vold[i] = lut_at(V->lut, row + min(d_old, last));
-            g.dmax[i] = max(d_new, d_old);
-        }
-    }
-};
-
-// The same with the window weights in LDS (greedy loop, loci without explicit weights): a window is 6 bytes — depth (23 bit) |
-// index into wk << 23 in a word, GC bin | index into wc << 7 in a half-word — and its weight the product of two LDS table
-// entries, which is how window_weight_kernel made it. Every 8-byte weight gather moved a 128-byte line out of the L2;
-// at 5 000 chains those lines were a quarter of the loop's time.
-constexpr uint32_t LW_DEPTH_BITS = 23, LW_DEPTH_MASK = (1u << LW_DEPTH_BITS) - 1u;      // nine bits for a table index
-struct ChainLW {
-    const SolveView* V;
-    uint32_t* wd;               // LDS: depth | wk index << 23
-    const uint16_t* wh;         // LDS: GC bin | wc index << 7
-    const double* wk; const double* wc;     // LDS
-    using DepthGather = Chain::DepthGather;
-    __device__ __forceinline__ double weight_of(uint32_t word, uint32_t half) const { return wk[word >> LW_DEPTH_BITS] * wc[half >> 7]; }
-    __device__ __forceinline__ double wlp_at(uint32_t w) const {
-        const uint32_t word = wd[w], half = wh[w];
-        const double weight = weight_of(word, half);
-        const uint32_t d = word & LW_DEPTH_MASK;
-        if (weight == 0.0) return 0.0;
-        if (d >= V->lut_depth) { atomicMax(V->overflow, 1u); return 0.0; }
-        return weight * lut_at(V->lut, (half & 0x7Fu) * V->lut_depth + d);
-    }
-    __device__ __forceinline__ void request(uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, DepthGather& g) const {
-        const int32_t e21 = w2 == w1, e31 = w3 == w1, e41 = w4 == w1;
-        const int32_t e32 = w3 == w2, e42 = w4 == w2, e43 = w4 == w3;
-        g.c[0] = -1 - e21 + e31 + e41;
-        g.c[1] = e21 ? 0 : -1 + e32 + e42;
-        g.c[2] = (e31 | e32) ? 0 : 1 + e43;
-        g.c[3] = (e41 | e42 | e43) ? 0 : 1;
-        const uint32_t w[4] = {w1, w2, w3, w4};
-        uint32_t word[4], half[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) { word[i] = wd[w[i]]; half[i] = wh[w[i]]; }
-        const uint32_t last = V->lut_depth - 1;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t d_old = word[i] & LW_DEPTH_MASK, row = (half[i] & 0x7Fu) << V->lut_shift;
-            const uint32_t d_new = static_cast<uint32_t>(static_cast<int32_t>(d_old) + g.c[i]);
-            g.vnew[i] = lut_at(V->lut, row + min(d_new, last));
-            g.vold[i] = lut_at(V->lut, row + min(d_old, last));
-            g.dmax[i] = max(d_new, d_old);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) g.weight[i] = weight_of(word[i], half[i]);
-    }
-    __device__ __forceinline__ double finish(const DepthGather& g) const {
-        uint32_t deepest = 0;
-        double sum = 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const bool live = g.c[i] != 0 && g.weight[i] != 0.0;
-            deepest = max(deepest, live ? g.dmax[i] : 0u);
-            const double term = live ? g.weight[i] * g.vnew[i] - g.weight[i] * g.vold[i] : 0.0;
-            sum = i == 0 ? term : sum + term;
-        }
-        if (deepest > V->lut_depth - 1) atomicMax(V->overflow, 1u);
-        return sum;
-    }
-    __device__ __forceinline__ double depth_lik_diff(uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) const {
-        DepthGather g;
-        request(w1, w2, w3, w4, g);
-        return finish(g);
-    }
-    // see Chain::request_pair
-    __device__ __forceinline__ void request_pair(uint32_t wa, uint32_t wb, int32_t dir, PairGather& g) const {
-        const int32_t same = wb == wa;
-        g.c[0] = dir * (1 + same); g.c[1] = same ? 0 : dir;
-        const uint32_t w[2] = {wa, wb};
-        uint32_t word[2], half[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) { word[i] = wd[w[i]]; half[i] = wh[w[i]]; }
-        const uint32_t last = V->lut_depth - 1;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const uint32_t d_old = word[i] & LW_DEPTH_MASK, row = (half[i] & 0x7Fu) << V->lut_shift;
-            const uint32_t d_new = static_cast<uint32_t>(static_cast<int32_t>(d_old) + g.c[i]);
-            g.vnew[i] = lut_at(V->lut, row + min(d_new, last));
-            g.vold[i] = lut_at(V->lut, row + min(d_old, last));
-            g.dmax[i] = max(d_new, d_old);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; i++) g.weight[i] = weight_of(word[i], half[i]);
+        gather<2>({wa, wb}, g.c, g.dmax, g.weight, g.vnew, g.vold);
     }
 };
 
@@ -1109,7 +1052,7 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ uint32_t flagged;
     constexpr uint32_t CPW = 64 / LPC, WAVES = LW ? 2u : 1u, ROWS = CPW * WAVES;
-    using ChainT = typename std::conditional<LW, ChainLW, Chain>::type;
+    using ChainT = Chain<typename std::conditional<LW, WinTables, WinGathered>::type>;
     // a batch whose initialisation raised a flag (a chain's run of further locations was too short, ...) is repeated by the host:
     // its records are incomplete and must not be followed
     if (threadIdx.x == 0) flagged = __hip_atomic_load(V.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1155,11 +1098,11 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
         }
         for (uint32_t i = threadIdx.x; i < V.n_wk; i += 64 * WAVES) lwk[i] = V.wk[i];
         for (uint32_t i = threadIdx.x; i < V.n_wc; i += 64 * WAVES) lwc[i] = V.wc[i];
-        C = ChainLW{&V, wd, wh, lwk, lwc};
+        C = ChainT{&V, {wd, wh, lwk, lwc}};
         __syncthreads();                                                         // the tables; from here on the wavefronts run apart
     } else {
         for (uint32_t w = jj; w < total_w && jj < LPC; w += LPC) wd[w] = gd[w] | (static_cast<uint32_t>(ggc[w]) << 25);
-        C = Chain{&V, wd, V.c_ww + static_cast<uint64_t>(chain) * W};
+        C = ChainT{&V, {wd, V.c_ww + static_cast<uint64_t>(chain) * W}};
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1491,7 +1434,7 @@ struct AnnealRing {
 template <int MODE>
 __global__ __launch_bounds__(128, 4) void anneal_loop_kernel(const SolveView V) {
     constexpr bool WWL = MODE == 1, LW = MODE == 2;
-    using ChainT = typename std::conditional<LW, ChainLW, Chain>::type;
+    using ChainT = Chain<typename std::conditional<LW, WinTables, WinGathered>::type>;
     extern __shared__ __align__(32) uint8_t smem[];
     __shared__ uint32_t flagged;
     if (threadIdx.x == 0) flagged = __hip_atomic_load(V.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1586,8 +1529,8 @@ __global__ __launch_bounds__(128, 4) void anneal_loop_kernel(const SolveView V) 
         return;
     }
     ChainT C;
-    if constexpr (LW) C = ChainLW{&V, wd, wh, lww, lww + V.n_wk};
-    else C = Chain{&V, wd, WWL ? lww : gww};
+    if constexpr (LW) C = ChainT{&V, {wd, wh, lww, lww + V.n_wk}};
+    else C = ChainT{&V, {wd, WWL ? lww : gww}};
     // depth_lik = sum over windows (recalc_likelihood, assgn.rs:347-350)
     double depth_lik = 0.0;
     for (uint32_t w = lane; w < total_w; w += 64) depth_lik += C.wlp_at(w);
@@ -2046,12 +1989,8 @@ __global__ void pause_kernel(uint32_t rounds) {
 
 template <uint32_t P>
 void launch_init_p(lcty_ctx* ctx, const SolveView& V, uint32_t nch, size_t lds_init, hipStream_t s) {
-    if (lds_init > 48 * 1024)
-        LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve_init_kernel<P>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds_init)));
-    ctx->timed(V.solver.kind == LCTY_SOLVER_ANNEAL ? LCTY_K_SOLVE_INIT_ANNEAL : LCTY_K_SOLVE_INIT,
-               [&] { hipLaunchKernelGGL(solve_init_kernel<P>, dim3(nch), dim3(256), lds_init, s, V); }, s);
-    LCTY_HIP(hipGetLastError());
+    launch_lds(ctx, V.solver.kind == LCTY_SOLVER_ANNEAL ? LCTY_K_SOLVE_INIT_ANNEAL : LCTY_K_SOLVE_INIT, solve_init_kernel<P>, dim3(nch), dim3(256),
+               lds_init, s, V);
 }
 
 // LDS of a greedy workgroup: the rows' windows (greedy_lds_windows) and four words per row for the parts of its record list
@@ -2061,14 +2000,7 @@ inline size_t greedy_lds(uint32_t lpc, const SolveView& V, bool lw) {
 template <uint32_t LPC, bool LW, uint32_t FORM = 0>
 void launch_greedy_form(lcty_ctx* ctx, const SolveView& V, uint32_t nch, hipStream_t s) {
     constexpr uint32_t ROWS = (64 / LPC) * (LW ? 2 : 1);
-    const size_t lds = greedy_lds(LPC, V, LW);
-    if (lds > 48 * 1024)
-        LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(greedy_loop_kernel<LPC, LW, FORM>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds)));
-    ctx->timed(LCTY_K_SOLVE, [&] {
-        hipLaunchKernelGGL((greedy_loop_kernel<LPC, LW, FORM>), dim3((nch + ROWS - 1) / ROWS), dim3(LW ? 128 : 64), lds, s, V, nch);
-    }, s);
-    LCTY_HIP(hipGetLastError());
+    launch_lds(ctx, LCTY_K_SOLVE, greedy_loop_kernel<LPC, LW, FORM>, dim3((nch + ROWS - 1) / ROWS), dim3(LW ? 128 : 64), greedy_lds(LPC, V, LW), s, V, nch);
 }
 template <uint32_t LPC, bool LW>
 void launch_greedy(lcty_ctx* ctx, const SolveView& V, uint32_t nch, hipStream_t s) {
@@ -2090,11 +2022,7 @@ void launch_anneal_as(lcty_ctx* ctx, const SolveView& V, uint32_t nch, hipStream
     const size_t words = (static_cast<size_t>(V.wstride) * 4 + 31) & ~static_cast<size_t>(31);
     const size_t lds = (MODE == 1 ? static_cast<size_t>(V.wstride) * 8 : MODE == 2 ? static_cast<size_t>(V.n_wk + V.n_wc) * 8 + ((static_cast<size_t>(V.wstride) * 2 + 31) & ~static_cast<size_t>(31)) : 0) +
                        words + sizeof(AnnealRing) + 64;
-    if (lds > 48 * 1024)
-        LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(anneal_loop_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     static_cast<int>(lds)));
-    ctx->timed(LCTY_K_ANNEAL, [&] { hipLaunchKernelGGL(anneal_loop_kernel<MODE>, dim3(nch), dim3(128), lds, s, V); }, s);
-    LCTY_HIP(hipGetLastError());
+    launch_lds(ctx, LCTY_K_ANNEAL, anneal_loop_kernel<MODE>, dim3(nch), dim3(128), lds, s, V);
 }
 void launch_anneal(lcty_ctx* ctx, const SolveView& V, uint32_t nch, hipStream_t s) {
     // lcty_ctx_set_knob "anneal_lds_weights": 0 gathered, 1 in LDS as they are, 2 table indices + tables in LDS (the kernel's comment);
@@ -2294,16 +2222,9 @@ void launch_init(lcty_ctx* ctx, const SolveView& V, uint32_t nch, size_t lds_ini
         ws.init_plan.ensure_slack(gb + cb + lb);
         LCTY_HIP(hipMemcpyAsync(ws.init_plan.p, plan.groups.data(), gb, hipMemcpyHostToDevice, s));
         LCTY_HIP(hipMemcpyAsync(ws.init_plan.p + gb, plan.chains.data(), cb, hipMemcpyHostToDevice, s));
-        if (plan.lds > 48 * 1024)
-            LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(solve_init_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         static_cast<int>(plan.lds)));
-        const InitGroup* d_groups = reinterpret_cast<const InitGroup*>(ws.init_plan.p);
-        const InitChainP* d_chains = reinterpret_cast<const InitChainP*>(ws.init_plan.p + gb);
-        ctx->timed(V.solver.kind == LCTY_SOLVER_ANNEAL ? LCTY_K_SOLVE_INIT_ANNEAL : LCTY_K_SOLVE_INIT, [&] {
-            hipLaunchKernelGGL(solve_init_tile_kernel, dim3(static_cast<uint32_t>(plan.groups.size())), dim3(256), plan.lds, s, V, d_groups, d_chains,
-                               reinterpret_cast<unsigned long long*>(ws.init_plan.p + gb + cb), plan.T, plan.R);
-        }, s);
-        LCTY_HIP(hipGetLastError());
+        launch_lds(ctx, V.solver.kind == LCTY_SOLVER_ANNEAL ? LCTY_K_SOLVE_INIT_ANNEAL : LCTY_K_SOLVE_INIT, solve_init_tile_kernel,
+                   dim3(static_cast<uint32_t>(plan.groups.size())), dim3(256), plan.lds, s, V, reinterpret_cast<const InitGroup*>(ws.init_plan.p),
+                   reinterpret_cast<const InitChainP*>(ws.init_plan.p + gb), reinterpret_cast<unsigned long long*>(ws.init_plan.p + gb + cb), plan.T, plan.R);
         return;
     }
     switch (V.ploidy) {
