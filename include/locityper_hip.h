@@ -240,7 +240,8 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       the error path of the exchanges);   "prefilter_gram_cols"   room for that many level columns per read (default 6; too few: the
  *       f64 kernel takes the batch);   "queue_early_head"   0: lcty_solve_queue makes the head of a locus after the chains of the locus before (default 1:
  *       beside them);   "prefilter_gram_levels"   levels of a row the contraction takes (<= 16; rows with more go
- *       through the f64 kernel).
+ *       through the f64 kernel);   "db_chunk_cols"   columns of the bit matrix per pass of lcty_db_divergences (default: what fits 1/8 of
+ *       the free device memory, 256 MB at most).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -943,6 +944,100 @@ int32_t lcty_bg_estimate(lcty_ctx* ctx, const lcty_bg_reads* reads, const uint8_
                          const uint16_t* kmer_counts, uint32_t k, uint32_t region_start, uint32_t region_end, const lcty_bg_params* params,
                          lcty_bg* out, double* read_len, lcty_bg_diag* diag /* may be NULL */);
 int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, char* out, uint64_t cap, uint64_t* needed);
+
+/* ---- locus database build (locityper target: the files of DB/loci/<locus>/) -----------------------------------------------------
+ * process_alleles (src/command/add.rs:585-652) and what it calls, on buffers: the haplotype sequences of one locus, the reference
+ * sequence of the locus and the k-mer counts `jellyfish query` returned for all of them (the caller runs Jellyfish, exactly as the
+ * caller runs the mapper for aln.bam). Out of scope: pangenome-VCF reconstruction and locus expansion (panvcf.rs, add.rs:370-518),
+ * ref.bed, lock and `success` files, haplotype-to-haplotype alignment (`locityper align`, haplotypes.paf.gz), prune / augment.
+ * Integer work throughout: every output equals the reference's bit for bit (the f64 divergence is one IEEE division of two u32).
+ *
+ * lcty_db_minimizers: kmers::minimizers::<u64, _, NON_CANONICAL> + sort_unstable per sequence (src/seq/kmers.rs:265-331,
+ *   src/seq/minim_div.rs:53-61): the sorted HASHES (fast_hash, kmers.rs:93-103) of the minimizers, one per minimizer position, so
+ *   a list is a multiset. 1 <= k <= 32: the reference asserts k <= 31 in debug builds only; at 32 the mask is the whole word (the
+ *   form the comment at kmers.rs:49 gives). 1 <= w <= 63: add.rs:101 lets 64 through, but the circular array of kmers.rs:205-236
+ *   holds 64 hashes and the loop asserts w < 64 (kmers.rs:270), so 64 is LCTY_ERR_INVALID_INPUT. Sequences of ACGT take a parallel
+ *   kernel (stats->n_fast); a sequence with any other byte — N, lower case: the reference matches the four capitals only — takes a
+ *   one-lane walk that restates the loop with its first_kmer / first_window rules (stats->n_walk). min_off[n_seqs + 1];
+ *   *hashes is released with lcty_io_free.
+ * lcty_db_divergences: minimizer_divergences over all pairs (minim_div.rs:45-72; jaccard_distance, 16-40) in the order of
+ *   TriangleMatrix::indices (src/ext/trimat.rs:15-17: rows i, then j > i): uniq[n (n - 1) / 2] the non-shared minimizers (what
+ *   distances.bin holds), diverg (may be NULL) uniq / union as f64, NaN where both lists are empty, as the reference's 0 / 0.
+ *   *check (may be NULL) is check_divergencies (add.rs:521-543): pairs with diverg >= 0.2, the highest value and its pair.
+ *   Fewer than two sequences: LCTY_ERR_INVALID_DATA (add.rs:656-658). lcty_ctx_set_knob "db_chunk_cols" = columns of the bit
+ *   matrix per pass (default: 1/8 of the free device memory, 256 MB at most); "host_threads" sorts lists longer than 8 192.
+ * lcty_db_off_target: KmerCounts::off_target_counts (src/seq/counts.rs:180-230) with the preparation of add.rs:626-644: runs of
+ *   N of ref_seq (n_runs, seq/mod.rs:57-74) count as A and the counts of the k-mers over them as 0. counts / cnt_off: the counts
+ *   of the sequences' k-mers (cnt_off[a + 1] - cnt_off[a] == len(a) + 1 - k, and n_ref_counts == ref_len + 1 - k, else
+ *   LCTY_ERR_INVALID_DATA as KmerCounts::validate, 159-172); counter_bytes (1..8) gives max_value = min(65535, 2^(8 bytes) - 1)
+ *   (KmerCounts::load, 133). 2 <= k <= 63: 64-bit keys on the device up to 31, the 128-bit table on the host from 32.
+ *   out[cnt_off[n_seqs]]. *warn_bits (may be NULL): LCTY_DB_WARN_*.
+ * lcty_db_discard_identical: discard_identical (add.rs:546-582): the first of equal sequences is kept, order kept. names: n_seqs
+ *   0-terminated names one after the other. kept[n_seqs] (the first *n_kept filled), owner[n_seqs] = input index of the kept
+ *   haplotype an input equals (itself when kept); text = discarded_haplotypes.txt as lines 567-578 write it, *needed its length
+ *   (0: nothing was discarded and the reference writes no file). kept, owner, text may be NULL.
+ * lcty_kmer_counts_write: KmerCounts::save (counts.rs:108-124): u8 k, u8 counter bytes, varint contigs, per contig varint length
+ *   + its counts as varints. A count above the counter's maximum: LCTY_ERR_INVALID_DATA. `kmers.bin.br` = the off-target block
+ *   and the block of the counts as given, back to back (add.rs:648-650), through lcty_io_write_br.
+ * lcty_distances_write: write_divergences (minim_div.rs:113-127): u8 k, u8 w, varint n, the triangle as varints. Not compressed.
+ * lcty_fasta_write_text: write_multiline_fasta (src/seq/fastx.rs:27-43) per sequence: ">name", lines of 120 bases;
+ *   `haplotypes.fa.gz` = this text through lcty_io_write_gz.
+ *   The three writers are called twice: out = NULL sizes (*needed), then cap >= *needed.
+ * lcty_db_build_locus: the sequence of process_alleles: discard_identical, FASTA text, [--calc-div: divergences -> distances.bin],
+ *   off-target counts -> the two blocks of kmers.bin. counts / cnt_off[n_seqs + 2]: one block of n_seqs + 1 contigs, the reference
+ *   sequence LAST (the order of add.rs:633-636). The reference counts k-mers after discard_identical; here the table covers every
+ *   input haplotype: the blocks of discarded haplotypes are dropped. only_seqs (add.rs:606-609): counts, ref_seq may be NULL.
+ *   The payloads come back uncompressed (the containers are the writers' business); release with lcty_db_files_free. */
+#define LCTY_DB_WARN_NEGATIVES_SEEN 1u   /* have_negatives (counts.rs:203): a k-mer occurs more often in ref_seq than its count says */
+#define LCTY_DB_WARN_REF_MISMATCH   2u   /* ... and ref_seq has no N runs: the error the reference logs at counts.rs:208-211 */
+typedef struct lcty_db_params {
+    uint32_t div_k, div_w;        /* 15, 15 (add.rs:77-78) */
+    int32_t  calc_div;            /* 0 (add.rs:76): 1 = --calc-div, distances.bin is made */
+    int32_t  only_seqs;           /* 0: 1 = --only-seqs, the FASTA text alone */
+} lcty_db_params;
+typedef struct lcty_db_check {
+    uint64_t n_high;              /* pairs with diverg >= 0.2 */
+    double   highest;             /* 0 when n_high == 0 */
+    uint32_t highest_i, highest_j;
+} lcty_db_check;
+typedef struct lcty_db_stats {
+    uint64_t n_minimizers, n_columns, n_chunks;    /* list entries; distinct (hash, copy) columns; passes over the bit matrix */
+    uint64_t n_fast, n_walk, n_sorted_host;        /* sequences per minimizer path; lists sorted on the host */
+    uint64_t bytes_h2d, bytes_d2h, bitmat_bytes;
+    /* wall time per stage with the stream drained at its end: minimizers (upload included), LDS sort, host sort, column index,
+     * bit matrix + Gram tiles (download included), off-target (transfers included), host work, whole call */
+    double   minim_ms, sort_ms, sort_host_ms, index_ms, tiles_ms, offt_ms, host_ms, total_ms;
+} lcty_db_stats;
+typedef struct lcty_db_files {
+    uint8_t* fasta;     uint64_t fasta_len;        /* text of haplotypes.fa */
+    uint8_t* kmers;     uint64_t kmers_len;        /* kmers.bin: off-target block, then the counts as given (empty with only_seqs) */
+    uint8_t* distances; uint64_t distances_len;    /* distances.bin (empty without calc_div) */
+    uint8_t* discarded; uint64_t discarded_len;    /* discarded_haplotypes.txt (empty: no file) */
+    uint32_t* kept;     uint32_t n_kept;           /* input indices of the haplotypes written */
+    uint32_t warn_bits;
+    lcty_db_check check;
+    lcty_db_stats stats;
+} lcty_db_files;
+
+void    lcty_db_params_default(lcty_db_params* params);
+int32_t lcty_db_minimizers(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t k, uint32_t w,
+                           uint64_t* min_off, uint64_t** hashes, lcty_db_stats* stats);
+int32_t lcty_db_divergences(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t k, uint32_t w,
+                            uint32_t* uniq, double* diverg, lcty_db_check* check, lcty_db_stats* stats);
+int32_t lcty_db_off_target(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, const uint16_t* counts,
+                           const uint64_t* cnt_off, uint32_t k, uint32_t counter_bytes, const uint8_t* ref_seq, uint64_t ref_len,
+                           const uint16_t* ref_counts, uint64_t n_ref_counts, uint16_t* out, uint32_t* warn_bits, lcty_db_stats* stats);
+int32_t lcty_db_discard_identical(uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, const char* names, uint32_t* kept,
+                                  uint32_t* n_kept, uint32_t* owner, char* text, uint64_t cap, uint64_t* needed);
+int32_t lcty_kmer_counts_write(uint32_t k, uint32_t counter_bytes, uint32_t n_contigs, const uint64_t* cnt_off, const uint16_t* counts,
+                               uint8_t* out, uint64_t cap, uint64_t* needed);
+int32_t lcty_distances_write(uint32_t k, uint32_t w, uint32_t n_alleles, const uint32_t* uniq, uint8_t* out, uint64_t cap, uint64_t* needed);
+int32_t lcty_fasta_write_text(uint32_t n_seqs, const char* names, const uint8_t* seqs, const uint64_t* seq_off, char* out, uint64_t cap,
+                              uint64_t* needed);
+int32_t lcty_db_build_locus(lcty_ctx* ctx, uint32_t n_seqs, const char* names, const uint8_t* seqs, const uint64_t* seq_off,
+                            const uint8_t* ref_seq, uint64_t ref_len, const uint16_t* counts, const uint64_t* cnt_off, uint32_t k,
+                            uint32_t counter_bytes, const lcty_db_params* params, lcty_db_files* out);
+void    lcty_db_files_free(lcty_db_files* files);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import Bg, BgParams, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
+from .cdefs import Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -31,6 +31,16 @@ SIGNATURES = {
     "lcty_bg_diag_sizes": (I32, [VP, U32, U32, P(BgParams), P(U64), P(U64), P(U64)]),
     "lcty_bg_estimate": (I32, [VP, VP, VP, U32, U32, VP, U32, U32, U32, P(BgParams), P(Bg), P(D), P(BgDiag)]),
     "lcty_bg_to_json": (I32, [P(Bg), D, U32, C.c_char_p, U64, P(U64)]),
+    "lcty_db_params_default": (None, [P(DbParams)]),
+    "lcty_db_minimizers": (I32, [VP, U32, VP, VP, U32, U32, VP, P(VP), P(DbStats)]),
+    "lcty_db_divergences": (I32, [VP, U32, VP, VP, U32, U32, VP, VP, P(DbCheck), P(DbStats)]),
+    "lcty_db_off_target": (I32, [VP, U32, VP, VP, VP, VP, U32, U32, VP, U64, VP, U64, VP, P(U32), P(DbStats)]),
+    "lcty_db_discard_identical": (I32, [U32, VP, VP, C.c_char_p, VP, P(U32), VP, VP, U64, P(U64)]),
+    "lcty_kmer_counts_write": (I32, [U32, U32, U32, VP, VP, VP, U64, P(U64)]),
+    "lcty_distances_write": (I32, [U32, U32, U32, VP, VP, U64, P(U64)]),
+    "lcty_fasta_write_text": (I32, [U32, C.c_char_p, VP, VP, VP, U64, P(U64)]),
+    "lcty_db_build_locus": (I32, [VP, U32, C.c_char_p, VP, VP, VP, U64, VP, VP, U32, U32, P(DbParams), P(DbFiles)]),
+    "lcty_db_files_free": (None, [P(DbFiles)]),
     "lcty_last_error": (C.c_char_p, []),
     "lcty_version": (C.c_char_p, []),
     "lcty_device_count": (I32, []),

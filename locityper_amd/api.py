@@ -959,3 +959,106 @@ def estimate_bg(ctx, reads, padded_seq, padded_start, kmer_counts, k, region_sta
     for f in ("ins_limit", "ins_mean", "ins_var", "ci_low", "ci_high", "unif_coef", "depth_mean", "depth_var", "fit_ms", "total_ms"):
         out[f] = getattr(dg, f)
     return bg, float(rl.value), out
+
+
+# ---- locus database build (locityper target; lcty_db.hip) ------------------------------------------------------------------------
+def db_params(**kw):
+    """lcty_db_params_default (div_k = div_w = 15, no divergences, counts wanted) with overrides."""
+    p = cdefs.DbParams()
+    lib().lcty_db_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _seq_arrays(seqs, seq_off):
+    return np.ascontiguousarray(seqs, dtype=np.uint8), np.ascontiguousarray(seq_off, dtype=np.uint64)
+
+
+def db_minimizers(ctx, seqs, seq_off, k=15, w=15):
+    """lcty_db_minimizers: (min_off[n + 1], sorted minimizer hashes of every sequence concatenated, stats dict)."""
+    sq, off = _seq_arrays(seqs, seq_off)
+    n = len(off) - 1
+    moff = np.zeros(n + 1, dtype=np.uint64)
+    h, st = VP(), cdefs.DbStats()
+    check(lib().lcty_db_minimizers(ctx._h, n, sq.ctypes.data, off.ctypes.data, k, w, moff.ctypes.data, C.byref(h), C.byref(st)))
+    try:
+        total = int(moff[-1])
+        hashes = np.frombuffer(C.string_at(h, 8 * total), dtype=np.uint64).copy() if total else np.zeros(0, dtype=np.uint64)
+    finally:
+        lib().lcty_io_free(h)
+    return moff, hashes, st.as_dict()
+
+
+def db_divergences(ctx, seqs, seq_off, k=15, w=15, with_f64=True):
+    """lcty_db_divergences: (uniq u32 triangle, diverg f64 triangle or None, check dict, stats dict), pairs in the order rows i, then j > i."""
+    sq, off = _seq_arrays(seqs, seq_off)
+    n = len(off) - 1
+    npairs = max(n * (n - 1) // 2, 0)
+    uniq = np.zeros(max(npairs, 1), dtype=np.uint32)
+    div = np.zeros(max(npairs, 1), dtype=np.float64) if with_f64 else None
+    ck, st = cdefs.DbCheck(), cdefs.DbStats()
+    check(lib().lcty_db_divergences(ctx._h, n, sq.ctypes.data, off.ctypes.data, k, w, uniq.ctypes.data, div.ctypes.data if with_f64 else None,
+                                    C.byref(ck), C.byref(st)))
+    chk = {"n_high": int(ck.n_high), "highest": float(ck.highest), "pair": (int(ck.highest_i), int(ck.highest_j))}
+    return uniq[:npairs], (div[:npairs] if with_f64 else None), chk, st.as_dict()
+
+
+def db_off_target(ctx, seqs, seq_off, counts, cnt_off, k, counter_bytes, ref_seq, ref_counts):
+    """lcty_db_off_target: (off-target counts u16 laid out as `counts`, warn bits, stats dict)."""
+    sq, off = _seq_arrays(seqs, seq_off)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint16)
+    coff = np.ascontiguousarray(cnt_off, dtype=np.uint64)
+    ref = np.ascontiguousarray(ref_seq, dtype=np.uint8)
+    rc = np.ascontiguousarray(ref_counts, dtype=np.uint16)
+    out = np.zeros(max(len(cnt), 1), dtype=np.uint16)
+    warn, st = U32(), cdefs.DbStats()
+    check(lib().lcty_db_off_target(ctx._h, len(off) - 1, sq.ctypes.data, off.ctypes.data, cnt.ctypes.data, coff.ctypes.data, k, counter_bytes,
+                                   ref.ctypes.data, len(ref), rc.ctypes.data, len(rc), out.ctypes.data, C.byref(warn), C.byref(st)))
+    return out[:len(cnt)], int(warn.value), st.as_dict()
+
+
+def db_discard_identical(names, seqs, seq_off):
+    """lcty_db_discard_identical: (kept input indices, {kept index: [names folded into it]}, text of discarded_haplotypes.txt — b"" = no file)."""
+    from .io import _names_blob
+    sq, off = _seq_arrays(seqs, seq_off)
+    n = len(off) - 1
+    blob = _names_blob(names)
+    kept = np.zeros(max(n, 1), dtype=np.uint32); owner = np.zeros(max(n, 1), dtype=np.uint32)
+    nk, need = U32(), U64()
+    check(lib().lcty_db_discard_identical(n, sq.ctypes.data, off.ctypes.data, blob, kept.ctypes.data, C.byref(nk), owner.ctypes.data, None, 0, C.byref(need)))
+    text = np.zeros(max(int(need.value), 1), dtype=np.uint8)
+    check(lib().lcty_db_discard_identical(n, sq.ctypes.data, off.ctypes.data, blob, None, C.byref(nk), None, text.ctypes.data, len(text), C.byref(need)))
+    folded = {int(i): [] for i in kept[:nk.value]}
+    for i in range(n):
+        if int(owner[i]) != i:
+            folded[int(owner[i])].append(names[i])
+    return kept[:nk.value].copy(), folded, text[:int(need.value)].tobytes()
+
+
+def db_build_locus(ctx, names, seqs, seq_off, ref_seq=None, counts=None, cnt_off=None, k=25, counter_bytes=2, params=None):
+    """lcty_db_build_locus: process_alleles on buffers. counts / cnt_off: one block of n + 1 contigs, the reference sequence last.
+    Returns a dict: fasta, kmers, distances, discarded (bytes, uncompressed), kept, warn_bits, check, stats."""
+    from .io import _names_blob
+    sq, off = _seq_arrays(seqs, seq_off)
+    p = params if params is not None else db_params()
+    ref = np.ascontiguousarray(ref_seq, dtype=np.uint8) if ref_seq is not None else None
+    cnt = np.ascontiguousarray(counts, dtype=np.uint16) if counts is not None else None
+    coff = np.ascontiguousarray(cnt_off, dtype=np.uint64) if cnt_off is not None else None
+    f = cdefs.DbFiles()
+    check(lib().lcty_db_build_locus(ctx._h, len(off) - 1, _names_blob(names), sq.ctypes.data, off.ctypes.data,
+                                    None if ref is None else ref.ctypes.data, 0 if ref is None else len(ref),
+                                    None if cnt is None else cnt.ctypes.data, None if coff is None else coff.ctypes.data, k, counter_bytes,
+                                    C.byref(p), C.byref(f)))
+    try:
+        return {
+            "fasta": C.string_at(f.fasta, f.fasta_len), "kmers": C.string_at(f.kmers, f.kmers_len),
+            "distances": C.string_at(f.distances, f.distances_len), "discarded": C.string_at(f.discarded, f.discarded_len),
+            "kept": np.frombuffer(C.string_at(f.kept, 4 * f.n_kept), dtype=np.uint32).copy(), "warn_bits": int(f.warn_bits),
+            "check": {"n_high": int(f.check.n_high), "highest": float(f.check.highest), "pair": (int(f.check.highest_i), int(f.check.highest_j))},
+            "stats": f.stats.as_dict(),
+        }
+    finally:
+        lib().lcty_db_files_free(C.byref(f))

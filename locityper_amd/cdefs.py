@@ -100,6 +100,34 @@ class BgParams(C.Structure):
     ]
 
 
+DB_WARN_NEGATIVES_SEEN, DB_WARN_REF_MISMATCH = 1, 2
+
+
+class DbParams(C.Structure):
+    """`locityper target`'s parameters of process_alleles (src/command/add.rs:76-78, 606, 611)."""
+    _fields_ = [("div_k", C.c_uint32), ("div_w", C.c_uint32), ("calc_div", C.c_int32), ("only_seqs", C.c_int32)]
+
+
+class DbCheck(C.Structure):
+    """check_divergencies (add.rs:521-543)."""
+    _fields_ = [("n_high", C.c_uint64), ("highest", C.c_double), ("highest_i", C.c_uint32), ("highest_j", C.c_uint32)]
+
+
+class DbStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_minimizers", "n_columns", "n_chunks", "n_fast", "n_walk", "n_sorted_host", "bytes_h2d",
+                                          "bytes_d2h", "bitmat_bytes")] + \
+               [(n, C.c_double) for n in ("minim_ms", "sort_ms", "sort_host_ms", "index_ms", "tiles_ms", "offt_ms", "host_ms", "total_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DbFiles(C.Structure):
+    _fields_ = [("fasta", C.c_void_p), ("fasta_len", C.c_uint64), ("kmers", C.c_void_p), ("kmers_len", C.c_uint64),
+                ("distances", C.c_void_p), ("distances_len", C.c_uint64), ("discarded", C.c_void_p), ("discarded_len", C.c_uint64),
+                ("kept", C.c_void_p), ("n_kept", C.c_uint32), ("warn_bits", C.c_uint32), ("check", DbCheck), ("stats", DbStats)]
+
+
 class BgReadsView(C.Structure):
     """The records of the background interval as load_alns keeps them (preproc.rs:988-1028)."""
     _fields_ = [

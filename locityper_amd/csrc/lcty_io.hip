@@ -892,6 +892,85 @@ int32_t lcty_distances_parse(const uint8_t* buf, uint64_t len, uint32_t n_allele
 
 }  // extern "C"
 
+// ---- the writers of a locus directory (locityper target): the parsers above read back what these write ------------------------------
+namespace {
+void put_varint(std::vector<uint8_t>& out, uint64_t v) {                        // varint_rs: 7 bits per byte, low first, high bit = more
+    while (v >= 0x80) { out.push_back(static_cast<uint8_t>(v) | 0x80); v >>= 7; }
+    out.push_back(static_cast<uint8_t>(v));
+}
+void hand_out(const std::vector<uint8_t>& bytes, uint8_t* out, uint64_t cap, uint64_t* needed) {
+    *needed = bytes.size();
+    if (!out) return;
+    if (cap < bytes.size()) fail(LCTY_ERR_INVALID_INPUT, "output buffer too small (%llu < %zu)", static_cast<unsigned long long>(cap), bytes.size());
+    if (!bytes.empty()) memcpy(out, bytes.data(), bytes.size());
+}
+}  // namespace
+
+extern "C" {
+
+// KmerCounts::save (seq/counts.rs:108-124)
+int32_t lcty_kmer_counts_write(uint32_t k, uint32_t counter_bytes, uint32_t n_contigs, const uint64_t* cnt_off, const uint16_t* counts, uint8_t* out,
+                               uint64_t cap, uint64_t* needed) {
+    return guarded([&] {
+        if (!cnt_off || !needed || (cnt_off[n_contigs] && !counts)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (k < 1 || k > 255) fail(LCTY_ERR_INVALID_INPUT, "k = %u does not fit the one byte the format gives it", k);
+        if (counter_bytes < 1 || counter_bytes > 8) fail(LCTY_ERR_INVALID_INPUT, "counter length %u: must be 1..8 bytes", counter_bytes);
+        const uint32_t max_value = counter_bytes >= 2 ? 65535u : 255u;
+        std::vector<uint8_t> b;
+        b.reserve(8 + cnt_off[n_contigs] + 5ull * n_contigs);
+        b.push_back(static_cast<uint8_t>(k)); b.push_back(static_cast<uint8_t>(counter_bytes));
+        put_varint(b, n_contigs);
+        for (uint32_t c = 0; c < n_contigs; c++) {
+            if (cnt_off[c + 1] < cnt_off[c] || cnt_off[c + 1] - cnt_off[c] > 0xFFFFFFFFull) fail(LCTY_ERR_INVALID_INPUT, "cnt_off is not ascending at %u", c);
+            put_varint(b, cnt_off[c + 1] - cnt_off[c]);
+            for (uint64_t i = cnt_off[c]; i < cnt_off[c + 1]; i++) {
+                if (counts[i] > max_value)
+                    fail(LCTY_ERR_INVALID_DATA, "count %u of contig %u exceeds the maximum of a %u-byte counter (%u)", counts[i], c, counter_bytes, max_value);
+                put_varint(b, counts[i]);
+            }
+        }
+        hand_out(b, out, cap, needed);
+    });
+}
+
+// write_divergences (seq/minim_div.rs:113-127)
+int32_t lcty_distances_write(uint32_t k, uint32_t w, uint32_t n_alleles, const uint32_t* uniq, uint8_t* out, uint64_t cap, uint64_t* needed) {
+    return guarded([&] {
+        const uint64_t n_pairs = n_alleles ? uint64_t(n_alleles) * (n_alleles - 1) / 2 : 0;
+        if (!needed || (n_pairs && !uniq)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (k > 255 || w > 255) fail(LCTY_ERR_INVALID_INPUT, "k = %u, w = %u: one byte each in the format", k, w);
+        std::vector<uint8_t> b;
+        b.reserve(8 + 2 * n_pairs);
+        b.push_back(static_cast<uint8_t>(k)); b.push_back(static_cast<uint8_t>(w));
+        put_varint(b, n_alleles);
+        for (uint64_t i = 0; i < n_pairs; i++) put_varint(b, uniq[i]);
+        hand_out(b, out, cap, needed);
+    });
+}
+
+// write_multiline_fasta (seq/fastx.rs:27-43) for every sequence
+int32_t lcty_fasta_write_text(uint32_t n_seqs, const char* names, const uint8_t* seqs, const uint64_t* seq_off, char* out, uint64_t cap, uint64_t* needed) {
+    return guarded([&] {
+        if (!needed || !seq_off || (n_seqs && !names) || (seq_off[n_seqs] && !seqs)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        std::vector<uint8_t> b;
+        b.reserve(seq_off[n_seqs] + seq_off[n_seqs] / 120 + 64ull * n_seqs);
+        const char* nm = names;
+        for (uint32_t a = 0; a < n_seqs; a++) {
+            if (seq_off[a + 1] < seq_off[a]) fail(LCTY_ERR_INVALID_INPUT, "seq_off is not ascending at %u", a);
+            const size_t nl = strlen(nm);
+            b.push_back('>'); b.insert(b.end(), nm, nm + nl); b.push_back('\n');
+            nm += nl + 1;
+            for (uint64_t i = seq_off[a]; i < seq_off[a + 1]; i += 120) {
+                const uint64_t e = std::min<uint64_t>(i + 120, seq_off[a + 1]);
+                b.insert(b.end(), seqs + i, seqs + e); b.push_back('\n');
+            }
+        }
+        hand_out(b, reinterpret_cast<uint8_t*>(out), cap, needed);
+    });
+}
+
+}  // extern "C"
+
 extern "C" {
 
 // ---- background reads: IndexedReader::fetch + load_alns of `preproc -a` (src/command/preproc.rs:988-1028, 1174-1192) --------------

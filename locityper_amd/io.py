@@ -40,6 +40,52 @@ def distances_parse(data, n_alleles):
     return int(k.value), int(w.value), dist
 
 
+def _sized(call):
+    need = U64(0)
+    check(call(None, 0, C.byref(need)))
+    buf = np.zeros(max(int(need.value), 1), dtype=np.uint8)
+    check(call(buf.ctypes.data, len(buf), C.byref(need)))
+    return buf[:int(need.value)].tobytes()
+
+
+def _names_blob(names):
+    return b"".join((n.encode() if isinstance(n, str) else bytes(n)) + b"\0" for n in names)
+
+
+def kmer_counts_write(k, counter_bytes, cnt_off, counts):
+    """lcty_kmer_counts_write (KmerCounts::save): one block of `kmers.bin`."""
+    off = np.ascontiguousarray(cnt_off, dtype=np.uint64)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint16)
+    return _sized(lambda o, c, n: lib().lcty_kmer_counts_write(k, counter_bytes, len(off) - 1, off.ctypes.data, cnt.ctypes.data, o, c, n))
+
+
+def distances_write(k, w, n_alleles, uniq):
+    """lcty_distances_write (write_divergences): the bytes of `distances.bin` from the triangle of non-shared minimizers."""
+    u = np.ascontiguousarray(uniq, dtype=np.uint32)
+    if len(u) != n_alleles * (n_alleles - 1) // 2:
+        raise ValueError("uniq must hold n (n - 1) / 2 values")
+    return _sized(lambda o, c, n: lib().lcty_distances_write(k, w, n_alleles, u.ctypes.data, o, c, n))
+
+
+def fasta_text(names, seqs, seq_off):
+    """lcty_fasta_write_text (write_multiline_fasta): the text of `haplotypes.fa` (write_gz makes the .gz)."""
+    sq = np.ascontiguousarray(seqs, dtype=np.uint8)
+    off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    blob = _names_blob(names)
+    return _sized(lambda o, c, n: lib().lcty_fasta_write_text(len(off) - 1, blob, sq.ctypes.data, off.ctypes.data, o, c, n))
+
+
+def fasta_read(path):
+    """lcty_fasta_read: (names, upper-cased sequences concatenated as u8, seq_off[n + 1])."""
+    n, nl, sl = U32(), U64(), U64()
+    check(lib().lcty_fasta_read(str(path).encode(), C.byref(n), None, C.byref(nl), None, C.byref(sl), None))
+    names = np.zeros(max(int(nl.value), 1), dtype=np.uint8)
+    seqs = np.zeros(max(int(sl.value), 1), dtype=np.uint8)
+    off = np.zeros(n.value + 1, dtype=np.uint64)
+    check(lib().lcty_fasta_read(str(path).encode(), C.byref(n), names.ctypes.data, C.byref(nl), seqs.ctypes.data, C.byref(sl), off.ctypes.data))
+    return [x.decode() for x in names[:int(nl.value)].tobytes().split(b"\0")[:n.value]], seqs[:int(sl.value)], off
+
+
 def paf_read(path, names, with_distances=False):
     """lcty_paf_read: haplotypes.paf[.gz|.br|.lz4] -> [(id1 query, id2 target, raw CIGAR words, n_matches, aln_len)] in file order,
     the list Locus.set_hap_alns takes. names: the contig names of the locus in id order."""
