@@ -14,8 +14,9 @@
 // that the largest fills the 35 bits), cut into five 7-bit digit planes; per plane the contraction is
 //     S_p[i][j] = sum_c (digit_p[c] * N[c][i]) * N[c][j]        i8 x i8 -> i32, v_mfma_i32_32x32x32_i8
 // and S = sum_p S_p << 7p is an exact 64-bit integer whatever the order of the columns — run to run reproducible, and within
-// 2^-36 of the largest level difference per column of the f64 sum the reference makes (the tests hold it to 1e-9 relative,
-// as the f64 tile kernel of lcty_prefilter.hip).
+// half a unit of the fixed point per column — 2^-36 to 2^-35 of the largest level difference, by its mantissa — of the exact sum
+// (the tests hold it to that bound against an 80-bit sum, and to 1e-9 relative against the reference's f64 sum, as the f64 tile
+// kernel of lcty_prefilter.hip).
 //
 //   gram_levels_kernel    per block of 128 reads: the levels of every row (a wavefront holds a row in registers), the columns'
 //                         weights, and the 0/1 columns as BITS, allele-major: word [a][c / 32], so that a lane of the
