@@ -241,7 +241,8 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       f64 kernel takes the batch);   "queue_early_head"   0: lcty_solve_queue makes the head of a locus after the chains of the locus before (default 1:
  *       beside them);   "prefilter_gram_levels"   levels of a row the contraction takes (<= 16; rows with more go
  *       through the f64 kernel);   "db_chunk_cols"   columns of the bit matrix per pass of lcty_db_divergences (default: what fits 1/8 of
- *       the free device memory, 256 MB at most).
+ *       the free device memory, 256 MB at most);   "basis_batch_words"   CIGAR words per batch of lcty_basis_windows (default: what fits a
+ *       quarter of the free device memory; an entry with more words travels alone).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -1038,6 +1039,67 @@ int32_t lcty_db_build_locus(lcty_ctx* ctx, uint32_t n_seqs, const char* names, c
                             const uint8_t* ref_seq, uint64_t ref_len, const uint16_t* counts, const uint64_t* cnt_off, uint32_t k,
                             uint32_t counter_bytes, const lcty_db_params* params, lcty_db_files* out);
 void    lcty_db_files_free(lcty_db_files* files);
+
+/* ---- basis haplotypes (locityper augment, the basis step: DB/loci/<locus>/haplotypes-basis[.TAG].fa.gz) ------------------------------
+ * construct_dominant_set -> inner_construct_dominant_set -> Cigar::locally_similar -> find_dominating_set (src/command/augment.rs:258-396,
+ * src/seq/cigar.rs:656-751, src/algo/dom_set.rs) on buffers: the pairwise haplotype alignments as lcty_paf_read returns them (the
+ * arguments of lcty_locus_set_hap_alns) and the haplotype lengths. The ids a basis holds are what lcty_locus_build_map_index takes.
+ * Out of scope: producing the PAF (`locityper align`), prune, lock files and rerun modes of augment.
+ * Integer work: the bit rows equal the reference's bit for bit. Differences, on purpose: a contig not longer than the window has ONE
+ * window (the reference's `l - window`, augment.rs:323, underflows there); the entries are those lcty_paf_read keeps (full length, forward
+ * strand); the reference solves the covering problem with SCIP, so only the SIZE of the optimum can be compared, not which optimum.
+ *
+ * lcty_basis_windows: for every entry (query id1, target id2, id1 != id2, with a CIGAR of M = X I D) and both of its sides — IN_QUERY
+ *   on contig id1, the reference form on contig id2 — the windows [s, s + window), s = t * step, whose edit count is at most
+ *   floor(window * divergence), and the last window at len - window (index ceil((len - window) / step)): bit `other` of row
+ *   (contig, window). A side not longer than the window counts for window 0 iff (aln_len - n_matches) / aln_len <= divergence (1.0 when
+ *   aln_len == 0): update_bitarray, augment.rs:291-312. Every row starts with its own contig's bit. lengths[n_alleles];
+ *   leave_out (may be NULL) [n_alleles]: != 0 = --basis-lo, the contig has no rows, entries that name it are skipped, ids stay those of
+ *   the full set. win_off[n_alleles + 1]: first row of every contig; *rows [win_off[n_alleles]][ceil(n_alleles / 32)] 32-bit words, bit
+ *   i of a row at word i / 32, bit i % 32; released with lcty_io_free. One wavefront per (entry, side); the entries stream through the
+ *   device in batches (a quarter of the free device memory; lcty_ctx_set_knob "basis_batch_words" = CIGAR words per batch).
+ *   A CIGAR with another operation, or one that does not cover its contig's length: LCTY_ERR_INVALID_DATA.
+ * lcty_basis_constraints: the distinct rows (the HashSet of augment.rs:341-344) in a fixed order — by number of bits, then by content —
+ *   and with minimal != 0 only the rows that contain no other row (a presolve of ours: a row that contains another is implied by it).
+ *   *out [*n_out][ceil(n_alleles / 32)], released with lcty_io_free.
+ * lcty_basis_select: find_dominating_set: the fewest haplotypes that hit every row, by a host branch and bound (no device is used).
+ *   ids[n_alleles] (the first *n_ids filled, ascending), *bound = a proven lower bound of the size, *optimal = 1 when *n_ids == *bound.
+ *   node_limit (0 = 2 000 000) reached: the best cover found, *optimal = 0 — the reference, too, only logs a status other than optimal
+ *   and takes the best solution (dom_set.rs:26-30). The same input gives the same ids. A row without a bit: LCTY_ERR_INVALID_INPUT.
+ * lcty_basis_build: the three in one call, the rows staying on the device between the first two.
+ * lcty_basis_tag: construct_basis_tag (augment.rs:259-279): "x" fmt_signif(divergence, 5), "-global" for window == UINT32_MAX, else
+ *   "-w" window ["-s" step when step != 0] as PrettyU32 prints them (1000 -> 1k), "-lo" names joined by commas (leave_out: n_leave_out
+ *   0-terminated names one after the other). 128 characters or more: LCTY_ERR_RUNTIME, as there. */
+typedef struct lcty_basis_params {
+    double   divergence;          /* 0.01 (augment.rs:59) */
+    uint32_t window;              /* 250 (augment.rs:60); UINT32_MAX = global */
+    uint32_t step;                /* 0 = not given: max(window >> 1, 1) (augment.rs:320) */
+    uint32_t minimal;             /* 1: lcty_basis_build reduces the rows to the minimal ones before the search; 0: the distinct rows as they are */
+    uint32_t _pad0;
+    uint64_t node_limit;          /* 2 000 000 nodes of the search */
+} lcty_basis_params;
+typedef struct lcty_basis_stats {
+    uint64_t n_entries, n_walks, n_batches;                /* entries taken; (entry, side) walks; batches they travelled in */
+    uint64_t n_rows_raw, n_rows_unique, n_rows_minimal;    /* rows per stage (minimal == unique where the presolve is off) */
+    uint64_t n_forced, n_nodes;                            /* haplotypes fixed by rows of one bit; nodes of the search */
+    uint64_t bytes_h2d, bytes_d2h;
+    /* wall time per stage with the stream drained at its end (transfers included) */
+    double   windows_ms, dedup_ms, subsume_ms, search_ms, total_ms;
+} lcty_basis_stats;
+
+void    lcty_basis_params_default(lcty_basis_params* params);
+int32_t lcty_basis_windows(lcty_ctx* ctx, uint32_t n_alleles, const uint32_t* lengths, uint64_t n_entries, const uint32_t* id1, const uint32_t* id2,
+                           const uint32_t* n_matches, const uint32_t* aln_len, const uint64_t* cigar_off, const uint32_t* cigar,
+                           const uint8_t* leave_out, const lcty_basis_params* params, uint64_t* win_off, uint32_t** rows, lcty_basis_stats* stats);
+int32_t lcty_basis_constraints(lcty_ctx* ctx, uint32_t n_alleles, uint64_t n_rows, const uint32_t* rows, int32_t minimal, uint64_t* n_out,
+                               uint32_t** out, lcty_basis_stats* stats);
+int32_t lcty_basis_select(uint32_t n_alleles, uint64_t n_rows, const uint32_t* rows, uint64_t node_limit, uint32_t* ids, uint32_t* n_ids,
+                          uint32_t* bound, int32_t* optimal, uint64_t* nodes);
+int32_t lcty_basis_build(lcty_ctx* ctx, uint32_t n_alleles, const uint32_t* lengths, uint64_t n_entries, const uint32_t* id1, const uint32_t* id2,
+                         const uint32_t* n_matches, const uint32_t* aln_len, const uint64_t* cigar_off, const uint32_t* cigar,
+                         const uint8_t* leave_out, const lcty_basis_params* params, uint32_t* ids, uint32_t* n_ids, uint32_t* bound,
+                         int32_t* optimal, lcty_basis_stats* stats);
+int32_t lcty_basis_tag(const lcty_basis_params* params, const char* leave_out, uint32_t n_leave_out, char* out, uint64_t cap);
 
 #ifdef __cplusplus
 }

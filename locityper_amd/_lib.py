@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
+from .cdefs import BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -41,6 +41,12 @@ SIGNATURES = {
     "lcty_fasta_write_text": (I32, [U32, C.c_char_p, VP, VP, VP, U64, P(U64)]),
     "lcty_db_build_locus": (I32, [VP, U32, C.c_char_p, VP, VP, VP, U64, VP, VP, U32, U32, P(DbParams), P(DbFiles)]),
     "lcty_db_files_free": (None, [P(DbFiles)]),
+    "lcty_basis_params_default": (None, [P(BasisParams)]),
+    "lcty_basis_windows": (I32, [VP, U32, VP, U64, VP, VP, VP, VP, VP, VP, VP, P(BasisParams), VP, P(VP), P(BasisStats)]),
+    "lcty_basis_constraints": (I32, [VP, U32, U64, VP, I32, P(U64), P(VP), P(BasisStats)]),
+    "lcty_basis_select": (I32, [U32, U64, VP, U64, VP, P(U32), P(U32), P(I32), P(U64)]),
+    "lcty_basis_build": (I32, [VP, U32, VP, U64, VP, VP, VP, VP, VP, VP, VP, P(BasisParams), VP, P(U32), P(U32), P(I32), P(BasisStats)]),
+    "lcty_basis_tag": (I32, [P(BasisParams), C.c_char_p, U32, C.c_char_p, U64]),
     "lcty_last_error": (C.c_char_p, []),
     "lcty_version": (C.c_char_p, []),
     "lcty_device_count": (I32, []),

@@ -1062,3 +1062,127 @@ def db_build_locus(ctx, names, seqs, seq_off, ref_seq=None, counts=None, cnt_off
         }
     finally:
         lib().lcty_db_files_free(C.byref(f))
+
+
+# ---- basis haplotypes (the basis step of `locityper augment`) ----------------------------------------------------------------------------
+def basis_params(**kw):
+    """lcty_basis_params_default (divergence 0.01, window 250, step 0 = window / 2, minimal rows, 2 M nodes) with overrides."""
+    p = cdefs.BasisParams()
+    lib().lcty_basis_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _basis_entries(entries):
+    """[(id1 query, id2 target, raw CIGAR words, n_matches, aln_len)] (io.paf_read, SynthLocus.hap_alns) -> the arrays of the C ABI"""
+    n = len(entries)
+    id1 = np.array([e[0] for e in entries], dtype=np.uint32)
+    id2 = np.array([e[1] for e in entries], dtype=np.uint32)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(e[2]) for e in entries], out=off[1:])
+    words = np.concatenate([np.asarray(e[2], dtype=np.uint32) for e in entries] + [np.zeros(1, dtype=np.uint32)])
+    nm = np.array([e[3] for e in entries], dtype=np.uint32)
+    ln = np.array([e[4] for e in entries], dtype=np.uint32)
+    return n, id1, id2, nm, ln, off, words
+
+
+def _leave_out_mask(n_alleles, leave_out):
+    if leave_out is None or len(leave_out) == 0:
+        return None
+    m = np.zeros(n_alleles, dtype=np.uint8)
+    m[np.asarray(list(leave_out), dtype=np.int64)] = 1
+    return m
+
+
+def _rows_ints(rows):
+    """[n][words] u32 -> Python ints (bit i = haplotype i)"""
+    return [int.from_bytes(r.astype("<u4").tobytes(), "little") for r in rows]
+
+
+def basis_rows_from_ints(n_alleles, ints):
+    words = (n_alleles + 31) // 32
+    out = np.zeros((len(ints), words), dtype=np.uint32)
+    for i, v in enumerate(ints):
+        out[i] = np.frombuffer(int(v).to_bytes(4 * words, "little"), dtype="<u4")
+    return out
+
+
+def basis_windows(ctx, lengths, entries, params=None, leave_out=None):
+    """lcty_basis_windows: (win_off[n + 1], rows [sum n_windows][ceil(n / 32)] u32, stats dict). leave_out: ids without rows."""
+    p = params if params is not None else basis_params()
+    lens = np.ascontiguousarray(lengths, dtype=np.uint32)
+    n, id1, id2, nm, ln, off, words = _basis_entries(entries)
+    mask = _leave_out_mask(len(lens), leave_out)
+    win_off = np.zeros(len(lens) + 1, dtype=np.uint64)
+    h, st = VP(), cdefs.BasisStats()
+    check(lib().lcty_basis_windows(ctx._h, len(lens), lens.ctypes.data, n, id1.ctypes.data, id2.ctypes.data, nm.ctypes.data, ln.ctypes.data,
+                                   off.ctypes.data, words.ctypes.data, None if mask is None else mask.ctypes.data, C.byref(p),
+                                   win_off.ctypes.data, C.byref(h), C.byref(st)))
+    try:
+        nw = (len(lens) + 31) // 32
+        total = int(win_off[-1]) * nw
+        rows = np.frombuffer(C.string_at(h, 4 * total), dtype=np.uint32).copy().reshape(-1, nw) if total else np.zeros((0, nw), dtype=np.uint32)
+    finally:
+        lib().lcty_io_free(h)
+    return win_off, rows, st.as_dict()
+
+
+def basis_constraints(ctx, n_alleles, rows, minimal=False):
+    """lcty_basis_constraints: (the distinct rows in a fixed order — with minimal only those that contain no other row —, stats dict)."""
+    r = np.ascontiguousarray(rows, dtype=np.uint32)
+    nw = (n_alleles + 31) // 32
+    n_out, h, st = U64(), VP(), cdefs.BasisStats()
+    check(lib().lcty_basis_constraints(ctx._h, n_alleles, r.size // nw, r.ctypes.data, int(bool(minimal)), C.byref(n_out), C.byref(h), C.byref(st)))
+    try:
+        total = int(n_out.value) * nw
+        out = np.frombuffer(C.string_at(h, 4 * total), dtype=np.uint32).copy().reshape(-1, nw) if total else np.zeros((0, nw), dtype=np.uint32)
+    finally:
+        lib().lcty_io_free(h)
+    return out, st.as_dict()
+
+
+def basis_select(n_alleles, rows, node_limit=0):
+    """lcty_basis_select (host only): (ids ascending, proven lower bound, optimal, nodes)."""
+    r = np.ascontiguousarray(rows, dtype=np.uint32)
+    nw = (n_alleles + 31) // 32
+    ids = np.zeros(max(n_alleles, 1), dtype=np.uint32)
+    n_ids, bound, opt, nodes = U32(), U32(), C.c_int32(), U64()
+    check(lib().lcty_basis_select(n_alleles, r.size // nw, r.ctypes.data, node_limit, ids.ctypes.data, C.byref(n_ids), C.byref(bound), C.byref(opt),
+                                  C.byref(nodes)))
+    return ids[:n_ids.value].copy(), int(bound.value), bool(opt.value), int(nodes.value)
+
+
+def basis_build(ctx, lengths, entries, params=None, leave_out=None):
+    """lcty_basis_build: windows -> constraints -> search. (ids ascending, bound, optimal, stats dict)."""
+    p = params if params is not None else basis_params()
+    lens = np.ascontiguousarray(lengths, dtype=np.uint32)
+    n, id1, id2, nm, ln, off, words = _basis_entries(entries)
+    mask = _leave_out_mask(len(lens), leave_out)
+    ids = np.zeros(len(lens), dtype=np.uint32)
+    n_ids, bound, opt, st = U32(), U32(), C.c_int32(), cdefs.BasisStats()
+    check(lib().lcty_basis_build(ctx._h, len(lens), lens.ctypes.data, n, id1.ctypes.data, id2.ctypes.data, nm.ctypes.data, ln.ctypes.data,
+                                 off.ctypes.data, words.ctypes.data, None if mask is None else mask.ctypes.data, C.byref(p), ids.ctypes.data,
+                                 C.byref(n_ids), C.byref(bound), C.byref(opt), C.byref(st)))
+    return ids[:n_ids.value].copy(), int(bound.value), bool(opt.value), st.as_dict()
+
+
+def basis_tag(params=None, leave_out_names=()):
+    """lcty_basis_tag (construct_basis_tag): the TAG of haplotypes-basis.TAG.fa.gz."""
+    from .io import _names_blob
+    p = params if params is not None else basis_params()
+    buf = C.create_string_buffer(160)
+    check(lib().lcty_basis_tag(C.byref(p), _names_blob(leave_out_names) if leave_out_names else None, len(leave_out_names), buf, len(buf)))
+    return buf.value.decode()
+
+
+def basis_fasta(names, seqs, seq_off, ids):
+    """The text of haplotypes-basis.TAG.fa (lcty_fasta_write_text over the chosen haplotypes, in id order; io.write_gz makes the .gz)."""
+    from .io import fasta_text
+    sq, off = _seq_arrays(seqs, seq_off)
+    parts = [sq[int(off[i]):int(off[i + 1])] for i in ids]
+    o = np.zeros(len(parts) + 1, dtype=np.uint64)
+    np.cumsum([len(x) for x in parts], out=o[1:])
+    return fasta_text([names[i] for i in ids], np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8), o)

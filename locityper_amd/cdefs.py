@@ -128,6 +128,21 @@ class DbFiles(C.Structure):
                 ("kept", C.c_void_p), ("n_kept", C.c_uint32), ("warn_bits", C.c_uint32), ("check", DbCheck), ("stats", DbStats)]
 
 
+class BasisParams(C.Structure):
+    """The basis step of `locityper augment` (src/command/augment.rs:59-61); window 2^32 - 1 = global, step 0 = max(window >> 1, 1)."""
+    _fields_ = [("divergence", C.c_double), ("window", C.c_uint32), ("step", C.c_uint32), ("minimal", C.c_uint32), ("_pad0", C.c_uint32),
+                ("node_limit", C.c_uint64)]
+
+
+class BasisStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_entries", "n_walks", "n_batches", "n_rows_raw", "n_rows_unique", "n_rows_minimal", "n_forced",
+                                          "n_nodes", "bytes_h2d", "bytes_d2h")] + \
+               [(n, C.c_double) for n in ("windows_ms", "dedup_ms", "subsume_ms", "search_ms", "total_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class BgReadsView(C.Structure):
     """The records of the background interval as load_alns keeps them (preproc.rs:988-1028)."""
     _fields_ = [
