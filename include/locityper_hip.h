@@ -242,7 +242,11 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       beside them);   "prefilter_gram_levels"   levels of a row the contraction takes (<= 16; rows with more go
  *       through the f64 kernel);   "db_chunk_cols"   columns of the bit matrix per pass of lcty_db_divergences (default: what fits 1/8 of
  *       the free device memory, 256 MB at most);   "basis_batch_words"   CIGAR words per batch of lcty_basis_windows (default: what fits a
- *       quarter of the free device memory; an entry with more words travels alone).
+ *       quarter of the free device memory; an entry with more words travels alone);   "align_batch_pairs"   pairs per batch of
+ *       lcty_align_haplotypes (default: sized from the free device memory);   "align_hash_bits"   bits kept of a backbone window's hash
+ *       (default 64; fewer: collisions, which the comparison of the bases must reject);   "align_dp_cells"   cells of the largest
+ *       stretch the exact aligner takes (default 2^26; a larger stretch is dropped to align_simple and counted in n_dropped — this one
+ *       changes CIGARs, as the limit itself does).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -950,7 +954,7 @@ int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, cha
  * process_alleles (src/command/add.rs:585-652) and what it calls, on buffers: the haplotype sequences of one locus, the reference
  * sequence of the locus and the k-mer counts `jellyfish query` returned for all of them (the caller runs Jellyfish, exactly as the
  * caller runs the mapper for aln.bam). Out of scope: pangenome-VCF reconstruction and locus expansion (panvcf.rs, add.rs:370-518),
- * ref.bed, lock and `success` files, haplotype-to-haplotype alignment (`locityper align`, haplotypes.paf.gz), prune / augment.
+ * ref.bed, lock and `success` files, prune / augment. (haplotypes.paf.gz: lcty_align_haplotypes, further down.)
  * Integer work throughout: every output equals the reference's bit for bit (the f64 divergence is one IEEE division of two u32).
  *
  * lcty_db_minimizers: kmers::minimizers::<u64, _, NON_CANONICAL> + sort_unstable per sequence (src/seq/kmers.rs:265-331,
@@ -1044,7 +1048,7 @@ void    lcty_db_files_free(lcty_db_files* files);
  * construct_dominant_set -> inner_construct_dominant_set -> Cigar::locally_similar -> find_dominating_set (src/command/augment.rs:258-396,
  * src/seq/cigar.rs:656-751, src/algo/dom_set.rs) on buffers: the pairwise haplotype alignments as lcty_paf_read returns them (the
  * arguments of lcty_locus_set_hap_alns) and the haplotype lengths. The ids a basis holds are what lcty_locus_build_map_index takes.
- * Out of scope: producing the PAF (`locityper align`), prune, lock files and rerun modes of augment.
+ * Out of scope: prune, lock files and rerun modes of augment. (The PAF itself: lcty_align_haplotypes, below.)
  * Integer work: the bit rows equal the reference's bit for bit. Differences, on purpose: a contig not longer than the window has ONE
  * window (the reference's `l - window`, augment.rs:323, underflows there); the entries are those lcty_paf_read keeps (full length, forward
  * strand); the reference solves the covering problem with SCIP, so only the SIZE of the optimum can be compared, not which optimum.
@@ -1100,6 +1104,95 @@ int32_t lcty_basis_build(lcty_ctx* ctx, uint32_t n_alleles, const uint32_t* leng
                          const uint8_t* leave_out, const lcty_basis_params* params, uint32_t* ids, uint32_t* n_ids, uint32_t* bound,
                          int32_t* optimal, lcty_basis_stats* stats);
 int32_t lcty_basis_tag(const lcty_basis_params* params, const char* leave_out, uint32_t n_leave_out, char* out, uint64_t cap);
+
+/* ---- pairwise haplotype alignments (locityper align --transitive 0: DB/loci/<locus>/haplotypes.paf.gz) ---------------------------------
+ * The backbone strategy of src/seq/align.rs on buffers. For a requested pair the reference is sequence ref_id (entry1) and the query
+ * sequence query_id (entry2): process_pair, 627-679.
+ *   divergence  um / md = jaccard_distance of the two minimizer lists = lcty_db_divergences (unless skip_div). The pair is aligned iff
+ *               md <= thresh_div, or <= against_div when either sequence carries the `against` flag (646-648); a pair that is not
+ *               still has its PAF line (`0 0 255`). thresh_div == 0 means "never align" (Params::validate, 67-89: the ks are
+ *               cleared); a pair that passes all the same — skip_div, or an `against` pair under against_div — is LCTY_ERR_RUNTIME
+ *               "No alignment found", as align_multik ends there (316).
+ *   stage A     backbone matches (precompute_kmers, get_kmer_matches; 102-120, 202-224): every (pos1, pos2) whose non-canonical k-mers
+ *               are equal, sorted. 5 <= k <= LCTY_ALIGN_MAX_K = 127 = U256::MAX_KMER_SIZE (kmers.rs:43: BITS / 2 - 1). Exact: windows
+ *               are found by a 64-bit hash, and every candidate is compared base by base before it counts. More than 2^24 matches of
+ *               one pair and k: LCTY_ERR_UNSUPPORTED (nothing is truncated).
+ *   stage B     LCSk++ (bio::alignment::sparse::lcskpp, called at 255; Pavetic, Zuzic, Sikic 2014): over the matches m = (i, j),
+ *               dp(m) = max of k; dp(m') + 1 where m' = (i - 1, j - 1) is a match; k + max dp(m'') over the matches with i'' + k <= i
+ *               and j'' + k <= j. The chain score is max dp, the path the predecessors back from the argmax. The SCORE is the
+ *               reference's; which optimal path comes back is fixed here: the lowest match index wherever values tie.
+ *   stage C     the walk of align_from_backbone (262-286) with smart_align (wfa.rs:280-321; threshold max_gap): an empty side is a
+ *               plain I or D, a side longer than max_gap takes align_simple, equal lengths <= 3 are compared base by base, anything
+ *               else takes the exact gap-affine aligner — accuracy level 9 puts no step limit on WFA. Here that is the Gotoh recurrence
+ *               of alignment recovery with its tie rule. A stretch beyond its largest scratch level (16 383 bases a side or 2^26 cells;
+ *               knob align_dp_cells) takes align_simple, as the reference does when WFA drops an alignment (wfa.rs:234-237), and is
+ *               counted in stats.n_dropped: never an error.
+ *   per pair    align_multik (294-318): the best score over backbone_ks, the first k on a tie; n_matches, aln_len, NM, AS as 652-664.
+ * Differences, on purpose: (1) no transitive acceleration: every aligned pair has its backbone alignment; (2) a window with a byte
+ * outside ACGT is not a backbone k-mer (the reference makes all such windows equal to each other, UNDEF); (3) in the gap fill any byte
+ * outside ACGT is N and N equals N; (4) a sequence shorter than k has no k-mers and the pair is one stretch (the reference indexes an
+ * empty buffer, 109); (5) which optimal chain and which co-optimal alignment of a stretch: the fixed tie rules above; (6) accuracy
+ * levels below 9 and penalties other than 4 / 6 / 1 are not offered (LCTY_ERR_UNSUPPORTED); (7) equal neighbouring CIGAR operations
+ * are merged (the reference's push_unchecked can write `5=25=`): the same alignment and score.
+ *
+ * lcty_align_haplotypes: pairs are taken and returned in input order; they stream through the device in batches sized from the free
+ *   memory (knob align_batch_pairs), the k-mer index is built once per call. against: u8[n_seqs] or NULL. out: per pair aligned,
+ *   n_matches, aln_len, nerrs, score (AS), best_k, um, md (0 with skip_div), cigar_off[n_pairs + 1] and cigar — raw BAM words with
+ *   = X I D, what lcty_locus_set_hap_alns and lcty_basis_build take (id1 = query_id, id2 = ref_id). Released with lcty_align_out_free.
+ *   ref_id == query_id, a pair given twice (in either order), an id out of range: LCTY_ERR_INVALID_INPUT.
+ * lcty_align_all_pairs: the order of TriangleMatrix::indices — rows i, then j > i, i the reference: load_pairs with --all
+ *   (command/align.rs:264-266). ref_id, query_id [n (n - 1) / 2].
+ * lcty_align_backbone: one pair and one k, every stage's output: matches [2 n_matches] (pos1, pos2), the chain score, the path as
+ *   match indices, the CIGAR and its score. Released with lcty_align_backbone_out_free.
+ * lcty_paf_write_text (host): the header line of command/align.rs:385-387 (accuracy=9) and one line per pair as process_pair 639-677
+ *   writes it; qv is `inf` when dv is 0. names: n_seqs 0-terminated names one after the other. Called twice: out = NULL sizes
+ *   (*needed), then cap >= *needed. `haplotypes.paf.gz` = this text through lcty_io_write_gz. */
+#define LCTY_ALIGN_MAX_K 127u
+typedef struct lcty_align_params {
+    uint32_t div_k, div_w;            /* 15, 15 */
+    int32_t  skip_div;                /* 0 */
+    uint32_t n_backbone_ks;           /* 3 */
+    double   thresh_div, against_div; /* 1.0, 1.0 */
+    uint32_t backbone_ks[8];          /* 25, 51, 101 */
+    uint32_t max_gap;                 /* 10000 */
+    int32_t  mismatch, gap_open, gap_extend;   /* 4, 6, 1 (Penalties::default, wfa.rs:30-38); anything else: LCTY_ERR_UNSUPPORTED */
+} lcty_align_params;
+typedef struct lcty_align_out {
+    uint64_t  n_pairs;
+    uint8_t*  aligned;                /* [n_pairs] 0: skipped by its divergence */
+    uint32_t* n_matches; uint32_t* aln_len; uint32_t* nerrs;
+    int32_t*  score;
+    uint32_t* best_k;
+    uint32_t* um; double* md;
+    uint64_t* cigar_off; uint32_t* cigar;
+} lcty_align_out;
+typedef struct lcty_align_backbone_out {
+    uint64_t  n_matches; uint32_t* matches;
+    uint32_t  chain_score, path_len; uint32_t* path;
+    uint32_t  n_cigar; int32_t score; uint32_t* cigar;
+    uint32_t  n_dropped, _pad0;
+} lcty_align_backbone_out;
+typedef struct lcty_align_stats {
+    uint64_t n_aligned, n_skipped, n_dropped;      /* pairs aligned / skipped by divergence; stretches dropped to align_simple */
+    uint64_t n_kmer_matches, n_chain_points;       /* over all (pair, k) */
+    uint64_t n_trivial, n_simple, n_small_dp, n_general_dp;   /* stretches by route; small / general DP are SIZE classes (both sides <= 7, or not) of one aligner */
+    uint64_t dp_cells, n_batches, n_level[3];      /* cells of the exact aligner; batches; (pair, k) tasks per scratch level */
+    uint64_t bytes_h2d, bytes_d2h;
+    /* wall time per stage with the stream drained at its end: divergences, k-mer index, matches, chains, gap fill, best k + download */
+    double   div_ms, index_ms, match_ms, chain_ms, fill_ms, select_ms, total_ms;
+} lcty_align_stats;
+
+void    lcty_align_params_default(lcty_align_params* params);
+int32_t lcty_align_all_pairs(uint32_t n_seqs, uint32_t* ref_id, uint32_t* query_id);
+int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref_id,
+                              const uint32_t* query_id, const uint8_t* against, const lcty_align_params* params, lcty_align_out* out,
+                              lcty_align_stats* stats);
+void    lcty_align_out_free(lcty_align_out* out);
+int32_t lcty_align_backbone(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref, uint32_t query, uint32_t k,
+                            const lcty_align_params* params, lcty_align_backbone_out* out, lcty_align_stats* stats);
+void    lcty_align_backbone_out_free(lcty_align_backbone_out* out);
+int32_t lcty_paf_write_text(const lcty_align_params* params, uint32_t n_seqs, const char* names, const uint64_t* seq_off, uint64_t n_pairs,
+                            const uint32_t* ref_id, const uint32_t* query_id, const lcty_align_out* res, char* out, uint64_t cap, uint64_t* needed);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -47,6 +47,13 @@ SIGNATURES = {
     "lcty_basis_select": (I32, [U32, U64, VP, U64, VP, P(U32), P(U32), P(I32), P(U64)]),
     "lcty_basis_build": (I32, [VP, U32, VP, U64, VP, VP, VP, VP, VP, VP, VP, P(BasisParams), VP, P(U32), P(U32), P(I32), P(BasisStats)]),
     "lcty_basis_tag": (I32, [P(BasisParams), C.c_char_p, U32, C.c_char_p, U64]),
+    "lcty_align_params_default": (None, [P(AlignParams)]),
+    "lcty_align_all_pairs": (I32, [U32, VP, VP]),
+    "lcty_align_haplotypes": (I32, [VP, U32, VP, VP, U64, VP, VP, VP, P(AlignParams), P(AlignOut), P(AlignStats)]),
+    "lcty_align_out_free": (None, [P(AlignOut)]),
+    "lcty_align_backbone": (I32, [VP, U32, VP, VP, U32, U32, U32, P(AlignParams), P(AlignBackboneOut), P(AlignStats)]),
+    "lcty_align_backbone_out_free": (None, [P(AlignBackboneOut)]),
+    "lcty_paf_write_text": (I32, [P(AlignParams), U32, C.c_char_p, VP, U64, VP, VP, P(AlignOut), VP, U64, P(U64)]),
     "lcty_last_error": (C.c_char_p, []),
     "lcty_version": (C.c_char_p, []),
     "lcty_device_count": (I32, []),

@@ -1186,3 +1186,75 @@ def basis_fasta(names, seqs, seq_off, ids):
     o = np.zeros(len(parts) + 1, dtype=np.uint64)
     np.cumsum([len(x) for x in parts], out=o[1:])
     return fasta_text([names[i] for i in ids], np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8), o)
+
+
+# ---- pairwise haplotype alignments (locityper align --transitive 0; lcty_align.hip) ------------------------------------------------------
+def align_params(**kw):
+    """lcty_align_params_default (minimizers 15 / 15, thresholds 1.0, backbone ks 25, 51, 101, max_gap 10 000) with overrides;
+    backbone_ks takes a sequence."""
+    p = cdefs.AlignParams()
+    lib().lcty_align_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "backbone_ks":
+            ks = list(v)
+            if len(ks) > 8:
+                raise ValueError("at most 8 backbone ks")
+            for i in range(8):
+                p.backbone_ks[i] = ks[i] if i < len(ks) else 0
+            p.n_backbone_ks = len(ks)
+        elif not hasattr(p, k):
+            raise AttributeError(k)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def align_all_pairs(n_seqs):
+    """lcty_align_all_pairs: (ref_id, query_id) in the order rows i, then j > i, with i as the reference (`--all`)."""
+    n = max(n_seqs * (n_seqs - 1) // 2, 0)
+    r = np.zeros(max(n, 1), dtype=np.uint32); q = np.zeros(max(n, 1), dtype=np.uint32)
+    check(lib().lcty_align_all_pairs(n_seqs, r.ctypes.data, q.ctypes.data))
+    return r[:n], q[:n]
+
+
+def _copy(ptr, count, dt):
+    return np.frombuffer(C.string_at(ptr, count * np.dtype(dt).itemsize), dtype=dt).copy() if count else np.zeros(0, dtype=dt)
+
+
+def align_haplotypes(ctx, seqs, seq_off, ref_id, query_id, params=None, against=None):
+    """lcty_align_haplotypes: (dict of per-pair arrays aligned, n_matches, aln_len, nerrs, score, best_k, um, md, cigar_off, cigar;
+    stats dict). Pairs in input order; ref_id[i] is the reference and query_id[i] the query of pair i."""
+    p = params if params is not None else align_params()
+    sq, off = _seq_arrays(seqs, seq_off)
+    r = np.ascontiguousarray(ref_id, dtype=np.uint32); q = np.ascontiguousarray(query_id, dtype=np.uint32)
+    if len(r) != len(q):
+        raise ValueError("ref_id and query_id differ in length")
+    ag = None if against is None else np.ascontiguousarray(against, dtype=np.uint8)
+    o, st = cdefs.AlignOut(), cdefs.AlignStats()
+    check(lib().lcty_align_haplotypes(ctx._h, len(off) - 1, sq.ctypes.data, off.ctypes.data, len(r), r.ctypes.data, q.ctypes.data,
+                                      None if ag is None else ag.ctypes.data, C.byref(p), C.byref(o), C.byref(st)))
+    try:
+        n = int(o.n_pairs)
+        res = {"aligned": _copy(o.aligned, n, np.uint8), "n_matches": _copy(o.n_matches, n, np.uint32), "aln_len": _copy(o.aln_len, n, np.uint32),
+               "nerrs": _copy(o.nerrs, n, np.uint32), "score": _copy(o.score, n, np.int32), "best_k": _copy(o.best_k, n, np.uint32),
+               "um": _copy(o.um, n, np.uint32), "md": _copy(o.md, n, np.float64), "cigar_off": _copy(o.cigar_off, n + 1, np.uint64)}
+        res["cigar"] = _copy(o.cigar, int(res["cigar_off"][-1]), np.uint32)
+    finally:
+        lib().lcty_align_out_free(C.byref(o))
+    return res, st.as_dict()
+
+
+def align_backbone(ctx, seqs, seq_off, ref, query, k, params=None):
+    """lcty_align_backbone: one pair, one k, every stage: dict of matches [n][2] (pos1, pos2), chain_score, path (match indices),
+    cigar (raw words), score, n_dropped; stats dict."""
+    p = params if params is not None else align_params()
+    sq, off = _seq_arrays(seqs, seq_off)
+    o, st = cdefs.AlignBackboneOut(), cdefs.AlignStats()
+    check(lib().lcty_align_backbone(ctx._h, len(off) - 1, sq.ctypes.data, off.ctypes.data, ref, query, k, C.byref(p), C.byref(o), C.byref(st)))
+    try:
+        res = {"matches": _copy(o.matches, 2 * int(o.n_matches), np.uint32).reshape(-1, 2), "chain_score": int(o.chain_score),
+               "path": _copy(o.path, int(o.path_len), np.uint32), "cigar": _copy(o.cigar, int(o.n_cigar), np.uint32), "score": int(o.score),
+               "n_dropped": int(o.n_dropped)}
+    finally:
+        lib().lcty_align_backbone_out_free(C.byref(o))
+    return res, st.as_dict()

@@ -143,6 +143,34 @@ class BasisStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AlignParams(C.Structure):
+    """`locityper align`, the backbone strategy (src/seq/align.rs:48-64); penalties other than 4 / 6 / 1 are not offered."""
+    _fields_ = [("div_k", C.c_uint32), ("div_w", C.c_uint32), ("skip_div", C.c_int32), ("n_backbone_ks", C.c_uint32),
+                ("thresh_div", C.c_double), ("against_div", C.c_double), ("backbone_ks", C.c_uint32 * 8), ("max_gap", C.c_uint32),
+                ("mismatch", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32)]
+
+
+class AlignOut(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("aligned", C.c_void_p), ("n_matches", C.c_void_p), ("aln_len", C.c_void_p), ("nerrs", C.c_void_p),
+                ("score", C.c_void_p), ("best_k", C.c_void_p), ("um", C.c_void_p), ("md", C.c_void_p), ("cigar_off", C.c_void_p),
+                ("cigar", C.c_void_p)]
+
+
+class AlignBackboneOut(C.Structure):
+    _fields_ = [("n_matches", C.c_uint64), ("matches", C.c_void_p), ("chain_score", C.c_uint32), ("path_len", C.c_uint32), ("path", C.c_void_p),
+                ("n_cigar", C.c_uint32), ("score", C.c_int32), ("cigar", C.c_void_p), ("n_dropped", C.c_uint32), ("_pad0", C.c_uint32)]
+
+
+class AlignStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_aligned", "n_skipped", "n_dropped", "n_kmer_matches", "n_chain_points", "n_trivial", "n_simple",
+                                          "n_small_dp", "n_general_dp", "dp_cells", "n_batches")] + [("n_level", C.c_uint64 * 3)] + \
+               [(n, C.c_uint64) for n in ("bytes_h2d", "bytes_d2h")] + \
+               [(n, C.c_double) for n in ("div_ms", "index_ms", "match_ms", "chain_ms", "fill_ms", "select_ms", "total_ms")]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n == "n_level" else getattr(self, n)) for n, _ in self._fields_}
+
+
 class BgReadsView(C.Structure):
     """The records of the background interval as load_alns keeps them (preproc.rs:988-1028)."""
     _fields_ = [

@@ -1,0 +1,860 @@
+// lcty_align.hip — pairwise alignments of a locus's haplotypes, the backbone strategy of `locityper align` (what `--transitive 0`
+// runs): src/seq/align.rs process_pair 627-679, precompute_kmers / get_kmer_matches 102-120 and 202-224, align_from_backbone 246-292,
+// align_multik 294-318; smart_align src/seq/wfa.rs:280-321. The result is the content of DB/loci/<locus>/haplotypes.paf.gz.
+//   index    per (sequence, k): a 64-bit hash per window out of prefix sums (align_prefix_kernel, align_keys_kernel), one segmented
+//            sort per k (rocPRIM) — once per call
+//   stage A  per (pair, k): every window of the reference looks its hash up in the query's sorted list; every candidate is compared
+//            base by base before it counts (align_join_kernel, counting pass, scan, emitting pass). The matches leave sorted by
+//            (pos1, pos2) because a reference position writes its own run in ascending pos2.
+//   stage B  per (pair, k): LCSk++ (Pavetic, Zuzic, Sikic 2014; rust-bio's bio::alignment::sparse::lcskpp): one lane per task,
+//            a prefix-maximum (Fenwick) tree over the query coordinate, a binary search for the diagonal predecessor
+//   stage C  per (pair, k): the walk of align_from_backbone with smart_align; the exact aligner is the Gotoh recurrence of
+//            lcty_transfer_device.hpp (same penalties, same tie rule: walking back from the end, diagonal before deletion before
+//            insertion, a gap is extended before it is opened) WITHOUT that header's step limit, which belongs to accuracy level 6:
+//            `locityper align` runs level 9, no limit. The header's functions themselves are bound to the packed read of a transfer
+//            (xfer::Seqs) and to its LDS-backed CIGAR, so the recurrence is restated here on plain bytes; its constants are shared.
+//   per pair the best k (first wins a tie) and the counts are taken on the device; only the winner's CIGAR is downloaded.
+#include "lcty_common.hpp"
+#include "lcty_transfer_device.hpp"
+
+#include <rocprim/rocprim.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+namespace {
+using namespace lcty;
+using xfer::OP_I; using xfer::OP_D; using xfer::OP_EQ; using xfer::OP_X; using xfer::PEN_X; using xfer::PEN_O; using xfer::PEN_E; using xfer::INF32;
+
+constexpr uint64_t kHashBase = 0x9E3779B97F4A7C15ull;          // odd: invertible modulo 2^64
+constexpr uint64_t kNoKey = ~0ull;                               // key of a window that is not a k-mer (sorts behind every hash)
+constexpr uint64_t kMaxMatches = 1ull << 24;                     // matches of one (pair, k); beyond: LCTY_ERR_UNSUPPORTED
+constexpr uint32_t kLevels = 3;
+constexpr uint32_t kLevelDim[kLevels] = {255, 2047, 16383};      // longest side of a stretch the exact aligner takes at a level
+constexpr uint32_t kLevelCells[kLevels] = {1u << 16, 1u << 22, 1u << 26};
+constexpr uint32_t kLevelLanes[kLevels] = {8192, 128, 8};        // lanes in flight (their scratch: 0.6 GB, 0.5 GB, 0.5 GB)
+enum : uint32_t { ST_TRIVIAL = 0, ST_SIMPLE, ST_SMALL, ST_GENERAL, ST_DROPPED, ST_CELLS, ST_POINTS, ST_OVERFLOW, ST_COUNT };
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+__host__ __device__ inline uint64_t powu(uint64_t b, uint64_t e) {
+    uint64_t r = 1;
+    for (; e; e >>= 1, b *= b) if (e & 1) r *= b;
+    return r;
+}
+__device__ __forceinline__ uint32_t base_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
+__device__ __forceinline__ uint8_t base_norm(uint8_t c) { return base_code(c) < 4u ? c : static_cast<uint8_t>('N'); }
+
+// P[i] = sum over t < i of (code(t) + 1) * B^t, NP[i] = bytes outside ACGT before i; sequence s has len + 1 entries from off[s] + s on.
+// One block per sequence: a run of consecutive bases per thread, a scan over the threads' sums.
+__global__ __launch_bounds__(256) void align_prefix_kernel(const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off,
+                                                           uint64_t* __restrict__ P, uint32_t* __restrict__ NP) {
+    __shared__ uint64_t sh[256];
+    __shared__ uint32_t sn[256];
+    __shared__ uint64_t tot_h;
+    __shared__ uint32_t tot_n;
+    const uint32_t s = blockIdx.x, t = threadIdx.x;
+    const uint64_t base = off[s], L = off[s + 1] - base, pb = base + s;
+    const uint64_t chunk = (L + 255) / 256, lo = min(t * chunk, L), hi = min(lo + chunk, L);
+    uint64_t sum = 0, pw = powu(kHashBase, lo);
+    uint32_t nn = 0;
+    for (uint64_t i = lo; i < hi; i++) {
+        uint32_t c = base_code(seq[base + i]);
+        if (c > 3u) { nn++; c = 0; }
+        sum += (c + 1) * pw; pw *= kHashBase;
+    }
+    sh[t] = sum; sn[t] = nn;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t a = 0; uint32_t b = 0;
+        for (uint32_t x = 0; x < 256; x++) { const uint64_t v = sh[x]; const uint32_t w = sn[x]; sh[x] = a; sn[x] = b; a += v; b += w; }
+        tot_h = a; tot_n = b;
+    }
+    __syncthreads();
+    uint64_t acc = sh[t]; uint32_t n = sn[t];
+    pw = powu(kHashBase, lo);
+    for (uint64_t i = lo; i < hi; i++) {
+        P[pb + i] = acc; NP[pb + i] = n;
+        uint32_t c = base_code(seq[base + i]);
+        if (c > 3u) { n++; c = 0; }
+        acc += (c + 1) * pw; pw *= kHashBase;
+    }
+    if (t == 0) { P[pb + L] = tot_h; NP[pb + L] = tot_n; }
+}
+
+// key of window p of every sequence: the hash of its k bases (independent of p), or kNoKey: the window runs over the end or holds a
+// byte outside ACGT. hash_mask: the knob align_hash_bits (all ones by default; then the one value that equals kNoKey is moved).
+__global__ __launch_bounds__(256) void align_keys_kernel(const uint64_t* __restrict__ off, const uint64_t* __restrict__ P, const uint32_t* __restrict__ NP,
+                                                         uint32_t k, uint64_t base_inv, uint64_t hash_mask, uint64_t* __restrict__ keys,
+                                                         uint32_t* __restrict__ vals) {
+    const uint32_t s = blockIdx.x;
+    const uint64_t base = off[s], L = off[s + 1] - base, pb = base + s;
+    for (uint64_t p = threadIdx.x; p < L; p += 256) {
+        uint64_t key = kNoKey;
+        if (p + k <= L && NP[pb + p + k] == NP[pb + p]) {
+            uint64_t h = (P[pb + p + k] - P[pb + p]) * powu(base_inv, p);
+            h ^= h >> 30; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 27; h *= 0x94D049BB133111EBull; h ^= h >> 31;
+            h &= hash_mask;
+            key = h == kNoKey ? kNoKey - 1 : h;
+        }
+        keys[base + p] = key; vals[base + p] = static_cast<uint32_t>(p);
+    }
+}
+
+struct Task { uint32_t ref, qry, ki, k; };
+
+// Stage A, both passes. One block per (pair, k); a thread per reference window p1. EMIT = false: cnt[slot] = verified matches of p1.
+// EMIT = true: they are written from mo[slot] on, in ascending pos2 (a bucket of equal keys is put in order here: the segmented sort
+// is not relied on to keep equal keys in input order).
+template <bool EMIT>
+__global__ __launch_bounds__(256) void align_join_kernel(const Task* __restrict__ tasks, const uint64_t* __restrict__ slot_off,
+                                                         const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, uint64_t total,
+                                                         const uint64_t* __restrict__ keys_in, const uint64_t* __restrict__ keys_sorted,
+                                                         const uint32_t* __restrict__ vals_sorted, uint32_t* __restrict__ cnt,
+                                                         const uint64_t* __restrict__ mo, uint2* __restrict__ matches) {
+    const Task tk = tasks[blockIdx.x];
+    const uint64_t rb = off[tk.ref], Lr = off[tk.ref + 1] - rb, qb = off[tk.qry], Lq = off[tk.qry + 1] - qb;
+    const uint64_t* kr = keys_in + static_cast<uint64_t>(tk.ki) * total + rb;
+    const uint64_t* kq = keys_sorted + static_cast<uint64_t>(tk.ki) * total + qb;
+    const uint32_t* vq = vals_sorted + static_cast<uint64_t>(tk.ki) * total + qb;
+    const uint64_t slot0 = slot_off[blockIdx.x];
+    for (uint64_t p1 = threadIdx.x; p1 < Lr; p1 += 256) {
+        const uint64_t h = kr[p1];
+        uint32_t c = 0;
+        uint2* dst = EMIT ? matches + mo[slot0 + p1] : nullptr;
+        if (h != kNoKey) {
+            uint64_t lo = 0, hi = Lq;
+            while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (kq[mid] < h) lo = mid + 1; else hi = mid; }
+            for (; lo < Lq && kq[lo] == h; lo++) {
+                const uint32_t p2 = vq[lo];
+                bool eq = true;
+                for (uint32_t i = 0; i < tk.k && eq; i++) eq = seq[rb + p1 + i] == seq[qb + p2 + i];
+                if (!eq) continue;
+                if (EMIT) {
+                    uint32_t at = c;                                          // insertion by pos2
+                    while (at > 0 && dst[at - 1].y > p2) { dst[at] = dst[at - 1]; at--; }
+                    dst[at] = make_uint2(static_cast<uint32_t>(p1), p2);
+                }
+                c++;
+            }
+        }
+        if (!EMIT) cnt[slot0 + p1] = c;
+    }
+}
+
+__global__ void align_task_offsets_kernel(const uint64_t* __restrict__ slot_off, const uint64_t* __restrict__ mo, uint32_t n_tasks, uint64_t* __restrict__ tm) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t <= n_tasks) tm[t] = mo[slot_off[t]];
+}
+
+// Stage B. dp(m) = max(k, dp(m') + 1 for m' = (i - 1, j - 1) a match, k + max dp(m'') over matches with i'' + k <= i and j'' + k <= j).
+// The matches are sorted, so their start events (i, j) and their end events (i + k, j + k) are two sorted sequences: merged on the fly,
+// an end before a start at the same point. A start asks the tree for the best dp among ends at columns <= j; an end takes the diagonal
+// predecessor (whose own end came earlier) and enters the tree at column j + k. Ties: the lowest match index (tree entries are
+// value << 32 | ~index; the argmax is taken with a strict >, ends come in index order); a jump is kept over an equal continuation.
+__device__ inline uint64_t fen_query(const uint64_t* f, uint32_t pos) {
+    uint64_t r = 0;
+    for (; pos > 0; pos -= pos & (0u - pos)) r = max(r, f[pos]);
+    return r;
+}
+__device__ inline void fen_update(uint64_t* f, uint32_t n, uint32_t pos, uint64_t v) {
+    for (; pos <= n; pos += pos & (0u - pos)) if (f[pos] < v) f[pos] = v;
+}
+__global__ __launch_bounds__(64) void align_chain_kernel(const Task* __restrict__ tasks, uint32_t n_tasks, const uint64_t* __restrict__ off,
+                                                         const uint64_t* __restrict__ tm, const uint2* __restrict__ matches, uint32_t* __restrict__ dp,
+                                                         uint32_t* __restrict__ prev, uint32_t* __restrict__ path, const uint64_t* __restrict__ fen_off,
+                                                         uint64_t* __restrict__ fen, uint32_t* __restrict__ chain, uint32_t* __restrict__ path_start,
+                                                         unsigned long long* __restrict__ stats) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_tasks) return;
+    const Task tk = tasks[t];
+    const uint64_t m0 = tm[t];
+    const uint32_t m = static_cast<uint32_t>(tm[t + 1] - m0), k = tk.k;
+    const uint2* M = matches + m0;
+    uint32_t* D = dp + m0; uint32_t* PV = prev + m0; uint32_t* PT = path + m0;
+    uint64_t* F = fen + fen_off[t];
+    const uint32_t fn = static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]);           // columns 1..qlen (j + k <= qlen)
+    uint32_t s = 0, e = 0, best = 0, best_ix = 0;
+    while (e < m) {
+        bool start = false;
+        if (s < m) { const uint2 a = M[s], b = M[e]; start = a.x < b.x + k || (a.x == b.x + k && a.y < b.y + k); }
+        if (start) {
+            const uint64_t q = fen_query(F, M[s].y);
+            if (q >> 32) { D[s] = k + static_cast<uint32_t>(q >> 32); PV[s] = ~static_cast<uint32_t>(q); }
+            else { D[s] = k; PV[s] = 0xFFFFFFFFu; }
+            s++;
+        } else {
+            const uint2 b = M[e];
+            if (b.x > 0 && b.y > 0) {
+                uint32_t lo = 0, hi = m;
+                const uint32_t wx = b.x - 1, wy = b.y - 1;
+                while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; const uint2 c = M[mid]; if (c.x < wx || (c.x == wx && c.y < wy)) lo = mid + 1; else hi = mid; }
+                if (lo < m && M[lo].x == wx && M[lo].y == wy && D[lo] + 1 > D[e]) { D[e] = D[lo] + 1; PV[e] = lo; }
+            }
+            fen_update(F, fn, b.y + k, (static_cast<uint64_t>(D[e]) << 32) | (~e));
+            if (D[e] > best) { best = D[e]; best_ix = e; }
+            e++;
+        }
+    }
+    uint32_t n = 0;
+    if (m) for (uint32_t x = best_ix; x != 0xFFFFFFFFu; x = PV[x]) { n++; PT[m - n] = x; }
+    chain[t] = best; path_start[t] = m - n;
+    atomicAdd(&stats[ST_POINTS], static_cast<unsigned long long>(n));
+}
+
+// Stage C -------------------------------------------------------------------------------------------------------------------------------
+struct Lim { uint32_t dim, cells; };                            // what the exact aligner takes (a level's scratch, or the largest level)
+__host__ __device__ inline bool lim_takes(const Lim& l, uint32_t n, uint32_t m) {
+    return n <= l.dim && m <= l.dim && (static_cast<uint64_t>(n) + 1) * (static_cast<uint64_t>(m) + 1) <= l.cells;
+}
+__host__ __device__ inline size_t lane_bytes(const Lim& l) { return (2 * (static_cast<size_t>(l.dim) + 1) * 12 + l.cells + 15) & ~size_t(15); }
+
+struct PairSeq {
+    const uint8_t* r; const uint8_t* q;                          // any byte outside ACGT is N, and N equals N
+    __device__ __forceinline__ uint8_t R(uint32_t i) const { return base_norm(r[i]); }
+    __device__ __forceinline__ uint8_t Q(uint32_t j) const { return base_norm(q[j]); }
+};
+// the CIGAR of a task: raw BAM words; equal neighbours merge (the reference's push_unchecked can leave `a=b=`: same alignment, same score)
+struct CigOut {
+    uint32_t* w; uint32_t n, cap; bool overflow;
+    __device__ __forceinline__ void push(uint32_t op, uint32_t len) {
+        if (!len) return;
+        if (n && (w[n - 1] & 15u) == op) { w[n - 1] += len << 4; return; }
+        if (n < cap) w[n++] = (len << 4) | op; else overflow = true;
+    }
+};
+
+// the walk of align_from_backbone (align.rs:262-286): v.anchor(len) for a finished '=' run, v.stretch(i1, i2, j1, j2) for smart_align
+template <class V>
+__device__ inline void walk_backbone(const uint2* M, const uint32_t* path, uint32_t n_path, uint32_t k, uint32_t n1, uint32_t n2, V& v) {
+    uint32_t i1 = 0, j1 = 0, cur = 0;
+    for (uint32_t x = 0; x < n_path; x++) {
+        const uint2 a = M[path[x]];
+        if (i1 > a.x) { cur++; i1++; j1++; continue; }
+        if (cur) { v.anchor(cur); cur = 0; }
+        v.stretch(i1, a.x, j1, a.y);
+        cur += k; i1 = a.x + k; j1 = a.y + k;
+    }
+    if (cur) v.anchor(cur);
+    v.stretch(i1, n1, j1, n2);
+}
+
+constexpr uint32_t kSafeMismatch = (2 * PEN_O + 2 * PEN_E) / PEN_X;                      // wfa.rs:212
+// which scratch level the task needs and an upper bound of its CIGAR's items
+struct Levels { Lim l[kLevels]; };                              // the levels' limits, already cut to the knob align_dp_cells
+struct PlanVisitor {
+    uint32_t max_gap; Lim top; Levels lv; uint32_t level; uint64_t bound;
+    __device__ void anchor(uint32_t) { bound++; }
+    __device__ void stretch(uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2) {
+        const uint32_t n = i2 - i1, m = j2 - j1;
+        if (!n || !m) { bound++; return; }
+        if (max_gap < n || max_gap < m || !lim_takes(top, n, m)) { bound += min(n, m) + 1; return; }
+        if (n == m && n <= kSafeMismatch) { bound += n; return; }
+        bound += static_cast<uint64_t>(n) + m;
+        for (uint32_t l = 0; l < kLevels; l++)
+            if (lim_takes(lv.l[l], n, m)) { level = max(level, l); return; }
+        level = kLevels - 1;
+    }
+};
+__global__ __launch_bounds__(64) void align_plan_kernel(const Task* __restrict__ tasks, uint32_t n_tasks, const uint64_t* __restrict__ off,
+                                                        const uint64_t* __restrict__ tm, const uint2* __restrict__ matches, const uint32_t* __restrict__ path,
+                                                        const uint32_t* __restrict__ path_start, uint32_t max_gap, Lim top, Levels lv,
+                                                        uint32_t* __restrict__ level, uint32_t* __restrict__ cig_cap) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_tasks) return;
+    const Task tk = tasks[t];
+    const uint64_t m0 = tm[t];
+    const uint32_t m = static_cast<uint32_t>(tm[t + 1] - m0);
+    PlanVisitor v{max_gap, top, lv, 0, 2};
+    walk_backbone(matches + m0, path + m0 + path_start[t], m - path_start[t], tk.k, static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]),
+                  static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]), v);
+    level[t] = v.level;
+    cig_cap[t] = static_cast<uint32_t>(min(v.bound, static_cast<uint64_t>(0xFFFFFFFFu)));
+}
+
+struct FillVisitor {
+    PairSeq S; CigOut cg; uint32_t max_gap; Lim top, mine; int32_t* rows; uint8_t* dirs; int score; uint32_t dropped;
+    unsigned long long n_route[4], cells;
+
+    // Penalties::align_simple (wfa.rs:49-84)
+    __device__ int simple(uint32_t i1, uint32_t n, uint32_t j1, uint32_t m) {
+        const int diff = static_cast<int>(n) - static_cast<int>(m);
+        int sc = 0;
+        uint32_t i = 0, j = 0;
+        if (diff < 0) { cg.push(OP_I, static_cast<uint32_t>(-diff)); sc = -PEN_O + diff * PEN_E; j = static_cast<uint32_t>(-diff); }
+        else if (diff > 0) { cg.push(OP_D, static_cast<uint32_t>(diff)); sc = -PEN_O - diff * PEN_E; i = static_cast<uint32_t>(diff); }
+        for (uint32_t t = 0; i + t < n && j + t < m; t++) {
+            const bool eq = S.R(i1 + i + t) == S.Q(j1 + j + t);
+            cg.push(eq ? OP_EQ : OP_X, 1);
+            sc -= eq ? 0 : PEN_X;
+        }
+        return sc;
+    }
+    // the end-to-end gap-affine optimum of reference [i1, +n) and query [j1, +m): recurrence, tie rule and walk back of xfer::dp_align
+    // (mode 0, no match bonus), without its step limit. The caller has checked lim_takes(mine, n, m).
+    __device__ int gotoh(uint32_t i1, uint32_t n, uint32_t j1, uint32_t m) {
+        const uint32_t W = m + 1;
+        cells += static_cast<unsigned long long>(n + 1) * W;
+        int32_t* prev = rows;
+        int32_t* cur = rows + (static_cast<size_t>(mine.dim) + 1) * 3;
+        for (uint32_t a = 0; a <= n; a++) {
+            const uint8_t rbase = a > 0 ? S.R(i1 + a - 1) : 0;
+            int32_t lm = INF32, ld = INF32, li = INF32, gm = INF32, gd = INF32, gi = INF32;
+            for (uint32_t b = 0; b <= m; b++) {
+                int32_t cm = INF32, cd = INF32, ci = INF32;
+                uint32_t dm = 3, dd = 0, di = 0;
+                int32_t um = INF32, ud = INF32, ui = INF32;
+                if (a > 0) { um = prev[b * 3]; ud = prev[b * 3 + 1]; ui = prev[b * 3 + 2]; }
+                if (a == 0 && b == 0) cm = 0;
+                if (a > 0 && b > 0) {
+                    const int32_t best = min(gm, min(gd, gi));
+                    if (best < INF32) {
+                        const int32_t v = best + (rbase == S.Q(j1 + b - 1) ? 0 : PEN_X);
+                        if (v < cm) { cm = v; dm = gm == best ? 0u : (gd == best ? 1u : 2u); }
+                    }
+                }
+                if (a > 0) {
+                    int32_t v = min(um, ui) + PEN_O + PEN_E;
+                    if (ud + PEN_E < v) v = ud + PEN_E;
+                    if (v < INF32) { cd = v; dd = (ud + PEN_E == v) ? 1u : (um <= ui ? 0u : 2u); }
+                }
+                if (b > 0) {
+                    int32_t v = min(lm, ld) + PEN_O + PEN_E;
+                    if (li + PEN_E < v) v = li + PEN_E;
+                    if (v < INF32) { ci = v; di = (li + PEN_E == v) ? 2u : (lm <= ld ? 0u : 1u); }
+                }
+                cur[b * 3] = cm; cur[b * 3 + 1] = cd; cur[b * 3 + 2] = ci;
+                dirs[static_cast<size_t>(a) * W + b] = static_cast<uint8_t>(dm | (dd << 2) | (di << 4));
+                lm = cm; ld = cd; li = ci;
+                gm = um; gd = ud; gi = ui;
+            }
+            int32_t* x = prev; prev = cur; cur = x;
+        }
+        const int32_t em = prev[m * 3], ed = prev[m * 3 + 1], ei = prev[m * 3 + 2];
+        const int32_t best = min(em, min(ed, ei));
+        // walk back: the runs arrive last first, behind the items the CIGAR has; then they are turned round and joined to them
+        const uint32_t r0 = cg.n;
+        CigOut rev{cg.w + r0, 0, cg.cap - r0, false};
+        uint32_t a = n, b = m;
+        uint32_t st = (em <= ed && em <= ei) ? 0u : (ed <= ei ? 1u : 2u);
+        while (a > 0 || b > 0) {
+            const uint32_t d = dirs[static_cast<size_t>(a) * W + b];
+            if (st == 0) { rev.push(S.R(i1 + a - 1) == S.Q(j1 + b - 1) ? OP_EQ : OP_X, 1); st = d & 3u; a--; b--; }
+            else if (st == 1) { rev.push(OP_D, 1); const uint32_t dd = (d >> 2) & 3u; st = dd == 1 ? 1u : (dd == 0 ? 0u : 2u); a--; }
+            else { rev.push(OP_I, 1); const uint32_t di = (d >> 4) & 3u; st = di == 2 ? 2u : (di == 0 ? 0u : 1u); b--; }
+        }
+        cg.overflow |= rev.overflow;
+        for (uint32_t x = 0, y = rev.n; x + 1 < y; x++, y--) { const uint32_t w = rev.w[x]; rev.w[x] = rev.w[y - 1]; rev.w[y - 1] = w; }
+        cg.n = r0;
+        for (uint32_t x = 0; x < rev.n; x++) { const uint32_t w = cg.w[r0 + x]; cg.push(w & 15u, w >> 4); }     // (reads at or ahead of what it writes)
+        return -best;
+    }
+    __device__ void anchor(uint32_t len) { cg.push(OP_EQ, len); }
+    // smart_align (wfa.rs:280-321) with max_gap as the threshold
+    __device__ void stretch(uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2) {
+        const uint32_t n = i2 - i1, m = j2 - j1;
+        if (n > 0 && m > 0) {
+            if (max_gap < n || max_gap < m) { n_route[ST_SIMPLE]++; score += simple(i1, n, j1, m); return; }
+            if (n == m && n <= kSafeMismatch) {
+                n_route[ST_TRIVIAL]++;
+                for (uint32_t t = 0; t < n; t++) { const bool eq = S.R(i1 + t) == S.Q(j1 + t); cg.push(eq ? OP_EQ : OP_X, 1); score -= eq ? 0 : PEN_X; }
+                return;
+            }
+            // beyond the largest scratch level the stretch is dropped, as the reference does when WFA drops an alignment (wfa.rs:234-237)
+            if (!lim_takes(top, n, m) || !lim_takes(mine, n, m)) { dropped++; n_route[ST_SIMPLE]++; score += simple(i1, n, j1, m); return; }
+            n_route[(n <= xfer::DP_SMALL && m <= xfer::DP_SMALL) ? ST_SMALL : ST_GENERAL]++;      // a size class: one aligner serves both
+            score += gotoh(i1, n, j1, m);
+            return;
+        }
+        if (n > 0) { n_route[ST_TRIVIAL]++; cg.push(OP_D, n); score -= PEN_O + static_cast<int>(n) * PEN_E; }
+        else if (m > 0) { n_route[ST_TRIVIAL]++; cg.push(OP_I, m); score -= PEN_O + static_cast<int>(m) * PEN_E; }
+    }
+};
+
+// one lane per task of the level's list; lane g works in scratch + g * lane_bytes(mine)
+__global__ __launch_bounds__(64) void align_fill_kernel(const uint32_t* __restrict__ list, uint32_t n_list, uint32_t n_lanes, const Task* __restrict__ tasks,
+                                                        const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint64_t* __restrict__ tm,
+                                                        const uint2* __restrict__ matches, const uint32_t* __restrict__ path,
+                                                        const uint32_t* __restrict__ path_start, uint32_t max_gap, Lim top, Lim mine, uint8_t* __restrict__ scratch,
+                                                        const uint64_t* __restrict__ cig_off, uint32_t* __restrict__ cig, int32_t* __restrict__ t_score,
+                                                        uint32_t* __restrict__ t_words, uint32_t* __restrict__ t_dropped, unsigned long long* __restrict__ stats) {
+    const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= n_lanes) return;
+    uint8_t* mem = scratch + static_cast<size_t>(g) * lane_bytes(mine);
+    for (uint32_t x = g; x < n_list; x += n_lanes) {
+        const uint32_t t = list[x];
+        const Task tk = tasks[t];
+        const uint64_t m0 = tm[t];
+        const uint32_t m = static_cast<uint32_t>(tm[t + 1] - m0);
+        FillVisitor v;
+        v.S = PairSeq{seq + off[tk.ref], seq + off[tk.qry]};
+        v.cg = CigOut{cig + cig_off[t], 0, static_cast<uint32_t>(cig_off[t + 1] - cig_off[t]), false};
+        v.max_gap = max_gap; v.top = top; v.mine = mine;
+        v.rows = reinterpret_cast<int32_t*>(mem); v.dirs = mem + 2 * (static_cast<size_t>(mine.dim) + 1) * 12;
+        v.score = 0; v.dropped = 0; v.cells = 0;
+        for (uint32_t r = 0; r < 4; r++) v.n_route[r] = 0;
+        walk_backbone(matches + m0, path + m0 + path_start[t], m - path_start[t], tk.k, static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]),
+                      static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]), v);
+        t_score[t] = v.score; t_words[t] = v.cg.n; t_dropped[t] = v.dropped;
+        for (uint32_t r = 0; r < 4; r++) if (v.n_route[r]) atomicAdd(&stats[r], v.n_route[r]);
+        if (v.dropped) atomicAdd(&stats[ST_DROPPED], static_cast<unsigned long long>(v.dropped));
+        if (v.cells) atomicAdd(&stats[ST_CELLS], v.cells);
+        if (v.cg.overflow) atomicAdd(&stats[ST_OVERFLOW], 1ull);
+    }
+}
+
+// align_multik (align.rs:294-318): the best score over the ks, the first k on a tie; the counts of process_pair 652-660
+struct PairRes { int32_t score; uint32_t best_ki, n_matches, nerrs, n_words, _pad; };
+__global__ __launch_bounds__(64) void align_select_kernel(uint32_t n_pairs, uint32_t nk, const int32_t* __restrict__ t_score, const uint32_t* __restrict__ t_words,
+                                                          const uint64_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, PairRes* __restrict__ res) {
+    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n_pairs) return;
+    uint32_t bk = 0;
+    for (uint32_t ki = 1; ki < nk; ki++) if (t_score[p * nk + ki] > t_score[p * nk + bk]) bk = ki;
+    const uint32_t t = p * nk + bk, nw = t_words[t];
+    const uint32_t* w = cig + cig_off[t];
+    uint32_t nm = 0, ne = 0;
+    for (uint32_t x = 0; x < nw; x++) { if ((w[x] & 15u) == OP_EQ) nm += w[x] >> 4; else ne += w[x] >> 4; }
+    res[p] = PairRes{t_score[t], bk, nm, ne, nw, 0};
+}
+__global__ __launch_bounds__(64) void align_gather_kernel(uint32_t nk, const PairRes* __restrict__ res, const uint64_t* __restrict__ cig_off,
+                                                          const uint32_t* __restrict__ cig, const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out) {
+    const uint32_t p = blockIdx.x;
+    const uint32_t* w = cig + cig_off[p * nk + res[p].best_ki];
+    for (uint32_t x = threadIdx.x; x < res[p].n_words; x += 64) out[out_off[p] + x] = w[x];
+}
+
+// Host ---------------------------------------------------------------------------------------------------------------------------------
+struct Index {
+    DevBuf<uint8_t> seq; DevBuf<uint64_t> off, keys_in, keys_sorted; DevBuf<uint32_t> vals_sorted;
+    uint64_t total = 0; uint32_t n_seqs = 0;
+    std::vector<uint32_t> ks;
+};
+
+void build_index(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, const std::vector<uint32_t>& ks, Index& ix, lcty_align_stats& st) {
+    hipStream_t s = ctx->stream;
+    const double t0 = now_ms();
+    ix.total = seq_off[n_seqs]; ix.n_seqs = n_seqs; ix.ks = ks;
+    if (ix.total >= 0xFFFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "%llu bases: the k-mer index holds at most 2^32 - 2", static_cast<unsigned long long>(ix.total));
+    const uint64_t T = ix.total, nk = ks.size();
+    ix.seq.alloc(T + 1); ix.off.alloc(n_seqs + 1);
+    ix.seq.upload(seqs, T, s); ix.off.upload(seq_off, n_seqs + 1, s);
+    st.bytes_h2d += T + 8ull * (n_seqs + 1);
+    ix.keys_in.alloc(std::max<uint64_t>(nk * T, 1)); ix.keys_sorted.alloc(std::max<uint64_t>(nk * T, 1)); ix.vals_sorted.alloc(std::max<uint64_t>(nk * T, 1));
+    if (nk && T) {
+        DevBuf<uint64_t> P, seg; DevBuf<uint32_t> NP, vals_in; DevBuf<uint8_t> tmp;
+        P.alloc(T + n_seqs); NP.alloc(T + n_seqs); vals_in.alloc(T);
+        hipLaunchKernelGGL(align_prefix_kernel, dim3(n_seqs), dim3(256), 0, s, ix.seq.p, ix.off.p, P.p, NP.p);
+        LCTY_HIP(hipGetLastError());
+        uint64_t inv = kHashBase;                                  // Newton: x <- x (2 - b x) doubles the correct low bits (3 to begin with)
+        for (int it = 0; it < 6; it++) inv *= 2 - kHashBase * inv;
+        const int64_t bits = ctx->knob("align_hash_bits", 64);
+        const uint64_t mask = bits >= 64 ? ~0ull : ((1ull << std::max<int64_t>(bits, 1)) - 1);
+        for (uint64_t ki = 0; ki < nk; ki++) {
+            uint64_t* kin = ix.keys_in.p + ki * T;
+            hipLaunchKernelGGL(align_keys_kernel, dim3(n_seqs), dim3(256), 0, s, ix.off.p, P.p, NP.p, ks[ki], inv, mask, kin, vals_in.p);
+            LCTY_HIP(hipGetLastError());
+            size_t bytes = 0;
+            LCTY_HIP(rocprim::segmented_radix_sort_pairs(nullptr, bytes, kin, ix.keys_sorted.p + ki * T, vals_in.p, ix.vals_sorted.p + ki * T,
+                                                         static_cast<unsigned int>(T), n_seqs, ix.off.p, ix.off.p + 1, 0, 64, s));
+            if (tmp.n < bytes) tmp.alloc(bytes + 16);
+            LCTY_HIP(rocprim::segmented_radix_sort_pairs(tmp.p, bytes, kin, ix.keys_sorted.p + ki * T, vals_in.p, ix.vals_sorted.p + ki * T,
+                                                         static_cast<unsigned int>(T), n_seqs, ix.off.p, ix.off.p + 1, 0, 64, s));
+        }
+        LCTY_HIP(hipStreamSynchronize(s));
+    }
+    LCTY_HIP(hipStreamSynchronize(s));
+    st.index_ms += now_ms() - t0;
+}
+
+struct Capture {                                               // lcty_align_backbone: every stage's output of the one task
+    std::vector<uint2> matches; std::vector<uint32_t> path, cigar; uint32_t chain = 0; int32_t score = 0; uint32_t dropped = 0;
+};
+struct PairOut { int32_t score; uint32_t best_ki, n_matches, nerrs; std::vector<uint32_t> cigar; };
+
+// the pairs [a, b) of refs / qrys through stages A to C; returns 0, or — the matches of the batch do not fit `budget` and the batch holds
+// more than one pair — the number of leading pairs whose matches do fit (at least 1): the caller comes back with those, so the counting
+// pass is repeated once, not once per halving
+uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, const uint32_t* refs, const uint32_t* qrys, uint64_t a, uint64_t b, uint32_t max_gap,
+               Lim top, uint64_t budget, PairOut* out, lcty_align_stats& st, Capture* cap) {
+    hipStream_t s = ctx->stream;
+    const uint32_t nk = static_cast<uint32_t>(ix.ks.size()), np = static_cast<uint32_t>(b - a), nt = np * nk;
+    double t0 = now_ms();
+    std::vector<Task> tasks(nt);
+    std::vector<uint64_t> slot_off(nt + 1, 0), fen_off(nt + 1, 0);
+    for (uint32_t p = 0; p < np; p++) for (uint32_t ki = 0; ki < nk; ki++) {
+        const uint32_t t = p * nk + ki, r = refs[a + p], q = qrys[a + p];
+        tasks[t] = Task{r, q, ki, ix.ks[ki]};
+        slot_off[t + 1] = slot_off[t] + (seq_off[r + 1] - seq_off[r]);
+        fen_off[t + 1] = fen_off[t] + (seq_off[q + 1] - seq_off[q]) + 2;
+    }
+    const uint64_t n_slots = slot_off[nt];
+    DevBuf<Task> d_tasks; DevBuf<uint64_t> d_slot, d_fen_off, d_mo, d_tm; DevBuf<uint32_t> d_cnt; DevBuf<uint8_t> d_tmp;
+    d_tasks.alloc(nt); d_slot.alloc(nt + 1); d_fen_off.alloc(nt + 1); d_cnt.alloc(n_slots + 1); d_mo.alloc(n_slots + 1); d_tm.alloc(nt + 1);
+    d_tasks.upload(tasks.data(), nt, s); d_slot.upload(slot_off.data(), nt + 1, s); d_fen_off.upload(fen_off.data(), nt + 1, s);
+    st.bytes_h2d += 16ull * nt + 16ull * (nt + 1);
+    d_cnt.zero(s);
+    hipLaunchKernelGGL(align_join_kernel<false>, dim3(nt), dim3(256), 0, s, d_tasks.p, d_slot.p, ix.seq.p, ix.off.p, ix.total, ix.keys_in.p, ix.keys_sorted.p,
+                       ix.vals_sorted.p, d_cnt.p, static_cast<const uint64_t*>(nullptr), static_cast<uint2*>(nullptr));
+    LCTY_HIP(hipGetLastError());
+    // 32-bit counts, 64-bit offsets: rocPRIM accumulates in the type of the operator applied to the initial value, uint64_t here
+    size_t bytes = 0;
+    LCTY_HIP(rocprim::exclusive_scan(nullptr, bytes, d_cnt.p, d_mo.p, uint64_t(0), n_slots + 1, rocprim::plus<uint64_t>(), s));
+    d_tmp.alloc(bytes + 16);
+    LCTY_HIP(rocprim::exclusive_scan(d_tmp.p, bytes, d_cnt.p, d_mo.p, uint64_t(0), n_slots + 1, rocprim::plus<uint64_t>(), s));
+    hipLaunchKernelGGL(align_task_offsets_kernel, dim3((nt + 256) / 256), dim3(256), 0, s, d_slot.p, d_mo.p, nt, d_tm.p);
+    LCTY_HIP(hipGetLastError());
+    std::vector<uint64_t> tm(nt + 1);
+    d_tm.download(tm.data(), nt + 1, s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    st.bytes_d2h += 8ull * (nt + 1);
+    const uint64_t n_m = tm[nt];
+    for (uint32_t t = 0; t < nt; t++)
+        if (tm[t + 1] - tm[t] > kMaxMatches)
+            fail(LCTY_ERR_UNSUPPORTED, "sequences %u and %u share %llu %u-mer matches: more than %llu per pair and k", tasks[t].ref, tasks[t].qry,
+                 static_cast<unsigned long long>(tm[t + 1] - tm[t]), tasks[t].k, static_cast<unsigned long long>(kMaxMatches));
+    if (np > 1 && n_m * 20 > budget) {
+        uint64_t fit = 1;
+        while (fit < np && tm[(fit + 1) * nk] * 20 <= budget) fit++;
+        st.match_ms += now_ms() - t0;
+        return fit;
+    }
+    DevBuf<uint2> d_m; DevBuf<uint32_t> d_dp, d_prev, d_path, d_chain, d_pstart; DevBuf<uint64_t> d_fen; DevBuf<unsigned long long> d_stats;
+    d_m.alloc(n_m + 1); d_dp.alloc(n_m + 1); d_prev.alloc(n_m + 1); d_path.alloc(n_m + 1); d_chain.alloc(nt); d_pstart.alloc(nt); d_fen.alloc(fen_off[nt]);
+    d_stats.alloc(ST_COUNT); d_stats.zero(s); d_fen.zero(s);
+    hipLaunchKernelGGL(align_join_kernel<true>, dim3(nt), dim3(256), 0, s, d_tasks.p, d_slot.p, ix.seq.p, ix.off.p, ix.total, ix.keys_in.p, ix.keys_sorted.p,
+                       ix.vals_sorted.p, static_cast<uint32_t*>(nullptr), d_mo.p, d_m.p);
+    LCTY_HIP(hipGetLastError());
+    LCTY_HIP(hipStreamSynchronize(s));
+    d_cnt.release(); d_mo.release(); d_tmp.release();
+    st.n_kmer_matches += n_m;
+    st.match_ms += now_ms() - t0; t0 = now_ms();
+
+    hipLaunchKernelGGL(align_chain_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, d_tasks.p, nt, ix.off.p, d_tm.p, d_m.p, d_dp.p, d_prev.p, d_path.p, d_fen_off.p,
+                       d_fen.p, d_chain.p, d_pstart.p, d_stats.p);
+    LCTY_HIP(hipGetLastError());
+    LCTY_HIP(hipStreamSynchronize(s));
+    d_fen.release(); d_dp.release(); d_prev.release();
+    st.chain_ms += now_ms() - t0; t0 = now_ms();
+
+    DevBuf<uint32_t> d_level, d_cap;
+    d_level.alloc(nt); d_cap.alloc(nt);
+    Levels lv;
+    for (uint32_t l = 0; l < kLevels; l++) lv.l[l] = Lim{std::min(kLevelDim[l], top.dim), std::min(kLevelCells[l], top.cells)};
+    hipLaunchKernelGGL(align_plan_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, d_tasks.p, nt, ix.off.p, d_tm.p, d_m.p, d_path.p, d_pstart.p, max_gap, top, lv,
+                       d_level.p, d_cap.p);
+    LCTY_HIP(hipGetLastError());
+    std::vector<uint32_t> level(nt), ccap(nt);
+    d_level.download(level.data(), nt, s); d_cap.download(ccap.data(), nt, s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    st.bytes_d2h += 8ull * nt;
+    std::vector<uint64_t> cig_off(nt + 1, 0);
+    for (uint32_t t = 0; t < nt; t++) cig_off[t + 1] = cig_off[t] + ccap[t];
+    DevBuf<uint64_t> d_cig_off; DevBuf<uint32_t> d_cig, d_words, d_drop, d_list; DevBuf<int32_t> d_score; DevBuf<uint8_t> d_scratch;
+    d_cig_off.alloc(nt + 1); d_cig.alloc(cig_off[nt] + 1); d_words.alloc(nt); d_drop.alloc(nt); d_score.alloc(nt); d_list.alloc(nt);
+    d_cig_off.upload(cig_off.data(), nt + 1, s);
+    st.bytes_h2d += 8ull * (nt + 1);
+    std::vector<uint32_t> list;
+    for (uint32_t l = 0; l < kLevels; l++) {
+        list.clear();
+        for (uint32_t t = 0; t < nt; t++) if (level[t] == l) list.push_back(t);
+        if (list.empty()) continue;
+        const Lim mine = lv.l[l];
+        const uint32_t lanes = static_cast<uint32_t>(std::min<size_t>(list.size(), kLevelLanes[l]));
+        d_scratch.ensure(lanes * lane_bytes(mine));
+        d_list.upload(list.data(), list.size(), s);
+        st.bytes_h2d += 4ull * list.size();
+        hipLaunchKernelGGL(align_fill_kernel, dim3((lanes + 63) / 64), dim3(64), 0, s, d_list.p, static_cast<uint32_t>(list.size()), lanes, d_tasks.p, ix.seq.p,
+                           ix.off.p, d_tm.p, d_m.p, d_path.p, d_pstart.p, max_gap, top, mine, d_scratch.p, d_cig_off.p, d_cig.p, d_score.p, d_words.p, d_drop.p,
+                           d_stats.p);
+        LCTY_HIP(hipGetLastError());
+        LCTY_HIP(hipStreamSynchronize(s));                                    // `list` is filled again
+        st.n_level[l] += list.size();
+    }
+    st.fill_ms += now_ms() - t0; t0 = now_ms();
+
+    DevBuf<PairRes> d_res; DevBuf<uint64_t> d_out_off; DevBuf<uint32_t> d_out;
+    d_res.alloc(np);
+    hipLaunchKernelGGL(align_select_kernel, dim3((np + 63) / 64), dim3(64), 0, s, np, nk, d_score.p, d_words.p, d_cig_off.p, d_cig.p, d_res.p);
+    LCTY_HIP(hipGetLastError());
+    std::vector<PairRes> res(np);
+    std::vector<unsigned long long> hs(ST_COUNT);
+    d_res.download(res.data(), np, s); d_stats.download(hs.data(), ST_COUNT, s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    if (hs[ST_OVERFLOW]) fail(LCTY_ERR_RUNTIME, "a CIGAR outgrew its bound (%llu tasks)", hs[ST_OVERFLOW]);
+    std::vector<uint64_t> out_off(np + 1, 0);
+    for (uint32_t p = 0; p < np; p++) out_off[p + 1] = out_off[p] + res[p].n_words;
+    d_out_off.alloc(np + 1); d_out.alloc(out_off[np] + 1);
+    d_out_off.upload(out_off.data(), np + 1, s);
+    hipLaunchKernelGGL(align_gather_kernel, dim3(np), dim3(64), 0, s, nk, d_res.p, d_cig_off.p, d_cig.p, d_out_off.p, d_out.p);
+    LCTY_HIP(hipGetLastError());
+    std::vector<uint32_t> words(out_off[np] + 1);
+    d_out.download(words.data(), out_off[np], s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    st.bytes_h2d += 8ull * (np + 1); st.bytes_d2h += sizeof(PairRes) * np + 4ull * out_off[np] + 8ull * ST_COUNT;
+    for (uint32_t p = 0; p < np; p++) {
+        out[a + p].score = res[p].score; out[a + p].best_ki = res[p].best_ki; out[a + p].n_matches = res[p].n_matches; out[a + p].nerrs = res[p].nerrs;
+        out[a + p].cigar.assign(words.begin() + out_off[p], words.begin() + out_off[p + 1]);
+    }
+    st.n_trivial += hs[ST_TRIVIAL]; st.n_simple += hs[ST_SIMPLE]; st.n_small_dp += hs[ST_SMALL]; st.n_general_dp += hs[ST_GENERAL];
+    st.n_dropped += hs[ST_DROPPED]; st.dp_cells += hs[ST_CELLS]; st.n_chain_points += hs[ST_POINTS];
+    if (cap) {                                                                // one pair, one k
+        cap->matches.resize(n_m); cap->path.resize(n_m);
+        uint32_t ps = 0;
+        if (n_m) { LCTY_HIP(hipMemcpyAsync(cap->matches.data(), d_m.p, 8 * n_m, hipMemcpyDeviceToHost, s)); d_path.download(cap->path.data(), n_m, s); }
+        d_chain.download(&cap->chain, 1, s); d_pstart.download(&ps, 1, s); d_drop.download(&cap->dropped, 1, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+        cap->path.erase(cap->path.begin(), cap->path.begin() + ps);
+        cap->cigar = out[a].cigar; cap->score = out[a].score;
+    }
+    st.select_ms += now_ms() - t0;
+    st.n_batches++;
+    return 0;
+}
+
+struct Prepared { std::vector<uint32_t> ks; Lim top; uint32_t max_gap; bool never; };
+Prepared validate(lcty_ctx* ctx, const lcty_align_params* p) {                // Params::validate, align.rs:67-89
+    if (!(p->div_k >= 1 && p->div_k <= 31)) fail(LCTY_ERR_INVALID_INPUT, "k-mer size (%u) must be between 1 and 31", p->div_k);
+    if (!(p->div_w >= 1 && p->div_w <= 63)) fail(LCTY_ERR_INVALID_INPUT, "Minimizer window (%u) must be between 1 and 63", p->div_w);
+    if (!(p->thresh_div >= 0.0 && p->thresh_div <= 1.0)) fail(LCTY_ERR_INVALID_INPUT, "Maximum divergence (%g) must be within [0, 1]", p->thresh_div);
+    if (p->mismatch != PEN_X || p->gap_open != PEN_O || p->gap_extend != PEN_E)
+        fail(LCTY_ERR_UNSUPPORTED, "penalties %d/%d/%d: the aligner is built for %d/%d/%d", p->mismatch, p->gap_open, p->gap_extend, PEN_X, PEN_O, PEN_E);
+    Prepared r;
+    r.never = p->thresh_div == 0.0;
+    if (!r.never) {
+        if (p->n_backbone_ks < 1 || p->n_backbone_ks > 8) fail(LCTY_ERR_INVALID_INPUT, "Expect at least one backbone k-mer (and at most 8)");
+        for (uint32_t i = 0; i < p->n_backbone_ks; i++) {
+            if (p->backbone_ks[i] < 5 || p->backbone_ks[i] > LCTY_ALIGN_MAX_K) fail(LCTY_ERR_INVALID_INPUT, "Backbone k-mer sizes must be between 5 and %u (%u)", LCTY_ALIGN_MAX_K, p->backbone_ks[i]);
+            r.ks.push_back(p->backbone_ks[i]);
+        }
+    }
+    r.max_gap = p->max_gap;
+    const int64_t cells = ctx->knob("align_dp_cells", kLevelCells[kLevels - 1]);
+    r.top = Lim{kLevelDim[kLevels - 1], static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(cells, 1), kLevelCells[kLevels - 1]))};
+    return r;
+}
+
+void check_seqs(uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off) {
+    if (!seqs || !seq_off || n_seqs < 2) fail(LCTY_ERR_INVALID_INPUT, "at least two sequences are needed");
+    for (uint32_t i = 0; i < n_seqs; i++) {
+        if (seq_off[i + 1] < seq_off[i]) fail(LCTY_ERR_INVALID_INPUT, "seq_off is not ascending at %u", i);
+        if (seq_off[i + 1] - seq_off[i] >= (1ull << 28)) fail(LCTY_ERR_UNSUPPORTED, "sequence %u is longer than 2^28 - 1 bases", i);
+    }
+}
+
+template <typename T> T* to_malloc(const T* p, uint64_t n) {
+    T* r = static_cast<T*>(malloc(std::max<uint64_t>(n, 1) * sizeof(T)));
+    if (!r) throw std::bad_alloc();
+    if (n) memcpy(r, p, n * sizeof(T));
+    return r;
+}
+
+std::string fmt_f(double v, int prec) {                                      // Rust's {:.N} of an f64
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v > 0 ? "inf" : "-inf";
+    char b[64];
+    snprintf(b, sizeof(b), "%.*f", prec, v);
+    return b;
+}
+}  // namespace
+
+extern "C" {
+
+void lcty_align_params_default(lcty_align_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->div_k = 15; p->div_w = 15; p->skip_div = 0; p->thresh_div = 1.0; p->against_div = 1.0;
+    p->backbone_ks[0] = 25; p->backbone_ks[1] = 51; p->backbone_ks[2] = 101; p->n_backbone_ks = 3;
+    p->max_gap = 10000; p->mismatch = PEN_X; p->gap_open = PEN_O; p->gap_extend = PEN_E;
+}
+
+int32_t lcty_align_all_pairs(uint32_t n_seqs, uint32_t* ref_id, uint32_t* query_id) {
+    return guarded([&] {
+        if (!ref_id || !query_id) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        uint64_t x = 0;
+        for (uint32_t i = 0; i < n_seqs; i++) for (uint32_t j = i + 1; j < n_seqs; j++) { ref_id[x] = i; query_id[x] = j; x++; }
+    });
+}
+
+void lcty_align_out_free(lcty_align_out* o) {
+    if (!o) return;
+    free(o->aligned); free(o->n_matches); free(o->aln_len); free(o->nerrs); free(o->score); free(o->best_k); free(o->um); free(o->md);
+    free(o->cigar_off); free(o->cigar);
+    memset(o, 0, sizeof(*o));
+}
+
+void lcty_align_backbone_out_free(lcty_align_backbone_out* o) {
+    if (!o) return;
+    free(o->matches); free(o->path); free(o->cigar);
+    memset(o, 0, sizeof(*o));
+}
+
+int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref_id,
+                              const uint32_t* query_id, const uint8_t* against, const lcty_align_params* params, lcty_align_out* out, lcty_align_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !params || !out || (n_pairs && (!ref_id || !query_id))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        memset(out, 0, sizeof(*out));
+        lcty_align_stats st{};
+        const double t_all = now_ms();
+        check_seqs(n_seqs, seqs, seq_off);
+        const Prepared pr = validate(ctx, params);
+        std::vector<std::pair<uint64_t, uint64_t>> seen(n_pairs);              // (smaller id << 32 | larger id, index)
+        for (uint64_t x = 0; x < n_pairs; x++) {
+            const uint32_t r = ref_id[x], q = query_id[x];
+            if (r >= n_seqs || q >= n_seqs) fail(LCTY_ERR_INVALID_INPUT, "pair %llu names sequence %u of %u", static_cast<unsigned long long>(x), std::max(r, q), n_seqs);
+            if (r == q) fail(LCTY_ERR_INVALID_INPUT, "pair %llu aligns sequence %u to itself", static_cast<unsigned long long>(x), r);
+            seen[x] = {(static_cast<uint64_t>(std::min(r, q)) << 32) | std::max(r, q), x};
+        }
+        std::sort(seen.begin(), seen.end());
+        for (uint64_t x = 1; x < n_pairs; x++)
+            if (seen[x].first == seen[x - 1].first)
+                fail(LCTY_ERR_INVALID_INPUT, "pair %llu (%u, %u) is given twice", static_cast<unsigned long long>(seen[x].second), ref_id[seen[x].second], query_id[seen[x].second]);
+        seen = {};
+        ctx->activate();
+        // divergences (process_pair 642-648): the triangle of lcty_db_divergences, rows i, then j > i
+        std::vector<uint32_t> um(n_pairs, 0); std::vector<double> md(n_pairs, 0.0); std::vector<uint8_t> aligned(n_pairs, 0);
+        double t0 = now_ms();
+        if (!params->skip_div) {
+            const uint64_t ntri = static_cast<uint64_t>(n_seqs) * (n_seqs - 1) / 2;
+            std::vector<uint32_t> uniq(ntri); std::vector<double> dv(ntri);
+            lcty_db_stats ds{};
+            const int32_t rc = lcty_db_divergences(ctx, n_seqs, seqs, seq_off, params->div_k, params->div_w, uniq.data(), dv.data(), nullptr, &ds);
+            if (rc != LCTY_OK) fail(rc, "%s", lcty_last_error());
+            st.bytes_h2d += ds.bytes_h2d; st.bytes_d2h += ds.bytes_d2h;
+            for (uint64_t x = 0; x < n_pairs; x++) {
+                const uint64_t i = std::min(ref_id[x], query_id[x]), j = std::max(ref_id[x], query_id[x]);
+                const uint64_t at = i * n_seqs - i * (i + 1) / 2 + (j - i - 1);
+                um[x] = uniq[at]; md[x] = dv[at];
+            }
+        }
+        st.div_ms = now_ms() - t0;
+        std::vector<uint32_t> refs, qrys; std::vector<uint64_t> which;
+        for (uint64_t x = 0; x < n_pairs; x++) {
+            const double lim = against && (against[ref_id[x]] || against[query_id[x]]) ? params->against_div : (pr.never ? -1.0 : params->thresh_div);
+            const bool take = params->skip_div || md[x] <= lim;
+            // thresh_div == 0 has cleared the ks (Params::validate): a pair that passes all the same — skip_div, or an `against` pair under
+            // against_div — ends align_multik without an alignment (align.rs:316)
+            if (take && pr.ks.empty()) fail(LCTY_ERR_RUNTIME, "No alignment found between sequences %u and %u", ref_id[x], query_id[x]);
+            if (take) { refs.push_back(ref_id[x]); qrys.push_back(query_id[x]); which.push_back(x); aligned[x] = 1; }
+        }
+        std::vector<PairOut> po(refs.size());
+        if (!refs.empty()) {
+            Index ix;
+            build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
+            size_t free_b = 0, total_b = 0;
+            LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
+            const uint64_t budget = std::max<uint64_t>(free_b / 4, 64ull << 20);
+            uint64_t max_len = 0;
+            for (uint32_t i = 0; i < n_seqs; i++) max_len = std::max(max_len, seq_off[i + 1] - seq_off[i]);
+            // a pair: per k 12 bytes a reference window (counts, offsets), 8 a query column (tree), and about 20 a match
+            uint64_t per_batch = std::max<uint64_t>(budget / (pr.ks.size() * (max_len + 2) * 40 + 1), 1);
+            const int64_t knob = ctx->knob("align_batch_pairs", 0);
+            if (knob > 0) per_batch = static_cast<uint64_t>(knob);
+            per_batch = std::min<uint64_t>(per_batch, (1u << 30) / pr.ks.size());
+            for (uint64_t at = 0; at < refs.size();) {
+                uint64_t n = std::min<uint64_t>(per_batch, refs.size() - at);
+                for (uint64_t fit; (fit = run_batch(ctx, ix, seq_off, refs.data(), qrys.data(), at, at + n, pr.max_gap, pr.top, budget, po.data(), st, nullptr)) != 0;) n = fit;
+                at += n;
+            }
+        }
+        std::vector<uint32_t> nm(n_pairs, 0), al(n_pairs, 0), ne(n_pairs, 0), bk(n_pairs, 0); std::vector<int32_t> sc(n_pairs, 0);
+        std::vector<uint64_t> coff(n_pairs + 1, 0);
+        for (uint64_t y = 0; y < which.size(); y++) coff[which[y] + 1] = po[y].cigar.size();
+        for (uint64_t x = 0; x < n_pairs; x++) coff[x + 1] += coff[x];
+        std::vector<uint32_t> words(coff[n_pairs]);
+        for (uint64_t y = 0; y < which.size(); y++) {
+            const uint64_t x = which[y];
+            nm[x] = po[y].n_matches; ne[x] = po[y].nerrs; al[x] = po[y].n_matches + po[y].nerrs; sc[x] = po[y].score; bk[x] = pr.ks[po[y].best_ki];
+            std::copy(po[y].cigar.begin(), po[y].cigar.end(), words.begin() + coff[x]);
+        }
+        out->n_pairs = n_pairs;
+        out->aligned = to_malloc(aligned.data(), n_pairs); out->n_matches = to_malloc(nm.data(), n_pairs); out->aln_len = to_malloc(al.data(), n_pairs);
+        out->nerrs = to_malloc(ne.data(), n_pairs); out->score = to_malloc(sc.data(), n_pairs); out->best_k = to_malloc(bk.data(), n_pairs);
+        out->um = to_malloc(um.data(), n_pairs); out->md = to_malloc(md.data(), n_pairs);
+        out->cigar_off = to_malloc(coff.data(), n_pairs + 1); out->cigar = to_malloc(words.data(), words.size());
+        st.n_aligned = which.size(); st.n_skipped = n_pairs - which.size();
+        st.total_ms = now_ms() - t_all;
+        if (stats) *stats = st;
+    });
+}
+
+int32_t lcty_align_backbone(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref, uint32_t query, uint32_t k,
+                            const lcty_align_params* params, lcty_align_backbone_out* out, lcty_align_stats* stats) {
+    return guarded([&] {
+        if (!ctx || !params || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        memset(out, 0, sizeof(*out));
+        lcty_align_stats st{};
+        const double t_all = now_ms();
+        check_seqs(n_seqs, seqs, seq_off);
+        lcty_align_params one = *params;
+        one.backbone_ks[0] = k; one.n_backbone_ks = 1;
+        if (one.thresh_div == 0.0) one.thresh_div = 1.0;
+        const Prepared pr = validate(ctx, &one);
+        if (ref >= n_seqs || query >= n_seqs || ref == query) fail(LCTY_ERR_INVALID_INPUT, "pair (%u, %u) of %u sequences", ref, query, n_seqs);
+        ctx->activate();
+        Index ix;
+        build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
+        PairOut po; Capture cap;
+        run_batch(ctx, ix, seq_off, &ref, &query, 0, 1, pr.max_gap, pr.top, ~0ull, &po, st, &cap);
+        out->n_matches = cap.matches.size();
+        out->matches = reinterpret_cast<uint32_t*>(to_malloc(cap.matches.data(), cap.matches.size()));
+        out->chain_score = cap.chain;
+        out->path_len = static_cast<uint32_t>(cap.path.size()); out->path = to_malloc(cap.path.data(), cap.path.size());
+        out->n_cigar = static_cast<uint32_t>(cap.cigar.size()); out->cigar = to_malloc(cap.cigar.data(), cap.cigar.size());
+        out->score = cap.score; out->n_dropped = cap.dropped;
+        st.n_aligned = 1;
+        st.total_ms = now_ms() - t_all;
+        if (stats) *stats = st;
+    });
+}
+
+int32_t lcty_paf_write_text(const lcty_align_params* params, uint32_t n_seqs, const char* names, const uint64_t* seq_off, uint64_t n_pairs,
+                            const uint32_t* ref_id, const uint32_t* query_id, const lcty_align_out* res, char* out, uint64_t cap, uint64_t* needed) {
+    return guarded([&] {
+        if (!params || !names || !seq_off || !res || !needed || (n_pairs && (!ref_id || !query_id))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (res->n_pairs != n_pairs) fail(LCTY_ERR_INVALID_INPUT, "the result holds %llu pairs, not %llu", static_cast<unsigned long long>(res->n_pairs), static_cast<unsigned long long>(n_pairs));
+        std::vector<const char*> nm(n_seqs);
+        const char* c = names;
+        for (uint32_t i = 0; i < n_seqs; i++) { nm[i] = c; c += strlen(c) + 1; }
+        std::string t;
+        // command/align.rs:385-387, after Params::validate (thresh_div 0 has become -1 and the ks are gone)
+        const bool never = params->thresh_div == 0.0;
+        std::string ks;
+        for (uint32_t i = 0; !never && i < params->n_backbone_ks && i < 8; i++) ks += (i ? "," : "") + std::to_string(params->backbone_ks[i]);
+        t += "# minimizers=" + std::to_string(params->div_k) + "," + std::to_string(params->div_w) + "; max_divergence=" + fmt_f(never ? -1.0 : params->thresh_div, 5) +
+             "; backbone-ks=" + ks + "; accuracy=9; max-gap=" + std::to_string(params->max_gap) + "\n";
+        static const char kOps[] = "MIDNSHP=X";
+        for (uint64_t x = 0; x < n_pairs; x++) {
+            const uint32_t r = ref_id[x], q = query_id[x];
+            if (r >= n_seqs || q >= n_seqs) fail(LCTY_ERR_INVALID_INPUT, "pair %llu names sequence %u of %u", static_cast<unsigned long long>(x), std::max(r, q), n_seqs);
+            const std::string lq = std::to_string(seq_off[q + 1] - seq_off[q]), lr = std::to_string(seq_off[r + 1] - seq_off[r]);
+            t += std::string(nm[q]) + "\t" + lq + "\t0\t" + lq + "\t+\t" + nm[r] + "\t" + lr + "\t0\t" + lr + "\t";
+            if (res->aligned[x]) {
+                const double dv = static_cast<double>(res->nerrs[x]) / static_cast<double>(res->aln_len[x]);
+                const double qv = std::isfinite(dv) ? -10.0 * std::log10(dv) : INFINITY;
+                t += std::to_string(res->n_matches[x]) + "\t" + std::to_string(res->aln_len[x]) + "\t255\tNM:i:" + std::to_string(res->nerrs[x]) + "\tAS:i:" +
+                     std::to_string(res->score[x]) + "\tdv:f:" + fmt_f(dv, 9) + "\tqv:f:" + fmt_f(qv, 6);
+            } else t += "0\t0\t255";
+            if (!params->skip_div) t += "\tum:i:" + std::to_string(res->um[x]) + "\tmd:f:" + fmt_f(res->md[x], 9);
+            if (res->aligned[x]) {
+                t += "\tcg:Z:";
+                for (uint64_t w = res->cigar_off[x]; w < res->cigar_off[x + 1]; w++) {
+                    const uint32_t op = res->cigar[w] & 15u;
+                    if (op > 8) fail(LCTY_ERR_INVALID_INPUT, "pair %llu: operation code %u", static_cast<unsigned long long>(x), op);
+                    t += std::to_string(res->cigar[w] >> 4) + kOps[op];
+                }
+            }
+            t += "\n";
+        }
+        *needed = t.size();
+        if (out) {
+            if (cap < t.size()) fail(LCTY_ERR_INVALID_INPUT, "buffer of %llu bytes, %llu needed", static_cast<unsigned long long>(cap), static_cast<unsigned long long>(t.size()));
+            memcpy(out, t.data(), t.size());
+        }
+    });
+}
+
+}  // extern "C"

@@ -234,6 +234,8 @@ __device__ inline int align_simple(const Seqs& S, uint32_t i1, uint32_t n, uint3
     return score;
 }
 
+// (The recurrence, tie rule and walk back of mode 0 without a match bonus are restated on plain bytes, without the step limit, in
+// lcty_align.hip, FillVisitor::gotoh — the haplotype-to-haplotype aligner: a change of the tie rule here must be made there too.)
 // Gap-affine alignment of reference [i1, i1+n) and query [j1, j1+m); mb = match bonus (0 global aligner, 2 semi-global one,
 // wfa.rs:194-197); mode 0 end to end, 1 free begin of both (LEFT), 2 free end of both (RIGHT). Writes the operations in
 // REVERSE order into sc.ops and returns the penalty, or DP_DROPPED (wfa.rs:262-266: status != 0).

@@ -103,6 +103,23 @@ def paf_read(path, names, with_distances=False):
     return (ents, dist) if with_distances else ents
 
 
+def paf_write(names, seq_off, ref_id, query_id, res, params=None):
+    """lcty_paf_write_text: the text of `haplotypes.paf` from the result dict of api.align_haplotypes (write_gz makes the .gz)."""
+    from . import api
+    p = params if params is not None else api.align_params()
+    off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    r = np.ascontiguousarray(ref_id, dtype=np.uint32); q = np.ascontiguousarray(query_id, dtype=np.uint32)
+    keep = {k: np.ascontiguousarray(res[k]) for k in ("aligned", "n_matches", "aln_len", "nerrs", "score", "best_k", "um", "md", "cigar_off")}
+    keep["cigar"] = np.ascontiguousarray(np.concatenate([res["cigar"], np.zeros(1, dtype=np.uint32)]), dtype=np.uint32)
+    o = cdefs.AlignOut()
+    o.n_pairs = len(r)
+    for k, a in keep.items():
+        setattr(o, k, a.ctypes.data)
+    blob = _names_blob(names)
+    return _sized(lambda b, c, n: lib().lcty_paf_write_text(C.byref(p), len(off) - 1, blob, off.ctypes.data, len(r), r.ctypes.data, q.ctypes.data,
+                                                            C.byref(o), b, c, n))
+
+
 def bg_from_json(text):
     """BgDistr::load -> (Bg, mean read length)."""
     if isinstance(text, str):

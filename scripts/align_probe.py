@@ -1,0 +1,96 @@
+"""Developer measurement: the pairwise haplotype alignments (lcty_align.hip) on synthetic haplotypes.
+   python3 scripts/align_probe.py ALLELES BASE_LEN [-D 0.01] [-k 25,51,101] [-g 10000] [--repeats 2] [--no-host] [--host-pairs N] [--batch-pairs N]
+One JSON line: per call of lcty_align_haplotypes over all pairs (the first call carries module loading and the first allocations) the
+per-stage milliseconds of lcty_align_stats (wall time per stage with the stream drained at its end: divergences, k-mer index, matches,
+chains, gap fill, best k + download), the counts of matches, chain points, stretches by route and DP cells, and as the comparison point
+the same backbone route in 16 host threads (scripts/align_probe_host.cpp, g++ -O3; scores only) over the pairs the device aligned —
+or over the first --host-pairs of them, the time then scaled to all — whose scores and best ks must equal the device's.
+Kernel times proper: run this under `rocprofv3 --kernel-trace --stats -- python3 scripts/align_probe.py ...`."""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+
+def host_lib():
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "align_probe_host.cpp")
+    out = os.path.join(tempfile.mkdtemp(prefix="align_probe_"), "libalign_probe_host.so")
+    subprocess.run(["g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", out], check=True)
+    L = C.CDLL(out)
+    L.align_probe_host.restype = C.c_double
+    L.align_probe_host.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    return L
+
+
+def host_route(seqs, off, ref, query, ks, max_gap, threads=16):
+    """(scores, best ks, ms of the pairs, ms of the k-mer lists) of the host-thread form"""
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.uint64)
+    ref = np.ascontiguousarray(ref, dtype=np.uint32); query = np.ascontiguousarray(query, dtype=np.uint32)
+    kk = np.ascontiguousarray(ks, dtype=np.uint32)
+    score = np.zeros(max(len(ref), 1), dtype=np.int32); best = np.zeros(max(len(ref), 1), dtype=np.uint32)
+    index_ms = C.c_double(0)
+    ms = host_lib().align_probe_host(len(off) - 1, seqs.ctypes.data, off.ctypes.data, len(ref), ref.ctypes.data, query.ctypes.data, len(kk), kk.ctypes.data,
+                                     max_gap, threads, score.ctypes.data, best.ctypes.data, C.byref(index_ms))
+    return score[:len(ref)], best[:len(ref)], ms, index_ms.value
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("alleles", type=int)
+    ap.add_argument("base_len", type=int)
+    ap.add_argument("-D", "--thresh-div", type=float, default=0.01)
+    ap.add_argument("-k", "--backbone-ks", default="25,51,101")
+    ap.add_argument("-g", "--max-gap", type=int, default=10000)
+    ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--host-pairs", type=int, default=0)
+    ap.add_argument("--batch-pairs", type=int, default=0)
+    a = ap.parse_args()
+    from locityper_amd import api, synth
+    ks = [int(x) for x in a.backbone_ks.split(",")]
+    t0 = time.perf_counter()
+    L = synth.SynthLocus(a.alleles, 16, base_len=a.base_len)
+    seqs, off = np.asarray(L.seqs, dtype=np.uint8), np.asarray(L.seq_off, dtype=np.uint64)
+    ref, query = api.align_all_pairs(a.alleles)
+    out = {"alleles": a.alleles, "base_len": a.base_len, "thresh_div": a.thresh_div, "backbone_ks": ks, "max_gap": a.max_gap, "pairs": len(ref),
+           "make_input_s": time.perf_counter() - t0, "calls": []}
+    ctx = api.Context(0)
+    if a.batch_pairs:
+        ctx.set_knob("align_batch_pairs", a.batch_pairs)
+    p = api.align_params(thresh_div=a.thresh_div, backbone_ks=ks, max_gap=a.max_gap)
+    res = None
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        res, st = api.align_haplotypes(ctx, seqs, off, ref, query, p)
+        st["wall_ms"] = 1e3 * (time.perf_counter() - t0)
+        out["calls"].append(st)
+    out["cigar_words"] = int(len(res["cigar"]))
+    if not a.no_host:
+        took = np.flatnonzero(res["aligned"])
+        n_all = len(took)
+        if a.host_pairs and a.host_pairs < n_all:
+            took = took[:a.host_pairs]
+        score, best, ms, index_ms = host_route(seqs, off, ref[took], query[took], ks, a.max_gap)
+        out["host_16_threads_pairs"] = int(len(took))
+        out["host_16_threads_index_ms"] = index_ms
+        out["host_16_threads_ms"] = ms
+        out["host_16_threads_ms_scaled_to_all"] = ms * n_all / max(len(took), 1)
+        out["host_scores_equal_device"] = bool(np.array_equal(score, res["score"][took]) and np.array_equal(best, res["best_k"][took]))
+        if not out["host_scores_equal_device"]:
+            bad = np.flatnonzero((score != res["score"][took]) | (best != res["best_k"][took]))
+            out["first_difference"] = {"pair": [int(ref[took[bad[0]]]), int(query[took[bad[0]]])], "host": [int(score[bad[0]]), int(best[bad[0]])],
+                                       "device": [int(res["score"][took[bad[0]]]), int(res["best_k"][took[bad[0]]])]}
+    print(json.dumps(out))
+    return 0 if out.get("host_scores_equal_device", True) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,174 @@
+"""CPU tier of the pairwise haplotype alignments: hand-derived answers for the transliteration (tests/pyref_align.py), the host-side
+PAF writer against the transliterated line byte for byte, the round trip through lcty_paf_read, and the fitness of the designed cases
+(tests/align_cases.py) the GPU tests rest on."""
+import numpy as np
+import pytest
+
+from locityper_amd import api, io
+from tests import align_cases as AC
+from tests import pyref_align as R
+
+
+# ---- 1. hand-derived answers ---------------------------------------------------------------------------------------------------------
+def test_matches_of_two_short_strings():
+    # 5-mers of ACGTACGTA: ACGTA@0, CGTAC@1, GTACG@2, TACGT@3, ACGTA@4; of TACGTAC: TACGT@0, ACGTA@1, CGTAC@2
+    assert R.kmer_matches(b"ACGTACGTA", b"TACGTAC", 5) == [(0, 1), (1, 2), (3, 0), (4, 1)]
+    assert R.kmer_matches(b"ACGTNACGTA", b"ACGTA", 5) == [(5, 0)]           # a window with an N is no k-mer
+    assert R.kmer_matches(b"ACG", b"ACGTACGT", 5) == []                      # shorter than k
+
+
+@pytest.mark.parametrize("matches,k,score,path", [
+    ([(0, 0), (1, 1), (2, 2)], 5, 7, [0, 1, 2]),                             # a diagonal run: 5, 6, 7
+    ([(0, 0), (5, 5)], 5, 10, [0, 1]),                                       # a jump that clears k on both sides
+    ([(0, 0), (10, 12)], 5, 10, [0, 1]),
+    ([(0, 0), (3, 4)], 5, 5, [0]),                                           # overlapping and off the diagonal: must not chain
+    ([(0, 0), (5, 4)], 5, 5, [0]),                                           # clears k in one coordinate only
+    ([(0, 0), (1, 1), (6, 7)], 5, 11, [0, 1, 2]),                            # run of two (6), then a jump (+ 5)
+    ([], 5, 0, []),
+])
+def test_chain_score_by_hand(matches, k, score, path):
+    s, p = R.lcskpp(matches, k)
+    assert s == score and p == path
+
+
+def _plain(seed=5, n=80):
+    return AC.rand_seq(np.random.default_rng(seed), n)
+
+
+def _aln(ref, query, k=25):
+    cig, score = R.align_from_backbone(ref, query, k, 10000)
+    return "".join(f"{ln}{op}" for op, ln in R.normalize(cig)), score
+
+
+def test_cigar_and_score_by_hand():
+    ref = _plain()
+    snp = lambda s, p: s[:p] + bytes([AC.B[(AC.B.index(s[p]) + 1) % 4]]) + s[p + 1:]
+    assert _aln(ref, ref) == ("80=", 0)
+    assert _aln(ref, snp(ref, 40)) == ("40=1X39=", -4)
+    assert _aln(ref, snp(ref, 3)) == ("3=1X76=", -4)                         # inside the first k bases
+    assert _aln(ref, snp(ref, 77)) == ("77=1X2=", -4)                        # inside the last k bases
+    assert _aln(ref, ref[:60]) == ("60=20D", -26)                            # the query is a prefix: a gap of 20 costs 6 + 20
+    assert _aln(ref[:60], ref) == ("60=20I", -26)
+    p = next(p for p in range(30, 50) if ref[p + 2] != ref[p - 1] and ref[p] != ref[p + 3])    # three bases that cannot slide
+    assert _aln(ref, ref[:p] + ref[p + 3:]) == (f"{p}=3D{80 - p - 3}=", -9)
+    assert _aln(ref[:p] + ref[p + 3:], ref) == (f"{p}=3I{80 - p - 3}=", -9)
+
+
+def test_full_dp_by_hand():
+    assert R.full_dp_score(b"ACGTACGT", b"ACGTACGT") == 0
+    assert R.full_dp_score(b"ACGTACGT", b"ACGAACGT") == -4
+    assert R.full_dp_score(b"ACGTACGT", b"ACGACGT") == -7                    # one gap of one base: 6 + 1
+    assert R.full_dp_score(b"ACGT", b"") == -10
+    assert R.full_dp_score(b"AAAA", b"TTTT") == -16                          # four mismatches (two gaps of four would cost 20)
+    assert R.full_dp_score(b"ANNA", b"ANNA") == 0                            # N equals N
+
+
+def test_all_pairs_order():
+    r, q = api.align_all_pairs(4)
+    assert list(zip(r.tolist(), q.tolist())) == [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
+
+
+# ---- 2. + 3. the PAF text ---------------------------------------------------------------------------------------------------------------
+def _hand_result():
+    """four pairs over three sequences: an alignment with errors, a skipped pair, an identical pair (dv = 0), a pair with a gap"""
+    names = ["hapA", "hapB", "hapC"]
+    lens = [100, 100, 97]
+    off = np.zeros(4, dtype=np.uint64); np.cumsum(lens, out=off[1:])
+    ref = np.array([0, 0, 1, 2], dtype=np.uint32); qry = np.array([1, 2, 0, 1], dtype=np.uint32)
+    items = [[("=", 40), ("X", 1), ("=", 59)], None, [("=", 100)], [("=", 50), ("I", 3), ("=", 47)]]
+    scores = [-4, 0, 0, -9]
+    um, md = [3, 250, 0, 7], [3 / 41, 0.5, 0.0, 7 / 39]
+    res = {k: np.zeros(4, dtype=dt) for k, dt in (("aligned", np.uint8), ("n_matches", np.uint32), ("aln_len", np.uint32), ("nerrs", np.uint32),
+                                                  ("score", np.int32), ("best_k", np.uint32), ("um", np.uint32), ("md", np.float64))}
+    coff, words = [0], []
+    for x, it in enumerate(items):
+        if it is not None:
+            nm, ne = R.counts(it)
+            res["aligned"][x] = 1; res["n_matches"][x] = nm; res["nerrs"][x] = ne; res["aln_len"][x] = nm + ne; res["score"][x] = scores[x]
+            res["best_k"][x] = 25
+            words += R.words(it).tolist()
+        res["um"][x] = um[x]; res["md"][x] = md[x]
+        coff.append(len(words))
+    res["cigar_off"] = np.array(coff, dtype=np.uint64); res["cigar"] = np.array(words, dtype=np.uint32)
+    return names, lens, off, ref, qry, items, scores, um, md, res
+
+
+@pytest.mark.parametrize("skip_div", [0, 1])
+def test_paf_text_equals_the_transliterated_lines(skip_div):
+    names, lens, off, ref, qry, items, scores, um, md, res = _hand_result()
+    p = api.align_params(skip_div=skip_div, thresh_div=0.25, max_gap=500, backbone_ks=[25, 51])
+    text = io.paf_write(names, off, ref, qry, res, p)
+    want = R.paf_header(15, 15, 0.25, (25, 51), 500)
+    for x in range(4):
+        r, q = int(ref[x]), int(qry[x])
+        want += R.paf_line(names[q], lens[q], names[r], lens[r], None if items[x] is None else (items[x], scores[x]),
+                           None if skip_div else (um[x], md[x]))
+    assert text == want.encode()
+    lines = text.decode().split("\n")
+    assert lines[0] == "# minimizers=15,15; max_divergence=0.25000; backbone-ks=25,51; accuracy=9; max-gap=500"
+    assert lines[1].startswith("hapB\t100\t0\t100\t+\thapA\t100\t0\t100\t99\t100\t255\tNM:i:1\tAS:i:-4\tdv:f:0.010000000\tqv:f:20.000000")
+    assert "\t0\t0\t255" in lines[2] and "cg:Z:" not in lines[2]
+    assert "dv:f:0.000000000\tqv:f:inf" in lines[3]
+    assert lines[1].endswith("cg:Z:40=1X59=")
+    assert ("um:i:3\tmd:f:0.073170732" in lines[1]) == (not skip_div)
+
+
+def test_paf_header_of_never_align():
+    names, lens, off, ref, qry, items, scores, um, md, res = _hand_result()
+    text = io.paf_write(names, off, ref[:0], qry[:0], {k: (v[:1] if k == "cigar_off" else v[:0]) for k, v in res.items()}, api.align_params(thresh_div=0.0))
+    assert text == R.paf_header(thresh_div=0.0).encode() == b"# minimizers=15,15; max_divergence=-1.00000; backbone-ks=; accuracy=9; max-gap=10000\n"
+
+
+def test_paf_round_trip(tmp_path):
+    names, lens, off, ref, qry, items, scores, um, md, res = _hand_result()
+    path = tmp_path / "haplotypes.paf.gz"
+    io.write_gz(path, io.paf_write(names, off, ref, qry, res))
+    ents = io.paf_read(path, names)
+    want = [(int(qry[x]), int(ref[x]), R.words(items[x]).tolist(), *R.counts(items[x])) for x in range(4) if items[x] is not None]
+    got = [(e[0], e[1], e[2].tolist(), e[3], e[4] - e[3]) for e in ents]
+    assert got == want
+
+
+# ---- 4. the designed cases are fit for purpose --------------------------------------------------------------------------------------------
+def _unique_pairs():
+    return [(c.name, r, q) for c in AC.cases() if c.unique for r, q in c.pairs]
+
+
+@pytest.mark.parametrize("name,ref,query", _unique_pairs())
+def test_unique_chain_cases_are_solved_optimally(name, ref, query):
+    items, score, _ = AC.reference_multik(name, ref, query)
+    assert score == R.calculate_score(items)
+    assert score == AC.optimum(name, ref, query), "the backbone route misses the full-DP optimum: no unique-chain case"
+    c = AC.by_name(name)
+    for k in c.ks:                                                          # every k alone reaches it too: best_k is the first one
+        m, chain, path = AC.reference(name, ref, query, k)
+        cig, s = R.align_from_path(c.seqs[ref], c.seqs[query], m, path, k, c.max_gap)
+        assert s == score
+
+
+def test_case_shapes():
+    for c in AC.cases():
+        assert 4 <= len(c.seqs) <= 12 and all(len(s) <= 3000 for s in c.seqs) and set(c.ks) <= {5, 25, 33, 51, 101}
+    assert any(len(s) < 25 for s in AC.by_name("short").seqs)
+    r, q = AC.by_name("unrelated").seqs[:2]
+    assert R.kmer_matches(r, q, 25) == []
+    assert len(AC.reference("tandem", 0, 1, 25)[0]) > 5000                   # quadratic matches
+
+
+# ---- 5. the host-thread form of the probe -----------------------------------------------------------------------------------------------
+def test_probe_host_route_equals_the_transliteration():
+    """scripts/align_probe_host.cpp (the comparison point of scripts/align_probe.py) on the unique-chain cases: score and best k of
+    align_multik; on every case its score is that of its own CIGAR-free route and never above the full-DP optimum."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("align_probe", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "align_probe.py"))
+    probe = importlib.util.module_from_spec(spec); spec.loader.exec_module(probe)
+    for c in AC.cases():
+        seqs, off = c.arrays()
+        ref = [p[0] for p in c.pairs]; query = [p[1] for p in c.pairs]
+        score, best, _, _ = probe.host_route(seqs, off, ref, query, c.ks, c.max_gap, threads=3)
+        for x, (r, q) in enumerate(c.pairs):
+            assert int(score[x]) <= AC.optimum(c.name, r, q)
+            if c.unique:
+                _, want, k = AC.reference_multik(c.name, r, q)
+                assert (int(score[x]), int(best[x])) == (want, k)
