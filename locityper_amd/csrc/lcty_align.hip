@@ -15,12 +15,12 @@
 //            (xfer::Seqs) and to its LDS-backed CIGAR, so the recurrence is restated here on plain bytes; its constants are shared.
 //   per pair the best k (first wins a tie) and the counts are taken on the device; only the winner's CIGAR is downloaded.
 #include "lcty_common.hpp"
+#include "lcty_seq.hpp"
 #include "lcty_transfer_device.hpp"
 
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 
 namespace {
@@ -36,17 +36,11 @@ constexpr uint32_t kLevelCells[kLevels] = {1u << 16, 1u << 22, 1u << 26};
 constexpr uint32_t kLevelLanes[kLevels] = {8192, 128, 8};        // lanes in flight (their scratch: 0.6 GB, 0.5 GB, 0.5 GB)
 enum : uint32_t { ST_TRIVIAL = 0, ST_SIMPLE, ST_SMALL, ST_GENERAL, ST_DROPPED, ST_CELLS, ST_POINTS, ST_OVERFLOW, ST_COUNT };
 
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 __host__ __device__ inline uint64_t powu(uint64_t b, uint64_t e) {
     uint64_t r = 1;
     for (; e; e >>= 1, b *= b) if (e & 1) r *= b;
     return r;
 }
-__device__ __forceinline__ uint32_t base_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
-__device__ __forceinline__ uint8_t base_norm(uint8_t c) { return base_code(c) < 4u ? c : static_cast<uint8_t>('N'); }
 
 // P[i] = sum over t < i of (code(t) + 1) * B^t, NP[i] = bytes outside ACGT before i; sequence s has len + 1 entries from off[s] + s on.
 // One block per sequence: a run of consecutive bases per thread, a scan over the threads' sums.
@@ -62,7 +56,7 @@ __global__ __launch_bounds__(256) void align_prefix_kernel(const uint8_t* __rest
     uint64_t sum = 0, pw = powu(kHashBase, lo);
     uint32_t nn = 0;
     for (uint64_t i = lo; i < hi; i++) {
-        uint32_t c = base_code(seq[base + i]);
+        uint32_t c = base_enc(seq[base + i]);
         if (c > 3u) { nn++; c = 0; }
         sum += (c + 1) * pw; pw *= kHashBase;
     }
@@ -78,7 +72,7 @@ __global__ __launch_bounds__(256) void align_prefix_kernel(const uint8_t* __rest
     pw = powu(kHashBase, lo);
     for (uint64_t i = lo; i < hi; i++) {
         P[pb + i] = acc; NP[pb + i] = n;
-        uint32_t c = base_code(seq[base + i]);
+        uint32_t c = base_enc(seq[base + i]);
         if (c > 3u) { n++; c = 0; }
         acc += (c + 1) * pw; pw *= kHashBase;
     }

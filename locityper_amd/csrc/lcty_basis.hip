@@ -22,9 +22,9 @@
 // tests/test_basis_host.py holds this against the walk itself (tests/pyref_basis.py), on designed CIGARs and on random ones.
 #include "lcty_common.hpp"
 #include "lcty_basis_search.hpp"
+#include "lcty_seq.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 
 namespace {
@@ -33,10 +33,6 @@ using namespace lcty;
 constexpr uint32_t kChunk = 1024;                          // CIGAR runs whose prefix sums one wavefront keeps in LDS (8 KB)
 constexpr uint32_t kPerLane = kChunk / 64;
 constexpr uint32_t kErrOp = 1u, kErrLen = 2u;
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // every row starts with the bit of its own contig (augment.rs:324-325)
 __global__ __launch_bounds__(256) void basis_init_kernel(const uint64_t* __restrict__ win_off, uint32_t words, uint32_t* __restrict__ bits) {
@@ -175,11 +171,6 @@ __global__ __launch_bounds__(64) void basis_windows_kernel(const uint32_t* __res
         const uint32_t edit = base_e - a_last + (g_last > gap_carry ? g_last - gap_carry : 0u);
         if (edit <= max_edit) atomicOr(row0 + uint64_t(t_last) * words, mask);
     }
-}
-
-__device__ inline uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-    return x;
 }
 
 // One wavefront per row: the row's hash (a sum over the words, so the order of the reduction does not matter), then linear probing in a

@@ -19,13 +19,13 @@
 
 #include <algorithm>
 #include <array>
-#include <chrono>
 #include <cmath>
 #include <map>
 #include <numeric>
 #include <vector>
 
 #include "lcty_common.hpp"
+#include "lcty_seq.hpp"
 #include "lcty_math.hpp"
 
 using namespace lcty;
@@ -344,7 +344,6 @@ struct Events {
     void rec(int i, hipStream_t s) { if (on) LCTY_HIP(hipEventRecord(ev[i], s)); }
     double ms(int a, int b) const { float t = 0.f; if (on) LCTY_HIP(hipEventElapsedTime(&t, ev[a], ev[b])); return t; }
 };
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 template <typename T> void put(T* dst, const std::vector<T>& src) { if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof(T)); }
 template <typename T> T* dev_copy(DevBuf<T>& d, const T* h, size_t n, hipStream_t s) { d.alloc(std::max<size_t>(n, 1)); d.upload(h, n, s); return d.p; }
@@ -384,7 +383,7 @@ int32_t lcty_bg_estimate(lcty_ctx* ctx, const lcty_bg_reads* reads, const uint8_
         if (k == 0 || k > 64 || padded_len < k) fail(LCTY_ERR_INVALID_INPUT, "k-mer size %u does not fit the padded sequence", k);
         for (uint32_t i = 0; i < padded_len; i++) {
             const uint8_t c = padded_seq[i];
-            if (c != 'A' && c != 'C' && c != 'G' && c != 'T') fail(LCTY_ERR_INVALID_INPUT, "Cannot count k-mers for sequence with Ns (position %u)", padded_start + i);
+            if (base_enc(c) > 3u) fail(LCTY_ERR_INVALID_INPUT, "Cannot count k-mers for sequence with Ns (position %u)", padded_start + i);
         }
         lcty_bg_reads_view v;
         if (lcty_bg_reads_view_get(reads, &v) != LCTY_OK) fail(LCTY_ERR_INVALID_INPUT, "bad reads handle");
@@ -408,7 +407,7 @@ int32_t lcty_bg_estimate(lcty_ctx* ctx, const lcty_bg_reads* reads, const uint8_
         std::vector<uint32_t> ref2(padded_len / 16 + 2, 0);
         for (uint32_t i = 0; i < padded_len; i++) {
             const uint8_t c = padded_seq[i];
-            ref2[i >> 4] |= static_cast<uint32_t>(c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3) << (2 * (i & 15));
+            ref2[i >> 4] |= base_enc(c) << (2 * (i & 15));                  // ACGT only: checked above
         }
         DevBuf<uint8_t> d_seq; DevBuf<uint16_t> d_cnt; DevBuf<uint32_t> d_gc, d_low, d_span, d_ref2;
         dev_copy(d_seq, padded_seq + off, region_len, s);

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -50,6 +51,9 @@ struct Error : std::runtime_error {
             ::lcty::fail(LCTY_ERR_RUNTIME, "HIP error %s at %s:%d: %s", hipGetErrorName(e__),   \
                          __FILE__, __LINE__, #expr);                                            \
     } while (0)
+
+// Wall clock in milliseconds, for the phase times of the *_stats structures and the traces of the developer build.
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Wraps a C-ABI body: exceptions -> status code + last-error string.
 template <typename F>

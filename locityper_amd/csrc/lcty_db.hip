@@ -17,37 +17,18 @@
 // device hash table of the distinct hashes (any bijection serves: the sums are integer, their order does not matter). Columns are
 // processed in chunks so that the bit matrix keeps to a fixed budget; the u32 overlap triangle accumulates over the chunks.
 #include "lcty_common.hpp"
+#include "lcty_seq.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <thread>
 #include <unordered_map>
 
 namespace {
 using namespace lcty;
 
-constexpr uint64_t UNDEF64 = ~0ull;                        // Kmer::UNDEF (kmers.rs:45)
 constexpr uint32_t kSortCap = 8192;                        // entries a workgroup sorts in LDS (64 KB); longer lists are sorted on the host
 constexpr uint32_t kTile = 1024;                           // k-mer end positions per workgroup of the clean-sequence minimizer kernel
 constexpr uint32_t kMaxW = 63;
-
-// the same mix as lcty_recruit.hip's fast_hash64 (Minimizer for u64, kmers.rs:93-103); kept apart so that recruitment's code is untouched
-__host__ __device__ inline uint64_t db_hash64(uint64_t x) {
-    x = ~x;
-    x ^= x >> 23;
-    x *= 0x2127599bf4325c37ull;
-    x ^= x >> 47;
-    return x;
-}
-
-// A 0, C 1, G 2, T 3; anything else (N, lower case: the reference matches the four capitals only) is 4
-__host__ __device__ inline uint32_t enc_base(uint8_t c) {
-    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-}
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // ---- minimizers -------------------------------------------------------------------------------------------------------------------------
 // flags[a] = 1: the sequence holds a base outside ACGT, or one of its k-mers hashes to UNDEF (one 64-bit value in 2^64 does): the
@@ -59,11 +40,11 @@ __global__ __launch_bounds__(256) void db_classify_kernel(const uint8_t* __restr
     const uint64_t len = seq_off[a + 1] - seq_off[a];
     bool bad = false;
     for (uint64_t p = uint64_t(blockIdx.y) * 256 + threadIdx.x; p < len; p += uint64_t(gridDim.y) * 256) {
-        if (enc_base(s[p]) > 3) { bad = true; break; }
+        if (base_enc(s[p]) > 3) { bad = true; break; }
         if (p + 1 >= k) {
             uint64_t km = 0;
-            for (uint32_t t = 0; t < k; t++) km = (km << 2) | (enc_base(s[p + 1 - k + t]) & 3);
-            if (db_hash64(km) == UNDEF64) { bad = true; break; }
+            for (uint32_t t = 0; t < k; t++) km = (km << 2) | (base_enc(s[p + 1 - k + t]) & 3);
+            if (fast_hash64(km) == UNDEF64) { bad = true; break; }
         }
     }
     if (bad) flags[a] = 1;
@@ -96,8 +77,8 @@ __global__ __launch_bounds__(256) void db_minim_fast_kernel(const uint8_t* __res
     if (threadIdx.x == 0) n_found = 0;
     for (int64_t q = lo + threadIdx.x; q <= hi; q += 256) {
         uint64_t km = 0;
-        for (uint32_t t = 0; t < k; t++) km = (km << 2) | enc_base(s[q + 1 - k + t]);
-        hs[q - lo] = db_hash64(km);
+        for (uint32_t t = 0; t < k; t++) km = (km << 2) | base_enc(s[q + 1 - k + t]);
+        hs[q - lo] = fast_hash64(km);
     }
     __syncthreads();
     for (int64_t p = p0 + threadIdx.x; p < p0 + kTile && p <= last; p += 256) {
@@ -115,8 +96,8 @@ __global__ __launch_bounds__(256) void db_minim_fast_kernel(const uint8_t* __res
     }
 }
 
-// The loop of kmers.rs:291-330 as written, one lane per sequence: a non-ACGT base encodes as 0 and sets first_kmer = i + k; hashes before
-// first_kmer are UNDEF; a window whose minimum is UNDEF moves first_window on by w - 1 (from its OLD value, not from i).
+// The loop of the reference as written (minimizers_as_written, lcty_seq.hpp: not canonical, k up to 32), one lane per sequence, the
+// ring of hashes in the lane's private memory.
 template <bool WRITE>
 __global__ __launch_bounds__(64) void db_minim_walk_kernel(const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ seq_off,
                                                            const uint32_t* __restrict__ list, uint32_t n_list, uint32_t k, uint32_t w,
@@ -127,36 +108,13 @@ __global__ __launch_bounds__(64) void db_minim_walk_kernel(const uint8_t* __rest
     const uint32_t a = list[t];
     const uint8_t* s = seqs + seq_off[a];
     const uint64_t len = seq_off[a + 1] - seq_off[a];
-    uint64_t hashes[64];
+    uint64_t hashes[64], m = 0;
     for (uint32_t q = 0; q < 64; q++) hashes[q] = UNDEF64;
-    const uint64_t mask = k == 32 ? ~0ull : (1ull << (2 * k)) - 1;
-    const uint64_t w_1 = w - 1;
-    uint64_t fw = 0, best_hash = UNDEF64, best_pos = 0, first_kmer = k - 1, first_window = k - 1 + w_1, m = 0;
-    int64_t last_pos = -1;
     uint64_t* dst = WRITE ? out + min_off[a] : nullptr;
-    for (uint64_t i = 0; i < len; i++) {
-        uint32_t e = enc_base(s[i]);
-        if (e > 3) { first_kmer = i + k; e = 0; }
-        fw = ((fw << 2) | e) & mask;
-        const uint64_t h = i < first_kmer ? UNDEF64 : db_hash64(fw);
-        hashes[i & 63] = h;
-        if (h < best_hash) { best_hash = h; best_pos = i; }
-        if (i < first_window) continue;
-        const uint64_t start = i - w_1;
-        if (best_pos < start) {
-            best_pos = start; best_hash = hashes[start & 63];                // find_min: the leftmost minimum of start..=i
-            for (uint64_t j = start + 1; j <= i; j++) {
-                const uint64_t v = hashes[j & 63];
-                if (v < best_hash) { best_pos = j; best_hash = v; }
-            }
-            if (best_hash == UNDEF64) { first_window += w_1; continue; }
-        }
-        if (int64_t(best_pos) > last_pos) {
-            last_pos = int64_t(best_pos);
-            if (WRITE) dst[m] = best_hash;
-            m++;
-        }
-    }
+    minimizers_as_written<false>(static_cast<uint32_t>(len), k, w,                // check_seqs: fewer than 2^31 bases
+        [&](uint32_t i) { return base_enc(s[i]); },
+        [&](uint32_t j) -> uint64_t& { return hashes[j & 63]; },
+        [&](uint32_t, uint64_t h, bool) { if (WRITE) dst[m] = h; m++; });
     cnt[a] = m;
 }
 
@@ -302,22 +260,13 @@ __global__ __launch_bounds__(256) void db_gram_kernel(const uint64_t* __restrict
 }
 
 // ---- off-target counts (k <= 31: 64-bit canonical k-mers; all-ones = a k-mer over a non-ACGT base, Kmer::UNDEF) -------------------------
-__device__ inline uint64_t canon_kmer(const uint8_t* s, uint64_t p, uint32_t k) {             // kmers::<_, CANONICAL>, kmers.rs:163-202, at start p
-    uint64_t fw = 0, rv = 0;
-    for (uint32_t t = 0; t < k; t++) {
-        const uint32_t e = enc_base(s[p + t]);
-        if (e > 3) return UNDEF64;
-        fw = (fw << 2) | e;
-        rv = (rv >> 2) | (uint64_t(3 - e) << (2 * k - 2));
-    }
-    return rv < fw ? rv : fw;
-}
+// the key of the tables is the value of canonical_kmer_ascii: min(fw, rv)
 __global__ __launch_bounds__(256) void db_ref_insert_kernel(const uint8_t* __restrict__ ref, uint64_t n_kmers, uint32_t k, unsigned long long* __restrict__ keys,
                                                             uint32_t* __restrict__ first, uint32_t* __restrict__ occ, uint64_t cap) {
     const uint64_t p = uint64_t(blockIdx.x) * 256 + threadIdx.x;
     if (p >= n_kmers) return;
-    const uint64_t km = canon_kmer(ref, p, k);
-    if (km == UNDEF64) return;                                                // the map's UNDEF entry is max_value whatever happens (counts.rs:198, 202)
+    uint64_t km;
+    if (!canonical_kmer_ascii(ref, p, k, &km)) return;                                              // the map's UNDEF entry is max_value whatever happens (counts.rs:198, 202)
     const uint64_t s = tab_insert(keys, cap, km);
     atomicMin(&first[s], static_cast<uint32_t>(p));
     atomicAdd(&occ[s], 1u);
@@ -338,9 +287,9 @@ __global__ __launch_bounds__(256) void db_offt_kernel(const uint8_t* __restrict_
     const uint8_t* s = seqs + seq_off[a];
     const uint64_t n = cnt_off[a + 1] - cnt_off[a];
     for (uint64_t p = uint64_t(blockIdx.y) * 256 + threadIdx.x; p < n; p += uint64_t(gridDim.y) * 256) {
-        const uint64_t km = canon_kmer(s, p, k);
+        uint64_t km;
         uint16_t v;
-        if (km == UNDEF64) v = static_cast<uint16_t>(max_value);
+        if (!canonical_kmer_ascii(s, p, k, &km)) v = static_cast<uint16_t>(max_value);
         else {
             const uint64_t slot = tab_find(keys, cap, km);
             v = slot <= cap ? value[slot] : counts[cnt_off[a] + p];
@@ -523,29 +472,18 @@ void divergences(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t*
     st.host_ms += now_ms() - t2;
 }
 
-struct U128Hash { size_t operator()(unsigned __int128 x) const { return size_t(db_hash64(uint64_t(x)) ^ (db_hash64(uint64_t(x >> 64)) * 31)); } };
+struct U128Hash { size_t operator()(unsigned __int128 x) const { return size_t(fast_hash64(uint64_t(x)) ^ (fast_hash64(uint64_t(x >> 64)) * 31)); } };
 
 // KmerCounts::off_target_counts for 32 <= k <= 63 on the host, in the closed form proved at off_target() below
 void off_target_host(uint32_t n, const uint8_t* seqs, const uint64_t* seq_off, const uint16_t* counts, const uint64_t* cnt_off, uint32_t k,
                      uint32_t max_value, const uint8_t* ref, uint64_t n_ref, const uint16_t* ref_counts, uint16_t* out, bool* negatives, unsigned n_thr) {
     typedef unsigned __int128 u128;
-    auto canon = [k](const uint8_t* s, uint64_t p, u128* km) {
-        u128 fw = 0, rv = 0;
-        for (uint32_t t = 0; t < k; t++) {
-            const uint32_t e = enc_base(s[p + t]);
-            if (e > 3) return false;
-            fw = (fw << 2) | e;
-            rv = (rv >> 2) | (u128(3 - e) << (2 * k - 2));
-        }
-        *km = rv < fw ? rv : fw;
-        return true;
-    };
     struct Ent { uint32_t first, occ; };
     std::unordered_map<u128, Ent, U128Hash> map;
     map.reserve(n_ref * 2);
     for (uint64_t p = 0; p < n_ref; p++) {
         u128 km;
-        if (!canon(ref, p, &km)) continue;
+        if (!canonical_kmer_ascii(ref, p, k, &km)) continue;                   // the key: min(fw, rv)
         auto it = map.find(km);
         if (it == map.end()) map.emplace(km, Ent{static_cast<uint32_t>(p), 1u}); else it->second.occ++;
     }
@@ -566,7 +504,7 @@ void off_target_host(uint32_t n, const uint8_t* seqs, const uint64_t* seq_off, c
                 for (uint64_t p = 0; p < m; p++) {
                     u128 km;
                     uint16_t v;
-                    if (!canon(s, p, &km)) v = static_cast<uint16_t>(max_value);
+                    if (!canonical_kmer_ascii(s, p, k, &km)) v = static_cast<uint16_t>(max_value);
                     else { auto it = val.find(km); v = it == val.end() ? counts[cnt_off[a] + p] : it->second; }
                     out[cnt_off[a] + p] = v;
                 }
@@ -673,7 +611,7 @@ uint64_t hash_bytes(const uint8_t* p, uint64_t n) {                            /
     uint64_t i = 0;
     for (; i + 8 <= n; i += 8) { uint64_t v; memcpy(&v, p + i, 8); h = (h ^ v) * 0x100000001b3ull; h ^= h >> 29; }
     for (; i < n; i++) h = (h ^ p[i]) * 0x100000001b3ull;
-    return db_hash64(h);
+    return fast_hash64(h);
 }
 
 std::vector<std::string> split_names(const char* names, uint32_t n) {

@@ -1,11 +1,12 @@
-// lcty_device.hpp — plain views passed by value to the gfx950 kernels, and the
-// device helpers shared between kernels (2-bit k-mer extraction, hash probing).
+// lcty_device.hpp — plain views passed by value to the gfx950 kernels, and the probes of the
+// UniqueKmers sets. The sequence primitives (base codes, hashes, k-mer extraction) are in lcty_seq.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "../../include/locityper_hip.h"
+#include "lcty_seq.hpp"
 
 namespace lcty {
 
@@ -13,7 +14,6 @@ constexpr int WAVE = 64;                       // CDNA4 wavefront
 // the pair-alignment arena of a scored batch: a wavefront of a large scoring launch reserves PA_CHUNK entries at a time
 // (lcty_score.hip); a batch that can hold such a launch gets an eighth more room and a chunk per wavefront (lcty_reads_create)
 constexpr uint32_t PA_CHUNK = 8192, PA_POOL_MIN_PAIRS = 32, PA_MAX_GRID = 256 * 16;
-constexpr uint64_t KSET_EMPTY = ~0ull;         // never a valid canonical k-mer for k <= 31
 
 // Device record of one PairAlignment (src/model/locs.rs:668-676), 24 B.
 struct PairAlnDev {
@@ -101,69 +101,10 @@ struct ReadsView {
     uint64_t park_stride;
 };
 
-__host__ __device__ inline uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
-
 #ifdef __HIPCC__
-// Canonical k-mer (src/seq/kmers.rs:192-196) of the window starting at base q of a mate whose
-// 2-bit stream starts at 64-bit word `w64` (mate offsets are multiples of 32 bases).
-// The stream is LSB-first: x = sum enc[q+t] << 2t, hence rv = ~x (masked) and fw = digit-reverse(x).
-__device__ inline uint64_t canonical_kmer_2bit(const uint64_t* w64, uint32_t q, uint32_t k) {
-    const uint32_t word = q >> 5, sh = (q & 31u) * 2u;
-    uint64_t x = w64[word] >> sh;
-    if (sh + 2u * k > 64u) x |= w64[word + 1] << (64u - sh);
-    const uint64_t mask = (1ull << (2u * k)) - 1ull;
-    x &= mask;
-    const uint64_t rv = (~x) & mask;
-    uint64_t y = __brevll(x);
-    y = ((y >> 1) & 0x5555555555555555ull) | ((y & 0x5555555555555555ull) << 1);
-    const uint64_t fw = y >> (64u - 2u * k);
-    return rv < fw ? rv : fw;
-}
-
-// any "not ACGT" base inside [q, q+k) of the mate's 1-bit stream starting at 32-bit word `nm`
-__device__ inline bool window_has_n(const uint32_t* nm, uint32_t q, uint32_t k) {
-    const uint32_t w = q >> 5, s = q & 31u;
-    uint32_t bits = nm[w] >> s;
-    if (s + k > 32u) bits |= nm[w + 1] << (32u - s);
-    return (bits & ((1u << k) - 1u)) != 0u;
-}
-
-// ---- k-mers of 32..63 bases (the reference keeps every k-mer of UniqueKmers in a u128, locs.rs:919-963): 128-bit keys as {lo, hi}
-// pairs, the set an open-addressing table of pairs built on the host (lcty_locus_create), free = {~0, ~0} ----
-struct Kmer128 { uint64_t lo, hi; };
+// ---- set probes. k-mers of 32..63 bases: the set is an open-addressing table of {lo, hi} pairs built on the host (lcty_locus_create),
+// free = {~0, ~0} ----
 __host__ __device__ inline uint64_t kmer128_hash(uint64_t lo, uint64_t hi) { return mix64(lo ^ mix64(hi ^ 0x9E3779B97F4A7C15ull)); }
-__device__ __forceinline__ uint64_t pair_reverse64(uint64_t x) {
-    const uint64_t y = __brevll(x);
-    return ((y >> 1) & 0x5555555555555555ull) | ((y & 0x5555555555555555ull) << 1);
-}
-// canonical k-mer of the window at base q, 32 <= k <= 63 (the 64-bit form above, on two words)
-__device__ inline Kmer128 canonical_kmer_2bit128(const uint64_t* w64, uint32_t q, uint32_t k) {
-    const uint32_t word = q >> 5, sh = (q & 31u) * 2u, last = (q + k - 1) >> 5;
-    const uint64_t a = w64[word], b = last > word ? w64[word + 1] : 0ull, c = last > word + 1 ? w64[word + 2] : 0ull;
-    uint64_t xlo = a, xhi = b;
-    if (sh) { xlo = (a >> sh) | (b << (64u - sh)); xhi = (b >> sh) | (c << (64u - sh)); }
-    const uint32_t hb = 2u * k - 64u;                                    // bits of the k-mer in the high word: 0..62
-    const uint64_t hmask = (1ull << hb) - 1ull;
-    xhi &= hmask;
-    const uint64_t rlo = ~xlo, rhi = (~xhi) & hmask;                      // the reverse complement's value
-    const uint64_t ylo = pair_reverse64(xhi), yhi = pair_reverse64(xlo); // the digits of x in reverse order, at the top of 128 bits
-    const uint32_t s = 128u - 2u * k;                                     // 2..64
-    const uint64_t flo = s == 64u ? yhi : (ylo >> s) | (yhi << (64u - s)), fhi = s == 64u ? 0ull : yhi >> s;
-    const bool rv_less = rhi < fhi || (rhi == fhi && rlo < flo);
-    return rv_less ? Kmer128{rlo, rhi} : Kmer128{flo, fhi};
-}
-// any "not ACGT" base inside [q, q+k), k <= 63
-__device__ inline bool window_has_n_wide(const uint32_t* nm, uint32_t q, uint32_t k) {
-    const uint32_t w = q >> 5, s = q & 31u, last = (q + k - 1) >> 5;
-    uint64_t bits = (static_cast<uint64_t>(nm[w]) | (last > w ? static_cast<uint64_t>(nm[w + 1]) << 32 : 0ull)) >> s;
-    if (last > w + 1) bits |= static_cast<uint64_t>(nm[w + 2]) << (64u - s);       // s > 0 here: three words only with an offset
-    return (bits & ((1ull << k) - 1ull)) != 0ull;
-}
 __device__ inline bool kset128_contains(const uint64_t* kset, uint64_t mask, Kmer128 key) {
     uint64_t slot = kmer128_hash(key.lo, key.hi) & mask;
     while (true) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "lcty_common.hpp"
+#include "lcty_seq.hpp"
 
 using namespace lcty;
 
@@ -179,11 +180,7 @@ void pack(lcty_fastx* f) {
             const std::string& s = f->recs[i * per + e].seq;
             const uint64_t o = f->mate_off[2 * i + e];
             for (size_t k = 0; k < s.size(); k++) {
-                uint32_t code = 0; bool other = false;
-                switch (s[k]) { case 'A': code = 0; break; case 'C': code = 1; break; case 'G': code = 2; break; case 'T': code = 3; break; default: other = true; }
-                const uint64_t at = o + k;
-                f->bases2[at >> 4] |= code << (2 * (at & 15));
-                if (other) f->nmask[at >> 5] |= 1u << (at & 31);
+                pack_base(f->bases2.data(), f->nmask.data(), o + k, static_cast<uint8_t>(s[k]));
             }
         }
 }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "lcty_common.hpp"
+#include "lcty_seq.hpp"
 
 using namespace lcty;
 
@@ -631,12 +632,7 @@ int32_t lcty_bam_read(const char* path, const char* const* names, uint32_t n_all
             T->bases2.resize(std::max<size_t>(T->bases2.size(), (words16 + 1) & ~1ull), 0);
             T->nmask.resize(std::max<size_t>(T->nmask.size(), words32), 0);
             for (uint32_t k = 0; k < l_seq; k++) {
-                const char c = NT16[(seq[k >> 1] >> ((~k & 1) << 2)) & 15];
-                const uint64_t at = base_at + k;
-                uint32_t code = 0; bool other = false;
-                switch (c) { case 'A': code = 0; break; case 'C': code = 1; break; case 'G': code = 2; break; case 'T': code = 3; break; default: other = true; }
-                T->bases2[at >> 4] |= code << (2 * (at & 15));
-                if (other) T->nmask[at >> 5] |= 1u << (at & 31);
+                pack_base(T->bases2.data(), T->nmask.data(), base_at + k, static_cast<uint8_t>(NT16[(seq[k >> 1] >> ((~k & 1) << 2)) & 15]));
             }
             T->quals.insert(T->quals.end(), qual, qual + l_seq);
             T->qual_off.push_back(T->quals.size());
@@ -1075,13 +1071,7 @@ int32_t lcty_bg_reads_load(const char* path, const char* contig, uint32_t start,
             const uint64_t next = (base_at + l_seq + 31) / 32 * 32;
             T->bases2.resize(next / 16 + 2, 0); T->nmask.resize(next / 32 + 1, 0);
             for (uint32_t k = 0; k < l_seq; k++) {
-                const uint64_t at = base_at + k;
-                uint32_t code = 0; bool other = false;
-                switch (NT16[(seq[k >> 1] >> ((~k & 1) << 2)) & 15]) {
-                    case 'A': code = 0; break; case 'C': code = 1; break; case 'G': code = 2; break; case 'T': code = 3; break; default: other = true;
-                }
-                T->bases2[at >> 4] |= code << (2 * (at & 15));
-                if (other) T->nmask[at >> 5] |= 1u << (at & 31);
+                pack_base(T->bases2.data(), T->nmask.data(), base_at + k, static_cast<uint8_t>(NT16[(seq[k >> 1] >> ((~k & 1) << 2)) & 15]));
             }
             T->seq_off.push_back(next);
             names.push_back(qname);

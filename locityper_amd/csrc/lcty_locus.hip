@@ -46,14 +46,7 @@ __global__ void kset_build_kernel(const uint8_t* __restrict__ seqs, const uint64
     uint64_t fw = 0, rv = 0;
     uint64_t reset = s + k - 1;
     for (uint64_t i = s; i < e + k - 1; i++) {
-        uint32_t enc;
-        switch (seq[i]) {
-            case 'A': enc = 0; break;
-            case 'C': enc = 1; break;
-            case 'G': enc = 2; break;
-            case 'T': enc = 3; break;
-            default: enc = 4;
-        }
+        const uint32_t enc = base_enc(seq[i]);
         if (enc == 4) {
             reset = i + k;
             if (i + 1 >= s + k && cnt[i + 1 - k] == 0) atomicOr(undef_flag, 1u);   // UNDEF enters the set (kmers.rs:184-190)
@@ -165,9 +158,7 @@ __global__ __launch_bounds__(64) void contig_info_kernel(const uint8_t* __restri
     for (uint32_t i = 0; i < neighb; i++) {
         const uint8_t b = seq[q + i];
         c_gc += (b == 'C' || b == 'G');
-        uint32_t enc;
-        switch (b) { case 'A': enc = 0; break; case 'C': enc = 1; break; case 'G': enc = 2; break; case 'T': enc = 3; break;
-                     default: enc = 4; }
+        const uint32_t enc = base_enc(b);
         if (enc == 4) { bad = ck; v = (v << 2) & mask; } else { v = ((v << 2) | enc) & mask; if (bad) bad--; }
         if (i + 1 >= ck) {
             if (bad) undef_seen = 1;
@@ -210,7 +201,6 @@ __global__ __launch_bounds__(64) void contig_info_slide_kernel(const uint8_t* __
     if (p0 >= n_pos) return;                                 // (no barrier below: every thread owns its column of `held`)
     const uint32_t p1 = min(n_pos, p0 + CI_SEG);
     const uint32_t mask = (1u << (2 * ck)) - 1u;
-    auto enc_of = [](uint8_t b) -> uint32_t { return b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u; };
     uint32_t c_gc = 0, v = 0, bad = 0, undef_cnt = 0, distinct = 0;
     auto enter = [&](uint32_t value, bool is_undef) {
         if (is_undef) undef_cnt++;
@@ -220,7 +210,7 @@ __global__ __launch_bounds__(64) void contig_info_slide_kernel(const uint8_t* __
     for (uint32_t i = 0; i < neighb; i++) {
         const uint8_t b = seq[p0 + i];
         c_gc += (b == 'C' || b == 'G');
-        const uint32_t enc = enc_of(b);
+        const uint32_t enc = base_enc(b);
         if (enc == 4) { bad = ck; v = (v << 2) & mask; } else { v = ((v << 2) | enc) & mask; if (bad) bad--; }
         if (i + 1 >= ck) enter(v, bad != 0);
     }
@@ -242,11 +232,11 @@ __global__ __launch_bounds__(64) void contig_info_slide_kernel(const uint8_t* __
         c_u -= cnt[p] == 0;
         // the ck-mer that started at p
         uint32_t lv = 0; bool lbad = false;
-        for (uint32_t j = 0; j < ck; j++) { const uint32_t e = enc_of(seq[p + j]); lbad |= e == 4; lv = (lv << 2) | (e & 3u); }
+        for (uint32_t j = 0; j < ck; j++) { const uint32_t e = base_enc(seq[p + j]); lbad |= e == 4; lv = (lv << 2) | (e & 3u); }
         if (lbad) undef_cnt--;
         else { uint16_t& h = held[(lv & mask) * 64 + tid]; if (--h == 0) distinct--; }
         // the ck-mer that ends at p + neighb
-        const uint32_t enc = enc_of(in_b);
+        const uint32_t enc = base_enc(in_b);
         if (enc == 4) { bad = ck; v = (v << 2) & mask; } else { v = ((v << 2) | enc) & mask; if (bad) bad--; }
         enter(v, bad != 0);
     }
@@ -445,8 +435,7 @@ int32_t lcty_locus_create(lcty_ctx* ctx, uint32_t n_alleles, const uint8_t* seqs
                 u128 fw = 0, rv = 0;
                 uint64_t reset = k - 1;
                 for (uint64_t i = 0; i < len; i++) {
-                    const uint8_t ch = seq[i];
-                    const uint32_t enc = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
+                    const uint32_t enc = base_enc(seq[i]);
                     if (enc == 4) {
                         reset = i + k;
                         if (i + 1 >= k && cnt[i + 1 - k] == 0) undef = true;         // UNDEF enters the set (kmers.rs:184-190)

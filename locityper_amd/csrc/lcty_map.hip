@@ -34,7 +34,6 @@
 // listed ones with gaps, one per lane; map_emit_kernel<WRITE> (one wavefront per read end, lane = candidate) runs twice: sizes,
 // then records, with a host prefix sum in between.
 #include <algorithm>
-#include <chrono>
 
 #include "lcty_map_internal.hpp"
 
@@ -113,7 +112,7 @@ __device__ void map_seed_one(const MapView& V, const uint64_t m, uint64_t* keys,
             if (!bad) {
                 read_fwd = fw <= rv;
                 const uint64_t canon = read_fwd ? fw : rv;
-                uint64_t h = map_hash(canon) & V.mask;
+                uint64_t h = fast_hash64(canon) & V.mask;
                 for (;;) {
                     const MapSlot s = V.table[h];
                     if (s.key == MAP_FREE) break;
@@ -205,7 +204,7 @@ __device__ void map_seed_one(const MapView& V, const uint64_t m, uint64_t* keys,
             if (!open || fresh > run) { run = fresh; run_s = i; open = true; }   // a stretch that starts here (an older start wins ties)
             const uint32_t src = strand ? L - 1 - i : i;
             const uint32_t e = strand ? 3u - base_at(V.bases2, off, src) : base_at(V.bases2, off, src);
-            run += !n_at(V.nmask, off, src) && enc_of(ref[diag + i]) == e ? V.match : -V.mismatch;
+            run += !n_at(V.nmask, off, src) && base_enc(ref[diag + i]) == e ? V.match : -V.mismatch;
             const int32_t total = run + (i + 1 == L ? V.end_bonus : 0);
             if (total > score) { score = total; s_best = run_s; e_best = i + 1; }
         }
@@ -274,7 +273,7 @@ __global__ __launch_bounds__(64) void map_gap_kernel(const MapView V) {
         const uint32_t span = L + 2 * static_cast<uint32_t>(B);
         for (uint32_t j = 0; j < span; j++) {
             const int64_t rp = diag - B + static_cast<int64_t>(j);
-            refw[j * 64 + lane] = rp >= 0 && rp < alen ? static_cast<uint8_t>(enc_of(ref[rp])) : 5u;
+            refw[j * 64 + lane] = rp >= 0 && rp < alen ? static_cast<uint8_t>(base_enc(ref[rp])) : 5u;
         }
         // the running row of M / deletion / insertion scores in registers: the loop over the band is unrolled to its full width
         // (a narrower band leaves the outer diagonals at "no alignment")
@@ -385,7 +384,7 @@ __device__ void map_emit_one(const MapView& V, const uint64_t m) {
         const uint32_t src = strand ? L - 1 - i : i;
         if (n_at(V.nmask, off, src)) return false;
         const uint32_t e = strand ? 3u - base_at(V.bases2, off, src) : base_at(V.bases2, off, src);
-        return enc_of(ref[diag + i]) == e;
+        return base_enc(ref[diag + i]) == e;
     };
     // ---- the primary record: best score, the smallest (allele, strand) on ties (the lanes are in that order)
     int32_t top = have ? score : INT32_MIN;
@@ -669,8 +668,8 @@ int32_t lcty_reads_map_append(lcty_reads* reads, const lcty_reads_host* chunk, c
         const uint64_t n = chunk->n_pairs;
         if (n == 0) return;
         const bool trace = reads->ctx->diag_knob("map_trace", 0) != 0;
-        const auto t_in = std::chrono::steady_clock::now();
-        auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count(); };
+        const double t_in = now_ms();
+        auto since = [&] { return now_ms() - t_in; };
         // the device buffers of the mapping (arenas of CIGAR words and chains, scratch of the kernels: tens of GB for long reads on many
         // alleles) stay with the context from chunk to chunk — a streaming loop does not allocate and release them per chunk — until the
         // solver stages take the memory back (lcty_ctx::release_transfer_scratch) or lcty_ctx_trim is called
@@ -688,10 +687,10 @@ int32_t lcty_reads_map_append(lcty_reads* reads, const lcty_reads_host* chunk, c
         lcty_reads_host h = *chunk;
         h.aln_off = aln_off.data(); h.cigar_off = cigar_off.data(); h.recs = nullptr; h.cigar = nullptr;
         DeviceRecords dev{X.d_recs.p, X.d_cigar.p, X.d_ob2.p, X.d_onm.p, X.nrec.data(), X.max_rec_cigar};
-        const auto t0 = std::chrono::steady_clock::now();
+        const double t0 = now_ms();
         const int32_t rc = reads_append_device(reads, &h, &dev);
         if (reads->ctx->diag_knob("map_trace", 0))
-            fprintf(stderr, "[lcty map] append of the mapped chunk: %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            fprintf(stderr, "[lcty map] append of the mapped chunk: %.3f ms\n", now_ms() - t0);
         if (rc != LCTY_OK) fail(rc, "%s", lcty_last_error());
     });
 }

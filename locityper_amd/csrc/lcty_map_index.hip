@@ -36,17 +36,10 @@ __global__ __launch_bounds__(256) void index_pairs_kernel(const uint8_t* __restr
         while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (win_off[mid] <= w) lo = mid; else hi = mid; }
         const uint32_t b = lo;
         const uint64_t i = w - win_off[b];
-        const uint8_t* s = seqs + seq_off[basis[b]] + i;
-        uint64_t fw = 0, rv = 0;
-        bool ok = true;
-        for (uint32_t j = 0; j < k; j++) {
-            const uint32_t e = enc_of(s[j]);
-            ok &= e < 4u;
-            fw = (fw << 2) | (e & 3u);
-            rv = (rv >> 2) | (static_cast<uint64_t>(3u - (e & 3u)) << (2 * k - 2));
-        }
-        const bool fwd = fw <= rv;
-        keys[w] = ok ? (fwd ? fw : rv) : MAP_FREE;
+        uint64_t kmer;
+        bool fwd;                                                    // fw <= rv: a palindrome's place counts as forward
+        const bool ok = canonical_kmer_ascii(seqs + seq_off[basis[b]], i, k, &kmer, &fwd);
+        keys[w] = ok ? kmer : MAP_FREE;
         places[w] = (static_cast<uint64_t>(b) << 33) | (i << 1) | (fwd ? 1ull : 0ull);
         bad = ok ? 0u : 1u;
     }
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(256) void index_insert_kernel(const uint64_t* __res
     if (r >= n_runs) return;
     const uint32_t start = run_start[r], end = r + 1 < n_runs ? run_start[r + 1] : n_valid;
     const uint64_t key = keys[start];
-    uint64_t h = map_hash(key) & mask;
+    uint64_t h = fast_hash64(key) & mask;
     for (;;) {
         const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[h].key), static_cast<unsigned long long>(MAP_FREE),
                                                  static_cast<unsigned long long>(key));

@@ -15,13 +15,7 @@ constexpr uint32_t MAP_MAX_BAND = 16;          // diagonals on either side in an
 constexpr uint32_t MAP_LONG_MAX_BASIS = 256;   // basis alleles on the long route
 constexpr uint32_t MAP_LONG_MAX_LEN = (1u << 20) - 1;
 
-struct MapSlot { uint64_t key; uint32_t start, count; };   // key ~0 = free
-constexpr uint64_t MAP_FREE = ~0ull;
-
-__host__ __device__ inline uint64_t map_hash(uint64_t x) {          // the mix of kmers.rs:93-103
-    x = ~x; x ^= x >> 23; x *= 0x2127599bf4325c37ull; x ^= x >> 47;
-    return x;
-}
+struct MapSlot { uint64_t key; uint32_t start, count; };   // key MAP_FREE = free; the slot of a k-mer starts at fast_hash64(key) & mask
 
 __device__ __forceinline__ uint32_t base_at(const uint32_t* b2, uint64_t off, uint32_t i) {
     const uint64_t p = off + i;
@@ -31,7 +25,6 @@ __device__ __forceinline__ bool n_at(const uint32_t* nm, uint64_t off, uint32_t 
     const uint64_t p = off + i;
     return (nm[p >> 5] >> (p & 31u)) & 1u;
 }
-__device__ __forceinline__ uint32_t enc_of(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
 
 struct MapIndex {
     DevBuf<MapSlot> table; DevBuf<uint64_t> entries; DevBuf<uint16_t> basis; DevBuf<uint32_t> scratch;

@@ -41,7 +41,6 @@
 // sides that differ by one gap only. map_long_emit_kernel<WRITE>, one wavefront per read end, runs twice: sizes, then records (host
 // prefix sums in between).
 #include <algorithm>
-#include <chrono>
 
 #include "lcty_map_internal.hpp"
 
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(64) void map_long_chain_kernel(const LongView V) {
                 if (!bad) {
                     read_fwd = fw <= rv;
                     const uint64_t canon = read_fwd ? fw : rv;
-                    uint64_t h = map_hash(canon) & V.mask;
+                    uint64_t h = fast_hash64(canon) & V.mask;
                     for (;;) {
                         const MapSlot sl = V.table[h];
                         if (sl.key == MAP_FREE) break;
@@ -239,7 +238,7 @@ struct Seqs {
     const uint8_t* ref; uint32_t alen; uint32_t strand;
     __device__ __forceinline__ uint32_t read_base(uint32_t q) const { return n_at(nm, off, q) ? 4u : base_at(b2, off, q); }
     __device__ __forceinline__ uint32_t allele_base(uint32_t t) const {
-        const uint32_t e = enc_of(strand ? ref[alen - 1 - t] : ref[t]);
+        const uint32_t e = base_enc(strand ? ref[alen - 1 - t] : ref[t]);
         return e == 4u ? 4u : (strand ? 3u - e : e);
     }
     __device__ __forceinline__ bool eq(uint32_t q, uint32_t t) const {
@@ -744,9 +743,9 @@ void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_ma
     const uint64_t nb = chunk->mate_off[n_mates];
     // lcty_ctx_set_knob "map_trace" 1: wall-clock marks of the phases of a call on stderr
     const bool trace = ctx->diag_knob("map_trace", 0) != 0;
-    const auto t_begin = std::chrono::steady_clock::now();
+    const double t_begin = now_ms();
     auto mark = [&](const char* what) {
-        if (trace) fprintf(stderr, "[lcty map] %8.3f ms %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), what);
+        if (trace) fprintf(stderr, "[lcty map] %8.3f ms %s\n", now_ms() - t_begin, what);
     };
     if (max_len > MAP_LONG_MAX_LEN) fail(LCTY_ERR_UNSUPPORTED, "read ends of up to %u bases (the longest here: %u)", MAP_LONG_MAX_LEN, max_len);
     if (params->chain_back == 0 || params->chain_back > 64) fail(LCTY_ERR_INVALID_INPUT, "chain_back %u: 1..64", params->chain_back);

@@ -1,6 +1,6 @@
 // lcty_recruit.hip — minimizer read recruitment: which loci does a read (pair) belong to?
 //   src/seq/recruit.rs (Params 43-105, MatchCount 236-367, TargetBuilder 663-756, Targets::recruit_* 848-996),
-//   src/seq/kmers.rs:93-103 (fasthash mix), 243-331 (canonical minimizers), src/math/frac.rs:50-93.
+//   src/math/frac.rs:50-93; the hash and the canonical minimizers of src/seq/kmers.rs are in lcty_seq.hpp.
 //
 // Targets are built on the host once (minimizers of the alleles, one entry per (minimizer, locus): direction bits, "rare");
 // the device holds an open-addressing table minimizer -> run of entries. recruit_kernel: one lane per read pair. A lane walks
@@ -19,17 +19,8 @@
 
 namespace lcty {
 
-constexpr uint64_t UNDEF64 = ~0ull;
 constexpr uint32_t MAX_LOCI_PER_READ = 8;
 constexpr uint32_t READ_LENGTH_THRESH = 500;       // recruit.rs:35
-
-__host__ __device__ inline uint64_t fast_hash64(uint64_t x) {      // kmers.rs:93-103
-    x = ~x;
-    x ^= x >> 23;
-    x *= 0x2127599bf4325c37ull;
-    x ^= x >> 47;
-    return x;
-}
 
 struct TableSlot { uint64_t key; uint32_t start, count; };      // key UNDEF64 = free (UNDEF is never a minimizer, kmers.rs:27-30)
 // entry: locus | direction << 24 (bit 0 backward, bit 1 forward) | rare << 26
@@ -60,10 +51,11 @@ struct Matches {
     uint32_t n;
 };
 
-// minimizers::<u64, _, CANONICAL> (kmers.rs:265-331) of one mate, as written there (ring of hashes, best position, rescan when the
-// best leaves the window, the first_kmer / first_window bookkeeping around bases that are not ACGT); calls
-// on_minimizer(hash, forward) for every minimizer; returns their number. The lanes of a wavefront rescan at different bases, so
-// this form runs its rescan loop at almost every base: it is kept for the mates that contain such bases (and as the definition).
+// The canonical minimizers of one mate as the reference writes them, from the packed words: the device form of minimizers_as_written
+// (lcty_seq.hpp, where the rules are explained), written out; see DESIGN.md 4.16. Ring of hashes in LDS
+// (slot j of this lane at ring[j * 64], V.ring slots), forward flags in a register; calls on_minimizer(hash, forward) for every
+// minimizer; returns their number. The lanes of a wavefront rescan at different bases, so this form runs its rescan loop at almost
+// every base: it is kept for the mates that contain such bases (and as the definition).
 template <typename F>
 __device__ inline uint32_t walk_minimizers(const RecruitView& V, const uint64_t* w64, const uint32_t* nm, uint32_t len, uint64_t* ring, F&& on_minimizer) {
     const uint32_t k = V.k, w = V.w, k_1 = k - 1, w_1 = w - 1, rmask = V.ring - 1;
@@ -93,7 +85,7 @@ __device__ inline uint32_t walk_minimizers(const RecruitView& V, const uint64_t*
         if (i < first_window) continue;
         const uint32_t start = i - w_1;
         if (best_pos < start) {
-            best_pos = start; best_hash = ring[(start & rmask) * 64];           // find_min (kmers.rs:243-258): leftmost minimum
+            best_pos = start; best_hash = ring[(start & rmask) * 64];           // find_min: leftmost minimum
             for (uint32_t j = start + 1; j <= i; j++) { const uint64_t v = ring[(j & rmask) * 64]; if (v < best_hash) { best_pos = j; best_hash = v; } }
             if (best_hash == UNDEF64) { first_window = first_window + w_1; continue; }
         }
@@ -104,6 +96,15 @@ __device__ inline uint32_t walk_minimizers(const RecruitView& V, const uint64_t*
         }
     }
     return total;
+}
+
+// the run of entries of a minimizer: its slot of the table, or none (count 0)
+__device__ __forceinline__ TableSlot find_minimizer(const RecruitView& V, uint64_t minim) {
+    uint64_t slot = mix64(minim) & V.table_mask;
+    TableSlot ts = V.table[slot];
+    while (ts.key != UNDEF64 && ts.key != minim) { slot = (slot + 1) & V.table_mask; ts = V.table[slot]; }
+    if (ts.key != minim) ts.count = 0;
+    return ts;
 }
 
 // The same minimizers for a mate made of A, C, G, T only, without data-dependent branches: with every hash defined, the best
@@ -197,10 +198,7 @@ __global__ __launch_bounds__(64) void recruit_kernel(const RecruitView V) {
         for (uint32_t j = 0; j < MAX_LOCI_PER_READ; j++) { M.locus[j] = 0xFFFFFFFFu; M.first[j] = 0; M.second[j] = 0; }
         bool overflow = false;
         auto probe = [&](uint64_t minim, bool forward, bool second) {
-            uint64_t slot = mix64(minim) & V.table_mask;
-            TableSlot ts = V.table[slot];
-            while (ts.key != UNDEF64 && ts.key != minim) { slot = (slot + 1) & V.table_mask; ts = V.table[slot]; }
-            if (ts.key != minim) return;
+            const TableSlot ts = find_minimizer(V, minim);
             for (uint32_t q = 0; q < ts.count; q++) {
                 const uint32_t e = V.entries[ts.start + q];
                 const uint32_t locus = e & 0xFFFFFFu, direction = (e >> 24) & 3u, rare = (e >> 26) & 1u;
@@ -406,10 +404,7 @@ __global__ __launch_bounds__(64) void recruit_single_kernel(const RecruitView V)
         for (uint32_t j = lane; j < total; j += 64) {
             const uint64_t minim = list_h[j];
             const bool forward = list_f[j] != 0;
-            uint64_t slot = mix64(minim) & V.table_mask;
-            TableSlot ts = V.table[slot];
-            while (ts.key != UNDEF64 && ts.key != minim) { slot = (slot + 1) & V.table_mask; ts = V.table[slot]; }
-            if (ts.key != minim) continue;
+            const TableSlot ts = find_minimizer(V, minim);
             for (uint32_t q = 0; q < ts.count; q++) {
                 const uint32_t e = V.entries[ts.start + q];
                 const uint32_t locus = e & 0xFFFFFFu, direction = (e >> 24) & 3u, rare = (e >> 26) & 1u;
@@ -453,11 +448,8 @@ __global__ __launch_bounds__(64) void recruit_single_kernel(const RecruitView V)
                         const uint64_t minim = list_h[j];
                         const bool forward = list_f[j] != 0;
                         int64_t add[2] = {0, 0};
-                        uint64_t slot = mix64(minim) & V.table_mask;
-                        TableSlot ts = V.table[slot];
-                        while (ts.key != UNDEF64 && ts.key != minim) { slot = (slot + 1) & V.table_mask; ts = V.table[slot]; }
-                        if (ts.key == minim)
-                            for (uint32_t q = 0; q < ts.count; q++) {
+                        const TableSlot ts = find_minimizer(V, minim);
+                        for (uint32_t q = 0; q < ts.count; q++) {
                                 const uint32_t e = V.entries[ts.start + q];
                                 if ((e & 0xFFFFFFu) != locus) continue;
                                 const uint32_t direction = (e >> 24) & 3u, x = 1u + ((e >> 26) & 1u) * 3u;           // SUBSUM_PENALTY + rare * SUBSUM_BONUS
@@ -513,40 +505,12 @@ namespace {
 // minimizers::<u64, _, CANONICAL> on the host (ASCII input), with positions: TargetBuilder::add needs them
 void host_minimizers(const uint8_t* seq, size_t n, uint32_t k, uint32_t w, std::vector<uint32_t>& pos, std::vector<uint64_t>& hs, std::vector<uint8_t>& fwv) {
     pos.clear(); hs.clear(); fwv.clear();
-    const uint64_t mask = (1ull << (2 * k)) - 1;
-    const uint32_t rv_shift = 2 * k - 2, k_1 = k - 1, w_1 = w - 1;
-    uint64_t fw_kmer = 0, rv_kmer = 0, hashes[64]; uint8_t forward[64];
-    for (int i = 0; i < 64; i++) { hashes[i] = UNDEF64; forward[i] = 1; }
-    int64_t last_pos = -1; uint32_t best_pos = 0; uint64_t best_hash = UNDEF64;
-    uint32_t first_kmer = k_1, first_window = k_1 + w_1;
-    for (size_t ii = 0; ii < n; ii++) {
-        const uint32_t i = static_cast<uint32_t>(ii);
-        uint64_t fe = 0, re = 0;
-        switch (seq[ii]) {
-            case 'A': fe = 0; re = 3; break;
-            case 'C': fe = 1; re = 2; break;
-            case 'G': fe = 2; re = 1; break;
-            case 'T': fe = 3; re = 0; break;
-            default: first_kmer = i + k;
-        }
-        fw_kmer = ((fw_kmer << 2) | fe) & mask;
-        rv_kmer = (rv_kmer >> 2) | (re << rv_shift);
-        const bool fwd = !(rv_kmer < fw_kmer);
-        const uint64_t h = i < first_kmer ? UNDEF64 : fast_hash64(fwd ? fw_kmer : rv_kmer);
-        hashes[i & 63] = h; forward[i & 63] = fwd;
-        if (h < best_hash) { best_hash = h; best_pos = i; }
-        if (i < first_window) continue;
-        const uint32_t start = i - w_1;
-        if (best_pos < start) {
-            best_pos = start; best_hash = hashes[start & 63];
-            for (uint32_t j = start + 1; j <= i; j++) if (hashes[j & 63] < best_hash) { best_pos = j; best_hash = hashes[j & 63]; }
-            if (best_hash == UNDEF64) { first_window = first_window + w_1; continue; }
-        }
-        if (static_cast<int64_t>(best_pos) > last_pos) {
-            last_pos = best_pos;
-            pos.push_back(best_pos - k_1); hs.push_back(best_hash); fwv.push_back(forward[best_pos & 63]);
-        }
-    }
+    uint64_t hashes[64];
+    for (int i = 0; i < 64; i++) hashes[i] = UNDEF64;
+    minimizers_as_written<true>(static_cast<uint32_t>(n), k, w,                      // n < 2^31: lcty_targets_add_locus
+        [&](uint32_t i) { return base_enc(seq[i]); },
+        [&](uint32_t j) -> uint64_t& { return hashes[j & 63]; },
+        [&](uint32_t p, uint64_t h, bool fw) { pos.push_back(p); hs.push_back(h); fwv.push_back(fw); });
 }
 
 // Fraction::<u16>::approximate (frac.rs:50-76)
@@ -613,6 +577,7 @@ int32_t lcty_targets_add_locus(lcty_targets* t, uint32_t n_alleles, const uint8_
         std::vector<uint32_t> pos; std::vector<uint64_t> hs; std::vector<uint8_t> fw;
         for (uint32_t a = 0; a < n_alleles; a++) {
             const size_t len = seq_off[a + 1] - seq_off[a], n_counts = cnt_off[a + 1] - cnt_off[a];
+            if (len >= (1ull << 31)) fail(LCTY_ERR_UNSUPPORTED, "an allele of more than 2^31 - 1 bases");      // positions are u32 in the walk, as in kmers.rs
             if ((len + 1 > base_k ? len + 1 - base_k : 0) != n_counts) fail(LCTY_ERR_INVALID_DATA, "Sequence and k-mer lengths do not match");   // recruit.rs:703
             const uint16_t* cnt = counts + cnt_off[a];
             host_minimizers(seqs + seq_off[a], len, mk, t->prm.minimizer_w, pos, hs, fw);

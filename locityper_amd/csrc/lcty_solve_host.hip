@@ -4,7 +4,6 @@
 // comparison (K15) and the C ABI of all of it. The kernels and their launchers are in lcty_solve_kernels.hip.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <exception>
 #include <memory>
@@ -234,12 +233,12 @@ struct StageRunner {
                                   used, sum[6] / used, sum[7] / std::max(sum[6], 1.0), sum[8] / used, sum[9] / used, sum[0] / used, sum[1] / used, sum[2] / used, sum[3] / used, sum[4] / used, sum[5] / used);
             }
             if (ctx->diag_knob("queue_trace", 0)) fprintf(stderr, "[lcty queue] %.3f ms batch %p annealing launched (lane %u)\n",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), static_cast<const void*>(reads), lane);
+                now_ms(), static_cast<const void*>(reads), lane);
             return;
         }
         if (lane == 0) announce_greedy();
         if (ctx->diag_knob("queue_trace", 0)) fprintf(stderr, "[lcty queue] %.3f ms batch %p greedy about to launch (lane %u)\n",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), static_cast<const void*>(reads), lane);
+            now_ms(), static_cast<const void*>(reads), lane);
         launch_greedy_chains(ctx, V, nch, stream, ws);
     }
 
@@ -876,7 +875,7 @@ struct LocusRun {
     // lcty_ctx_set_knob "queue_trace" 1: wall-clock marks of the phases of a locus on stderr (where does a step of the queue go?)
     void mark(const char* what) const {
         if (!reads || reads->ctx->diag_knob("queue_trace", 0) == 0) return;
-        const double t = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        const double t = now_ms();
         fprintf(stderr, "[lcty queue] %.3f ms batch %p %s\n", t, static_cast<const void*>(reads), what);
     }
 

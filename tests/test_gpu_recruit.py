@@ -6,7 +6,7 @@ from locityper_amd import _lib, api, cdefs
 from locityper_amd.cdefs import ReadsChunk
 from tests import oracle_ffi as O
 from tests.helpers import noisy_read
-from tests.test_oracle_recruit import _loci, revcomp
+from tests.test_oracle_recruit import _loci, _loci_with_other_bases, revcomp
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +71,45 @@ def test_read_pairs_and_single_reads_match_oracle(gpu_ctx, over):
     cnt, out = gt.recruit(ch, paired=False)
     for i, pr in enumerate(pairs):
         assert list(out[i, :cnt[i]]) == ot.recruit(pr["seq1"].encode()), (i, over)
+
+
+def _pairs_of_other_bases(loci, seed):
+    """200 read pairs of 150 bases copied from the alleles (every third with three substitutions); every tenth pair starts inside or
+    just before the run of N of loci[1][1], so that a mate crosses it."""
+    rng = np.random.default_rng(seed)
+    pairs = []
+    for i in range(200):
+        if i % 10 == 0: li, ai, p = 1, 1, int(rng.integers(560, 720))
+        else: li, ai, p = int(rng.integers(0, 3)), int(rng.integers(0, 3)), int(rng.integers(0, 2000 - 450))
+        al = loci[li][ai]
+        r1, r2 = bytearray(al[p:p + 150]), bytearray(al[p + 300:p + 450])
+        if i % 3 == 1:
+            for r in (r1, r2):
+                for q in rng.integers(0, 150, 3): r[int(q)] = b"ACGT"[int(rng.integers(0, 4))]
+        r1, r2 = bytes(r1), revcomp(bytes(r2))
+        if i % 2: r1, r2 = revcomp(r1), revcomp(r2)
+        pairs.append({"seq1": r1.decode(), "seq2": r2.decode(), "recs": []})
+    return pairs
+
+
+@pytest.mark.parametrize("over", [dict(), dict(minimizer_k=11, minimizer_w=20, match_frac=0.3), dict(minimizer_k=27, minimizer_w=5, match_frac=0.7)])
+def test_alleles_and_reads_with_other_bases_match_oracle(gpu_ctx, over):
+    """Targets made from alleles that start with N, hold a run of N longer than w, a lower-case stretch and an R (the host walk of
+    lcty_targets_add_locus), and reads drawn from them (the device walk as written): sets of loci as the oracle's, read by read."""
+    loci = _loci_with_other_bases(np.random.default_rng(41))
+    gt, ot = _both(gpu_ctx, loci, **over)                                    # asserts the number of distinct minimizers
+    pairs = _pairs_of_other_bases(loci, 43)
+    assert sum("N" in p["seq1"] or "N" in p["seq2"] for p in pairs) >= 10
+    ch = ReadsChunk.from_pairs(pairs)
+    for paired in (True, False):
+        cnt, out = gt.recruit(ch, paired=paired)
+        n_rec = 0
+        for i, pr in enumerate(pairs):
+            exp = ot.recruit(pr["seq1"].encode(), pr["seq2"].encode()) if paired else ot.recruit(pr["seq1"].encode())
+            assert list(out[i, :cnt[i]]) == exp, (i, paired, over)
+            n_rec += bool(exp)
+        assert n_rec >= 1, (paired, over)
+    gt.close()
 
 
 def test_edges_and_misuse(gpu_ctx):

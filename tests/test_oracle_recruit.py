@@ -84,6 +84,28 @@ def _targets(loci, base_k=25, **kw):
     return ot, pt
 
 
+def _loci_with_other_bases(rng):
+    """Three loci of three alleles of 2 000 bases; one allele starts with N, one holds a run of N longer than every w of the tests
+    (25), one a lower-case stretch and an R: the bases that move first_kmer and first_window in the walk of kmers.rs:291-330."""
+    loci = _loci(rng, n_loci=3, n_alleles=3, length=2000)
+    a = loci[0][0]; loci[0][0] = b"N" + a[1:]
+    a = loci[1][1]; loci[1][1] = a[:700] + b"N" * 25 + a[725:]
+    a = loci[2][2]; loci[2][2] = a[:300] + a[300:340].lower() + a[340:900] + b"R" + a[901:]
+    assert all(len(al) == 2000 for alleles in loci for al in alleles)
+    return loci
+
+
+def test_targets_of_alleles_with_other_bases_match_the_transliteration():
+    rng = np.random.default_rng(41)
+    loci = _loci_with_other_bases(rng)
+    clean = [[bytes(al).upper().replace(b"N", b"A").replace(b"R", b"A") for al in alleles] for alleles in loci]
+    for kw in (dict(k=15, w=10, match_frac=0.5), dict(k=27, w=5, match_frac=0.7, thresh_kmer_count=50), dict(k=11, w=20, match_frac=0.3)):
+        ot, pt = _targets(loci, **kw)
+        exp = sorted((m, l, d, r) for m, v in pt.minim_to_loci.items() for l, d, r in v)
+        assert ot.entries() == exp, kw
+        assert exp != _targets(clean, **kw)[0].entries()                     # the other bases do change the entries
+
+
 def test_targets_and_recruitment_match_the_transliteration():
     rng = np.random.default_rng(21)
     loci = _loci(rng)
