@@ -8,15 +8,14 @@
 //            (pos1, pos2) because a reference position writes its own run in ascending pos2.
 //   stage B  per (pair, k): LCSk++ (Pavetic, Zuzic, Sikic 2014; rust-bio's bio::alignment::sparse::lcskpp): one lane per task,
 //            a prefix-maximum (Fenwick) tree over the query coordinate, a binary search for the diagonal predecessor
-//   stage C  per (pair, k): the walk of align_from_backbone with smart_align; the exact aligner is the Gotoh recurrence of
-//            lcty_transfer_device.hpp (same penalties, same tie rule: walking back from the end, diagonal before deletion before
-//            insertion, a gap is extended before it is opened) WITHOUT that header's step limit, which belongs to accuracy level 6:
-//            `locityper align` runs level 9, no limit. The header's functions themselves are bound to the packed read of a transfer
-//            (xfer::Seqs) and to its LDS-backed CIGAR, so the recurrence is restated here on plain bytes; its constants are shared.
+//   stage C  per (pair, k): the walk of align_from_backbone with smart_align; routing, align_simple and the exact aligner's cell,
+//            tie rule and walk back are those of lcty_gotoh.hpp, which alignment recovery (lcty_transfer_device.hpp) calls too; here
+//            on plain bytes and WITHOUT recovery's step limit, which belongs to accuracy level 6: `locityper align` runs level 9.
 //   per pair the best k (first wins a tie) and the counts are taken on the device; only the winner's CIGAR is downloaded.
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
-#include "lcty_transfer_device.hpp"
+#include "lcty_gotoh.hpp"
+#include "lcty_transfer_device.hpp"                 // xfer::DP_SMALL, the size class of the statistics
 
 #include <rocprim/rocprim.hpp>
 
@@ -25,7 +24,7 @@
 
 namespace {
 using namespace lcty;
-using xfer::OP_I; using xfer::OP_D; using xfer::OP_EQ; using xfer::OP_X; using xfer::PEN_X; using xfer::PEN_O; using xfer::PEN_E; using xfer::INF32;
+using gotoh::OP_I; using gotoh::OP_D; using gotoh::OP_EQ; using gotoh::OP_X; using gotoh::PEN_X; using gotoh::PEN_O; using gotoh::PEN_E; using gotoh::INF32;
 
 constexpr uint64_t kHashBase = 0x9E3779B97F4A7C15ull;          // odd: invertible modulo 2^64
 constexpr uint64_t kNoKey = ~0ull;                               // key of a window that is not a k-mer (sorts behind every hash)
@@ -204,7 +203,7 @@ struct Lim { uint32_t dim, cells; };                            // what the exac
 __host__ __device__ inline bool lim_takes(const Lim& l, uint32_t n, uint32_t m) {
     return n <= l.dim && m <= l.dim && (static_cast<uint64_t>(n) + 1) * (static_cast<uint64_t>(m) + 1) <= l.cells;
 }
-__host__ __device__ inline size_t lane_bytes(const Lim& l) { return (2 * (static_cast<size_t>(l.dim) + 1) * 12 + l.cells + 15) & ~size_t(15); }
+__host__ __device__ inline size_t lane_bytes(const Lim& l) { return (2 * (static_cast<size_t>(l.dim) + 1) * sizeof(gotoh::Cell) + l.cells + 15) & ~size_t(15); }
 
 struct PairSeq {
     const uint8_t* r; const uint8_t* q;                          // any byte outside ACGT is N, and N equals N
@@ -236,7 +235,6 @@ __device__ inline void walk_backbone(const uint2* M, const uint32_t* path, uint3
     v.stretch(i1, n1, j1, n2);
 }
 
-constexpr uint32_t kSafeMismatch = (2 * PEN_O + 2 * PEN_E) / PEN_X;                      // wfa.rs:212
 // which scratch level the task needs and an upper bound of its CIGAR's items
 struct Levels { Lim l[kLevels]; };                              // the levels' limits, already cut to the knob align_dp_cells
 struct PlanVisitor {
@@ -244,9 +242,10 @@ struct PlanVisitor {
     __device__ void anchor(uint32_t) { bound++; }
     __device__ void stretch(uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2) {
         const uint32_t n = i2 - i1, m = j2 - j1;
-        if (!n || !m) { bound++; return; }
-        if (max_gap < n || max_gap < m || !lim_takes(top, n, m)) { bound += min(n, m) + 1; return; }
-        if (n == m && n <= kSafeMismatch) { bound += n; return; }
+        const gotoh::Route route = gotoh::route(n, m, max_gap);
+        if (route == gotoh::ROUTE_STRAIGHT) { bound += n; return; }
+        if (route == gotoh::ROUTE_SIMPLE || (route == gotoh::ROUTE_EXACT && !lim_takes(top, n, m))) { bound += min(n, m) + 1; return; }
+        if (route != gotoh::ROUTE_EXACT) { bound++; return; }                 // one gap, or nothing
         bound += static_cast<uint64_t>(n) + m;
         for (uint32_t l = 0; l < kLevels; l++)
             if (lim_takes(lv.l[l], n, m)) { level = max(level, l); return; }
@@ -270,101 +269,74 @@ __global__ __launch_bounds__(64) void align_plan_kernel(const Task* __restrict__
 }
 
 struct FillVisitor {
-    PairSeq S; CigOut cg; uint32_t max_gap; Lim top, mine; int32_t* rows; uint8_t* dirs; int score; uint32_t dropped;
+    PairSeq S; CigOut cg; uint32_t max_gap; Lim top, mine; gotoh::Cell* rows; uint8_t* dirs; int score; uint32_t dropped;
     unsigned long long n_route[4], cells;
 
-    // Penalties::align_simple (wfa.rs:49-84)
+    __device__ bool same(uint32_t i, uint32_t j) const { return S.R(i) == S.Q(j); }
     __device__ int simple(uint32_t i1, uint32_t n, uint32_t j1, uint32_t m) {
-        const int diff = static_cast<int>(n) - static_cast<int>(m);
-        int sc = 0;
-        uint32_t i = 0, j = 0;
-        if (diff < 0) { cg.push(OP_I, static_cast<uint32_t>(-diff)); sc = -PEN_O + diff * PEN_E; j = static_cast<uint32_t>(-diff); }
-        else if (diff > 0) { cg.push(OP_D, static_cast<uint32_t>(diff)); sc = -PEN_O - diff * PEN_E; i = static_cast<uint32_t>(diff); }
-        for (uint32_t t = 0; i + t < n && j + t < m; t++) {
-            const bool eq = S.R(i1 + i + t) == S.Q(j1 + j + t);
-            cg.push(eq ? OP_EQ : OP_X, 1);
-            sc -= eq ? 0 : PEN_X;
-        }
-        return sc;
+        return gotoh::align_simple(n, m, [&](uint32_t i, uint32_t j) { return same(i1 + i, j1 + j); }, [&](uint32_t op, uint32_t len) { cg.push(op, len); });
     }
-    // the end-to-end gap-affine optimum of reference [i1, +n) and query [j1, +m): recurrence, tie rule and walk back of xfer::dp_align
-    // (mode 0, no match bonus), without its step limit. The caller has checked lim_takes(mine, n, m).
-    __device__ int gotoh(uint32_t i1, uint32_t n, uint32_t j1, uint32_t m) {
+    // the end-to-end gap-affine optimum of reference [i1, +n) and query [j1, +m), no match bonus, no step limit: two rolling rows of
+    // cells and a direction byte per cell, unstrided, in the lane's own scratch. The caller has checked lim_takes(mine, n, m).
+    __device__ int exact(uint32_t i1, uint32_t n, uint32_t j1, uint32_t m) {
         const uint32_t W = m + 1;
         cells += static_cast<unsigned long long>(n + 1) * W;
-        int32_t* prev = rows;
-        int32_t* cur = rows + (static_cast<size_t>(mine.dim) + 1) * 3;
+        gotoh::Cell* prev = rows;
+        gotoh::Cell* cur = rows + mine.dim + 1;
+        const gotoh::Cell none{INF32, INF32, INF32};
         for (uint32_t a = 0; a <= n; a++) {
             const uint8_t rbase = a > 0 ? S.R(i1 + a - 1) : 0;
-            int32_t lm = INF32, ld = INF32, li = INF32, gm = INF32, gd = INF32, gi = INF32;
+            gotoh::Cell left = none, diag = none;
             for (uint32_t b = 0; b <= m; b++) {
-                int32_t cm = INF32, cd = INF32, ci = INF32;
-                uint32_t dm = 3, dd = 0, di = 0;
-                int32_t um = INF32, ud = INF32, ui = INF32;
-                if (a > 0) { um = prev[b * 3]; ud = prev[b * 3 + 1]; ui = prev[b * 3 + 2]; }
-                if (a == 0 && b == 0) cm = 0;
-                if (a > 0 && b > 0) {
-                    const int32_t best = min(gm, min(gd, gi));
-                    if (best < INF32) {
-                        const int32_t v = best + (rbase == S.Q(j1 + b - 1) ? 0 : PEN_X);
-                        if (v < cm) { cm = v; dm = gm == best ? 0u : (gd == best ? 1u : 2u); }
-                    }
-                }
-                if (a > 0) {
-                    int32_t v = min(um, ui) + PEN_O + PEN_E;
-                    if (ud + PEN_E < v) v = ud + PEN_E;
-                    if (v < INF32) { cd = v; dd = (ud + PEN_E == v) ? 1u : (um <= ui ? 0u : 2u); }
-                }
-                if (b > 0) {
-                    int32_t v = min(lm, ld) + PEN_O + PEN_E;
-                    if (li + PEN_E < v) v = li + PEN_E;
-                    if (v < INF32) { ci = v; di = (li + PEN_E == v) ? 2u : (lm <= ld ? 0u : 1u); }
-                }
-                cur[b * 3] = cm; cur[b * 3 + 1] = cd; cur[b * 3 + 2] = ci;
-                dirs[static_cast<size_t>(a) * W + b] = static_cast<uint8_t>(dm | (dd << 2) | (di << 4));
-                lm = cm; ld = cd; li = ci;
-                gm = um; gd = ud; gi = ui;
+                const gotoh::Cell up = a > 0 ? prev[b] : none;
+                const int32_t sub = (a > 0 && b > 0 && rbase != S.Q(j1 + b - 1)) ? PEN_X : 0;
+                uint32_t dir;
+                const gotoh::Cell c = gotoh::cell(up, left, diag, sub, a > 0, b > 0, a == 0 && b == 0, &dir);
+                cur[b] = c;
+                dirs[static_cast<size_t>(a) * W + b] = static_cast<uint8_t>(dir);
+                left = c; diag = up;
             }
-            int32_t* x = prev; prev = cur; cur = x;
+            gotoh::Cell* x = prev; prev = cur; cur = x;
         }
-        const int32_t em = prev[m * 3], ed = prev[m * 3 + 1], ei = prev[m * 3 + 2];
-        const int32_t best = min(em, min(ed, ei));
         // walk back: the runs arrive last first, behind the items the CIGAR has; then they are turned round and joined to them
         const uint32_t r0 = cg.n;
         CigOut rev{cg.w + r0, 0, cg.cap - r0, false};
         uint32_t a = n, b = m;
-        uint32_t st = (em <= ed && em <= ei) ? 0u : (ed <= ei ? 1u : 2u);
+        const gotoh::Cell end = prev[m];
+        uint32_t st = gotoh::end_state(end);
         while (a > 0 || b > 0) {
             const uint32_t d = dirs[static_cast<size_t>(a) * W + b];
-            if (st == 0) { rev.push(S.R(i1 + a - 1) == S.Q(j1 + b - 1) ? OP_EQ : OP_X, 1); st = d & 3u; a--; b--; }
-            else if (st == 1) { rev.push(OP_D, 1); const uint32_t dd = (d >> 2) & 3u; st = dd == 1 ? 1u : (dd == 0 ? 0u : 2u); a--; }
-            else { rev.push(OP_I, 1); const uint32_t di = (d >> 4) & 3u; st = di == 2 ? 2u : (di == 0 ? 0u : 1u); b--; }
+            if (st == gotoh::ST_M) { rev.push(same(i1 + a - 1, j1 + b - 1) ? OP_EQ : OP_X, 1); a--; b--; }
+            else if (st == gotoh::ST_D) { rev.push(OP_D, 1); a--; }
+            else { rev.push(OP_I, 1); b--; }
+            st = gotoh::back_step(st, d);
         }
         cg.overflow |= rev.overflow;
         for (uint32_t x = 0, y = rev.n; x + 1 < y; x++, y--) { const uint32_t w = rev.w[x]; rev.w[x] = rev.w[y - 1]; rev.w[y - 1] = w; }
         cg.n = r0;
         for (uint32_t x = 0; x < rev.n; x++) { const uint32_t w = cg.w[r0 + x]; cg.push(w & 15u, w >> 4); }     // (reads at or ahead of what it writes)
-        return -best;
+        return -gotoh::best_of(end);
     }
     __device__ void anchor(uint32_t len) { cg.push(OP_EQ, len); }
     // smart_align (wfa.rs:280-321) with max_gap as the threshold
     __device__ void stretch(uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2) {
         const uint32_t n = i2 - i1, m = j2 - j1;
-        if (n > 0 && m > 0) {
-            if (max_gap < n || max_gap < m) { n_route[ST_SIMPLE]++; score += simple(i1, n, j1, m); return; }
-            if (n == m && n <= kSafeMismatch) {
-                n_route[ST_TRIVIAL]++;
-                for (uint32_t t = 0; t < n; t++) { const bool eq = S.R(i1 + t) == S.Q(j1 + t); cg.push(eq ? OP_EQ : OP_X, 1); score -= eq ? 0 : PEN_X; }
-                return;
-            }
+        switch (gotoh::route(n, m, max_gap)) {
+        case gotoh::ROUTE_SIMPLE: n_route[ST_SIMPLE]++; score += simple(i1, n, j1, m); break;
+        case gotoh::ROUTE_STRAIGHT:
+            n_route[ST_TRIVIAL]++;
+            score += gotoh::align_straight(n, [&](uint32_t i, uint32_t j) { return same(i1 + i, j1 + j); }, [&](uint32_t op, uint32_t len) { cg.push(op, len); });
+            break;
+        case gotoh::ROUTE_EXACT:
             // beyond the largest scratch level the stretch is dropped, as the reference does when WFA drops an alignment (wfa.rs:234-237)
-            if (!lim_takes(top, n, m) || !lim_takes(mine, n, m)) { dropped++; n_route[ST_SIMPLE]++; score += simple(i1, n, j1, m); return; }
+            if (!lim_takes(top, n, m) || !lim_takes(mine, n, m)) { dropped++; n_route[ST_SIMPLE]++; score += simple(i1, n, j1, m); break; }
             n_route[(n <= xfer::DP_SMALL && m <= xfer::DP_SMALL) ? ST_SMALL : ST_GENERAL]++;      // a size class: one aligner serves both
-            score += gotoh(i1, n, j1, m);
-            return;
+            score += exact(i1, n, j1, m);
+            break;
+        case gotoh::ROUTE_DEL: n_route[ST_TRIVIAL]++; cg.push(OP_D, n); score += gotoh::gap_score(n); break;
+        case gotoh::ROUTE_INS: n_route[ST_TRIVIAL]++; cg.push(OP_I, m); score += gotoh::gap_score(m); break;
+        default: break;
         }
-        if (n > 0) { n_route[ST_TRIVIAL]++; cg.push(OP_D, n); score -= PEN_O + static_cast<int>(n) * PEN_E; }
-        else if (m > 0) { n_route[ST_TRIVIAL]++; cg.push(OP_I, m); score -= PEN_O + static_cast<int>(m) * PEN_E; }
     }
 };
 
@@ -387,7 +359,7 @@ __global__ __launch_bounds__(64) void align_fill_kernel(const uint32_t* __restri
         v.S = PairSeq{seq + off[tk.ref], seq + off[tk.qry]};
         v.cg = CigOut{cig + cig_off[t], 0, static_cast<uint32_t>(cig_off[t + 1] - cig_off[t]), false};
         v.max_gap = max_gap; v.top = top; v.mine = mine;
-        v.rows = reinterpret_cast<int32_t*>(mem); v.dirs = mem + 2 * (static_cast<size_t>(mine.dim) + 1) * 12;
+        v.rows = reinterpret_cast<gotoh::Cell*>(mem); v.dirs = mem + 2 * (static_cast<size_t>(mine.dim) + 1) * sizeof(gotoh::Cell);
         v.score = 0; v.dropped = 0; v.cells = 0;
         for (uint32_t r = 0; r < 4; r++) v.n_route[r] = 0;
         walk_backbone(matches + m0, path + m0 + path_start[t], m - path_start[t], tk.k, static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]),

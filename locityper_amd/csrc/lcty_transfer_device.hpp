@@ -1,21 +1,21 @@
 // lcty_transfer_device.hpp — device side of alignment recovery (K6): one lane carries one transfer of a read alignment
 // from the haplotype it was found on to another haplotype, through the alignment of the two haplotypes
 // (Cigar::transfer_read_alignment, src/seq/cigar.rs:1248-1384) with the aligner calls of src/seq/wfa.rs restated as an
-// exact gap-affine dynamic programme (WFA2-lib computes the same optimum; its tie-breaks are not pinned anywhere, ours
-// are: walking back from the end, diagonal before deletion before insertion, a gap is extended before it is opened).
+// exact gap-affine dynamic programme (lcty_gotoh.hpp: the cell, its tie rule, the walk back, align_simple and the routing of
+// smart_align are stated there once; here are the loops around them, with their memory layouts).
 // Scalar code per lane with private scratch in global memory: this is control-heavy work, the parallelism is across the
 // (alignment, target haplotype) pairs of a read.
 #pragma once
 
 #include "lcty_device.hpp"
+#include "lcty_gotoh.hpp"
 
 namespace lcty {
 namespace xfer {
 
-constexpr uint32_t OP_I = 1, OP_D = 2, OP_S = 4, OP_H = 5, OP_EQ = 7, OP_X = 8;
-constexpr int PEN_X = 4, PEN_O = 6, PEN_E = 1;             // Penalties::default (wfa.rs:30-38)
+using gotoh::OP_I; using gotoh::OP_D; using gotoh::OP_S; using gotoh::OP_H; using gotoh::OP_EQ; using gotoh::OP_X;
+using gotoh::PEN_X; using gotoh::PEN_O; using gotoh::PEN_E; using gotoh::INF32; using gotoh::SAFE_MISMATCH;
 constexpr int MAX_STEPS = 10000;                            // alignment_steps(6), wfa.rs:103-117
-constexpr int INF32 = 1 << 28;
 constexpr int DP_DROPPED = -(1 << 30);
 constexpr int DP_TOO_BIG = DP_DROPPED + 1;                  // the stretch does not fit the lane's scratch at this level
 
@@ -213,35 +213,24 @@ __device__ inline Scratch scratch_at(uint8_t* base, uint32_t lane, const Limits&
 
 // Penalties::align_simple (wfa.rs:49-84): reference [i1, i1+n) against query [j1, j1+m)
 __device__ inline int align_simple(const Seqs& S, uint32_t i1, uint32_t n, uint32_t j1, uint32_t m, DCigar& cg) {
-    const int diff = static_cast<int>(n) - static_cast<int>(m);
-    int score;
-    uint32_t i = 0, j = 0;
-    if (diff < 0) { cg.push_unchecked(OP_I, static_cast<uint32_t>(-diff)); score = -PEN_O + diff * PEN_E; j = static_cast<uint32_t>(-diff); }
-    else if (diff > 0) { cg.push_unchecked(OP_D, static_cast<uint32_t>(diff)); score = -PEN_O - diff * PEN_E; i = static_cast<uint32_t>(diff); }
-    else score = 0;
-    bool curr_match = S.r(i1 + i) == S.q(j1 + j);
-    uint32_t curr_len = 1;
-    for (uint32_t t = 1; i + t < n && j + t < m; t++) {
-        const bool eq = S.r(i1 + i + t) == S.q(j1 + j + t);
-        if (eq != curr_match) {
-            cg.push_unchecked(curr_match ? OP_EQ : OP_X, curr_len);
-            score -= curr_match ? 0 : PEN_X * static_cast<int>(curr_len);
-            curr_match = !curr_match; curr_len = 1;
-        } else curr_len++;
-    }
-    cg.push_unchecked(curr_match ? OP_EQ : OP_X, curr_len);
-    score -= curr_match ? 0 : PEN_X * static_cast<int>(curr_len);
-    return score;
+    return gotoh::align_simple(n, m, [&](uint32_t i, uint32_t j) { return S.r(i1 + i) == S.q(j1 + j); },
+                               [&](uint32_t op, uint32_t len) { cg.push_unchecked(op, len); });
 }
 
-// (The recurrence, tie rule and walk back of mode 0 without a match bonus are restated on plain bytes, without the step limit, in
-// lcty_align.hip, FillVisitor::gotoh — the haplotype-to-haplotype aligner: a change of the tie rule here must be made there too.)
+// cell x of a row (or of the last column) of the three matrices in the lane's interleaved scratch
+__device__ __forceinline__ gotoh::Cell row_get(const int32_t* row, uint32_t x) {
+    return gotoh::Cell{row[(x * 3) * LANE_STRIDE], row[(x * 3 + 1) * LANE_STRIDE], row[(x * 3 + 2) * LANE_STRIDE]};
+}
+__device__ __forceinline__ void row_set(int32_t* row, uint32_t x, const gotoh::Cell& c) {
+    row[(x * 3) * LANE_STRIDE] = c.m; row[(x * 3 + 1) * LANE_STRIDE] = c.d; row[(x * 3 + 2) * LANE_STRIDE] = c.i;
+}
+
 // Gap-affine alignment of reference [i1, i1+n) and query [j1, j1+m); mb = match bonus (0 global aligner, 2 semi-global one,
 // wfa.rs:194-197); mode 0 end to end, 1 free begin of both (LEFT), 2 free end of both (RIGHT). Writes the operations in
 // REVERSE order into sc.ops and returns the penalty, or DP_DROPPED (wfa.rs:262-266: status != 0).
 __device__ inline int dp_align(const Seqs& S, uint32_t i1, uint32_t n, uint32_t j1, uint32_t m, int mb, int mode, Scratch& sc, uint32_t* n_ops) {
     // end to end, every alignment pays for the difference of the lengths: beyond MAX_STEPS the aligner gives up whatever the bases are
-    if (mode == 0 && n != m && PEN_O + static_cast<int>(n > m ? n - m : m - n) * PEN_E > MAX_STEPS) return DP_DROPPED;
+    if (mode == 0 && n != m && -gotoh::gap_score(n > m ? n - m : m - n) > MAX_STEPS) return DP_DROPPED;
     if (n > sc.lim.dp_dim || m > sc.lim.dp_dim || (static_cast<uint64_t>(n) + 1) * (m + 1) > sc.lim.dp_cells) {
         sc.big |= mode == 0 ? 1u : 2u;
         return DP_TOO_BIG;
@@ -258,59 +247,41 @@ __device__ inline int dp_align(const Seqs& S, uint32_t i1, uint32_t n, uint32_t 
         const uint8_t rbase = a > 0 ? S.r(i1 + a - 1) : 0;
         // the cell to the left (this row) and the cell above-left (previous row) travel in registers: reading them back from the
         // rows in memory made every cell wait for the stores of the cell before it
-        int32_t lm = INF32, ld = INF32, li = INF32;                            // cell (a, b - 1)
-        int32_t gm = INF32, gd = INF32, gi = INF32;                            // cell (a - 1, b - 1)
+        const gotoh::Cell none{INF32, INF32, INF32};
+        gotoh::Cell left = none, diag = none;                                  // cells (a, b - 1) and (a - 1, b - 1)
         for (uint32_t b = 0; b <= m; b++) {
-            int32_t cm = INF32, cd = INF32, ci = INF32;
-            uint32_t dm = 3, dd = 0, di = 0;
-            int32_t um = INF32, ud = INF32, ui = INF32;                        // cell (a - 1, b)
-            if (a > 0) { um = prev[(b * 3) * LANE_STRIDE]; ud = prev[(b * 3 + 1) * LANE_STRIDE]; ui = prev[(b * 3 + 2) * LANE_STRIDE]; }
-            if (a == 0 && b == 0) cm = 0;
-            else if (mode == 1 && (a == 0 || b == 0)) cm = 0;                 // a prefix of one sequence is skipped for free
+            const gotoh::Cell up = a > 0 ? row_get(prev, b) : none;            // cell (a - 1, b)
+            int32_t sub = 0;
             if (a > 0 && b > 0) {
-                const int32_t pm = gm, pd = gd, pi = gi;
-                const int32_t best = min(pm, min(pd, pi));
-                if (best < INF32) {
-                    const uint8_t qbase = q_packed ? static_cast<uint8_t>(qpack >> (8 * (b - 1))) : S.q(j1 + b - 1);
-                    const int32_t v = best + (rbase == qbase ? -mb : PEN_X);
-                    if (v < cm) { cm = v; dm = pm == best ? 0u : (pd == best ? 1u : 2u); }
-                }
+                const uint8_t qbase = q_packed ? static_cast<uint8_t>(qpack >> (8 * (b - 1))) : S.q(j1 + b - 1);
+                sub = rbase == qbase ? -mb : PEN_X;
             }
-            if (a > 0) {
-                const int32_t pm = um, pd = ud, pi = ui;
-                int32_t v = min(pm, pi) + PEN_O + PEN_E;
-                if (pd + PEN_E < v) v = pd + PEN_E;
-                if (v < INF32) { cd = v; dd = (pd + PEN_E == v) ? 1u : (pm <= pi ? 0u : 2u); }
-            }
-            if (b > 0) {
-                const int32_t pm = lm, pd = ld, pi = li;
-                int32_t v = min(pm, pd) + PEN_O + PEN_E;
-                if (pi + PEN_E < v) v = pi + PEN_E;
-                if (v < INF32) { ci = v; di = (pi + PEN_E == v) ? 2u : (pm <= pd ? 0u : 1u); }
-            }
-            cur[(b * 3) * LANE_STRIDE] = cm; cur[(b * 3 + 1) * LANE_STRIDE] = cd; cur[(b * 3 + 2) * LANE_STRIDE] = ci;
-            sc.dirs[static_cast<size_t>(a * W + b) * LANE_STRIDE] = static_cast<uint8_t>(dm | (dd << 2) | (di << 4));
-            lm = cm; ld = cd; li = ci;
-            gm = um; gd = ud; gi = ui;
+            // mode 1: a prefix of one sequence is skipped for free
+            uint32_t dir;
+            const gotoh::Cell c = gotoh::cell(up, left, diag, sub, a > 0, b > 0, (a == 0 && b == 0) || (mode == 1 && (a == 0 || b == 0)), &dir);
+            row_set(cur, b, c);
+            sc.dirs[static_cast<size_t>(a * W + b) * LANE_STRIDE] = static_cast<uint8_t>(dir);
+            left = c; diag = up;
         }
-        sc.lastcol[(a * 3) * LANE_STRIDE] = lm; sc.lastcol[(a * 3 + 1) * LANE_STRIDE] = ld; sc.lastcol[(a * 3 + 2) * LANE_STRIDE] = li;
+        row_set(sc.lastcol, a, left);
         int32_t* t = prev; prev = cur; cur = t;
     }
     const int32_t* lastrow = prev;                                           // row n
     uint32_t ea = n, eb = m;
-    int32_t best = INF32, em = INF32, ed = INF32, ei = INF32;
+    int32_t best = INF32;
+    gotoh::Cell end{INF32, INF32, INF32};
     if (mode == 2) {                                                         // the alignment may stop on the last row or column
         for (uint32_t b = 0; b <= m; b++) {
-            const int32_t v = min(lastrow[(b * 3) * LANE_STRIDE], min(lastrow[(b * 3 + 1) * LANE_STRIDE], lastrow[(b * 3 + 2) * LANE_STRIDE]));
-            if (v < best) { best = v; ea = n; eb = b; em = lastrow[(b * 3) * LANE_STRIDE]; ed = lastrow[(b * 3 + 1) * LANE_STRIDE]; ei = lastrow[(b * 3 + 2) * LANE_STRIDE]; }
+            const gotoh::Cell c = row_get(lastrow, b);
+            if (gotoh::best_of(c) < best) { best = gotoh::best_of(c); ea = n; eb = b; end = c; }
         }
         for (uint32_t a = 0; a <= n; a++) {
-            const int32_t v = min(sc.lastcol[(a * 3) * LANE_STRIDE], min(sc.lastcol[(a * 3 + 1) * LANE_STRIDE], sc.lastcol[(a * 3 + 2) * LANE_STRIDE]));
-            if (v < best) { best = v; ea = a; eb = m; em = sc.lastcol[(a * 3) * LANE_STRIDE]; ed = sc.lastcol[(a * 3 + 1) * LANE_STRIDE]; ei = sc.lastcol[(a * 3 + 2) * LANE_STRIDE]; }
+            const gotoh::Cell c = row_get(sc.lastcol, a);
+            if (gotoh::best_of(c) < best) { best = gotoh::best_of(c); ea = a; eb = m; end = c; }
         }
     } else {
-        em = lastrow[(m * 3) * LANE_STRIDE]; ed = lastrow[(m * 3 + 1) * LANE_STRIDE]; ei = lastrow[(m * 3 + 2) * LANE_STRIDE];
-        best = min(em, min(ed, ei));
+        end = row_get(lastrow, m);
+        best = gotoh::best_of(end);
     }
     if (best >= INF32 || best > MAX_STEPS) return DP_DROPPED;
     uint32_t k = 0;
@@ -319,24 +290,15 @@ __device__ inline int dp_align(const Seqs& S, uint32_t i1, uint32_t n, uint32_t 
         for (uint32_t a = n; a > ea; a--) sc.ops[static_cast<size_t>(k++) * LANE_STRIDE] = 'D';
     }
     uint32_t a = ea, b = eb;
-    uint32_t st = (em <= ed && em <= ei) ? 0u : (ed <= ei ? 1u : 2u);
+    uint32_t st = gotoh::end_state(end);
     while (a > 0 || b > 0) {
-        if (mode == 1 && (a == 0 || b == 0) && st == 0) break;               // reached the free border
+        if (mode == 1 && (a == 0 || b == 0) && st == gotoh::ST_M) break;     // reached the free border
         const uint32_t d = sc.dirs[static_cast<size_t>(a * W + b) * LANE_STRIDE];
-        if (st == 0) {
-            sc.ops[static_cast<size_t>(k++) * LANE_STRIDE] = S.r(i1 + a - 1) == S.q(j1 + b - 1) ? '=' : 'X';
-            st = d & 3u; a--; b--;
-        } else if (st == 1) {
-            sc.ops[static_cast<size_t>(k++) * LANE_STRIDE] = 'D';
-            const uint32_t dd = (d >> 2) & 3u;
-            st = dd == 1 ? 1u : (dd == 0 ? 0u : 2u);
-            a--;
-        } else {
-            sc.ops[static_cast<size_t>(k++) * LANE_STRIDE] = 'I';
-            const uint32_t di = (d >> 4) & 3u;
-            st = di == 2 ? 2u : (di == 0 ? 0u : 1u);
-            b--;
-        }
+        uint8_t* op = &sc.ops[static_cast<size_t>(k++) * LANE_STRIDE];
+        if (st == gotoh::ST_M) { *op = S.r(i1 + a - 1) == S.q(j1 + b - 1) ? '=' : 'X'; a--; b--; }
+        else if (st == gotoh::ST_D) { *op = 'D'; a--; }
+        else { *op = 'I'; b--; }
+        st = gotoh::back_step(st, d);
     }
     if (mode == 1) {                                                         // the skipped prefix
         for (; b > 0; b--) sc.ops[static_cast<size_t>(k++) * LANE_STRIDE] = 'I';
@@ -365,77 +327,50 @@ __device__ inline int dp_align_small(const Seqs& S, uint32_t i1, uint32_t n, uin
     uint64_t qpack = 0, rpack = 0;
     for (uint32_t b = 0; b < m; b++) qpack |= static_cast<uint64_t>(S.q(j1 + b)) << (8 * b);
     for (uint32_t a = 0; a < n; a++) rpack |= static_cast<uint64_t>(S.r(i1 + a)) << (8 * a);
-    int32_t pm[W8], pd[W8], pi[W8];                                          // row a - 1 (then row a, column by column)
+    gotoh::Cell p[W8];                                                       // row a - 1 (then row a, column by column)
     uint64_t drow[W8];
 #pragma unroll
-    for (uint32_t b = 0; b < W8; b++) { pm[b] = pd[b] = pi[b] = INF32; drow[b] = 0; }
+    for (uint32_t b = 0; b < W8; b++) { p[b] = gotoh::Cell{INF32, INF32, INF32}; drow[b] = 0; }
     for (uint32_t a = 0; a <= n; a++) {
         const uint32_t rbase = a > 0 ? static_cast<uint32_t>(rpack >> (8 * (a - 1))) & 0xFFu : 0u;
-        int32_t lm = INF32, ld = INF32, li = INF32;                            // cell (a, b - 1)
-        int32_t gm = INF32, gd = INF32, gi = INF32;                            // cell (a - 1, b - 1)
+        const gotoh::Cell none{INF32, INF32, INF32};
+        gotoh::Cell left = none, diag = none;                                  // cells (a, b - 1) and (a - 1, b - 1)
         uint64_t row = 0;
 #pragma unroll
         for (uint32_t b = 0; b < W8; b++) {
             if (b <= m) {
-                int32_t cm = INF32, cd = INF32, ci = INF32;
-                uint32_t dm = 3, dd = 0, di = 0;
-                const int32_t um = a > 0 ? pm[b] : INF32, ud = a > 0 ? pd[b] : INF32, ui = a > 0 ? pi[b] : INF32;      // cell (a - 1, b)
-                if (a == 0 && b == 0) cm = 0;
-                if (a > 0 && b > 0) {
-                    const int32_t best = min(gm, min(gd, gi));
-                    if (best < INF32) {
-                        const uint32_t qbase = static_cast<uint32_t>(qpack >> (8 * (b - 1))) & 0xFFu;
-                        const int32_t v = best + (rbase == qbase ? 0 : PEN_X);
-                        if (v < cm) { cm = v; dm = gm == best ? 0u : (gd == best ? 1u : 2u); }
-                    }
-                }
-                if (a > 0) {
-                    int32_t v = min(um, ui) + PEN_O + PEN_E;
-                    if (ud + PEN_E < v) v = ud + PEN_E;
-                    if (v < INF32) { cd = v; dd = (ud + PEN_E == v) ? 1u : (um <= ui ? 0u : 2u); }
-                }
-                if (b > 0) {
-                    int32_t v = min(lm, ld) + PEN_O + PEN_E;
-                    if (li + PEN_E < v) v = li + PEN_E;
-                    if (v < INF32) { ci = v; di = (li + PEN_E == v) ? 2u : (lm <= ld ? 0u : 1u); }
-                }
-                pm[b] = cm; pd[b] = cd; pi[b] = ci;
-                row |= static_cast<uint64_t>(dm | (dd << 2) | (di << 4)) << (8 * b);
-                lm = cm; ld = cd; li = ci;
-                gm = um; gd = ud; gi = ui;
+                const gotoh::Cell up = a > 0 ? p[b] : none;                    // cell (a - 1, b)
+                const uint32_t qbase = b > 0 ? static_cast<uint32_t>(qpack >> (8 * (b - 1))) & 0xFFu : 0u;
+                uint32_t dir;
+                const gotoh::Cell c = gotoh::cell(up, left, diag, rbase == qbase ? 0 : PEN_X, a > 0, b > 0, a == 0 && b == 0, &dir);
+                p[b] = c;
+                row |= static_cast<uint64_t>(dir) << (8 * b);
+                left = c; diag = up;
             }
         }
 #pragma unroll
         for (uint32_t k = 0; k < W8; k++) drow[k] = a == k ? row : drow[k];
     }
-    int32_t em = INF32, ed = INF32, ei = INF32;
+    gotoh::Cell end{INF32, INF32, INF32};
 #pragma unroll
-    for (uint32_t b = 0; b < W8; b++) if (b == m) { em = pm[b]; ed = pd[b]; ei = pi[b]; }
-    const int32_t best = min(em, min(ed, ei));
+    for (uint32_t b = 0; b < W8; b++) if (b == m) end = p[b];
+    const int32_t best = gotoh::best_of(end);
     if (best >= INF32 || best > MAX_STEPS) return DP_DROPPED;
     uint32_t k = 0, ops = 0;
     uint32_t a = n, b = m;
-    uint32_t st = (em <= ed && em <= ei) ? 0u : (ed <= ei ? 1u : 2u);
+    uint32_t st = gotoh::end_state(end);
     while (a > 0 || b > 0) {
         uint64_t row = 0;
 #pragma unroll
         for (uint32_t r = 0; r < W8; r++) row = a == r ? drow[r] : row;
         const uint32_t d = static_cast<uint32_t>(row >> (8 * b)) & 0xFFu;
-        if (st == 0) {
+        if (st == gotoh::ST_M) {
             const bool eq = (static_cast<uint32_t>(rpack >> (8 * (a - 1))) & 0xFFu) == (static_cast<uint32_t>(qpack >> (8 * (b - 1))) & 0xFFu);
-            ops |= (eq ? 0u : 1u) << (2 * k); k++;
-            st = d & 3u; a--; b--;
-        } else if (st == 1) {
-            ops |= 3u << (2 * k); k++;
-            const uint32_t dd = (d >> 2) & 3u;
-            st = dd == 1 ? 1u : (dd == 0 ? 0u : 2u);
-            a--;
-        } else {
-            ops |= 2u << (2 * k); k++;
-            const uint32_t di = (d >> 4) & 3u;
-            st = di == 2 ? 2u : (di == 0 ? 0u : 1u);
-            b--;
-        }
+            ops |= (eq ? 0u : 1u) << (2 * k); a--; b--;
+        } else if (st == gotoh::ST_D) { ops |= 3u << (2 * k); a--; }
+        else { ops |= 2u << (2 * k); b--; }
+        k++;
+        st = gotoh::back_step(st, d);
     }
     *n_ops = k; *ops2 = ops;
     return best;
@@ -485,23 +420,16 @@ __device__ inline int aligner_align(const Seqs& S, uint32_t i1, uint32_t n, uint
 template <bool SMALL>
 __device__ inline int smart_align(const Seqs& S, uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2, uint32_t max_gap, DCigar& cg, Scratch& sc) {
     const uint32_t jump1 = i2 - i1, jump2 = j2 - j1;
-    if (jump1 > 0 && jump2 > 0) {
-        const uint32_t safe_mismatch = (2 * PEN_O + 2 * PEN_E) / PEN_X;      // wfa.rs:212
-        if (max_gap < jump1 || max_gap < jump2) return align_simple(S, i1, jump1, j1, jump2, cg);
-        if (jump1 == jump2 && jump1 <= safe_mismatch) {
-            int ndiff = 0;
-            for (uint32_t t = 0; t < jump1; t++) {
-                const bool eq = S.r(i1 + t) == S.q(j1 + t);
-                cg.push_checked(eq ? OP_EQ : OP_X, 1);
-                ndiff -= !eq;
-            }
-            return ndiff * PEN_X;
-        }
-        return aligner_align<SMALL>(S, i1, jump1, j1, jump2, 0, false, cg, sc);
+    switch (gotoh::route(jump1, jump2, max_gap)) {
+    case gotoh::ROUTE_SIMPLE: return align_simple(S, i1, jump1, j1, jump2, cg);
+    case gotoh::ROUTE_STRAIGHT:
+        return gotoh::align_straight(jump1, [&](uint32_t i, uint32_t j) { return S.r(i1 + i) == S.q(j1 + j); },
+                                     [&](uint32_t op, uint32_t len) { cg.push_checked(op, len); });
+    case gotoh::ROUTE_EXACT: return aligner_align<SMALL>(S, i1, jump1, j1, jump2, 0, false, cg, sc);
+    case gotoh::ROUTE_DEL: cg.push_unchecked(OP_D, jump1); return gotoh::gap_score(jump1);
+    case gotoh::ROUTE_INS: cg.push_unchecked(OP_I, jump2); return gotoh::gap_score(jump2);
+    default: return 0;
     }
-    if (jump1 > 0) { cg.push_unchecked(OP_D, jump1); return -PEN_O - static_cast<int>(jump1) * PEN_E; }
-    if (jump2 > 0) { cg.push_unchecked(OP_I, jump2); return -PEN_O - static_cast<int>(jump2) * PEN_E; }
-    return 0;
 }
 
 struct Job { uint32_t i1, n, j1, m; int semiglobal; bool left_clipping; };
@@ -705,37 +633,36 @@ __device__ inline uint32_t walk_step(Walk& w, const SrcCigar& ij, const Seqs& S,
                     if (from == w.pos2) out.push_unchecked(OP_I, w.pos1 - w.last1);
                     else { job = Job{from, w.pos2 - from, w.last1, w.pos1 - w.last1, 1, true}; return WALK_JOB; }
                 } else {
-                    // smart_align (wfa.rs:301-347) without a maximum gap; only the dynamic programme is handed out
+                    // smart_align (wfa.rs:301-347) without a maximum gap (so never ROUTE_SIMPLE); only the dynamic programme is handed out
                     const uint32_t jump1 = w.pos2 - w.last2, jump2 = w.pos1 - w.last1;
-                    if (jump1 > 0 && jump2 > 0) {
-                        constexpr uint32_t safe_mismatch = (2 * PEN_O + 2 * PEN_E) / PEN_X;  // wfa.rs:212
-                        if (jump1 == jump2 && jump1 <= safe_mismatch) {
-                            // (one base: the short-read case. Else the bases of the whole stretch first — at most three of each — then the
-                            // pushes: their stores would hold the loads up)
-                            if (jump1 == 1) out.push_checked(S.r(w.last2) == S.q(w.last1) ? OP_EQ : OP_X, 1);
-                            else {
-                            bool eq[safe_mismatch];
+                    const gotoh::Route route = gotoh::route(jump1, jump2, 0xFFFFFFFFu);
+                    if (route == gotoh::ROUTE_STRAIGHT) {
+                        // gotoh::align_straight, written out for the order of its memory operations: one base is the short-read case;
+                        // else the bases of the whole stretch first — at most three of each — then the pushes: their stores would hold
+                        // the loads up
+                        if (jump1 == 1) out.push_checked(S.r(w.last2) == S.q(w.last1) ? OP_EQ : OP_X, 1);
+                        else {
+                        bool eq[SAFE_MISMATCH];
 #pragma unroll
-                            for (uint32_t t = 0; t < safe_mismatch; t++) eq[t] = S.r(w.last2 + min(t, jump1 - 1)) == S.q(w.last1 + min(t, jump1 - 1));
+                        for (uint32_t t = 0; t < SAFE_MISMATCH; t++) eq[t] = S.r(w.last2 + min(t, jump1 - 1)) == S.q(w.last1 + min(t, jump1 - 1));
 #pragma unroll
-                            for (uint32_t t = 0; t < safe_mismatch; t++) if (t < jump1) out.push_checked(eq[t] ? OP_EQ : OP_X, 1);
-                            }
-                        } else {
-                            // A stretch for the aligner between two anchors. Nothing of the walk depends on how it aligns (an end-to-end
-                            // alignment consumes both stretches completely, whatever its operations): the stretch is noted, a marker takes
-                            // its place in the CIGAR and the walk goes on. The aligner runs when the walk has reached the end of the
-                            // read's CIGAR (assemble_jobs, WALK_ASSEMBLE) — for all lanes of the wavefront together, stretch by stretch.
-                            // Calling it from here made every lane wait at every stretch of every other lane: an indel every fifty
-                            // bases of a long read, at another step in every lane (16 of 64 lanes active, profiles/r03_pmc_transfer_*).
-                            if (w.n_jobs < sc.lim.cigar_cap / 2 + 8) {
-                                sc.jobs[static_cast<size_t>(w.n_jobs) * LANE_STRIDE] = make_uint4(w.last2, jump1, w.last1, jump2);
-                                out.push_raw(make_uint2(JOB_MARK, w.n_jobs));
-                                out.rlen += jump1; out.qlen += jump2;
-                                w.n_jobs++;
-                            } else out.overflow = true;
+                        for (uint32_t t = 0; t < SAFE_MISMATCH; t++) if (t < jump1) out.push_checked(eq[t] ? OP_EQ : OP_X, 1);
                         }
-                    } else if (jump1 > 0) out.push_unchecked(OP_D, jump1);
-                    else if (jump2 > 0) out.push_unchecked(OP_I, jump2);
+                    } else if (route == gotoh::ROUTE_EXACT) {
+                        // A stretch for the aligner between two anchors. Nothing of the walk depends on how it aligns (an end-to-end
+                        // alignment consumes both stretches completely, whatever its operations): the stretch is noted, a marker takes
+                        // its place in the CIGAR and the walk goes on. The aligner runs when the walk has reached the end of the
+                        // read's CIGAR (assemble_jobs, WALK_ASSEMBLE) — for all lanes of the wavefront together, stretch by stretch.
+                        // Calling it from here made every lane wait at every stretch of every other lane: an indel every fifty
+                        // bases of a long read, at another step in every lane (16 of 64 lanes active, profiles/r03_pmc_transfer_*).
+                        if (w.n_jobs < sc.lim.cigar_cap / 2 + 8) {
+                            sc.jobs[static_cast<size_t>(w.n_jobs) * LANE_STRIDE] = make_uint4(w.last2, jump1, w.last1, jump2);
+                            out.push_raw(make_uint2(JOB_MARK, w.n_jobs));
+                            out.rlen += jump1; out.qlen += jump2;
+                            w.n_jobs++;
+                        } else out.overflow = true;
+                    } else if (route == gotoh::ROUTE_DEL) out.push_unchecked(OP_D, jump1);
+                    else if (route == gotoh::ROUTE_INS) out.push_unchecked(OP_I, jump2);
                 }
             }
         }

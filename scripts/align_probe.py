@@ -20,14 +20,29 @@ import numpy as np  # noqa: E402
 
 
 def host_lib():
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "align_probe_host.cpp")
+    here = os.path.dirname(os.path.abspath(__file__))
+    src = os.path.join(here, "align_probe_host.cpp")
     out = os.path.join(tempfile.mkdtemp(prefix="align_probe_"), "libalign_probe_host.so")
-    subprocess.run(["g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", out], check=True)
+    # lcty_gotoh.hpp, the library's own aligner primitives, compiled for the host
+    subprocess.run(["g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I", os.path.join(os.path.dirname(here), "locityper_amd", "csrc"), src,
+                    "-o", out], check=True)
     L = C.CDLL(out)
     L.align_probe_host.restype = C.c_double
     L.align_probe_host.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+    L.align_probe_stretch.restype = C.c_int32
+    L.align_probe_stretch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     return L
+
+
+def host_stretch(ref, query, max_gap, lib=None):
+    """(score, pushes as (operation code, length)) of smart_align on one stretch, walk back included: the host instantiation of lcty_gotoh.hpp"""
+    r = np.frombuffer(bytes(ref), dtype=np.uint8); q = np.frombuffer(bytes(query), dtype=np.uint8)
+    words = np.zeros(2 * (len(r) + len(q)) + 4, dtype=np.uint32)
+    n = C.c_uint32(0)
+    score = (lib or host_lib()).align_probe_stretch(r.ctypes.data, len(r), q.ctypes.data, len(q), max_gap, words.ctypes.data, len(words), C.byref(n))
+    assert n.value <= len(words)
+    return score, [(int(w) & 15, int(w) >> 4) for w in words[:n.value]]
 
 
 def host_route(seqs, off, ref, query, ks, max_gap, threads=16):

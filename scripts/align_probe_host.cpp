@@ -1,9 +1,13 @@
 // The comparison point of scripts/align_probe.py: the backbone route of src/seq/align.rs (precompute_kmers, get_kmer_matches, LCSk++,
 // align_from_backbone with smart_align, align_multik) for the given pairs in `threads` host threads, as the reference spreads them.
 // Plain C++, -O3. Scores only: the exact aligner is a two-row Gotoh optimum without a walk back (the optimum is what WFA at accuracy 9
-// returns too), so this side does LESS than the reference does per stretch. The rules the library states are restated, not shared:
-// a window with a byte outside ACGT is no k-mer, such a byte is N in the gap fill, the chain's ties go to the lowest match index and a
-// jump is kept over an equal diagonal continuation, a stretch beyond 16 383 bases a side or 2^26 cells takes align_simple.
+// returns too), so this side does LESS than the reference does per stretch. Stages A and B are restated, not shared, because they are
+// what the device's stages are compared with: a window with a byte outside ACGT is no k-mer, the chain's ties go to the lowest match
+// index and a jump is kept over an equal diagonal continuation. The gap fill is NOT restated: routing, align_simple, the cell of the
+// exact aligner and its walk back are the host instantiation of locityper_amd/csrc/lcty_gotoh.hpp (compile with -I to that
+// directory), around this file's own loop over two rows; a byte outside ACGT is N, a stretch beyond 16 383 bases a side or 2^26
+// cells takes align_simple. align_probe_stretch is the same route for one stretch WITH the walk back and a recording sink
+// (tests/test_align_host.py holds it against tests/pyref_align.py).
 // Returns the milliseconds of the pairs (the k-mer lists of the sequences, made once, are timed apart: *index_ms).
 #include <algorithm>
 #include <atomic>
@@ -14,8 +18,10 @@
 #include <utility>
 #include <vector>
 
+#include "lcty_gotoh.hpp"
+
 namespace {
-constexpr int PEN_X = 4, PEN_O = 6, PEN_E = 1, INF = 1 << 28;
+namespace G = lcty::gotoh;
 constexpr uint32_t DP_DIM = 16383;
 constexpr uint64_t DP_CELLS = 1ull << 26;
 
@@ -90,53 +96,76 @@ void lcskpp(const std::vector<std::pair<uint32_t, uint32_t>>& M, uint32_t k, uin
     std::reverse(path.begin(), path.end());
 }
 
-int align_simple(const Seq& r, uint32_t i1, uint32_t n, const Seq& q, uint32_t j1, uint32_t m) {       // wfa.rs:49-84, the score
-    int sc = 0;
-    uint32_t i = 0, j = 0;
-    if (n < m) { sc = -PEN_O - static_cast<int>(m - n) * PEN_E; j = m - n; }
-    else if (n > m) { sc = -PEN_O - static_cast<int>(n - m) * PEN_E; i = n - m; }
-    for (uint32_t t = 0; i + t < n && j + t < m; t++) sc -= norm(r.p[i1 + i + t]) == norm(q.p[j1 + j + t]) ? 0 : PEN_X;
-    return sc;
-}
+// reference base i against query base j of a stretch, a byte outside ACGT as N
+struct Same {
+    const uint8_t* r; const uint8_t* q;
+    bool operator()(uint32_t i, uint32_t j) const { return norm(r[i]) == norm(q[j]); }
+};
 
-int gotoh(const Seq& r, uint32_t i1, uint32_t n, const Seq& q, uint32_t j1, uint32_t m, std::vector<int>& rows) {
-    rows.assign(3 * (static_cast<size_t>(m) + 1), INF);
-    int* Mx = rows.data(); int* D = Mx + m + 1; int* I = D + m + 1;
-    Mx[0] = 0;
-    for (uint32_t b = 1; b <= m; b++) I[b] = PEN_O + static_cast<int>(b) * PEN_E;
-    for (uint32_t a = 1; a <= n; a++) {
-        const uint8_t rb = norm(r.p[i1 + a - 1]);
-        int diag = std::min(Mx[0], std::min(D[0], I[0]));                     // best of cell (a - 1, b - 1)
-        D[0] = std::min(D[0] + PEN_E, std::min(Mx[0], I[0]) + PEN_O + PEN_E); Mx[0] = INF; I[0] = INF;
-        for (uint32_t b = 1; b <= m; b++) {
-            const int up = std::min(Mx[b], I[b]), upd = D[b], here = std::min(Mx[b], std::min(D[b], I[b]));
-            const int nm = diag + (rb == norm(q.p[j1 + b - 1]) ? 0 : PEN_X);
-            const int nd = std::min(upd + PEN_E, up + PEN_O + PEN_E);
-            const int ni = std::min(I[b - 1] + PEN_E, std::min(Mx[b - 1], D[b - 1]) + PEN_O + PEN_E);
-            diag = here;
-            Mx[b] = std::min(nm, INF); D[b] = std::min(nd, INF); I[b] = std::min(ni, INF);
+// The exact aligner, end to end: G::cell over two rolling rows. dirs == nullptr: the optimum alone, what the timed route asks for;
+// else a direction byte per cell and the walk back, push(op, 1) per operation in the order of the alignment.
+template <class Push>
+int gotoh(const Same& same, uint32_t n, uint32_t m, std::vector<G::Cell>& rows, std::vector<uint8_t>* dirs, Push&& push) {
+    const G::Cell none{G::INF32, G::INF32, G::INF32};
+    const size_t W = static_cast<size_t>(m) + 1;
+    rows.assign(2 * W, none);
+    G::Cell* prev = rows.data(); G::Cell* cur = prev + W;
+    if (dirs) dirs->resize((static_cast<size_t>(n) + 1) * W);
+    for (uint32_t a = 0; a <= n; a++) {
+        G::Cell left = none, diag = none;
+        for (uint32_t b = 0; b <= m; b++) {
+            const G::Cell up = a > 0 ? prev[b] : none;
+            uint32_t dir;
+            cur[b] = G::cell(up, left, diag, (a > 0 && b > 0 && !same(a - 1, b - 1)) ? G::PEN_X : 0, a > 0, b > 0, a == 0 && b == 0, &dir);
+            if (dirs) (*dirs)[a * W + b] = static_cast<uint8_t>(dir);
+            left = cur[b]; diag = up;
         }
+        std::swap(prev, cur);
     }
-    return -std::min(Mx[m], std::min(D[m], I[m]));
+    const G::Cell end = prev[m];
+    if (dirs) {
+        std::vector<uint32_t> rev;
+        uint32_t a = n, b = m, st = G::end_state(end);
+        while (a > 0 || b > 0) {
+            const uint32_t d = (*dirs)[a * W + b];
+            if (st == G::ST_M) { rev.push_back(same(a - 1, b - 1) ? G::OP_EQ : G::OP_X); a--; b--; }
+            else if (st == G::ST_D) { rev.push_back(G::OP_D); a--; }
+            else { rev.push_back(G::OP_I); b--; }
+            st = G::back_step(st, d);
+        }
+        for (size_t x = rev.size(); x-- > 0;) push(rev[x], 1u);
+    }
+    return -G::best_of(end);
 }
 
-int smart_align(const Seq& r, uint32_t i1, uint32_t i2, const Seq& q, uint32_t j1, uint32_t j2, uint32_t max_gap, std::vector<int>& rows) {    // wfa.rs:280-321
+template <class Push>
+int smart_align(const Seq& r, uint32_t i1, uint32_t i2, const Seq& q, uint32_t j1, uint32_t j2, uint32_t max_gap, std::vector<G::Cell>& rows,
+                std::vector<uint8_t>* dirs, Push&& push) {    // wfa.rs:280-321
     const uint32_t n = i2 - i1, m = j2 - j1;
-    if (n && m) {
-        if (max_gap < n || max_gap < m) return align_simple(r, i1, n, q, j1, m);
-        if (n == m && n <= (2 * PEN_O + 2 * PEN_E) / PEN_X) {
-            int sc = 0;
-            for (uint32_t t = 0; t < n; t++) sc -= norm(r.p[i1 + t]) == norm(q.p[j1 + t]) ? 0 : PEN_X;
-            return sc;
-        }
-        if (n > DP_DIM || m > DP_DIM || (static_cast<uint64_t>(n) + 1) * (m + 1) > DP_CELLS) return align_simple(r, i1, n, q, j1, m);
-        return gotoh(r, i1, n, q, j1, m, rows);
+    const Same same{r.p + i1, q.p + j1};
+    switch (G::route(n, m, max_gap)) {
+    case G::ROUTE_SIMPLE: return G::align_simple(n, m, same, push);
+    case G::ROUTE_STRAIGHT: return G::align_straight(n, same, push);
+    case G::ROUTE_EXACT:
+        if (n > DP_DIM || m > DP_DIM || (static_cast<uint64_t>(n) + 1) * (m + 1) > DP_CELLS) return G::align_simple(n, m, same, push);
+        return gotoh(same, n, m, rows, dirs, push);
+    case G::ROUTE_DEL: push(G::OP_D, n); return G::gap_score(n);
+    case G::ROUTE_INS: push(G::OP_I, m); return G::gap_score(m);
+    default: return 0;
     }
-    if (n) return -PEN_O - static_cast<int>(n) * PEN_E;
-    if (m) return -PEN_O - static_cast<int>(m) * PEN_E;
-    return 0;
 }
 }  // namespace
+
+// smart_align of reference r[0, n) and query q[0, m) with every push recorded as it comes, a word an item (length << 4 | operation);
+// *n_words counts the pushes, of which the first `cap` are kept. Returns the score.
+extern "C" int32_t align_probe_stretch(const uint8_t* r, uint32_t n, const uint8_t* q, uint32_t m, uint32_t max_gap, uint32_t* words, uint32_t cap,
+                                       uint32_t* n_words) {
+    std::vector<G::Cell> rows; std::vector<uint8_t> dirs;
+    uint32_t k = 0;
+    const int score = smart_align(Seq{r, n}, 0, n, Seq{q, m}, 0, m, max_gap, rows, &dirs, [&](uint32_t op, uint32_t len) { if (k < cap) words[k] = (len << 4) | op; k++; });
+    *n_words = k;
+    return score;
+}
 
 extern "C" double align_probe_host(uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref, const uint32_t* query,
                                    uint32_t nk, const uint32_t* ks, uint32_t max_gap, uint32_t threads, int32_t* score, uint32_t* best_k, double* index_ms) {
@@ -159,7 +188,7 @@ extern "C" double align_probe_host(uint32_t n_seqs, const uint8_t* seqs, const u
     for (uint32_t t = 0; t < threads; t++)
         pool.emplace_back([&, t] {
             std::vector<std::pair<uint32_t, uint32_t>> M;
-            std::vector<uint64_t> fen; std::vector<uint32_t> dp, prev, path; std::vector<int> rows;
+            std::vector<uint64_t> fen; std::vector<uint32_t> dp, prev, path; std::vector<G::Cell> rows;
             // contiguous shares of the pairs, as align_pairs_parallel deals them (align.rs:721-742)
             const uint64_t lo = n_pairs * t / threads, hi = n_pairs * (t + 1) / threads;
             for (uint64_t x = lo; x < hi; x++) {
@@ -174,10 +203,10 @@ extern "C" double align_probe_host(uint32_t n_seqs, const uint8_t* seqs, const u
                     for (uint32_t ix : path) {                                // align_from_backbone, align.rs:262-286
                         const uint32_t i2 = M[ix].first, j2 = M[ix].second;
                         if (i1 > i2) { i1++; j1++; continue; }
-                        sc += smart_align(r, i1, i2, q, j1, j2, max_gap, rows);
+                        sc += smart_align(r, i1, i2, q, j1, j2, max_gap, rows, nullptr, G::NoPush{});
                         i1 = i2 + k; j1 = j2 + k;
                     }
-                    sc += smart_align(r, i1, r.len, q, j1, q.len, max_gap, rows);
+                    sc += smart_align(r, i1, r.len, q, j1, q.len, max_gap, rows, nullptr, G::NoPush{});
                     if (sc > best) { best = sc; bk = k; }
                 }
                 score[x] = best; best_k[x] = bk;

@@ -164,3 +164,65 @@ def reference_multik(name, ref, query):
 def optimum(name, ref, query):
     c = by_name(name)
     return R.full_dp_score(c.seqs[ref], c.seqs[query])
+
+
+# ---- stretches whose optimal alignment is not unique: where the aligner's tie rule decides (lcty_gotoh.hpp) --------------------------------
+# (name, reference, query, max_gap, more than one optimal alignment). Every sequence is shorter than k = 25, so a pair is one stretch
+# of smart_align; tests/test_align_host.py checks the last column against an enumeration and runs the host instantiation,
+# tests/test_gpu_align.py the device. Each stretch is also run with reference and query exchanged.
+TIE_CASES = [
+    ("homopolymer", b"A" * 9, b"A" * 6, 10000, True),                         # where does the gap go
+    ("dinucleotide", b"AC" * 6, b"AC" * 5, 10000, True),
+    ("sub_next_to_indel", b"TTGCAACGTCAT", b"TTGCAGGTCAT", 10000, True),      # AC against G: X then gap, or gap then X
+    ("sub_next_to_indel_in_a_run", b"GATCTTTAGC", b"GATCTGGC", 10000, True),  # TTTA against TG
+    ("equal_3", b"ACG", b"TGA", 10000, False),                                # at safe_mismatch: base against base, no aligner
+    ("equal_4", b"ACGT", b"TGCA", 10000, False),                              # just beyond it: the aligner, four mismatches beat two gaps
+    ("empty_reference", b"", b"ACGT", 10000, False),
+    ("empty_query", b"ACGT", b"", 10000, False),
+    ("beyond_max_gap", b"ACGTTTTAC", b"ACGTTAC", 8, True),                    # align_simple: the gap in front, whatever is optimal
+    # at most 7 bases a side: what alignment recovery gives to its in-register aligner (xfer::dp_align_small) in a batch with long CIGARs
+    ("homopolymer_short", b"A" * 6, b"A" * 4, 10000, True),
+    ("dinucleotide_short", b"AC" * 3, b"AC" * 2, 10000, True),
+    ("sub_next_to_indel_short", b"GCAACG", b"GCAGG", 10000, True),
+]
+
+
+def tie_runs():
+    """every stretch of TIE_CASES both ways round: (name, reference, query, max_gap)"""
+    return [(name + sfx, a, b, mg) for name, r, q, mg, _ in TIE_CASES for sfx, a, b in (("", r, q), ("_swapped", q, r))]
+
+
+TIE_FLANK = 215
+
+
+@functools.lru_cache(maxsize=None)
+def tie_transfer_case():
+    """The stretches of tie_runs() as work for alignment recovery: (two alleles, the CIGAR of allele 0 as query on allele 1, reads).
+    Allele 0 is a row of blocks F G of random flanks, allele 1 has the stretch's reference between them (F R G; the haplotype alignment
+    says 215= nD 215=). A read is the end of F, the stretch's query and the start of G, reported on allele 0 as f= mI f=. In its
+    transfer to allele 1 the flanks anchor and neither CIGAR has an `=` in between, so smart_align gets exactly (R, Q)
+    (cigar.rs:1248-1384). Each stretch comes as a read with flanks of 210 — long enough that its m <= 12 edits on allele 0 are within
+    3 % of the read, the threshold of tests/helpers.py::make_bg for a well mapped read, so the read stays in use —
+    and as one with flanks of 5 (at most 32 bases; no record of it can stay: with the stretch as an insertion among so few bases it is
+    poorly mapped and not transferred, and where it is, the result is below MIN_ALN_SIZE = 50). Both alleles begin with 300 and end
+    with 700 equal bases (the boundary of the locus; room for a read with a long CIGAR). reads: [(name, start on allele 0, bases, CIGAR)]."""
+    rng = np.random.default_rng(47)
+    a0, a1, hap, reads = bytearray(), bytearray(), [], []
+
+    def push(op, n):
+        if n and hap and hap[-1][0] == op: hap[-1][1] += n
+        elif n: hap.append([op, n])
+    head = rand_seq(rng, 300)
+    a0 += head; a1 += head; push("=", 300)
+    for name, r, q, _ in tie_runs():
+        f, g = rand_seq(rng, TIE_FLANK), rand_seq(rng, TIE_FLANK)
+        at = len(a0)
+        a0 += f + g; a1 += f + r + g
+        push("=", TIE_FLANK); push("D", len(r)); push("=", TIE_FLANK)
+        for tag, fl in (("", 210), ("/32", 5)):
+            cg = f"{fl}={len(q)}I{fl}=" if q else f"{2 * fl}="
+            reads.append((name + tag, at + TIE_FLANK - fl, f[TIE_FLANK - fl:] + q + g[:fl], cg))
+            assert fl == 210 or len(reads[-1][2]) <= 32
+    tail = rand_seq(rng, 700)
+    a0 += tail; a1 += tail; push("=", 700)
+    return (bytes(a0), bytes(a1)), "".join(f"{n}{op}" for op, n in hap), reads

@@ -155,14 +155,19 @@ def test_case_shapes():
     assert len(AC.reference("tandem", 0, 1, 25)[0]) > 5000                   # quadratic matches
 
 
-# ---- 5. the host-thread form of the probe -----------------------------------------------------------------------------------------------
-def test_probe_host_route_equals_the_transliteration():
-    """scripts/align_probe_host.cpp (the comparison point of scripts/align_probe.py) on the unique-chain cases: score and best k of
-    align_multik; on every case its score is that of its own CIGAR-free route and never above the full-DP optimum."""
+def _probe():
     import importlib.util
     import os
     spec = importlib.util.spec_from_file_location("align_probe", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "align_probe.py"))
     probe = importlib.util.module_from_spec(spec); spec.loader.exec_module(probe)
+    return probe
+
+
+# ---- 5. the host-thread form of the probe -----------------------------------------------------------------------------------------------
+def test_probe_host_route_equals_the_transliteration():
+    """scripts/align_probe_host.cpp (the comparison point of scripts/align_probe.py) on the unique-chain cases: score and best k of
+    align_multik; on every case its score is that of its own CIGAR-free route and never above the full-DP optimum."""
+    probe = _probe()
     for c in AC.cases():
         seqs, off = c.arrays()
         ref = [p[0] for p in c.pairs]; query = [p[1] for p in c.pairs]
@@ -172,3 +177,75 @@ def test_probe_host_route_equals_the_transliteration():
             if c.unique:
                 _, want, k = AC.reference_multik(c.name, r, q)
                 assert (int(score[x]), int(best[x])) == (want, k)
+
+
+# ---- 6. the aligner primitives of lcty_gotoh.hpp, compiled for the host, on stretches where a tie rule decides -----------------------------
+def n_optimal_alignments(ref, query):
+    """(optimum, number of distinct end-to-end alignments that reach it) under 4 / 6 / 1, by counting over the three matrices: an
+    alignment is its sequence of operations, and that sequence fixes the path through (cell, matrix)."""
+    n, m, INF = len(ref), len(query), 1 << 30
+    best = {(0, 0, "M"): (0, 1)}
+
+    def get(i, j, s):
+        return best.get((i, j, s), (INF, 0))
+
+    def merge(cands):
+        v = min(c[0] for c in cands)
+        return (v, sum(c[1] for c in cands if c[0] == v)) if v < INF else (INF, 0)
+    for i in range(n + 1):
+        for j in range(m + 1):
+            if i and j:
+                sub = 0 if ref[i - 1] == query[j - 1] else R.MISMATCH
+                best[i, j, "M"] = merge([(get(i - 1, j - 1, s)[0] + sub, get(i - 1, j - 1, s)[1]) for s in "MDI"])
+            if i:
+                best[i, j, "D"] = merge([(get(i - 1, j, "D")[0] + R.GAP_EXTEND, get(i - 1, j, "D")[1])] +
+                                        [(get(i - 1, j, s)[0] + R.GAP_OPEN + R.GAP_EXTEND, get(i - 1, j, s)[1]) for s in "MI"])
+            if j:
+                best[i, j, "I"] = merge([(get(i, j - 1, "I")[0] + R.GAP_EXTEND, get(i, j - 1, "I")[1])] +
+                                        [(get(i, j - 1, s)[0] + R.GAP_OPEN + R.GAP_EXTEND, get(i, j - 1, s)[1]) for s in "MD"])
+    pen, cnt = merge([get(n, m, s) for s in "MDI"])
+    return -pen, cnt
+
+
+def test_tie_cases_have_ties():
+    """The last column of AC.TIE_CASES is what the enumeration says, its optimum is pyref_align's full-matrix optimum, and at least
+    four of the stretches have more than one optimal alignment: homopolymer (7: the gap of three in front of any of the six bases of the
+    query, or behind the last), dinucleotide, both substitutions next to an indel, and the stretch beyond max_gap."""
+    tied = 0
+    for name, r, q, _, co in AC.TIE_CASES:
+        opt, cnt = n_optimal_alignments(r, q)
+        assert opt == R.full_dp_score(r, q), name
+        assert (cnt > 1) == co, (name, cnt)
+        assert len(r) < 25 and len(q) < 25
+        tied += cnt > 1
+    assert tied >= 4
+    assert n_optimal_alignments(b"A" * 9, b"A" * 6) == (-9, 7)
+
+
+def test_header_host_instantiation_on_tie_cases():
+    """scripts/align_probe_host.cpp::align_probe_stretch — routing, align_simple, the straight comparison, the cell, the end state and the
+    walk back of locityper_amd/csrc/lcty_gotoh.hpp — against pyref_align.smart_align: the score, and the CIGAR as the recording
+    sink saw it. The aligner and the straight comparison push base by base (push_checked joins them: compared joined); align_simple,
+    DEL and INS push whole items (push_unchecked: compared push for push)."""
+    probe = _probe()
+    lib = probe.host_lib()
+    routes = set()
+    for name, r, q, mg in AC.tie_runs():
+        cig = R.Cig()
+        want = R.smart_align(R.norm(r), 0, len(r), R.norm(q), 0, len(q), mg, cig)
+        score, pushes = probe.host_stretch(r, q, mg, lib)
+        got = [[R.OPS[op], ln] for op, ln in pushes]
+        assert score == want, name
+        joined = R.Cig()
+        for op, ln in got:
+            joined.push_checked(op, ln)
+        assert joined.t == [list(t) for t in R.normalize(cig)], name
+        simple = bool(r) and bool(q) and (mg < len(r) or mg < len(q))
+        exact = bool(r) and bool(q) and not simple and not (len(r) == len(q) and len(r) <= R.SAFE_MISMATCH)
+        if simple or not (r and q):
+            assert got == cig.t, name
+        if exact:
+            assert score == R.full_dp_score(r, q), name
+            assert all(ln == 1 for _, ln in got)
+        routes.add("simple" if simple else "exact" if exact else "gap" if not (r and q) else "straight")
+    assert routes == {"simple", "exact", "gap", "straight"}

@@ -178,6 +178,31 @@ def test_max_gap_routes(gpu_ctx):
     assert R.items_of(res["cigar"][int(res["cigar_off"][x]):int(res["cigar_off"][x + 1])]) == [("=", 500), ("I", 300), ("=", 700)]
 
 
+def test_tie_cases_take_the_reference_choice(gpu_ctx):
+    """The stretches of AC.TIE_CASES, where the optimal alignment is not unique or a route changes, each way round: both sequences are
+    shorter than k, so a pair has no match and is one stretch of smart_align. CIGAR and score are pyref_align's, and the stretches
+    meant for the exact aligner reach it (tests/test_align_host.py puts the same list through the host instantiation)."""
+    seqs = [s for _, r, q, _, _ in AC.TIE_CASES for s in (r, q)]
+    arr = np.frombuffer(b"".join(seqs), dtype=np.uint8).copy()
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    np.cumsum([len(s) for s in seqs], out=off[1:])
+    n_exact = 0
+    for x, (name, r, q, max_gap, _) in enumerate(AC.TIE_CASES):
+        for ri, qi in ((2 * x, 2 * x + 1), (2 * x + 1, 2 * x)):
+            ref, query = seqs[ri], seqs[qi]
+            got, st = api.align_backbone(gpu_ctx, arr, off, ri, qi, 25, api.align_params(max_gap=max_gap))
+            cig, score = R.align_from_backbone(ref, query, 25, max_gap)
+            assert len(got["matches"]) == 0 and got["n_dropped"] == 0, name
+            assert np.array_equal(got["cigar"], R.words(R.normalize(cig))), (name, R.items_of(got["cigar"]), R.normalize(cig))
+            assert got["score"] == score, name
+            exact = bool(ref) and bool(query) and max_gap >= max(len(ref), len(query)) and not (len(ref) == len(query) <= R.SAFE_MISMATCH)
+            assert st["n_small_dp"] + st["n_general_dp"] == int(exact), name
+            if exact:
+                assert score == R.full_dp_score(ref, query), name
+            n_exact += exact
+    assert n_exact >= 10
+
+
 # ---- 6. divergences and skipping ---------------------------------------------------------------------------------------------------------
 def _mixed_set():
     rng = np.random.default_rng(23)

@@ -1050,6 +1050,55 @@ def test_alignment_recovery_neighbour_bin_quirk(gpu_ctx):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("long_cigars", [False, True])
+def test_alignment_recovery_tie_stretches_take_the_oracle_choice(gpu_ctx, long_cigars):
+    """The stretches of tests/align_cases.py::TIE_CASES (the list that tests/test_gpu_align.py puts through the haplotype aligner),
+    each way round, through the aligners of alignment recovery: reads against two alleles built so that smart_align gets exactly the
+    stretch (AC.tie_transfer_case). Pair alignments against the oracle as in the tests above, and the transferred records themselves:
+    start and CIGAR, item for item, against the oracle's transfer of the same read. Every stretch comes as a read of at most 32 bases
+    (which leaves no record: poorly mapped, or transferred and dropped, as a transferred alignment covers at least 50 reference bases,
+    transfer.rs MIN_ALN_SIZE) and as a read of 420 bases and the stretch, which stays in use and whose record stays. Without a long CIGAR in the batch every stretch takes xfer::dp_align; with one (a
+    record of more than 256 items) the kernel's build for long CIGARs runs, where stretches of at most 7 bases a side take
+    xfer::dp_align_small and the others xfer::dp_align."""
+    from tests import align_cases as AC
+    haps, hap_cigar, reads = AC.tie_transfer_case()
+    H = O.HapAlns(2, 3, 0.2)
+    H.add(0, 1, hap_cigar)
+    H.sort()
+    pairs = [{"seq1": s.decode(), "seq2": None, "recs": [(0, st, 0, cg)]} for _, st, s, cg in reads]
+    if long_cigars:                                                           # every other base of 520 in the equal tail is wrong
+        at = len(haps[0]) - 650
+        s = bytearray(haps[0][at:at + 560])
+        for i in range(1, 520, 2): s[i] = ord("A") if s[i] != ord("A") else ord("C")
+        pairs.append({"seq1": bytes(s).decode(), "seq2": None, "recs": [(0, at, 0, "1=1X" * 260 + "40=")]})
+    bg = make_bg(paired=False)
+    p = api.resolve_params(api.default_params(), bg)
+    seqs, seq_off, cflat, cnt_off, _ = locus_arrays([bytearray(h) for h in haps], 25)
+    loc = api.Locus(gpu_ctx, seqs, seq_off, cflat, cnt_off, 25, bg, p)
+    ol = O.OracleLocus(seqs, seq_off, cflat, cnt_off, 25, bg, p)
+    loc.set_hap_alns(H.entries, transfer_fails=3, max_div=0.2)
+    ch = ReadsChunk.from_pairs(pairs)
+    aa = api.AllAlignments.load(loc, ch)
+    n_rec = aa.recover()
+    oa = ol.load_recover(ch, H)
+    compare_gpu_to_oracle(aa, oa, index_fields=())
+    aln_off, recs, cig_off, cigar = aa.records()
+    n_kept = 0
+    for x, (name, st, s, cg) in enumerate(reads):
+        mine = recs[int(aln_off[x]):int(aln_off[x + 1])]
+        assert (int(mine[0]["contig"]), int(mine[0]["pos"])) == (0, st), name
+        got = [(int(r["pos"]), O.cigar_str(cigar[int(cig_off[x]) + int(r["cigar_rel"]):][:int(r["n_cigar"])])) for r in mine[1:]]
+        assert all(int(r["contig"]) == 1 for r in mine[1:]), name
+        if name.endswith("/32"):
+            assert got == [], (name, got)
+        else:
+            assert got == [H.transfer_one(0, 1, st, cg, s, haps[1])], name
+            assert oa.status[x] == cdefs.READ_GOOD and oa.pa_off[x + 1] - oa.pa_off[x] == 2, name
+            n_kept += 1
+    assert n_kept == 2 * len(AC.TIE_CASES) and n_rec >= n_kept
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("read_len,longest", [(10_000, 7000), (500, 600)])
 def test_alignment_recovery_of_10kb_reads_against_the_oracle(gpu_ctx, read_len, longest):
     """BASELINE.json configs[2] in its stated form, at test size: 10-kb single-end ONT reads (3 % errors, CIGARs of ~670 operations),
