@@ -243,7 +243,9 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       through the f64 kernel);   "db_chunk_cols"   columns of the bit matrix per pass of lcty_db_divergences (default: what fits 1/8 of
  *       the free device memory, 256 MB at most);   "basis_batch_words"   CIGAR words per batch of lcty_basis_windows (default: what fits a
  *       quarter of the free device memory; an entry with more words travels alone);   "align_batch_pairs"   pairs per batch of
- *       lcty_align_haplotypes (default: sized from the free device memory);   "align_hash_bits"   bits kept of a backbone window's hash
+ *       lcty_align_haplotypes (default: sized from the free device memory);   "align_match_budget"   bytes for the k-mer matches of such
+ *       a batch, 20 a match (default: a quarter of the free device memory, at least 64 MB; a batch with more is cut to its longest
+ *       prefix of pairs that fits, a single pair always runs);   "align_hash_bits"   bits kept of a backbone window's hash
  *       (default 64; fewer: collisions, which the comparison of the bases must reject);   "align_dp_cells"   cells of the largest
  *       stretch the exact aligner takes (default 2^26; a larger stretch is dropped to align_simple and counted in n_dropped — this one
  *       changes CIGARs, as the limit itself does).

@@ -712,7 +712,8 @@ int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seq
             build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
             size_t free_b = 0, total_b = 0;
             LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
-            const uint64_t budget = std::max<uint64_t>(free_b / 4, 64ull << 20);
+            // bytes for the matches of a batch (20 a match); knob align_match_budget: a test reaches the "do not fit" return of run_batch
+            const uint64_t budget = static_cast<uint64_t>(ctx->knob("align_match_budget", static_cast<int64_t>(std::max<uint64_t>(free_b / 4, 64ull << 20))));
             uint64_t max_len = 0;
             for (uint32_t i = 0; i < n_seqs; i++) max_len = std::max(max_len, seq_off[i + 1] - seq_off[i]);
             // a pair: per k 12 bytes a reference window (counts, offsets), 8 a query column (tree), and about 20 a match

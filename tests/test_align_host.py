@@ -6,6 +6,7 @@ import pytest
 
 from locityper_amd import api, io
 from tests import align_cases as AC
+from tests import oracle_ffi as O
 from tests import pyref_align as R
 
 
@@ -249,3 +250,128 @@ def test_header_host_instantiation_on_tie_cases():
             assert all(ln == 1 for _, ln in got)
         routes.add("simple" if simple else "exact" if exact else "gap" if not (r and q) else "straight")
     assert routes == {"simple", "exact", "gap", "straight"}
+
+
+# ---- 7. the designed sets for the limits of the device aligner are fit for purpose (tests/test_gpu_align_limits.py runs them) -----------------
+LEVEL_DIM, LEVEL_CELLS = (255, 2047, 16383), (1 << 16, 1 << 22, 1 << 26)     # kLevelDim, kLevelCells of lcty_align.hip
+
+
+def _level(n, m):
+    return next(l for l in range(3) if n <= LEVEL_DIM[l] and m <= LEVEL_DIM[l] and (n + 1) * (m + 1) <= LEVEL_CELLS[l])
+
+
+def _plan(name, r, q, k=AC.K):
+    c = AC.by_name(name)
+    m, _, path = AC.reference(name, r, q, k)
+    return m, path, AC.plan_bound(c.seqs[r], c.seqs[q], m, path, k, c.max_gap)
+
+
+@pytest.mark.parametrize("shape", AC.LEVEL_SHAPES, ids=[s[0] for s in AC.LEVEL_SHAPES])
+def test_level_cases_are_one_stretch_of_the_intended_shape(shape):
+    name, n, m, pairs, max_gap, n_level, n_dropped = shape
+    c = AC.by_name("lv_" + name)
+    assert tuple(int(x) for x in name.split("x")) == c.stretch[pairs[0]]
+    assert not any(c.middles[0][p:p + AC.K] in c.middles[1] for p in range(n - AC.K + 1))          # R and Q share no 25-mer
+    for r, q in pairs:
+        matches, path, (anchors, stretches) = _plan(c.name, r, q)
+        a, b = c.stretch[(r, q)]
+        # the flanks' windows on their two diagonals and nothing else: no unintended match
+        want = [(p, p) for p in range(AC.FLANK - AC.K + 1)] + [(AC.FLANK + a + p, AC.FLANK + b + p) for p in range(AC.FLANK - AC.K + 1)]
+        assert matches == want and path == list(range(len(want)))
+        assert anchors == 2 and stretches == [("dropped" if n_dropped else "exact", a, b, min(a, b) + 1 if n_dropped else a + b)]
+        if not n_dropped:
+            assert [int(l == _level(a, b)) for l in range(3)] == n_level
+        counters = {}
+        if name in AC.BEYOND_ORACLE:
+            with pytest.raises(R.UnfitCase):
+                R.align_from_path(c.seqs[r], c.seqs[q], matches, path, AC.K, max_gap)
+            continue
+        cig, score = R.align_from_path(c.seqs[r], c.seqs[q], matches, path, AC.K, max_gap, counters=counters)     # no UnfitCase
+        assert counters.get("dropped", 0) == n_dropped
+        AC.check_cigar(R.normalize(cig), score, c.seqs[r], c.seqs[q])
+        if n_dropped:                                                          # the oracle's aligner itself refuses this one too
+            assert O.dp_align(c.seqs[r][AC.FLANK:-AC.FLANK], c.seqs[q][AC.FLANK:-AC.FLANK])[0] == R.DROPPED
+    # the limits the shapes stand at
+    assert _level(255, 255) == 0 and _level(255, 256) == 1 and _level(2047, 2047) == 1 and _level(2047, 2048) == 2 and _level(2048, 1) == 2
+
+
+def test_reuse_cases_fill_their_level_beyond_its_lanes():
+    c = AC.by_name("reuse1")
+    widths = set()
+    assert len(c.pairs) == 136 > 128
+    for r, q in c.pairs:
+        matches, path, (anchors, stretches) = _plan("reuse1", r, q)
+        assert anchors == 2 and len(stretches) == 1 and stretches[0][0] == "exact"
+        _, a, b, _ = stretches[0]
+        assert _level(a, b) == 1, (r, q, a, b)
+        assert len(matches) == len(path) == len(c.seqs[r]) - a - 2 * (AC.K - 1)           # the two flank diagonals only
+        widths.add(b)
+        R.align_from_path(c.seqs[r], c.seqs[q], matches, path, AC.K, c.max_gap)            # answers: no UnfitCase
+    assert len(widths) > 8
+    c = AC.by_name("reuse2")
+    assert len(c.pairs) == 24
+    for r, q in c.pairs:
+        matches, path, (anchors, stretches) = _plan("reuse2", r, q)
+        a, b = len(c.seqs[r]) - 2 * AC.FLANK, len(c.seqs[q]) - 2 * AC.FLANK
+        assert anchors == 2 and stretches == [("exact", a, b, a + b)] and max(a, b) == 2048 and 8 <= min(a, b) <= 19 and _level(a, b) == 2
+        assert len(matches) == 2 * (AC.FLANK - AC.K + 1)
+        R.align_from_path(c.seqs[r], c.seqs[q], matches, path, AC.K, c.max_gap)
+
+
+def test_tight_bound_case_fills_the_bound():
+    c = AC.by_name("tight_bound")
+    shape = {"X=X": ("straight", 3, 3, 3), "=X=": ("straight", 3, 3, 3), "9x12": ("simple", 9, 12, 10), "12x9": ("simple", 12, 9, 10),
+             "D": ("gap", 5, 0, 1), "I": ("gap", 0, 7, 1)}
+    for r, q in c.pairs:
+        kinds = c.kinds[(r, q)]
+        matches, path, (anchors, stretches) = _plan("tight_bound", r, q)
+        assert len(matches) == len(path) == anchors == len(kinds) + 1            # anchors of exactly k bases: one 25-mer each, no other match
+        want = [shape[kd] for kd in kinds]
+        if r > q:
+            want = [(t, m, n, b) for t, n, m, b in want]
+        assert stretches == want and len(stretches) >= 6
+        items, count = AC.tight_bound_items(r, q)
+        assert len(items) == count
+        if "=X=" not in kinds:
+            assert count == anchors + sum(s[3] for s in stretches) and sum(s[0] != "gap" for s in stretches) >= 6
+            assert min(sum(s[0] == t for s in stretches) for t in ("straight", "simple", "gap")) >= 3      # an undercount by one in any route outgrows the start of 2
+
+
+def test_lowcomplexity_and_lengths_and_random_cases_answer():
+    c = AC.by_name("lowcomplexity")
+    assert max(len(AC.reference(c.name, r, q, 5)[0]) for r, q in c.pairs) > 10000
+    for name in ["lowcomplexity", "lengths"] + [f"random_k{k}" for k in AC.RANDOM_KS]:
+        c = AC.by_name(name)
+        for r, q in c.pairs:
+            for k in c.ks:
+                m, chain, path = AC.reference(name, r, q, k)
+                cig, score = R.align_from_path(c.seqs[r], c.seqs[q], m, path, k, c.max_gap)       # no UnfitCase
+                AC.check_cigar(R.normalize(cig), score, c.seqs[r], c.seqs[q], AC.optimum(name, r, q))
+    c = AC.by_name("lengths")
+    assert [len(s) for s in c.seqs] == [1024] + AC.LENGTHS and len(c.pairs) == 24
+    assert len(AC.reference("lengths", 0, 4, AC.K)[0]) == 0 and len(AC.reference("lengths", 0, 3, AC.K)[0]) == 0     # 25 bases with a substitution, 24 bases
+    assert sum(len(c.pairs) for c in AC.limit_cases() if c.name.startswith("random")) == AC.N_RANDOM
+    for k in AC.RANDOM_KS:
+        c = AC.by_name(f"random_k{k}")
+        assert all(60 <= len(c.seqs[r]) <= 400 for r, _ in c.pairs)
+        assert any(b"N" in c.seqs[q] for _, q in c.pairs) and any(c.seqs[q] != c.seqs[q].upper() for _, q in c.pairs)
+
+
+def test_header_host_instantiation_on_level_shapes():
+    """the cell, the end state and the walk back of lcty_gotoh.hpp, compiled for the host, on the stretches of the level cases the
+    oracle's aligner answers: score and CIGAR of pyref_align.smart_align at up to 2 047 x 2 048"""
+    probe = _probe()
+    lib = probe.host_lib()
+    for name, _, _, pairs, max_gap, _, n_dropped in AC.LEVEL_SHAPES:
+        if name in AC.BEYOND_ORACLE or n_dropped:
+            continue
+        c = AC.by_name("lv_" + name)
+        for r, q in pairs:
+            a, b = c.seqs[r][AC.FLANK:-AC.FLANK], c.seqs[q][AC.FLANK:-AC.FLANK]
+            cig = R.Cig()
+            want = R.smart_align(R.norm(a), 0, len(a), R.norm(b), 0, len(b), max_gap, cig)
+            score, pushes = probe.host_stretch(a, b, max_gap, lib)
+            joined = R.Cig()
+            for op, ln in pushes:
+                joined.push_checked(R.OPS[op], ln)
+            assert score == want == R.full_dp_score(a, b) and joined.t == [list(t) for t in R.normalize(cig)], name

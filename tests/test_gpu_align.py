@@ -12,23 +12,7 @@ from tests import pyref_align as R
 pytestmark = pytest.mark.gpu
 
 TASKS = [(c.name, r, q, k) for c in AC.cases() for r, q in c.pairs for k in c.ks]
-_bb = {}
-
-
-def backbone(ctx, name, ref, query, k, hash_bits=None):
-    """lcty_align_backbone of one task, once per session"""
-    key = (name, ref, query, k, hash_bits)
-    if key not in _bb:
-        c = AC.by_name(name)
-        seqs, off = c.arrays()
-        if hash_bits is not None:
-            ctx.set_knob("align_hash_bits", hash_bits)
-        try:
-            _bb[key] = api.align_backbone(ctx, seqs, off, ref, query, k, api.align_params(max_gap=c.max_gap))[0]
-        finally:
-            if hash_bits is not None:
-                ctx.set_knob("align_hash_bits", -1)
-    return _bb[key]
+backbone, check_cigar = AC.backbone, AC.check_cigar
 
 
 _full = {}
@@ -64,63 +48,22 @@ def full(ctx, name):
     return _full[name]
 
 
-def check_cigar(items, score, ref, query, optimum=None):
-    """assertion 5: the properties every alignment has"""
-    ref, query = R.norm(ref), R.norm(query)
-    i = j = 0
-    for x, (op, ln) in enumerate(items):
-        assert ln > 0 and op in "=XID"
-        assert x == 0 or items[x - 1][0] != op, "adjacent equal operations"
-        if op == "=":
-            assert ref[i:i + ln] == query[j:j + ln]
-        if op == "X":
-            assert all(a != b for a, b in zip(ref[i:i + ln], query[j:j + ln]))
-        i += ln if op in "=XD" else 0
-        j += ln if op in "=XI" else 0
-    assert (i, j) == (len(ref), len(query)), "the CIGAR does not consume both sequences"
-    assert score == R.calculate_score(items)
-    if optimum is not None:
-        assert score <= optimum
-
-
 # ---- 1. stage A -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,ref,query,k", TASKS)
 def test_stage_a_matches(gpu_ctx, name, ref, query, k):
-    want = np.array(AC.reference(name, ref, query, k)[0], dtype=np.uint32).reshape(-1, 2)
-    assert np.array_equal(backbone(gpu_ctx, name, ref, query, k)["matches"], want)
-    # eight bits of hash: every bucket is full of collisions, the comparison of the bases has to reject them
-    assert np.array_equal(backbone(gpu_ctx, name, ref, query, k, hash_bits=8)["matches"], want)
+    AC.check_stage_a(gpu_ctx, name, ref, query, k)
 
 
 # ---- 2. stage B -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,ref,query,k", TASKS)
 def test_stage_b_chain(gpu_ctx, name, ref, query, k):
-    matches, score, _ = AC.reference(name, ref, query, k)
-    got = backbone(gpu_ctx, name, ref, query, k)
-    assert got["chain_score"] == score
-    path = got["path"].tolist()
-    assert all(0 <= x < len(matches) for x in path) and (len(path) > 0) == (len(matches) > 0)
-    total = k if path else 0
-    for a, b in zip(path, path[1:]):
-        assert a < b, "the path is not strictly ordered"
-        (i1, j1), (i2, j2) = matches[a], matches[b]
-        diagonal = (i2, j2) == (i1 + 1, j1 + 1)
-        assert diagonal or (i1 + k <= i2 and j1 + k <= j2), "a step is neither a diagonal + 1 nor clears k in both coordinates"
-        # a diagonal neighbour that also clears k cannot exist (k >= 5), so the step's worth is unambiguous
-        total += 1 if diagonal else k
-    assert total == score, "the path does not add up to the chain score"
+    AC.check_stage_b(gpu_ctx, name, ref, query, k)
 
 
 # ---- 3. stage C -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,ref,query,k", TASKS)
 def test_stage_c_gap_fill(gpu_ctx, name, ref, query, k):
-    c = AC.by_name(name)
-    matches = AC.reference(name, ref, query, k)[0]
-    got = backbone(gpu_ctx, name, ref, query, k)
-    cig, score = R.align_from_path(c.seqs[ref], c.seqs[query], matches, got["path"].tolist(), k, c.max_gap)
-    assert np.array_equal(got["cigar"], R.words(R.normalize(cig)))
-    assert got["score"] == score and got["n_dropped"] == 0
-    check_cigar(R.items_of(got["cigar"]), got["score"], c.seqs[ref], c.seqs[query], AC.optimum(name, ref, query))
+    AC.check_stage_c(gpu_ctx, name, ref, query, k)
 
 
 # ---- 4. + 5. end to end ------------------------------------------------------------------------------------------------------------------

@@ -233,6 +233,22 @@ def test_knobs_are_named_and_checked():
     assert L.lcty_ctx_set_knob(None, b"solve_budget_mb", 1) == cdefs.ERR_INVALID_INPUT
 
 
+def test_align_knobs_are_in_the_list_and_in_the_header():
+    """the knobs of lcty_align_haplotypes: each is in the list lcty_ctx_set_knob accepts (lcty_api.hip), has its words in the knob
+    paragraph of the header, and is what lcty_align.hip asks its context for"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    read = lambda *p: open(os.path.join(root, *p)).read()
+    api_src, header, align_src = read("locityper_amd", "csrc", "lcty_api.hip"), read("include", "locityper_hip.h"), read("locityper_amd", "csrc", "lcty_align.hip")
+    known = api_src[api_src.index("known[] = {"):api_src.index("nullptr};")]
+    paragraph = header[:header.index("int32_t lcty_ctx_set_knob(")]
+    asked = set(re.findall(r'knob\("(align_[a-z_]+)"', align_src))
+    assert asked == {"align_batch_pairs", "align_hash_bits", "align_dp_cells", "align_match_budget"}
+    for name in asked:
+        assert f'"{name}"' in known and f'"{name}"   ' in paragraph, name
+
+
 def test_mapper_and_solver_defaults():
     """lcty_map_params_default / _default_long (host only): strobealign's and minimap2's scores, the long route's chaining limits; the struct is
     the header's (15 four-byte fields). lcty_solver_default for the exact solver: HiGHS' default relative gap of 1e-4, which the reference
