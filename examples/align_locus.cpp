@@ -1,5 +1,5 @@
-// examples/align_locus.cpp — the pairwise alignments of one locus's haplotypes (`locityper align --transitive 0`, the backbone
-// strategy of src/seq/align.rs) through the C ABI, files in, files out:
+// examples/align_locus.cpp — the pairwise alignments of one locus's haplotypes (`locityper align`: the backbone strategy of
+// src/seq/align.rs, or with --tr-div the transitive one) through the C ABI, files in, files out:
 //
 //   <haplotypes.fa.gz>  the haplotypes of the locus                                            (lcty_fasta_read)
 //   -> <out.paf.gz>     DB/loci/<locus>/haplotypes.paf.gz                                      (lcty_align_haplotypes, lcty_paf_write_text,
@@ -7,6 +7,7 @@
 //   pairs as load_pairs has them (command/align.rs:256-299; duplicates are dropped, the first one counts):
 //   [--all]  [--pairs-file FILE: lines `query ref`, '#' comments]  [--against NAME ...: NAME as the reference of every other haplotype]
 //   [-D THRESH_DIV] [--against-div DIV] [--skip-div] [-k K1,K2,..] [-g MAX_GAP]
+//   [--tr-div DIV: lcty_align_haplotypes_transitive with that divergence; without it the backbone route]  [--tr-anchor SIZE]
 //
 // Prints one JSON line with the counts and the per-stage milliseconds. Build: see tests/test_gpu_align_example.py.
 #include <cstdint>
@@ -30,7 +31,9 @@ int main(int argc, char** argv) {
     lcty_align_params_default(&prm);
     std::string fa, out_path, pairs_file;
     std::vector<std::string> against;
-    bool all = false;
+    bool all = false, transitive = false;
+    lcty_align_tr_params trp;
+    lcty_align_tr_params_default(&trp);
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--all") all = true;
@@ -39,6 +42,8 @@ int main(int argc, char** argv) {
         else if (a == "-D" && i + 1 < argc) prm.thresh_div = std::atof(argv[++i]);
         else if (a == "--against-div" && i + 1 < argc) prm.against_div = std::atof(argv[++i]);
         else if (a == "--skip-div") prm.skip_div = 1;
+        else if (a == "--tr-div" && i + 1 < argc) { trp.transitive_div = std::atof(argv[++i]); transitive = true; }
+        else if (a == "--tr-anchor" && i + 1 < argc) trp.transitive_anchor = static_cast<uint32_t>(std::strtoul(argv[++i], nullptr, 10));
         else if (a == "-g" && i + 1 < argc) prm.max_gap = static_cast<uint32_t>(std::strtoul(argv[++i], nullptr, 10));
         else if (a == "-k" && i + 1 < argc) {
             std::stringstream ss(argv[++i]);
@@ -52,7 +57,7 @@ int main(int argc, char** argv) {
     }
     if (fa.empty() || out_path.empty()) {
         std::fprintf(stderr, "usage: align_locus <haplotypes.fa.gz> <out.paf.gz> [--all] [--pairs-file FILE] [--against NAME ...] [-D DIV] [--against-div DIV] "
-                             "[--skip-div] [-k K1,K2,..] [-g MAX_GAP]\n");
+                             "[--skip-div] [-k K1,K2,..] [-g MAX_GAP] [--tr-div DIV] [--tr-anchor SIZE]\n");
         return 2;
     }
     uint32_t n = 0; uint64_t nl = 0, sl = 0;
@@ -99,8 +104,15 @@ int main(int argc, char** argv) {
     ok(lcty_ctx_create(0, &ctx), "lcty_ctx_create");
     lcty_align_out res;
     lcty_align_stats st;
-    ok(lcty_align_haplotypes(ctx, n, seqs.data(), off.data(), ref.size(), ref.data(), query.data(), against.empty() ? nullptr : against_flag.data(), &prm, &res,
-                             &st), "align_sequences");
+    lcty_align_tr_out tro{};
+    lcty_align_tr_stats trs{};
+    if (transitive)
+        ok(lcty_align_haplotypes_transitive(ctx, n, seqs.data(), off.data(), ref.size(), ref.data(), query.data(), against.empty() ? nullptr : against_flag.data(),
+                                            &prm, &trp, &res, &tro, &st, &trs), "align_sequences");
+    else
+        ok(lcty_align_haplotypes(ctx, n, seqs.data(), off.data(), ref.size(), ref.data(), query.data(), against.empty() ? nullptr : against_flag.data(), &prm, &res,
+                                 &st), "align_sequences");
+    lcty_align_tr_out_free(&tro);
     lcty_ctx_destroy(ctx);
     std::string blob;
     for (uint32_t a = 0; a < n; a++) { blob += name_of[a]; blob.push_back('\0'); }
@@ -112,13 +124,13 @@ int main(int argc, char** argv) {
     lcty_align_out_free(&res);
     std::printf("{\"haplotypes\": %u, \"pairs\": %llu, \"aligned\": %llu, \"skipped\": %llu, \"dropped\": %llu, \"kmer_matches\": %llu, \"chain_points\": %llu, "
                 "\"stretches\": {\"trivial\": %llu, \"simple\": %llu, \"small_dp\": %llu, \"general_dp\": %llu}, \"dp_cells\": %llu, \"batches\": %llu, "
-                "\"bytes_h2d\": %llu, \"bytes_d2h\": %llu, \"ms\": {\"div\": %.3f, \"index\": %.3f, \"match\": %.3f, \"chain\": %.3f, \"fill\": %.3f, "
+                "\"accelerated\": %llu, \"rounds\": %llu, \"bytes_h2d\": %llu, \"bytes_d2h\": %llu, \"ms\": {\"div\": %.3f, \"index\": %.3f, \"match\": %.3f, \"chain\": %.3f, \"fill\": %.3f, "
                 "\"select\": %.3f, \"total\": %.3f}}\n",
                 n, static_cast<unsigned long long>(ref.size()), static_cast<unsigned long long>(st.n_aligned), static_cast<unsigned long long>(st.n_skipped),
                 static_cast<unsigned long long>(st.n_dropped), static_cast<unsigned long long>(st.n_kmer_matches), static_cast<unsigned long long>(st.n_chain_points),
                 static_cast<unsigned long long>(st.n_trivial), static_cast<unsigned long long>(st.n_simple), static_cast<unsigned long long>(st.n_small_dp),
                 static_cast<unsigned long long>(st.n_general_dp), static_cast<unsigned long long>(st.dp_cells), static_cast<unsigned long long>(st.n_batches),
-                static_cast<unsigned long long>(st.bytes_h2d), static_cast<unsigned long long>(st.bytes_d2h), st.div_ms, st.index_ms, st.match_ms, st.chain_ms,
+                static_cast<unsigned long long>(trs.n_accelerated), static_cast<unsigned long long>(trs.n_rounds), static_cast<unsigned long long>(st.bytes_h2d), static_cast<unsigned long long>(st.bytes_d2h), st.div_ms, st.index_ms, st.match_ms, st.chain_ms,
                 st.fill_ms, st.select_ms, st.total_ms);
     return 0;
 }

@@ -248,7 +248,9 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       prefix of pairs that fits, a single pair always runs);   "align_hash_bits"   bits kept of a backbone window's hash
  *       (default 64; fewer: collisions, which the comparison of the bases must reject);   "align_dp_cells"   cells of the largest
  *       stretch the exact aligner takes (default 2^26; a larger stretch is dropped to align_simple and counted in n_dropped — this one
- *       changes CIGARs, as the limit itself does).
+ *       changes CIGARs, as the limit itself does);   "align_cigar_store_mb"   megabytes of device memory for the finished CIGARs of
+ *       lcty_align_haplotypes_transitive (default: an eighth of the free device memory, at least 64; a call whose CIGARs outgrow it is
+ *       LCTY_ERR_UNSUPPORTED naming this knob — it never takes another route).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -1195,6 +1197,50 @@ int32_t lcty_align_backbone(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs,
 void    lcty_align_backbone_out_free(lcty_align_backbone_out* out);
 int32_t lcty_paf_write_text(const lcty_align_params* params, uint32_t n_seqs, const char* names, const uint64_t* seq_off, uint64_t n_pairs,
                             const uint32_t* ref_id, const uint32_t* query_id, const lcty_align_out* res, char* out, uint64_t cap, uint64_t* needed);
+
+/* ---- transitive haplotype alignments (locityper align --tr-div D, D > 0: the default route of the tool, D = 0.01) ---------------------
+ * lcty_align_haplotypes_transitive = lcty_align_haplotypes with the single-thread TransitiveStrategy of src/seq/align.rs:452-514 run
+ * over the pairs in input order (the multi-thread form is racy by its own comment, 581-583, and defines nothing). State: closest[q] =
+ * (reference id, that pair's CIGAR, its dv), and the finished CIGARs with their direction (DirectedCigar, 428-450). For the pair
+ * (k = ref, i = query):
+ *   route 2     closest[k] = (j, ..) exists and {i, j} is aligned: i-k is composed of i-j and j-k through j (first clause, 481-484);
+ *   route 3     else closest[i] = (j, ..) exists and {k, j} is aligned: the same through that j (second clause, 485-488);
+ *   route 1     else the backbone alignment, exactly as lcty_align_haplotypes makes it;
+ *   save        dv = nerrs / aln_len in f64 (process_pair 652-665); the CIGAR is kept; if dv <= transitive_div and closest[i] is empty
+ *               or has a strictly greater dv, closest[i] = (k, CIGAR, dv) (save_cigar, 504-513).
+ * A pair skipped by its minimizer divergence (route 0) reads and writes nothing. transitive_div <= 0, or fewer than 16 pairs in the
+ * call (align.rs:784): every pair goes the backbone route and the result is lcty_align_haplotypes' bit for bit (n_rounds 0).
+ * The composed CIGAR is Cigar::find_transitive_alignment (cigar.rs:1389-1414) = transfer_alignment::<true> (1248-1368) as written: both
+ * full_sequence_match shortcuts (they return before optimize), the four direction combinations, anchors of transitive_anchor equal
+ * bases with ANCHOR_MARGIN 5, smart_align with max_gap for every stretch between anchors and for the tail, Cigar::optimize(1000, 51)
+ * at the end. Its score is calculate_score of the CIGAR (wfa.rs:87-99), its best_k 0. Aligner, tie rules, N handling and the merging of
+ * equal neighbouring operations are those of the section above (differences 2-7); merging is applied throughout: the CIGARs the walk
+ * reads are the merged ones this library returns, and optimize looks for its anchors in the merged walk. A stretch beyond the largest
+ * scratch level takes align_simple and counts in n_dropped, as there. Of the four direction combinations three can occur: the CIGAR of
+ * closest[k] always has k as its query, so "j-k with k the reference" meets "i-j with i the reference" in neither clause (the kernels take it all the same; no test reaches
+ * that path on the device).
+ * Schedule: rounds. A round is the longest prefix of the remaining pairs in which no pair reads a cell an earlier pair of the prefix
+ * writes — read: closest[k], closest[i] and the CIGAR cells its clause tests; written: its own CIGAR cell and closest[i] (whatever dv
+ * turns out to be). With lcty_align_all_pairs a round is one row of the triangle. The host decides a round from its mirror of closest
+ * (id, dv) and of which cells exist; the round's backbone pairs go through the usual batches, its transitive pairs through the
+ * transitive kernels (one lane per pair: plan, fill per scratch level, optimize, counts; the walk and optimize write into per-round
+ * temporaries sized by the plan's bounds, which are not part of the store's budget); finished CIGARs are gathered into one store on the
+ * device (knob align_cigar_store_mb), only the counts of a round come back, the store is downloaded once at the end.
+ * out: as lcty_align_haplotypes. tr_out: per pair route (0 skipped, 1 backbone, 2 first clause, 3 second clause) and via (j, or
+ * UINT32_MAX); released with lcty_align_tr_out_free. Input errors are those of lcty_align_haplotypes; transitive_div > 1 or NaN and
+ * transitive_anchor 0 are LCTY_ERR_INVALID_INPUT. */
+typedef struct lcty_align_tr_params { double transitive_div; uint32_t transitive_anchor; uint32_t _pad0; } lcty_align_tr_params;  /* 0.01, 101 */
+typedef struct lcty_align_tr_out   { uint8_t* route; uint32_t* via; } lcty_align_tr_out;
+typedef struct lcty_align_tr_stats {
+    uint64_t n_rounds, n_accelerated, n_shortcut, n_tr_stretches, tr_dp_cells, store_bytes;   /* shortcut: a full_sequence_match copy; stretches, cells: of the transitive kernels */
+    double   plan_ms, tr_fill_ms, optimize_ms, count_ms;   /* wall time with the stream drained: both planning passes, the walk, optimize, counts + gather into the store */
+} lcty_align_tr_stats;
+void    lcty_align_tr_params_default(lcty_align_tr_params* params);
+int32_t lcty_align_haplotypes_transitive(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs,
+                                         const uint32_t* ref_id, const uint32_t* query_id, const uint8_t* against, const lcty_align_params* params,
+                                         const lcty_align_tr_params* tr_params, lcty_align_out* out, lcty_align_tr_out* tr_out,
+                                         lcty_align_stats* stats, lcty_align_tr_stats* tr_stats);
+void    lcty_align_tr_out_free(lcty_align_tr_out* out);
 
 #ifdef __cplusplus
 }

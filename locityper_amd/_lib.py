@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -53,6 +53,10 @@ SIGNATURES = {
     "lcty_align_out_free": (None, [P(AlignOut)]),
     "lcty_align_backbone": (I32, [VP, U32, VP, VP, U32, U32, U32, P(AlignParams), P(AlignBackboneOut), P(AlignStats)]),
     "lcty_align_backbone_out_free": (None, [P(AlignBackboneOut)]),
+    "lcty_align_tr_params_default": (None, [P(AlignTrParams)]),
+    "lcty_align_haplotypes_transitive": (I32, [VP, U32, VP, VP, U64, VP, VP, VP, P(AlignParams), P(AlignTrParams), P(AlignOut), P(AlignTrOut),
+                                               P(AlignStats), P(AlignTrStats)]),
+    "lcty_align_tr_out_free": (None, [P(AlignTrOut)]),
     "lcty_paf_write_text": (I32, [P(AlignParams), U32, C.c_char_p, VP, U64, VP, VP, P(AlignOut), VP, U64, P(U64)]),
     "lcty_last_error": (C.c_char_p, []),
     "lcty_version": (C.c_char_p, []),

@@ -1244,6 +1244,44 @@ def align_haplotypes(ctx, seqs, seq_off, ref_id, query_id, params=None, against=
     return res, st.as_dict()
 
 
+def align_tr_params(**kw):
+    """lcty_align_tr_params_default (transitive_div 0.01, transitive_anchor 101) with overrides."""
+    p = cdefs.AlignTrParams()
+    lib().lcty_align_tr_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def align_haplotypes_transitive(ctx, seqs, seq_off, ref_id, query_id, params=None, tr_params=None, against=None):
+    """lcty_align_haplotypes_transitive (`locityper align --tr-div`): the dict of align_haplotypes plus route (0 skipped, 1 backbone,
+    2 / 3 composed through `via` by the first / second clause) and via (2^32 - 1: none); stats dict with the fields of both stats structs."""
+    p = params if params is not None else align_params()
+    tp = tr_params if tr_params is not None else align_tr_params()
+    sq, off = _seq_arrays(seqs, seq_off)
+    r = np.ascontiguousarray(ref_id, dtype=np.uint32); q = np.ascontiguousarray(query_id, dtype=np.uint32)
+    if len(r) != len(q):
+        raise ValueError("ref_id and query_id differ in length")
+    ag = None if against is None else np.ascontiguousarray(against, dtype=np.uint8)
+    o, to, st, ts = cdefs.AlignOut(), cdefs.AlignTrOut(), cdefs.AlignStats(), cdefs.AlignTrStats()
+    check(lib().lcty_align_haplotypes_transitive(ctx._h, len(off) - 1, sq.ctypes.data, off.ctypes.data, len(r), r.ctypes.data, q.ctypes.data,
+                                                 None if ag is None else ag.ctypes.data, C.byref(p), C.byref(tp), C.byref(o), C.byref(to),
+                                                 C.byref(st), C.byref(ts)))
+    try:
+        n = int(o.n_pairs)
+        res = {"aligned": _copy(o.aligned, n, np.uint8), "n_matches": _copy(o.n_matches, n, np.uint32), "aln_len": _copy(o.aln_len, n, np.uint32),
+               "nerrs": _copy(o.nerrs, n, np.uint32), "score": _copy(o.score, n, np.int32), "best_k": _copy(o.best_k, n, np.uint32),
+               "um": _copy(o.um, n, np.uint32), "md": _copy(o.md, n, np.float64), "cigar_off": _copy(o.cigar_off, n + 1, np.uint64),
+               "route": _copy(to.route, n, np.uint8), "via": _copy(to.via, n, np.uint32)}
+        res["cigar"] = _copy(o.cigar, int(res["cigar_off"][-1]), np.uint32)
+    finally:
+        lib().lcty_align_out_free(C.byref(o))
+        lib().lcty_align_tr_out_free(C.byref(to))
+    return res, {**st.as_dict(), **ts.as_dict()}
+
+
 def align_backbone(ctx, seqs, seq_off, ref, query, k, params=None):
     """lcty_align_backbone: one pair, one k, every stage: dict of matches [n][2] (pos1, pos2), chain_score, path (match indices),
     cigar (raw words), score, n_dropped; stats dict."""

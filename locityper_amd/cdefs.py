@@ -171,6 +171,23 @@ class AlignStats(C.Structure):
         return {n: (list(getattr(self, n)) if n == "n_level" else getattr(self, n)) for n, _ in self._fields_}
 
 
+class AlignTrParams(C.Structure):
+    """`locityper align --tr-div / --tr-anchor` (src/seq/align.rs:59-60): 0.01, 101."""
+    _fields_ = [("transitive_div", C.c_double), ("transitive_anchor", C.c_uint32), ("_pad0", C.c_uint32)]
+
+
+class AlignTrOut(C.Structure):
+    _fields_ = [("route", C.c_void_p), ("via", C.c_void_p)]
+
+
+class AlignTrStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rounds", "n_accelerated", "n_shortcut", "n_tr_stretches", "tr_dp_cells", "store_bytes")] + \
+               [(n, C.c_double) for n in ("plan_ms", "tr_fill_ms", "optimize_ms", "count_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class BgReadsView(C.Structure):
     """The records of the background interval as load_alns keeps them (preproc.rs:988-1028)."""
     _fields_ = [

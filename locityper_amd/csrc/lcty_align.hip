@@ -15,7 +15,8 @@
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
 #include "lcty_gotoh.hpp"
-#include "lcty_transfer_device.hpp"                 // xfer::DP_SMALL, the size class of the statistics
+#include "lcty_transfer_device.hpp"                 // xfer::DP_SMALL, the size class of the statistics; double_move and the operation classes
+#include "lcty_align_internal.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -240,6 +241,7 @@ struct Levels { Lim l[kLevels]; };                              // the levels' l
 struct PlanVisitor {
     uint32_t max_gap; Lim top; Levels lv; uint32_t level; uint64_t bound;
     __device__ void anchor(uint32_t) { bound++; }
+    __device__ void item(uint32_t, uint32_t) { bound++; }
     __device__ void stretch(uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2) {
         const uint32_t n = i2 - i1, m = j2 - j1;
         const gotoh::Route route = gotoh::route(n, m, max_gap);
@@ -318,6 +320,7 @@ struct FillVisitor {
         return -gotoh::best_of(end);
     }
     __device__ void anchor(uint32_t len) { cg.push(OP_EQ, len); }
+    __device__ void item(uint32_t op, uint32_t len) { cg.push(op, len); }
     // smart_align (wfa.rs:280-321) with max_gap as the threshold
     __device__ void stretch(uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2) {
         const uint32_t n = i2 - i1, m = j2 - j1;
@@ -393,6 +396,98 @@ __global__ __launch_bounds__(64) void align_gather_kernel(uint32_t nk, const Pai
     for (uint32_t x = threadIdx.x; x < res[p].n_words; x += 64) out[out_off[p] + x] = w[x];
 }
 
+// Transitive route -----------------------------------------------------------------------------------------------------------------------
+// Cigar::find_transitive_alignment (cigar.rs:1389-1414) = transfer_alignment::<true> (1248-1368): the alignment of query i to reference
+// k out of the finished alignments i-j and j-k. The two CIGARs are walked side by side (double_move of lcty_cigar_walk.hpp);
+// where both stand in a long enough '=' the operation is copied, what lies between two such anchors goes to smart_align — the very
+// stretch() of stage C. Then Cigar::optimize (1167-1237; lcty_transfer_device.hpp holds its resumable form for wavefronts that
+// carry 64 reads; here a lane has one pair and walks straight through; the predicates are shared). Both walks are templates of
+// lcty_cigar_walk.hpp over the visitors of stage C: v.item() for a copied operation, v.stretch() for smart_align. One lane per task.
+struct TrTaskDev { uint64_t ij_off, jk_off; uint32_t ij_n, jk_n, ref, qry, inv, _pad; };      // inv: bit 0 i-j is read inverted, bit 1 j-k
+using trwalk::TrCig; using trwalk::walk_transitive; using trwalk::walk_optimize;          // lcty_cigar_walk.hpp: the host probe instantiates them too
+
+// PASS 0: the walk of the two CIGARs out of the store; PASS 1: optimize over the CIGAR pass 0 left (src), a plain copy for a shortcut
+template <int PASS, class V>
+__device__ inline bool tr_pass(const TrTaskDev& tk, const uint32_t* store, const uint64_t* off, const uint32_t* src, uint32_t src_n, bool shortcut,
+                               uint32_t anchor_size, V& v) {
+    if (PASS == 0) {
+        const TrCig ij{store + tk.ij_off, tk.ij_n, (tk.inv & 1u) != 0}, jk{store + tk.jk_off, tk.jk_n, (tk.inv & 2u) != 0};
+        return walk_transitive(ij, jk, static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]), static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]), anchor_size, v);
+    }
+    if (shortcut) for (uint32_t x = 0; x < src_n; x++) v.item(src[x] & 15u, src[x] >> 4);
+    else walk_optimize(src, src_n, trwalk::kOptGap, trwalk::kOptAnchor, v);
+    return shortcut;
+}
+
+// the pass without aligning: the scratch level the task needs (the levels and the routing of stage C) and an upper bound of the items
+// it writes, by which its slice is reserved
+template <int PASS>
+__global__ __launch_bounds__(64) void tr_plan_kernel(const TrTaskDev* __restrict__ tasks, uint32_t n_tasks, const uint64_t* __restrict__ off,
+                                                     const uint32_t* __restrict__ store, uint32_t anchor_size, uint32_t max_gap, Lim top, Levels lv,
+                                                     const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ src, const uint32_t* __restrict__ src_words,
+                                                     uint8_t* __restrict__ shortcut, uint32_t* __restrict__ level, uint32_t* __restrict__ cig_cap) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_tasks) return;
+    PlanVisitor v{PASS == 0 ? max_gap : 0xFFFFFFFFu, top, lv, 0, 2};
+    const bool sc = tr_pass<PASS>(tasks[t], store, off, PASS ? src + src_off[t] : nullptr, PASS ? src_words[t] : 0u, PASS ? shortcut[t] != 0 : false, anchor_size, v);
+    if (PASS == 0) shortcut[t] = sc ? 1 : 0;
+    level[t] = v.level;
+    cig_cap[t] = static_cast<uint32_t>(min(v.bound, static_cast<uint64_t>(0xFFFFFFFFu)));
+}
+
+// one lane per task of the level's list, as align_fill_kernel; the CIGAR goes to cig + cig_off[t]
+template <int PASS>
+__global__ __launch_bounds__(64) void tr_fill_kernel(const uint32_t* __restrict__ list, uint32_t n_list, uint32_t n_lanes, const TrTaskDev* __restrict__ tasks,
+                                                     const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint32_t* __restrict__ store,
+                                                     uint32_t anchor_size, uint32_t max_gap, Lim top, Lim mine, uint8_t* __restrict__ scratch,
+                                                     const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ src, const uint32_t* __restrict__ src_words,
+                                                     const uint8_t* __restrict__ shortcut, const uint64_t* __restrict__ cig_off, uint32_t* __restrict__ cig,
+                                                     uint32_t* __restrict__ t_words, unsigned long long* __restrict__ stats) {
+    const uint32_t g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= n_lanes) return;
+    uint8_t* mem = scratch + static_cast<size_t>(g) * lane_bytes(mine);
+    for (uint32_t x = g; x < n_list; x += n_lanes) {
+        const uint32_t t = list[x];
+        const TrTaskDev tk = tasks[t];
+        FillVisitor v;
+        v.S = PairSeq{seq + off[tk.ref], seq + off[tk.qry]};
+        v.cg = CigOut{cig + cig_off[t], 0, static_cast<uint32_t>(cig_off[t + 1] - cig_off[t]), false};
+        v.max_gap = PASS == 0 ? max_gap : 0xFFFFFFFFu; v.top = top; v.mine = mine;
+        v.rows = reinterpret_cast<gotoh::Cell*>(mem); v.dirs = mem + 2 * (static_cast<size_t>(mine.dim) + 1) * sizeof(gotoh::Cell);
+        v.score = 0; v.dropped = 0; v.cells = 0;
+        for (uint32_t r = 0; r < 4; r++) v.n_route[r] = 0;
+        tr_pass<PASS>(tk, store, off, PASS ? src + src_off[t] : nullptr, PASS ? src_words[t] : 0u, PASS ? shortcut[t] != 0 : false, anchor_size, v);
+        t_words[t] = v.cg.n;
+        for (uint32_t r = 0; r < 4; r++) if (v.n_route[r]) atomicAdd(&stats[r], v.n_route[r]);
+        if (v.dropped) atomicAdd(&stats[ST_DROPPED], static_cast<unsigned long long>(v.dropped));
+        if (v.cells) atomicAdd(&stats[ST_CELLS], v.cells);
+        if (v.cg.overflow) atomicAdd(&stats[ST_OVERFLOW], 1ull);
+    }
+}
+
+// the counts of process_pair 652-660 and Penalties::calculate_score (wfa.rs:87-99) of a finished transitive CIGAR; best_ki stays 0
+__global__ __launch_bounds__(64) void tr_count_kernel(uint32_t n_tasks, const uint64_t* __restrict__ cig_off, const uint32_t* __restrict__ cig,
+                                                      const uint32_t* __restrict__ t_words, PairRes* __restrict__ res) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_tasks) return;
+    const uint32_t* w = cig + cig_off[t];
+    const uint32_t nw = t_words[t];
+    uint32_t nm = 0, ne = 0;
+    int32_t score = 0;
+    for (uint32_t x = 0; x < nw; x++) {
+        const uint32_t op = w[x] & 15u, len = w[x] >> 4;
+        if (op == OP_EQ) nm += len;
+        else { ne += len; score -= op == OP_X ? PEN_X * static_cast<int32_t>(len) : PEN_O + PEN_E * static_cast<int32_t>(len); }
+    }
+    res[t] = PairRes{score, 0, nm, ne, nw, 0};
+}
+__global__ __launch_bounds__(64) void tr_gather_kernel(const PairRes* __restrict__ res, const uint64_t* __restrict__ cig_off, const uint32_t* __restrict__ cig,
+                                                       const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out) {
+    const uint32_t t = blockIdx.x;
+    const uint32_t* w = cig + cig_off[t];
+    for (uint32_t x = threadIdx.x; x < res[t].n_words; x += 64) out[out_off[t] + x] = w[x];
+}
+
 // Host ---------------------------------------------------------------------------------------------------------------------------------
 struct Index {
     DevBuf<uint8_t> seq; DevBuf<uint64_t> off, keys_in, keys_sorted; DevBuf<uint32_t> vals_sorted;
@@ -436,16 +531,29 @@ void build_index(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint
     st.index_ms += now_ms() - t0;
 }
 
+// the finished CIGARs of a call that keeps them on the device (lcty_align_haplotypes_transitive): one arena of raw BAM words, a slice per
+// input pair. reserve() is the bounds check, on the host, in front of every launch that writes into it.
+struct Store {
+    DevBuf<uint32_t> buf; uint64_t used = 0;
+    std::vector<uint64_t> off; std::vector<uint32_t> len;
+    void reserve(uint64_t words) const {
+        if (used + words > buf.n)
+            fail(LCTY_ERR_UNSUPPORTED, "the finished CIGARs outgrow their store of %llu bytes: raise the knob align_cigar_store_mb",
+                 static_cast<unsigned long long>(buf.n * 4));
+    }
+};
+
 struct Capture {                                               // lcty_align_backbone: every stage's output of the one task
     std::vector<uint2> matches; std::vector<uint32_t> path, cigar; uint32_t chain = 0; int32_t score = 0; uint32_t dropped = 0;
 };
+constexpr uint32_t kNoK = 0xFFFFFFFFu;                           // best_ki of a pair no backbone k made: a transitive alignment (best_k 0)
 struct PairOut { int32_t score; uint32_t best_ki, n_matches, nerrs; std::vector<uint32_t> cigar; };
 
 // the pairs [a, b) of refs / qrys through stages A to C; returns 0, or — the matches of the batch do not fit `budget` and the batch holds
 // more than one pair — the number of leading pairs whose matches do fit (at least 1): the caller comes back with those, so the counting
 // pass is repeated once, not once per halving
 uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, const uint32_t* refs, const uint32_t* qrys, uint64_t a, uint64_t b, uint32_t max_gap,
-               Lim top, uint64_t budget, PairOut* out, lcty_align_stats& st, Capture* cap) {
+               Lim top, uint64_t budget, PairOut* out, lcty_align_stats& st, Capture* cap, Store* store = nullptr, const uint64_t* pair_ix = nullptr) {
     hipStream_t s = ctx->stream;
     const uint32_t nk = static_cast<uint32_t>(ix.ks.size()), np = static_cast<uint32_t>(b - a), nt = np * nk;
     double t0 = now_ms();
@@ -553,17 +661,26 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     if (hs[ST_OVERFLOW]) fail(LCTY_ERR_RUNTIME, "a CIGAR outgrew its bound (%llu tasks)", hs[ST_OVERFLOW]);
     std::vector<uint64_t> out_off(np + 1, 0);
     for (uint32_t p = 0; p < np; p++) out_off[p + 1] = out_off[p] + res[p].n_words;
-    d_out_off.alloc(np + 1); d_out.alloc(out_off[np] + 1);
-    d_out_off.upload(out_off.data(), np + 1, s);
-    hipLaunchKernelGGL(align_gather_kernel, dim3(np), dim3(64), 0, s, nk, d_res.p, d_cig_off.p, d_cig.p, d_out_off.p, d_out.p);
+    // with a store the winners stay on the device: gathered behind what the store holds, downloaded once when the call ends
+    if (store) store->reserve(out_off[np]);
+    std::vector<uint64_t> dst_off(out_off);
+    if (store) for (uint32_t p = 0; p <= np; p++) dst_off[p] += store->used;
+    d_out_off.alloc(np + 1);
+    if (!store) d_out.alloc(out_off[np] + 1);
+    d_out_off.upload(dst_off.data(), np + 1, s);
+    hipLaunchKernelGGL(align_gather_kernel, dim3(np), dim3(64), 0, s, nk, d_res.p, d_cig_off.p, d_cig.p, d_out_off.p, store ? store->buf.p : d_out.p);
     LCTY_HIP(hipGetLastError());
-    std::vector<uint32_t> words(out_off[np] + 1);
-    d_out.download(words.data(), out_off[np], s);
+    std::vector<uint32_t> words(store ? 1 : out_off[np] + 1);
+    if (!store) d_out.download(words.data(), out_off[np], s);
     LCTY_HIP(hipStreamSynchronize(s));
-    st.bytes_h2d += 8ull * (np + 1); st.bytes_d2h += sizeof(PairRes) * np + 4ull * out_off[np] + 8ull * ST_COUNT;
+    if (store) {
+        for (uint32_t p = 0; p < np; p++) { store->off[pair_ix[a + p]] = dst_off[p]; store->len[pair_ix[a + p]] = res[p].n_words; }
+        store->used += out_off[np];
+    }
+    st.bytes_h2d += 8ull * (np + 1); st.bytes_d2h += sizeof(PairRes) * np + (store ? 0 : 4ull * out_off[np]) + 8ull * ST_COUNT;
     for (uint32_t p = 0; p < np; p++) {
         out[a + p].score = res[p].score; out[a + p].best_ki = res[p].best_ki; out[a + p].n_matches = res[p].n_matches; out[a + p].nerrs = res[p].nerrs;
-        out[a + p].cigar.assign(words.begin() + out_off[p], words.begin() + out_off[p + 1]);
+        if (!store) out[a + p].cigar.assign(words.begin() + out_off[p], words.begin() + out_off[p + 1]);
     }
     st.n_trivial += hs[ST_TRIVIAL]; st.n_simple += hs[ST_SIMPLE]; st.n_small_dp += hs[ST_SMALL]; st.n_general_dp += hs[ST_GENERAL];
     st.n_dropped += hs[ST_DROPPED]; st.dp_cells += hs[ST_CELLS]; st.n_chain_points += hs[ST_POINTS];
@@ -625,7 +742,265 @@ std::string fmt_f(double v, int prec) {                                      // 
     snprintf(b, sizeof(b), "%.*f", prec, v);
     return b;
 }
+
+// what lcty_align_haplotypes decides before it aligns: the input checks, the divergences (process_pair 642-648) and which pairs are taken
+struct Selection {
+    Prepared pr;
+    std::vector<uint32_t> um; std::vector<double> md; std::vector<uint8_t> aligned;
+    std::vector<uint32_t> refs, qrys; std::vector<uint64_t> which;            // the taken pairs, in input order; which = their input index
+};
+void select_pairs(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref_id, const uint32_t* query_id,
+                  const uint8_t* against, const lcty_align_params* params, lcty_align_stats& st, Selection& sel) {
+    check_seqs(n_seqs, seqs, seq_off);
+    sel.pr = validate(ctx, params);
+    const Prepared& pr = sel.pr;
+    std::vector<std::pair<uint64_t, uint64_t>> seen(n_pairs);              // (smaller id << 32 | larger id, index)
+    for (uint64_t x = 0; x < n_pairs; x++) {
+        const uint32_t r = ref_id[x], q = query_id[x];
+        if (r >= n_seqs || q >= n_seqs) fail(LCTY_ERR_INVALID_INPUT, "pair %llu names sequence %u of %u", static_cast<unsigned long long>(x), std::max(r, q), n_seqs);
+        if (r == q) fail(LCTY_ERR_INVALID_INPUT, "pair %llu aligns sequence %u to itself", static_cast<unsigned long long>(x), r);
+        seen[x] = {(static_cast<uint64_t>(std::min(r, q)) << 32) | std::max(r, q), x};
+    }
+    std::sort(seen.begin(), seen.end());
+    for (uint64_t x = 1; x < n_pairs; x++)
+        if (seen[x].first == seen[x - 1].first)
+            fail(LCTY_ERR_INVALID_INPUT, "pair %llu (%u, %u) is given twice", static_cast<unsigned long long>(seen[x].second), ref_id[seen[x].second], query_id[seen[x].second]);
+    seen = {};
+    ctx->activate();
+    // divergences (process_pair 642-648): the triangle of lcty_db_divergences, rows i, then j > i
+    sel.um.assign(n_pairs, 0); sel.md.assign(n_pairs, 0.0); sel.aligned.assign(n_pairs, 0);
+    double t0 = now_ms();
+    if (!params->skip_div) {
+        const uint64_t ntri = static_cast<uint64_t>(n_seqs) * (n_seqs - 1) / 2;
+        std::vector<uint32_t> uniq(ntri); std::vector<double> dv(ntri);
+        lcty_db_stats ds{};
+        const int32_t rc = lcty_db_divergences(ctx, n_seqs, seqs, seq_off, params->div_k, params->div_w, uniq.data(), dv.data(), nullptr, &ds);
+        if (rc != LCTY_OK) fail(rc, "%s", lcty_last_error());
+        st.bytes_h2d += ds.bytes_h2d; st.bytes_d2h += ds.bytes_d2h;
+        for (uint64_t x = 0; x < n_pairs; x++) {
+            const uint64_t i = std::min(ref_id[x], query_id[x]), j = std::max(ref_id[x], query_id[x]);
+            const uint64_t at = i * n_seqs - i * (i + 1) / 2 + (j - i - 1);
+            sel.um[x] = uniq[at]; sel.md[x] = dv[at];
+        }
+    }
+    st.div_ms = now_ms() - t0;
+    for (uint64_t x = 0; x < n_pairs; x++) {
+        const double lim = against && (against[ref_id[x]] || against[query_id[x]]) ? params->against_div : (pr.never ? -1.0 : params->thresh_div);
+        const bool take = params->skip_div || sel.md[x] <= lim;
+        // thresh_div == 0 has cleared the ks (Params::validate): a pair that passes all the same — skip_div, or an `against` pair under
+        // against_div — ends align_multik without an alignment (align.rs:316)
+        if (take && pr.ks.empty()) fail(LCTY_ERR_RUNTIME, "No alignment found between sequences %u and %u", ref_id[x], query_id[x]);
+        if (take) { sel.refs.push_back(ref_id[x]); sel.qrys.push_back(query_id[x]); sel.which.push_back(x); sel.aligned[x] = 1; }
+    }
+}
+
+struct Batching { uint64_t budget, per_batch; };
+Batching batching(lcty_ctx* ctx, uint32_t n_seqs, const uint64_t* seq_off, const Prepared& pr) {
+    size_t free_b = 0, total_b = 0;
+    LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
+    // bytes for the matches of a batch (20 a match); knob align_match_budget: a test reaches the "do not fit" return of run_batch
+    const uint64_t budget = static_cast<uint64_t>(ctx->knob("align_match_budget", static_cast<int64_t>(std::max<uint64_t>(free_b / 4, 64ull << 20))));
+    uint64_t max_len = 0;
+    for (uint32_t i = 0; i < n_seqs; i++) max_len = std::max(max_len, seq_off[i + 1] - seq_off[i]);
+    // a pair: per k 12 bytes a reference window (counts, offsets), 8 a query column (tree), and about 20 a match
+    uint64_t per_batch = std::max<uint64_t>(budget / (pr.ks.size() * (max_len + 2) * 40 + 1), 1);
+    const int64_t knob = ctx->knob("align_batch_pairs", 0);
+    if (knob > 0) per_batch = static_cast<uint64_t>(knob);
+    per_batch = std::min<uint64_t>(per_batch, (1u << 30) / pr.ks.size());
+    return Batching{budget, per_batch};
+}
+
+// po[y]: the result of taken pair y (its CIGAR is words[coff[which[y]], ...))
+void write_out(lcty_align_out* out, uint64_t n_pairs, const Selection& sel, const std::vector<PairOut>& po, const std::vector<uint64_t>& coff,
+               const std::vector<uint32_t>& words) {
+    std::vector<uint32_t> nm(n_pairs, 0), al(n_pairs, 0), ne(n_pairs, 0), bk(n_pairs, 0); std::vector<int32_t> sc(n_pairs, 0);
+    for (uint64_t y = 0; y < sel.which.size(); y++) {
+        const uint64_t x = sel.which[y];
+        nm[x] = po[y].n_matches; ne[x] = po[y].nerrs; al[x] = po[y].n_matches + po[y].nerrs; sc[x] = po[y].score;
+        bk[x] = po[y].best_ki == kNoK ? 0 : sel.pr.ks[po[y].best_ki];
+    }
+    out->n_pairs = n_pairs;
+    out->aligned = to_malloc(sel.aligned.data(), n_pairs); out->n_matches = to_malloc(nm.data(), n_pairs); out->aln_len = to_malloc(al.data(), n_pairs);
+    out->nerrs = to_malloc(ne.data(), n_pairs); out->score = to_malloc(sc.data(), n_pairs); out->best_k = to_malloc(bk.data(), n_pairs);
+    out->um = to_malloc(sel.um.data(), n_pairs); out->md = to_malloc(sel.md.data(), n_pairs);
+    out->cigar_off = to_malloc(coff.data(), n_pairs + 1); out->cigar = to_malloc(words.data(), words.size());
+}
 }  // namespace
+
+// the device side of lcty_align_haplotypes_transitive (lcty_align_transitive.hip decides the rounds; lcty_align_internal.hpp)
+namespace lcty {
+namespace align {
+struct Session::Impl {
+    lcty_ctx* ctx; uint32_t n_seqs; const uint8_t* seqs; const uint64_t* seq_off; uint64_t n_pairs; const uint32_t* ref_id; const uint32_t* query_id;
+    Selection sel; Index ix; Batching bt{0, 1}; Store store; std::vector<PairOut> res;      // res: per INPUT pair
+    // grow-only workspaces of the transitive rounds: a call has a round per row of the triangle, and nothing is allocated per round
+    // once the widest row has been seen
+    DevBuf<uint8_t> scratch, d_short; DevBuf<TrTaskDev> d_tasks; DevBuf<uint32_t> d_level, d_cap, d_list, d_words[2], d_cig[2];
+    DevBuf<uint64_t> d_off[2], d_dst; DevBuf<PairRes> d_res; DevBuf<unsigned long long> d_stats;
+    lcty_align_stats st{}; lcty_align_tr_stats tr{};
+    double t_all = 0;
+};
+
+Session::Session(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref_id, const uint32_t* query_id,
+                 const uint8_t* against, const lcty_align_params* params) : im(new Impl) {
+    try {
+        im->ctx = ctx; im->n_seqs = n_seqs; im->seqs = seqs; im->seq_off = seq_off; im->n_pairs = n_pairs; im->ref_id = ref_id; im->query_id = query_id;
+        im->t_all = now_ms();
+        select_pairs(ctx, n_seqs, seqs, seq_off, n_pairs, ref_id, query_id, against, params, im->st, im->sel);
+        im->res.assign(n_pairs, PairOut{0, kNoK, 0, 0, {}});
+        im->store.off.assign(n_pairs, 0); im->store.len.assign(n_pairs, 0);
+    } catch (...) { delete im; throw; }
+}
+Session::~Session() { delete im; }
+const uint8_t* Session::aligned() const { return im->sel.aligned.data(); }
+uint32_t Session::nerrs(uint64_t pair) const { return im->res[pair].nerrs; }
+uint32_t Session::aln_len(uint64_t pair) const { return im->res[pair].n_matches + im->res[pair].nerrs; }
+
+void Session::open(uint64_t store_words) {
+    if (im->sel.which.empty()) return;
+    build_index(im->ctx, im->n_seqs, im->seqs, im->seq_off, im->sel.pr.ks, im->ix, im->st);
+    im->bt = batching(im->ctx, im->n_seqs, im->seq_off, im->sel.pr);
+    im->store.buf.alloc(store_words);
+}
+
+void Session::backbone(const uint64_t* pairs, uint64_t n) {
+    if (!n) return;
+    std::vector<uint32_t> refs(n), qrys(n);
+    for (uint64_t y = 0; y < n; y++) { refs[y] = im->ref_id[pairs[y]]; qrys[y] = im->query_id[pairs[y]]; }
+    std::vector<PairOut> po(n);
+    const Prepared& pr = im->sel.pr;
+    for (uint64_t at = 0; at < n;) {
+        uint64_t m = std::min<uint64_t>(im->bt.per_batch, n - at);
+        for (uint64_t fit; (fit = run_batch(im->ctx, im->ix, im->seq_off, refs.data(), qrys.data(), at, at + m, pr.max_gap, pr.top, im->bt.budget, po.data(), im->st,
+                                            nullptr, &im->store, pairs)) != 0;) m = fit;
+        at += m;
+    }
+    for (uint64_t y = 0; y < n; y++) im->res[pairs[y]] = po[y];
+}
+
+void Session::transitive(const TrTask* tasks, uint64_t n, uint32_t anchor_size) {
+    if (!n) return;
+    if (n > 0x7FFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "%llu transitive tasks in one round", static_cast<unsigned long long>(n));
+    lcty_ctx* ctx = im->ctx;
+    hipStream_t s = ctx->stream;
+    const Prepared& pr = im->sel.pr;
+    Store& store = im->store;
+    const uint32_t nt = static_cast<uint32_t>(n);
+    double t0 = now_ms();
+    std::vector<TrTaskDev> h(nt);
+    for (uint32_t t = 0; t < nt; t++) {
+        const TrTask& k = tasks[t];
+        h[t] = TrTaskDev{store.off[k.ij], store.off[k.jk], store.len[k.ij], store.len[k.jk], im->ref_id[k.pair], im->query_id[k.pair],
+                         (k.inv_ij ? 1u : 0u) | (k.inv_jk ? 2u : 0u), 0};
+    }
+    Levels lv;
+    for (uint32_t l = 0; l < kLevels; l++) lv.l[l] = Lim{std::min(kLevelDim[l], pr.top.dim), std::min(kLevelCells[l], pr.top.cells)};
+    DevBuf<TrTaskDev>& d_tasks = im->d_tasks; DevBuf<uint8_t>& d_short = im->d_short; DevBuf<uint32_t>& d_level = im->d_level; DevBuf<uint32_t>& d_cap = im->d_cap;
+    DevBuf<uint32_t>& d_list = im->d_list; DevBuf<uint32_t>* d_words = im->d_words; DevBuf<uint32_t>* d_cig = im->d_cig; DevBuf<uint64_t>* d_off = im->d_off;
+    DevBuf<unsigned long long>& d_stats = im->d_stats;
+    d_tasks.ensure_slack(nt); d_short.ensure_slack(nt); d_level.ensure_slack(nt); d_cap.ensure_slack(nt); d_list.ensure_slack(nt); d_stats.ensure(ST_COUNT);
+    d_tasks.upload(h.data(), nt, s); d_stats.zero(s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    im->st.bytes_h2d += sizeof(TrTaskDev) * nt;
+    t0 = now_ms();                                                            // (the upload is not planning)
+    std::vector<uint32_t> level(nt), ccap(nt), list;
+    std::vector<uint64_t> cig_off(nt + 1);
+    const dim3 grid((nt + 63) / 64), block(64);
+    // a pass: plan, reserve the slices by the bounds, fill level by level
+    auto pass = [&](int ps) {
+        const uint64_t* so = ps ? d_off[0].p : nullptr; const uint32_t* sc = ps ? d_cig[0].p : nullptr; const uint32_t* sw = ps ? d_words[0].p : nullptr;
+        if (ps == 0) hipLaunchKernelGGL(tr_plan_kernel<0>, grid, block, 0, s, d_tasks.p, nt, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, lv, so, sc, sw, d_short.p, d_level.p, d_cap.p);
+        else hipLaunchKernelGGL(tr_plan_kernel<1>, grid, block, 0, s, d_tasks.p, nt, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, lv, so, sc, sw, d_short.p, d_level.p, d_cap.p);
+        LCTY_HIP(hipGetLastError());
+        d_level.download(level.data(), nt, s); d_cap.download(ccap.data(), nt, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+        im->st.bytes_d2h += 8ull * nt;
+        cig_off[0] = 0;
+        for (uint32_t t = 0; t < nt; t++) cig_off[t + 1] = cig_off[t] + ccap[t];
+        // the CIGARs of a pass: per-round temporaries sized by the bounds, beside the store (not part of its budget)
+        d_off[ps].ensure_slack(nt + 1); d_cig[ps].ensure_slack(cig_off[nt] + 1); d_words[ps].ensure_slack(nt);
+        d_off[ps].upload(cig_off.data(), nt + 1, s);
+        im->st.bytes_h2d += 8ull * (nt + 1);
+        im->tr.plan_ms += now_ms() - t0; t0 = now_ms();
+        for (uint32_t l = 0; l < kLevels; l++) {
+            list.clear();
+            for (uint32_t t = 0; t < nt; t++) if (level[t] == l) list.push_back(t);
+            if (list.empty()) continue;
+            const Lim mine = lv.l[l];
+            const uint32_t lanes = static_cast<uint32_t>(std::min<size_t>(list.size(), kLevelLanes[l]));
+            im->scratch.ensure(lanes * lane_bytes(mine));
+            d_list.upload(list.data(), list.size(), s);
+            im->st.bytes_h2d += 4ull * list.size();
+            const dim3 g((lanes + 63) / 64);
+            if (ps == 0) hipLaunchKernelGGL(tr_fill_kernel<0>, g, block, 0, s, d_list.p, static_cast<uint32_t>(list.size()), lanes, d_tasks.p, im->ix.seq.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, mine, im->scratch.p, so, sc, sw, d_short.p, d_off[0].p, d_cig[0].p, d_words[0].p, d_stats.p);
+            else hipLaunchKernelGGL(tr_fill_kernel<1>, g, block, 0, s, d_list.p, static_cast<uint32_t>(list.size()), lanes, d_tasks.p, im->ix.seq.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, mine, im->scratch.p, so, sc, sw, d_short.p, d_off[1].p, d_cig[1].p, d_words[1].p, d_stats.p);
+            LCTY_HIP(hipGetLastError());
+            LCTY_HIP(hipStreamSynchronize(s));                                    // `list` is filled again
+        }
+        (ps ? im->tr.optimize_ms : im->tr.tr_fill_ms) += now_ms() - t0; t0 = now_ms();
+    };
+    pass(0);
+    pass(1);
+    DevBuf<PairRes>& d_res = im->d_res; DevBuf<uint64_t>& d_dst = im->d_dst;
+    d_res.ensure_slack(nt); d_dst.ensure_slack(nt);
+    hipLaunchKernelGGL(tr_count_kernel, grid, block, 0, s, nt, d_off[1].p, d_cig[1].p, d_words[1].p, d_res.p);
+    LCTY_HIP(hipGetLastError());
+    std::vector<PairRes> res(nt); std::vector<unsigned long long> hs(ST_COUNT); std::vector<uint8_t> shortcut(nt);
+    d_res.download(res.data(), nt, s); d_stats.download(hs.data(), ST_COUNT, s); d_short.download(shortcut.data(), nt, s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    im->st.bytes_d2h += (sizeof(PairRes) + 1) * nt + 8ull * ST_COUNT;
+    if (hs[ST_OVERFLOW]) fail(LCTY_ERR_RUNTIME, "a transitive CIGAR outgrew its bound (%llu tasks)", hs[ST_OVERFLOW]);
+    std::vector<uint64_t> dst(nt);
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < nt; t++) { dst[t] = store.used + total; total += res[t].n_words; }
+    store.reserve(total);
+    d_dst.upload(dst.data(), nt, s);
+    hipLaunchKernelGGL(tr_gather_kernel, dim3(nt), block, 0, s, d_res.p, d_off[1].p, d_cig[1].p, d_dst.p, store.buf.p);
+    LCTY_HIP(hipGetLastError());
+    LCTY_HIP(hipStreamSynchronize(s));
+    im->st.bytes_h2d += 8ull * nt;
+    store.used += total;
+    for (uint32_t t = 0; t < nt; t++) {
+        const uint64_t x = tasks[t].pair;
+        store.off[x] = dst[t]; store.len[x] = res[t].n_words;
+        im->res[x] = PairOut{res[t].score, kNoK, res[t].n_matches, res[t].nerrs, {}};
+        im->tr.n_shortcut += shortcut[t];
+    }
+    im->tr.n_accelerated += nt;
+    im->tr.n_tr_stretches += hs[ST_TRIVIAL] + hs[ST_SIMPLE] + hs[ST_SMALL] + hs[ST_GENERAL];
+    im->tr.tr_dp_cells += hs[ST_CELLS];
+    im->st.n_dropped += hs[ST_DROPPED];
+    im->tr.count_ms += now_ms() - t0;
+}
+
+void Session::finish(uint64_t n_rounds, lcty_align_out* out, lcty_align_stats* stats, lcty_align_tr_stats* tr_stats) {
+    hipStream_t s = im->ctx->stream;
+    Store& store = im->store;
+    const uint64_t n_pairs = im->n_pairs;
+    const double t0 = now_ms();
+    std::vector<uint32_t> arena(store.used + 1);
+    store.buf.download(arena.data(), store.used, s);                           // the one download of the CIGARs
+    LCTY_HIP(hipStreamSynchronize(s));
+    im->st.bytes_d2h += 4ull * store.used;
+    std::vector<uint64_t> coff(n_pairs + 1, 0);
+    for (uint64_t x = 0; x < n_pairs; x++) coff[x + 1] = coff[x] + (im->sel.aligned[x] ? store.len[x] : 0);
+    std::vector<uint32_t> words(coff[n_pairs]);
+    std::vector<PairOut> po(im->sel.which.size());
+    for (uint64_t y = 0; y < im->sel.which.size(); y++) {
+        const uint64_t x = im->sel.which[y];
+        po[y] = im->res[x];
+        std::copy(arena.begin() + store.off[x], arena.begin() + store.off[x] + store.len[x], words.begin() + coff[x]);
+    }
+    write_out(out, n_pairs, im->sel, po, coff, words);
+    im->st.select_ms += now_ms() - t0;
+    im->st.n_aligned = im->sel.which.size(); im->st.n_skipped = n_pairs - im->sel.which.size();
+    im->st.total_ms = now_ms() - im->t_all;
+    im->tr.n_rounds = n_rounds; im->tr.store_bytes = 4ull * store.used;
+    if (stats) *stats = im->st;
+    if (tr_stats) *tr_stats = im->tr;
+}
+}  // namespace align
+}  // namespace lcty
 
 extern "C" {
 
@@ -665,83 +1040,27 @@ int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seq
         memset(out, 0, sizeof(*out));
         lcty_align_stats st{};
         const double t_all = now_ms();
-        check_seqs(n_seqs, seqs, seq_off);
-        const Prepared pr = validate(ctx, params);
-        std::vector<std::pair<uint64_t, uint64_t>> seen(n_pairs);              // (smaller id << 32 | larger id, index)
-        for (uint64_t x = 0; x < n_pairs; x++) {
-            const uint32_t r = ref_id[x], q = query_id[x];
-            if (r >= n_seqs || q >= n_seqs) fail(LCTY_ERR_INVALID_INPUT, "pair %llu names sequence %u of %u", static_cast<unsigned long long>(x), std::max(r, q), n_seqs);
-            if (r == q) fail(LCTY_ERR_INVALID_INPUT, "pair %llu aligns sequence %u to itself", static_cast<unsigned long long>(x), r);
-            seen[x] = {(static_cast<uint64_t>(std::min(r, q)) << 32) | std::max(r, q), x};
-        }
-        std::sort(seen.begin(), seen.end());
-        for (uint64_t x = 1; x < n_pairs; x++)
-            if (seen[x].first == seen[x - 1].first)
-                fail(LCTY_ERR_INVALID_INPUT, "pair %llu (%u, %u) is given twice", static_cast<unsigned long long>(seen[x].second), ref_id[seen[x].second], query_id[seen[x].second]);
-        seen = {};
-        ctx->activate();
-        // divergences (process_pair 642-648): the triangle of lcty_db_divergences, rows i, then j > i
-        std::vector<uint32_t> um(n_pairs, 0); std::vector<double> md(n_pairs, 0.0); std::vector<uint8_t> aligned(n_pairs, 0);
-        double t0 = now_ms();
-        if (!params->skip_div) {
-            const uint64_t ntri = static_cast<uint64_t>(n_seqs) * (n_seqs - 1) / 2;
-            std::vector<uint32_t> uniq(ntri); std::vector<double> dv(ntri);
-            lcty_db_stats ds{};
-            const int32_t rc = lcty_db_divergences(ctx, n_seqs, seqs, seq_off, params->div_k, params->div_w, uniq.data(), dv.data(), nullptr, &ds);
-            if (rc != LCTY_OK) fail(rc, "%s", lcty_last_error());
-            st.bytes_h2d += ds.bytes_h2d; st.bytes_d2h += ds.bytes_d2h;
-            for (uint64_t x = 0; x < n_pairs; x++) {
-                const uint64_t i = std::min(ref_id[x], query_id[x]), j = std::max(ref_id[x], query_id[x]);
-                const uint64_t at = i * n_seqs - i * (i + 1) / 2 + (j - i - 1);
-                um[x] = uniq[at]; md[x] = dv[at];
-            }
-        }
-        st.div_ms = now_ms() - t0;
-        std::vector<uint32_t> refs, qrys; std::vector<uint64_t> which;
-        for (uint64_t x = 0; x < n_pairs; x++) {
-            const double lim = against && (against[ref_id[x]] || against[query_id[x]]) ? params->against_div : (pr.never ? -1.0 : params->thresh_div);
-            const bool take = params->skip_div || md[x] <= lim;
-            // thresh_div == 0 has cleared the ks (Params::validate): a pair that passes all the same — skip_div, or an `against` pair under
-            // against_div — ends align_multik without an alignment (align.rs:316)
-            if (take && pr.ks.empty()) fail(LCTY_ERR_RUNTIME, "No alignment found between sequences %u and %u", ref_id[x], query_id[x]);
-            if (take) { refs.push_back(ref_id[x]); qrys.push_back(query_id[x]); which.push_back(x); aligned[x] = 1; }
-        }
+        Selection sel;
+        select_pairs(ctx, n_seqs, seqs, seq_off, n_pairs, ref_id, query_id, against, params, st, sel);
+        const Prepared& pr = sel.pr;
+        const std::vector<uint32_t>& refs = sel.refs; const std::vector<uint32_t>& qrys = sel.qrys; const std::vector<uint64_t>& which = sel.which;
         std::vector<PairOut> po(refs.size());
         if (!refs.empty()) {
             Index ix;
             build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
-            size_t free_b = 0, total_b = 0;
-            LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
-            // bytes for the matches of a batch (20 a match); knob align_match_budget: a test reaches the "do not fit" return of run_batch
-            const uint64_t budget = static_cast<uint64_t>(ctx->knob("align_match_budget", static_cast<int64_t>(std::max<uint64_t>(free_b / 4, 64ull << 20))));
-            uint64_t max_len = 0;
-            for (uint32_t i = 0; i < n_seqs; i++) max_len = std::max(max_len, seq_off[i + 1] - seq_off[i]);
-            // a pair: per k 12 bytes a reference window (counts, offsets), 8 a query column (tree), and about 20 a match
-            uint64_t per_batch = std::max<uint64_t>(budget / (pr.ks.size() * (max_len + 2) * 40 + 1), 1);
-            const int64_t knob = ctx->knob("align_batch_pairs", 0);
-            if (knob > 0) per_batch = static_cast<uint64_t>(knob);
-            per_batch = std::min<uint64_t>(per_batch, (1u << 30) / pr.ks.size());
+            const Batching bt = batching(ctx, n_seqs, seq_off, pr);
             for (uint64_t at = 0; at < refs.size();) {
-                uint64_t n = std::min<uint64_t>(per_batch, refs.size() - at);
-                for (uint64_t fit; (fit = run_batch(ctx, ix, seq_off, refs.data(), qrys.data(), at, at + n, pr.max_gap, pr.top, budget, po.data(), st, nullptr)) != 0;) n = fit;
+                uint64_t n = std::min<uint64_t>(bt.per_batch, refs.size() - at);
+                for (uint64_t fit; (fit = run_batch(ctx, ix, seq_off, refs.data(), qrys.data(), at, at + n, pr.max_gap, pr.top, bt.budget, po.data(), st, nullptr)) != 0;) n = fit;
                 at += n;
             }
         }
-        std::vector<uint32_t> nm(n_pairs, 0), al(n_pairs, 0), ne(n_pairs, 0), bk(n_pairs, 0); std::vector<int32_t> sc(n_pairs, 0);
         std::vector<uint64_t> coff(n_pairs + 1, 0);
         for (uint64_t y = 0; y < which.size(); y++) coff[which[y] + 1] = po[y].cigar.size();
         for (uint64_t x = 0; x < n_pairs; x++) coff[x + 1] += coff[x];
         std::vector<uint32_t> words(coff[n_pairs]);
-        for (uint64_t y = 0; y < which.size(); y++) {
-            const uint64_t x = which[y];
-            nm[x] = po[y].n_matches; ne[x] = po[y].nerrs; al[x] = po[y].n_matches + po[y].nerrs; sc[x] = po[y].score; bk[x] = pr.ks[po[y].best_ki];
-            std::copy(po[y].cigar.begin(), po[y].cigar.end(), words.begin() + coff[x]);
-        }
-        out->n_pairs = n_pairs;
-        out->aligned = to_malloc(aligned.data(), n_pairs); out->n_matches = to_malloc(nm.data(), n_pairs); out->aln_len = to_malloc(al.data(), n_pairs);
-        out->nerrs = to_malloc(ne.data(), n_pairs); out->score = to_malloc(sc.data(), n_pairs); out->best_k = to_malloc(bk.data(), n_pairs);
-        out->um = to_malloc(um.data(), n_pairs); out->md = to_malloc(md.data(), n_pairs);
-        out->cigar_off = to_malloc(coff.data(), n_pairs + 1); out->cigar = to_malloc(words.data(), words.size());
+        for (uint64_t y = 0; y < which.size(); y++) std::copy(po[y].cigar.begin(), po[y].cigar.end(), words.begin() + coff[which[y]]);
+        write_out(out, n_pairs, sel, po, coff, words);
         st.n_aligned = which.size(); st.n_skipped = n_pairs - which.size();
         st.total_ms = now_ms() - t_all;
         if (stats) *stats = st;

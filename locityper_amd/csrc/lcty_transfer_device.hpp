@@ -9,6 +9,7 @@
 
 #include "lcty_device.hpp"
 #include "lcty_gotoh.hpp"
+#include "lcty_cigar_walk.hpp"
 
 namespace lcty {
 namespace xfer {
@@ -35,12 +36,7 @@ __host__ __device__ inline size_t lane_scratch_bytes(const Limits& m) {
     return (b + 15) & ~size_t(15);
 }
 
-// consumes the query: M I S = X; consumes the reference: M D = X (bit `op` of a mask; operations are 4-bit codes)
-__device__ __forceinline__ bool cons_q(uint32_t op) { return ((0x193u >> (op & 15u)) & 1u) != 0; }
-__device__ __forceinline__ bool cons_r(uint32_t op) { return ((0x185u >> (op & 15u)) & 1u) != 0; }
-__device__ __forceinline__ uint32_t op_invert(uint32_t op) {                  // Operation::invert, cigar.rs:147-159
-    return (op == OP_I || op == OP_S) ? OP_D : (op == OP_D ? OP_I : op);
-}
+// (cons_q, cons_r, op_invert, double_move and the predicates of optimize: lcty_cigar_walk.hpp)
 
 // Cigar under construction (cigar.rs:203-208): items {op, len}, an item one word, length << 4 | operation (the BAM form, which is also
 // what leaves the kernel).
@@ -480,9 +476,9 @@ __device__ inline bool opt_step(OptState& o, DCigar& self, uint32_t max_gap, uin
             const uint2 item_j = o.win.get(o.j);
             const uint32_t op = item_j.x, len = item_j.y;
             const bool cq = cons_q(op), cr = cons_r(op);
-            if (cq && cr && len >= anchor_size) {
+            if (opt_is_anchor(op, len, anchor_size)) {
                 const uint32_t qshift = o.qpos2 - o.qpos1, rshift = o.rpos2 - o.rpos1;
-                if (o.flag == 3 && !(max_gap < qshift) && !(max_gap < rshift)) {
+                if (opt_realigns(o.flag, qshift, rshift, max_gap)) {
                     opt_begin_copy(o, self);
                     job = Job{o.rpos1, o.rpos2 - o.rpos1, o.qpos1, o.qpos2 - o.qpos1, 0, false};
                     o.stage = 1;
@@ -491,7 +487,7 @@ __device__ inline bool opt_step(OptState& o, DCigar& self, uint32_t max_gap, uin
                 opt_past_anchor(o, self, op, len);
             } else {
                 o.qpos2 += cq ? len : 0; o.rpos2 += cr ? len : 0;
-                o.flag |= (cq ? 0u : 1u) | ((cr ? 0u : 1u) << 1);
+                o.flag |= opt_gap_flag(op);
                 o.j++;
             }
         } else if (o.stage == 1) {                                            // back from the aligner, in front of the anchor item j
@@ -502,7 +498,7 @@ __device__ inline bool opt_step(OptState& o, DCigar& self, uint32_t max_gap, uin
         } else if (o.stage == 2) {                                            // what is behind the last anchor
             const uint32_t qshift = o.qpos2 - o.qpos1, rshift = o.rpos2 - o.rpos1;
             o.stage = 4;
-            if (o.flag == 3 && !(max_gap < qshift) && !(max_gap < rshift)) {
+            if (opt_realigns(o.flag, qshift, rshift, max_gap)) {
                 opt_begin_copy(o, self);
                 job = Job{o.rpos1, o.rpos2 - o.rpos1, o.qpos1, o.qpos2 - o.qpos1, 0, false};
                 o.stage = 3;
@@ -523,19 +519,6 @@ __device__ inline bool opt_step(OptState& o, DCigar& self, uint32_t max_gap, uin
             return false;
         }
     }
-}
-
-// double_cigar_move_and_shift (cigar.rs:1422-1466)
-__device__ __forceinline__ uint32_t cons_class(uint32_t op) { return cons_q(op) && cons_r(op) ? 0u : (cons_q(op) ? 1u : 2u); }
-__device__ inline uint32_t double_move(uint32_t op1, uint32_t op2, uint32_t& pos1, uint32_t& rem1, uint32_t& pos2, uint32_t& rem2) {
-    // bit 0 read moves, 1 read CIGAR shifts, 2 haplotype moves, 3 haplotype CIGAR shifts; index = class(op1) * 3 + class(op2)
-    // the nine cases as nibbles of one constant, case 0 lowest: {0xF, 0xB, 0xC, 0x3, 0x3, 0xF, 0xE, 0xA, 0xC}
-    const uint32_t f = static_cast<uint32_t>(0xCAEF33CBFull >> (4u * (cons_class(op1) * 3 + cons_class(op2)))) & 0xFu;
-    const bool rs = f & 2u, hs = f & 8u;
-    const uint32_t shift = (rs && (!hs || rem1 <= rem2)) ? rem1 : rem2;
-    pos1 += (f & 1u) ? shift : 0; rem1 -= rs ? shift : 0;
-    pos2 += (f & 4u) ? shift : 0; rem2 -= hs ? shift : 0;
-    return shift;
 }
 
 // the read's own CIGAR as it is stored: raw BAM words, hard clips at the ends count as soft ones (cigar.rs:309-320)

@@ -9,6 +9,11 @@
 // cells takes align_simple. align_probe_stretch is the same route for one stretch WITH the walk back and a recording sink
 // (tests/test_align_host.py holds it against tests/pyref_align.py).
 // Returns the milliseconds of the pairs (the k-mer lists of the sequences, made once, are timed apart: *index_ms).
+// align_probe_host_transitive is the transitive route (TransitiveStrategy, align.rs:452-514) in the same threads: the rounds of
+// lcty_align_haplotypes_transitive, decided from the same mirror of `closest`; the pairs of a round are dealt to the threads, backbone
+// pairs along the route above WITH the walk back (their CIGARs are what later pairs are composed of), transitive pairs through the
+// host instantiation of lcty_cigar_walk.hpp (walk_transitive, walk_optimize — the templates the kernels run). It returns scores,
+// best ks, routes and via, which must equal the device's.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -19,6 +24,10 @@
 #include <vector>
 
 #include "lcty_gotoh.hpp"
+#include "lcty_cigar_walk.hpp"
+
+#include <unordered_map>
+#include <unordered_set>
 
 namespace {
 namespace G = lcty::gotoh;
@@ -213,5 +222,152 @@ extern "C" double align_probe_host(uint32_t n_seqs, const uint8_t* seqs, const u
             }
         });
     for (auto& th : pool) th.join();
+    return now_ms() - t1;
+}
+
+namespace {
+// a CIGAR under construction: raw BAM words, equal neighbours merge (the library's CigOut)
+struct Cig {
+    std::vector<uint32_t> w;
+    void operator()(uint32_t op, uint32_t len) {
+        if (!len) return;
+        if (!w.empty() && (w.back() & 15u) == op) w.back() += len << 4; else w.push_back((len << 4) | op);
+    }
+};
+struct Work { std::vector<std::pair<uint32_t, uint32_t>> M; std::vector<uint64_t> fen; std::vector<uint32_t> dp, prev, path; std::vector<G::Cell> rows; std::vector<uint8_t> dirs; };
+
+// align_multik with the CIGAR of the winner
+int backbone_cigar(const Seq& r, const Seq& q, const std::vector<uint32_t>* lr, const std::vector<uint32_t>* lq, uint32_t nk, const uint32_t* ks, uint32_t max_gap,
+                   Work& wk, Cig& out, uint32_t* best_k) {
+    int best = INT32_MIN;
+    for (uint32_t ki = 0; ki < nk; ki++) {
+        const uint32_t k = ks[ki];
+        matches_of(r, lr[ki], q, lq[ki], k, wk.M);
+        lcskpp(wk.M, k, q.len, wk.fen, wk.dp, wk.prev, wk.path);
+        Cig cg;
+        int sc = 0;
+        uint32_t i1 = 0, j1 = 0, cur = 0;
+        for (uint32_t ix : wk.path) {                                         // align_from_backbone, align.rs:262-286
+            const uint32_t i2 = wk.M[ix].first, j2 = wk.M[ix].second;
+            if (i1 > i2) { cur++; i1++; j1++; continue; }
+            if (cur) { cg(G::OP_EQ, cur); cur = 0; }
+            sc += smart_align(r, i1, i2, q, j1, j2, max_gap, wk.rows, &wk.dirs, cg);
+            cur += k; i1 = i2 + k; j1 = j2 + k;
+        }
+        if (cur) cg(G::OP_EQ, cur);
+        sc += smart_align(r, i1, r.len, q, j1, q.len, max_gap, wk.rows, &wk.dirs, cg);
+        if (sc > best) { best = sc; *best_k = k; out.w.swap(cg.w); }
+    }
+    return best;
+}
+
+struct WalkVisitor {                                                           // what the kernels' FillVisitor is on the device
+    const Seq& r; const Seq& q; uint32_t max_gap; Work& wk; Cig& cg;
+    void item(uint32_t op, uint32_t len) { cg(op, len); }
+    void stretch(uint32_t i1, uint32_t i2, uint32_t j1, uint32_t j2) { smart_align(r, i1, i2, q, j1, j2, max_gap, wk.rows, &wk.dirs, cg); }
+};
+}  // namespace
+
+extern "C" double align_probe_host_transitive(uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref, const uint32_t* query,
+                                              const uint8_t* aligned, uint32_t nk, const uint32_t* ks, uint32_t max_gap, double tr_div, uint32_t anchor_size,
+                                              uint32_t threads, int32_t* score, uint32_t* best_k, uint8_t* route, uint32_t* via, uint64_t* n_rounds,
+                                              double* index_ms) {
+    namespace W = lcty::trwalk;
+    std::vector<Seq> S(n_seqs);
+    for (uint32_t i = 0; i < n_seqs; i++) S[i] = Seq{seqs + seq_off[i], static_cast<uint32_t>(seq_off[i + 1] - seq_off[i])};
+    const double t0 = now_ms();
+    std::vector<std::vector<uint32_t>> lists(static_cast<size_t>(n_seqs) * nk);
+    {
+        std::atomic<uint32_t> next{0};
+        std::vector<std::thread> pool;
+        for (uint32_t t = 0; t < threads; t++) pool.emplace_back([&] { for (uint32_t x; (x = next++) < n_seqs * nk;) lists[x] = kmer_list(S[x / nk], ks[x % nk]); });
+        for (auto& th : pool) th.join();
+    }
+    const double t1 = now_ms();
+    if (index_ms) *index_ms = t1 - t0;
+    const bool accelerate = tr_div > 0.0 && n_pairs >= 16;                     // align.rs:784
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    auto key = [](uint32_t a, uint32_t b) { return (static_cast<uint64_t>(std::min(a, b)) << 32) | std::max(a, b); };
+    std::vector<Cig> cig(n_pairs);
+    std::vector<uint32_t> c_id(n_seqs, NONE); std::vector<double> c_dv(n_seqs, 0.0); std::vector<uint64_t> c_pair(n_seqs, 0);
+    std::unordered_map<uint64_t, uint64_t> cell;
+    std::vector<uint64_t> w_closest(n_seqs, 0);
+    std::unordered_set<uint64_t> w_cell;
+    struct Task { uint64_t pair, ij, jk; };
+    std::vector<Task> members;
+    std::vector<Work> work(threads);
+    uint64_t rounds = 0;
+    for (uint64_t x = 0; x < n_pairs; x++) { route[x] = 0; via[x] = NONE; score[x] = 0; best_k[x] = 0; }
+    for (uint64_t x0 = 0, round = 1; x0 < n_pairs; round++) {
+        w_cell.clear(); members.clear();
+        uint64_t x = x0;
+        for (; x < n_pairs; x++) {
+            if (aligned && !aligned[x]) continue;
+            const uint32_t k = ref[x], i = query[x];
+            uint8_t rt = 1; uint32_t j = NONE; uint64_t ij = 0, jk = 0;
+            if (accelerate) {
+                if (w_closest[k] == round || w_closest[i] == round) break;
+                bool cut = false;
+                if (c_id[k] != NONE) {
+                    const uint64_t kk = key(i, c_id[k]);
+                    if (w_cell.count(kk)) cut = true;
+                    else { const auto it = cell.find(kk); if (it != cell.end()) { rt = 2; j = c_id[k]; ij = it->second; jk = c_pair[k]; } }
+                }
+                if (!cut && rt == 1 && c_id[i] != NONE) {
+                    const uint64_t kk = key(k, c_id[i]);
+                    if (w_cell.count(kk)) cut = true;
+                    else { const auto it = cell.find(kk); if (it != cell.end()) { rt = 3; j = c_id[i]; ij = c_pair[i]; jk = it->second; } }
+                }
+                if (cut) break;
+                w_cell.insert(key(k, i)); w_closest[i] = round;
+            }
+            route[x] = rt; via[x] = j;
+            members.push_back(Task{x, ij, jk});
+        }
+        std::atomic<uint64_t> next{0};
+        std::vector<std::thread> pool;
+        for (uint32_t t = 0; t < threads; t++)
+            pool.emplace_back([&, t] {
+                Work& wk = work[t];
+                for (uint64_t y; (y = next++) < members.size();) {
+                    const Task& tk = members[y];
+                    const uint32_t k = ref[tk.pair], i = query[tk.pair];
+                    Cig& out = cig[tk.pair];
+                    if (route[tk.pair] == 1) {
+                        score[tk.pair] = backbone_cigar(S[k], S[i], &lists[static_cast<size_t>(k) * nk], &lists[static_cast<size_t>(i) * nk], nk, ks, max_gap, wk, out,
+                                                        &best_k[tk.pair]);
+                        continue;
+                    }
+                    const uint32_t j = via[tk.pair];
+                    const W::TrCig cij{cig[tk.ij].w.data(), static_cast<uint32_t>(cig[tk.ij].w.size()), ref[tk.ij] != j};
+                    const W::TrCig cjk{cig[tk.jk].w.data(), static_cast<uint32_t>(cig[tk.jk].w.size()), ref[tk.jk] != k};
+                    Cig walk;
+                    WalkVisitor v{S[k], S[i], max_gap, wk, walk};
+                    if (W::walk_transitive(cij, cjk, S[i].len, S[k].len, anchor_size, v)) out.w.swap(walk.w);
+                    else {
+                        WalkVisitor o{S[k], S[i], 0xFFFFFFFFu, wk, out};
+                        W::walk_optimize(walk.w.data(), static_cast<uint32_t>(walk.w.size()), W::kOptGap, W::kOptAnchor, o);
+                    }
+                    int sc = 0;                                                // Penalties::calculate_score, wfa.rs:87-99
+                    for (const uint32_t w : out.w) {
+                        const uint32_t op = w & 15u; const int len = static_cast<int>(w >> 4);
+                        sc -= op == G::OP_EQ ? 0 : (op == G::OP_X ? G::PEN_X * len : G::PEN_O + G::PEN_E * len);
+                    }
+                    score[tk.pair] = sc;
+                }
+            });
+        for (auto& th : pool) th.join();
+        for (const Task& tk : members) {                                       // save_cigar, align.rs:504-513
+            const uint32_t k = ref[tk.pair], i = query[tk.pair];
+            uint64_t nm = 0, ne = 0;
+            for (const uint32_t w : cig[tk.pair].w) ((w & 15u) == G::OP_EQ ? nm : ne) += w >> 4;
+            const double dv = static_cast<double>(ne) / static_cast<double>(nm + ne);
+            if (accelerate && dv <= tr_div && !(c_id[i] != NONE && c_dv[i] <= dv)) { c_id[i] = k; c_dv[i] = dv; c_pair[i] = tk.pair; }
+            cell[key(k, i)] = tk.pair;
+        }
+        rounds += accelerate && !members.empty() ? 1 : 0;
+        x0 = x;
+    }
+    if (n_rounds) *n_rounds = rounds;
     return now_ms() - t1;
 }
