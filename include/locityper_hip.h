@@ -958,7 +958,7 @@ int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, cha
  * process_alleles (src/command/add.rs:585-652) and what it calls, on buffers: the haplotype sequences of one locus, the reference
  * sequence of the locus and the k-mer counts `jellyfish query` returned for all of them (the caller runs Jellyfish, exactly as the
  * caller runs the mapper for aln.bam). Out of scope: pangenome-VCF reconstruction and locus expansion (panvcf.rs, add.rs:370-518),
- * ref.bed, lock and `success` files, prune / augment. (haplotypes.paf.gz: lcty_align_haplotypes, further down.)
+ * ref.bed, lock and `success` files, augment. (haplotypes.paf.gz: lcty_align_haplotypes; prune: lcty_db_prune_locus, both further down.)
  * Integer work throughout: every output equals the reference's bit for bit (the f64 divergence is one IEEE division of two u32).
  *
  * lcty_db_minimizers: kmers::minimizers::<u64, _, NON_CANONICAL> + sort_unstable per sequence (src/seq/kmers.rs:265-331,
@@ -1052,7 +1052,7 @@ void    lcty_db_files_free(lcty_db_files* files);
  * construct_dominant_set -> inner_construct_dominant_set -> Cigar::locally_similar -> find_dominating_set (src/command/augment.rs:258-396,
  * src/seq/cigar.rs:656-751, src/algo/dom_set.rs) on buffers: the pairwise haplotype alignments as lcty_paf_read returns them (the
  * arguments of lcty_locus_set_hap_alns) and the haplotype lengths. The ids a basis holds are what lcty_locus_build_map_index takes.
- * Out of scope: prune, lock files and rerun modes of augment. (The PAF itself: lcty_align_haplotypes, below.)
+ * Out of scope: lock files and rerun modes of augment. (The PAF itself: lcty_align_haplotypes; prune: lcty_db_prune_locus, both below.)
  * Integer work: the bit rows equal the reference's bit for bit. Differences, on purpose: a contig not longer than the window has ONE
  * window (the reference's `l - window`, augment.rs:323, underflows there); the entries are those lcty_paf_read keeps (full length, forward
  * strand); the reference solves the covering problem with SCIP, so only the SIZE of the optimum can be compared, not which optimum.
@@ -1241,6 +1241,134 @@ int32_t lcty_align_haplotypes_transitive(lcty_ctx* ctx, uint32_t n_seqs, const u
                                          const lcty_align_tr_params* tr_params, lcty_align_out* out, lcty_align_tr_out* tr_out,
                                          lcty_align_stats* stats, lcty_align_tr_stats* tr_stats);
 void    lcty_align_tr_out_free(lcty_align_tr_out* out);
+
+/* ---- pruning similar haplotypes (locityper prune: DB/loci/<locus>/ -> a thinned DB/loci/<locus>/, all_haplotypes.nwk.gz) ----------------
+ * process_locus + prune_files (src/command/prune.rs:471-582) on buffers, for one locus. Out of scope: *.bed copies, `success` and lock
+ * files, rerun modes, --subset-loci and the loop over loci.
+ *
+ * lcty_paf_divergences (host): load_divergences (prune.rs:159-230) on the decompressed text of haplotypes.paf (lcty_io_read_file gives
+ *   it). Lines end at '\n'; white space at the end of a line is dropped before it is split at tabs. Per line: columns 1 and 6 are the
+ *   two names; the first column from the 13th on that starts with `<field>:` is the tag, its value is what follows the two type
+ *   characters (`dv:f:0.01` -> 0.01), parsed as Rust's str::parse::<f64> does (decimal, exponent, inf / infinity / nan in any case,
+ *   an optional sign; no white space, no hexadecimal). Skipped, as there: a line naming a contig the locus does not have (checked
+ *   column 1 first, so '#' lines and empty lines fall here), self pairs, lines without the tag, negative values (n_negative), a
+ *   second DIFFERENT value for a pair (n_conflicting; the first stays). A tag whose value does not parse: LCTY_ERR_INVALID_DATA; so
+ *   is a line of a known contig with fewer than 6 columns, or of two known contigs with fewer than 12 (the reference indexes past the
+ *   end there). Pairs without a value become repl_missing (n_missing; missing_i < missing_j is the LAST such pair in triangle order,
+ *   the one the reference names in its warning; UINT32_MAX without one); the caller passes 10 x threshold, or +inf with n_clusters
+ *   (process_locus:537). All pairs missing (n < 2 included): LCTY_ERR_INVALID_INPUT. field NULL = "dv"; a field with ':' is
+ *   LCTY_ERR_INVALID_INPUT (Args::validate, 63). tri[n (n - 1) / 2]: TriangleMatrix's linear order (src/ext/trimat.rs:43-46: rows
+ *   i, then j > i). A caller that has lcty_align_haplotypes' result passes nerrs / aln_len per pair instead and never makes the text.
+ * lcty_prune_multiplicities (host): DiscardedHaplotypes::load (src/seq/contigs.rs:488-528) on the text of the locus's old
+ *   discarded_haplotypes.txt, as far as pruning uses it: mult[n] = 1 + the number of names listed for the contig (add_identical,
+ *   prune.rs:251-260, counts `~` entries as well). A line with fewer than 3 columns: LCTY_ERR_INVALID_INPUT. text NULL / len 0: all 1.
+ *   *all_identical (may be NULL): 0 when a line has `~` (the reference then warns that the tree will be inaccurate).
+ * lcty_prune_linkage (device): complete-linkage clustering of the triangle — what the reference asks of kodama::linkage(..,
+ *   Method::Complete) (prune.rs:375). THE CONTRACT, which is this library's own definition: leaves carry the labels 0 .. n - 1, step
+ *   s creates label n + s; at every step, among the active clusters, the pair (a, b), a < b BY LABEL, with the smallest dissimilarity
+ *   is merged, on equal dissimilarities the smallest a, then the smallest b; the new cluster's dissimilarity to every other cluster x
+ *   is max(D[a][x], D[b][x]). steps[n - 1] = {cluster1 < cluster2, dissimilarity, size}. Every dissimilarity is one of the input
+ *   values, bit for bit; +inf is a legal input, NaN is LCTY_ERR_INVALID_INPUT; the steps come out in non-decreasing order. Where all
+ *   input values are distinct the dendrogram is unique (and is SciPy's linkage(.., 'complete'), whose output kodama documents as its
+ *   own); under ties equality with the reference is NOT claimed: kodama is not in the reference tree.
+ *   n = 1: zero steps. n > LCTY_PRUNE_MAX_N: LCTY_ERR_UNSUPPORTED, before anything is read or allocated.
+ *   The full symmetric matrix lives in device memory (8 n^2 bytes: 512 MB at n = 8 192), built from the triangle by a kernel of
+ *   many workgroups; per matrix row the minimum and its partner of smallest label are cached; the n - 1 merges run in ONE launch of
+ *   ONE workgroup (no cross-workgroup wait of any kind): argmin over the cached rows, new row and column as the elementwise maximum,
+ *   rescan of the rows whose cached partner was merged (one wavefront per row).
+ * lcty_prune_cluster (device): cluster_haplotypes (prune.rs:350-427) without its texts: linkage, the cut, the clusters and their
+ *   representatives. Cut: with n_clusters != 0 the threshold is steps[n - n_clusters - 1].dissimilarity, 0 when n <= n_clusters
+ *   (select_cut_threshold, 327-347); a step is above the cut iff dissimilarity > threshold. Clusters in the order the reference's
+ *   loop meets them (by step, child 1 before child 2, the root last when no step exceeded the cut), members in merge_and_clear order
+ *   (the first child's, then the second's). Representatives: select_representative (276-304), one workgroup per cluster of more
+ *   than one member, one thread per member x accumulating over y in member order exactly as buf[x] is fed there: epsilon =
+ *   max(1e-6 min(tri), 1e-12) (1e-12 when n = 1), div = epsilon + D, PowerMean::update_mult (src/math/mod.rs:288-295) with powi as
+ *   compiler-rt's __powidf2 and nothing fused: the accumulators equal the reference's bit for bit for min, max and every non-zero
+ *   power; power 0 uses the device's log (no bit equality claimed). The representative is the first minimum of the accumulators,
+ *   the first maximum for negative powers (src/ext/vec.rs:223-232). mult[n] (NULL: all 1). power: -128 .. 127, LCTY_PRUNE_POWER_MIN
+ *   or LCTY_PRUNE_POWER_MAX. threshold < 0 or NaN: LCTY_ERR_INVALID_INPUT. Released with lcty_prune_out_free.
+ * lcty_prune_texts (host): the Newick text (Cluster::new / add_identical / merge_and_clear, 243-274: a leaf is its name, with old
+ *   discarded names `(name:0,other:0,...)`, a merge `(A:{:.8},B:{:.8})` with branch 0.5 (div - child.div), the root + ";\n") and the
+ *   new discarded_haplotypes.txt: the old text, then `repr ~ a, b, c\n` per cluster of more than one member (write_discarded_haplotypes,
+ *   306-323). names: n 0-terminated names one after the other. *newick, *discarded released with lcty_io_free; *discarded_len 0: no file.
+ * lcty_db_prune_locus: process_locus + prune_files on the DECOMPRESSED contents of the locus directory: paf (required), kmers (both
+ *   KmerCounts blocks of kmers.bin.*; NULL: none), distances (distances.bin; NULL: none), discarded (the old discarded_haplotypes.txt;
+ *   NULL: none; not read with skip_tree, as there, so its lines are not carried over then). Out: newick (unless skip_tree); with
+ *   only_tree nothing else; discarded (old + new lines; empty: no file), keep (sorted ids). If every haplotype is kept, unchanged = 1
+ *   and the caller copies its files as they are (copy_output_files). Otherwise fasta (the kept haplotypes in id order, one line per
+ *   sequence: fastx::write_fasta), kmers (both blocks thinned, KmerCounts::thin_out + save; empty with LCTY_PRUNE_WARN_KMERS when the
+ *   blocks do not match the haplotypes, as prune.rs:494-503), distances (TriangleMatrix::thin_out + write_divergences) and paf
+ *   (prune_paf, src/seq/paf.rs:237-267: '#' lines kept, a line kept iff both names are kept, fewer than 7 columns LCTY_ERR_INVALID_DATA).
+ *   The containers (.gz, .br) are the writers' business. Released with lcty_prune_files_free.
+ * lcty_prune_thin (host): that second half alone, for ids the caller has: fasta, kmers, distances, paf of `keep` (ascending) into *out. */
+#define LCTY_PRUNE_MAX_N      16384u
+#define LCTY_PRUNE_POWER_MIN  INT32_MIN          /* PowerMean::Min */
+#define LCTY_PRUNE_POWER_MAX  INT32_MAX          /* PowerMean::Max */
+#define LCTY_PRUNE_WARN_KMERS 1u                 /* the k-mer counts do not match the haplotypes: no kmers output */
+typedef struct lcty_paf_div_stats {
+    uint64_t n_missing, n_negative, n_conflicting;
+    uint32_t missing_i, missing_j;
+} lcty_paf_div_stats;
+typedef struct lcty_prune_step {
+    uint32_t cluster1, cluster2;      /* labels, cluster1 < cluster2 */
+    double   dissimilarity;
+    uint32_t size, _pad0;
+} lcty_prune_step;
+typedef struct lcty_prune_params {
+    double   threshold;               /* 0.0002 (prune.rs:49) */
+    uint32_t n_clusters;              /* 0 = none: cut at threshold */
+    int32_t  power;                   /* 2 (prune.rs:51) */
+    int32_t  only_tree, skip_tree;    /* 0, 0: lcty_db_prune_locus only */
+} lcty_prune_params;
+typedef struct lcty_prune_stats {
+    uint64_t n_rescans, n_rep_pairs;  /* rows scanned again by the merge loop; pair terms of the representatives kernel */
+    uint64_t bytes_h2d, bytes_d2h, matrix_bytes;
+    /* wall time per stage with the stream drained at its end: matrix + row caches, the merge loop, representatives, host work, whole call */
+    double   build_ms, merge_ms, repr_ms, host_ms, total_ms;
+} lcty_prune_stats;
+typedef struct lcty_prune_out {
+    uint32_t  n, n_clusters;          /* n_clusters: clusters found (= haplotypes kept) */
+    double    threshold, epsilon;     /* the cut used; the epsilon of the representatives */
+    lcty_prune_step* steps;           /* [n - 1] */
+    uint32_t* keep_ids;               /* [n_clusters] ascending */
+    uint32_t* cluster_off;            /* [n_clusters + 1] into members / acc */
+    uint32_t* members;                /* [n] */
+    uint32_t* repr;                   /* [n_clusters] */
+    double*   acc;                    /* [n] the accumulators, beside members (0 for clusters of one) */
+    lcty_prune_stats stats;
+} lcty_prune_out;
+typedef struct lcty_prune_files {
+    uint8_t* newick;    uint64_t newick_len;       /* text of all_haplotypes.nwk (empty with skip_tree) */
+    uint8_t* discarded; uint64_t discarded_len;    /* discarded_haplotypes.txt (empty: no file) */
+    uint8_t* fasta;     uint64_t fasta_len;        /* text of haplotypes.fa */
+    uint8_t* kmers;     uint64_t kmers_len;        /* kmers.bin: both blocks */
+    uint8_t* distances; uint64_t distances_len;    /* distances.bin (empty: there was none) */
+    uint8_t* paf;       uint64_t paf_len;          /* text of haplotypes.paf */
+    uint32_t* keep;     uint32_t n_keep;
+    int32_t  unchanged;                            /* every haplotype kept: fasta, kmers, distances, paf are empty, the inputs stand */
+    uint32_t warn_bits, _pad0;
+    double   threshold;
+    lcty_paf_div_stats div;
+    lcty_prune_stats stats;
+} lcty_prune_files;
+
+void    lcty_prune_params_default(lcty_prune_params* params);
+int32_t lcty_paf_divergences(const uint8_t* text, uint64_t len, const char* const* names, uint32_t n, const char* field, double repl_missing,
+                             double* tri, lcty_paf_div_stats* stats);
+int32_t lcty_prune_multiplicities(const char* text, uint64_t len, const char* const* names, uint32_t n, uint32_t* mult, int32_t* all_identical);
+int32_t lcty_prune_linkage(lcty_ctx* ctx, uint32_t n, const double* tri, lcty_prune_step* steps, lcty_prune_stats* stats);
+int32_t lcty_prune_cluster(lcty_ctx* ctx, uint32_t n, const double* tri, const uint32_t* mult, const lcty_prune_params* params, lcty_prune_out* out);
+void    lcty_prune_out_free(lcty_prune_out* out);
+int32_t lcty_prune_texts(uint32_t n, const char* names, const char* old_discarded, uint64_t old_len, const lcty_prune_out* res,
+                         uint8_t** newick, uint64_t* newick_len, uint8_t** discarded, uint64_t* discarded_len);
+int32_t lcty_db_prune_locus(lcty_ctx* ctx, uint32_t n, const char* names, const uint8_t* seqs, const uint64_t* seq_off, const uint8_t* paf,
+                            uint64_t paf_len, const uint8_t* kmers, uint64_t kmers_len, const uint8_t* distances, uint64_t distances_len,
+                            const char* discarded, uint64_t discarded_len, const char* field, const lcty_prune_params* params,
+                            lcty_prune_files* out);
+int32_t lcty_prune_thin(uint32_t n, const char* names, const uint8_t* seqs, const uint64_t* seq_off, const uint8_t* paf, uint64_t paf_len,
+                        const uint8_t* kmers, uint64_t kmers_len, const uint8_t* distances, uint64_t distances_len, const uint32_t* keep,
+                        uint32_t n_keep, lcty_prune_files* out);
+void    lcty_prune_files_free(lcty_prune_files* files);
 
 #ifdef __cplusplus
 }

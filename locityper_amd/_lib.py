@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -58,6 +58,16 @@ SIGNATURES = {
                                                P(AlignStats), P(AlignTrStats)]),
     "lcty_align_tr_out_free": (None, [P(AlignTrOut)]),
     "lcty_paf_write_text": (I32, [P(AlignParams), U32, C.c_char_p, VP, U64, VP, VP, P(AlignOut), VP, U64, P(U64)]),
+    "lcty_prune_params_default": (None, [P(PruneParams)]),
+    "lcty_paf_divergences": (I32, [VP, U64, P(C.c_char_p), U32, C.c_char_p, D, VP, P(PafDivStats)]),
+    "lcty_prune_multiplicities": (I32, [C.c_char_p, U64, P(C.c_char_p), U32, VP, P(I32)]),
+    "lcty_prune_linkage": (I32, [VP, U32, VP, VP, P(PruneStats)]),
+    "lcty_prune_cluster": (I32, [VP, U32, VP, VP, P(PruneParams), P(PruneOut)]),
+    "lcty_prune_out_free": (None, [P(PruneOut)]),
+    "lcty_prune_texts": (I32, [U32, C.c_char_p, C.c_char_p, U64, P(PruneOut), P(VP), P(U64), P(VP), P(U64)]),
+    "lcty_db_prune_locus": (I32, [VP, U32, C.c_char_p, VP, VP, VP, U64, VP, U64, VP, U64, C.c_char_p, U64, C.c_char_p, P(PruneParams), P(PruneFiles)]),
+    "lcty_prune_thin": (I32, [U32, C.c_char_p, VP, VP, VP, U64, VP, U64, VP, U64, VP, U32, P(PruneFiles)]),
+    "lcty_prune_files_free": (None, [P(PruneFiles)]),
     "lcty_last_error": (C.c_char_p, []),
     "lcty_version": (C.c_char_p, []),
     "lcty_device_count": (I32, []),

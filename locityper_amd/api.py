@@ -1296,3 +1296,170 @@ def align_backbone(ctx, seqs, seq_off, ref, query, k, params=None):
     finally:
         lib().lcty_align_backbone_out_free(C.byref(o))
     return res, st.as_dict()
+
+
+# ---- pruning similar haplotypes (locityper prune; lcty_prune.hip) ------------------------------------------------------------------------
+def prune_power(power):
+    """`--power` as lcty_prune_params.power takes it: "min" / "max" (PowerMean::from_str's names) or an integer -128 .. 127."""
+    if isinstance(power, str):
+        low = power.lower()
+        if low in ("min", "-inf", "neg-inf"):
+            return cdefs.PRUNE_POWER_MIN
+        if low in ("max", "inf"):
+            return cdefs.PRUNE_POWER_MAX
+        return 0 if low == "geom" else int(power)
+    return int(power)
+
+
+def prune_params(**kw):
+    """lcty_prune_params_default (threshold 0.0002, no n_clusters, power 2) with overrides; power takes prune_power's forms."""
+    p = cdefs.PruneParams()
+    lib().lcty_prune_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, prune_power(v) if k == "power" else v)
+    return p
+
+
+def _name_array(names):
+    return (C.c_char_p * len(names))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
+
+
+def paf_divergences(text, names, field=None, repl_missing=0.002):
+    """lcty_paf_divergences: (triangle f64 in the order rows i, then j > i; dict n_missing, n_negative, n_conflicting, missing_i, missing_j)."""
+    buf = bytes(text)
+    n = len(names)
+    tri = np.zeros(max(n * (n - 1) // 2, 1), dtype=np.float64)
+    st = cdefs.PafDivStats()
+    check(lib().lcty_paf_divergences(buf, len(buf), _name_array(names), n, None if field is None else field.encode(), float(repl_missing),
+                                     tri.ctypes.data, C.byref(st)))
+    return tri[:n * (n - 1) // 2], st.as_dict()
+
+
+def prune_multiplicities(text, names):
+    """lcty_prune_multiplicities: (mult u32[n] = 1 + names the old discarded_haplotypes.txt lists per contig, all_identical)."""
+    buf = None if text is None else bytes(text)
+    mult = np.zeros(max(len(names), 1), dtype=np.uint32)
+    all_id = C.c_int32(1)
+    check(lib().lcty_prune_multiplicities(buf, 0 if buf is None else len(buf), _name_array(names), len(names), mult.ctypes.data, C.byref(all_id)))
+    return mult[:len(names)], bool(all_id.value)
+
+
+def _tri(n, tri):
+    t = np.ascontiguousarray(tri, dtype=np.float64)
+    if len(t) != n * (n - 1) // 2:
+        raise ValueError("tri must hold n (n - 1) / 2 values")
+    return t if len(t) else np.zeros(1, dtype=np.float64)
+
+
+def prune_linkage(ctx, n, tri):
+    """lcty_prune_linkage: (steps as a structured array cluster1, cluster2, dissimilarity, size; stats dict)."""
+    t = _tri(n, tri)
+    steps = np.zeros(max(n - 1, 1), dtype=cdefs.PRUNE_STEP_DTYPE)
+    st = cdefs.PruneStats()
+    check(lib().lcty_prune_linkage(ctx._h, n, t.ctypes.data, steps.ctypes.data, C.byref(st)))
+    return steps[:n - 1], st.as_dict()
+
+
+def _prune_out_dict(o):
+    n, nc = int(o.n), int(o.n_clusters)
+    steps = np.frombuffer(C.string_at(o.steps, cdefs.PRUNE_STEP_DTYPE.itemsize * (n - 1)), dtype=cdefs.PRUNE_STEP_DTYPE).copy() if n > 1 \
+        else np.zeros(0, dtype=cdefs.PRUNE_STEP_DTYPE)
+    off = _copy(o.cluster_off, nc + 1, np.uint32)
+    members, acc = _copy(o.members, n, np.uint32), _copy(o.acc, n, np.float64)
+    return {"steps": steps, "threshold": float(o.threshold), "epsilon": float(o.epsilon), "keep_ids": _copy(o.keep_ids, nc, np.uint32),
+            "clusters": [members[int(off[k]):int(off[k + 1])] for k in range(nc)], "acc": [acc[int(off[k]):int(off[k + 1])] for k in range(nc)],
+            "repr": _copy(o.repr, nc, np.uint32), "stats": o.stats.as_dict()}
+
+
+def prune_cluster(ctx, n, tri, mult=None, params=None, names=None, old_discarded=None):
+    """lcty_prune_cluster: dict of steps, threshold, epsilon, keep_ids (sorted), clusters (member arrays in the reference's order), acc
+    (the accumulators beside them), repr, stats. With names also newick and discarded (lcty_prune_texts on the same result)."""
+    p = params if params is not None else prune_params()
+    t = _tri(n, tri)
+    m = None if mult is None else np.ascontiguousarray(mult, dtype=np.uint32)
+    o = cdefs.PruneOut()
+    check(lib().lcty_prune_cluster(ctx._h, n, t.ctypes.data, None if m is None else m.ctypes.data, C.byref(p), C.byref(o)))
+    try:
+        res = _prune_out_dict(o)
+        if names is not None:
+            res["newick"], res["discarded"] = _prune_texts(names, old_discarded, o)
+    finally:
+        lib().lcty_prune_out_free(C.byref(o))
+    return res
+
+
+def _prune_texts(names, old_discarded, o):
+    from .io import _names_blob
+    old = None if old_discarded is None else bytes(old_discarded)
+    a, al, b, bl = VP(), U64(), VP(), U64()
+    check(lib().lcty_prune_texts(len(names), _names_blob(names), old, 0 if old is None else len(old), C.byref(o), C.byref(a), C.byref(al),
+                                 C.byref(b), C.byref(bl)))
+    try:
+        return C.string_at(a, al.value), C.string_at(b, bl.value)
+    finally:
+        lib().lcty_io_free(a)
+        lib().lcty_io_free(b)
+
+
+def prune_texts(names, steps, clusters, reprs, old_discarded=None):
+    """lcty_prune_texts (host only) on a result given as arrays: (Newick text, discarded_haplotypes.txt text)."""
+    n = len(names)
+    st = np.ascontiguousarray(steps, dtype=cdefs.PRUNE_STEP_DTYPE)
+    off = np.zeros(len(clusters) + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(c) for c in clusters])
+    mem = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint32) for c in clusters]), dtype=np.uint32)
+    rp = np.ascontiguousarray(reprs, dtype=np.uint32)
+    o = cdefs.PruneOut()
+    o.n, o.n_clusters = n, len(clusters)
+    o.steps, o.cluster_off, o.members, o.repr = st.ctypes.data if len(st) else None, off.ctypes.data, mem.ctypes.data, rp.ctypes.data
+    return _prune_texts(names, old_discarded, o)
+
+
+def db_prune_locus(ctx, names, seqs, seq_off, paf, kmers=None, distances=None, discarded=None, field=None, params=None):
+    """lcty_db_prune_locus: process_locus + prune_files on the decompressed contents of a locus directory. Returns a dict: newick,
+    discarded, fasta, kmers, distances, paf (bytes), keep, unchanged, warn_bits, threshold, div, stats."""
+    from .io import _names_blob
+    p = params if params is not None else prune_params()
+    sq, off = _seq_arrays(seqs, seq_off)
+    b = lambda x: None if x is None else bytes(x)
+    paf, kmers, distances, discarded = b(paf), b(kmers), b(distances), b(discarded)
+    ln = lambda x: 0 if x is None else len(x)
+    f = cdefs.PruneFiles()
+    check(lib().lcty_db_prune_locus(ctx._h, len(off) - 1, _names_blob(names), sq.ctypes.data, off.ctypes.data, paf, ln(paf), kmers, ln(kmers),
+                                    distances, ln(distances), discarded, ln(discarded), None if field is None else field.encode(), C.byref(p),
+                                    C.byref(f)))
+    try:
+        return _prune_files_dict(f)
+    finally:
+        lib().lcty_prune_files_free(C.byref(f))
+
+
+def _bytes_at(p, n):
+    return C.string_at(p, n) if p and n else b""
+
+
+def _prune_files_dict(f):
+    return {"newick": _bytes_at(f.newick, f.newick_len), "discarded": _bytes_at(f.discarded, f.discarded_len),
+            "fasta": _bytes_at(f.fasta, f.fasta_len), "kmers": _bytes_at(f.kmers, f.kmers_len),
+            "distances": _bytes_at(f.distances, f.distances_len), "paf": _bytes_at(f.paf, f.paf_len),
+            "keep": _copy(f.keep, int(f.n_keep), np.uint32), "unchanged": bool(f.unchanged), "warn_bits": int(f.warn_bits),
+            "threshold": float(f.threshold), "div": f.div.as_dict(), "stats": f.stats.as_dict()}
+
+
+def prune_thin(names, seqs, seq_off, paf, keep, kmers=None, distances=None):
+    """lcty_prune_thin (host only): the files of the kept haplotypes; the dict of db_prune_locus with fasta, kmers, distances, paf filled."""
+    from .io import _names_blob
+    sq, off = _seq_arrays(seqs, seq_off)
+    b = lambda x: None if x is None else bytes(x)
+    paf, kmers, distances = b(paf), b(kmers), b(distances)
+    ln = lambda x: 0 if x is None else len(x)
+    kp = np.ascontiguousarray(keep, dtype=np.uint32)
+    f = cdefs.PruneFiles()
+    check(lib().lcty_prune_thin(len(off) - 1, _names_blob(names), sq.ctypes.data, off.ctypes.data, paf, ln(paf), kmers, ln(kmers), distances,
+                                ln(distances), kp.ctypes.data, len(kp), C.byref(f)))
+    try:
+        return _prune_files_dict(f)
+    finally:
+        lib().lcty_prune_files_free(C.byref(f))

@@ -188,6 +188,54 @@ class AlignTrStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+PRUNE_MAX_N = 16384
+PRUNE_POWER_MIN, PRUNE_POWER_MAX = -(1 << 31), (1 << 31) - 1      # PowerMean::Min / ::Max
+PRUNE_WARN_KMERS = 1
+
+
+class PafDivStats(C.Structure):
+    """What load_divergences (src/command/prune.rs:159-230) only logs."""
+    _fields_ = [("n_missing", C.c_uint64), ("n_negative", C.c_uint64), ("n_conflicting", C.c_uint64), ("missing_i", C.c_uint32),
+                ("missing_j", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PruneStep(C.Structure):
+    _fields_ = [("cluster1", C.c_uint32), ("cluster2", C.c_uint32), ("dissimilarity", C.c_double), ("size", C.c_uint32), ("_pad0", C.c_uint32)]
+
+
+PRUNE_STEP_DTYPE = np.dtype([("cluster1", "<u4"), ("cluster2", "<u4"), ("dissimilarity", "<f8"), ("size", "<u4"), ("_pad0", "<u4")])
+
+
+class PruneParams(C.Structure):
+    """`locityper prune` (src/command/prune.rs:39-55): threshold 0.0002, no n_clusters, power 2."""
+    _fields_ = [("threshold", C.c_double), ("n_clusters", C.c_uint32), ("power", C.c_int32), ("only_tree", C.c_int32), ("skip_tree", C.c_int32)]
+
+
+class PruneStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_rescans", "n_rep_pairs", "bytes_h2d", "bytes_d2h", "matrix_bytes")] + \
+               [(n, C.c_double) for n in ("build_ms", "merge_ms", "repr_ms", "host_ms", "total_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PruneOut(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("n_clusters", C.c_uint32), ("threshold", C.c_double), ("epsilon", C.c_double), ("steps", C.c_void_p),
+                ("keep_ids", C.c_void_p), ("cluster_off", C.c_void_p), ("members", C.c_void_p), ("repr", C.c_void_p), ("acc", C.c_void_p),
+                ("stats", PruneStats)]
+
+
+class PruneFiles(C.Structure):
+    _fields_ = [("newick", C.c_void_p), ("newick_len", C.c_uint64), ("discarded", C.c_void_p), ("discarded_len", C.c_uint64),
+                ("fasta", C.c_void_p), ("fasta_len", C.c_uint64), ("kmers", C.c_void_p), ("kmers_len", C.c_uint64),
+                ("distances", C.c_void_p), ("distances_len", C.c_uint64), ("paf", C.c_void_p), ("paf_len", C.c_uint64),
+                ("keep", C.c_void_p), ("n_keep", C.c_uint32), ("unchanged", C.c_int32), ("warn_bits", C.c_uint32), ("_pad0", C.c_uint32),
+                ("threshold", C.c_double), ("div", PafDivStats), ("stats", PruneStats)]
+
+
 class BgReadsView(C.Structure):
     """The records of the background interval as load_alns keeps them (preproc.rs:988-1028)."""
     _fields_ = [
