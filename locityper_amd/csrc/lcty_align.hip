@@ -21,6 +21,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 
 namespace {
@@ -254,21 +255,6 @@ struct PlanVisitor {
         level = kLevels - 1;
     }
 };
-__global__ __launch_bounds__(64) void align_plan_kernel(const Task* __restrict__ tasks, uint32_t n_tasks, const uint64_t* __restrict__ off,
-                                                        const uint64_t* __restrict__ tm, const uint2* __restrict__ matches, const uint32_t* __restrict__ path,
-                                                        const uint32_t* __restrict__ path_start, uint32_t max_gap, Lim top, Levels lv,
-                                                        uint32_t* __restrict__ level, uint32_t* __restrict__ cig_cap) {
-    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= n_tasks) return;
-    const Task tk = tasks[t];
-    const uint64_t m0 = tm[t];
-    const uint32_t m = static_cast<uint32_t>(tm[t + 1] - m0);
-    PlanVisitor v{max_gap, top, lv, 0, 2};
-    walk_backbone(matches + m0, path + m0 + path_start[t], m - path_start[t], tk.k, static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]),
-                  static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]), v);
-    level[t] = v.level;
-    cig_cap[t] = static_cast<uint32_t>(min(v.bound, static_cast<uint64_t>(0xFFFFFFFFu)));
-}
 
 struct FillVisitor {
     PairSeq S; CigOut cg; uint32_t max_gap; Lim top, mine; gotoh::Cell* rows; uint8_t* dirs; int score; uint32_t dropped;
@@ -343,58 +329,37 @@ struct FillVisitor {
     }
 };
 
-// one lane per task of the level's list; lane g works in scratch + g * lane_bytes(mine)
-__global__ __launch_bounds__(64) void align_fill_kernel(const uint32_t* __restrict__ list, uint32_t n_list, uint32_t n_lanes, const Task* __restrict__ tasks,
-                                                        const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint64_t* __restrict__ tm,
-                                                        const uint2* __restrict__ matches, const uint32_t* __restrict__ path,
-                                                        const uint32_t* __restrict__ path_start, uint32_t max_gap, Lim top, Lim mine, uint8_t* __restrict__ scratch,
-                                                        const uint64_t* __restrict__ cig_off, uint32_t* __restrict__ cig, int32_t* __restrict__ t_score,
-                                                        uint32_t* __restrict__ t_words, uint32_t* __restrict__ t_dropped, unsigned long long* __restrict__ stats) {
-    const uint32_t g = blockIdx.x * 64 + threadIdx.x;
-    if (g >= n_lanes) return;
-    uint8_t* mem = scratch + static_cast<size_t>(g) * lane_bytes(mine);
-    for (uint32_t x = g; x < n_list; x += n_lanes) {
-        const uint32_t t = list[x];
+// the visitor of lane memory `mem` (lane_bytes(mine): two rows of mine.dim + 1 cells, then the direction bytes) that writes into cg
+__device__ inline FillVisitor fill_visitor(PairSeq S, CigOut cg, uint32_t max_gap, Lim top, Lim mine, uint8_t* mem) {
+    FillVisitor v;
+    v.S = S; v.cg = cg;
+    v.max_gap = max_gap; v.top = top; v.mine = mine;
+    v.rows = reinterpret_cast<gotoh::Cell*>(mem); v.dirs = mem + 2 * (static_cast<size_t>(mine.dim) + 1) * sizeof(gotoh::Cell);
+    v.score = 0; v.dropped = 0; v.cells = 0;
+    for (uint32_t r = 0; r < 4; r++) v.n_route[r] = 0;
+    return v;
+}
+
+// Task sources. Stage C has two kinds of task: a (pair, k) whose walk follows the chain of stage B, and a transitive pair whose walk
+// reads finished CIGARs. A source is a small struct the plan and the fill kernel take by value: walk(t, v) leads the visitor through
+// task t (true: the task turned out a shortcut), pair(t) names the two sequences it aligns, max_gap() is the threshold of its stretches;
+// planned() and filled() write the per-task outputs that only this route reads.
+struct BackboneSrc {
+    const Task* tasks; const uint64_t* tm; const uint2* matches; const uint32_t* path; const uint32_t* path_start; const uint64_t* off;
+    uint32_t gap; int32_t* t_score; uint32_t* t_dropped;
+    __device__ uint32_t max_gap() const { return gap; }
+    __device__ uint2 pair(uint32_t t) const { return make_uint2(tasks[t].ref, tasks[t].qry); }
+    template <class V> __device__ bool walk(uint32_t t, V& v) const {
         const Task tk = tasks[t];
         const uint64_t m0 = tm[t];
         const uint32_t m = static_cast<uint32_t>(tm[t + 1] - m0);
-        FillVisitor v;
-        v.S = PairSeq{seq + off[tk.ref], seq + off[tk.qry]};
-        v.cg = CigOut{cig + cig_off[t], 0, static_cast<uint32_t>(cig_off[t + 1] - cig_off[t]), false};
-        v.max_gap = max_gap; v.top = top; v.mine = mine;
-        v.rows = reinterpret_cast<gotoh::Cell*>(mem); v.dirs = mem + 2 * (static_cast<size_t>(mine.dim) + 1) * sizeof(gotoh::Cell);
-        v.score = 0; v.dropped = 0; v.cells = 0;
-        for (uint32_t r = 0; r < 4; r++) v.n_route[r] = 0;
         walk_backbone(matches + m0, path + m0 + path_start[t], m - path_start[t], tk.k, static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]),
                       static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]), v);
-        t_score[t] = v.score; t_words[t] = v.cg.n; t_dropped[t] = v.dropped;
-        for (uint32_t r = 0; r < 4; r++) if (v.n_route[r]) atomicAdd(&stats[r], v.n_route[r]);
-        if (v.dropped) atomicAdd(&stats[ST_DROPPED], static_cast<unsigned long long>(v.dropped));
-        if (v.cells) atomicAdd(&stats[ST_CELLS], v.cells);
-        if (v.cg.overflow) atomicAdd(&stats[ST_OVERFLOW], 1ull);
+        return false;
     }
-}
-
-// align_multik (align.rs:294-318): the best score over the ks, the first k on a tie; the counts of process_pair 652-660
-struct PairRes { int32_t score; uint32_t best_ki, n_matches, nerrs, n_words, _pad; };
-__global__ __launch_bounds__(64) void align_select_kernel(uint32_t n_pairs, uint32_t nk, const int32_t* __restrict__ t_score, const uint32_t* __restrict__ t_words,
-                                                          const uint64_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, PairRes* __restrict__ res) {
-    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= n_pairs) return;
-    uint32_t bk = 0;
-    for (uint32_t ki = 1; ki < nk; ki++) if (t_score[p * nk + ki] > t_score[p * nk + bk]) bk = ki;
-    const uint32_t t = p * nk + bk, nw = t_words[t];
-    const uint32_t* w = cig + cig_off[t];
-    uint32_t nm = 0, ne = 0;
-    for (uint32_t x = 0; x < nw; x++) { if ((w[x] & 15u) == OP_EQ) nm += w[x] >> 4; else ne += w[x] >> 4; }
-    res[p] = PairRes{t_score[t], bk, nm, ne, nw, 0};
-}
-__global__ __launch_bounds__(64) void align_gather_kernel(uint32_t nk, const PairRes* __restrict__ res, const uint64_t* __restrict__ cig_off,
-                                                          const uint32_t* __restrict__ cig, const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out) {
-    const uint32_t p = blockIdx.x;
-    const uint32_t* w = cig + cig_off[p * nk + res[p].best_ki];
-    for (uint32_t x = threadIdx.x; x < res[p].n_words; x += 64) out[out_off[p] + x] = w[x];
-}
+    __device__ void planned(uint32_t, bool) const {}
+    __device__ void filled(uint32_t t, const FillVisitor& v) const { t_score[t] = v.score; t_dropped[t] = v.dropped; }
+};
 
 // Transitive route -----------------------------------------------------------------------------------------------------------------------
 // Cigar::find_transitive_alignment (cigar.rs:1389-1414) = transfer_alignment::<true> (1248-1368): the alignment of query i to reference
@@ -406,58 +371,60 @@ __global__ __launch_bounds__(64) void align_gather_kernel(uint32_t nk, const Pai
 struct TrTaskDev { uint64_t ij_off, jk_off; uint32_t ij_n, jk_n, ref, qry, inv, _pad; };      // inv: bit 0 i-j is read inverted, bit 1 j-k
 using trwalk::TrCig; using trwalk::walk_transitive; using trwalk::walk_optimize;          // lcty_cigar_walk.hpp: the host probe instantiates them too
 
-// PASS 0: the walk of the two CIGARs out of the store; PASS 1: optimize over the CIGAR pass 0 left (src), a plain copy for a shortcut
-template <int PASS, class V>
-__device__ inline bool tr_pass(const TrTaskDev& tk, const uint32_t* store, const uint64_t* off, const uint32_t* src, uint32_t src_n, bool shortcut,
-                               uint32_t anchor_size, V& v) {
-    if (PASS == 0) {
-        const TrCig ij{store + tk.ij_off, tk.ij_n, (tk.inv & 1u) != 0}, jk{store + tk.jk_off, tk.jk_n, (tk.inv & 2u) != 0};
-        return walk_transitive(ij, jk, static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]), static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]), anchor_size, v);
-    }
-    if (shortcut) for (uint32_t x = 0; x < src_n; x++) v.item(src[x] & 15u, src[x] >> 4);
-    else walk_optimize(src, src_n, trwalk::kOptGap, trwalk::kOptAnchor, v);
-    return shortcut;
-}
-
-// the pass without aligning: the scratch level the task needs (the levels and the routing of stage C) and an upper bound of the items
-// it writes, by which its slice is reserved
+// PASS 0: the walk of the two CIGARs out of the store, with the caller's max_gap; it finds out which tasks are shortcuts. PASS 1: optimize
+// (no maximum gap) over the CIGAR pass 0 left at src + src_off[t], a plain copy for a shortcut
 template <int PASS>
-__global__ __launch_bounds__(64) void tr_plan_kernel(const TrTaskDev* __restrict__ tasks, uint32_t n_tasks, const uint64_t* __restrict__ off,
-                                                     const uint32_t* __restrict__ store, uint32_t anchor_size, uint32_t max_gap, Lim top, Levels lv,
-                                                     const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ src, const uint32_t* __restrict__ src_words,
-                                                     uint8_t* __restrict__ shortcut, uint32_t* __restrict__ level, uint32_t* __restrict__ cig_cap) {
+struct TrSrc {
+    const TrTaskDev* tasks; const uint64_t* off; const uint32_t* store; uint32_t anchor_size, gap;
+    const uint64_t* src_off; const uint32_t* src; const uint32_t* src_words; uint8_t* shortcut;
+    __device__ uint32_t max_gap() const { return PASS == 0 ? gap : 0xFFFFFFFFu; }
+    __device__ uint2 pair(uint32_t t) const { return make_uint2(tasks[t].ref, tasks[t].qry); }
+    template <class V> __device__ bool walk(uint32_t t, V& v) const {
+        if (PASS == 0) {
+            const TrTaskDev tk = tasks[t];
+            const TrCig ij{store + tk.ij_off, tk.ij_n, (tk.inv & 1u) != 0}, jk{store + tk.jk_off, tk.jk_n, (tk.inv & 2u) != 0};
+            return walk_transitive(ij, jk, static_cast<uint32_t>(off[tk.qry + 1] - off[tk.qry]), static_cast<uint32_t>(off[tk.ref + 1] - off[tk.ref]), anchor_size, v);
+        }
+        const uint32_t* w = src + src_off[t];
+        const uint32_t n = src_words[t];
+        const bool sc = shortcut[t] != 0;
+        if (sc) for (uint32_t x = 0; x < n; x++) v.item(w[x] & 15u, w[x] >> 4);
+        else walk_optimize(w, n, trwalk::kOptGap, trwalk::kOptAnchor, v);
+        return sc;
+    }
+    __device__ void planned(uint32_t t, bool sc) const { if (PASS == 0) shortcut[t] = sc ? 1 : 0; }
+    __device__ void filled(uint32_t, const FillVisitor&) const {}
+};
+
+// The two kernels of stage C, instantiated for BackboneSrc (the backbone route), TrSrc<0> (the transitive walk) and TrSrc<1> (optimize).
+// The plan is the walk without aligning: the scratch level the task needs and an upper bound of the items it writes, by which its slice
+// is reserved.
+template <class Src>
+__global__ __launch_bounds__(64) void align_plan_kernel(Src src, uint32_t n_tasks, Lim top, Levels lv, uint32_t* __restrict__ level, uint32_t* __restrict__ cig_cap) {
     const uint32_t t = blockIdx.x * 64 + threadIdx.x;
     if (t >= n_tasks) return;
-    PlanVisitor v{PASS == 0 ? max_gap : 0xFFFFFFFFu, top, lv, 0, 2};
-    const bool sc = tr_pass<PASS>(tasks[t], store, off, PASS ? src + src_off[t] : nullptr, PASS ? src_words[t] : 0u, PASS ? shortcut[t] != 0 : false, anchor_size, v);
-    if (PASS == 0) shortcut[t] = sc ? 1 : 0;
+    PlanVisitor v{src.max_gap(), top, lv, 0, 2};
+    src.planned(t, src.walk(t, v));
     level[t] = v.level;
     cig_cap[t] = static_cast<uint32_t>(min(v.bound, static_cast<uint64_t>(0xFFFFFFFFu)));
 }
 
-// one lane per task of the level's list, as align_fill_kernel; the CIGAR goes to cig + cig_off[t]
-template <int PASS>
-__global__ __launch_bounds__(64) void tr_fill_kernel(const uint32_t* __restrict__ list, uint32_t n_list, uint32_t n_lanes, const TrTaskDev* __restrict__ tasks,
-                                                     const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint32_t* __restrict__ store,
-                                                     uint32_t anchor_size, uint32_t max_gap, Lim top, Lim mine, uint8_t* __restrict__ scratch,
-                                                     const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ src, const uint32_t* __restrict__ src_words,
-                                                     const uint8_t* __restrict__ shortcut, const uint64_t* __restrict__ cig_off, uint32_t* __restrict__ cig,
-                                                     uint32_t* __restrict__ t_words, unsigned long long* __restrict__ stats) {
+// one lane per task of the level's list; lane g works in scratch + g * lane_bytes(mine); the CIGAR goes to cig + cig_off[t]
+template <class Src>
+__global__ __launch_bounds__(64) void align_fill_kernel(Src src, const uint32_t* __restrict__ list, uint32_t n_list, uint32_t n_lanes, const uint8_t* __restrict__ seq,
+                                                        Lim top, Lim mine, uint8_t* __restrict__ scratch, const uint64_t* __restrict__ cig_off,
+                                                        uint32_t* __restrict__ cig, uint32_t* __restrict__ t_words, unsigned long long* __restrict__ stats) {
     const uint32_t g = blockIdx.x * 64 + threadIdx.x;
     if (g >= n_lanes) return;
     uint8_t* mem = scratch + static_cast<size_t>(g) * lane_bytes(mine);
     for (uint32_t x = g; x < n_list; x += n_lanes) {
         const uint32_t t = list[x];
-        const TrTaskDev tk = tasks[t];
-        FillVisitor v;
-        v.S = PairSeq{seq + off[tk.ref], seq + off[tk.qry]};
-        v.cg = CigOut{cig + cig_off[t], 0, static_cast<uint32_t>(cig_off[t + 1] - cig_off[t]), false};
-        v.max_gap = PASS == 0 ? max_gap : 0xFFFFFFFFu; v.top = top; v.mine = mine;
-        v.rows = reinterpret_cast<gotoh::Cell*>(mem); v.dirs = mem + 2 * (static_cast<size_t>(mine.dim) + 1) * sizeof(gotoh::Cell);
-        v.score = 0; v.dropped = 0; v.cells = 0;
-        for (uint32_t r = 0; r < 4; r++) v.n_route[r] = 0;
-        tr_pass<PASS>(tk, store, off, PASS ? src + src_off[t] : nullptr, PASS ? src_words[t] : 0u, PASS ? shortcut[t] != 0 : false, anchor_size, v);
+        const uint2 p = src.pair(t);
+        FillVisitor v = fill_visitor(PairSeq{seq + src.off[p.x], seq + src.off[p.y]},
+                                     CigOut{cig + cig_off[t], 0, static_cast<uint32_t>(cig_off[t + 1] - cig_off[t]), false}, src.max_gap(), top, mine, mem);
+        src.walk(t, v);
         t_words[t] = v.cg.n;
+        src.filled(t, v);
         for (uint32_t r = 0; r < 4; r++) if (v.n_route[r]) atomicAdd(&stats[r], v.n_route[r]);
         if (v.dropped) atomicAdd(&stats[ST_DROPPED], static_cast<unsigned long long>(v.dropped));
         if (v.cells) atomicAdd(&stats[ST_CELLS], v.cells);
@@ -465,27 +432,50 @@ __global__ __launch_bounds__(64) void tr_fill_kernel(const uint32_t* __restrict_
     }
 }
 
-// the counts of process_pair 652-660 and Penalties::calculate_score (wfa.rs:87-99) of a finished transitive CIGAR; best_ki stays 0
+// the '=' bases and the others of a finished CIGAR (the counts of process_pair 652-660); err(op, len) sees every item that is not '=',
+// so that a caller with a sum of its own reads the words once
+struct CigCounts { uint32_t n_matches, nerrs; };
+template <class F>
+__device__ inline CigCounts cig_counts(const uint32_t* w, uint32_t nw, F err) {
+    CigCounts c{0, 0};
+    for (uint32_t x = 0; x < nw; x++) {
+        const uint32_t op = w[x] & 15u, len = w[x] >> 4;
+        if (op == OP_EQ) c.n_matches += len;
+        else { c.nerrs += len; err(op, len); }
+    }
+    return c;
+}
+
+// align_multik (align.rs:294-318): the best score over the ks, the first k on a tie
+struct PairRes { int32_t score; uint32_t best_ki, n_matches, nerrs, n_words, _pad; };
+__global__ __launch_bounds__(64) void align_select_kernel(uint32_t n_pairs, uint32_t nk, const int32_t* __restrict__ t_score, const uint32_t* __restrict__ t_words,
+                                                          const uint64_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, PairRes* __restrict__ res) {
+    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n_pairs) return;
+    uint32_t bk = 0;
+    for (uint32_t ki = 1; ki < nk; ki++) if (t_score[p * nk + ki] > t_score[p * nk + bk]) bk = ki;
+    const uint32_t t = p * nk + bk, nw = t_words[t];
+    const CigCounts c = cig_counts(cig + cig_off[t], nw, [](uint32_t, uint32_t) {});
+    res[p] = PairRes{t_score[t], bk, c.n_matches, c.nerrs, nw, 0};
+}
+// a finished transitive CIGAR: its score is Penalties::calculate_score (wfa.rs:87-99) of its items; best_ki stays 0
 __global__ __launch_bounds__(64) void tr_count_kernel(uint32_t n_tasks, const uint64_t* __restrict__ cig_off, const uint32_t* __restrict__ cig,
                                                       const uint32_t* __restrict__ t_words, PairRes* __restrict__ res) {
     const uint32_t t = blockIdx.x * 64 + threadIdx.x;
     if (t >= n_tasks) return;
-    const uint32_t* w = cig + cig_off[t];
     const uint32_t nw = t_words[t];
-    uint32_t nm = 0, ne = 0;
     int32_t score = 0;
-    for (uint32_t x = 0; x < nw; x++) {
-        const uint32_t op = w[x] & 15u, len = w[x] >> 4;
-        if (op == OP_EQ) nm += len;
-        else { ne += len; score -= op == OP_X ? PEN_X * static_cast<int32_t>(len) : PEN_O + PEN_E * static_cast<int32_t>(len); }
-    }
-    res[t] = PairRes{score, 0, nm, ne, nw, 0};
+    const CigCounts c = cig_counts(cig + cig_off[t], nw, [&](uint32_t op, uint32_t len) {
+        score -= op == OP_X ? PEN_X * static_cast<int32_t>(len) : PEN_O + PEN_E * static_cast<int32_t>(len);
+    });
+    res[t] = PairRes{score, 0, c.n_matches, c.nerrs, nw, 0};
 }
-__global__ __launch_bounds__(64) void tr_gather_kernel(const PairRes* __restrict__ res, const uint64_t* __restrict__ cig_off, const uint32_t* __restrict__ cig,
-                                                       const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out) {
-    const uint32_t t = blockIdx.x;
-    const uint32_t* w = cig + cig_off[t];
-    for (uint32_t x = threadIdx.x; x < res[t].n_words; x += 64) out[out_off[t] + x] = w[x];
+// the CIGAR of pair p's best k to out + out_off[p]; a transitive task is a pair with one k
+__global__ __launch_bounds__(64) void align_gather_kernel(uint32_t nk, const PairRes* __restrict__ res, const uint64_t* __restrict__ cig_off,
+                                                          const uint32_t* __restrict__ cig, const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out) {
+    const uint32_t p = blockIdx.x;
+    const uint32_t* w = cig + cig_off[p * nk + res[p].best_ki];
+    for (uint32_t x = threadIdx.x; x < res[p].n_words; x += 64) out[out_off[p] + x] = w[x];
 }
 
 // Host ---------------------------------------------------------------------------------------------------------------------------------
@@ -543,6 +533,57 @@ struct Store {
     }
 };
 
+struct Prepared { std::vector<uint32_t> ks; Lim top; Levels lv; uint32_t max_gap; bool never; };
+
+// the buffers of one pass of stage C: per task the level and the bound the plan gives (level, cap), the slices reserved by the bounds
+// (off, cig) and the words the fill wrote into them, a level's task list and its lanes' scratch. slack: the owner keeps the workspace
+// for passes to come, so it grows with head-room; without it every buffer gets the exact size.
+struct StageC {
+    DevBuf<uint32_t> level, cap, list, cig, words; DevBuf<uint64_t> off; DevBuf<uint8_t> scratch;
+    bool slack = false;
+    template <typename T> void fit(DevBuf<T>& b, size_t n) const { if (slack) b.ensure_slack(n); else b.ensure(n); }
+};
+
+// one pass of stage C over the nt tasks of a source: plan, reserve the slices by the bounds, fill level by level. Returns the tasks per level.
+template <class Src>
+std::array<uint64_t, kLevels> stage_c(lcty_ctx* ctx, const Src& src, uint32_t nt, const uint8_t* seq, const Prepared& pr, StageC& ws, unsigned long long* stats,
+                                      lcty_align_stats& st, double& plan_ms, double& fill_ms) {
+    hipStream_t s = ctx->stream;
+    double t0 = now_ms();
+    ws.fit(ws.level, nt); ws.fit(ws.cap, nt); ws.fit(ws.list, nt);
+    hipLaunchKernelGGL(align_plan_kernel<Src>, dim3((nt + 63) / 64), dim3(64), 0, s, src, nt, pr.top, pr.lv, ws.level.p, ws.cap.p);
+    LCTY_HIP(hipGetLastError());
+    std::vector<uint32_t> level(nt), ccap(nt);
+    ws.level.download(level.data(), nt, s); ws.cap.download(ccap.data(), nt, s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    st.bytes_d2h += 8ull * nt;
+    std::vector<uint64_t> cig_off(nt + 1, 0);
+    for (uint32_t t = 0; t < nt; t++) cig_off[t + 1] = cig_off[t] + ccap[t];
+    ws.fit(ws.off, nt + 1); ws.fit(ws.cig, cig_off[nt] + 1); ws.fit(ws.words, nt);
+    ws.off.upload(cig_off.data(), nt + 1, s);
+    st.bytes_h2d += 8ull * (nt + 1);
+    plan_ms += now_ms() - t0; t0 = now_ms();
+    std::array<uint64_t, kLevels> n_level{};
+    std::vector<uint32_t> list;
+    for (uint32_t l = 0; l < kLevels; l++) {
+        list.clear();
+        for (uint32_t t = 0; t < nt; t++) if (level[t] == l) list.push_back(t);
+        if (list.empty()) continue;
+        const Lim mine = pr.lv.l[l];
+        const uint32_t lanes = static_cast<uint32_t>(std::min<size_t>(list.size(), kLevelLanes[l]));
+        ws.scratch.ensure(lanes * lane_bytes(mine));
+        ws.list.upload(list.data(), list.size(), s);
+        st.bytes_h2d += 4ull * list.size();
+        hipLaunchKernelGGL(align_fill_kernel<Src>, dim3((lanes + 63) / 64), dim3(64), 0, s, src, ws.list.p, static_cast<uint32_t>(list.size()), lanes, seq, pr.top, mine,
+                           ws.scratch.p, ws.off.p, ws.cig.p, ws.words.p, stats);
+        LCTY_HIP(hipGetLastError());
+        LCTY_HIP(hipStreamSynchronize(s));                                    // `list` is filled again
+        n_level[l] = list.size();
+    }
+    fill_ms += now_ms() - t0;
+    return n_level;
+}
+
 struct Capture {                                               // lcty_align_backbone: every stage's output of the one task
     std::vector<uint2> matches; std::vector<uint32_t> path, cigar; uint32_t chain = 0; int32_t score = 0; uint32_t dropped = 0;
 };
@@ -552,8 +593,8 @@ struct PairOut { int32_t score; uint32_t best_ki, n_matches, nerrs; std::vector<
 // the pairs [a, b) of refs / qrys through stages A to C; returns 0, or — the matches of the batch do not fit `budget` and the batch holds
 // more than one pair — the number of leading pairs whose matches do fit (at least 1): the caller comes back with those, so the counting
 // pass is repeated once, not once per halving
-uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, const uint32_t* refs, const uint32_t* qrys, uint64_t a, uint64_t b, uint32_t max_gap,
-               Lim top, uint64_t budget, PairOut* out, lcty_align_stats& st, Capture* cap, Store* store = nullptr, const uint64_t* pair_ix = nullptr) {
+uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, const uint32_t* refs, const uint32_t* qrys, uint64_t a, uint64_t b, const Prepared& pr,
+               uint64_t budget, PairOut* out, lcty_align_stats& st, Capture* cap, Store* store = nullptr, const uint64_t* pair_ix = nullptr) {
     hipStream_t s = ctx->stream;
     const uint32_t nk = static_cast<uint32_t>(ix.ks.size()), np = static_cast<uint32_t>(b - a), nt = np * nk;
     double t0 = now_ms();
@@ -596,8 +637,9 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
         st.match_ms += now_ms() - t0;
         return fit;
     }
-    DevBuf<uint2> d_m; DevBuf<uint32_t> d_dp, d_prev, d_path, d_chain, d_pstart; DevBuf<uint64_t> d_fen; DevBuf<unsigned long long> d_stats;
+    DevBuf<uint2> d_m; DevBuf<uint32_t> d_dp, d_prev, d_path, d_chain, d_pstart, d_drop; DevBuf<int32_t> d_score; DevBuf<uint64_t> d_fen; DevBuf<unsigned long long> d_stats;
     d_m.alloc(n_m + 1); d_dp.alloc(n_m + 1); d_prev.alloc(n_m + 1); d_path.alloc(n_m + 1); d_chain.alloc(nt); d_pstart.alloc(nt); d_fen.alloc(fen_off[nt]);
+    d_score.alloc(nt); d_drop.alloc(nt);
     d_stats.alloc(ST_COUNT); d_stats.zero(s); d_fen.zero(s);
     hipLaunchKernelGGL(align_join_kernel<true>, dim3(nt), dim3(256), 0, s, d_tasks.p, d_slot.p, ix.seq.p, ix.off.p, ix.total, ix.keys_in.p, ix.keys_sorted.p,
                        ix.vals_sorted.p, static_cast<uint32_t*>(nullptr), d_mo.p, d_m.p);
@@ -614,45 +656,15 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     d_fen.release(); d_dp.release(); d_prev.release();
     st.chain_ms += now_ms() - t0; t0 = now_ms();
 
-    DevBuf<uint32_t> d_level, d_cap;
-    d_level.alloc(nt); d_cap.alloc(nt);
-    Levels lv;
-    for (uint32_t l = 0; l < kLevels; l++) lv.l[l] = Lim{std::min(kLevelDim[l], top.dim), std::min(kLevelCells[l], top.cells)};
-    hipLaunchKernelGGL(align_plan_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, d_tasks.p, nt, ix.off.p, d_tm.p, d_m.p, d_path.p, d_pstart.p, max_gap, top, lv,
-                       d_level.p, d_cap.p);
-    LCTY_HIP(hipGetLastError());
-    std::vector<uint32_t> level(nt), ccap(nt);
-    d_level.download(level.data(), nt, s); d_cap.download(ccap.data(), nt, s);
-    LCTY_HIP(hipStreamSynchronize(s));
-    st.bytes_d2h += 8ull * nt;
-    std::vector<uint64_t> cig_off(nt + 1, 0);
-    for (uint32_t t = 0; t < nt; t++) cig_off[t + 1] = cig_off[t] + ccap[t];
-    DevBuf<uint64_t> d_cig_off; DevBuf<uint32_t> d_cig, d_words, d_drop, d_list; DevBuf<int32_t> d_score; DevBuf<uint8_t> d_scratch;
-    d_cig_off.alloc(nt + 1); d_cig.alloc(cig_off[nt] + 1); d_words.alloc(nt); d_drop.alloc(nt); d_score.alloc(nt); d_list.alloc(nt);
-    d_cig_off.upload(cig_off.data(), nt + 1, s);
-    st.bytes_h2d += 8ull * (nt + 1);
-    std::vector<uint32_t> list;
-    for (uint32_t l = 0; l < kLevels; l++) {
-        list.clear();
-        for (uint32_t t = 0; t < nt; t++) if (level[t] == l) list.push_back(t);
-        if (list.empty()) continue;
-        const Lim mine = lv.l[l];
-        const uint32_t lanes = static_cast<uint32_t>(std::min<size_t>(list.size(), kLevelLanes[l]));
-        d_scratch.ensure(lanes * lane_bytes(mine));
-        d_list.upload(list.data(), list.size(), s);
-        st.bytes_h2d += 4ull * list.size();
-        hipLaunchKernelGGL(align_fill_kernel, dim3((lanes + 63) / 64), dim3(64), 0, s, d_list.p, static_cast<uint32_t>(list.size()), lanes, d_tasks.p, ix.seq.p,
-                           ix.off.p, d_tm.p, d_m.p, d_path.p, d_pstart.p, max_gap, top, mine, d_scratch.p, d_cig_off.p, d_cig.p, d_score.p, d_words.p, d_drop.p,
-                           d_stats.p);
-        LCTY_HIP(hipGetLastError());
-        LCTY_HIP(hipStreamSynchronize(s));                                    // `list` is filled again
-        st.n_level[l] += list.size();
-    }
-    st.fill_ms += now_ms() - t0; t0 = now_ms();
+    StageC ws;                                                                // fresh per batch: exact sizes
+    const BackboneSrc src{d_tasks.p, d_tm.p, d_m.p, d_path.p, d_pstart.p, ix.off.p, pr.max_gap, d_score.p, d_drop.p};
+    const std::array<uint64_t, kLevels> n_level = stage_c(ctx, src, nt, ix.seq.p, pr, ws, d_stats.p, st, st.fill_ms, st.fill_ms);
+    for (uint32_t l = 0; l < kLevels; l++) st.n_level[l] += n_level[l];
+    t0 = now_ms();
 
     DevBuf<PairRes> d_res; DevBuf<uint64_t> d_out_off; DevBuf<uint32_t> d_out;
     d_res.alloc(np);
-    hipLaunchKernelGGL(align_select_kernel, dim3((np + 63) / 64), dim3(64), 0, s, np, nk, d_score.p, d_words.p, d_cig_off.p, d_cig.p, d_res.p);
+    hipLaunchKernelGGL(align_select_kernel, dim3((np + 63) / 64), dim3(64), 0, s, np, nk, d_score.p, ws.words.p, ws.off.p, ws.cig.p, d_res.p);
     LCTY_HIP(hipGetLastError());
     std::vector<PairRes> res(np);
     std::vector<unsigned long long> hs(ST_COUNT);
@@ -668,7 +680,7 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     d_out_off.alloc(np + 1);
     if (!store) d_out.alloc(out_off[np] + 1);
     d_out_off.upload(dst_off.data(), np + 1, s);
-    hipLaunchKernelGGL(align_gather_kernel, dim3(np), dim3(64), 0, s, nk, d_res.p, d_cig_off.p, d_cig.p, d_out_off.p, store ? store->buf.p : d_out.p);
+    hipLaunchKernelGGL(align_gather_kernel, dim3(np), dim3(64), 0, s, nk, d_res.p, ws.off.p, ws.cig.p, d_out_off.p, store ? store->buf.p : d_out.p);
     LCTY_HIP(hipGetLastError());
     std::vector<uint32_t> words(store ? 1 : out_off[np] + 1);
     if (!store) d_out.download(words.data(), out_off[np], s);
@@ -698,7 +710,6 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     return 0;
 }
 
-struct Prepared { std::vector<uint32_t> ks; Lim top; uint32_t max_gap; bool never; };
 Prepared validate(lcty_ctx* ctx, const lcty_align_params* p) {                // Params::validate, align.rs:67-89
     if (!(p->div_k >= 1 && p->div_k <= 31)) fail(LCTY_ERR_INVALID_INPUT, "k-mer size (%u) must be between 1 and 31", p->div_k);
     if (!(p->div_w >= 1 && p->div_w <= 63)) fail(LCTY_ERR_INVALID_INPUT, "Minimizer window (%u) must be between 1 and 63", p->div_w);
@@ -717,6 +728,7 @@ Prepared validate(lcty_ctx* ctx, const lcty_align_params* p) {                //
     r.max_gap = p->max_gap;
     const int64_t cells = ctx->knob("align_dp_cells", kLevelCells[kLevels - 1]);
     r.top = Lim{kLevelDim[kLevels - 1], static_cast<uint32_t>(std::min<int64_t>(std::max<int64_t>(cells, 1), kLevelCells[kLevels - 1]))};
+    for (uint32_t l = 0; l < kLevels; l++) r.lv.l[l] = Lim{std::min(kLevelDim[l], r.top.dim), std::min(kLevelCells[l], r.top.cells)};
     return r;
 }
 
@@ -810,9 +822,14 @@ Batching batching(lcty_ctx* ctx, uint32_t n_seqs, const uint64_t* seq_off, const
     return Batching{budget, per_batch};
 }
 
-// po[y]: the result of taken pair y (its CIGAR is words[coff[which[y]], ...))
-void write_out(lcty_align_out* out, uint64_t n_pairs, const Selection& sel, const std::vector<PairOut>& po, const std::vector<uint64_t>& coff,
-               const std::vector<uint32_t>& words) {
+// po[y]: the result of taken pair y; words_of(y): its CIGAR, as (first word, number of words)
+template <class W>
+void write_out(lcty_align_out* out, uint64_t n_pairs, const Selection& sel, const std::vector<PairOut>& po, W words_of) {
+    std::vector<uint64_t> coff(n_pairs + 1, 0);
+    for (uint64_t y = 0; y < sel.which.size(); y++) coff[sel.which[y] + 1] = words_of(y).second;
+    for (uint64_t x = 0; x < n_pairs; x++) coff[x + 1] += coff[x];
+    std::vector<uint32_t> words(coff[n_pairs]);
+    for (uint64_t y = 0; y < sel.which.size(); y++) { const auto w = words_of(y); std::copy(w.first, w.first + w.second, words.begin() + coff[sel.which[y]]); }
     std::vector<uint32_t> nm(n_pairs, 0), al(n_pairs, 0), ne(n_pairs, 0), bk(n_pairs, 0); std::vector<int32_t> sc(n_pairs, 0);
     for (uint64_t y = 0; y < sel.which.size(); y++) {
         const uint64_t x = sel.which[y];
@@ -825,6 +842,16 @@ void write_out(lcty_align_out* out, uint64_t n_pairs, const Selection& sel, cons
     out->um = to_malloc(sel.um.data(), n_pairs); out->md = to_malloc(sel.md.data(), n_pairs);
     out->cigar_off = to_malloc(coff.data(), n_pairs + 1); out->cigar = to_malloc(words.data(), words.size());
 }
+
+// the pairs [0, n) of refs / qrys in batches of bt.per_batch; a batch whose matches do not fit comes back as its prefix that does
+void run_batches(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, const uint32_t* refs, const uint32_t* qrys, uint64_t n, const Prepared& pr, const Batching& bt,
+                 PairOut* out, lcty_align_stats& st, Store* store = nullptr, const uint64_t* pair_ix = nullptr) {
+    for (uint64_t at = 0; at < n;) {
+        uint64_t m = std::min<uint64_t>(bt.per_batch, n - at);
+        for (uint64_t fit; (fit = run_batch(ctx, ix, seq_off, refs, qrys, at, at + m, pr, bt.budget, out, st, nullptr, store, pair_ix)) != 0;) m = fit;
+        at += m;
+    }
+}
 }  // namespace
 
 // the device side of lcty_align_haplotypes_transitive (lcty_align_transitive.hip decides the rounds; lcty_align_internal.hpp)
@@ -835,8 +862,8 @@ struct Session::Impl {
     Selection sel; Index ix; Batching bt{0, 1}; Store store; std::vector<PairOut> res;      // res: per INPUT pair
     // grow-only workspaces of the transitive rounds: a call has a round per row of the triangle, and nothing is allocated per round
     // once the widest row has been seen
-    DevBuf<uint8_t> scratch, d_short; DevBuf<TrTaskDev> d_tasks; DevBuf<uint32_t> d_level, d_cap, d_list, d_words[2], d_cig[2];
-    DevBuf<uint64_t> d_off[2], d_dst; DevBuf<PairRes> d_res; DevBuf<unsigned long long> d_stats;
+    StageC ws[2];                                                              // of the walk and of optimize; one scratch serves both
+    DevBuf<uint8_t> d_short; DevBuf<TrTaskDev> d_tasks; DevBuf<uint64_t> d_dst; DevBuf<PairRes> d_res; DevBuf<unsigned long long> d_stats;
     lcty_align_stats st{}; lcty_align_tr_stats tr{};
     double t_all = 0;
 };
@@ -848,6 +875,7 @@ Session::Session(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint
         im->t_all = now_ms();
         select_pairs(ctx, n_seqs, seqs, seq_off, n_pairs, ref_id, query_id, against, params, im->st, im->sel);
         im->res.assign(n_pairs, PairOut{0, kNoK, 0, 0, {}});
+        im->ws[0].slack = im->ws[1].slack = true;
         im->store.off.assign(n_pairs, 0); im->store.len.assign(n_pairs, 0);
     } catch (...) { delete im; throw; }
 }
@@ -868,13 +896,7 @@ void Session::backbone(const uint64_t* pairs, uint64_t n) {
     std::vector<uint32_t> refs(n), qrys(n);
     for (uint64_t y = 0; y < n; y++) { refs[y] = im->ref_id[pairs[y]]; qrys[y] = im->query_id[pairs[y]]; }
     std::vector<PairOut> po(n);
-    const Prepared& pr = im->sel.pr;
-    for (uint64_t at = 0; at < n;) {
-        uint64_t m = std::min<uint64_t>(im->bt.per_batch, n - at);
-        for (uint64_t fit; (fit = run_batch(im->ctx, im->ix, im->seq_off, refs.data(), qrys.data(), at, at + m, pr.max_gap, pr.top, im->bt.budget, po.data(), im->st,
-                                            nullptr, &im->store, pairs)) != 0;) m = fit;
-        at += m;
-    }
+    run_batches(im->ctx, im->ix, im->seq_off, refs.data(), qrys.data(), n, im->sel.pr, im->bt, po.data(), im->st, &im->store, pairs);
     for (uint64_t y = 0; y < n; y++) im->res[pairs[y]] = po[y];
 }
 
@@ -886,64 +908,30 @@ void Session::transitive(const TrTask* tasks, uint64_t n, uint32_t anchor_size) 
     const Prepared& pr = im->sel.pr;
     Store& store = im->store;
     const uint32_t nt = static_cast<uint32_t>(n);
-    double t0 = now_ms();
     std::vector<TrTaskDev> h(nt);
     for (uint32_t t = 0; t < nt; t++) {
         const TrTask& k = tasks[t];
         h[t] = TrTaskDev{store.off[k.ij], store.off[k.jk], store.len[k.ij], store.len[k.jk], im->ref_id[k.pair], im->query_id[k.pair],
                          (k.inv_ij ? 1u : 0u) | (k.inv_jk ? 2u : 0u), 0};
     }
-    Levels lv;
-    for (uint32_t l = 0; l < kLevels; l++) lv.l[l] = Lim{std::min(kLevelDim[l], pr.top.dim), std::min(kLevelCells[l], pr.top.cells)};
-    DevBuf<TrTaskDev>& d_tasks = im->d_tasks; DevBuf<uint8_t>& d_short = im->d_short; DevBuf<uint32_t>& d_level = im->d_level; DevBuf<uint32_t>& d_cap = im->d_cap;
-    DevBuf<uint32_t>& d_list = im->d_list; DevBuf<uint32_t>* d_words = im->d_words; DevBuf<uint32_t>* d_cig = im->d_cig; DevBuf<uint64_t>* d_off = im->d_off;
-    DevBuf<unsigned long long>& d_stats = im->d_stats;
-    d_tasks.ensure_slack(nt); d_short.ensure_slack(nt); d_level.ensure_slack(nt); d_cap.ensure_slack(nt); d_list.ensure_slack(nt); d_stats.ensure(ST_COUNT);
+    DevBuf<TrTaskDev>& d_tasks = im->d_tasks; DevBuf<uint8_t>& d_short = im->d_short; DevBuf<unsigned long long>& d_stats = im->d_stats;
+    StageC& walk = im->ws[0]; StageC& opt = im->ws[1];
+    d_tasks.ensure_slack(nt); d_short.ensure_slack(nt); d_stats.ensure(ST_COUNT);
     d_tasks.upload(h.data(), nt, s); d_stats.zero(s);
     LCTY_HIP(hipStreamSynchronize(s));
     im->st.bytes_h2d += sizeof(TrTaskDev) * nt;
-    t0 = now_ms();                                                            // (the upload is not planning)
-    std::vector<uint32_t> level(nt), ccap(nt), list;
-    std::vector<uint64_t> cig_off(nt + 1);
-    const dim3 grid((nt + 63) / 64), block(64);
-    // a pass: plan, reserve the slices by the bounds, fill level by level
-    auto pass = [&](int ps) {
-        const uint64_t* so = ps ? d_off[0].p : nullptr; const uint32_t* sc = ps ? d_cig[0].p : nullptr; const uint32_t* sw = ps ? d_words[0].p : nullptr;
-        if (ps == 0) hipLaunchKernelGGL(tr_plan_kernel<0>, grid, block, 0, s, d_tasks.p, nt, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, lv, so, sc, sw, d_short.p, d_level.p, d_cap.p);
-        else hipLaunchKernelGGL(tr_plan_kernel<1>, grid, block, 0, s, d_tasks.p, nt, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, lv, so, sc, sw, d_short.p, d_level.p, d_cap.p);
-        LCTY_HIP(hipGetLastError());
-        d_level.download(level.data(), nt, s); d_cap.download(ccap.data(), nt, s);
-        LCTY_HIP(hipStreamSynchronize(s));
-        im->st.bytes_d2h += 8ull * nt;
-        cig_off[0] = 0;
-        for (uint32_t t = 0; t < nt; t++) cig_off[t + 1] = cig_off[t] + ccap[t];
-        // the CIGARs of a pass: per-round temporaries sized by the bounds, beside the store (not part of its budget)
-        d_off[ps].ensure_slack(nt + 1); d_cig[ps].ensure_slack(cig_off[nt] + 1); d_words[ps].ensure_slack(nt);
-        d_off[ps].upload(cig_off.data(), nt + 1, s);
-        im->st.bytes_h2d += 8ull * (nt + 1);
-        im->tr.plan_ms += now_ms() - t0; t0 = now_ms();
-        for (uint32_t l = 0; l < kLevels; l++) {
-            list.clear();
-            for (uint32_t t = 0; t < nt; t++) if (level[t] == l) list.push_back(t);
-            if (list.empty()) continue;
-            const Lim mine = lv.l[l];
-            const uint32_t lanes = static_cast<uint32_t>(std::min<size_t>(list.size(), kLevelLanes[l]));
-            im->scratch.ensure(lanes * lane_bytes(mine));
-            d_list.upload(list.data(), list.size(), s);
-            im->st.bytes_h2d += 4ull * list.size();
-            const dim3 g((lanes + 63) / 64);
-            if (ps == 0) hipLaunchKernelGGL(tr_fill_kernel<0>, g, block, 0, s, d_list.p, static_cast<uint32_t>(list.size()), lanes, d_tasks.p, im->ix.seq.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, mine, im->scratch.p, so, sc, sw, d_short.p, d_off[0].p, d_cig[0].p, d_words[0].p, d_stats.p);
-            else hipLaunchKernelGGL(tr_fill_kernel<1>, g, block, 0, s, d_list.p, static_cast<uint32_t>(list.size()), lanes, d_tasks.p, im->ix.seq.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, pr.top, mine, im->scratch.p, so, sc, sw, d_short.p, d_off[1].p, d_cig[1].p, d_words[1].p, d_stats.p);
-            LCTY_HIP(hipGetLastError());
-            LCTY_HIP(hipStreamSynchronize(s));                                    // `list` is filled again
-        }
-        (ps ? im->tr.optimize_ms : im->tr.tr_fill_ms) += now_ms() - t0; t0 = now_ms();
-    };
-    pass(0);
-    pass(1);
+    // two passes of stage C (the upload is not planning). The CIGARs of a pass are per-round temporaries sized by the bounds, beside the
+    // store (not part of its budget); optimize reads what the walk left.
+    stage_c(ctx, TrSrc<0>{d_tasks.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, nullptr, nullptr, nullptr, d_short.p}, nt, im->ix.seq.p, pr, walk, d_stats.p,
+            im->st, im->tr.plan_ms, im->tr.tr_fill_ms);
+    std::swap(walk.scratch, opt.scratch);                                     // the lanes' scratch goes along and comes back
+    stage_c(ctx, TrSrc<1>{d_tasks.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, walk.off.p, walk.cig.p, walk.words.p, d_short.p}, nt, im->ix.seq.p, pr, opt, d_stats.p,
+            im->st, im->tr.plan_ms, im->tr.optimize_ms);
+    std::swap(walk.scratch, opt.scratch);
+    const double t0 = now_ms();
     DevBuf<PairRes>& d_res = im->d_res; DevBuf<uint64_t>& d_dst = im->d_dst;
     d_res.ensure_slack(nt); d_dst.ensure_slack(nt);
-    hipLaunchKernelGGL(tr_count_kernel, grid, block, 0, s, nt, d_off[1].p, d_cig[1].p, d_words[1].p, d_res.p);
+    hipLaunchKernelGGL(tr_count_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, nt, opt.off.p, opt.cig.p, opt.words.p, d_res.p);
     LCTY_HIP(hipGetLastError());
     std::vector<PairRes> res(nt); std::vector<unsigned long long> hs(ST_COUNT); std::vector<uint8_t> shortcut(nt);
     d_res.download(res.data(), nt, s); d_stats.download(hs.data(), ST_COUNT, s); d_short.download(shortcut.data(), nt, s);
@@ -955,7 +943,7 @@ void Session::transitive(const TrTask* tasks, uint64_t n, uint32_t anchor_size) 
     for (uint32_t t = 0; t < nt; t++) { dst[t] = store.used + total; total += res[t].n_words; }
     store.reserve(total);
     d_dst.upload(dst.data(), nt, s);
-    hipLaunchKernelGGL(tr_gather_kernel, dim3(nt), block, 0, s, d_res.p, d_off[1].p, d_cig[1].p, d_dst.p, store.buf.p);
+    hipLaunchKernelGGL(align_gather_kernel, dim3(nt), dim3(64), 0, s, 1u, d_res.p, opt.off.p, opt.cig.p, d_dst.p, store.buf.p);
     LCTY_HIP(hipGetLastError());
     LCTY_HIP(hipStreamSynchronize(s));
     im->st.bytes_h2d += 8ull * nt;
@@ -982,16 +970,10 @@ void Session::finish(uint64_t n_rounds, lcty_align_out* out, lcty_align_stats* s
     store.buf.download(arena.data(), store.used, s);                           // the one download of the CIGARs
     LCTY_HIP(hipStreamSynchronize(s));
     im->st.bytes_d2h += 4ull * store.used;
-    std::vector<uint64_t> coff(n_pairs + 1, 0);
-    for (uint64_t x = 0; x < n_pairs; x++) coff[x + 1] = coff[x] + (im->sel.aligned[x] ? store.len[x] : 0);
-    std::vector<uint32_t> words(coff[n_pairs]);
-    std::vector<PairOut> po(im->sel.which.size());
-    for (uint64_t y = 0; y < im->sel.which.size(); y++) {
-        const uint64_t x = im->sel.which[y];
-        po[y] = im->res[x];
-        std::copy(arena.begin() + store.off[x], arena.begin() + store.off[x] + store.len[x], words.begin() + coff[x]);
-    }
-    write_out(out, n_pairs, im->sel, po, coff, words);
+    const std::vector<uint64_t>& which = im->sel.which;
+    std::vector<PairOut> po(which.size());
+    for (uint64_t y = 0; y < which.size(); y++) po[y] = im->res[which[y]];
+    write_out(out, n_pairs, im->sel, po, [&](uint64_t y) { return std::make_pair(arena.data() + store.off[which[y]], static_cast<size_t>(store.len[which[y]])); });
     im->st.select_ms += now_ms() - t0;
     im->st.n_aligned = im->sel.which.size(); im->st.n_skipped = n_pairs - im->sel.which.size();
     im->st.total_ms = now_ms() - im->t_all;
@@ -1048,19 +1030,9 @@ int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seq
         if (!refs.empty()) {
             Index ix;
             build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
-            const Batching bt = batching(ctx, n_seqs, seq_off, pr);
-            for (uint64_t at = 0; at < refs.size();) {
-                uint64_t n = std::min<uint64_t>(bt.per_batch, refs.size() - at);
-                for (uint64_t fit; (fit = run_batch(ctx, ix, seq_off, refs.data(), qrys.data(), at, at + n, pr.max_gap, pr.top, bt.budget, po.data(), st, nullptr)) != 0;) n = fit;
-                at += n;
-            }
+            run_batches(ctx, ix, seq_off, refs.data(), qrys.data(), refs.size(), pr, batching(ctx, n_seqs, seq_off, pr), po.data(), st);
         }
-        std::vector<uint64_t> coff(n_pairs + 1, 0);
-        for (uint64_t y = 0; y < which.size(); y++) coff[which[y] + 1] = po[y].cigar.size();
-        for (uint64_t x = 0; x < n_pairs; x++) coff[x + 1] += coff[x];
-        std::vector<uint32_t> words(coff[n_pairs]);
-        for (uint64_t y = 0; y < which.size(); y++) std::copy(po[y].cigar.begin(), po[y].cigar.end(), words.begin() + coff[which[y]]);
-        write_out(out, n_pairs, sel, po, coff, words);
+        write_out(out, n_pairs, sel, po, [&](uint64_t y) { return std::make_pair(po[y].cigar.data(), po[y].cigar.size()); });
         st.n_aligned = which.size(); st.n_skipped = n_pairs - which.size();
         st.total_ms = now_ms() - t_all;
         if (stats) *stats = st;
@@ -1084,7 +1056,7 @@ int32_t lcty_align_backbone(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs,
         Index ix;
         build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
         PairOut po; Capture cap;
-        run_batch(ctx, ix, seq_off, &ref, &query, 0, 1, pr.max_gap, pr.top, ~0ull, &po, st, &cap);
+        run_batch(ctx, ix, seq_off, &ref, &query, 0, 1, pr, ~0ull, &po, st, &cap);
         out->n_matches = cap.matches.size();
         out->matches = reinterpret_cast<uint32_t*>(to_malloc(cap.matches.data(), cap.matches.size()));
         out->chain_score = cap.chain;

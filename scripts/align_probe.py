@@ -1,6 +1,6 @@
 """Developer measurement: the pairwise haplotype alignments (lcty_align.hip) on synthetic haplotypes.
    python3 scripts/align_probe.py ALLELES BASE_LEN [-D 0.01] [-k 25,51,101] [-g 10000] [--repeats 2] [--no-host] [--host-pairs N] [--batch-pairs N]
-                                  [--tr-div 0.01 [--tr-anchor 101]]
+                                  [--tr-div 0.01 [--tr-anchor 101]] [--lib path]
 One JSON line: per call of lcty_align_haplotypes over all pairs (the first call carries module loading and the first allocations) the
 per-stage milliseconds of lcty_align_stats (wall time per stage with the stream drained at its end: divergences, k-mer index, matches,
 chains, gap fill, best k + download), the counts of matches, chain points, stretches by route and DP cells, and as the comparison point
@@ -96,8 +96,11 @@ def main():
     ap.add_argument("--batch-pairs", type=int, default=0)
     ap.add_argument("--tr-div", type=float, default=None, help="the transitive route (lcty_align_haplotypes_transitive) with this divergence")
     ap.add_argument("--tr-anchor", type=int, default=101)
+    ap.add_argument("--lib", default=None, help="a library built by hand, such as the commit before a change, for a side-by-side run")
     a = ap.parse_args()
-    from locityper_amd import api, synth
+    from locityper_amd import _lib, api, synth
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     ks = [int(x) for x in a.backbone_ks.split(",")]
     t0 = time.perf_counter()
     L = synth.SynthLocus(a.alleles, 16, base_len=a.base_len)

@@ -36,7 +36,7 @@ def same(a, b):
     return all(np.array_equal(a[k], b[k]) for k in KEYS if k in a and k in b)
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + [c.name for c in TC.level_cases()])
 def test_every_pair_equals_the_transliteration(gpu_ctx, name):
     c, want = TC.by_name(name), TC.expected(name)
     res, st = device(gpu_ctx, name)

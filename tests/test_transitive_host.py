@@ -16,6 +16,7 @@ from tests import transitive_cases as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [c.name for c in TC.cases()]
+LEVEL_NAMES = [c.name for c in TC.level_cases()]
 
 
 def trace_routes(name, phases):
@@ -83,6 +84,17 @@ def test_round_boundaries():
     assert e["route"][x] == 3 and e["via"][x] == 3
 
 
+@pytest.mark.parametrize("name,level", [("level1", 1), ("level2", 2)])
+def test_level_cases_walk_at_their_level(name, level):
+    """an exact stretch of the walk at the scratch level the family is named for (every family of cases() stays at level 0), on 21 pairs
+    of which 6 go the backbone route and 15 the transitive one"""
+    from tests.test_align_host import _level
+    c, e = TC.by_name(name), TC.expected(name)
+    assert len(c.seqs) == 7 and len(c.pairs) == 21 and e["route"] == [1] * 6 + [2] * 15
+    levels = [_level(n, m) for p, r, n, m in e["events"]["trace"] if p == "walk" and r == "exact"]
+    assert levels and max(levels) == level and levels.count(level) >= 1
+
+
 # ---- the transliteration is sound -------------------------------------------------------------------------------------------------------
 def check_items(items, score, ref, qry):
     ref, qry = R.norm(ref), R.norm(qry)
@@ -101,7 +113,7 @@ def check_items(items, score, ref, qry):
     assert score == R.calculate_score(items)
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + LEVEL_NAMES)
 def test_pyref_cigars_are_alignments(name):
     c, e = TC.by_name(name), TC.expected(name)
     for x, (r, q) in enumerate(c.pairs):

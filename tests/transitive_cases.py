@@ -103,8 +103,30 @@ def cases():
     return out
 
 
+def _dense(rng, length, start, end, tail):
+    """7 haplotypes, h from (h - 1) // 2: SNPs every 60 bases of [start + 7 h, end), so no '=' run of the anchor (101) lies in the
+    region and the walk sees it as one stretch; behind it one indel of 2 + h bases at tail + 11 h"""
+    fam = [rand_seq(rng, length)]
+    for h in range(1, 7):
+        prev = fam[(h - 1) // 2]
+        edits = [snp(prev, p, rng) for p in range(start + 7 * h, end, 60)]
+        at = tail + 11 * h
+        fam.append(apply_edits(prev, edits + [ins(prev, at, 2 + h, rng) if h % 2 else dele(prev, at, 2 + h)]))
+    return fam
+
+
+@functools.lru_cache(maxsize=None)
+def level_cases():
+    """walk stretches above scratch level 0 (every family of cases() stays below 256 bases a side): 360 to 390 bases a side, level 1,
+    and 2 100 to 2 140 a side, level 2. Of the 21 pairs the 6 of row 0 go the backbone route, the other 15 the transitive one, a row
+    (5, 4, ... tasks) per round. A list of its own: test_transitive_host.py bounds the sizes of cases()."""
+    rng = np.random.default_rng(505)
+    kw = dict(ks=(25, 51), tr_div=0.08, anchor=101, max_gap=10000)
+    return [TrCase("level1", _dense(rng, 1200, 300, 700, 900), **kw), TrCase("level2", _dense(rng, 2700, 200, 2350, 2500), **kw)]
+
+
 def by_name(name):
-    return next(c for c in cases() if c.name == name)
+    return next(c for c in cases() + level_cases() if c.name == name)
 
 
 @functools.lru_cache(maxsize=None)
