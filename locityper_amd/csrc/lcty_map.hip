@@ -7,8 +7,8 @@
 //
 //   index    every k-mer (k <= 31, canonical form) of every basis allele -> its (basis allele, position, "forward is canonical"),
 //            an open-addressing table of runs built on the host once per locus (basis sets are small: --basis).
-//   seeds    the k-mers of a read end at every `stride`-th position plus the last one; k-mers with a base that is not ACGT are skipped,
-//            and so are k-mers with more than max_occ places in the index (microsatellites; at most 64 places vote in any case).
+//   seeds    as in lcty_map_internal.hpp (every `stride`-th k-mer plus the last one; k-mers over a base that is not ACGT or with more
+//            than max_occ places in the index skipped: microsatellites); here at most 64 of them, and at most 64 places vote per seed.
 //   votes    every (seed, index entry) pair votes for (basis allele, strand, diagonal). An (allele, strand) whose best diagonal has
 //            >= half the votes of the read end's best one (strobealign -S 0.5) contributes its diagonals with >= min_votes votes and
 //            >= half the votes of its best as candidates (a read end in a tandem repeat has as many votes one period off), the
@@ -24,15 +24,14 @@
 //            its score is higher. Order of preference on ties, fixed here and in the restatement: continue before starting
 //            afresh, M before deletion before insertion as predecessor, open before extend, the first best end cell by (read
 //            position, diagonal).
-//   records  the best candidate of a read end is its primary record, the others with a score >= min_score are secondary
-//            records (the samtools filter above); a read end without a candidate is an unmapped record. Record order, flags,
-//            =/X/S CIGARs and SEQ orientation (reverse-complemented when the primary is on the reverse strand) are those of
+//   records  as in lcty_map_internal.hpp: primary, secondary records from min_score (the samtools filter above), unmapped record;
+//            = / X / S CIGARs (or the gap kernel's words between the clips). Record order, flags and SEQ orientation are those of
 //            the BAM the reference reads (model/locs.rs:1116-1150), so the chunk goes straight into lcty_reads_append.
 //
 // Three kernels: map_seed_kernel (one wavefront per read end; lane = seed, then lane = hit: bitonic sort of <= 1 024 vote keys in
 // LDS, then lane = candidate, <= 64) leaves the candidates that stayed and lists the clipped ones; map_gap_kernel aligns the
 // listed ones with gaps, one per lane; map_emit_kernel<WRITE> (one wavefront per read end, lane = candidate) runs twice: sizes,
-// then records, with a host prefix sum in between.
+// then records, with the host's prefix sums in between (map_emit_two_pass, lcty_map_internal.hpp).
 #include <algorithm>
 
 #include "lcty_map_internal.hpp"
@@ -56,31 +55,10 @@ struct MapCand {
     int32_t g_score; uint32_t g_pos; uint16_t g_lead, g_trail; uint32_t ops_at; uint16_t g_inner, pad;
 };
 
-struct MapView {
-    const MapSlot* table; uint64_t mask;
-    const uint64_t* entries;               // basis index << 33 | position << 1 | forward-is-canonical
-    const uint16_t* basis;                 // basis index -> allele
-    uint32_t n_basis, k, stride, min_votes, max_occ, band;
-    int32_t match, mismatch, end_bonus, min_score, gap_open, gap_extend;
-    // between the kernels
-    MapCand* cands; uint32_t slots;        // [read end][slots]: the candidates that stayed, in (allele, strand) order
-    uint32_t* n_have;                      // per read end
+struct MapView : MapViewCommon {
+    MapCand* cands;                        // [read end][slots]: the candidates that stayed, in (allele, strand) order
     uint32_t* work; uint32_t n_work;       // slots of the candidates to be aligned with gaps
-    uint32_t* counters;                    // [0] entries of `work`, [1] CIGAR words asked for in `ops`
-    uint32_t* ops; uint32_t ops_cap;       // CIGAR words of the alignments with gaps (without the soft clips)
     uint32_t* scratch; uint32_t max_len;   // direction nibbles: [workgroup of kernel 2][max_len * MAP_DIR_WORDS][64]
-    const uint8_t* seqs; const uint64_t* seq_off; const uint32_t* allele_len;
-    // reads
-    uint64_t n_mates;
-    const uint32_t* mate_len; const uint64_t* mate_off; const uint32_t* bases2; const uint32_t* nmask;
-    int paired;
-    // pass 1
-    uint32_t* n_recs; uint32_t* n_cigar;
-    // pass 2
-    const uint64_t* rec_at; const uint64_t* cig_at;      // per read end: first record, first CIGAR word
-    const uint64_t* pair_cig;                            // per pair: first CIGAR word (records carry offsets relative to it)
-    lcty_aln_rec* recs; uint32_t* cigar;
-    uint32_t* out_bases2; uint32_t* out_nmask;
 };
 
 // ---- kernel 1: seeds -> votes -> candidates -> extension without gaps; the candidates that stay, in (allele, strand) order
@@ -96,43 +74,18 @@ __device__ void map_seed_one(const MapView& V, const uint64_t m, uint64_t* keys,
     // ---- seeds and votes
     uint32_t n_hits = 0;
     if (L >= k) {
-        const uint32_t span = L - k, n0 = span / V.stride + 1, n_seeds = n0 + (span % V.stride ? 1u : 0u);
-        uint32_t start = 0, count = 0, pr = 0;
-        bool read_fwd = false;
-        if (lane < n_seeds) {
-            pr = lane < n0 ? lane * V.stride : span;
-            uint64_t fw = 0, rv = 0;
-            bool bad = false;
-            for (uint32_t j = 0; j < k; j++) {
-                const uint32_t e = base_at(V.bases2, off, pr + j);
-                bad |= n_at(V.nmask, off, pr + j);
-                fw = (fw << 2) | e;
-                rv = (rv >> 2) | (static_cast<uint64_t>(3u - e) << (2 * k - 2));
-            }
-            if (!bad) {
-                read_fwd = fw <= rv;
-                const uint64_t canon = read_fwd ? fw : rv;
-                uint64_t h = fast_hash64(canon) & V.mask;
-                for (;;) {
-                    const MapSlot s = V.table[h];
-                    if (s.key == MAP_FREE) break;
-                    if (s.key == canon) { start = s.start; count = s.count > V.max_occ ? 0u : min(s.count, MAP_PER_SEED); break; }      // a repetitive k-mer says nothing about the place
-                    h = (h + 1) & V.mask;
-                }
-            }
-        }
+        MapSeed sd{};                                                           // lane = seed (run_map: at most 64); as in lcty_map_internal.hpp
+        if (lane < map_n_seeds(L, k, V.stride)) sd = map_seed_at(V, off, L, lane, MAP_PER_SEED);
+        const uint32_t count = sd.count;
         // places of the lanes' votes in the list (seed order); what does not fit is dropped
         uint32_t incl = count;
         for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (lane >= static_cast<uint32_t>(o)) incl += up; }
         const uint32_t at = incl - count;
         n_hits = min(static_cast<uint32_t>(__shfl(incl, 63)), MAP_MAX_HITS);
         for (uint32_t j = 0; j < count && at + j < MAP_MAX_HITS; j++) {
-            const uint64_t e = V.entries[start + j];
-            const uint32_t b = static_cast<uint32_t>(e >> 33), pa = static_cast<uint32_t>(e >> 1);
-            const bool allele_fwd = e & 1ull;
-            const uint32_t strand = read_fwd == allele_fwd ? 0u : 1u;
-            const int64_t diag = strand ? static_cast<int64_t>(pa) - static_cast<int64_t>(L - k - pr) : static_cast<int64_t>(pa) - static_cast<int64_t>(pr);
-            keys[at + j] = (static_cast<uint64_t>(b * 2 + strand) << 32) | static_cast<uint32_t>(diag + 0x80000000ll);
+            const MapPlace pl = map_place(V.entries[sd.start + j], sd.read_fwd);
+            const int64_t diag = static_cast<int64_t>(pl.pos) - static_cast<int64_t>(pl.strand ? L - k - sd.pr : sd.pr);
+            keys[at + j] = (static_cast<uint64_t>(pl.b * 2 + pl.strand) << 32) | static_cast<uint32_t>(diag + 0x80000000ll);
         }
     }
     // ---- sort the votes (bitonic over the next power of two, padded with the largest key)
@@ -230,7 +183,7 @@ __device__ void map_seed_one(const MapView& V, const uint64_t m, uint64_t* keys,
     if (lane == 0) V.n_have[m] = static_cast<uint32_t>(__popcll(hm));
     if (wm) {
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&V.counters[0], static_cast<uint32_t>(__popcll(wm)));
+        if (lane == 0) base = atomicAdd(&V.counters[MAPC_WORK], static_cast<uint32_t>(__popcll(wm)));
         base = static_cast<uint32_t>(__shfl(static_cast<int>(base), 0));
         if (need) V.work[base + static_cast<uint32_t>(__popcll(wm & below))] = slot;
     }
@@ -349,8 +302,8 @@ __global__ __launch_bounds__(64) void map_gap_kernel(const MapView V) {
             if (cur_len) { if (pass) V.ops[at + n_words - 1 - n] = (cur_len << 4) | cur_op; n++; }
             if (!pass) {
                 n_words = n; lead = i; k_first = k;
-                at = atomicAdd(&V.counters[1], n_words);
-                if (at + n_words > V.ops_cap || at + n_words < at) break;      // the host repeats the kernel with room for counters[1] words
+                at = atomicAdd(&V.counters[MAPC_OPS], n_words);
+                if (at + n_words > V.ops_cap || at + n_words < at) break;      // the host repeats the kernel with room for counters[MAPC_OPS] words
             } else {
                 c.state = 2; c.g_score = best_total; c.g_pos = static_cast<uint32_t>(diag + static_cast<int64_t>(lead) + (k_first - B));
                 c.g_lead = static_cast<uint16_t>(lead); c.g_trail = static_cast<uint16_t>(L - 1 - end_i); c.g_inner = static_cast<uint16_t>(n_words); c.ops_at = at;
@@ -360,113 +313,59 @@ __global__ __launch_bounds__(64) void map_gap_kernel(const MapView V) {
     }
 }
 
-// ---- kernel 3: the records of a read end from its candidates; sizes (WRITE = false), then the records themselves
-template <bool WRITE>
-__device__ void map_emit_one(const MapView& V, const uint64_t m) {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t L = V.mate_len[m];
-    if (L == 0) {
-        if (!WRITE && lane == 0) { V.n_recs[m] = 0; V.n_cigar[m] = 0; }
-        return;
-    }
-    const uint64_t off = V.mate_off[m];
-    const bool have = lane < V.n_have[m];
-    MapCand c{};
-    if (have) c = V.cands[static_cast<uint32_t>(m) * V.slots + lane];
-    const bool gapped = have && c.state == 2;
-    const int32_t score = gapped ? c.g_score : c.score;
-    const uint32_t strand = c.g & 1u, allele = have ? V.basis[c.g >> 1] : 0u;
-    const int64_t diag = static_cast<int64_t>(c.diag) - 0x80000000ll;
-    const uint8_t* ref = V.seqs + V.seq_off[allele];
-    const uint32_t s_best = c.s, e_best = c.e;
+// ---- kernel 3: the records of a read end from its candidates, as in lcty_map_internal.hpp (map_emit_read_end). What this route
+// supplies: lane = candidate (at most 64: one batch), which counts and writes its own = / X / S runs, or copies what kernel 2 left
+struct ShortRoute {
+    using View = MapView; using Cand = MapCand;
+    const MapView& V; const uint64_t m; const uint32_t L; const uint64_t off;
+    __device__ ShortRoute(const MapView& V_, uint64_t m_, uint32_t L_, uint64_t off_) : V(V_), m(m_), L(L_), off(off_) {}
+    __device__ MapCand load(uint32_t slot) const { return V.cands[static_cast<uint32_t>(m) * V.slots + slot]; }
+    __device__ static int32_t score(const MapCand& c) { return c.state == 2 ? c.g_score : c.score; }
+    __device__ static uint32_t group(const MapCand& c) { return c.g; }
+    __device__ static uint32_t pos(const MapCand& c) { return c.state == 2 ? c.g_pos : static_cast<uint32_t>(static_cast<int64_t>(c.diag) - 0x80000000ll + c.s); }
     // a position of the read end in alignment orientation: equal to the allele's base there?
-    auto equal_at = [&](uint32_t i) -> bool {
-        const uint32_t src = strand ? L - 1 - i : i;
+    __device__ bool equal_at(const MapCand& c, const uint8_t* ref, uint32_t i) const {
+        const uint32_t strand = c.g & 1u, src = strand ? L - 1 - i : i;
         if (n_at(V.nmask, off, src)) return false;
         const uint32_t e = strand ? 3u - base_at(V.bases2, off, src) : base_at(V.bases2, off, src);
-        return base_enc(ref[diag + i]) == e;
-    };
-    // ---- the primary record: best score, the smallest (allele, strand) on ties (the lanes are in that order)
-    int32_t top = have ? score : INT32_MIN;
-    for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o));
-    const unsigned long long tops = __ballot(have && score == top);
-    const uint32_t lp = tops ? static_cast<uint32_t>(__ffsll(static_cast<long long>(tops))) - 1u : 0xFFFFFFFFu;
-    const bool keep = have && (lane == lp || score >= V.min_score);
-    // CIGAR words of a kept candidate: [S] runs of = / X [S], or what kernel 2 left
-    uint32_t n_ops = 0;
-    if (keep && gapped) n_ops = c.g_inner + (c.g_lead > 0) + (c.g_trail > 0);
-    else if (keep) {
-        n_ops = (s_best > 0) + (e_best < L);
+        return base_enc(ref[static_cast<int64_t>(c.diag) - 0x80000000ll + i]) == e;
+    }
+    __device__ const uint8_t* ref_of(const MapCand& c) const { return V.seqs + V.seq_off[V.basis[c.g >> 1]]; }
+    // [S] runs of = / X [S], or what kernel 2 left
+    __device__ uint32_t n_words(const MapCand& c) const {
+        if (c.state == 2) return c.g_inner + (c.g_lead > 0) + (c.g_trail > 0);
+        const uint8_t* ref = ref_of(c);
+        uint32_t n = (c.s > 0) + (c.e < L);
         bool prev = false;
-        for (uint32_t i = s_best; i < e_best; i++) { const bool eq = equal_at(i); if (i == s_best || eq != prev) n_ops++; prev = eq; }
+        for (uint32_t i = c.s; i < c.e; i++) { const bool eq = equal_at(c, ref, i); if (i == c.s || eq != prev) n++; prev = eq; }
+        return n;
     }
-    const unsigned long long kept = __ballot(keep);
-    const uint32_t n_kept = static_cast<uint32_t>(__popcll(kept));
-    uint32_t ops_incl = keep && lane != lp ? n_ops : 0u;                         // the others follow the primary in (allele, strand) order
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(ops_incl, o); if (lane >= static_cast<uint32_t>(o)) ops_incl += up; }
-    const uint32_t ops_primary = lp != 0xFFFFFFFFu ? static_cast<uint32_t>(__shfl(static_cast<int>(n_ops), static_cast<int>(lp))) : 0u;
-    const uint32_t ops_total = ops_primary + static_cast<uint32_t>(__shfl(static_cast<int>(ops_incl), 63));
-    if (!WRITE) {
-        if (lane == 0) { V.n_recs[m] = n_kept ? n_kept : 1u; V.n_cigar[m] = ops_total; }       // no candidate: one unmapped record
-        uint32_t widest = n_ops;
-        for (int o = 32; o > 0; o >>= 1) widest = max(widest, static_cast<uint32_t>(__shfl_xor(static_cast<int>(widest), o)));
-        if (lane == 0 && widest > V.counters[2]) atomicMax(&V.counters[2], widest);
-        return;
-    }
-    const uint32_t mate2 = V.paired && (m & 1u) ? LCTY_FLAG_MATE2 : 0u;
-    const uint64_t rec0 = V.rec_at[m], cig0 = V.cig_at[m], rel0 = cig0 - V.pair_cig[m >> 1];
-    const bool primary_reverse = lp != 0xFFFFFFFFu && __shfl(static_cast<int>(strand), static_cast<int>(lp)) != 0;
-    if (n_kept == 0) {
-        if (lane == 0) V.recs[rec0] = lcty_aln_rec{0u, 0u, static_cast<uint16_t>(LCTY_FLAG_UNMAPPED | mate2), 0u, static_cast<uint32_t>(rel0)};
-    } else if (keep) {
-        const uint32_t rank = lane == lp ? 0u : 1u + static_cast<uint32_t>(__popcll(kept & ((1ull << lane) - 1ull) & ~(1ull << lp)));
-        const uint32_t cig_rel = lane == lp ? 0u : ops_primary + ops_incl - n_ops;
-        uint32_t* cg = V.cigar + cig0 + cig_rel;
+    __device__ void write_words(bool keep, const MapCand& c, uint32_t, uint32_t* cg0, uint32_t rel) const {
+        if (!keep) return;
+        uint32_t* cg = cg0 + rel;
         uint32_t w = 0;
-        if (gapped) {
+        if (c.state == 2) {
             if (c.g_lead > 0) cg[w++] = (static_cast<uint32_t>(c.g_lead) << 4) | 4u;
             for (uint32_t j = 0; j < c.g_inner; j++) cg[w++] = V.ops[c.ops_at + j];
             if (c.g_trail > 0) cg[w++] = (static_cast<uint32_t>(c.g_trail) << 4) | 4u;
-        } else {
-            if (s_best > 0) cg[w++] = (s_best << 4) | 4u;                        // S
-            bool prev = false; uint32_t len = 0;
-            for (uint32_t i = s_best; i < e_best; i++) {
-                const bool eq = equal_at(i);
-                if (i > s_best && eq != prev) { cg[w++] = (len << 4) | (prev ? 7u : 8u); len = 0; }      // = / X
-                prev = eq; len++;
-            }
-            cg[w++] = (len << 4) | (prev ? 7u : 8u);
-            if (e_best < L) cg[w++] = ((L - e_best) << 4) | 4u;
+            return;
         }
-        const uint16_t flags = static_cast<uint16_t>((strand ? LCTY_FLAG_REVERSE : 0u) | (lane == lp ? 0u : LCTY_FLAG_SECONDARY) | mate2);
-        V.recs[rec0 + rank] = lcty_aln_rec{gapped ? c.g_pos : static_cast<uint32_t>(diag + s_best), static_cast<uint16_t>(allele), flags, n_ops,
-                                           static_cast<uint32_t>(rel0 + cig_rel)};
-    }
-    // SEQ as the BAM has it: reverse-complemented when the primary record is on the reverse strand. The read end owns whole
-    // 32-base words of the output (offsets are multiples of 32); lane = output word of 16 bases.
-    const uint32_t words = (L + 15) / 16;
-    for (uint32_t wi = lane; wi < words; wi += 64) {
-        uint32_t out = 0;
-        for (uint32_t j = 0; j < 16 && wi * 16 + j < L; j++) {
-            const uint32_t i = wi * 16 + j, src = primary_reverse ? L - 1 - i : i;
-            const uint32_t e = base_at(V.bases2, off, src);
-            out |= (primary_reverse ? 3u - e : e) << (2 * j);
+        const uint8_t* ref = ref_of(c);
+        if (c.s > 0) cg[w++] = (static_cast<uint32_t>(c.s) << 4) | 4u;            // S
+        bool prev = false; uint32_t len = 0;
+        for (uint32_t i = c.s; i < c.e; i++) {
+            const bool eq = equal_at(c, ref, i);
+            if (i > c.s && eq != prev) { cg[w++] = (len << 4) | (prev ? 7u : 8u); len = 0; }      // = / X
+            prev = eq; len++;
         }
-        V.out_bases2[(off >> 4) + wi] = out;
+        cg[w++] = (len << 4) | (prev ? 7u : 8u);
+        if (c.e < L) cg[w++] = ((L - c.e) << 4) | 4u;
     }
-    for (uint32_t wi = lane; wi < (L + 31) / 32; wi += 64) {
-        uint32_t out = 0;
-        for (uint32_t j = 0; j < 32 && wi * 32 + j < L; j++) {
-            const uint32_t i = wi * 32 + j, src = primary_reverse ? L - 1 - i : i;
-            out |= static_cast<uint32_t>(n_at(V.nmask, off, src)) << j;
-        }
-        V.out_nmask[(off >> 5) + wi] = out;
-    }
-}
+};
 
 template <bool WRITE>
 __global__ __launch_bounds__(64) void map_emit_kernel(const MapView V) {
-    for (uint64_t m = blockIdx.x; m < V.n_mates; m += gridDim.x) map_emit_one<WRITE>(V, m);
+    for (uint64_t m = blockIdx.x; m < V.n_mates; m += gridDim.x) map_emit_read_end<WRITE, ShortRoute>(V, m);
 }
 
 }  // namespace
@@ -554,7 +453,7 @@ void run_map(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_par
         if (ix->n_basis > MAP_MAX_BASIS) fail(LCTY_ERR_UNSUPPORTED, "up to %u basis alleles on the short route (the index has %u)", MAP_MAX_BASIS, ix->n_basis);
         for (uint64_t m = 0; m < n_mates; m++) {
             if (chunk->mate_len[m] > MAP_MAX_LEN) fail(LCTY_ERR_UNSUPPORTED, "read ends of up to %u bases on the short route (this one: %u)", MAP_MAX_LEN, chunk->mate_len[m]);
-            if (chunk->mate_len[m] >= params->k && (chunk->mate_len[m] - params->k) / params->stride + 2 > 64)
+            if (map_seed_bound(chunk->mate_len[m], params->k, params->stride) > 64)
                 fail(LCTY_ERR_UNSUPPORTED, "more than 64 seeds per read end: raise the stride");
         }
     }
@@ -568,78 +467,35 @@ void run_map(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_par
         return;
     }
     MapView V{};
-    V.table = ix->table.p; V.mask = ix->mask; V.entries = ix->entries.p; V.basis = ix->basis.p; V.n_basis = ix->n_basis;
-    V.k = params->k; V.stride = params->stride; V.min_votes = std::max<uint32_t>(params->min_votes, 1);
-    V.max_occ = params->max_occ ? params->max_occ : 4 * ix->n_basis;
-    V.match = params->match; V.mismatch = params->mismatch; V.end_bonus = params->end_bonus; V.min_score = params->min_score;
-    V.band = params->band; V.gap_open = params->gap_open; V.gap_extend = params->gap_extend;
+    fill_map_view(V, locus, *ix, params, X, n_mates, std::min<uint32_t>(64, 2 * ix->n_basis), sizeof(MapCand));
     const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
     const uint32_t n_wg = static_cast<uint32_t>(std::min<uint64_t>(n_mates, 16ull * cus));
-    V.seqs = locus->d_seqs.p; V.seq_off = locus->d_seq_off.p; V.allele_len = locus->d_allele_len.p;
-    V.n_mates = n_mates; V.mate_len = X.d_len.p; V.mate_off = X.d_off.p; V.bases2 = X.d_b2.p; V.nmask = X.d_nm.p;
-    V.paired = locus->bg.is_paired;
-    V.n_recs = X.d_nrec.p; V.n_cigar = X.d_ncig.p;
     // kernel 1: the candidates that stay, and the list of those to be aligned with gaps
-    V.slots = std::min<uint32_t>(64, 2 * ix->n_basis);
-    if (n_mates * V.slots > 0xFFFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "chunks of up to %llu read pairs with this basis", (unsigned long long)(0xFFFFFFFFull / V.slots / 2));
-    X.d_cands.ensure_slack(n_mates * V.slots * sizeof(MapCand)); X.d_nhave.ensure_slack(n_mates); X.d_work.ensure_slack(n_mates * V.slots);
-    X.d_counters.ensure_slack(4); X.d_counters.zero(s);
-    V.cands = reinterpret_cast<MapCand*>(X.d_cands.p); V.n_have = X.d_nhave.p; V.work = X.d_work.p; V.counters = X.d_counters.p;
+    X.d_work.ensure_slack(n_mates * V.slots);
+    V.cands = reinterpret_cast<MapCand*>(X.d_cands.p); V.work = X.d_work.p;
     ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_seed_kernel, dim3(n_wg), dim3(64), 0, s, V); }, s);
     LCTY_HIP(hipGetLastError());
-    uint32_t counters[4] = {0, 0, 0, 0};
-    X.d_counters.download(counters, 4, s);
+    uint32_t counters[MAPC_HOST] = {};
+    X.d_counters.download(counters, MAPC_HOST, s);
     LCTY_HIP(hipStreamSynchronize(s));
     // kernel 2: the band alignments, repeated with more room if their CIGAR words did not fit
-    V.n_work = counters[0];
+    V.n_work = counters[MAPC_WORK];
     if (V.n_work) {
         const uint32_t n_wg2 = static_cast<uint32_t>(std::min<uint64_t>((V.n_work + 63) / 64, 4ull * cus));
         V.max_len = max_len;
         ix->scratch.ensure(static_cast<size_t>(n_wg2) * max_len * MAP_DIR_WORDS * 64);
         V.scratch = ix->scratch.p;
-        uint64_t cap = 6ull * V.n_work + 1024;
-        for (;;) {
-            if (cap > 0xFFFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "CIGAR words of the alignments with gaps: map the chunk in parts");
+        map_fill_arena(s, X, counters, 6ull * V.n_work + 1024, MAPC_OPS, {MAPC_OPS}, "CIGAR words of the alignments with gaps: map the chunk in parts", [&](uint64_t cap) {
             X.d_ops.ensure_slack(cap);
             V.ops = X.d_ops.p; V.ops_cap = static_cast<uint32_t>(cap);
             ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_gap_kernel, dim3(n_wg2), dim3(64), 0, s, V); }, s);
-            LCTY_HIP(hipGetLastError());
-            X.d_counters.download(counters, 4, s);
-            LCTY_HIP(hipStreamSynchronize(s));
-            if (counters[1] <= cap) break;
-            cap = static_cast<uint64_t>(counters[1]) + 1024;
-            const uint32_t zero = 0;
-            X.d_counters.upload(&zero, 1, s, 1);
-        }
+        });
     }
-    // kernel 3, sizes
-    ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_emit_kernel<false>, dim3(n_wg), dim3(64), 0, s, V); }, s);
-    LCTY_HIP(hipGetLastError());
-    X.d_counters.download(counters, 4, s);
-    X.nrec.resize(n_mates); X.ncig.resize(n_mates);
-    X.d_nrec.download(X.nrec.data(), n_mates, s); X.d_ncig.download(X.ncig.data(), n_mates, s);
-    LCTY_HIP(hipStreamSynchronize(s));
-    X.max_rec_cigar = counters[2];
-    std::vector<uint64_t> rec_at(n_mates), cig_at(n_mates), pair_cig(n);
-    uint64_t r = 0, c = 0;
-    for (uint64_t p = 0; p < n; p++) {
-        pair_cig[p] = c;
-        for (uint32_t e = 0; e < 2; e++) { rec_at[2 * p + e] = r; cig_at[2 * p + e] = c; r += X.nrec[2 * p + e]; c += X.ncig[2 * p + e]; }
-        aln_off[p + 1] = r; cigar_off[p + 1] = c;
-    }
-    X.n_recs = r; X.n_cigar = c;
-    if (sizes_only) return;
-    X.d_rec_at.ensure_slack(n_mates); X.d_rec_at.upload(rec_at.data(), n_mates, s);
-    X.d_cig_at.ensure_slack(n_mates); X.d_cig_at.upload(cig_at.data(), n_mates, s);
-    X.d_pair_cig.ensure_slack(n); X.d_pair_cig.upload(pair_cig.data(), n, s);
-    X.d_recs.ensure_slack(std::max<uint64_t>(r, 1)); X.d_cigar.ensure_slack(std::max<uint64_t>(c, 1));
-    X.d_ob2.ensure_slack(std::max<uint64_t>(nb / 16, 1)); X.d_onm.ensure_slack(std::max<uint64_t>(nb / 32, 1));
-    X.d_ob2.zero(s); X.d_onm.zero(s);
-    V.rec_at = X.d_rec_at.p; V.cig_at = X.d_cig_at.p; V.pair_cig = X.d_pair_cig.p; V.recs = X.d_recs.p; V.cigar = X.d_cigar.p;
-    V.out_bases2 = X.d_ob2.p; V.out_nmask = X.d_onm.p;
-    ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_emit_kernel<true>, dim3(n_wg), dim3(64), 0, s, V); }, s);
-    LCTY_HIP(hipGetLastError());
-    LCTY_HIP(hipStreamSynchronize(s));                                          // rec_at & co. are host vectors of this frame
+    // kernel 3: sizes, then records
+    map_emit_two_pass(ctx, chunk, V, X, aln_off, cigar_off, sizes_only, [&](const MapView& view, bool write, uint32_t wgs) {
+        if (write) hipLaunchKernelGGL(map_emit_kernel<true>, dim3(wgs), dim3(64), 0, s, view);
+        else hipLaunchKernelGGL(map_emit_kernel<false>, dim3(wgs), dim3(64), 0, s, view);
+    });
 }
 
 }  // namespace

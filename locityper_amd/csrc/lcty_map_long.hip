@@ -8,8 +8,7 @@
 // orientation (strand 0: the allele itself; strand 1: its reverse complement). Everything up to the record is done in (q, t); the
 // record (position, CIGAR order) is turned into BAM orientation when it is written.
 //
-//   seeds    as on the short route (every `stride`-th k-mer plus the last one, k-mers with a base that is not ACGT or with more than
-//            max_occ places in the index skipped), any number of them.
+//   seeds    as in lcty_map_internal.hpp, any number of them and every place of each.
 //   anchors  every (seed, place) pair is an anchor (q, t) of its group g = basis allele x 2 + strand; a group keeps the first
 //            2 x seeds anchors, in seed order (within a seed: in index order).
 //   chains   an anchor starts a chain (value k) or follows one of the last `chain_back` anchors j of its group: 0 < dq, dt <=
@@ -25,8 +24,7 @@
 //            diagonals apart; H = best of (base step, deletion, insertion), gaps open from H at gap_open and go on at gap_extend a
 //            base. Preference on ties: the base step before the deletion before the insertion, to go on before starting afresh,
 //            to open before to extend, the first best end node by (i, diagonal).
-//   records  as on the short route: best score first (the smallest (allele, strand) on ties), the others with score >= min_score
-//            as secondary records, no candidate = an unmapped record; = / X / I / D / S CIGARs, SEQ in BAM orientation.
+//   records  as in lcty_map_internal.hpp; = / X / I / D / S CIGARs copied from the arena.
 //
 // Three kernels. map_long_chain_kernel, one wavefront per read end: lane = seed (index lookups), then lane = place of a seed (the
 // chains of all groups grow side by side in a scratch of the workgroup; two places of one group in a batch take turns in index
@@ -38,8 +36,8 @@
 // direction bits per node stay in LDS (short segments) or go to a scratch of the wavefront, the walk back reads them in blocks through
 // LDS, takes runs of equal base steps at once, and leaves the CIGAR runs right to left in scratch; they are copied into the arena at
 // the end. Two kinds of piece never reach the rows: equal lengths with so few mismatches that the diagonal provably beats any gap, and
-// sides that differ by one gap only. map_long_emit_kernel<WRITE>, one wavefront per read end, runs twice: sizes, then records (host
-// prefix sums in between).
+// sides that differ by one gap only. map_long_emit_kernel<WRITE>, one wavefront per read end, runs twice: sizes, then records (the
+// host's prefix sums in between: map_emit_two_pass, lcty_map_internal.hpp).
 #include <algorithm>
 
 #include "lcty_map_internal.hpp"
@@ -54,31 +52,17 @@ constexpr uint32_t LONG_MAX_GROUPS = 2 * MAP_LONG_MAX_BASIS;
 struct LongCand { int32_t score; uint32_t pos, ops_at, n_words, g, pad; };
 struct LongWork { uint32_t mate, g_slot, chain_at, chain_n; };         // g | slot of the read end's candidates << 16
 
-struct LongView {
-    const MapSlot* table; uint64_t mask;
-    const uint64_t* entries; const uint16_t* basis;
-    uint32_t n_basis, k, stride, min_votes, max_occ, band, chain_gap, chain_skew, chain_back;
-    int32_t match, mismatch, end_bonus, min_score, gap_open, gap_extend;
-    const uint8_t* seqs; const uint64_t* seq_off; const uint32_t* allele_len;
-    uint64_t n_mates;
-    const uint32_t* mate_len; const uint64_t* mate_off; const uint32_t* bases2; const uint32_t* nmask;
-    int paired;
+struct LongView : MapViewCommon {
+    uint32_t chain_gap, chain_skew, chain_back;
     // kernel 1: scratch of a workgroup, and what it leaves
     uint4* anchors; uint32_t cap_g;               // [workgroup][group][cap_g]: q, t, value, back | anchors in the chain << 8
     uint2* chain; uint32_t chain_cap;             // the chains to be aligned: (q, t), last anchor first
     LongWork* work; uint32_t n_work;
-    uint32_t* n_have;
-    uint32_t* counters;                           // [0] work items, [1] CIGAR words asked for in `ops`, [2] the widest record, [3] chain entries asked for, [4] next work item of kernel 2
     // kernel 2: scratch of a wavefront, and what it leaves
     uint8_t* dirs; uint64_t dirs_bytes;           // [wavefront][dirs_bytes]
     uint32_t* opsbuf; uint32_t ops_wave;          // [wavefront][ops_wave]
     uint32_t wmax, tb_bytes;
-    LongCand* cands; uint32_t slots;
-    uint32_t* ops; uint32_t ops_cap;
-    // kernel 3
-    uint32_t* n_recs; uint32_t* n_cigar;
-    const uint64_t* rec_at; const uint64_t* cig_at; const uint64_t* pair_cig;
-    lcty_aln_rec* recs; uint32_t* cigar; uint32_t* out_bases2; uint32_t* out_nmask;
+    LongCand* cands;
 };
 
 // ---- kernel 1: seeds -> anchors -> chains -> the chains to be aligned
@@ -99,34 +83,12 @@ __global__ __launch_bounds__(64) void map_long_chain_kernel(const LongView V) {
         const uint64_t off = V.mate_off[m];
         for (uint32_t g = lane; g < n_groups; g += 64) { g_n[g] = 0; g_bf[g] = LNEG; g_bi[g] = 0; owner[g] = 64; }
         __syncthreads();
-        uint32_t n_seeds = 0, n0 = 0, span = 0;
-        if (L >= k) { span = L - k; n0 = span / V.stride + 1; n_seeds = n0 + (span % V.stride ? 1u : 0u); }
+        const uint32_t n_seeds = map_n_seeds(L, k, V.stride);                 // as in lcty_map_internal.hpp, any number of them
         const uint32_t cap = min(2 * n_seeds, V.cap_g);
         for (uint32_t s0 = 0; s0 < n_seeds; s0 += 64) {
-            const uint32_t sidx = s0 + lane;
-            uint32_t start = 0, count = 0, pr = 0; bool read_fwd = false;
-            if (sidx < n_seeds) {
-                pr = sidx < n0 ? sidx * V.stride : span;
-                uint64_t fw = 0, rv = 0; bool bad = false;
-                for (uint32_t j = 0; j < k; j++) {
-                    const uint32_t e = base_at(V.bases2, off, pr + j);
-                    bad |= n_at(V.nmask, off, pr + j);
-                    fw = (fw << 2) | e;
-                    rv = (rv >> 2) | (static_cast<uint64_t>(3u - e) << (2 * k - 2));
-                }
-                if (!bad) {
-                    read_fwd = fw <= rv;
-                    const uint64_t canon = read_fwd ? fw : rv;
-                    uint64_t h = fast_hash64(canon) & V.mask;
-                    for (;;) {
-                        const MapSlot sl = V.table[h];
-                        if (sl.key == MAP_FREE) break;
-                        if (sl.key == canon) { start = sl.start; count = sl.count > V.max_occ ? 0u : sl.count; break; }
-                        h = (h + 1) & V.mask;
-                    }
-                }
-            }
-            sd_start[lane] = start; sd_count[lane] = count; sd_pr[lane] = pr; sd_fwd[lane] = read_fwd;
+            MapSeed sd{};
+            if (s0 + lane < n_seeds) sd = map_seed_at(V, off, L, s0 + lane);
+            sd_start[lane] = sd.start; sd_count[lane] = sd.count; sd_pr[lane] = sd.pr; sd_fwd[lane] = sd.read_fwd;
             __syncthreads();
             const uint32_t in_batch = min(64u, n_seeds - s0);
             for (uint32_t si = 0; si < in_batch; si++) {
@@ -137,11 +99,9 @@ __global__ __launch_bounds__(64) void map_long_chain_kernel(const LongView V) {
                     bool pending = e0 + lane < cnt;
                     uint32_t g = 0, t = 0;
                     if (pending) {
-                        const uint64_t en = V.entries[st + e0 + lane];
-                        const uint32_t b = static_cast<uint32_t>(en >> 33), pa = static_cast<uint32_t>(en >> 1);
-                        const uint32_t strand = rfwd == ((en & 1ull) != 0) ? 0u : 1u;
-                        g = 2 * b + strand;
-                        t = strand ? V.allele_len[V.basis[b]] - k - pa : pa;
+                        const MapPlace pl = map_place(V.entries[st + e0 + lane], rfwd);
+                        g = 2 * pl.b + pl.strand;
+                        t = pl.strand ? V.allele_len[V.basis[pl.b]] - k - pl.pos : pl.pos;
                     }
                     // two places of one group take turns, in index order
                     while (__ballot(pending) != 0ull) {
@@ -214,7 +174,7 @@ __global__ __launch_bounds__(64) void map_long_chain_kernel(const LongView V) {
             const uint32_t total = static_cast<uint32_t>(__shfl(static_cast<int>(incl), 63));
             const uint32_t in_batch = min(64u, n_cand - c0);
             uint32_t cbase = 0, wbase = 0;
-            if (lane == 0) { cbase = atomicAdd(&V.counters[3], total); wbase = atomicAdd(&V.counters[0], in_batch); }
+            if (lane == 0) { cbase = atomicAdd(&V.counters[MAPC_CHAIN], total); wbase = atomicAdd(&V.counters[MAPC_WORK], in_batch); }
             cbase = static_cast<uint32_t>(__shfl(static_cast<int>(cbase), 0)); wbase = static_cast<uint32_t>(__shfl(static_cast<int>(wbase), 0));
             const uint32_t mine_at = cbase + incl - len;
             if (have && cbase + total <= V.chain_cap && cbase + total >= cbase) {
@@ -593,7 +553,7 @@ __global__ __launch_bounds__(64) void map_long_align_kernel(const LongView V) {
     for (;;) {
         // the next work item, whichever wavefront is free: the alignments of a chunk differ in length
         uint32_t w = 0;
-        if (lane == 0) w = atomicAdd(&V.counters[4], 1u);
+        if (lane == 0) w = atomicAdd(&V.counters[MAPC_CURSOR], 1u);
         w = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(w)));
         if (w >= V.n_work) break;
         const LongWork item = V.work[w];
@@ -630,7 +590,7 @@ __global__ __launch_bounds__(64) void map_long_align_kernel(const LongView V) {
         // into the arena: the runs were met right to left in (q, t), which is left to right in BAM orientation on the reverse strand
         const uint32_t nw = C.n;
         uint32_t dst = 0;
-        if (lane == 0) dst = atomicAdd(&V.counters[1], nw);
+        if (lane == 0) dst = atomicAdd(&V.counters[MAPC_OPS], nw);
         dst = static_cast<uint32_t>(__shfl(static_cast<int>(dst), 0));
         __syncthreads();
         if (dst + nw <= V.ops_cap && dst + nw >= dst)
@@ -640,97 +600,31 @@ __global__ __launch_bounds__(64) void map_long_align_kernel(const LongView V) {
     }
 }
 
-// ---- kernel 2: the records of a read end from its candidates; sizes (WRITE = false), then the records themselves
-template <bool WRITE>
-__device__ void map_long_emit_one(const LongView& V, const uint64_t m) {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t L = V.mate_len[m];
-    if (L == 0) {
-        if (!WRITE && lane == 0) { V.n_recs[m] = 0; V.n_cigar[m] = 0; }
-        return;
-    }
-    const uint64_t off = V.mate_off[m];
-    const uint32_t nh = V.n_have[m];
-    const LongCand* cands = V.cands + m * V.slots;
-    // the primary record: best score, the smallest (allele, strand) on ties (the slots are in that order)
-    int32_t top = INT32_MIN;
-    for (uint32_t s = lane; s < nh; s += 64) top = max(top, cands[s].score);
-    for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o));
-    uint32_t prim = 0xFFFFFFFFu;
-    for (uint32_t s = lane; s < nh; s += 64) if (cands[s].score == top) { prim = s; break; }
-    for (int o = 32; o > 0; o >>= 1) prim = min(prim, static_cast<uint32_t>(__shfl_xor(static_cast<int>(prim), o)));
-    const uint32_t ops_primary = nh ? cands[prim].n_words : 0u;
-    const uint32_t mate2 = V.paired && (m & 1u) ? LCTY_FLAG_MATE2 : 0u;
-    uint64_t rec0 = 0, cig0 = 0, rel0 = 0;
-    if (WRITE) { rec0 = V.rec_at[m]; cig0 = V.cig_at[m]; rel0 = cig0 - V.pair_cig[m >> 1]; }
-    uint32_t n_kept = 0, words = ops_primary, widest = 0;
-    for (uint32_t s0 = 0; s0 < nh; s0 += 64) {
-        const uint32_t s = s0 + lane;
-        LongCand c{};
-        if (s < nh) c = cands[s];
-        const bool keep = s < nh && (s == prim || c.score >= V.min_score);
-        const bool other = keep && s != prim;
-        const unsigned long long om = __ballot(other);
-        uint32_t incl = other ? c.n_words : 0u;
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (lane >= static_cast<uint32_t>(o)) incl += up; }
-        if (keep) widest = max(widest, c.n_words);
-        if (WRITE) {
-            const uint32_t rank = s == prim ? 0u : 1u + n_kept + static_cast<uint32_t>(__popcll(om & ((1ull << lane) - 1ull)));
-            const uint32_t cig_rel = s == prim ? 0u : words + incl - c.n_words;
-            if (keep) {
-                const uint32_t strand = c.g & 1u;
-                const uint16_t flags = static_cast<uint16_t>((strand ? LCTY_FLAG_REVERSE : 0u) | (s == prim ? 0u : LCTY_FLAG_SECONDARY) | mate2);
-                V.recs[rec0 + rank] = lcty_aln_rec{c.pos, V.basis[c.g >> 1], flags, c.n_words, static_cast<uint32_t>(rel0 + cig_rel)};
-            }
-            // the CIGAR words of the kept candidates of this batch, one candidate at a time over all lanes
-            unsigned long long km = __ballot(keep);
-            while (km) {
-                const int src_lane = __ffsll(static_cast<long long>(km)) - 1;
-                km &= km - 1;
-                const uint32_t from = static_cast<uint32_t>(__shfl(static_cast<int>(c.ops_at), src_lane));
-                const uint32_t nw = static_cast<uint32_t>(__shfl(static_cast<int>(c.n_words), src_lane));
-                const uint32_t to = static_cast<uint32_t>(__shfl(static_cast<int>(cig_rel), src_lane));
-                for (uint32_t w = lane; w < nw; w += 64) V.cigar[cig0 + to + w] = V.ops[from + w];
-            }
+// ---- kernel 3: the records of a read end from its candidates, as in lcty_map_internal.hpp (map_emit_read_end). What this route
+// supplies: any number of candidates, whose words all lanes copy from the arena, one candidate at a time
+struct LongRoute {
+    using View = LongView; using Cand = LongCand;
+    const LongView& V; const LongCand* cands;
+    __device__ LongRoute(const LongView& V_, uint64_t m, uint32_t, uint64_t) : V(V_), cands(V_.cands + m * V_.slots) {}
+    __device__ LongCand load(uint32_t slot) const { return cands[slot]; }
+    __device__ static int32_t score(const LongCand& c) { return c.score; }
+    __device__ static uint32_t group(const LongCand& c) { return c.g; }
+    __device__ static uint32_t pos(const LongCand& c) { return c.pos; }
+    __device__ static uint32_t n_words(const LongCand& c) { return c.n_words; }
+    __device__ void write_words(bool keep, const LongCand& c, uint32_t n, uint32_t* cg0, uint32_t rel) const {
+        for (unsigned long long km = __ballot(keep); km; km &= km - 1) {
+            const int src_lane = __ffsll(static_cast<long long>(km)) - 1;
+            const uint32_t from = static_cast<uint32_t>(__shfl(static_cast<int>(c.ops_at), src_lane));
+            const uint32_t nw = static_cast<uint32_t>(__shfl(static_cast<int>(n), src_lane));
+            const uint32_t to = static_cast<uint32_t>(__shfl(static_cast<int>(rel), src_lane));
+            for (uint32_t w = threadIdx.x; w < nw; w += 64) cg0[to + w] = V.ops[from + w];
         }
-        n_kept += static_cast<uint32_t>(__popcll(om));
-        words += static_cast<uint32_t>(__shfl(static_cast<int>(incl), 63));
     }
-    if (!WRITE) {
-        for (int o = 32; o > 0; o >>= 1) widest = max(widest, static_cast<uint32_t>(__shfl_xor(static_cast<int>(widest), o)));
-        if (lane == 0) {
-            V.n_recs[m] = nh ? n_kept + 1 : 1u;                                  // no candidate: one unmapped record
-            V.n_cigar[m] = nh ? words : 0u;
-            if (widest > V.counters[2]) atomicMax(&V.counters[2], widest);
-        }
-        return;
-    }
-    if (nh == 0 && lane == 0) V.recs[rec0] = lcty_aln_rec{0u, 0u, static_cast<uint16_t>(LCTY_FLAG_UNMAPPED | mate2), 0u, static_cast<uint32_t>(rel0)};
-    // SEQ as the BAM has it: reverse-complemented when the primary record is on the reverse strand
-    const bool primary_reverse = nh && (cands[prim].g & 1u);
-    const uint32_t words16 = (L + 15) / 16;
-    for (uint32_t wi = lane; wi < words16; wi += 64) {
-        uint32_t out = 0;
-        for (uint32_t j = 0; j < 16 && wi * 16 + j < L; j++) {
-            const uint32_t i = wi * 16 + j, src = primary_reverse ? L - 1 - i : i;
-            const uint32_t e = base_at(V.bases2, off, src);
-            out |= (primary_reverse ? 3u - e : e) << (2 * j);
-        }
-        V.out_bases2[(off >> 4) + wi] = out;
-    }
-    for (uint32_t wi = lane; wi < (L + 31) / 32; wi += 64) {
-        uint32_t out = 0;
-        for (uint32_t j = 0; j < 32 && wi * 32 + j < L; j++) {
-            const uint32_t i = wi * 32 + j, src = primary_reverse ? L - 1 - i : i;
-            out |= static_cast<uint32_t>(n_at(V.nmask, off, src)) << j;
-        }
-        V.out_nmask[(off >> 5) + wi] = out;
-    }
-}
+};
 
 template <bool WRITE>
 __global__ __launch_bounds__(64) void map_long_emit_kernel(const LongView V) {
-    for (uint64_t m = blockIdx.x; m < V.n_mates; m += gridDim.x) map_long_emit_one<WRITE>(V, m);
+    for (uint64_t m = blockIdx.x; m < V.n_mates; m += gridDim.x) map_emit_read_end<WRITE, LongRoute>(V, m);
 }
 
 }  // namespace
@@ -752,31 +646,18 @@ void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_ma
     if (params->chain_gap == 0 || params->chain_gap > 8192) fail(LCTY_ERR_INVALID_INPUT, "chain_gap %u: 1..8192", params->chain_gap);
     if (params->chain_skew > 1024) fail(LCTY_ERR_INVALID_INPUT, "chain_skew %u: 0..1024", params->chain_skew);
     if (params->chain_skew > params->chain_gap) fail(LCTY_ERR_INVALID_INPUT, "chain_skew %u > chain_gap %u", params->chain_skew, params->chain_gap);
-    LongView V{};
-    V.table = ix.table.p; V.mask = ix.mask; V.entries = ix.entries.p; V.basis = ix.basis.p; V.n_basis = ix.n_basis;
-    V.k = params->k; V.stride = params->stride; V.min_votes = std::max<uint32_t>(params->min_votes, 1);
-    V.max_occ = params->max_occ ? params->max_occ : 4 * ix.n_basis;
-    V.band = params->band; V.chain_gap = params->chain_gap; V.chain_skew = params->chain_skew; V.chain_back = params->chain_back;
-    V.match = params->match; V.mismatch = params->mismatch; V.end_bonus = params->end_bonus; V.min_score = params->min_score;
-    V.gap_open = params->gap_open; V.gap_extend = params->gap_extend;
-    V.seqs = locus->d_seqs.p; V.seq_off = locus->d_seq_off.p; V.allele_len = locus->d_allele_len.p;
-    V.n_mates = n_mates; V.mate_len = X.d_len.p; V.mate_off = X.d_off.p; V.bases2 = X.d_b2.p; V.nmask = X.d_nm.p;
-    V.paired = locus->bg.is_paired;
-    V.n_recs = X.d_nrec.p; V.n_cigar = X.d_ncig.p;
     if (params->gap_open < params->gap_extend) fail(LCTY_ERR_UNSUPPORTED, "the long route needs gap_open >= gap_extend (%d < %d)", params->gap_open, params->gap_extend);
     const uint32_t n_groups = 2 * ix.n_basis;
     const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
     size_t free_b = 0, total_b = 0;
-    V.slots = n_groups;
-    if (n_mates * V.slots > 0xFFFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "chunks of up to %llu read pairs with this basis", (unsigned long long)(0xFFFFFFFFull / V.slots / 2));
-    X.d_cands.ensure_slack(n_mates * V.slots * sizeof(LongCand)); X.d_nhave.ensure_slack(n_mates);
-    X.d_counters.ensure_slack(8);
-    V.cands = reinterpret_cast<LongCand*>(X.d_cands.p); V.n_have = X.d_nhave.p; V.counters = X.d_counters.p;
-    uint32_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    LongView V{};
+    fill_map_view(V, locus, ix, params, X, n_mates, n_groups, sizeof(LongCand));
+    V.chain_gap = params->chain_gap; V.chain_skew = params->chain_skew; V.chain_back = params->chain_back;
+    V.cands = reinterpret_cast<LongCand*>(X.d_cands.p);
+    uint32_t counters[MAPC_HOST] = {};
     // ---- kernel 1: the chains. Scratch of a workgroup: the anchors of every group; it leaves the chains to be aligned (repeated with
     // more room if they did not fit) and a work item for each
-    const uint32_t max_seeds = max_len >= params->k ? (max_len - params->k) / params->stride + 2 : 0;
-    V.cap_g = std::max<uint32_t>(2 * max_seeds, 1);
+    V.cap_g = std::max<uint32_t>(2 * map_seed_bound(max_len, params->k, params->stride), 1);
     {
         const uint64_t per_wg = static_cast<uint64_t>(n_groups) * V.cap_g * sizeof(uint4);
         LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -788,26 +669,18 @@ void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_ma
         X.d_work.ensure_slack(n_mates * V.slots * (sizeof(LongWork) / sizeof(uint32_t)));
         V.work = reinterpret_cast<LongWork*>(X.d_work.p);
         uint64_t seeds_total = 0;
-        for (uint64_t m = 0; m < n_mates; m++)
-            if (chunk->mate_len[m] >= params->k) seeds_total += (chunk->mate_len[m] - params->k) / params->stride + 2;
+        for (uint64_t m = 0; m < n_mates; m++) seeds_total += map_seed_bound(chunk->mate_len[m], params->k, params->stride);
         // room for the chains of a chunk of noisy reads on every basis allele (every other seed an anchor), as far as the memory goes; the
         // kernel says how many entries it needed when that was not enough
         LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
-        uint64_t cap = std::min<uint64_t>(0xFFFFFFF0ull, std::min<uint64_t>(free_b / 64, seeds_total * ix.n_basis / 2) + 4096);
-        for (;;) {
-            X.d_counters.zero(s);
-            X.d_chain.ensure_slack(cap);
-            V.chain = X.d_chain.p; V.chain_cap = static_cast<uint32_t>(cap);
+        const uint64_t cap = std::min<uint64_t>(0xFFFFFFF0ull, std::min<uint64_t>(free_b / 64, seeds_total * ix.n_basis / 2) + 4096);
+        map_fill_arena(s, X, counters, cap, MAPC_CHAIN, {MAPC_WORK, MAPC_CHAIN}, "anchors of the chunk's chains: map it in parts", [&](uint64_t room) {
+            X.d_chain.ensure_slack(room);
+            V.chain = X.d_chain.p; V.chain_cap = static_cast<uint32_t>(room);
             ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_long_chain_kernel, dim3(n_wg), dim3(64), 0, s, V); }, s);
-            LCTY_HIP(hipGetLastError());
-            X.d_counters.download(counters, 4, s);
-            LCTY_HIP(hipStreamSynchronize(s));
-            if (counters[3] <= cap) break;
-            if (counters[3] >= 0xFFFFFFF0u) fail(LCTY_ERR_UNSUPPORTED, "anchors of the chunk's chains: map it in parts");
-            cap = static_cast<uint64_t>(counters[3]) + 1024;
-        }
+        });
         mark("chains done");
-        V.n_work = counters[0];
+        V.n_work = counters[MAPC_WORK];
     }
     // ---- kernel 2: the alignments. Scratch of a wavefront: the direction bytes of the largest segment, the CIGAR runs of a candidate;
     // it leaves the CIGAR words in an arena (repeated with more room if they did not fit)
@@ -830,57 +703,24 @@ void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_ma
         // room for the words of a chunk of noisy reads (a word per ~4 bases of every alignment), as far as the memory goes; the kernel
         // says how many it needed when that was not enough
         LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
-        uint64_t cap = std::min<uint64_t>(0xFFFFFFF0ull, std::min<uint64_t>(free_b / 32, static_cast<uint64_t>(V.n_work) * (nb / std::max<uint64_t>(n, 1) / 4 + 8)) + 4096);
+        const uint64_t cap = std::min<uint64_t>(0xFFFFFFF0ull, std::min<uint64_t>(free_b / 32, static_cast<uint64_t>(V.n_work) * (nb / std::max<uint64_t>(n, 1) / 4 + 8)) + 4096);
         mark("alignment scratch allocated");
         LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(map_long_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-        for (;;) {
-            const uint32_t zero = 0;
-            X.d_counters.upload(&zero, 1, s, 1); X.d_counters.upload(&zero, 1, s, 4);
-            X.d_ops.ensure_slack(cap);
-            V.ops = X.d_ops.p; V.ops_cap = static_cast<uint32_t>(cap);
+        map_fill_arena(s, X, counters, cap, MAPC_OPS, {MAPC_OPS, MAPC_CURSOR}, "CIGAR words of the chunk's alignments: map it in parts", [&](uint64_t room) {
+            X.d_ops.ensure_slack(room);
+            V.ops = X.d_ops.p; V.ops_cap = static_cast<uint32_t>(room);
             ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_long_align_kernel, dim3(n_waves), dim3(64), lds, s, V); }, s);
-            LCTY_HIP(hipGetLastError());
-            X.d_counters.download(counters, 4, s);
-            LCTY_HIP(hipStreamSynchronize(s));
-            if (counters[1] <= cap) break;
-            if (counters[1] >= 0xFFFFFFF0u) fail(LCTY_ERR_UNSUPPORTED, "CIGAR words of the chunk's alignments: map it in parts");
-            cap = static_cast<uint64_t>(counters[1]) + 1024;
-        }
+        });
         mark("alignments done");
     } else {
         X.d_ops.ensure_slack(1);
         V.ops = X.d_ops.p; V.ops_cap = 1;
     }
-    // ---- kernel 3, sizes
-    const uint32_t n_wg2 = static_cast<uint32_t>(std::min<uint64_t>(n_mates, 16ull * cus));
-    ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_long_emit_kernel<false>, dim3(n_wg2), dim3(64), 0, s, V); }, s);
-    LCTY_HIP(hipGetLastError());
-    X.d_counters.download(counters, 4, s);
-    X.nrec.resize(n_mates); X.ncig.resize(n_mates);
-    X.d_nrec.download(X.nrec.data(), n_mates, s); X.d_ncig.download(X.ncig.data(), n_mates, s);
-    LCTY_HIP(hipStreamSynchronize(s));
-    X.max_rec_cigar = counters[2];
-    mark("sizes done");
-    std::vector<uint64_t> rec_at(n_mates), cig_at(n_mates), pair_cig(n);
-    uint64_t r = 0, c = 0;
-    for (uint64_t p = 0; p < n; p++) {
-        pair_cig[p] = c;
-        for (uint32_t e = 0; e < 2; e++) { rec_at[2 * p + e] = r; cig_at[2 * p + e] = c; r += X.nrec[2 * p + e]; c += X.ncig[2 * p + e]; }
-        aln_off[p + 1] = r; cigar_off[p + 1] = c;
-    }
-    X.n_recs = r; X.n_cigar = c;
-    if (sizes_only) return;
-    X.d_rec_at.ensure_slack(n_mates); X.d_rec_at.upload(rec_at.data(), n_mates, s);
-    X.d_cig_at.ensure_slack(n_mates); X.d_cig_at.upload(cig_at.data(), n_mates, s);
-    X.d_pair_cig.ensure_slack(n); X.d_pair_cig.upload(pair_cig.data(), n, s);
-    X.d_recs.ensure_slack(std::max<uint64_t>(r, 1)); X.d_cigar.ensure_slack(std::max<uint64_t>(c, 1));
-    X.d_ob2.ensure_slack(std::max<uint64_t>(nb / 16, 1)); X.d_onm.ensure_slack(std::max<uint64_t>(nb / 32, 1));
-    X.d_ob2.zero(s); X.d_onm.zero(s);
-    V.rec_at = X.d_rec_at.p; V.cig_at = X.d_cig_at.p; V.pair_cig = X.d_pair_cig.p; V.recs = X.d_recs.p; V.cigar = X.d_cigar.p;
-    V.out_bases2 = X.d_ob2.p; V.out_nmask = X.d_onm.p;
-    ctx->timed(LCTY_K_MAP, [&] { hipLaunchKernelGGL(map_long_emit_kernel<true>, dim3(n_wg2), dim3(64), 0, s, V); }, s);
-    LCTY_HIP(hipGetLastError());
-    LCTY_HIP(hipStreamSynchronize(s));                                          // rec_at & co. are host vectors of this frame
+    // ---- kernel 3: sizes, then records
+    map_emit_two_pass(ctx, chunk, V, X, aln_off, cigar_off, sizes_only, [&](const LongView& view, bool write, uint32_t wgs) {
+        if (write) hipLaunchKernelGGL(map_long_emit_kernel<true>, dim3(wgs), dim3(64), 0, s, view);
+        else hipLaunchKernelGGL(map_long_emit_kernel<false>, dim3(wgs), dim3(64), 0, s, view);
+    });
     mark("records written");
 }
 

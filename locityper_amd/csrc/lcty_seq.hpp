@@ -116,8 +116,9 @@ __host__ __device__ __forceinline__ void minimizers_as_written(uint32_t len, uin
 #ifdef __HIPCC__
 // Canonical k-mer (src/seq/kmers.rs:192-196) of the window starting at base q of a mate whose
 // 2-bit stream starts at 64-bit word `w64` (mate offsets are multiples of 32 bases).
-// The stream is LSB-first: x = sum enc[q+t] << 2t, hence rv = ~x (masked) and fw = digit-reverse(x).
-__device__ inline uint64_t canonical_kmer_2bit(const uint64_t* w64, uint32_t q, uint32_t k) {
+// The stream is LSB-first: x = sum enc[q+t] << 2t, hence rv = ~x (masked) and fw = digit-reverse(x). *forward as in
+// canonical_kmer_ascii: fw <= rv, a palindrome counting as forward. w64[word + 1] is read only when the window reaches into it.
+__device__ inline uint64_t canonical_kmer_2bit(const uint64_t* w64, uint32_t q, uint32_t k, bool* forward = nullptr) {
     const uint32_t word = q >> 5, sh = (q & 31u) * 2u;
     uint64_t x = w64[word] >> sh;
     if (sh + 2u * k > 64u) x |= w64[word + 1] << (64u - sh);
@@ -127,6 +128,7 @@ __device__ inline uint64_t canonical_kmer_2bit(const uint64_t* w64, uint32_t q, 
     uint64_t y = __brevll(x);
     y = ((y >> 1) & 0x5555555555555555ull) | ((y & 0x5555555555555555ull) << 1);
     const uint64_t fw = y >> (64u - 2u * k);
+    if (forward) *forward = !(rv < fw);
     return rv < fw ? rv : fw;
 }
 

@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 REC = [("pos", "<u4"), ("contig", "<u2"), ("flags", "<u2"), ("n_cigar", "<u4"), ("cigar_rel", "<u4")]
 OP = "MIDNSHP=X"
+SECOND_BATCH_MIN_SCORE = 230         # 120 bases end to end (2 a base, -8 a mismatch, 10 an end): 260, 250 / 240 with one / two mismatches, 210 / 200 with five / six
 
 
 def cigar_score(words, mp):
@@ -303,3 +304,54 @@ def test_long_route_on_256_basis_alleles_equals_the_restatement(gpu_ctx):
     recs, cigar, cig_off = assert_equals_restatement(got, fq, L.seqs, L.seq_off, basis, mp, paired=False)
     mapped = [r for r in recs if not r[2] & cdefs.FLAG_UNMAPPED]
     assert len(mapped) >= 8 * 250 and len({r[1] for r in mapped}) == 256          # every allele reached, by (nearly) every read
+
+
+def second_batch_inputs():
+    """80 alleles of 1 kb, equal except for designed SNVs; 120-base read ends cut without errors from alleles 70..79 over positions
+    400..560. Allele a >= 70 has a private SNV at 455 + (a - 70): inside every read end. Every third allele (0, 3, .., 78) has four more
+    at 472, 480, 488, 496: inside every read end too."""
+    rng = np.random.default_rng(64)
+    base = rng.choice(list(b"ACGT"), size=1000).astype(np.uint8)
+    other = lambda c: ord("ACGT"[("ACGT".index(chr(c)) + 1) % 4])
+    haps = []
+    for a in range(80):
+        h = base.copy()
+        for q in ([455 + a - 70] if a >= 70 else []) + ([472, 480, 488, 496] if a % 3 == 0 else []):
+            h[q] = other(h[q])
+        haps.append(bytearray(h.tolist()))
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    cut = lambda a, at, rev=False: (bytes(haps[a][at:at + 120]).translate(comp)[::-1] if rev else bytes(haps[a][at:at + 120])).decode()
+    pairs = [{"seq1": cut(70, 400), "seq2": cut(73, 431, rev=True), "recs": []}, {"seq1": cut(76, 417, rev=True), "seq2": "", "recs": []},
+             {"seq1": cut(79, 440), "seq2": cut(71, 409), "recs": []}, {"seq1": cut(77, 424), "seq2": cut(74, 436), "recs": []}]
+    return haps, pairs
+
+
+def test_primary_in_the_second_batch_of_slots_behind_dropped_candidates(gpu_ctx):
+    """The record selection over more than 64 candidates with candidates dropped: each read end has a candidate on (nearly) every one of
+    80 basis alleles, in allele order; its primary is the allele it was cut from (70 or above: the second batch of 64 slots), the alleles
+    with one or two mismatches are kept as secondary records, every third allele (five or six mismatches, on both sides of slot 64)
+    falls below min_score. Records, CIGAR words, offsets and SEQ orientation equal the restatement's."""
+    from tests.helpers import locus_arrays, make_bg
+    haps, pairs = second_batch_inputs()
+    bg = make_bg()
+    seqs, seq_off, cflat, cnt_off, _ = locus_arrays(haps, 25)
+    loc = api.Locus(gpu_ctx, seqs, seq_off, cflat, cnt_off, 25, bg, api.resolve_params(api.default_params(), bg))
+    ch = cdefs.ReadsChunk.from_pairs(pairs)
+    mp = api.map_params(stride=7, min_score=SECOND_BATCH_MIN_SCORE, route=cdefs.MAP_ROUTE_LONG)
+    basis = list(range(80))
+    api.build_map_index(loc, basis, k=mp.k)
+    got = api.map_reads(loc, ch, mp)
+    recs, cigar, cig_off = assert_equals_restatement(got, ch, seqs, seq_off, basis, mp, paired=True)
+    # the shape this test is about, on the restatement's own output
+    at = 0
+    for m in range(2 * ch.n_pairs):
+        if int(ch.mate_len[m]) == 0:
+            continue
+        mine = []
+        while at < len(recs) and (not mine or recs[at][2] & cdefs.FLAG_SECONDARY):
+            mine.append(recs[at]); at += 1
+        assert mine[0][1] >= 64 and not mine[0][2] & (cdefs.FLAG_SECONDARY | cdefs.FLAG_UNMAPPED)
+        assert any(r[1] < 64 for r in mine[1:]) and any(r[1] >= 64 for r in mine[1:])
+        assert len(mine) < len(basis)
+        assert [r[1] for r in mine[1:]] == sorted(r[1] for r in mine[1:])
+    assert at == len(recs)
