@@ -957,8 +957,8 @@ int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, cha
 /* ---- locus database build (locityper target: the files of DB/loci/<locus>/) -----------------------------------------------------
  * process_alleles (src/command/add.rs:585-652) and what it calls, on buffers: the haplotype sequences of one locus, the reference
  * sequence of the locus and the k-mer counts `jellyfish query` returned for all of them (the caller runs Jellyfish, exactly as the
- * caller runs the mapper for aln.bam). Out of scope: pangenome-VCF reconstruction and locus expansion (panvcf.rs, add.rs:370-518),
- * ref.bed, lock and `success` files, augment. (haplotypes.paf.gz: lcty_align_haplotypes; prune: lcty_db_prune_locus, both further down.)
+ * caller runs the mapper for aln.bam). Out of scope: lock and `success` files, augment. (From a pangenome VCF — reconstruction, locus
+ * expansion, ref.bed: lcty_db_locus_from_vcf; haplotypes.paf.gz: lcty_align_haplotypes; prune: lcty_db_prune_locus, all further down.)
  * Integer work throughout: every output equals the reference's bit for bit (the f64 divergence is one IEEE division of two u32).
  *
  * lcty_db_minimizers: kmers::minimizers::<u64, _, NON_CANONICAL> + sort_unstable per sequence (src/seq/kmers.rs:265-331,
@@ -1047,6 +1047,160 @@ int32_t lcty_db_build_locus(lcty_ctx* ctx, uint32_t n_seqs, const char* names, c
                             const uint8_t* ref_seq, uint64_t ref_len, const uint16_t* counts, const uint64_t* cnt_off, uint32_t k,
                             uint32_t counter_bytes, const lcty_db_params* params, lcty_db_files* out);
 void    lcty_db_files_free(lcty_db_files* files);
+
+/* ---- a locus from a pangenome VCF (locityper target -v: expansion, reconstruction, ref.bed; lcty_panvcf.hip) --------------------------
+ * What add_locus does with a VCF before process_alleles (src/command/add.rs:733-782): the boundaries of the locus move onto a quiet,
+ * unique piece of the reference, every phased haplotype of the VCF is rebuilt over the new interval, and the sequences go to
+ * lcty_db_build_locus unchanged. Integer and byte work, and one short f64 recipe that is followed to the bit. Positions are 0-based.
+ *
+ * lcty_vcf_open / _view_get / _region / _free (host): a text VCF — plain, gzip or BGZF, told by its first bytes; no index, no BCF (a
+ *   `.bcf` path is LCTY_ERR_UNSUPPORTED). open reads the sample names of the #CHROM line and the ploidies of the FIRST record
+ *   (HaplotypeNames::new, panvcf.rs:85-91); a file without records is LCTY_ERR_INVALID_DATA as there. region returns the records htslib's
+ *   fetch(start, end) returns — same contig, pos < end, pos + len(REF) > start, in file order; INFO/END is NOT looked at, a stated
+ *   difference for symbolic alleles — as flat arrays: pos, ref_len = len(REF), the alleles verbatim (REF first; no case folding) in
+ *   allele_bytes with rec_allele[n_recs + 1] indexing allele_off[n_alleles + 1], gt[n_recs][n_haps] the allele indices of every sample's
+ *   GT one after the other (hap_off of the view; -1 for '.'), phased[n_recs][n_samples] = the separator before the sample's last allele
+ *   is '|' (a haploid call has none: 1). sample_used (NULL: all) [n_samples]: for these samples a GT whose allele count differs from the
+ *   first record's ploidy ("has ploidy ... (expected ...)", panvcf.rs:161-164) and a sample of ploidy > 1 whose last separator is '/'
+ *   ("is unphased", 167-171) are LCTY_ERR_INVALID_DATA. A contig the file does not name gives no records.
+ * lcty_panvcf_names (host): HaplotypeNames::new (panvcf.rs:65-135) on samples (n_samples 0-terminated names) and their ploidies: the
+ *   retained columns in order (shift_ix), the reference first (col_sample = LCTY_NONE_U32) unless leave_out (n_leave_out 0-terminated
+ *   names) holds ref_name; a haplotype is `sample` for ploidy 1, else `sample.<hap_ix + 1>`; leave_out matches a sample or a haplotype.
+ *   LCTY_ERR_INVALID_DATA: duplicate name, ploidy 0, ploidy > 255, no sample left ("Loaded zero haplotypes"). Called twice: col_sample =
+ *   col_hap = names = NULL sizes it (*n_cols, *names_len). *n_left_out (may be NULL): haplotypes left out.
+ * lcty_panvcf_filter (device): filter_variants' has_variation (panvcf.rs:173-181): kept[v] = some column of gt[n_recs][n_cols] (the
+ *   matrix restricted to the retained columns; a kept reference is a column of zeros) has allele >= 1.
+ * lcty_panvcf_reconstruct (device): filter_variants (149-184), reconstruct_sequences (223-321) and the has_n filter of add_locus
+ *   (add.rs:775-780) over [ref_start, ref_end) with its reference bytes ref_seq. A record is kept iff some column has allele >= 1; a
+ *   kept record with var_end <= ref_start is skipped, one with ref_end <= var_start ends the walk, one that straddles either end is
+ *   LCTY_ERR_INVALID_INPUT ("overlaps the boundary of the region"). Per column a non-reference allele is taken iff var_start >=
+ *   prev_end, else it counts in total_overlaps — or, with overlaps_allowed == 0, is LCTY_ERR_INVALID_DATA naming the first such
+ *   (record, haplotype) in record-major order ("Overlapping variants forbidden (contig:pos for name)"). A missing allele adds ref_len
+ *   to the column's unknown_nts and uses the reference. ALT bytes are appended verbatim. A column is dropped when f64(unknown) >
+ *   unknown_frac * f64(len) (LCTY_PANVCF_UNKNOWN), and then when its sequence holds b'N' (LCTY_PANVCF_HAS_N). names: n_cols
+ *   0-terminated names. Out: the surviving sequences concatenated with seq_off[n_seqs + 1] and their names, in the layout
+ *   lcty_db_build_locus takes, kept_cols[n_seqs] their columns; per column col_unknown, col_len, col_reason. An allele index the
+ *   record does not have, or a broken allele table, is LCTY_ERR_INVALID_DATA. Kernels: a row reduction with the transposed copy of
+ *   the matrix, one wavefront per column for the accept rule, scans for the offsets, a tiled gather, a compaction;
+ *   no host loop over records and no host copy per haplotype. Release with lcty_panvcf_out_free.
+ * lcty_db_find_boundary (device): find_best_boundary::<LEFT> (add.rs:371-435) over [start, end): counts[n_counts] the k-mer counts of
+ *   the side's sequence, n_counts == (end - start) + moving_window - k; the records (pos, ref_len) sorted by position (else
+ *   LCTY_ERR_INVALID_DATA), applied to every position IN RECORD ORDER: covered positions 0, the nine to the left scaled by
+ *   (9 - i) / 10, the nine to the right by (i + 1) / 10; then w -= (w * (0.2 / allowed_expansion)) * i with i the distance from the
+ *   locus side; left != 0: the LAST maximum, else the FIRST; a maximum of 0.0 is *found = 0; start == end as lines 381-387.
+ *   weights (may be NULL) [end - start]: the final weights, equal to the reference's to the bit.
+ * lcty_db_expand_locus: expand_locus (438-518) and the retry loop of add_locus (733-755). win_seq / win_counts: the reference bytes
+ *   and the k-mer counts (n_win_counts == win_len + 1 - k) of ONE window [win_start, win_start + win_len) that holds the flanks of
+ *   every attempt, [inner_start - E, min(inner_end + E, contig_len)); the counts of a flank are a slice of it. pos / ref_len: the
+ *   KEPT records of the window (lcty_panvcf_filter) in file order. expansions: strictly increasing, 0 only alone; moving_window is
+ *   raised to k (add.rs:812). Per attempt: the flank ranges of 459-466, the crop at the last / first N (an N inside the locus side:
+ *   LCTY_ERR_INVALID_INPUT "Unknown sequence at the locus"), the records of [left_start, inner_start + 1) and [inner_end - 1,
+ *   right_end) by the fetch rule, two boundary searches. A locus shorter than the moving window: LCTY_ERR_INVALID_INPUT; no attempt
+ *   succeeds: LCTY_ERR_RUNTIME "Cannot expand locus ...".
+ * lcty_db_locus_from_vcf: the whole step: lcty_panvcf_filter over the window's records, lcty_db_expand_locus (unless the only
+ *   allowed expansion is 0), lcty_panvcf_reconstruct over the new interval, check_sequences without a reference (add.rs:655-690:
+ *   fewer than two haplotypes LCTY_ERR_INVALID_DATA; a sequence shorter than the 5-base affix LCTY_ERR_INVALID_INPUT; the warnings
+ *   as LCTY_LOCUS_WARN_* bits), lcty_db_build_locus. hap_counts / hap_cnt_off: the k-mer counts of the SURVIVING haplotypes and the
+ *   new reference interval as lcty_db_build_locus takes them — known only once the sequences are, so a first call with
+ *   params->only_seqs = 1 gives the sequences to count. ref_bed: the line of ref.bed, "contig\tstart\tend\tname\n". files.kept
+ *   indexes the reconstructed haplotypes, hap_cols[n_hap_cols] their columns. Lock files, `success`, Jellyfish and the rerun modes
+ *   stay with the caller. Release with lcty_locus_vcf_out_free. */
+#define LCTY_PANVCF_KEPT    0u
+#define LCTY_PANVCF_UNKNOWN 1u   /* too many unknown bases (discard_unknown, panvcf.rs:196-219) */
+#define LCTY_PANVCF_HAS_N   2u   /* the sequence holds N (add.rs:776) */
+#define LCTY_LOCUS_WARN_VERY_SHORT       1u   /* shortest haplotype < 1 000 (add.rs:660-662) */
+#define LCTY_LOCUS_WARN_SHORT            2u   /* ... < 10 000 (663-664) */
+#define LCTY_LOCUS_WARN_BOUNDARY_DIFFERS 4u   /* the haplotypes differ in their first or last 5 bases (684-688) */
+typedef struct lcty_vcf lcty_vcf;
+typedef struct lcty_vcf_view {
+    uint32_t n_samples, n_haps;                    /* n_haps = sum of the ploidies */
+    uint64_t n_records;                            /* records in the file */
+    const char* samples; uint64_t samples_len;     /* 0-terminated names */
+    const uint32_t* ploidy;                        /* [n_samples], from the first record */
+    const uint32_t* hap_off;                       /* [n_samples + 1] columns of gt */
+} lcty_vcf_view;
+typedef struct lcty_vcf_records {
+    uint32_t n_recs, n_haps, n_samples, _pad0;
+    uint64_t n_alleles, pool_len;
+    uint32_t* pos; uint32_t* ref_len; uint32_t* rec_allele;
+    uint64_t* allele_off; uint8_t* allele_bytes;
+    int16_t* gt; uint8_t* phased;
+} lcty_vcf_records;
+typedef struct lcty_panvcf_stats {
+    uint64_t bytes_h2d, bytes_d2h, n_segments, out_bytes;
+    /* wall time per stage with the stream drained at its end: uploads, row reduction + transpose, chain, scans + segment lists, gather,
+     * compaction + download, whole call */
+    double   upload_ms, rows_ms, chain_ms, scan_ms, gather_ms, compact_ms, total_ms;
+} lcty_panvcf_stats;
+typedef struct lcty_panvcf_out {
+    uint8_t* seqs; uint64_t* seq_off;              /* the surviving haplotypes, seq_off[n_seqs + 1] */
+    char* names; uint64_t names_len;               /* their names, 0-terminated */
+    uint32_t* kept_cols;                           /* [n_seqs] their columns */
+    uint32_t* col_unknown; uint32_t* col_len; uint8_t* col_reason;   /* [n_cols] unknown_nts, reconstructed length, LCTY_PANVCF_* */
+    uint32_t n_seqs, n_cols, n_unknown, n_with_n;
+    uint64_t total_overlaps, n_kept_records;       /* ignored alleles; records that passed the variation filter */
+    lcty_panvcf_stats stats;
+} lcty_panvcf_out;
+typedef struct lcty_expand_out {
+    uint32_t start, end;                           /* the new interval */
+    int32_t  attempt;                              /* index of the allowed expansion that succeeded */
+    uint32_t allowed_expansion, n_attempts;
+    uint32_t crop_bits;                            /* 1: the left flank was cropped at an N, 2: the right one */
+    double   total_ms;
+} lcty_expand_out;
+typedef struct lcty_locus_vcf_in {
+    const char* locus; const char* contig;
+    uint32_t inner_start, inner_end, contig_len, win_start;
+    const uint8_t* win_seq; uint64_t win_len;
+    const uint16_t* win_counts; uint64_t n_win_counts;      /* may be NULL when the only allowed expansion is 0 */
+    uint32_t k, counter_bytes;
+    uint32_t n_recs, n_cols;                                /* the records of the window (lcty_vcf_region) and the retained columns */
+    const uint32_t* pos; const uint32_t* ref_len; const uint32_t* rec_allele;
+    const uint64_t* allele_off; const uint8_t* allele_bytes;
+    const int16_t* gt; const char* names;
+    const uint32_t* expansions; uint32_t n_expansions, moving_window;   /* 20 000, 50 000, 200 000; 500 (add.rs:72-73) */
+    double   unknown_frac;                                  /* 0.0001 (add.rs:79) */
+    int32_t  overlaps_allowed, _pad0;
+    const uint16_t* hap_counts; const uint64_t* hap_cnt_off; /* NULL with params->only_seqs */
+} lcty_locus_vcf_in;
+typedef struct lcty_locus_vcf_stats {
+    uint32_t start, end;                           /* the interval of ref.bed */
+    int32_t  attempt; uint32_t allowed_expansion, crop_bits, warn_bits;
+    uint32_t n_cols, n_haplotypes, n_unknown, n_with_n, n_identical, n_records;   /* columns in; reconstructed and passed; dropped for unknown / N / identity */
+    uint64_t n_kept_records, total_overlaps, shortest;
+    double   filter_ms, expand_ms, reconstruct_ms, build_ms, total_ms;
+    lcty_panvcf_stats recon;
+} lcty_locus_vcf_stats;
+typedef struct lcty_locus_vcf_out {
+    lcty_db_files files;
+    char* ref_bed; uint64_t ref_bed_len;
+    uint32_t* hap_cols; uint32_t n_hap_cols, _pad0;
+    lcty_locus_vcf_stats stats;
+} lcty_locus_vcf_out;
+
+int32_t lcty_vcf_open(const char* path, lcty_vcf** out);
+int32_t lcty_vcf_view_get(const lcty_vcf* vcf, lcty_vcf_view* view);
+int32_t lcty_vcf_region(const lcty_vcf* vcf, const char* contig, uint32_t start, uint32_t end, const uint8_t* sample_used, lcty_vcf_records* out);
+void    lcty_vcf_records_free(lcty_vcf_records* records);
+void    lcty_vcf_free(lcty_vcf* vcf);
+int32_t lcty_panvcf_names(uint32_t n_samples, const char* samples, const uint32_t* ploidy, const char* ref_name, uint32_t n_leave_out,
+                          const char* leave_out, uint32_t cap_cols, uint32_t* n_cols, uint32_t* col_sample, uint32_t* col_hap, char* names,
+                          uint64_t cap_names, uint64_t* names_len, uint32_t* n_left_out);
+int32_t lcty_panvcf_filter(lcty_ctx* ctx, uint32_t n_recs, uint32_t n_cols, const int16_t* gt, uint8_t* kept, uint64_t* n_kept);
+int32_t lcty_panvcf_reconstruct(lcty_ctx* ctx, const char* contig, uint32_t ref_start, uint32_t ref_end, const uint8_t* ref_seq,
+                                uint32_t n_recs, const uint32_t* pos, const uint32_t* ref_len, const uint32_t* rec_allele,
+                                const uint64_t* allele_off, const uint8_t* allele_bytes, uint32_t n_cols, const int16_t* gt, const char* names,
+                                double unknown_frac, int32_t overlaps_allowed, lcty_panvcf_out* out);
+void    lcty_panvcf_out_free(lcty_panvcf_out* out);
+int32_t lcty_db_find_boundary(lcty_ctx* ctx, uint32_t start, uint32_t end, uint32_t n_recs, const uint32_t* pos, const uint32_t* ref_len,
+                              uint32_t k, const uint16_t* counts, uint64_t n_counts, uint32_t allowed_expansion, uint32_t moving_window,
+                              int32_t left, int32_t* found, uint32_t* position, double* weights);
+int32_t lcty_db_expand_locus(lcty_ctx* ctx, const char* locus, uint32_t inner_start, uint32_t inner_end, uint32_t contig_len,
+                             uint32_t win_start, const uint8_t* win_seq, uint64_t win_len, uint32_t k, const uint16_t* win_counts,
+                             uint64_t n_win_counts, uint32_t n_recs, const uint32_t* pos, const uint32_t* ref_len, uint32_t n_expansions,
+                             const uint32_t* expansions, uint32_t moving_window, lcty_expand_out* out);
+int32_t lcty_db_locus_from_vcf(lcty_ctx* ctx, const lcty_locus_vcf_in* in, const lcty_db_params* params, lcty_locus_vcf_out* out);
+void    lcty_locus_vcf_out_free(lcty_locus_vcf_out* out);
 
 /* ---- basis haplotypes (locityper augment, the basis step: DB/loci/<locus>/haplotypes-basis[.TAG].fa.gz) ------------------------------
  * construct_dominant_set -> inner_construct_dominant_set -> Cigar::locally_similar -> find_dominating_set (src/command/augment.rs:258-396,

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -41,6 +41,19 @@ SIGNATURES = {
     "lcty_fasta_write_text": (I32, [U32, C.c_char_p, VP, VP, VP, U64, P(U64)]),
     "lcty_db_build_locus": (I32, [VP, U32, C.c_char_p, VP, VP, VP, U64, VP, VP, U32, U32, P(DbParams), P(DbFiles)]),
     "lcty_db_files_free": (None, [P(DbFiles)]),
+    "lcty_vcf_open": (I32, [C.c_char_p, P(VP)]),
+    "lcty_vcf_view_get": (I32, [VP, P(VcfView)]),
+    "lcty_vcf_region": (I32, [VP, C.c_char_p, U32, U32, VP, P(VcfRecords)]),
+    "lcty_vcf_records_free": (None, [P(VcfRecords)]),
+    "lcty_vcf_free": (None, [VP]),
+    "lcty_panvcf_names": (I32, [U32, C.c_char_p, VP, C.c_char_p, U32, C.c_char_p, U32, P(U32), VP, VP, VP, U64, P(U64), P(U32)]),
+    "lcty_panvcf_filter": (I32, [VP, U32, U32, VP, VP, P(U64)]),
+    "lcty_panvcf_reconstruct": (I32, [VP, C.c_char_p, U32, U32, VP, U32, VP, VP, VP, VP, VP, U32, VP, C.c_char_p, D, I32, P(PanvcfOut)]),
+    "lcty_panvcf_out_free": (None, [P(PanvcfOut)]),
+    "lcty_db_find_boundary": (I32, [VP, U32, U32, U32, VP, VP, U32, VP, U64, U32, U32, I32, P(I32), P(U32), VP]),
+    "lcty_db_expand_locus": (I32, [VP, C.c_char_p, U32, U32, U32, U32, VP, U64, U32, VP, U64, U32, VP, VP, U32, VP, U32, P(ExpandOut)]),
+    "lcty_db_locus_from_vcf": (I32, [VP, P(LocusVcfIn), P(DbParams), P(LocusVcfOut)]),
+    "lcty_locus_vcf_out_free": (None, [P(LocusVcfOut)]),
     "lcty_basis_params_default": (None, [P(BasisParams)]),
     "lcty_basis_windows": (I32, [VP, U32, VP, U64, VP, VP, VP, VP, VP, VP, VP, P(BasisParams), VP, P(VP), P(BasisStats)]),
     "lcty_basis_constraints": (I32, [VP, U32, U64, VP, I32, P(U64), P(VP), P(BasisStats)]),

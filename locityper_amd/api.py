@@ -1064,6 +1064,141 @@ def db_build_locus(ctx, names, seqs, seq_off, ref_seq=None, counts=None, cnt_off
         lib().lcty_db_files_free(C.byref(f))
 
 
+# ---- a locus from a pangenome VCF (locityper target -v; lcty_panvcf.hip) -------------------------------------------------------------
+def panvcf_names(samples, ploidy, ref_name, leave_out=()):
+    """lcty_panvcf_names (HaplotypeNames::new): (names of the retained columns, col_sample — NONE_U32 for the reference —, col_hap, haplotypes left out)."""
+    from .io import _names_blob
+    pl = np.ascontiguousarray(ploidy, dtype=np.uint32)
+    sb, lb = _names_blob(samples), _names_blob(leave_out)
+    n, nl, left = U32(), U64(), U32()
+    args = (len(samples), sb, pl.ctypes.data, ref_name.encode(), len(leave_out), lb)
+    check(lib().lcty_panvcf_names(*args, 0, C.byref(n), None, None, None, 0, C.byref(nl), C.byref(left)))
+    cs = np.zeros(max(n.value, 1), dtype=np.uint32); ch = np.zeros(max(n.value, 1), dtype=np.uint32)
+    names = np.zeros(max(int(nl.value), 1), dtype=np.uint8)
+    check(lib().lcty_panvcf_names(*args, len(cs), C.byref(n), cs.ctypes.data, ch.ctypes.data, names.ctypes.data, len(names), C.byref(nl), C.byref(left)))
+    return [x.decode() for x in names[:int(nl.value)].tobytes().split(b"\0")[:-1]], cs[:n.value].copy(), ch[:n.value].copy(), int(left.value)
+
+
+def panvcf_columns(gt, hap_off, col_sample, col_hap):
+    """The genotype matrix restricted to the retained columns of panvcf_names: a kept reference is a column of zeros."""
+    gt = np.asarray(gt, dtype=np.int16)
+    out = np.zeros((gt.shape[0], len(col_sample)), dtype=np.int16)
+    for c, (s, h) in enumerate(zip(col_sample, col_hap)):
+        if int(s) != cdefs.NONE_U32:
+            out[:, c] = gt[:, int(hap_off[int(s)]) + int(h)]
+    return out
+
+
+def panvcf_filter(ctx, gt):
+    """lcty_panvcf_filter: kept[v] = some column of gt[v] has allele >= 1."""
+    g = np.ascontiguousarray(gt, dtype=np.int16)
+    kept = np.zeros(max(g.shape[0], 1), dtype=np.uint8)
+    n = U64()
+    check(lib().lcty_panvcf_filter(ctx._h, g.shape[0], g.shape[1], g.ctypes.data, kept.ctypes.data, C.byref(n)))
+    return kept[:g.shape[0]].astype(bool)
+
+
+def _rec_arrays(recs):
+    return (np.ascontiguousarray(recs["pos"], dtype=np.uint32), np.ascontiguousarray(recs["ref_len"], dtype=np.uint32),
+            np.ascontiguousarray(recs["rec_allele"], dtype=np.uint32), np.ascontiguousarray(recs["allele_off"], dtype=np.uint64),
+            np.ascontiguousarray(recs["allele_bytes"], dtype=np.uint8))
+
+
+def panvcf_reconstruct(ctx, contig, ref_start, ref_end, ref_seq, recs, gt, names, unknown_frac=0.0001, overlaps_allowed=False):
+    """lcty_panvcf_reconstruct: recs = the dict of io.Vcf.region (pos, ref_len, rec_allele, allele_off, allele_bytes), gt [n_recs][n_cols] the
+    matrix of the retained columns (panvcf_columns). Returns a dict: names, seqs, seq_off, kept_cols, col_unknown, col_len, col_reason,
+    total_overlaps, n_kept_records, stats."""
+    from .io import _names_blob
+    pos, rl, ra, ao, ab = _rec_arrays(recs)
+    g = np.ascontiguousarray(gt, dtype=np.int16)
+    if g.ndim != 2 or g.shape[0] != len(pos) or g.shape[1] != len(names):
+        raise ValueError("gt must be [n_recs][n_cols]")
+    ref = np.ascontiguousarray(ref_seq, dtype=np.uint8)
+    if len(ref) != ref_end - ref_start:
+        raise ValueError("ref_seq must hold ref_end - ref_start bytes")
+    o = cdefs.PanvcfOut()
+    check(lib().lcty_panvcf_reconstruct(ctx._h, contig.encode(), ref_start, ref_end, ref.ctypes.data, len(pos), pos.ctypes.data, rl.ctypes.data, ra.ctypes.data,
+                                        ao.ctypes.data, ab.ctypes.data, g.shape[1], g.ctypes.data, _names_blob(names), unknown_frac, int(overlaps_allowed),
+                                        C.byref(o)))
+    try:
+        def arr(p, n, dt):
+            return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+        off = arr(o.seq_off, o.n_seqs + 1, np.uint64)
+        return {"names": [x.decode() for x in C.string_at(o.names, o.names_len).split(b"\0")[:-1]], "seqs": arr(o.seqs, int(off[-1]), np.uint8),
+                "seq_off": off, "kept_cols": arr(o.kept_cols, o.n_seqs, np.uint32), "col_unknown": arr(o.col_unknown, o.n_cols, np.uint32),
+                "col_len": arr(o.col_len, o.n_cols, np.uint32), "col_reason": arr(o.col_reason, o.n_cols, np.uint8),
+                "total_overlaps": int(o.total_overlaps), "n_kept_records": int(o.n_kept_records), "stats": o.stats.as_dict()}
+    finally:
+        lib().lcty_panvcf_out_free(C.byref(o))
+
+
+def db_find_boundary(ctx, start, end, pos, ref_len, k, counts, allowed_expansion, moving_window, left, with_weights=True):
+    """lcty_db_find_boundary: (position or None, the final weights [end - start] or None)."""
+    p = np.ascontiguousarray(pos, dtype=np.uint32); rl = np.ascontiguousarray(ref_len, dtype=np.uint32)
+    cnt = np.ascontiguousarray(counts, dtype=np.uint16)
+    w = np.zeros(max(end - start, 1), dtype=np.float64) if with_weights and end > start else None
+    found, at = C.c_int32(), U32()
+    check(lib().lcty_db_find_boundary(ctx._h, start, end, len(p), p.ctypes.data, rl.ctypes.data, k, cnt.ctypes.data, len(cnt), allowed_expansion, moving_window,
+                                      int(left), C.byref(found), C.byref(at), None if w is None else w.ctypes.data))
+    return (int(at.value) if found.value else None), (None if w is None else w[:end - start])
+
+
+DEFAULT_EXPANSIONS = (20_000, 50_000, 200_000)        # add.rs:72
+
+
+def db_expand_locus(ctx, locus, inner_start, inner_end, contig_len, win_start, win_seq, k, win_counts, pos, ref_len, expansions=DEFAULT_EXPANSIONS,
+                    moving_window=500):
+    """lcty_db_expand_locus: pos / ref_len = the kept records of the window. Returns the ExpandOut fields as a dict."""
+    ws = np.ascontiguousarray(win_seq, dtype=np.uint8); wc = np.ascontiguousarray(win_counts, dtype=np.uint16)
+    p = np.ascontiguousarray(pos, dtype=np.uint32); rl = np.ascontiguousarray(ref_len, dtype=np.uint32)
+    ex = np.ascontiguousarray(expansions, dtype=np.uint32)
+    o = cdefs.ExpandOut()
+    check(lib().lcty_db_expand_locus(ctx._h, locus.encode(), inner_start, inner_end, contig_len, win_start, ws.ctypes.data, len(ws), k, wc.ctypes.data, len(wc),
+                                     len(p), p.ctypes.data, rl.ctypes.data, len(ex), ex.ctypes.data, moving_window, C.byref(o)))
+    return o.as_dict()
+
+
+def db_locus_from_vcf(ctx, locus, contig, inner_start, inner_end, contig_len, win_start, win_seq, recs, gt, names, k=25, win_counts=None,
+                      expansions=DEFAULT_EXPANSIONS, moving_window=500, unknown_frac=0.0001, overlaps_allowed=False, hap_counts=None, hap_cnt_off=None,
+                      counter_bytes=2, params=None):
+    """lcty_db_locus_from_vcf: expansion, reconstruction, check_sequences, lcty_db_build_locus. recs / gt / names as panvcf_reconstruct, over the
+    window. Returns the dict of db_build_locus plus ref_bed (bytes), hap_cols and the stats of the whole step under "locus_stats"."""
+    from .io import _names_blob
+    pos, rl, ra, ao, ab = _rec_arrays(recs)
+    g = np.ascontiguousarray(gt, dtype=np.int16)
+    if g.ndim != 2 or g.shape[0] != len(pos) or g.shape[1] != len(names):
+        raise ValueError("gt must be [n_recs][n_cols]")
+    ws = np.ascontiguousarray(win_seq, dtype=np.uint8)
+    wc = None if win_counts is None else np.ascontiguousarray(win_counts, dtype=np.uint16)
+    ex = np.ascontiguousarray(expansions, dtype=np.uint32)
+    hc = None if hap_counts is None else np.ascontiguousarray(hap_counts, dtype=np.uint16)
+    hco = None if hap_cnt_off is None else np.ascontiguousarray(hap_cnt_off, dtype=np.uint64)
+    p = params if params is not None else db_params(only_seqs=int(hc is None))
+    i = cdefs.LocusVcfIn()
+    i.locus, i.contig, i.names = locus.encode(), contig.encode(), _names_blob(names)
+    i.inner_start, i.inner_end, i.contig_len, i.win_start = inner_start, inner_end, contig_len, win_start
+    i.win_seq, i.win_len = ws.ctypes.data, len(ws)
+    i.win_counts, i.n_win_counts = (None, 0) if wc is None else (wc.ctypes.data, len(wc))
+    i.k, i.counter_bytes, i.n_recs, i.n_cols = k, counter_bytes, len(pos), g.shape[1]
+    i.pos, i.ref_len, i.rec_allele, i.allele_off, i.allele_bytes, i.gt = pos.ctypes.data, rl.ctypes.data, ra.ctypes.data, ao.ctypes.data, ab.ctypes.data, g.ctypes.data
+    i.expansions, i.n_expansions, i.moving_window = ex.ctypes.data, len(ex), moving_window
+    i.unknown_frac, i.overlaps_allowed = unknown_frac, int(overlaps_allowed)
+    i.hap_counts, i.hap_cnt_off = (None if hc is None else hc.ctypes.data), (None if hco is None else hco.ctypes.data)
+    o = cdefs.LocusVcfOut()
+    check(lib().lcty_db_locus_from_vcf(ctx._h, C.byref(i), C.byref(p), C.byref(o)))
+    try:
+        f = o.files
+        return {
+            "fasta": C.string_at(f.fasta, f.fasta_len), "kmers": C.string_at(f.kmers, f.kmers_len),
+            "distances": C.string_at(f.distances, f.distances_len), "discarded": C.string_at(f.discarded, f.discarded_len),
+            "kept": np.frombuffer(C.string_at(f.kept, 4 * f.n_kept), dtype=np.uint32).copy(), "warn_bits": int(f.warn_bits),
+            "stats": f.stats.as_dict(), "ref_bed": C.string_at(o.ref_bed, o.ref_bed_len),
+            "hap_cols": np.frombuffer(C.string_at(o.hap_cols, 4 * o.n_hap_cols), dtype=np.uint32).copy(), "locus_stats": o.stats.as_dict(),
+        }
+    finally:
+        lib().lcty_locus_vcf_out_free(C.byref(o))
+
+
 # ---- basis haplotypes (the basis step of `locityper augment`) ----------------------------------------------------------------------------
 def basis_params(**kw):
     """lcty_basis_params_default (divergence 0.01, window 250, step 0 = window / 2, minimal rows, 2 M nodes) with overrides."""

@@ -128,6 +128,67 @@ class DbFiles(C.Structure):
                 ("kept", C.c_void_p), ("n_kept", C.c_uint32), ("warn_bits", C.c_uint32), ("check", DbCheck), ("stats", DbStats)]
 
 
+# ---- a locus from a pangenome VCF (lcty_panvcf.hip, the VCF reader of lcty_io.hip) ----
+PANVCF_KEPT, PANVCF_UNKNOWN, PANVCF_HAS_N = 0, 1, 2
+LOCUS_WARN_VERY_SHORT, LOCUS_WARN_SHORT, LOCUS_WARN_BOUNDARY_DIFFERS = 1, 2, 4
+
+
+class _Dictable(C.Structure):
+    def as_dict(self):
+        return {n: (getattr(self, n).as_dict() if hasattr(getattr(self, n), "as_dict") else getattr(self, n)) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class VcfView(C.Structure):
+    _fields_ = [("n_samples", C.c_uint32), ("n_haps", C.c_uint32), ("n_records", C.c_uint64), ("samples", C.c_void_p), ("samples_len", C.c_uint64),
+                ("ploidy", C.c_void_p), ("hap_off", C.c_void_p)]
+
+
+class VcfRecords(C.Structure):
+    _fields_ = [("n_recs", C.c_uint32), ("n_haps", C.c_uint32), ("n_samples", C.c_uint32), ("_pad0", C.c_uint32), ("n_alleles", C.c_uint64),
+                ("pool_len", C.c_uint64), ("pos", C.c_void_p), ("ref_len", C.c_void_p), ("rec_allele", C.c_void_p), ("allele_off", C.c_void_p),
+                ("allele_bytes", C.c_void_p), ("gt", C.c_void_p), ("phased", C.c_void_p)]
+
+
+class PanvcfStats(_Dictable):
+    _fields_ = [(n, C.c_uint64) for n in ("bytes_h2d", "bytes_d2h", "n_segments", "out_bytes")] + \
+               [(n, C.c_double) for n in ("upload_ms", "rows_ms", "chain_ms", "scan_ms", "gather_ms", "compact_ms", "total_ms")]
+
+
+class PanvcfOut(C.Structure):
+    _fields_ = [("seqs", C.c_void_p), ("seq_off", C.c_void_p), ("names", C.c_void_p), ("names_len", C.c_uint64), ("kept_cols", C.c_void_p),
+                ("col_unknown", C.c_void_p), ("col_len", C.c_void_p), ("col_reason", C.c_void_p), ("n_seqs", C.c_uint32), ("n_cols", C.c_uint32),
+                ("n_unknown", C.c_uint32), ("n_with_n", C.c_uint32), ("total_overlaps", C.c_uint64), ("n_kept_records", C.c_uint64),
+                ("stats", PanvcfStats)]
+
+
+class ExpandOut(_Dictable):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("attempt", C.c_int32), ("allowed_expansion", C.c_uint32), ("n_attempts", C.c_uint32),
+                ("crop_bits", C.c_uint32), ("total_ms", C.c_double)]
+
+
+class LocusVcfIn(C.Structure):
+    _fields_ = [("locus", C.c_char_p), ("contig", C.c_char_p), ("inner_start", C.c_uint32), ("inner_end", C.c_uint32), ("contig_len", C.c_uint32),
+                ("win_start", C.c_uint32), ("win_seq", C.c_void_p), ("win_len", C.c_uint64), ("win_counts", C.c_void_p), ("n_win_counts", C.c_uint64),
+                ("k", C.c_uint32), ("counter_bytes", C.c_uint32), ("n_recs", C.c_uint32), ("n_cols", C.c_uint32), ("pos", C.c_void_p),
+                ("ref_len", C.c_void_p), ("rec_allele", C.c_void_p), ("allele_off", C.c_void_p), ("allele_bytes", C.c_void_p), ("gt", C.c_void_p),
+                ("names", C.c_char_p), ("expansions", C.c_void_p), ("n_expansions", C.c_uint32), ("moving_window", C.c_uint32),
+                ("unknown_frac", C.c_double), ("overlaps_allowed", C.c_int32), ("_pad0", C.c_int32), ("hap_counts", C.c_void_p),
+                ("hap_cnt_off", C.c_void_p)]
+
+
+class LocusVcfStats(_Dictable):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("attempt", C.c_int32), ("allowed_expansion", C.c_uint32), ("crop_bits", C.c_uint32),
+                ("warn_bits", C.c_uint32)] + \
+               [(n, C.c_uint32) for n in ("n_cols", "n_haplotypes", "n_unknown", "n_with_n", "n_identical", "n_records")] + \
+               [(n, C.c_uint64) for n in ("n_kept_records", "total_overlaps", "shortest")] + \
+               [(n, C.c_double) for n in ("filter_ms", "expand_ms", "reconstruct_ms", "build_ms", "total_ms")] + [("recon", PanvcfStats)]
+
+
+class LocusVcfOut(C.Structure):
+    _fields_ = [("files", DbFiles), ("ref_bed", C.c_void_p), ("ref_bed_len", C.c_uint64), ("hap_cols", C.c_void_p), ("n_hap_cols", C.c_uint32),
+                ("_pad0", C.c_uint32), ("stats", LocusVcfStats)]
+
+
 class BasisParams(C.Structure):
     """The basis step of `locityper augment` (src/command/augment.rs:59-61); window 2^32 - 1 = global, step 0 = max(window >> 1, 1)."""
     _fields_ = [("divergence", C.c_double), ("window", C.c_uint32), ("step", C.c_uint32), ("minimal", C.c_uint32), ("_pad0", C.c_uint32),

@@ -1147,3 +1147,206 @@ int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, cha
 }
 
 }  // extern "C"
+
+// ---- pangenome VCF (text: plain, gzip, BGZF; no index, no BCF) --------------------------------------------------------------------------
+// What bcf::IndexedReader gives panvcf.rs: the samples of the header, the ploidies of the first record (HaplotypeNames::new, 85-91) and
+// the records of a region with their alleles and GT fields (filter_variants, 155-172).
+struct lcty_vcf {
+    std::vector<uint8_t> text;
+    std::vector<std::string> samples;
+    std::string sample_blob;
+    std::vector<uint32_t> ploidy, hap_off;           // of the first record; hap_off[n_samples + 1]
+    struct Line { uint64_t begin, end; uint32_t contig, pos, ref_len; };
+    std::vector<Line> lines;                         // the records in file order
+    std::vector<std::string> contigs;                // in the order of first appearance
+    lcty_vcf_view view{};
+};
+
+namespace {
+
+struct Field { const char* p; size_t n; };
+
+// the tab-separated fields of [begin, end)
+std::vector<Field> split_tabs(const uint8_t* text, uint64_t begin, uint64_t end) {
+    std::vector<Field> out;
+    uint64_t s = begin;
+    for (uint64_t i = begin; i <= end; i++)
+        if (i == end || text[i] == '\t') { out.push_back({reinterpret_cast<const char*>(text) + s, size_t(i - s)}); s = i + 1; }
+    return out;
+}
+
+// The GT subfield of one sample: allele indices (-1 for '.') and whether the separator before the last allele is '|' (a haploid call has
+// none and counts as phased). `which` = position of GT among the FORMAT keys.
+void parse_gt(Field sample, size_t which, std::vector<int32_t>& alleles, bool& phased, const std::string& where) {
+    const char* p = sample.p; const char* e = sample.p + sample.n;
+    for (size_t skip = 0; skip < which && p < e; skip++) { while (p < e && *p != ':') p++; if (p < e) p++; else { p = e; } }
+    const char* q = p;
+    while (q < e && *q != ':') q++;
+    alleles.clear(); phased = true;
+    if (p == q) { alleles.push_back(-1); return; }                     // a dropped trailing field: one missing allele
+    while (p < q) {
+        if (*p == '.') { alleles.push_back(-1); p++; }
+        else {
+            if (*p < '0' || *p > '9') fail(LCTY_ERR_INVALID_DATA, "Variant %s: cannot parse the genotype '%.*s'", where.c_str(), int(sample.n), sample.p);
+            int64_t v = 0;
+            while (p < q && *p >= '0' && *p <= '9') { v = v * 10 + (*p - '0'); if (v > 32767) fail(LCTY_ERR_UNSUPPORTED, "Variant %s: allele index above 32767", where.c_str()); p++; }
+            alleles.push_back(static_cast<int32_t>(v));
+        }
+        if (p < q) {
+            if (*p != '/' && *p != '|') fail(LCTY_ERR_INVALID_DATA, "Variant %s: cannot parse the genotype '%.*s'", where.c_str(), int(sample.n), sample.p);
+            phased = *p == '|';
+            p++;
+            if (p == q) fail(LCTY_ERR_INVALID_DATA, "Variant %s: cannot parse the genotype '%.*s'", where.c_str(), int(sample.n), sample.p);
+        }
+    }
+}
+
+size_t gt_index(Field format, const std::string& where) {
+    size_t ix = 0, s = 0;
+    for (size_t i = 0; i <= format.n; i++)
+        if (i == format.n || format.p[i] == ':') {
+            if (i - s == 2 && format.p[s] == 'G' && format.p[s + 1] == 'T') return ix;
+            ix++; s = i + 1;
+        }
+    fail(LCTY_ERR_INVALID_DATA, "Variant %s has no GT field", where.c_str());
+}
+
+template <typename T> T* vcf_malloc_copy(const std::vector<T>& v) {
+    T* out = static_cast<T*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
+    if (!out) throw std::bad_alloc();
+    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(T));
+    return out;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t lcty_vcf_open(const char* path, lcty_vcf** out) {
+    return guarded([&] {
+        if (!path || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        *out = nullptr;
+        const std::string p(path);
+        if (ends_with(p, ".bcf")) fail(LCTY_ERR_UNSUPPORTED, "%s: BCF is not read here, convert it to a text VCF", path);
+        auto V = std::make_unique<lcty_vcf>();
+        std::vector<uint8_t> raw = slurp(path);
+        if (raw.size() >= 2 && raw[0] == 0x1f && raw[1] == 0x8b) V->text = inflate_gzip(raw, path); else V->text.swap(raw);
+        const std::vector<uint8_t>& t = V->text;
+        bool have_header = false;
+        std::unordered_map<std::string, uint32_t> contig_ix;
+        for (uint64_t b = 0; b < t.size();) {
+            uint64_t e = b;
+            while (e < t.size() && t[e] != '\n') e++;
+            uint64_t le = e;
+            if (le > b && t[le - 1] == '\r') le--;
+            if (le > b) {
+                if (t[b] == '#') {
+                    if (le - b >= 6 && !memcmp(&t[b], "#CHROM", 6)) {
+                        const std::vector<Field> f = split_tabs(t.data(), b, le);
+                        if (f.size() < 8) fail(LCTY_ERR_INVALID_DATA, "%s: the #CHROM line has %zu columns", path, f.size());
+                        for (size_t i = 9; i < f.size(); i++) V->samples.emplace_back(f[i].p, f[i].n);
+                        have_header = true;
+                    }
+                } else {
+                    if (!have_header) fail(LCTY_ERR_INVALID_DATA, "%s: a record comes before the #CHROM line", path);
+                    // CHROM, POS, ID, REF
+                    uint64_t c[4]; uint32_t nc = 0;
+                    for (uint64_t i = b; i < le && nc < 4; i++) if (t[i] == '\t') c[nc++] = i;
+                    if (nc < 4) fail(LCTY_ERR_INVALID_DATA, "%s: a record has fewer than five columns", path);
+                    const std::string chrom(reinterpret_cast<const char*>(&t[b]), c[0] - b);
+                    uint64_t pos = 0;
+                    if (c[1] == c[0] + 1) fail(LCTY_ERR_INVALID_DATA, "%s: a record of %s has no position", path, chrom.c_str());
+                    for (uint64_t i = c[0] + 1; i < c[1]; i++) {
+                        if (t[i] < '0' || t[i] > '9' || pos > 0xFFFFFFFFull) fail(LCTY_ERR_INVALID_DATA, "%s: bad position in a record of %s", path, chrom.c_str());
+                        pos = pos * 10 + (t[i] - '0');
+                    }
+                    if (pos < 1 || pos > 0xFFFFFFFFull) fail(LCTY_ERR_INVALID_DATA, "%s: bad position in a record of %s", path, chrom.c_str());
+                    auto it = contig_ix.find(chrom);
+                    if (it == contig_ix.end()) { it = contig_ix.emplace(chrom, static_cast<uint32_t>(V->contigs.size())).first; V->contigs.push_back(chrom); }
+                    V->lines.push_back({b, le, it->second, static_cast<uint32_t>(pos - 1), static_cast<uint32_t>(c[3] - c[2] - 1)});
+                }
+            }
+            b = e + 1;
+        }
+        if (!have_header) fail(LCTY_ERR_INVALID_DATA, "%s has no #CHROM line", path);
+        if (V->lines.empty()) fail(LCTY_ERR_INVALID_DATA, "Input VCF file does not contain any records");          // panvcf.rs:85-86
+        // the ploidies of the first record
+        const uint32_t S = static_cast<uint32_t>(V->samples.size());
+        V->ploidy.assign(S, 0); V->hap_off.assign(S + 1, 0);
+        if (S) {
+            const lcty_vcf::Line& l0 = V->lines[0];
+            const std::string where = V->contigs[l0.contig] + ":" + std::to_string(uint64_t(l0.pos) + 1);
+            const std::vector<Field> f = split_tabs(t.data(), l0.begin, l0.end);
+            if (f.size() != 9 + size_t(S)) fail(LCTY_ERR_INVALID_DATA, "Variant %s has %zu columns (expected %u)", where.c_str(), f.size(), 9 + S);
+            const size_t which = gt_index(f[8], where);
+            std::vector<int32_t> al; bool ph;
+            for (uint32_t i = 0; i < S; i++) { parse_gt(f[9 + i], which, al, ph, where); V->ploidy[i] = static_cast<uint32_t>(al.size()); }
+        }
+        for (uint32_t i = 0; i < S; i++) { V->hap_off[i + 1] = V->hap_off[i] + V->ploidy[i]; V->sample_blob += V->samples[i]; V->sample_blob.push_back('\0'); }
+        V->view.n_samples = S; V->view.n_haps = V->hap_off[S]; V->view.n_records = V->lines.size();
+        V->view.samples = V->sample_blob.data(); V->view.samples_len = V->sample_blob.size();
+        V->view.ploidy = V->ploidy.data(); V->view.hap_off = V->hap_off.data();
+        *out = V.release();
+    });
+}
+
+int32_t lcty_vcf_view_get(const lcty_vcf* vcf, lcty_vcf_view* view) {
+    return guarded([&] {
+        if (!vcf || !view) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        *view = vcf->view;
+    });
+}
+
+void lcty_vcf_free(lcty_vcf* vcf) { delete vcf; }
+
+int32_t lcty_vcf_region(const lcty_vcf* vcf, const char* contig, uint32_t start, uint32_t end, const uint8_t* sample_used, lcty_vcf_records* out) {
+    return guarded([&] {
+        if (!vcf || !contig || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        memset(out, 0, sizeof(*out));
+        const uint32_t S = vcf->view.n_samples, Hn = vcf->view.n_haps;
+        uint32_t cix = LCTY_NONE_U32;
+        for (uint32_t i = 0; i < vcf->contigs.size(); i++) if (vcf->contigs[i] == contig) cix = i;
+        std::vector<uint32_t> pos, rlen, rec_allele{0}; std::vector<uint64_t> allele_off{0}; std::vector<uint8_t> pool, phased; std::vector<int16_t> gt;
+        std::vector<int32_t> al;
+        const uint8_t* t = vcf->text.data();
+        for (const lcty_vcf::Line& l : vcf->lines) {
+            if (l.contig != cix || !(l.pos < end && uint64_t(l.pos) + l.ref_len > start)) continue;          // htslib's fetch; INFO/END is not looked at
+            const std::string where = std::string(contig) + ":" + std::to_string(uint64_t(l.pos) + 1);       // format_var, panvcf.rs:187-193
+            const std::vector<Field> f = split_tabs(t, l.begin, l.end);
+            if (f.size() != (S ? 9 + size_t(S) : f.size()) || f.size() < 8) fail(LCTY_ERR_INVALID_DATA, "Variant %s has %zu columns (expected %u)", where.c_str(), f.size(), 9 + S);
+            pos.push_back(l.pos); rlen.push_back(l.ref_len);
+            pool.insert(pool.end(), f[3].p, f[3].p + f[3].n); allele_off.push_back(pool.size());
+            if (!(f[4].n == 1 && f[4].p[0] == '.')) {
+                size_t s = 0;
+                for (size_t i = 0; i <= f[4].n; i++)
+                    if (i == f[4].n || f[4].p[i] == ',') { pool.insert(pool.end(), f[4].p + s, f[4].p + i); allele_off.push_back(pool.size()); s = i + 1; }
+            }
+            rec_allele.push_back(static_cast<uint32_t>(allele_off.size() - 1));
+            if (!S) continue;
+            const size_t which = gt_index(f[8], where);
+            for (uint32_t i = 0; i < S; i++) {
+                bool ph = true;
+                parse_gt(f[9 + i], which, al, ph, where);
+                const uint32_t pl = vcf->ploidy[i];
+                const bool used = !sample_used || sample_used[i];
+                if (used && al.size() != pl)                                                                 // panvcf.rs:161-164
+                    fail(LCTY_ERR_INVALID_DATA, "Variant %s in sample %s has ploidy %zu (expected %u)", where.c_str(), vcf->samples[i].c_str(), al.size(), pl);
+                if (used && pl > 1 && !ph)                                                                   // panvcf.rs:167-171
+                    fail(LCTY_ERR_INVALID_DATA, "Variant %s is unphased in sample %s", where.c_str(), vcf->samples[i].c_str());
+                for (uint32_t h = 0; h < pl; h++) gt.push_back(h < al.size() ? static_cast<int16_t>(al[h]) : int16_t(-1));
+                phased.push_back(ph ? 1 : 0);
+            }
+        }
+        out->n_recs = static_cast<uint32_t>(pos.size()); out->n_haps = Hn; out->n_samples = S; out->n_alleles = allele_off.size() - 1; out->pool_len = pool.size();
+        out->pos = vcf_malloc_copy(pos); out->ref_len = vcf_malloc_copy(rlen); out->rec_allele = vcf_malloc_copy(rec_allele);
+        out->allele_off = vcf_malloc_copy(allele_off); out->allele_bytes = vcf_malloc_copy(pool); out->gt = vcf_malloc_copy(gt); out->phased = vcf_malloc_copy(phased);
+    });
+}
+
+void lcty_vcf_records_free(lcty_vcf_records* r) {
+    if (!r) return;
+    free(r->pos); free(r->ref_len); free(r->rec_allele); free(r->allele_off); free(r->allele_bytes); free(r->gt); free(r->phased);
+    memset(r, 0, sizeof(*r));
+}
+
+}  // extern "C"

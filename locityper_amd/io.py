@@ -270,3 +270,57 @@ class FastxWriters:
         if self._h:
             h, self._h = self._h, VP()
             check(lib().lcty_fastx_writers_close(h))
+
+
+class Vcf:
+    """lcty_vcf_open: a text VCF (plain, gzip, BGZF). samples, ploidy (of the first record), hap_off (columns of gt)."""
+
+    def __init__(self, path):
+        self._h = VP()
+        check(lib().lcty_vcf_open(str(path).encode(), C.byref(self._h)))
+        v = cdefs.VcfView()
+        check(lib().lcty_vcf_view_get(self._h, C.byref(v)))
+        blob = C.string_at(v.samples, v.samples_len) if v.samples_len else b""
+        self.samples = [s.decode() for s in blob.split(b"\0")[:-1]]
+        self.ploidy = np.frombuffer(C.string_at(v.ploidy, 4 * v.n_samples), dtype=np.uint32).copy() if v.n_samples else np.zeros(0, np.uint32)
+        self.hap_off = np.frombuffer(C.string_at(v.hap_off, 4 * (v.n_samples + 1)), dtype=np.uint32).copy()
+        self.n_haps, self.n_records = int(v.n_haps), int(v.n_records)
+
+    def region(self, contig, start, end, sample_used=None):
+        """lcty_vcf_region: the records fetch(start, end) returns, as a dict of flat arrays: pos, ref_len, rec_allele, allele_off,
+        allele_bytes, gt [n_recs][n_haps] (int16, -1 = missing), phased [n_recs][n_samples]."""
+        used = None if sample_used is None else np.ascontiguousarray(sample_used, dtype=np.uint8)
+        if used is not None and len(used) != len(self.samples):
+            raise ValueError("sample_used must have one entry per sample")
+        r = cdefs.VcfRecords()
+        check(lib().lcty_vcf_region(self._h, contig.encode(), start, end, None if used is None else used.ctypes.data, C.byref(r)))
+        try:
+            def arr(p, n, dt):
+                return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+            n = int(r.n_recs)
+            return {"pos": arr(r.pos, n, np.uint32), "ref_len": arr(r.ref_len, n, np.uint32), "rec_allele": arr(r.rec_allele, n + 1, np.uint32),
+                    "allele_off": arr(r.allele_off, int(r.n_alleles) + 1, np.uint64), "allele_bytes": arr(r.allele_bytes, int(r.pool_len), np.uint8),
+                    "gt": arr(r.gt, n * int(r.n_haps), np.int16).reshape(n, int(r.n_haps)),
+                    "phased": arr(r.phased, n * int(r.n_samples), np.uint8).reshape(n, int(r.n_samples))}
+        finally:
+            lib().lcty_vcf_records_free(C.byref(r))
+
+    def close(self):
+        if self._h:
+            lib().lcty_vcf_free(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vcf_region(path, contig, start, end, sample_used=None):
+    """Open, lcty_vcf_region, close: (Vcf fields as a dict, records dict)."""
+    v = Vcf(path)
+    try:
+        return {"samples": v.samples, "ploidy": v.ploidy, "hap_off": v.hap_off}, v.region(contig, start, end, sample_used)
+    finally:
+        v.close()
