@@ -250,7 +250,10 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       stretch the exact aligner takes (default 2^26; a larger stretch is dropped to align_simple and counted in n_dropped — this one
  *       changes CIGARs, as the limit itself does);   "align_cigar_store_mb"   megabytes of device memory for the finished CIGARs of
  *       lcty_align_haplotypes_transitive (default: an eighth of the free device memory, at least 64; a call whose CIGARs outgrow it is
- *       LCTY_ERR_UNSUPPORTED naming this knob — it never takes another route).
+ *       LCTY_ERR_UNSUPPORTED naming this knob — it never takes another route);   "pafvcf_hash_bits"   bits kept of the hash of an
+ *       allele's bytes in lcty_pafvcf_table (default 64; fewer: collisions, which the comparison of the bytes must reject);
+ *       "pafvcf_table_mb"   megabytes the resident allele table (n_ranges x n_seqs x 4 bytes) of lcty_pafvcf_table / lcty_paf_to_vcf may
+ *       take (default: a quarter of the free device memory; a larger table is LCTY_ERR_UNSUPPORTED naming this knob).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -1201,6 +1204,98 @@ int32_t lcty_db_expand_locus(lcty_ctx* ctx, const char* locus, uint32_t inner_st
                              const uint32_t* expansions, uint32_t moving_window, lcty_expand_out* out);
 int32_t lcty_db_locus_from_vcf(lcty_ctx* ctx, const lcty_locus_vcf_in* in, const lcty_db_params* params, lcty_locus_vcf_out* out);
 void    lcty_locus_vcf_out_free(lcty_locus_vcf_out* out);
+
+/* ---- a locus's haplotypes as a VCF (locityper paf-vcf, src/command/paf_vcf.rs; lcty_pafvcf.hip) ----------------------------------------
+ * The inverse of the section above: haplotypes.fa.gz + haplotypes.paf.gz (what lcty_align_haplotypes writes) -> haplotypes.vcf.gz.
+ * Integer and byte work. Positions are 0-based inside the reference haplotype; the text adds shift + 1. A variant is the four numbers
+ * (ref_start, ref_end, hap_start, hap_end) of VarRange (202-208). Every device entry point fills the parts of one lcty_pafvcf_out it
+ * makes (the others stay NULL / 0) and the out is released with lcty_pafvcf_out_free; on an error it is left empty.
+ *
+ * lcty_pafvcf_samples (host): group_haplotypes (569-621) over names (n_seqs 0-terminated contig names) and the text of
+ *   discarded_haplotypes.txt (NULL / 0: none; DiscardedHaplotypes::load, src/seq/contigs.rs:488-528, with its chaining through left-hand
+ *   names the FASTA does not have; a line with fewer than 3 columns is LCTY_ERR_INVALID_INPUT). A name must match
+ *   ^([0-9A-Za-z][0-9A-Za-z+._|~=@^-]*?)([._][1-9])?$ (577), else LCTY_ERR_INVALID_DATA (Error::ParsingError): with a suffix sample =
+ *   prefix, slot = digit - 1 and the sample has at least 2 slots, without one slot 0; a later writer of a slot replaces an earlier one;
+ *   every contig under its own name, then under every discarded name listed behind it ('=' and '~' lines alike). The name equal to
+ *   ref_hap gives *ref_id and is no sample — unless it has a suffix: then it stays one and LCTY_PAFVCF_WARN_REF_SUFFIX is set (588-590).
+ *   ref_hap not found: LCTY_ERR_INVALID_INPUT (612-616). A '~' line sets LCTY_PAFVCF_WARN_PRUNED (convert_to_vcf 633-635). Out: the
+ *   samples sorted bytewise (618-619) as 0-terminated names, slot_off[n_samples + 1], slot_hap[n_slots] (contig index or LCTY_NONE_U32).
+ *   Called twice: sample_names = slot_off = slot_hap = NULL sizes it (*n_samples, *names_len, *n_slots).
+ * lcty_pafvcf_variants (device): process_paf (362-415), process_haplotype (276-332) and move_all_left (242-271, gap_move_left 231-239)
+ *   for all haplotypes at once, on the arrays of lcty_paf_read (id1 = query, id2 = target, CIGAR words length << 4 | BAM operation).
+ *   Only entries with the reference on one side count; with the reference as the query the items are inverted (I, S -> D; D -> I;
+ *   cigar.rs:147-158); an entry whose CIGAR lengths differ from the two sequences is skipped and counted (n_bad_len, 403-407); of the
+ *   others the LAST in file order is the haplotype's (408) — a stated difference: the reference also walks the entries it then replaces,
+ *   so an M in a replaced entry fails there and not here. A haplotype without an entry is missing (has_aln 0, counted in n_missing, 410);
+ *   the reference haplotype has an entry and no variant (371). An M or H item is LCTY_ERR_RUNTIME (293-295), a last variant that reaches
+ *   past a sequence too (325-329). Items merge as 300-310, a new variant takes one of the three forms of 313-319 — reproduced as
+ *   written, the right-padded form's quirk included (`5I1D1=` on `GG` gives (0, 1, 0, 6)). n_shifted: variants the shift moved. A stated
+ *   difference: every '=' run is compared with the bases it covers, and a run over different bases is LCTY_ERR_INVALID_DATA (the
+ *   reference writes a VCF that does not describe the haplotype). Out: var_off[n_seqs + 1], ref_start / ref_end / hap_start / hap_end
+ *   [n_variants] after the shift, has_aln[n_seqs].
+ * lcty_pafvcf_ranges (device): combine_variants (535-555) on the (ref_start, ref_end) of all variants: unique_* the sorted, deduplicated
+ *   ranges, merged_* those with every run of OVERLAPPING ranges joined (prev_end > start; ranges that touch stay apart).
+ * lcty_pafvcf_table (device): get_hap_ranges (420-460, the bisections of src/algo/bisect.rs:45-83) and the allele part of write_vcf
+ *   (473-494) for a list of ranges: allele_ix[n_ranges][n_seqs] — -1 for None: a missing haplotype, a range that starts or ends inside
+ *   one of the haplotype's variants, a slice with an N —, 0 the reference's slice, k >= 1 the k-th other allele in the order of its
+ *   first carrier in contig order. n_alleles[n_ranges] (the reference's included), and for the alleles from 1 on allele_off[n_ranges + 1]
+ *   into allele_hap (the first carrier) / allele_start / allele_len (the slice inside that haplotype). Equality is decided by the
+ *   bytes; lcty_ctx_set_knob "pafvcf_hash_bits" only narrows the hash that picks the candidates. A slice that lies outside its
+ *   haplotype (where the reference panics: the quirk above) is LCTY_ERR_RUNTIME. The variants of a haplotype must be ordered
+ *   (LCTY_ERR_INVALID_INPUT).
+ * lcty_pafvcf_text (device): the record lines of write_vcf (495-517) from a table: a range with one allele gives no line; else
+ *   chrom \t start + shift + 1 \t . \t REF \t ALT[,ALT..] \t60\t.\t.\tGT and per sample \t and its slots joined by '|', '.' for an empty
+ *   slot or a None cell. Out: merged / merged_len (no header).
+ * lcty_paf_to_vcf (device): convert_to_vcf (623-657) on buffers: the samples, the variants, the ranges, and for the merged ranges —
+ *   with_separate != 0: also for the unique ones (separate) — the table and the text behind the header of 349-357. chrom NULL: the
+ *   records are named ref_hap with shift 0; else [region_start, region_end) must be as long as the reference haplotype
+ *   (LCTY_ERR_INVALID_DATA, 639-642) and shift = region_start. Kernels: a wavefront per entry and per haplotype, a lane
+ *   per variant, a radix sort, scans and compactions, a lane per cell, a workgroup per line; no host loop over haplotypes, variants,
+ *   ranges or cells and no host copy per haplotype — but for the checks of the caller's offset arrays (seq_off, cigar_off, slot_off;
+ *   in the part-wise entry points also var_off, the variants' order and the ranges), which keep the kernels inside their buffers.
+ * Limits (LCTY_ERR_UNSUPPORTED): more than 65 535 haplotypes, a haplotype of 2^31 bases, 2^31 variants / ranges / alleles, a line of
+ *   2^32 bytes, an allele table beyond knob "pafvcf_table_mb". */
+#define LCTY_PAFVCF_WARN_REF_SUFFIX 1u   /* the reference haplotype's name has a haplotype suffix and stays in the VCF (588-590) */
+#define LCTY_PAFVCF_WARN_PRUNED     2u   /* "Haplotypes were previously pruned (~ for some lines), VCF will be inaccurate" (633-635) */
+typedef struct lcty_pafvcf_stats {
+    uint64_t n_variants, n_unique, n_merged, n_shifted, n_lines_merged, n_lines_separate, merged_bytes, separate_bytes;
+    uint32_t n_missing, n_bad_len, warn_bits, n_samples;
+    /* wall time per stage with the stream drained at its end: uploads, variants (entries, walk, shift), ranges, tables, texts (with
+     * their download), whole call */
+    double   upload_ms, variants_ms, ranges_ms, table_ms, text_ms, total_ms;
+} lcty_pafvcf_stats;
+typedef struct lcty_pafvcf_out {
+    uint32_t n_seqs, _pad0;
+    uint64_t n_variants, n_unique, n_merged, n_ranges;
+    uint64_t* var_off; uint32_t* ref_start; uint32_t* ref_end; uint32_t* hap_start; uint32_t* hap_end; uint8_t* has_aln;      /* variants */
+    uint32_t* unique_start; uint32_t* unique_end; uint32_t* merged_start; uint32_t* merged_end;                                /* ranges */
+    int32_t* allele_ix; uint32_t* n_alleles; uint64_t* allele_off; uint32_t* allele_hap; uint32_t* allele_start; uint32_t* allele_len;   /* table */
+    char* merged; uint64_t merged_len; char* separate; uint64_t separate_len;                                                  /* text */
+    lcty_pafvcf_stats stats;
+} lcty_pafvcf_out;
+
+int32_t lcty_pafvcf_samples(uint32_t n_seqs, const char* names, const char* discarded, uint64_t discarded_len, const char* ref_hap, uint32_t cap_samples,
+                            uint32_t* n_samples, char* sample_names, uint64_t cap_names, uint64_t* names_len, uint32_t* slot_off, uint32_t cap_slots,
+                            uint32_t* n_slots, uint32_t* slot_hap, uint32_t* ref_id, uint32_t* warn_bits);
+int32_t lcty_pafvcf_variants(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref_id, uint64_t n_entries,
+                             const uint32_t* id1, const uint32_t* id2, const uint64_t* cigar_off, const uint32_t* cigar, lcty_pafvcf_out* out);
+int32_t lcty_pafvcf_ranges(lcty_ctx* ctx, uint64_t n_variants, const uint32_t* ref_start, const uint32_t* ref_end, lcty_pafvcf_out* out);
+int32_t lcty_pafvcf_table(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref_id, const uint64_t* var_off,
+                          const uint32_t* ref_start, const uint32_t* ref_end, const uint32_t* hap_start, const uint32_t* hap_end, const uint8_t* has_aln,
+                          uint64_t n_ranges, const uint32_t* range_start, const uint32_t* range_end, lcty_pafvcf_out* out);
+int32_t lcty_pafvcf_text(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref_id, uint64_t n_ranges,
+                         const uint32_t* range_start, const uint32_t* range_end, const int32_t* allele_ix, const uint32_t* n_alleles,
+                         const uint64_t* allele_off, const uint32_t* allele_hap, const uint32_t* allele_start, const uint32_t* allele_len,
+                         uint32_t n_samples, const uint32_t* slot_off, const uint32_t* slot_hap, const char* chrom, uint32_t shift, lcty_pafvcf_out* out);
+int32_t lcty_paf_to_vcf(lcty_ctx* ctx, uint32_t n_seqs, const char* names, const uint8_t* seqs, const uint64_t* seq_off, const char* discarded,
+                        uint64_t discarded_len, const char* ref_hap, uint64_t n_entries, const uint32_t* id1, const uint32_t* id2,
+                        const uint64_t* cigar_off, const uint32_t* cigar, const char* chrom, uint32_t region_start, uint32_t region_end,
+                        int32_t with_separate, lcty_pafvcf_out* out);
+void    lcty_pafvcf_out_free(lcty_pafvcf_out* out);
+/* A buffer as a BGZF file (SAM specification 4.1; what htslib::bgzf::Writer gives create_vcf_writer, 341-344): blocks of at most 0xff00
+ * input bytes and the empty end-of-file block. The deflate bytes are zlib's at level 6; the inflated bytes are `data`. Host code; the
+ * writer is the one behind lcty_write_bam. */
+int32_t lcty_io_write_bgzf(const char* path, const uint8_t* data, uint64_t len);
 
 /* ---- basis haplotypes (locityper augment, the basis step: DB/loci/<locus>/haplotypes-basis[.TAG].fa.gz) ------------------------------
  * construct_dominant_set -> inner_construct_dominant_set -> Cigar::locally_similar -> find_dominating_set (src/command/augment.rs:258-396,

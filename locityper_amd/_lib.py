@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -54,6 +54,13 @@ SIGNATURES = {
     "lcty_db_expand_locus": (I32, [VP, C.c_char_p, U32, U32, U32, U32, VP, U64, U32, VP, U64, U32, VP, VP, U32, VP, U32, P(ExpandOut)]),
     "lcty_db_locus_from_vcf": (I32, [VP, P(LocusVcfIn), P(DbParams), P(LocusVcfOut)]),
     "lcty_locus_vcf_out_free": (None, [P(LocusVcfOut)]),
+    "lcty_pafvcf_samples": (I32, [U32, C.c_char_p, C.c_char_p, U64, C.c_char_p, U32, P(U32), VP, U64, P(U64), VP, U32, P(U32), VP, P(U32), P(U32)]),
+    "lcty_pafvcf_variants": (I32, [VP, U32, VP, VP, U32, U64, VP, VP, VP, VP, P(PafvcfOut)]),
+    "lcty_pafvcf_ranges": (I32, [VP, U64, VP, VP, P(PafvcfOut)]),
+    "lcty_pafvcf_table": (I32, [VP, U32, VP, VP, U32, VP, VP, VP, VP, VP, VP, U64, VP, VP, P(PafvcfOut)]),
+    "lcty_pafvcf_text": (I32, [VP, U32, VP, VP, U32, U64, VP, VP, VP, VP, VP, VP, VP, VP, U32, VP, VP, C.c_char_p, U32, P(PafvcfOut)]),
+    "lcty_paf_to_vcf": (I32, [VP, U32, C.c_char_p, VP, VP, C.c_char_p, U64, C.c_char_p, U64, VP, VP, VP, VP, C.c_char_p, U32, U32, I32, P(PafvcfOut)]),
+    "lcty_pafvcf_out_free": (None, [P(PafvcfOut)]),
     "lcty_basis_params_default": (None, [P(BasisParams)]),
     "lcty_basis_windows": (I32, [VP, U32, VP, U64, VP, VP, VP, VP, VP, VP, VP, P(BasisParams), VP, P(VP), P(BasisStats)]),
     "lcty_basis_constraints": (I32, [VP, U32, U64, VP, I32, P(U64), P(VP), P(BasisStats)]),
@@ -178,6 +185,7 @@ SIGNATURES = {
     "lcty_io_read_file": (I32, [C.c_char_p, P(VP), P(U64)]),
     "lcty_io_free": (None, [VP]),
     "lcty_io_write_gz": (I32, [C.c_char_p, VP, U64]),
+    "lcty_io_write_bgzf": (I32, [C.c_char_p, VP, U64]),
     "lcty_io_write_br": (I32, [C.c_char_p, VP, U64, I32, P(I32)]),
     "lcty_bg_from_json": (I32, [C.c_char_p, U64, VP, P(D)]),
     "lcty_res_to_json": (I32, [VP, VP, U32, VP, U32, VP, VP, VP, I32, D, VP, U64, P(U64)]),

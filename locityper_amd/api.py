@@ -1224,6 +1224,130 @@ def _basis_entries(entries):
     return n, id1, id2, nm, ln, off, words
 
 
+# ---- a locus's haplotypes as a VCF (locityper paf-vcf; lcty_pafvcf.hip) -------------------------------------------------------------
+def pafvcf_samples(names, ref_hap, discarded=None):
+    """lcty_pafvcf_samples (group_haplotypes): ([(sample, [contig index or None])] sorted by name, ref_id, warning bits). discarded: the
+    text of discarded_haplotypes.txt (bytes) or None."""
+    from .io import _names_blob
+    nb = _names_blob(names)
+    disc = None if discarded is None else bytes(discarded)
+    ref = ref_hap.encode() if isinstance(ref_hap, str) else bytes(ref_hap)
+    ns, nl, nslots, ref_id, warn = U32(), U64(), U32(), U32(), U32()
+    args = (len(names), nb, disc, 0 if disc is None else len(disc), ref)
+    check(lib().lcty_pafvcf_samples(*args, 0, C.byref(ns), None, 0, C.byref(nl), None, 0, C.byref(nslots), None, C.byref(ref_id), C.byref(warn)))
+    blob = np.zeros(max(int(nl.value), 1), dtype=np.uint8)
+    off = np.zeros(ns.value + 1, dtype=np.uint32); hap = np.zeros(max(nslots.value, 1), dtype=np.uint32)
+    check(lib().lcty_pafvcf_samples(*args, ns.value, C.byref(ns), blob.ctypes.data, len(blob), C.byref(nl), off.ctypes.data, len(hap), C.byref(nslots),
+                                    hap.ctypes.data, C.byref(ref_id), C.byref(warn)))
+    sn = blob[:int(nl.value)].tobytes().split(b"\0")[:-1]
+    groups = [(sn[i], [None if int(h) == cdefs.NONE_U32 else int(h) for h in hap[off[i]:off[i + 1]]]) for i in range(ns.value)]
+    return groups, int(ref_id.value), int(warn.value)
+
+
+def _pafvcf_seqs(seqs, seq_off):
+    return np.ascontiguousarray(seqs, dtype=np.uint8), np.ascontiguousarray(seq_off, dtype=np.uint64)
+
+
+def _pafvcf_arr(p, n, dt):
+    return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if n and p else np.zeros(0, dtype=dt)
+
+
+def pafvcf_variants(ctx, seqs, seq_off, ref_id, entries):
+    """lcty_pafvcf_variants: entries = [(id1 query, id2 target, raw CIGAR words, ...)] (io.paf_read). Returns a dict: var_off, ref_start,
+    ref_end, hap_start, hap_end (after the left shift), has_aln, n_missing, n_bad_len, n_shifted."""
+    sq, so = _pafvcf_seqs(seqs, seq_off)
+    n, id1, id2, _nm, _ln, off, words = _basis_entries([(e[0], e[1], e[2], 0, 0) for e in entries]) if entries else \
+        (0, np.zeros(1, np.uint32), np.zeros(1, np.uint32), None, None, np.zeros(1, np.uint64), np.zeros(1, np.uint32))
+    o = cdefs.PafvcfOut()
+    check(lib().lcty_pafvcf_variants(ctx._h, len(so) - 1, sq.ctypes.data, so.ctypes.data, ref_id, n, id1.ctypes.data, id2.ctypes.data, off.ctypes.data,
+                                     words.ctypes.data, C.byref(o)))
+    try:
+        nv = int(o.n_variants)
+        out = {k: _pafvcf_arr(getattr(o, k), nv, np.uint32) for k in ("ref_start", "ref_end", "hap_start", "hap_end")}
+        out.update(var_off=_pafvcf_arr(o.var_off, o.n_seqs + 1, np.uint64), has_aln=_pafvcf_arr(o.has_aln, o.n_seqs, np.uint8),
+                   n_missing=int(o.stats.n_missing), n_bad_len=int(o.stats.n_bad_len), n_shifted=int(o.stats.n_shifted))
+        return out
+    finally:
+        lib().lcty_pafvcf_out_free(C.byref(o))
+
+
+def pafvcf_ranges(ctx, ref_start, ref_end):
+    """lcty_pafvcf_ranges: (unique ranges [n][2], merged ranges [m][2])."""
+    rs = np.ascontiguousarray(ref_start, dtype=np.uint32); re_ = np.ascontiguousarray(ref_end, dtype=np.uint32)
+    o = cdefs.PafvcfOut()
+    check(lib().lcty_pafvcf_ranges(ctx._h, len(rs), rs.ctypes.data, re_.ctypes.data, C.byref(o)))
+    try:
+        nu, nm = int(o.n_unique), int(o.n_merged)
+        return (np.stack([_pafvcf_arr(o.unique_start, nu, np.uint32), _pafvcf_arr(o.unique_end, nu, np.uint32)], axis=1),
+                np.stack([_pafvcf_arr(o.merged_start, nm, np.uint32), _pafvcf_arr(o.merged_end, nm, np.uint32)], axis=1))
+    finally:
+        lib().lcty_pafvcf_out_free(C.byref(o))
+
+
+def pafvcf_table(ctx, seqs, seq_off, ref_id, variants, ranges):
+    """lcty_pafvcf_table: variants = the dict of pafvcf_variants, ranges [n][2]. Returns a dict: allele_ix [n_ranges][n_seqs] (-1 = None),
+    n_alleles, allele_off, allele_hap, allele_start, allele_len."""
+    sq, so = _pafvcf_seqs(seqs, seq_off)
+    v = {k: np.ascontiguousarray(variants[k], dtype=np.uint32) for k in ("ref_start", "ref_end", "hap_start", "hap_end")}
+    vo = np.ascontiguousarray(variants["var_off"], dtype=np.uint64); has = np.ascontiguousarray(variants["has_aln"], dtype=np.uint8)
+    rg = np.ascontiguousarray(ranges, dtype=np.uint32).reshape(-1, 2)
+    r0, r1 = np.ascontiguousarray(rg[:, 0]), np.ascontiguousarray(rg[:, 1])
+    o = cdefs.PafvcfOut()
+    check(lib().lcty_pafvcf_table(ctx._h, len(so) - 1, sq.ctypes.data, so.ctypes.data, ref_id, vo.ctypes.data, v["ref_start"].ctypes.data, v["ref_end"].ctypes.data,
+                                  v["hap_start"].ctypes.data, v["hap_end"].ctypes.data, has.ctypes.data, len(rg), r0.ctypes.data, r1.ctypes.data, C.byref(o)))
+    try:
+        nr, ns = int(o.n_ranges), int(o.n_seqs)
+        aoff = _pafvcf_arr(o.allele_off, nr + 1, np.uint64)
+        na = int(aoff[-1]) if nr else 0
+        return {"allele_ix": _pafvcf_arr(o.allele_ix, nr * ns, np.int32).reshape(nr, ns), "n_alleles": _pafvcf_arr(o.n_alleles, nr, np.uint32),
+                "allele_off": aoff if nr else np.zeros(1, np.uint64), "allele_hap": _pafvcf_arr(o.allele_hap, na, np.uint32),
+                "allele_start": _pafvcf_arr(o.allele_start, na, np.uint32), "allele_len": _pafvcf_arr(o.allele_len, na, np.uint32)}
+    finally:
+        lib().lcty_pafvcf_out_free(C.byref(o))
+
+
+def pafvcf_text(ctx, seqs, seq_off, ref_id, ranges, table, groups, chrom, shift=0):
+    """lcty_pafvcf_text: the record lines (bytes, no header) of a table (the dict of pafvcf_table) for the samples of pafvcf_samples."""
+    sq, so = _pafvcf_seqs(seqs, seq_off)
+    rg = np.ascontiguousarray(ranges, dtype=np.uint32).reshape(-1, 2)
+    r0, r1 = np.ascontiguousarray(rg[:, 0]), np.ascontiguousarray(rg[:, 1])
+    ix = np.ascontiguousarray(table["allele_ix"], dtype=np.int32); na = np.ascontiguousarray(table["n_alleles"], dtype=np.uint32)
+    ao = np.ascontiguousarray(table["allele_off"], dtype=np.uint64)
+    ah, as_, al = (np.ascontiguousarray(table[k], dtype=np.uint32) for k in ("allele_hap", "allele_start", "allele_len"))
+    slot_off = np.zeros(len(groups) + 1, dtype=np.uint32)
+    np.cumsum([len(g[1]) for g in groups], out=slot_off[1:])
+    slot_hap = np.array([cdefs.NONE_U32 if h is None else h for g in groups for h in g[1]] + [0], dtype=np.uint32)
+    c = chrom.encode() if isinstance(chrom, str) else bytes(chrom)
+    o = cdefs.PafvcfOut()
+    check(lib().lcty_pafvcf_text(ctx._h, len(so) - 1, sq.ctypes.data, so.ctypes.data, ref_id, len(rg), r0.ctypes.data, r1.ctypes.data, ix.ctypes.data, na.ctypes.data,
+                                 ao.ctypes.data, ah.ctypes.data, as_.ctypes.data, al.ctypes.data, len(groups), slot_off.ctypes.data, slot_hap.ctypes.data, c, shift,
+                                 C.byref(o)))
+    try:
+        return C.string_at(o.merged, o.merged_len) if o.merged_len else b""
+    finally:
+        lib().lcty_pafvcf_out_free(C.byref(o))
+
+
+def paf_to_vcf(ctx, names, seqs, seq_off, entries, ref_hap, discarded=None, region=None, with_separate=True):
+    """lcty_paf_to_vcf: (merged text, separate text or None, stats dict). region: None or (chrom, start, end)."""
+    from .io import _names_blob
+    sq, so = _pafvcf_seqs(seqs, seq_off)
+    n, id1, id2, _nm, _ln, off, words = _basis_entries([(e[0], e[1], e[2], 0, 0) for e in entries]) if entries else \
+        (0, np.zeros(1, np.uint32), np.zeros(1, np.uint32), None, None, np.zeros(1, np.uint64), np.zeros(1, np.uint32))
+    disc = None if discarded is None else bytes(discarded)
+    ref = ref_hap.encode() if isinstance(ref_hap, str) else bytes(ref_hap)
+    chrom, start, end = (None, 0, 0) if region is None else region
+    if chrom is not None and isinstance(chrom, str):
+        chrom = chrom.encode()
+    o = cdefs.PafvcfOut()
+    check(lib().lcty_paf_to_vcf(ctx._h, len(names), _names_blob(names), sq.ctypes.data, so.ctypes.data, disc, 0 if disc is None else len(disc), ref, n,
+                                id1.ctypes.data, id2.ctypes.data, off.ctypes.data, words.ctypes.data, chrom, start, end, int(with_separate), C.byref(o)))
+    try:
+        return C.string_at(o.merged, o.merged_len), (C.string_at(o.separate, o.separate_len) if with_separate else None), o.stats.as_dict()
+    finally:
+        lib().lcty_pafvcf_out_free(C.byref(o))
+
+
 def _leave_out_mask(n_alleles, leave_out):
     if leave_out is None or len(leave_out) == 0:
         return None

@@ -161,6 +161,24 @@ class PanvcfOut(C.Structure):
                 ("stats", PanvcfStats)]
 
 
+# ---- a locus's haplotypes as a VCF (lcty_pafvcf.hip) ----
+PAFVCF_WARN_REF_SUFFIX, PAFVCF_WARN_PRUNED = 1, 2
+
+
+class PafvcfStats(_Dictable):
+    _fields_ = [(n, C.c_uint64) for n in ("n_variants", "n_unique", "n_merged", "n_shifted", "n_lines_merged", "n_lines_separate", "merged_bytes",
+                                          "separate_bytes")] + \
+               [(n, C.c_uint32) for n in ("n_missing", "n_bad_len", "warn_bits", "n_samples")] + \
+               [(n, C.c_double) for n in ("upload_ms", "variants_ms", "ranges_ms", "table_ms", "text_ms", "total_ms")]
+
+
+class PafvcfOut(C.Structure):
+    _fields_ = [("n_seqs", C.c_uint32), ("_pad0", C.c_uint32)] + [(n, C.c_uint64) for n in ("n_variants", "n_unique", "n_merged", "n_ranges")] + \
+               [(n, C.c_void_p) for n in ("var_off", "ref_start", "ref_end", "hap_start", "hap_end", "has_aln", "unique_start", "unique_end", "merged_start",
+                                          "merged_end", "allele_ix", "n_alleles", "allele_off", "allele_hap", "allele_start", "allele_len")] + \
+               [("merged", C.c_void_p), ("merged_len", C.c_uint64), ("separate", C.c_void_p), ("separate_len", C.c_uint64), ("stats", PafvcfStats)]
+
+
 class ExpandOut(_Dictable):
     _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("attempt", C.c_int32), ("allowed_expansion", C.c_uint32), ("n_attempts", C.c_uint32),
                 ("crop_bits", C.c_uint32), ("total_ms", C.c_double)]

@@ -21,6 +21,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
 
@@ -441,6 +442,15 @@ int32_t lcty_io_read_file(const char* path, uint8_t** data, uint64_t* len) {
 }
 
 void lcty_io_free(void* p) { free(p); }
+
+int32_t lcty_io_write_bgzf(const char* path, const uint8_t* data, uint64_t len) {
+    return guarded([&] {
+        if (!path || (len && !data)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        BgzfOut out(path);
+        out.write(data, len);
+        out.close();
+    });
+}
 
 int32_t lcty_io_write_gz(const char* path, const uint8_t* data, uint64_t len) {
     return guarded([&] {

@@ -22,6 +22,12 @@ def write_gz(path, data):
     check(lib().lcty_io_write_gz(str(path).encode(), buf, len(buf)))
 
 
+def write_bgzf(path, data):
+    """lcty_io_write_bgzf: `data` as a BGZF file (blocks of at most 0xff00 bytes and the end-of-file block)."""
+    buf = bytes(data)
+    check(lib().lcty_io_write_bgzf(str(path).encode(), buf, len(buf)))
+
+
 def write_br(path, data, quality=5):
     """lcty_io_write_br: a brotli stream of `data` (the reference's `.csv.br` debug tables); returns True when the stream is STORED in
     uncompressed meta-blocks (no libbrotlienc on this system, or quality < 0)."""
