@@ -4,10 +4,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -114,6 +116,23 @@ struct DevBuf {
         if (n) LCTY_HIP(hipMemsetAsync(p, 0, n * sizeof(T), s));
     }
 };
+
+// Arrays handed to the caller of the C interface, who frees them with free(): a copy of n host values, n values of a device buffer
+// (asynchronous: the caller synchronises s before reading). n == 0 still gives a pointer.
+template <typename T> T* malloc_copy(const T* p, size_t n) {
+    T* out = static_cast<T*>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
+    if (!out) throw std::bad_alloc();
+    if (n) memcpy(out, p, n * sizeof(T));
+    return out;
+}
+template <typename T> T* malloc_from(const DevBuf<T>& d, size_t n, hipStream_t s) {
+    T* out = static_cast<T*>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
+    if (!out) throw std::bad_alloc();
+    try { d.download(out, n, s); } catch (...) { free(out); throw; }
+    return out;
+}
+// workgroups of `per` items that cover n
+inline uint32_t blocks_of(uint64_t n, uint32_t per) { return static_cast<uint32_t>((n + per - 1) / per); }
 
 // One non-trivial read of one solver chain / a location beyond its second (lcty_solve_kernels.hip)
 struct __attribute__((aligned(32))) ChainRec {

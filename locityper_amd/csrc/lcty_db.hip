@@ -16,6 +16,7 @@
 // matrix: popcount(x & y) over 64-bit words. The column of (hash, t) is base[hash] + t - 1, base handed out by an atomic counter over a
 // device hash table of the distinct hashes (any bijection serves: the sums are integer, their order does not matter). Columns are
 // processed in chunks so that the bit matrix keeps to a fixed budget; the u32 overlap triangle accumulates over the chunks.
+#include "lcty_bitonic.hpp"
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
 
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(64) void db_minim_walk_kernel(const uint8_t* __rest
     cnt[a] = m;
 }
 
-// One workgroup sorts one list in LDS (bitonic network over the next power of two, padded with all-ones, which sort last).
+// One workgroup sorts one list in LDS (the bitonic network of lcty_bitonic.hpp over the next power of two, padded with all-ones, which sort last).
 __global__ __launch_bounds__(1024) void db_sort_kernel(uint64_t* __restrict__ hashes, const uint64_t* __restrict__ min_off) {
     __shared__ uint64_t s[kSortCap];
     const uint32_t a = blockIdx.x;
@@ -129,16 +130,7 @@ __global__ __launch_bounds__(1024) void db_sort_kernel(uint64_t* __restrict__ ha
     while (P < n) P <<= 1;
     for (uint32_t t = threadIdx.x; t < P; t += 1024) s[t] = t < n ? v[t] : UNDEF64;
     __syncthreads();
-    for (uint32_t size = 2; size <= P; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = threadIdx.x; t < P / 2; t += 1024) {
-                const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool asc = (lo & size) == 0;
-                const uint64_t x = s[lo], y = s[hi];
-                if ((x > y) == asc) { s[lo] = y; s[hi] = x; }
-            }
-            __syncthreads();
-        }
+    bitonic_sort_lds<1024>(P, BitonicKeys{s});
     for (uint32_t t = threadIdx.x; t < n; t += 1024) v[t] = s[t];
 }
 

@@ -30,6 +30,7 @@
 //                         the sum over k is right whatever the instruction's internal k order is.
 //   gram_finish_kernel    score = C - S * 2^-F (+ the residual rows' f64 partial).
 #include "lcty_objects.hpp"
+#include "lcty_scan.hpp"
 
 namespace lcty {
 
@@ -98,8 +99,7 @@ __global__ __launch_bounds__(256) void gram_levels_kernel(const double* __restri
     // ---- columns of the block: prefix over its rows, a whole number of 32-column words from the global counter
     if (wave == 0) {
         const uint32_t n0 = ncol[2 * lane], n1 = ncol[2 * lane + 1];
-        uint32_t incl = n0 + n1;
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (lane >= static_cast<uint32_t>(o)) incl += up; }
+        const uint32_t incl = wave_scan_incl(n0 + n1, AddOp{});
         off[2 * lane] = incl - n0 - n1; off[2 * lane + 1] = incl - n1;
         // sum of the rows' largest values, rows in order (reproducible)
         double c = 0.0;

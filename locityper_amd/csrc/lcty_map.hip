@@ -34,6 +34,7 @@
 // then records, with the host's prefix sums in between (map_emit_two_pass, lcty_map_internal.hpp).
 #include <algorithm>
 
+#include "lcty_bitonic.hpp"
 #include "lcty_map_internal.hpp"
 
 namespace lcty {
@@ -78,7 +79,7 @@ __device__ void map_seed_one(const MapView& V, const uint64_t m, uint64_t* keys,
         if (lane < map_n_seeds(L, k, V.stride)) sd = map_seed_at(V, off, L, lane, MAP_PER_SEED);
         const uint32_t count = sd.count;
         // places of the lanes' votes in the list (seed order); what does not fit is dropped
-        uint32_t incl = count;
+        uint32_t incl = count;                                                  // written out: wave_scan_incl changes this kernel's code
         for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (lane >= static_cast<uint32_t>(o)) incl += up; }
         const uint32_t at = incl - count;
         n_hits = min(static_cast<uint32_t>(__shfl(incl, 63)), MAP_MAX_HITS);
@@ -88,22 +89,13 @@ __device__ void map_seed_one(const MapView& V, const uint64_t m, uint64_t* keys,
             keys[at + j] = (static_cast<uint64_t>(pl.b * 2 + pl.strand) << 32) | static_cast<uint32_t>(diag + 0x80000000ll);
         }
     }
-    // ---- sort the votes (bitonic over the next power of two, padded with the largest key)
+    // ---- sort the votes (the bitonic network of lcty_bitonic.hpp over the next power of two, padded with the largest key)
     uint32_t n2 = 1;
     while (n2 < n_hits) n2 <<= 1;
     for (uint32_t i = n_hits + lane; i < n2; i += 64) keys[i] = ~0ull;
     for (uint32_t i = lane; i < 2 * MAP_MAX_BASIS; i += 64) best[i] = 0ull;
     __syncthreads();
-    for (uint32_t size = 2; size <= n2; size <<= 1)
-        for (uint32_t strd = size >> 1; strd > 0; strd >>= 1) {
-            for (uint32_t i = lane; i < n2 / 2; i += 64) {
-                const uint32_t lo = 2 * i - (i & (strd - 1)), hi = lo + strd;
-                const bool up = (lo & size) == 0;
-                const uint64_t a = keys[lo], b = keys[hi];
-                if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
+    bitonic_sort_lds<64>(n2, BitonicKeys{keys});
     // ---- per (allele, strand): the votes of its best diagonal
     for (uint32_t i = lane; i < n_hits; i += 64) {
         const uint64_t key = keys[i];

@@ -9,17 +9,17 @@
 // claims a slot (64-bit compare-and-swap on the key, linear probing). Which slot a k-mer ends up in depends on who gets there first;
 // what a lookup finds does not.
 //
-// The sort: least significant digit first, eight bits a pass, over the bytes a k-mer of this k can differ in plus the top byte (where
-// the key of a window without a k-mer differs from all of them). A pass is three steps over tiles of 4 096 pairs, a wavefront per tile:
-// the tile's count of every digit value (LDS atomics) into a [256][tiles] matrix; the exclusive prefix sums of that matrix in
-// (digit, tile) order — the first place in the output of every (digit value, tile) —; and the scatter, in which the wavefront goes
-// over its tile 64 pairs at a time, in order: the lanes that hold the same digit value find each other by eight ballots, the first of
-// them takes their places from the tile's running counter of that value (LDS), a lane's place is that plus its rank among its peers.
-// Pairs with equal digits keep their order: stable. The prefix sums are the file's own three-kernel scan (chunks of 4 096, their sums
-// scanned by the same code one level up, added back).
+// The sort (RadixSort, lcty_sort.hpp): least significant digit first, eight bits a pass, over the bytes a k-mer of this
+// k can differ in plus the top byte (where the key of a window without a k-mer differs from all of them). A pass is three steps over
+// tiles of 4 096 pairs, a wavefront per tile: the tile's count of every digit value (LDS atomics) into a [256][tiles] matrix; the
+// exclusive prefix sums of that matrix in (digit, tile) order — the first place in the output of every (digit value, tile) —; and the
+// scatter, in which the wavefront goes over its tile 64 pairs at a time, in order: the lanes that hold the same digit value find each
+// other by eight ballots, the first of them takes their places from the tile's running counter of that value (LDS), a lane's place is
+// that plus its rank among its peers. Pairs with equal digits keep their order: stable. The run starts take ScanTotal (lcty_scan.hpp).
 
 #include "lcty_common.hpp"
 #include "lcty_map_internal.hpp"
+#include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
 
 namespace lcty {
@@ -90,13 +90,13 @@ std::shared_ptr<MapIndex> build_map_index_device(lcty_locus* locus, const uint16
         win_off[b + 1] = win_off[b] + (len >= k ? len + 1 - k : 0);
     }
     const uint64_t n_windows = win_off[n_basis];
-    if (n_windows > 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "more than 2^31 k-mer places in the basis alleles");   // places and run starts are 32-bit; the sort's offsets too
+    if (n_windows >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "more than 2^31 k-mer places in the basis alleles");   // places and run starts are 32-bit; the sort's offsets too
     auto ix = std::make_shared<MapIndex>();
     ix->basis.alloc(n_basis); ix->basis.upload(basis, n_basis, s);
     ix->k = k; ix->n_basis = n_basis;
     DevBuf<uint64_t> d_win_off, keys_a, keys_b, places_a;
     DevBuf<unsigned long long> d_counts;
-    DevBuf<uint32_t> head, rank, run_start, tile_counts, tile_first, scan_tmp;
+    DevBuf<uint32_t> head, rank, run_start;
     d_win_off.alloc(n_basis + 1); d_win_off.upload(win_off.data(), n_basis + 1, s);
     d_counts.alloc(1); d_counts.zero(s);
     const size_t n = static_cast<size_t>(std::max<uint64_t>(n_windows, 1));
@@ -109,38 +109,26 @@ std::shared_ptr<MapIndex> build_map_index_device(lcty_locus* locus, const uint16
         std::vector<uint32_t> shifts;
         for (uint32_t b = 0; b < 8 && 8 * b < 2 * k; b++) shifts.push_back(8 * b);
         if (shifts.back() != 56) shifts.push_back(56);
-        // the pairs are written where an even number of passes away from (keys_b, entries): the last pass ends there
+        // the pairs are written where the sort's result (the parity of the number of passes) is (keys_b, entries)
         uint64_t* ka = keys_a.p; uint64_t* va = places_a.p; uint64_t* kb = keys_b.p; uint64_t* vb = ix->entries.p;
         if (shifts.size() % 2 == 0) { std::swap(ka, kb); std::swap(va, vb); }
         const uint32_t blocks = static_cast<uint32_t>((n_windows + 255) / 256);
         hipLaunchKernelGGL(index_pairs_kernel, dim3(blocks), dim3(256), 0, s, locus->d_seqs.p, locus->d_seq_off.p, ix->basis.p, d_win_off.p, n_basis, k,
                            n_windows, ka, va, d_counts.p);
         LCTY_HIP(hipGetLastError());
-        const uint32_t n_tiles = static_cast<uint32_t>((n_windows + SORT_TILE - 1) / SORT_TILE);
-        const uint64_t cells = 256ull * n_tiles;
-        tile_counts.alloc(cells); tile_first.alloc(cells); scan_tmp.alloc(scan_scratch_words(cells));
-        for (uint32_t shift : shifts) {
-            hipLaunchKernelGGL(sort_count_kernel, dim3(n_tiles), dim3(64), 0, s, ka, n_windows, shift, tile_counts.p, n_tiles);
-            exclusive_scan(tile_counts.p, tile_first.p, cells, scan_tmp.p, s);
-            hipLaunchKernelGGL(sort_scatter_kernel, dim3(n_tiles), dim3(64), 0, s, ka, va, kb, vb, n_windows, shift, tile_first.p, n_tiles);
-            LCTY_HIP(hipGetLastError());
-            std::swap(ka, kb); std::swap(va, vb);
-        }
+        RadixSort sort;
+        sort.run(ka, va, kb, vb, n_windows, shifts, s);
         d_counts.download(&n_invalid, 1, s);
         LCTY_HIP(hipStreamSynchronize(s));
         n_valid = static_cast<uint32_t>(n_windows - n_invalid);
     }
     if (n_valid) {
         const uint32_t blocks = (n_valid + 255) / 256;
-        head.alloc(n_valid); rank.alloc(n_valid);
+        head.alloc(n_valid);
         hipLaunchKernelGGL(index_heads_kernel, dim3(blocks), dim3(256), 0, s, keys_b.p, static_cast<uint64_t>(n_valid), head.p);
         LCTY_HIP(hipGetLastError());
-        if (scan_tmp.n < scan_scratch_words(n_valid)) scan_tmp.alloc(scan_scratch_words(n_valid));
-        exclusive_scan(head.p, rank.p, n_valid, scan_tmp.p, s);
-        uint32_t last_rank = 0, last_head = 0;
-        rank.download(&last_rank, 1, s, n_valid - 1); head.download(&last_head, 1, s, n_valid - 1);
-        LCTY_HIP(hipStreamSynchronize(s));
-        n_runs = last_rank + last_head;
+        ScanTotal scan;
+        n_runs = scan.run(head, rank, n_valid, ctx);
         run_start.alloc(n_runs);
         hipLaunchKernelGGL(index_starts_kernel, dim3(blocks), dim3(256), 0, s, head.p, rank.p, static_cast<uint64_t>(n_valid), run_start.p);
         LCTY_HIP(hipGetLastError());

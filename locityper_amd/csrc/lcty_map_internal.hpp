@@ -191,7 +191,7 @@ __device__ void map_emit_read_end(const typename Route::View& V, const uint64_t 
         }
         const bool other = keep && s != prim;                                   // the others follow the primary in slot order
         const unsigned long long om = __ballot(other);
-        uint32_t incl = other ? n : 0u;
+        uint32_t incl = other ? n : 0u;                                         // written out: wave_scan_incl costs the long-read kernels registers
         for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (lane >= static_cast<uint32_t>(o)) incl += up; }
         widest = max(widest, n);
         if (WRITE) {

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64) void map_long_chain_kernel(const LongView V) {
             const uint4* list = wg_anchors + static_cast<size_t>(g) * V.cap_g;
             uint32_t at = have ? g_bi[g] : 0u;
             const uint32_t len = have ? list[at].w >> 8 : 0u;
-            uint32_t incl = len;
+            uint32_t incl = len;                                                // written out: wave_scan_incl costs this kernel a register
             for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (lane >= static_cast<uint32_t>(o)) incl += up; }
             const uint32_t total = static_cast<uint32_t>(__shfl(static_cast<int>(incl), 63));
             const uint32_t in_batch = min(64u, n_cand - c0);

@@ -2,7 +2,8 @@
 // (group_haplotypes, 569-621), the variants of every haplotype against the reference haplotype (process_paf 362-415, process_haplotype
 // 276-332, move_all_left 242-271), the unique and the merged reference ranges (combine_variants 525-563), the allele of every haplotype
 // in every range (get_hap_ranges 420-460, write_vcf 473-494) and the text of the records (495-517). The contract of every entry point
-// is stated in the header and in DESIGN.md 5l. Positions are 0-based inside the reference haplotype.
+// is stated in the header and in DESIGN.md 5l. Positions are 0-based inside the reference haplotype. The scans (wave_scan_incl,
+// launch_scan, ScanTotal: lcty_scan.hpp) and the sort of the ranges (RadixSort: lcty_sort.hpp) are the shared ones of DESIGN.md 4.18.
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -29,8 +30,6 @@ enum { F_BADOP = 0, F_LYING = 1, F_RANGE = 2, F_SLICE = 3, F_BADID = 4, F_LONGLI
 
 struct Seqs { const uint8_t* seqs; const uint64_t* off; uint32_t n, ref_id; };
 struct Paf { const uint32_t* id1; const uint32_t* id2; const uint64_t* cigar_off; const uint32_t* cigar; uint64_t n; };
-struct LoadU32 { const uint32_t* p; __device__ uint32_t operator()(uint64_t i) const { return p[i]; } };
-struct LoadU64 { const uint64_t* p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
 struct Vars { const uint32_t* off; const uint32_t* rs; const uint32_t* re; const uint32_t* hs; const uint32_t* he; const uint8_t* has; };
 
 // One CIGAR item (length << 4 | operation, BAM numbering) of an alignment of the haplotype (query) to the reference (target), or of the
@@ -47,15 +46,6 @@ __device__ inline void item_diffs(uint32_t w, bool inv, uint32_t* rd, uint32_t* 
     case 0: *rd = len; *qd = len; *kind = 2; break;
     default: *kind = 2; break;
     }
-}
-
-__device__ inline uint32_t wave_scan_incl_max(uint32_t x) {
-    const uint32_t lane = threadIdx.x & (WAVE - 1);
-    for (int off = 1; off < WAVE; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= uint32_t(off)) x = x > y ? x : y;
-    }
-    return x;
 }
 
 // ---- device: variants -----------------------------------------------------------------------------------------------------------------
@@ -142,9 +132,9 @@ __global__ __launch_bounds__(WG) void pafvcf_walk_kernel(Seqs S, Paf P, const ui
         uint32_t rd = 0, qd = 0, kind = 0;
         if (k < n) item_diffs(cg[k], inv, &rd, &qd, &kind);
         if (kind == 2) atomicMin(&flags[F_BADOP], h);
-        const uint32_t rpos = carry_r + wave_scan_incl_add(rd) - rd, qpos = carry_q + wave_scan_incl_add(qd) - qd;
+        const uint32_t rpos = carry_r + wave_scan_incl(rd, AddOp{}) - rd, qpos = carry_q + wave_scan_incl(qd, AddOp{}) - qd;
         const bool edit = k < n && kind == 1;
-        const uint32_t ir = wave_scan_incl_max(edit ? rpos + rd : 0u), iq = wave_scan_incl_max(edit ? qpos + qd : 0u);
+        const uint32_t ir = wave_scan_incl(edit ? rpos + rd : 0u, MaxOp{}), iq = wave_scan_incl(edit ? qpos + qd : 0u, MaxOp{});
         uint32_t prev_er = __shfl_up(ir, 1), prev_eq = __shfl_up(iq, 1);
         if (lane == 0) { prev_er = 0; prev_eq = 0; }
         prev_er = max(prev_er, carry_er); prev_eq = max(prev_eq, carry_eq);
@@ -482,7 +472,7 @@ __global__ __launch_bounds__(WG) void pafvcf_write_kernel(TextIn T, Seqs S, cons
         const uint32_t s = s0 + tid;
         int32_t v = CELL_NONE;
         const uint32_t w = s < T.n_slots ? cell_width(T, r, s, &v) : 0u;
-        const uint32_t incl = wave_scan_incl_add(w);
+        const uint32_t incl = wave_scan_incl(w, AddOp{});
         __syncthreads();
         if (lane == WAVE - 1) wsum[wave] = incl;
         __syncthreads();
@@ -502,43 +492,6 @@ __global__ __launch_bounds__(WG) void pafvcf_write_kernel(TextIn T, Seqs S, cons
 
 void sync(lcty_ctx* ctx) { LCTY_HIP(hipStreamSynchronize(ctx->stream)); }
 #define LAUNCH(kernel, grid, ...) do { hipLaunchKernelGGL(kernel, dim3 grid, dim3(WG), 0, s, __VA_ARGS__); LCTY_HIP(hipGetLastError()); } while (0)
-uint32_t blocks_of(uint64_t n, uint32_t per) { return static_cast<uint32_t>((n + per - 1) / per); }
-
-template <typename T> T* malloc_copy(const T* p, size_t n) {
-    T* out = static_cast<T*>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
-    if (!out) throw std::bad_alloc();
-    if (n) memcpy(out, p, n * sizeof(T));
-    return out;
-}
-template <typename T> T* malloc_from(const DevBuf<T>& d, size_t n, hipStream_t s) {          // the caller synchronises
-    T* out = static_cast<T*>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
-    if (!out) throw std::bad_alloc();
-    try { d.download(out, n, s); } catch (...) { free(out); throw; }
-    return out;
-}
-
-// exclusive_scan of lcty_sort.hpp with its scratch, and the total
-struct Scan32 {
-    DevBuf<uint32_t> tmp;
-    uint32_t run(const DevBuf<uint32_t>& in, DevBuf<uint32_t>& out, uint64_t n, lcty_ctx* ctx) {      // out[n + 1]: out[n] = the total
-        hipStream_t s = ctx->stream;
-        if (n >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "%llu items to scan (32-bit offsets)", static_cast<unsigned long long>(n));
-        out.alloc(n + 1);
-        uint32_t total = 0;
-        if (n) {
-            tmp.ensure(scan_scratch_words(n));
-            exclusive_scan(in.p, out.p, n, tmp.p, s);
-            uint32_t last_out = 0, last_in = 0;
-            out.download(&last_out, 1, s, n - 1); in.download(&last_in, 1, s, n - 1);
-            sync(ctx);
-            if (uint64_t(last_out) + last_in >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "more than 2^31 items (32-bit offsets)");
-            total = last_out + last_in;
-        }
-        out.upload(&total, 1, s, n);
-        sync(ctx);                                                       // `total` leaves the stack
-        return total;
-    }
-};
 
 struct DSeqs {
     DevBuf<uint8_t> seqs; DevBuf<uint64_t> off;
@@ -602,7 +555,7 @@ void variants_dev(lcty_ctx* ctx, const DSeqs& S, uint64_t n_entries, const uint3
     uint32_t* const null32 = nullptr;
     V.has.alloc(H);
     LAUNCH(pafvcf_walk_kernel<false>, (blocks_of(H, WG / WAVE)), S.view(), P, d_entry.p, d_cnt.p, null32, null32, null32, null32, null32, V.has.p, d_flags.p);
-    Scan32 scan;
+    ScanTotal scan;
     V.n = scan.run(d_cnt, V.off, H, ctx);
     uint32_t flags[F_COUNT];
     read_flags(ctx, d_flags, flags);
@@ -632,24 +585,15 @@ void ranges_dev(lcty_ctx* ctx, uint32_t n_vars, const DevBuf<uint32_t>& rs, cons
     R.nu = R.nm = 0;
     R.u_start.alloc(std::max(n_vars, 1u)); R.u_end.alloc(std::max(n_vars, 1u));
     if (!n_vars) { R.m_start.alloc(1); R.m_end.alloc(1); return; }
-    DevBuf<uint64_t> ka, kb; DevBuf<uint32_t> counts, first, tmp, head, rank, end_max;
+    DevBuf<uint64_t> ka, kb; DevBuf<uint32_t> head, rank, end_max;
     ka.alloc(n_vars); kb.alloc(n_vars);
     LAUNCH(pafvcf_keys_kernel, (blocks_of(n_vars, WG)), n_vars, rs.p, re.p, ka.p);
     std::vector<uint32_t> shifts;
     for (uint32_t half = 0; half < 2; half++)
         for (uint32_t b = 0; b < 4 && (b == 0 || (uint64_t(max_pos) >> (8 * b))); b++) shifts.push_back(32 * half + 8 * b);
-    const uint32_t n_tiles = blocks_of(n_vars, SORT_TILE);
-    const uint64_t cells = 256ull * n_tiles;
-    counts.alloc(cells); first.alloc(cells); tmp.alloc(scan_scratch_words(cells));
-    uint64_t* a = ka.p; uint64_t* b = kb.p; uint64_t* const no_vals = nullptr;
-    for (uint32_t shift : shifts) {
-        hipLaunchKernelGGL(sort_count_kernel, dim3(n_tiles), dim3(64), 0, s, a, uint64_t(n_vars), shift, counts.p, n_tiles);
-        exclusive_scan(counts.p, first.p, cells, tmp.p, s);
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3(n_tiles), dim3(64), 0, s, a, no_vals, b, no_vals, uint64_t(n_vars), shift, first.p, n_tiles);
-        LCTY_HIP(hipGetLastError());
-        std::swap(a, b);
-    }
-    Scan32 scan;
+    RadixSort sort;
+    const uint64_t* a = sort.run(ka.p, nullptr, kb.p, nullptr, n_vars, shifts, s) ? kb.p : ka.p;
+    ScanTotal scan;
     head.alloc(n_vars);
     LAUNCH(pafvcf_head_kernel, (blocks_of(n_vars, WG)), n_vars, a, head.p);
     R.nu = scan.run(head, rank, n_vars, ctx);
@@ -687,7 +631,7 @@ void table_dev(lcty_ctx* ctx, const DSeqs& S, const DVars& V, uint32_t n_ranges,
     init_flags(ctx, d_flags);
     n_pend.alloc(n_ranges); n_pend.zero(s); n_car.alloc(n_ranges); n_car.zero(s);
     LAUNCH(pafvcf_cell_kernel, (n_ranges, blocks_of(H, WG)), S.view(), V.view(), n_ranges, r_start, r_end, T.ix.p, n_pend.p, d_flags.p);
-    Scan32 scan;
+    ScanTotal scan;
     const uint32_t n_list = scan.run(n_pend, poff, n_ranges, ctx);
     uint32_t flags[F_COUNT];
     read_flags(ctx, d_flags, flags);

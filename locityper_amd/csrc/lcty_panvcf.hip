@@ -35,8 +35,6 @@ static_assert(sizeof(Seg) == 24, "Seg layout");
 
 // ---- device: scans (lcty_scan.hpp) -----------------------------------------------------------------------------------------------------
 
-struct LoadU32AsU64 { const uint32_t* p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
-struct LoadU64 { const uint64_t* p; __device__ uint64_t operator()(uint64_t i) const { return p[i]; } };
 struct LoadUniqueKmer { const uint16_t* p; __device__ uint32_t operator()(uint64_t i) const { return p[i] <= 1 ? 1u : 0u; } };     // add.rs:389
 struct LoadVarEnd { const uint32_t* pos; const uint32_t* rlen; __device__ uint64_t operator()(uint64_t i) const { return uint64_t(pos[i]) + rlen[i]; } };
 
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(COL_THREADS) void panvcf_segment_kernel(const int16
             src = allele_off[ai]; alt = static_cast<uint32_t>(allele_off[ai + 1] - src);
         }
         const long long d = mine ? static_cast<long long>(alt) - static_cast<long long>(rl) : 0;
-        const long long incl = wave_scan_incl_add(d);
+        const long long incl = wave_scan_incl(d, AddOp{});
         if (mine) {
             const uint64_t slot = s0 + rank0 + __popcll(acc & ((1ull << lane) - 1));
             if (slot < s1) {
@@ -348,13 +346,6 @@ std::vector<std::string> split_blob(const char* names, uint32_t n) {
     std::vector<std::string> out;
     const char* p = names;
     for (uint32_t i = 0; i < n; i++) { out.emplace_back(p); p += out.back().size() + 1; }
-    return out;
-}
-
-template <typename T> T* malloc_copy(const T* p, size_t n) {
-    T* out = static_cast<T*>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
-    if (!out) throw std::bad_alloc();
-    if (n) memcpy(out, p, n * sizeof(T));
     return out;
 }
 

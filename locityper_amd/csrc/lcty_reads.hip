@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "lcty_objects.hpp"
+#include "lcty_scan.hpp"
 
 using namespace lcty;
 
@@ -74,8 +75,7 @@ __global__ __launch_bounds__(1024) void good_scan_kernel(uint32_t* __restrict__ 
     for (uint32_t b0 = 0; b0 < blocks; b0 += 1024) {
         const uint32_t i = b0 + threadIdx.x;
         const uint32_t v = i < blocks ? cnt[i] : 0u;
-        uint32_t incl = v;
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if ((threadIdx.x & 63u) >= static_cast<uint32_t>(o)) incl += up; }
+        const uint32_t incl = wave_scan_incl(v, AddOp{});
         if ((threadIdx.x & 63u) == 63u) wsum[threadIdx.x >> 6] = incl;
         __syncthreads();
         uint32_t before = carry;

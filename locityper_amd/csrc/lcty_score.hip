@@ -26,6 +26,7 @@
 // (Staging a pair's records + CIGAR words through LDS with all loads in flight was measured: slower —
 //  pass 1 is instruction-issue bound, not latency bound, once the loads are grouped.)
 #include "lcty_objects.hpp"
+#include "lcty_scan.hpp"
 
 namespace lcty {
 
@@ -62,11 +63,7 @@ __device__ inline double wave_sum_f64(double v) {
 }
 // exclusive prefix sum across the wave; *total = wave sum
 __device__ inline uint32_t wave_excl_scan_u32(uint32_t v, int lane, uint32_t* total) {
-    uint32_t x = v;
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t y = static_cast<uint32_t>(__shfl_up(static_cast<int>(x), o));
-        if (lane >= o) x += y;
-    }
+    const uint32_t x = wave_scan_incl(v, AddOp{});
     *total = static_cast<uint32_t>(__shfl(static_cast<int>(x), WAVE - 1));
     return x - v;
 }

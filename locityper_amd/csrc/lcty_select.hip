@@ -12,6 +12,7 @@
 //   sort      the survivors by (key, index) in the LDS of one workgroup (bitonic, up to 8 192 of them; the default scheme keeps
 //             5 000); more than that are ordered by the host from the compacted pairs.
 // Only the kept indices travel. Equal to the host form lcty_truncate index for index (tests/helpers check_prefilter).
+#include "lcty_bitonic.hpp"
 #include "lcty_objects.hpp"
 
 namespace lcty {
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(256) void sel_compact_kernel(const uint64_t* __rest
     }
 }
 
-// the survivors by (key, index): bitonic sort of up to SORT_LDS_MAX pairs in the LDS of one workgroup; the first SEL_M indices out
+// the survivors by (key, index): bitonic sort (lcty_bitonic.hpp) of up to SORT_LDS_MAX pairs in the LDS of one workgroup; the first SEL_M indices out
 __global__ __launch_bounds__(1024) void sel_sort_kernel(const uint64_t* __restrict__ cand_key, const uint64_t* __restrict__ cand_ix,
                                                         unsigned long long* __restrict__ ctl, uint64_t* __restrict__ out_ix) {
     extern __shared__ __align__(16) uint8_t smem[];
@@ -177,19 +178,7 @@ __global__ __launch_bounds__(1024) void sel_sort_kernel(const uint64_t* __restri
     uint32_t* ix = reinterpret_cast<uint32_t*>(key + N);
     for (uint32_t i = threadIdx.x; i < N; i += 1024) { key[i] = i < c ? cand_key[i] : ~0ull; ix[i] = i < c ? static_cast<uint32_t>(cand_ix[i]) : 0xFFFFFFFFu; }
     __syncthreads();
-    for (uint32_t size = 2; size <= N; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t t = threadIdx.x; t < N / 2; t += 1024) {
-                const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const uint64_t ka = key[lo], kb = key[hi];
-                const uint32_t ia = ix[lo], ib = ix[hi];
-                const bool a_after_b = ka > kb || (ka == kb && ia > ib);
-                if (a_after_b == up) { key[lo] = kb; key[hi] = ka; ix[lo] = ib; ix[hi] = ia; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_lds<1024>(N, BitonicKeyIx{key, ix});
     const uint64_t m = ctl[SEL_M];
     for (uint32_t i = threadIdx.x; i < m && i < c; i += 1024) out_ix[i] = ix[i];
 }

@@ -526,6 +526,7 @@ __global__ __launch_bounds__(64, WPS) void transfer_kernel(const LocusView L, co
                 const bool fresh = alive && kind == 3;
                 const unsigned long long fresh_mask = __ballot(fresh);
                 // slots and CIGAR space in lane order
+                // written out: wave_scan_incl changes this kernel's code
                 uint32_t my_words = fresh ? out.n : 0u, word_at = my_words;
                 for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(word_at, o); if (lane >= static_cast<uint32_t>(o)) word_at += v; }
                 const uint32_t words_total = __shfl(word_at, 63);
