@@ -32,6 +32,10 @@ extern "C" {
 #define LCTY_ERR_RUNTIME       3   /* Error::RuntimeError */
 #define LCTY_ERR_SOLVER        4   /* Error::Solver       */
 #define LCTY_ERR_UNSUPPORTED   5   /* shape outside what this build handles (fails loudly, never silently) */
+/* Results the library allocates (the locus-file stages from "locus database build" down: an out struct with arrays, or out pointers
+ * with their lengths): ON ANY NON-ZERO STATUS THE OUT STRUCT IS ALL ZERO, EVERY OUT POINTER IS NULL AND ITS LENGTH 0, AND NOTHING IS
+ * LEAKED. The arrays appear in the caller's struct only when the call can no longer fail; the *_free of the struct (lcty_io_free for
+ * a lone pointer) takes a zeroed one as well. */
 
 /* ---- constants of the path -------------------------------------------- */
 #define LCTY_GC_BINS        101    /* src/bg/depth.rs:42 */
@@ -964,6 +968,12 @@ int32_t lcty_bg_to_json(const lcty_bg* bg, double read_len, uint32_t ploidy, cha
  * expansion, ref.bed: lcty_db_locus_from_vcf; haplotypes.paf.gz: lcty_align_haplotypes; prune: lcty_db_prune_locus, all further down.)
  * Integer work throughout: every output equals the reference's bit for bit (the f64 divergence is one IEEE division of two u32).
  *
+ * A HAPLOTYPE SET (n_seqs, seqs, seq_off), here and in every section below: the sequences back to back in seqs, sequence a at
+ *   [seq_off[a], seq_off[a + 1]). seq_off[0] MUST BE 0 and the offsets ascend; seqs may be NULL only when no sequence has a base.
+ *   Anything else is LCTY_ERR_INVALID_INPUT, as is a count below what the call needs. A sequence too long for the stage's kernels, or
+ *   too many sequences, is LCTY_ERR_UNSUPPORTED: below 2^31 bases here, below 2^28 for the aligner, below 0x7FFFFFF0 and at most
+ *   65 535 haplotypes for paf-vcf; prune has no bound. The offsets are checked before a base is read or sent to the device.
+ *
  * lcty_db_minimizers: kmers::minimizers::<u64, _, NON_CANONICAL> + sort_unstable per sequence (src/seq/kmers.rs:265-331,
  *   src/seq/minim_div.rs:53-61): the sorted HASHES (fast_hash, kmers.rs:93-103) of the minimizers, one per minimizer position, so
  *   a list is a multiset. 1 <= k <= 32: the reference asserts k <= 31 in debug builds only; at 32 the mask is the whole word (the
@@ -1209,7 +1219,7 @@ void    lcty_locus_vcf_out_free(lcty_locus_vcf_out* out);
  * The inverse of the section above: haplotypes.fa.gz + haplotypes.paf.gz (what lcty_align_haplotypes writes) -> haplotypes.vcf.gz.
  * Integer and byte work. Positions are 0-based inside the reference haplotype; the text adds shift + 1. A variant is the four numbers
  * (ref_start, ref_end, hap_start, hap_end) of VarRange (202-208). Every device entry point fills the parts of one lcty_pafvcf_out it
- * makes (the others stay NULL / 0) and the out is released with lcty_pafvcf_out_free; on an error it is left empty.
+ * makes (the others stay NULL / 0) and the out is released with lcty_pafvcf_out_free.
  *
  * lcty_pafvcf_samples (host): group_haplotypes (569-621) over names (n_seqs 0-terminated contig names) and the text of
  *   discarded_haplotypes.txt (NULL / 0: none; DiscardedHaplotypes::load, src/seq/contigs.rs:488-528, with its chaining through left-hand

@@ -973,13 +973,19 @@ def db_params(**kw):
     return p
 
 
-def _seq_arrays(seqs, seq_off):
+def _haps(seqs, seq_off):
+    """A haplotype set as the C interface takes it: the bases back to back and the offsets, seq_off[0] = 0."""
     return np.ascontiguousarray(seqs, dtype=np.uint8), np.ascontiguousarray(seq_off, dtype=np.uint64)
+
+
+def _take(ptr, n, dtype):
+    """A copy of the n values at ptr (none for a null pointer)."""
+    return np.frombuffer(C.string_at(ptr, n * np.dtype(dtype).itemsize), dtype=dtype).copy() if n and ptr else np.zeros(0, dtype=dtype)
 
 
 def db_minimizers(ctx, seqs, seq_off, k=15, w=15):
     """lcty_db_minimizers: (min_off[n + 1], sorted minimizer hashes of every sequence concatenated, stats dict)."""
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     n = len(off) - 1
     moff = np.zeros(n + 1, dtype=np.uint64)
     h, st = VP(), cdefs.DbStats()
@@ -994,7 +1000,7 @@ def db_minimizers(ctx, seqs, seq_off, k=15, w=15):
 
 def db_divergences(ctx, seqs, seq_off, k=15, w=15, with_f64=True):
     """lcty_db_divergences: (uniq u32 triangle, diverg f64 triangle or None, check dict, stats dict), pairs in the order rows i, then j > i."""
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     n = len(off) - 1
     npairs = max(n * (n - 1) // 2, 0)
     uniq = np.zeros(max(npairs, 1), dtype=np.uint32)
@@ -1008,7 +1014,7 @@ def db_divergences(ctx, seqs, seq_off, k=15, w=15, with_f64=True):
 
 def db_off_target(ctx, seqs, seq_off, counts, cnt_off, k, counter_bytes, ref_seq, ref_counts):
     """lcty_db_off_target: (off-target counts u16 laid out as `counts`, warn bits, stats dict)."""
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     cnt = np.ascontiguousarray(counts, dtype=np.uint16)
     coff = np.ascontiguousarray(cnt_off, dtype=np.uint64)
     ref = np.ascontiguousarray(ref_seq, dtype=np.uint8)
@@ -1023,7 +1029,7 @@ def db_off_target(ctx, seqs, seq_off, counts, cnt_off, k, counter_bytes, ref_seq
 def db_discard_identical(names, seqs, seq_off):
     """lcty_db_discard_identical: (kept input indices, {kept index: [names folded into it]}, text of discarded_haplotypes.txt — b"" = no file)."""
     from .io import _names_blob
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     n = len(off) - 1
     blob = _names_blob(names)
     kept = np.zeros(max(n, 1), dtype=np.uint32); owner = np.zeros(max(n, 1), dtype=np.uint32)
@@ -1042,7 +1048,7 @@ def db_build_locus(ctx, names, seqs, seq_off, ref_seq=None, counts=None, cnt_off
     """lcty_db_build_locus: process_alleles on buffers. counts / cnt_off: one block of n + 1 contigs, the reference sequence last.
     Returns a dict: fasta, kmers, distances, discarded (bytes, uncompressed), kept, warn_bits, check, stats."""
     from .io import _names_blob
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     p = params if params is not None else db_params()
     ref = np.ascontiguousarray(ref_seq, dtype=np.uint8) if ref_seq is not None else None
     cnt = np.ascontiguousarray(counts, dtype=np.uint16) if counts is not None else None
@@ -1121,8 +1127,7 @@ def panvcf_reconstruct(ctx, contig, ref_start, ref_end, ref_seq, recs, gt, names
                                         ao.ctypes.data, ab.ctypes.data, g.shape[1], g.ctypes.data, _names_blob(names), unknown_frac, int(overlaps_allowed),
                                         C.byref(o)))
     try:
-        def arr(p, n, dt):
-            return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+        arr = _take
         off = arr(o.seq_off, o.n_seqs + 1, np.uint64)
         return {"names": [x.decode() for x in C.string_at(o.names, o.names_len).split(b"\0")[:-1]], "seqs": arr(o.seqs, int(off[-1]), np.uint8),
                 "seq_off": off, "kept_cols": arr(o.kept_cols, o.n_seqs, np.uint32), "col_unknown": arr(o.col_unknown, o.n_cols, np.uint32),
@@ -1244,18 +1249,10 @@ def pafvcf_samples(names, ref_hap, discarded=None):
     return groups, int(ref_id.value), int(warn.value)
 
 
-def _pafvcf_seqs(seqs, seq_off):
-    return np.ascontiguousarray(seqs, dtype=np.uint8), np.ascontiguousarray(seq_off, dtype=np.uint64)
-
-
-def _pafvcf_arr(p, n, dt):
-    return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if n and p else np.zeros(0, dtype=dt)
-
-
 def pafvcf_variants(ctx, seqs, seq_off, ref_id, entries):
     """lcty_pafvcf_variants: entries = [(id1 query, id2 target, raw CIGAR words, ...)] (io.paf_read). Returns a dict: var_off, ref_start,
     ref_end, hap_start, hap_end (after the left shift), has_aln, n_missing, n_bad_len, n_shifted."""
-    sq, so = _pafvcf_seqs(seqs, seq_off)
+    sq, so = _haps(seqs, seq_off)
     n, id1, id2, _nm, _ln, off, words = _basis_entries([(e[0], e[1], e[2], 0, 0) for e in entries]) if entries else \
         (0, np.zeros(1, np.uint32), np.zeros(1, np.uint32), None, None, np.zeros(1, np.uint64), np.zeros(1, np.uint32))
     o = cdefs.PafvcfOut()
@@ -1263,8 +1260,8 @@ def pafvcf_variants(ctx, seqs, seq_off, ref_id, entries):
                                      words.ctypes.data, C.byref(o)))
     try:
         nv = int(o.n_variants)
-        out = {k: _pafvcf_arr(getattr(o, k), nv, np.uint32) for k in ("ref_start", "ref_end", "hap_start", "hap_end")}
-        out.update(var_off=_pafvcf_arr(o.var_off, o.n_seqs + 1, np.uint64), has_aln=_pafvcf_arr(o.has_aln, o.n_seqs, np.uint8),
+        out = {k: _take(getattr(o, k), nv, np.uint32) for k in ("ref_start", "ref_end", "hap_start", "hap_end")}
+        out.update(var_off=_take(o.var_off, o.n_seqs + 1, np.uint64), has_aln=_take(o.has_aln, o.n_seqs, np.uint8),
                    n_missing=int(o.stats.n_missing), n_bad_len=int(o.stats.n_bad_len), n_shifted=int(o.stats.n_shifted))
         return out
     finally:
@@ -1278,8 +1275,8 @@ def pafvcf_ranges(ctx, ref_start, ref_end):
     check(lib().lcty_pafvcf_ranges(ctx._h, len(rs), rs.ctypes.data, re_.ctypes.data, C.byref(o)))
     try:
         nu, nm = int(o.n_unique), int(o.n_merged)
-        return (np.stack([_pafvcf_arr(o.unique_start, nu, np.uint32), _pafvcf_arr(o.unique_end, nu, np.uint32)], axis=1),
-                np.stack([_pafvcf_arr(o.merged_start, nm, np.uint32), _pafvcf_arr(o.merged_end, nm, np.uint32)], axis=1))
+        return (np.stack([_take(o.unique_start, nu, np.uint32), _take(o.unique_end, nu, np.uint32)], axis=1),
+                np.stack([_take(o.merged_start, nm, np.uint32), _take(o.merged_end, nm, np.uint32)], axis=1))
     finally:
         lib().lcty_pafvcf_out_free(C.byref(o))
 
@@ -1287,7 +1284,7 @@ def pafvcf_ranges(ctx, ref_start, ref_end):
 def pafvcf_table(ctx, seqs, seq_off, ref_id, variants, ranges):
     """lcty_pafvcf_table: variants = the dict of pafvcf_variants, ranges [n][2]. Returns a dict: allele_ix [n_ranges][n_seqs] (-1 = None),
     n_alleles, allele_off, allele_hap, allele_start, allele_len."""
-    sq, so = _pafvcf_seqs(seqs, seq_off)
+    sq, so = _haps(seqs, seq_off)
     v = {k: np.ascontiguousarray(variants[k], dtype=np.uint32) for k in ("ref_start", "ref_end", "hap_start", "hap_end")}
     vo = np.ascontiguousarray(variants["var_off"], dtype=np.uint64); has = np.ascontiguousarray(variants["has_aln"], dtype=np.uint8)
     rg = np.ascontiguousarray(ranges, dtype=np.uint32).reshape(-1, 2)
@@ -1297,18 +1294,18 @@ def pafvcf_table(ctx, seqs, seq_off, ref_id, variants, ranges):
                                   v["hap_start"].ctypes.data, v["hap_end"].ctypes.data, has.ctypes.data, len(rg), r0.ctypes.data, r1.ctypes.data, C.byref(o)))
     try:
         nr, ns = int(o.n_ranges), int(o.n_seqs)
-        aoff = _pafvcf_arr(o.allele_off, nr + 1, np.uint64)
+        aoff = _take(o.allele_off, nr + 1, np.uint64)
         na = int(aoff[-1]) if nr else 0
-        return {"allele_ix": _pafvcf_arr(o.allele_ix, nr * ns, np.int32).reshape(nr, ns), "n_alleles": _pafvcf_arr(o.n_alleles, nr, np.uint32),
-                "allele_off": aoff if nr else np.zeros(1, np.uint64), "allele_hap": _pafvcf_arr(o.allele_hap, na, np.uint32),
-                "allele_start": _pafvcf_arr(o.allele_start, na, np.uint32), "allele_len": _pafvcf_arr(o.allele_len, na, np.uint32)}
+        return {"allele_ix": _take(o.allele_ix, nr * ns, np.int32).reshape(nr, ns), "n_alleles": _take(o.n_alleles, nr, np.uint32),
+                "allele_off": aoff if nr else np.zeros(1, np.uint64), "allele_hap": _take(o.allele_hap, na, np.uint32),
+                "allele_start": _take(o.allele_start, na, np.uint32), "allele_len": _take(o.allele_len, na, np.uint32)}
     finally:
         lib().lcty_pafvcf_out_free(C.byref(o))
 
 
 def pafvcf_text(ctx, seqs, seq_off, ref_id, ranges, table, groups, chrom, shift=0):
     """lcty_pafvcf_text: the record lines (bytes, no header) of a table (the dict of pafvcf_table) for the samples of pafvcf_samples."""
-    sq, so = _pafvcf_seqs(seqs, seq_off)
+    sq, so = _haps(seqs, seq_off)
     rg = np.ascontiguousarray(ranges, dtype=np.uint32).reshape(-1, 2)
     r0, r1 = np.ascontiguousarray(rg[:, 0]), np.ascontiguousarray(rg[:, 1])
     ix = np.ascontiguousarray(table["allele_ix"], dtype=np.int32); na = np.ascontiguousarray(table["n_alleles"], dtype=np.uint32)
@@ -1331,7 +1328,7 @@ def pafvcf_text(ctx, seqs, seq_off, ref_id, ranges, table, groups, chrom, shift=
 def paf_to_vcf(ctx, names, seqs, seq_off, entries, ref_hap, discarded=None, region=None, with_separate=True):
     """lcty_paf_to_vcf: (merged text, separate text or None, stats dict). region: None or (chrom, start, end)."""
     from .io import _names_blob
-    sq, so = _pafvcf_seqs(seqs, seq_off)
+    sq, so = _haps(seqs, seq_off)
     n, id1, id2, _nm, _ln, off, words = _basis_entries([(e[0], e[1], e[2], 0, 0) for e in entries]) if entries else \
         (0, np.zeros(1, np.uint32), np.zeros(1, np.uint32), None, None, np.zeros(1, np.uint64), np.zeros(1, np.uint32))
     disc = None if discarded is None else bytes(discarded)
@@ -1440,7 +1437,7 @@ def basis_tag(params=None, leave_out_names=()):
 def basis_fasta(names, seqs, seq_off, ids):
     """The text of haplotypes-basis.TAG.fa (lcty_fasta_write_text over the chosen haplotypes, in id order; io.write_gz makes the .gz)."""
     from .io import fasta_text
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     parts = [sq[int(off[i]):int(off[i + 1])] for i in ids]
     o = np.zeros(len(parts) + 1, dtype=np.uint64)
     np.cumsum([len(x) for x in parts], out=o[1:])
@@ -1476,15 +1473,11 @@ def align_all_pairs(n_seqs):
     return r[:n], q[:n]
 
 
-def _copy(ptr, count, dt):
-    return np.frombuffer(C.string_at(ptr, count * np.dtype(dt).itemsize), dtype=dt).copy() if count else np.zeros(0, dtype=dt)
-
-
 def align_haplotypes(ctx, seqs, seq_off, ref_id, query_id, params=None, against=None):
     """lcty_align_haplotypes: (dict of per-pair arrays aligned, n_matches, aln_len, nerrs, score, best_k, um, md, cigar_off, cigar;
     stats dict). Pairs in input order; ref_id[i] is the reference and query_id[i] the query of pair i."""
     p = params if params is not None else align_params()
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     r = np.ascontiguousarray(ref_id, dtype=np.uint32); q = np.ascontiguousarray(query_id, dtype=np.uint32)
     if len(r) != len(q):
         raise ValueError("ref_id and query_id differ in length")
@@ -1494,10 +1487,10 @@ def align_haplotypes(ctx, seqs, seq_off, ref_id, query_id, params=None, against=
                                       None if ag is None else ag.ctypes.data, C.byref(p), C.byref(o), C.byref(st)))
     try:
         n = int(o.n_pairs)
-        res = {"aligned": _copy(o.aligned, n, np.uint8), "n_matches": _copy(o.n_matches, n, np.uint32), "aln_len": _copy(o.aln_len, n, np.uint32),
-               "nerrs": _copy(o.nerrs, n, np.uint32), "score": _copy(o.score, n, np.int32), "best_k": _copy(o.best_k, n, np.uint32),
-               "um": _copy(o.um, n, np.uint32), "md": _copy(o.md, n, np.float64), "cigar_off": _copy(o.cigar_off, n + 1, np.uint64)}
-        res["cigar"] = _copy(o.cigar, int(res["cigar_off"][-1]), np.uint32)
+        res = {"aligned": _take(o.aligned, n, np.uint8), "n_matches": _take(o.n_matches, n, np.uint32), "aln_len": _take(o.aln_len, n, np.uint32),
+               "nerrs": _take(o.nerrs, n, np.uint32), "score": _take(o.score, n, np.int32), "best_k": _take(o.best_k, n, np.uint32),
+               "um": _take(o.um, n, np.uint32), "md": _take(o.md, n, np.float64), "cigar_off": _take(o.cigar_off, n + 1, np.uint64)}
+        res["cigar"] = _take(o.cigar, int(res["cigar_off"][-1]), np.uint32)
     finally:
         lib().lcty_align_out_free(C.byref(o))
     return res, st.as_dict()
@@ -1519,7 +1512,7 @@ def align_haplotypes_transitive(ctx, seqs, seq_off, ref_id, query_id, params=Non
     2 / 3 composed through `via` by the first / second clause) and via (2^32 - 1: none); stats dict with the fields of both stats structs."""
     p = params if params is not None else align_params()
     tp = tr_params if tr_params is not None else align_tr_params()
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     r = np.ascontiguousarray(ref_id, dtype=np.uint32); q = np.ascontiguousarray(query_id, dtype=np.uint32)
     if len(r) != len(q):
         raise ValueError("ref_id and query_id differ in length")
@@ -1530,11 +1523,11 @@ def align_haplotypes_transitive(ctx, seqs, seq_off, ref_id, query_id, params=Non
                                                  C.byref(st), C.byref(ts)))
     try:
         n = int(o.n_pairs)
-        res = {"aligned": _copy(o.aligned, n, np.uint8), "n_matches": _copy(o.n_matches, n, np.uint32), "aln_len": _copy(o.aln_len, n, np.uint32),
-               "nerrs": _copy(o.nerrs, n, np.uint32), "score": _copy(o.score, n, np.int32), "best_k": _copy(o.best_k, n, np.uint32),
-               "um": _copy(o.um, n, np.uint32), "md": _copy(o.md, n, np.float64), "cigar_off": _copy(o.cigar_off, n + 1, np.uint64),
-               "route": _copy(to.route, n, np.uint8), "via": _copy(to.via, n, np.uint32)}
-        res["cigar"] = _copy(o.cigar, int(res["cigar_off"][-1]), np.uint32)
+        res = {"aligned": _take(o.aligned, n, np.uint8), "n_matches": _take(o.n_matches, n, np.uint32), "aln_len": _take(o.aln_len, n, np.uint32),
+               "nerrs": _take(o.nerrs, n, np.uint32), "score": _take(o.score, n, np.int32), "best_k": _take(o.best_k, n, np.uint32),
+               "um": _take(o.um, n, np.uint32), "md": _take(o.md, n, np.float64), "cigar_off": _take(o.cigar_off, n + 1, np.uint64),
+               "route": _take(to.route, n, np.uint8), "via": _take(to.via, n, np.uint32)}
+        res["cigar"] = _take(o.cigar, int(res["cigar_off"][-1]), np.uint32)
     finally:
         lib().lcty_align_out_free(C.byref(o))
         lib().lcty_align_tr_out_free(C.byref(to))
@@ -1545,12 +1538,12 @@ def align_backbone(ctx, seqs, seq_off, ref, query, k, params=None):
     """lcty_align_backbone: one pair, one k, every stage: dict of matches [n][2] (pos1, pos2), chain_score, path (match indices),
     cigar (raw words), score, n_dropped; stats dict."""
     p = params if params is not None else align_params()
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     o, st = cdefs.AlignBackboneOut(), cdefs.AlignStats()
     check(lib().lcty_align_backbone(ctx._h, len(off) - 1, sq.ctypes.data, off.ctypes.data, ref, query, k, C.byref(p), C.byref(o), C.byref(st)))
     try:
-        res = {"matches": _copy(o.matches, 2 * int(o.n_matches), np.uint32).reshape(-1, 2), "chain_score": int(o.chain_score),
-               "path": _copy(o.path, int(o.path_len), np.uint32), "cigar": _copy(o.cigar, int(o.n_cigar), np.uint32), "score": int(o.score),
+        res = {"matches": _take(o.matches, 2 * int(o.n_matches), np.uint32).reshape(-1, 2), "chain_score": int(o.chain_score),
+               "path": _take(o.path, int(o.path_len), np.uint32), "cigar": _take(o.cigar, int(o.n_cigar), np.uint32), "score": int(o.score),
                "n_dropped": int(o.n_dropped)}
     finally:
         lib().lcty_align_backbone_out_free(C.byref(o))
@@ -1625,11 +1618,11 @@ def _prune_out_dict(o):
     n, nc = int(o.n), int(o.n_clusters)
     steps = np.frombuffer(C.string_at(o.steps, cdefs.PRUNE_STEP_DTYPE.itemsize * (n - 1)), dtype=cdefs.PRUNE_STEP_DTYPE).copy() if n > 1 \
         else np.zeros(0, dtype=cdefs.PRUNE_STEP_DTYPE)
-    off = _copy(o.cluster_off, nc + 1, np.uint32)
-    members, acc = _copy(o.members, n, np.uint32), _copy(o.acc, n, np.float64)
-    return {"steps": steps, "threshold": float(o.threshold), "epsilon": float(o.epsilon), "keep_ids": _copy(o.keep_ids, nc, np.uint32),
+    off = _take(o.cluster_off, nc + 1, np.uint32)
+    members, acc = _take(o.members, n, np.uint32), _take(o.acc, n, np.float64)
+    return {"steps": steps, "threshold": float(o.threshold), "epsilon": float(o.epsilon), "keep_ids": _take(o.keep_ids, nc, np.uint32),
             "clusters": [members[int(off[k]):int(off[k + 1])] for k in range(nc)], "acc": [acc[int(off[k]):int(off[k + 1])] for k in range(nc)],
-            "repr": _copy(o.repr, nc, np.uint32), "stats": o.stats.as_dict()}
+            "repr": _take(o.repr, nc, np.uint32), "stats": o.stats.as_dict()}
 
 
 def prune_cluster(ctx, n, tri, mult=None, params=None, names=None, old_discarded=None):
@@ -1681,7 +1674,7 @@ def db_prune_locus(ctx, names, seqs, seq_off, paf, kmers=None, distances=None, d
     discarded, fasta, kmers, distances, paf (bytes), keep, unchanged, warn_bits, threshold, div, stats."""
     from .io import _names_blob
     p = params if params is not None else prune_params()
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     b = lambda x: None if x is None else bytes(x)
     paf, kmers, distances, discarded = b(paf), b(kmers), b(distances), b(discarded)
     ln = lambda x: 0 if x is None else len(x)
@@ -1703,14 +1696,14 @@ def _prune_files_dict(f):
     return {"newick": _bytes_at(f.newick, f.newick_len), "discarded": _bytes_at(f.discarded, f.discarded_len),
             "fasta": _bytes_at(f.fasta, f.fasta_len), "kmers": _bytes_at(f.kmers, f.kmers_len),
             "distances": _bytes_at(f.distances, f.distances_len), "paf": _bytes_at(f.paf, f.paf_len),
-            "keep": _copy(f.keep, int(f.n_keep), np.uint32), "unchanged": bool(f.unchanged), "warn_bits": int(f.warn_bits),
+            "keep": _take(f.keep, int(f.n_keep), np.uint32), "unchanged": bool(f.unchanged), "warn_bits": int(f.warn_bits),
             "threshold": float(f.threshold), "div": f.div.as_dict(), "stats": f.stats.as_dict()}
 
 
 def prune_thin(names, seqs, seq_off, paf, keep, kmers=None, distances=None):
     """lcty_prune_thin (host only): the files of the kept haplotypes; the dict of db_prune_locus with fasta, kmers, distances, paf filled."""
     from .io import _names_blob
-    sq, off = _seq_arrays(seqs, seq_off)
+    sq, off = _haps(seqs, seq_off)
     b = lambda x: None if x is None else bytes(x)
     paf, kmers, distances = b(paf), b(kmers), b(distances)
     ln = lambda x: 0 if x is None else len(x)

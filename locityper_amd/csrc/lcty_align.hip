@@ -480,25 +480,24 @@ __global__ __launch_bounds__(64) void align_gather_kernel(uint32_t nk, const Pai
 
 // Host ---------------------------------------------------------------------------------------------------------------------------------
 struct Index {
-    DevBuf<uint8_t> seq; DevBuf<uint64_t> off, keys_in, keys_sorted; DevBuf<uint32_t> vals_sorted;
+    DevHaps haps; DevBuf<uint64_t> keys_in, keys_sorted; DevBuf<uint32_t> vals_sorted;
     uint64_t total = 0; uint32_t n_seqs = 0;
     std::vector<uint32_t> ks;
 };
 
-void build_index(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, const std::vector<uint32_t>& ks, Index& ix, lcty_align_stats& st) {
+void build_index(lcty_ctx* ctx, const HapSet& hs, const uint8_t* seqs, const uint64_t* seq_off, const std::vector<uint32_t>& ks, Index& ix, lcty_align_stats& st) {
     hipStream_t s = ctx->stream;
     const double t0 = now_ms();
-    ix.total = seq_off[n_seqs]; ix.n_seqs = n_seqs; ix.ks = ks;
+    const uint32_t n_seqs = hs.n;
+    ix.total = hs.total; ix.n_seqs = n_seqs; ix.ks = ks;
     if (ix.total >= 0xFFFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "%llu bases: the k-mer index holds at most 2^32 - 2", static_cast<unsigned long long>(ix.total));
     const uint64_t T = ix.total, nk = ks.size();
-    ix.seq.alloc(T + 1); ix.off.alloc(n_seqs + 1);
-    ix.seq.upload(seqs, T, s); ix.off.upload(seq_off, n_seqs + 1, s);
-    st.bytes_h2d += T + 8ull * (n_seqs + 1);
+    st.bytes_h2d += ix.haps.upload(ctx, hs, seqs, seq_off, 1);
     ix.keys_in.alloc(std::max<uint64_t>(nk * T, 1)); ix.keys_sorted.alloc(std::max<uint64_t>(nk * T, 1)); ix.vals_sorted.alloc(std::max<uint64_t>(nk * T, 1));
     if (nk && T) {
         DevBuf<uint64_t> P, seg; DevBuf<uint32_t> NP, vals_in; DevBuf<uint8_t> tmp;
         P.alloc(T + n_seqs); NP.alloc(T + n_seqs); vals_in.alloc(T);
-        hipLaunchKernelGGL(align_prefix_kernel, dim3(n_seqs), dim3(256), 0, s, ix.seq.p, ix.off.p, P.p, NP.p);
+        hipLaunchKernelGGL(align_prefix_kernel, dim3(n_seqs), dim3(256), 0, s, ix.haps.seqs.p, ix.haps.off.p, P.p, NP.p);
         LCTY_HIP(hipGetLastError());
         uint64_t inv = kHashBase;                                  // Newton: x <- x (2 - b x) doubles the correct low bits (3 to begin with)
         for (int it = 0; it < 6; it++) inv *= 2 - kHashBase * inv;
@@ -506,14 +505,14 @@ void build_index(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint
         const uint64_t mask = bits >= 64 ? ~0ull : ((1ull << std::max<int64_t>(bits, 1)) - 1);
         for (uint64_t ki = 0; ki < nk; ki++) {
             uint64_t* kin = ix.keys_in.p + ki * T;
-            hipLaunchKernelGGL(align_keys_kernel, dim3(n_seqs), dim3(256), 0, s, ix.off.p, P.p, NP.p, ks[ki], inv, mask, kin, vals_in.p);
+            hipLaunchKernelGGL(align_keys_kernel, dim3(n_seqs), dim3(256), 0, s, ix.haps.off.p, P.p, NP.p, ks[ki], inv, mask, kin, vals_in.p);
             LCTY_HIP(hipGetLastError());
             size_t bytes = 0;
             LCTY_HIP(rocprim::segmented_radix_sort_pairs(nullptr, bytes, kin, ix.keys_sorted.p + ki * T, vals_in.p, ix.vals_sorted.p + ki * T,
-                                                         static_cast<unsigned int>(T), n_seqs, ix.off.p, ix.off.p + 1, 0, 64, s));
+                                                         static_cast<unsigned int>(T), n_seqs, ix.haps.off.p, ix.haps.off.p + 1, 0, 64, s));
             if (tmp.n < bytes) tmp.alloc(bytes + 16);
             LCTY_HIP(rocprim::segmented_radix_sort_pairs(tmp.p, bytes, kin, ix.keys_sorted.p + ki * T, vals_in.p, ix.vals_sorted.p + ki * T,
-                                                         static_cast<unsigned int>(T), n_seqs, ix.off.p, ix.off.p + 1, 0, 64, s));
+                                                         static_cast<unsigned int>(T), n_seqs, ix.haps.off.p, ix.haps.off.p + 1, 0, 64, s));
         }
         LCTY_HIP(hipStreamSynchronize(s));
     }
@@ -612,7 +611,7 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     d_tasks.upload(tasks.data(), nt, s); d_slot.upload(slot_off.data(), nt + 1, s); d_fen_off.upload(fen_off.data(), nt + 1, s);
     st.bytes_h2d += 16ull * nt + 16ull * (nt + 1);
     d_cnt.zero(s);
-    hipLaunchKernelGGL(align_join_kernel<false>, dim3(nt), dim3(256), 0, s, d_tasks.p, d_slot.p, ix.seq.p, ix.off.p, ix.total, ix.keys_in.p, ix.keys_sorted.p,
+    hipLaunchKernelGGL(align_join_kernel<false>, dim3(nt), dim3(256), 0, s, d_tasks.p, d_slot.p, ix.haps.seqs.p, ix.haps.off.p, ix.total, ix.keys_in.p, ix.keys_sorted.p,
                        ix.vals_sorted.p, d_cnt.p, static_cast<const uint64_t*>(nullptr), static_cast<uint2*>(nullptr));
     LCTY_HIP(hipGetLastError());
     // 32-bit counts, 64-bit offsets: rocPRIM accumulates in the type of the operator applied to the initial value, uint64_t here
@@ -641,7 +640,7 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     d_m.alloc(n_m + 1); d_dp.alloc(n_m + 1); d_prev.alloc(n_m + 1); d_path.alloc(n_m + 1); d_chain.alloc(nt); d_pstart.alloc(nt); d_fen.alloc(fen_off[nt]);
     d_score.alloc(nt); d_drop.alloc(nt);
     d_stats.alloc(ST_COUNT); d_stats.zero(s); d_fen.zero(s);
-    hipLaunchKernelGGL(align_join_kernel<true>, dim3(nt), dim3(256), 0, s, d_tasks.p, d_slot.p, ix.seq.p, ix.off.p, ix.total, ix.keys_in.p, ix.keys_sorted.p,
+    hipLaunchKernelGGL(align_join_kernel<true>, dim3(nt), dim3(256), 0, s, d_tasks.p, d_slot.p, ix.haps.seqs.p, ix.haps.off.p, ix.total, ix.keys_in.p, ix.keys_sorted.p,
                        ix.vals_sorted.p, static_cast<uint32_t*>(nullptr), d_mo.p, d_m.p);
     LCTY_HIP(hipGetLastError());
     LCTY_HIP(hipStreamSynchronize(s));
@@ -649,7 +648,7 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     st.n_kmer_matches += n_m;
     st.match_ms += now_ms() - t0; t0 = now_ms();
 
-    hipLaunchKernelGGL(align_chain_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, d_tasks.p, nt, ix.off.p, d_tm.p, d_m.p, d_dp.p, d_prev.p, d_path.p, d_fen_off.p,
+    hipLaunchKernelGGL(align_chain_kernel, dim3((nt + 63) / 64), dim3(64), 0, s, d_tasks.p, nt, ix.haps.off.p, d_tm.p, d_m.p, d_dp.p, d_prev.p, d_path.p, d_fen_off.p,
                        d_fen.p, d_chain.p, d_pstart.p, d_stats.p);
     LCTY_HIP(hipGetLastError());
     LCTY_HIP(hipStreamSynchronize(s));
@@ -657,8 +656,8 @@ uint64_t run_batch(lcty_ctx* ctx, const Index& ix, const uint64_t* seq_off, cons
     st.chain_ms += now_ms() - t0; t0 = now_ms();
 
     StageC ws;                                                                // fresh per batch: exact sizes
-    const BackboneSrc src{d_tasks.p, d_tm.p, d_m.p, d_path.p, d_pstart.p, ix.off.p, pr.max_gap, d_score.p, d_drop.p};
-    const std::array<uint64_t, kLevels> n_level = stage_c(ctx, src, nt, ix.seq.p, pr, ws, d_stats.p, st, st.fill_ms, st.fill_ms);
+    const BackboneSrc src{d_tasks.p, d_tm.p, d_m.p, d_path.p, d_pstart.p, ix.haps.off.p, pr.max_gap, d_score.p, d_drop.p};
+    const std::array<uint64_t, kLevels> n_level = stage_c(ctx, src, nt, ix.haps.seqs.p, pr, ws, d_stats.p, st, st.fill_ms, st.fill_ms);
     for (uint32_t l = 0; l < kLevels; l++) st.n_level[l] += n_level[l];
     t0 = now_ms();
 
@@ -732,20 +731,7 @@ Prepared validate(lcty_ctx* ctx, const lcty_align_params* p) {                //
     return r;
 }
 
-void check_seqs(uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off) {
-    if (!seqs || !seq_off || n_seqs < 2) fail(LCTY_ERR_INVALID_INPUT, "at least two sequences are needed");
-    for (uint32_t i = 0; i < n_seqs; i++) {
-        if (seq_off[i + 1] < seq_off[i]) fail(LCTY_ERR_INVALID_INPUT, "seq_off is not ascending at %u", i);
-        if (seq_off[i + 1] - seq_off[i] >= (1ull << 28)) fail(LCTY_ERR_UNSUPPORTED, "sequence %u is longer than 2^28 - 1 bases", i);
-    }
-}
-
-template <typename T> T* to_malloc(const T* p, uint64_t n) {
-    T* r = static_cast<T*>(malloc(std::max<uint64_t>(n, 1) * sizeof(T)));
-    if (!r) throw std::bad_alloc();
-    if (n) memcpy(r, p, n * sizeof(T));
-    return r;
-}
+constexpr HapLimits kAlignHaps{2, UINT32_MAX, 1ull << 28};                    // a CIGAR word holds a run of fewer than 2^28 bases
 
 std::string fmt_f(double v, int prec) {                                      // Rust's {:.N} of an f64
     if (std::isnan(v)) return "NaN";
@@ -757,13 +743,13 @@ std::string fmt_f(double v, int prec) {                                      // 
 
 // what lcty_align_haplotypes decides before it aligns: the input checks, the divergences (process_pair 642-648) and which pairs are taken
 struct Selection {
-    Prepared pr;
+    HapSet hs; Prepared pr;
     std::vector<uint32_t> um; std::vector<double> md; std::vector<uint8_t> aligned;
     std::vector<uint32_t> refs, qrys; std::vector<uint64_t> which;            // the taken pairs, in input order; which = their input index
 };
 void select_pairs(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref_id, const uint32_t* query_id,
                   const uint8_t* against, const lcty_align_params* params, lcty_align_stats& st, Selection& sel) {
-    check_seqs(n_seqs, seqs, seq_off);
+    sel.hs = check_haps(n_seqs, seqs, seq_off, kAlignHaps);
     sel.pr = validate(ctx, params);
     const Prepared& pr = sel.pr;
     std::vector<std::pair<uint64_t, uint64_t>> seen(n_pairs);              // (smaller id << 32 | larger id, index)
@@ -807,15 +793,13 @@ void select_pairs(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uin
 }
 
 struct Batching { uint64_t budget, per_batch; };
-Batching batching(lcty_ctx* ctx, uint32_t n_seqs, const uint64_t* seq_off, const Prepared& pr) {
+Batching batching(lcty_ctx* ctx, const HapSet& hs, const Prepared& pr) {
     size_t free_b = 0, total_b = 0;
     LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
     // bytes for the matches of a batch (20 a match); knob align_match_budget: a test reaches the "do not fit" return of run_batch
     const uint64_t budget = static_cast<uint64_t>(ctx->knob("align_match_budget", static_cast<int64_t>(std::max<uint64_t>(free_b / 4, 64ull << 20))));
-    uint64_t max_len = 0;
-    for (uint32_t i = 0; i < n_seqs; i++) max_len = std::max(max_len, seq_off[i + 1] - seq_off[i]);
     // a pair: per k 12 bytes a reference window (counts, offsets), 8 a query column (tree), and about 20 a match
-    uint64_t per_batch = std::max<uint64_t>(budget / (pr.ks.size() * (max_len + 2) * 40 + 1), 1);
+    uint64_t per_batch = std::max<uint64_t>(budget / (pr.ks.size() * (hs.max_len + 2) * 40 + 1), 1);
     const int64_t knob = ctx->knob("align_batch_pairs", 0);
     if (knob > 0) per_batch = static_cast<uint64_t>(knob);
     per_batch = std::min<uint64_t>(per_batch, (1u << 30) / pr.ks.size());
@@ -824,7 +808,7 @@ Batching batching(lcty_ctx* ctx, uint32_t n_seqs, const uint64_t* seq_off, const
 
 // po[y]: the result of taken pair y; words_of(y): its CIGAR, as (first word, number of words)
 template <class W>
-void write_out(lcty_align_out* out, uint64_t n_pairs, const Selection& sel, const std::vector<PairOut>& po, W words_of) {
+void write_out(Handoff& h, lcty_align_out& o, uint64_t n_pairs, const Selection& sel, const std::vector<PairOut>& po, W words_of) {
     std::vector<uint64_t> coff(n_pairs + 1, 0);
     for (uint64_t y = 0; y < sel.which.size(); y++) coff[sel.which[y] + 1] = words_of(y).second;
     for (uint64_t x = 0; x < n_pairs; x++) coff[x + 1] += coff[x];
@@ -836,11 +820,9 @@ void write_out(lcty_align_out* out, uint64_t n_pairs, const Selection& sel, cons
         nm[x] = po[y].n_matches; ne[x] = po[y].nerrs; al[x] = po[y].n_matches + po[y].nerrs; sc[x] = po[y].score;
         bk[x] = po[y].best_ki == kNoK ? 0 : sel.pr.ks[po[y].best_ki];
     }
-    out->n_pairs = n_pairs;
-    out->aligned = to_malloc(sel.aligned.data(), n_pairs); out->n_matches = to_malloc(nm.data(), n_pairs); out->aln_len = to_malloc(al.data(), n_pairs);
-    out->nerrs = to_malloc(ne.data(), n_pairs); out->score = to_malloc(sc.data(), n_pairs); out->best_k = to_malloc(bk.data(), n_pairs);
-    out->um = to_malloc(sel.um.data(), n_pairs); out->md = to_malloc(sel.md.data(), n_pairs);
-    out->cigar_off = to_malloc(coff.data(), n_pairs + 1); out->cigar = to_malloc(words.data(), words.size());
+    o.n_pairs = n_pairs;
+    o.aligned = h.copy(sel.aligned); o.n_matches = h.copy(nm); o.aln_len = h.copy(al); o.nerrs = h.copy(ne); o.score = h.copy(sc); o.best_k = h.copy(bk);
+    o.um = h.copy(sel.um); o.md = h.copy(sel.md); o.cigar_off = h.copy(coff); o.cigar = h.copy(words);
 }
 
 // the pairs [0, n) of refs / qrys in batches of bt.per_batch; a batch whose matches do not fit comes back as its prefix that does
@@ -886,8 +868,8 @@ uint32_t Session::aln_len(uint64_t pair) const { return im->res[pair].n_matches 
 
 void Session::open(uint64_t store_words) {
     if (im->sel.which.empty()) return;
-    build_index(im->ctx, im->n_seqs, im->seqs, im->seq_off, im->sel.pr.ks, im->ix, im->st);
-    im->bt = batching(im->ctx, im->n_seqs, im->seq_off, im->sel.pr);
+    build_index(im->ctx, im->sel.hs, im->seqs, im->seq_off, im->sel.pr.ks, im->ix, im->st);
+    im->bt = batching(im->ctx, im->sel.hs, im->sel.pr);
     im->store.buf.alloc(store_words);
 }
 
@@ -922,10 +904,10 @@ void Session::transitive(const TrTask* tasks, uint64_t n, uint32_t anchor_size) 
     im->st.bytes_h2d += sizeof(TrTaskDev) * nt;
     // two passes of stage C (the upload is not planning). The CIGARs of a pass are per-round temporaries sized by the bounds, beside the
     // store (not part of its budget); optimize reads what the walk left.
-    stage_c(ctx, TrSrc<0>{d_tasks.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, nullptr, nullptr, nullptr, d_short.p}, nt, im->ix.seq.p, pr, walk, d_stats.p,
+    stage_c(ctx, TrSrc<0>{d_tasks.p, im->ix.haps.off.p, store.buf.p, anchor_size, pr.max_gap, nullptr, nullptr, nullptr, d_short.p}, nt, im->ix.haps.seqs.p, pr, walk, d_stats.p,
             im->st, im->tr.plan_ms, im->tr.tr_fill_ms);
     std::swap(walk.scratch, opt.scratch);                                     // the lanes' scratch goes along and comes back
-    stage_c(ctx, TrSrc<1>{d_tasks.p, im->ix.off.p, store.buf.p, anchor_size, pr.max_gap, walk.off.p, walk.cig.p, walk.words.p, d_short.p}, nt, im->ix.seq.p, pr, opt, d_stats.p,
+    stage_c(ctx, TrSrc<1>{d_tasks.p, im->ix.haps.off.p, store.buf.p, anchor_size, pr.max_gap, walk.off.p, walk.cig.p, walk.words.p, d_short.p}, nt, im->ix.haps.seqs.p, pr, opt, d_stats.p,
             im->st, im->tr.plan_ms, im->tr.optimize_ms);
     std::swap(walk.scratch, opt.scratch);
     const double t0 = now_ms();
@@ -961,7 +943,7 @@ void Session::transitive(const TrTask* tasks, uint64_t n, uint32_t anchor_size) 
     im->tr.count_ms += now_ms() - t0;
 }
 
-void Session::finish(uint64_t n_rounds, lcty_align_out* out, lcty_align_stats* stats, lcty_align_tr_stats* tr_stats) {
+void Session::finish(uint64_t n_rounds, Handoff& h, lcty_align_out& out, lcty_align_stats* stats, lcty_align_tr_stats* tr_stats) {
     hipStream_t s = im->ctx->stream;
     Store& store = im->store;
     const uint64_t n_pairs = im->n_pairs;
@@ -973,7 +955,7 @@ void Session::finish(uint64_t n_rounds, lcty_align_out* out, lcty_align_stats* s
     const std::vector<uint64_t>& which = im->sel.which;
     std::vector<PairOut> po(which.size());
     for (uint64_t y = 0; y < which.size(); y++) po[y] = im->res[which[y]];
-    write_out(out, n_pairs, im->sel, po, [&](uint64_t y) { return std::make_pair(arena.data() + store.off[which[y]], static_cast<size_t>(store.len[which[y]])); });
+    write_out(h, out, n_pairs, im->sel, po, [&](uint64_t y) { return std::make_pair(arena.data() + store.off[which[y]], static_cast<size_t>(store.len[which[y]])); });
     im->st.select_ms += now_ms() - t0;
     im->st.n_aligned = im->sel.which.size(); im->st.n_skipped = n_pairs - im->sel.which.size();
     im->st.total_ms = now_ms() - im->t_all;
@@ -1018,8 +1000,8 @@ void lcty_align_backbone_out_free(lcty_align_backbone_out* o) {
 int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint64_t n_pairs, const uint32_t* ref_id,
                               const uint32_t* query_id, const uint8_t* against, const lcty_align_params* params, lcty_align_out* out, lcty_align_stats* stats) {
     return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !params || !out || (n_pairs && (!ref_id || !query_id))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         lcty_align_stats st{};
         const double t_all = now_ms();
         Selection sel;
@@ -1029,10 +1011,12 @@ int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seq
         std::vector<PairOut> po(refs.size());
         if (!refs.empty()) {
             Index ix;
-            build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
-            run_batches(ctx, ix, seq_off, refs.data(), qrys.data(), refs.size(), pr, batching(ctx, n_seqs, seq_off, pr), po.data(), st);
+            build_index(ctx, sel.hs, seqs, seq_off, pr.ks, ix, st);
+            run_batches(ctx, ix, seq_off, refs.data(), qrys.data(), refs.size(), pr, batching(ctx, sel.hs, pr), po.data(), st);
         }
-        write_out(out, n_pairs, sel, po, [&](uint64_t y) { return std::make_pair(po[y].cigar.data(), po[y].cigar.size()); });
+        lcty_align_out o{}; Handoff h;
+        write_out(h, o, n_pairs, sel, po, [&](uint64_t y) { return std::make_pair(po[y].cigar.data(), po[y].cigar.size()); });
+        *out = o; h.commit();
         st.n_aligned = which.size(); st.n_skipped = n_pairs - which.size();
         st.total_ms = now_ms() - t_all;
         if (stats) *stats = st;
@@ -1042,11 +1026,11 @@ int32_t lcty_align_haplotypes(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seq
 int32_t lcty_align_backbone(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref, uint32_t query, uint32_t k,
                             const lcty_align_params* params, lcty_align_backbone_out* out, lcty_align_stats* stats) {
     return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !params || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         lcty_align_stats st{};
         const double t_all = now_ms();
-        check_seqs(n_seqs, seqs, seq_off);
+        const HapSet hs = check_haps(n_seqs, seqs, seq_off, kAlignHaps);
         lcty_align_params one = *params;
         one.backbone_ks[0] = k; one.n_backbone_ks = 1;
         if (one.thresh_div == 0.0) one.thresh_div = 1.0;
@@ -1054,15 +1038,16 @@ int32_t lcty_align_backbone(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs,
         if (ref >= n_seqs || query >= n_seqs || ref == query) fail(LCTY_ERR_INVALID_INPUT, "pair (%u, %u) of %u sequences", ref, query, n_seqs);
         ctx->activate();
         Index ix;
-        build_index(ctx, n_seqs, seqs, seq_off, pr.ks, ix, st);
+        build_index(ctx, hs, seqs, seq_off, pr.ks, ix, st);
         PairOut po; Capture cap;
         run_batch(ctx, ix, seq_off, &ref, &query, 0, 1, pr, ~0ull, &po, st, &cap);
-        out->n_matches = cap.matches.size();
-        out->matches = reinterpret_cast<uint32_t*>(to_malloc(cap.matches.data(), cap.matches.size()));
-        out->chain_score = cap.chain;
-        out->path_len = static_cast<uint32_t>(cap.path.size()); out->path = to_malloc(cap.path.data(), cap.path.size());
-        out->n_cigar = static_cast<uint32_t>(cap.cigar.size()); out->cigar = to_malloc(cap.cigar.data(), cap.cigar.size());
-        out->score = cap.score; out->n_dropped = cap.dropped;
+        lcty_align_backbone_out o{}; Handoff h;
+        o.n_matches = cap.matches.size(); o.matches = reinterpret_cast<uint32_t*>(h.copy(cap.matches));
+        o.chain_score = cap.chain;
+        o.path_len = static_cast<uint32_t>(cap.path.size()); o.path = h.copy(cap.path);
+        o.n_cigar = static_cast<uint32_t>(cap.cigar.size()); o.cigar = h.copy(cap.cigar);
+        o.score = cap.score; o.n_dropped = cap.dropped;
+        *out = o; h.commit();
         st.n_aligned = 1;
         st.total_ms = now_ms() - t_all;
         if (stats) *stats = st;

@@ -25,7 +25,7 @@ public:
     void transitive(const TrTask* tasks, uint64_t n, uint32_t anchor_size);   // plan, fill, optimize, counts; into the store
     uint32_t nerrs(uint64_t pair) const;
     uint32_t aln_len(uint64_t pair) const;
-    void finish(uint64_t n_rounds, lcty_align_out* out, lcty_align_stats* stats, lcty_align_tr_stats* tr_stats);
+    void finish(uint64_t n_rounds, Handoff& h, lcty_align_out& out, lcty_align_stats* stats, lcty_align_tr_stats* tr_stats);   // the arrays of out: through h
 private:
     struct Impl;
     Impl* im;

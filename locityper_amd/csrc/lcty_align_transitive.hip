@@ -34,25 +34,23 @@ int32_t lcty_align_haplotypes_transitive(lcty_ctx* ctx, uint32_t n_seqs, const u
                                          const lcty_align_tr_params* tr_params, lcty_align_out* out, lcty_align_tr_out* tr_out, lcty_align_stats* stats,
                                          lcty_align_tr_stats* tr_stats) {
     return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
+        if (tr_out) memset(tr_out, 0, sizeof(*tr_out));
         if (!ctx || !params || !tr_params || !out || !tr_out || (n_pairs && (!ref_id || !query_id))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out)); memset(tr_out, 0, sizeof(*tr_out));
         if (tr_stats) memset(tr_stats, 0, sizeof(*tr_stats));
         if (tr_params->transitive_div != tr_params->transitive_div || tr_params->transitive_div > 1.0)
             fail(LCTY_ERR_INVALID_INPUT, "Transitive divergence (%g) must be at most 1", tr_params->transitive_div);
         if (tr_params->transitive_anchor < 1) fail(LCTY_ERR_INVALID_INPUT, "Transitive anchor size must be at least 1");
         std::vector<uint8_t> route(std::max<uint64_t>(n_pairs, 1), 0);
         std::vector<uint32_t> via(std::max<uint64_t>(n_pairs, 1), 0xFFFFFFFFu);
-        auto hand_out = [&] {
-            tr_out->route = static_cast<uint8_t*>(malloc(route.size())); tr_out->via = static_cast<uint32_t*>(malloc(via.size() * 4));
-            if (!tr_out->route || !tr_out->via) { lcty_align_out_free(out); lcty_align_tr_out_free(tr_out); throw std::bad_alloc(); }
-            memcpy(tr_out->route, route.data(), route.size()); memcpy(tr_out->via, via.data(), via.size() * 4);
-        };
+        lcty_align_out o{}; lcty_align_tr_out t{}; Handoff h;
         // align.rs:784: no acceleration without a positive divergence or below 16 pairs — the backbone route as it stands
         if (!(tr_params->transitive_div > 0.0) || n_pairs < 16) {
-            const int32_t rc = lcty_align_haplotypes(ctx, n_seqs, seqs, seq_off, n_pairs, ref_id, query_id, against, params, out, stats);
+            t.route = h.copy(route); t.via = h.copy(via);                     // before the call: nothing fails once it has filled o
+            const int32_t rc = lcty_align_haplotypes(ctx, n_seqs, seqs, seq_off, n_pairs, ref_id, query_id, against, params, &o, stats);
             if (rc != LCTY_OK) fail(rc, "%s", lcty_last_error());
-            for (uint64_t x = 0; x < n_pairs; x++) route[x] = out->aligned[x] ? 1 : 0;
-            hand_out();
+            for (uint64_t x = 0; x < n_pairs; x++) t.route[x] = o.aligned[x] ? 1 : 0;
+            *out = o; *tr_out = t; h.commit();
             return;
         }
         align::Session ses(ctx, n_seqs, seqs, seq_off, n_pairs, ref_id, query_id, against, params);
@@ -109,8 +107,9 @@ int32_t lcty_align_haplotypes_transitive(lcty_ctx* ctx, uint32_t n_seqs, const u
             n_rounds += members.empty() ? 0 : 1;
             x0 = x;
         }
-        ses.finish(n_rounds, out, stats, tr_stats);
-        hand_out();
+        ses.finish(n_rounds, h, o, stats, tr_stats);
+        t.route = h.copy(route); t.via = h.copy(via);
+        *out = o; *tr_out = t; h.commit();
     });
 }
 

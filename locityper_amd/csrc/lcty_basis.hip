@@ -421,15 +421,6 @@ void basis_constraints_device(lcty_ctx* ctx, const uint32_t* d_rows, uint64_t n_
 
 }  // namespace lcty
 
-namespace {
-uint32_t* to_malloc_u32(const uint32_t* p, uint64_t n) {
-    uint32_t* b = static_cast<uint32_t*>(malloc(n ? 4 * n : 4));
-    if (!b) throw std::bad_alloc();
-    if (n) memcpy(b, p, 4 * n);
-    return b;
-}
-}  // namespace
-
 extern "C" {
 
 void lcty_basis_params_default(lcty_basis_params* p) {
@@ -510,17 +501,18 @@ int32_t lcty_basis_windows(lcty_ctx* ctx, uint32_t n_alleles, const uint32_t* le
                            const uint32_t* n_matches, const uint32_t* aln_len, const uint64_t* cigar_off, const uint32_t* cigar, const uint8_t* leave_out,
                            const lcty_basis_params* params, uint64_t* win_off, uint32_t** rows, lcty_basis_stats* stats) {
     return guarded([&] {
+        if (rows) *rows = nullptr;
         if (!ctx || !win_off || !rows) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         lcty_basis_stats st{};
         const double t0 = now_ms();
         BasisRows R;
         basis_windows_device(ctx, n_alleles, lengths, n_entries, id1, id2, n_matches, aln_len, cigar_off, cigar, leave_out, params, R, st);
-        std::vector<uint32_t> h(R.n_rows * R.words);
-        R.bits.download(h.data(), h.size(), ctx->stream);
+        Handoff h;
+        uint32_t* bits = from(h, R.bits, R.n_rows * R.words, ctx->stream);
         LCTY_HIP(hipStreamSynchronize(ctx->stream));
-        st.bytes_d2h += 4 * h.size();
+        st.bytes_d2h += 4 * R.n_rows * R.words;
         memcpy(win_off, R.win_off.data(), 8ull * (n_alleles + 1));
-        *rows = to_malloc_u32(h.data(), h.size());
+        *rows = bits; h.commit();
         st.total_ms = now_ms() - t0;
         if (stats) *stats = st;
     });
@@ -529,6 +521,8 @@ int32_t lcty_basis_windows(lcty_ctx* ctx, uint32_t n_alleles, const uint32_t* le
 int32_t lcty_basis_constraints(lcty_ctx* ctx, uint32_t n_alleles, uint64_t n_rows, const uint32_t* rows, int32_t minimal, uint64_t* n_out, uint32_t** out,
                                lcty_basis_stats* stats) {
     return guarded([&] {
+        if (out) *out = nullptr;
+        if (n_out) *n_out = 0;
         if (!ctx || !n_out || !out || (n_rows && !rows)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         if (n_alleles < 1) fail(LCTY_ERR_INVALID_INPUT, "no haplotypes");
         lcty_basis_stats st{};
@@ -541,8 +535,8 @@ int32_t lcty_basis_constraints(lcty_ctx* ctx, uint32_t n_alleles, uint64_t n_row
         st.bytes_h2d += 4 * n_rows * words; st.n_rows_raw = n_rows;
         std::vector<uint32_t> res;
         basis_constraints_device(ctx, d.p, n_rows, words, minimal != 0, res, st);
-        *n_out = res.size() / words;
-        *out = to_malloc_u32(res.data(), res.size());
+        Handoff h;
+        *out = h.copy(res); *n_out = res.size() / words; h.commit();
         st.total_ms = now_ms() - t0;
         if (stats) *stats = st;
     });

@@ -1,5 +1,5 @@
-// lcty_common.hpp — shared host-side plumbing of liblocityper_hip.so:
-// error reporting (mirrors src/err.rs:11-30 categories), HIP checks, device buffers, context.
+// lcty_common.hpp — shared host-side plumbing of liblocityper_hip.so: HIP checks, device buffers, context. What needs no HIP — error
+// reporting (mirrors src/err.rs:11-30 categories), the hand-off of results, the check of a haplotype set — is in lcty_host.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/locityper_hip.h"
+#include "lcty_host.hpp"
 
 namespace lcty {
 
@@ -28,23 +28,6 @@ constexpr bool kDiag = true;
 #else
 constexpr bool kDiag = false;
 #endif
-
-// Thread-local message of the last failure (lcty_last_error()).
-void set_last_error(const std::string& msg);
-
-struct Error : std::runtime_error {
-    int32_t code;
-    Error(int32_t c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-[[noreturn]] inline void fail(int32_t code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    throw Error(code, buf);
-}
 
 #define LCTY_HIP(expr)                                                                          \
     do {                                                                                        \
@@ -56,24 +39,6 @@ struct Error : std::runtime_error {
 
 // Wall clock in milliseconds, for the phase times of the *_stats structures and the traces of the developer build.
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// Wraps a C-ABI body: exceptions -> status code + last-error string.
-template <typename F>
-int32_t guarded(F&& body) {
-    try {
-        body();
-        return LCTY_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        set_last_error("out of host memory");
-        return LCTY_ERR_RUNTIME;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return LCTY_ERR_RUNTIME;
-    }
-}
 
 // Owning device allocation.
 template <typename T>
@@ -117,18 +82,10 @@ struct DevBuf {
     }
 };
 
-// Arrays handed to the caller of the C interface, who frees them with free(): a copy of n host values, n values of a device buffer
-// (asynchronous: the caller synchronises s before reading). n == 0 still gives a pointer.
-template <typename T> T* malloc_copy(const T* p, size_t n) {
-    T* out = static_cast<T*>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
-    if (!out) throw std::bad_alloc();
-    if (n) memcpy(out, p, n * sizeof(T));
-    return out;
-}
-template <typename T> T* malloc_from(const DevBuf<T>& d, size_t n, hipStream_t s) {
-    T* out = static_cast<T*>(malloc(std::max<size_t>(n, 1) * sizeof(T)));
-    if (!out) throw std::bad_alloc();
-    try { d.download(out, n, s); } catch (...) { free(out); throw; }
+// n values of a device buffer on their way to the caller (lcty_host.hpp: Handoff). Asynchronous: synchronise s before reading or committing.
+template <typename T> T* from(Handoff& h, const DevBuf<T>& d, size_t n, hipStream_t s) {
+    T* out = static_cast<T*>(h.raw(n * sizeof(T)));
+    d.download(out, n, s);
     return out;
 }
 // workgroups of `per` items that cover n
@@ -295,3 +252,15 @@ struct lcty_ctx {
     int64_t diag_knob(const char* name, int64_t dflt) const { return lcty::kDiag ? knob(name, dflt) : dflt; }
     void activate() const { LCTY_HIP(hipSetDevice(device)); }
 };
+
+namespace lcty {
+// A checked haplotype set (lcty_host.hpp: check_haps) on the device. pad_bytes: what a stage's kernels may read behind the last base.
+struct DevHaps {
+    DevBuf<uint8_t> seqs; DevBuf<uint64_t> off;
+    uint64_t upload(lcty_ctx* ctx, const HapSet& hs, const uint8_t* h_seqs, const uint64_t* seq_off, uint64_t pad_bytes) {      // -> bytes sent
+        seqs.alloc(std::max<uint64_t>(hs.total + pad_bytes, 1)); seqs.upload(h_seqs, hs.total, ctx->stream);
+        off.alloc(uint64_t(hs.n) + 1); off.upload(seq_off, uint64_t(hs.n) + 1, ctx->stream);
+        return hs.total + 8ull * (hs.n + 1);
+    }
+};
+}  // namespace lcty

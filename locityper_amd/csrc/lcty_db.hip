@@ -112,7 +112,7 @@ __global__ __launch_bounds__(64) void db_minim_walk_kernel(const uint8_t* __rest
     uint64_t hashes[64], m = 0;
     for (uint32_t q = 0; q < 64; q++) hashes[q] = UNDEF64;
     uint64_t* dst = WRITE ? out + min_off[a] : nullptr;
-    minimizers_as_written<false>(static_cast<uint32_t>(len), k, w,                // check_seqs: fewer than 2^31 bases
+    minimizers_as_written<false>(static_cast<uint32_t>(len), k, w,                // check_db_haps: fewer than 2^31 bases
         [&](uint32_t i) { return base_enc(s[i]); },
         [&](uint32_t j) -> uint64_t& { return hashes[j & 63]; },
         [&](uint32_t, uint64_t h, bool) { if (WRITE) dst[m] = h; m++; });
@@ -293,13 +293,9 @@ __global__ __launch_bounds__(256) void db_offt_kernel(const uint8_t* __restrict_
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
 uint64_t pow2_at_least(uint64_t x) { uint64_t c = 1024; while (c < x) c <<= 1; return c; }
 
-void check_seqs(uint32_t n, const uint8_t* seqs, const uint64_t* seq_off) {
-    if (!seqs || !seq_off) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-    if (seq_off[0] != 0) fail(LCTY_ERR_INVALID_INPUT, "seq_off[0] must be 0");
-    for (uint32_t a = 0; a < n; a++) {
-        if (seq_off[a + 1] < seq_off[a]) fail(LCTY_ERR_INVALID_INPUT, "seq_off is not ascending at %u", a);
-        if (seq_off[a + 1] - seq_off[a] >= (1ull << 31)) fail(LCTY_ERR_UNSUPPORTED, "sequence %u is longer than 2^31 - 1 bases", a);
-    }
+// what the kernels here take: positions inside a sequence are 31 bits wide
+HapSet check_db_haps(uint32_t n, const uint8_t* seqs, const uint64_t* seq_off, uint32_t min_seqs) {
+    return check_haps(n, seqs, seq_off, HapLimits{min_seqs, UINT32_MAX, 1ull << 31});
 }
 void check_kw(uint32_t k, uint32_t w) {
     if (k < 1 || k > 32) fail(LCTY_ERR_INVALID_INPUT, "minimizer k = %u: must be 1..32 (64-bit k-mers)", k);
@@ -318,18 +314,16 @@ struct Lists {
 };
 
 // sorted minimizer lists of every sequence on the device
-void build_lists(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t* seq_off, uint32_t k, uint32_t w, Lists& L, lcty_db_stats& st) {
+void build_lists(lcty_ctx* ctx, const HapSet& hs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t k, uint32_t w, Lists& L, lcty_db_stats& st) {
     hipStream_t s = ctx->stream;
     double t0 = now_ms();
-    const uint64_t total_len = seq_off[n];
-    uint64_t max_len = 0;
-    for (uint32_t a = 0; a < n; a++) max_len = std::max(max_len, seq_off[a + 1] - seq_off[a]);
-    DevBuf<uint8_t> d_seqs; DevBuf<uint64_t> d_seq_off; DevBuf<uint32_t> d_flags, d_list; DevBuf<unsigned long long> d_cnt;
-    d_seqs.alloc(std::max<uint64_t>(total_len, 1)); d_seq_off.alloc(n + 1); d_flags.alloc(n); d_cnt.alloc(n);
-    d_seqs.upload(seqs, total_len, s); d_seq_off.upload(seq_off, n + 1, s);
+    const uint32_t n = hs.n;
+    const uint64_t max_len = hs.max_len;
+    DevHaps d; DevBuf<uint32_t> d_flags, d_list; DevBuf<unsigned long long> d_cnt;
+    d_flags.alloc(n); d_cnt.alloc(n);
+    st.bytes_h2d += d.upload(ctx, hs, seqs, seq_off, 0);
     d_flags.zero(s); d_cnt.zero(s);
-    st.bytes_h2d += total_len + 8ull * (n + 1);
-    hipLaunchKernelGGL(db_classify_kernel, per_allele_grid(n, max_len), dim3(256), 0, s, d_seqs.p, d_seq_off.p, k, d_flags.p);
+    hipLaunchKernelGGL(db_classify_kernel, per_allele_grid(n, max_len), dim3(256), 0, s, d.seqs.p, d.off.p, k, d_flags.p);
     std::vector<uint32_t> flags(n), walk;
     d_flags.download(flags.data(), n, s);
     LCTY_HIP(hipStreamSynchronize(s));
@@ -340,8 +334,8 @@ void build_lists(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t*
     const dim3 fast_grid(n, static_cast<uint32_t>(std::max<uint64_t>((max_len + kTile - 1) / kTile, 1)));
     if (fast_grid.y > 65535) fail(LCTY_ERR_UNSUPPORTED, "a sequence of %llu bases: more than 65 535 tiles", static_cast<unsigned long long>(max_len));
     // pass 1: lengths of the lists
-    hipLaunchKernelGGL(db_minim_fast_kernel<false>, fast_grid, dim3(256), 0, s, d_seqs.p, d_seq_off.p, d_flags.p, k, w, d_cnt.p, nullptr, nullptr);
-    if (n_walk) hipLaunchKernelGGL(db_minim_walk_kernel<false>, dim3((n_walk + 63) / 64), dim3(64), 0, s, d_seqs.p, d_seq_off.p, d_list.p, n_walk, k, w, d_cnt.p, nullptr, nullptr);
+    hipLaunchKernelGGL(db_minim_fast_kernel<false>, fast_grid, dim3(256), 0, s, d.seqs.p, d.off.p, d_flags.p, k, w, d_cnt.p, nullptr, nullptr);
+    if (n_walk) hipLaunchKernelGGL(db_minim_walk_kernel<false>, dim3((n_walk + 63) / 64), dim3(64), 0, s, d.seqs.p, d.off.p, d_list.p, n_walk, k, w, d_cnt.p, nullptr, nullptr);
     std::vector<unsigned long long> cnt(n);
     d_cnt.download(cnt.data(), n, s);
     LCTY_HIP(hipStreamSynchronize(s));
@@ -354,8 +348,8 @@ void build_lists(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t*
     L.d_off.upload(L.off.data(), n + 1, s);
     d_cnt.zero(s);
     // pass 2: the hashes (the clean kernel places them in any order inside a list: the list is sorted next)
-    hipLaunchKernelGGL(db_minim_fast_kernel<true>, fast_grid, dim3(256), 0, s, d_seqs.p, d_seq_off.p, d_flags.p, k, w, d_cnt.p, L.d_off.p, L.hashes.p);
-    if (n_walk) hipLaunchKernelGGL(db_minim_walk_kernel<true>, dim3((n_walk + 63) / 64), dim3(64), 0, s, d_seqs.p, d_seq_off.p, d_list.p, n_walk, k, w, d_cnt.p, L.d_off.p, L.hashes.p);
+    hipLaunchKernelGGL(db_minim_fast_kernel<true>, fast_grid, dim3(256), 0, s, d.seqs.p, d.off.p, d_flags.p, k, w, d_cnt.p, L.d_off.p, L.hashes.p);
+    if (n_walk) hipLaunchKernelGGL(db_minim_walk_kernel<true>, dim3((n_walk + 63) / 64), dim3(64), 0, s, d.seqs.p, d.off.p, d_list.p, n_walk, k, w, d_cnt.p, L.d_off.p, L.hashes.p);
     LCTY_HIP(hipGetLastError());
     LCTY_HIP(hipStreamSynchronize(s));
     double t1 = now_ms();
@@ -392,11 +386,12 @@ void build_lists(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t*
     }
 }
 
-void divergences(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t* seq_off, uint32_t k, uint32_t w, uint32_t* uniq, double* diverg,
+void divergences(lcty_ctx* ctx, const HapSet& hs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t k, uint32_t w, uint32_t* uniq, double* diverg,
                  lcty_db_check* check, lcty_db_stats& st) {
     hipStream_t s = ctx->stream;
+    const uint32_t n = hs.n;
     Lists L;
-    build_lists(ctx, n, seqs, seq_off, k, w, L, st);
+    build_lists(ctx, hs, seqs, seq_off, k, w, L, st);
     const uint64_t total = L.off[n], n_pairs = uint64_t(n) * (n - 1) / 2;
     double t0 = now_ms();
     // column index
@@ -525,7 +520,7 @@ void off_target(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t* 
                 uint32_t* warn, lcty_db_stats& st) {
     if (k < 2 || k > 63) fail(LCTY_ERR_INVALID_INPUT, "k = %u: must be 2..63 (128-bit k-mers, counts.rs:189)", k);
     const uint32_t max_value = max_value_of(counter_bytes);
-    check_seqs(n, seqs, seq_off);
+    const HapSet hs = check_db_haps(n, seqs, seq_off, 1);
     if (!counts || !cnt_off || !ref_seq || !ref_counts_in || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
     if (ref_len >= (1ull << 31)) fail(LCTY_ERR_UNSUPPORTED, "reference sequence longer than 2^31 - 1 bases");
     for (uint32_t a = 0; a < n; a++) {
@@ -567,14 +562,15 @@ void off_target(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t* 
         uint64_t max_n = 0;
         for (uint32_t a = 0; a < n; a++) max_n = std::max(max_n, cnt_off[a + 1] - cnt_off[a]);
         const uint64_t cap = pow2_at_least(2 * std::max<uint64_t>(n_ref, 1));
-        DevBuf<uint8_t> d_seqs, d_ref; DevBuf<uint64_t> d_seq_off, d_cnt_off; DevBuf<uint16_t> d_counts, d_out, d_ref_counts, d_value;
+        DevHaps d; DevBuf<uint8_t> d_ref; DevBuf<uint64_t> d_cnt_off; DevBuf<uint16_t> d_counts, d_out, d_ref_counts, d_value;
         DevBuf<unsigned long long> keys; DevBuf<uint32_t> first, occ, d_neg;
-        d_seqs.alloc(std::max<uint64_t>(seq_off[n], 1)); d_ref.alloc(std::max<uint64_t>(ref_len, 1)); d_seq_off.alloc(n + 1); d_cnt_off.alloc(n + 1);
+        d_ref.alloc(std::max<uint64_t>(ref_len, 1)); d_cnt_off.alloc(n + 1);
         d_counts.alloc(std::max<uint64_t>(n_counts, 1)); d_out.alloc(std::max<uint64_t>(n_counts, 1)); d_ref_counts.alloc(std::max<uint64_t>(n_ref, 1));
         d_value.alloc(cap + 1); keys.alloc(cap + 1); first.alloc(cap + 1); occ.alloc(cap + 1); d_neg.alloc(1);
-        d_seqs.upload(seqs, seq_off[n], s); d_ref.upload(ref.data(), ref_len, s); d_seq_off.upload(seq_off, n + 1, s); d_cnt_off.upload(cnt_off, n + 1, s);
+        st.bytes_h2d += d.upload(ctx, hs, seqs, seq_off, 0);
+        d_ref.upload(ref.data(), ref_len, s); d_cnt_off.upload(cnt_off, n + 1, s);
         d_counts.upload(counts, n_counts, s); d_ref_counts.upload(ref_counts.data(), n_ref, s);
-        st.bytes_h2d += seq_off[n] + ref_len + 16ull * (n + 1) + 2 * (n_counts + n_ref);
+        st.bytes_h2d += ref_len + 8ull * (n + 1) + 2 * (n_counts + n_ref);
         LCTY_HIP(hipMemsetAsync(keys.p, 0xFF, (cap + 1) * 8, s));
         LCTY_HIP(hipMemsetAsync(first.p, 0xFF, (cap + 1) * 4, s));
         occ.zero(s); d_neg.zero(s); d_value.zero(s);
@@ -584,7 +580,7 @@ void off_target(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t* 
                                max_value, d_value.p, d_neg.p);
         }
         if (n_counts)
-            hipLaunchKernelGGL(db_offt_kernel, per_allele_grid(n, max_n), dim3(256), 0, s, d_seqs.p, d_seq_off.p, d_counts.p, d_cnt_off.p, k, keys.p, d_value.p, cap,
+            hipLaunchKernelGGL(db_offt_kernel, per_allele_grid(n, max_n), dim3(256), 0, s, d.seqs.p, d.off.p, d_counts.p, d_cnt_off.p, k, keys.p, d_value.p, cap,
                                max_value, d_out.p);
         LCTY_HIP(hipGetLastError());
         uint32_t neg = 0;
@@ -604,14 +600,6 @@ uint64_t hash_bytes(const uint8_t* p, uint64_t n) {                            /
     for (; i + 8 <= n; i += 8) { uint64_t v; memcpy(&v, p + i, 8); h = (h ^ v) * 0x100000001b3ull; h ^= h >> 29; }
     for (; i < n; i++) h = (h ^ p[i]) * 0x100000001b3ull;
     return fast_hash64(h);
-}
-
-std::vector<std::string> split_names(const char* names, uint32_t n) {
-    if (!names) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-    std::vector<std::string> v;
-    const char* p = names;
-    for (uint32_t i = 0; i < n; i++) { v.emplace_back(p); p += v.back().size() + 1; }
-    return v;
 }
 
 // discard_identical (add.rs:546-582): the first of equal sequences is kept, the order stays; owner[i] = input index of the kept
@@ -643,13 +631,6 @@ void discard_identical(uint32_t n, const uint8_t* seqs, const uint64_t* seq_off,
     }
 }
 
-uint8_t* to_malloc(const void* p, uint64_t n) {
-    uint8_t* b = static_cast<uint8_t*>(malloc(n ? n : 1));
-    if (!b) throw std::bad_alloc();
-    if (n) memcpy(b, p, n);
-    return b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -665,23 +646,23 @@ void lcty_db_params_default(lcty_db_params* p) {
 int32_t lcty_db_minimizers(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t k, uint32_t w, uint64_t* min_off,
                            uint64_t** hashes, lcty_db_stats* stats) {
     return guarded([&] {
+        if (hashes) *hashes = nullptr;
         if (!ctx || !min_off || !hashes) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         if (n_seqs < 1) fail(LCTY_ERR_INVALID_INPUT, "no sequences");
         check_kw(k, w);
-        check_seqs(n_seqs, seqs, seq_off);
+        const HapSet hs = check_db_haps(n_seqs, seqs, seq_off, 1);
         ctx->activate();
         lcty_db_stats st{};
         const double t0 = now_ms();
         Lists L;
-        build_lists(ctx, n_seqs, seqs, seq_off, k, w, L, st);
+        build_lists(ctx, hs, seqs, seq_off, k, w, L, st);
         const uint64_t total = L.off[n_seqs];
-        uint64_t* h = static_cast<uint64_t*>(malloc(std::max<uint64_t>(total, 1) * 8));
-        if (!h) throw std::bad_alloc();
-        L.hashes.download(h, total, ctx->stream);
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { free(h); fail(LCTY_ERR_RUNTIME, "HIP error while reading the minimizers back"); }
+        Handoff h;
+        uint64_t* hashes_out = from(h, L.hashes, total, ctx->stream);
+        LCTY_HIP(hipStreamSynchronize(ctx->stream));
         st.bytes_d2h += 8 * total;
         memcpy(min_off, L.off.data(), 8 * (n_seqs + 1));
-        *hashes = h;
+        *hashes = hashes_out; h.commit();
         st.total_ms = now_ms() - t0;
         if (stats) *stats = st;
     });
@@ -693,11 +674,11 @@ int32_t lcty_db_divergences(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs,
         if (!ctx || !uniq) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         check_kw(k, w);
         if (n_seqs < 2) fail(LCTY_ERR_INVALID_DATA, "Less than two haplotypes available");
-        check_seqs(n_seqs, seqs, seq_off);
+        const HapSet hs = check_db_haps(n_seqs, seqs, seq_off, 2);
         ctx->activate();
         lcty_db_stats st{};
         const double t0 = now_ms();
-        divergences(ctx, n_seqs, seqs, seq_off, k, w, uniq, diverg, check, st);
+        divergences(ctx, hs, seqs, seq_off, k, w, uniq, diverg, check, st);
         st.total_ms = now_ms() - t0;
         if (stats) *stats = st;
     });
@@ -721,7 +702,7 @@ int32_t lcty_db_discard_identical(uint32_t n_seqs, const uint8_t* seqs, const ui
                                   uint32_t* owner, char* text, uint64_t cap, uint64_t* needed) {
     return guarded([&] {
         if (!n_kept || !needed) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        check_seqs(n_seqs, seqs, seq_off);
+        check_db_haps(n_seqs, seqs, seq_off, 0);
         std::vector<uint32_t> kv, ov; std::string tx;
         discard_identical(n_seqs, seqs, seq_off, split_names(names, n_seqs), kv, ov, tx);
         *n_kept = static_cast<uint32_t>(kv.size()); *needed = tx.size();
@@ -738,10 +719,10 @@ int32_t lcty_db_build_locus(lcty_ctx* ctx, uint32_t n_seqs, const char* names, c
                             uint64_t ref_len, const uint16_t* counts, const uint64_t* cnt_off, uint32_t k, uint32_t counter_bytes,
                             const lcty_db_params* params, lcty_db_files* out) {
     return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !params || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         if (n_seqs < 2) fail(LCTY_ERR_INVALID_DATA, "Less than two haplotypes available");          // check_sequences, add.rs:656-658
-        check_seqs(n_seqs, seqs, seq_off);
+        check_db_haps(n_seqs, seqs, seq_off, 2);
         if (params->calc_div) check_kw(params->div_k, params->div_w);
         const double t0 = now_ms();
         lcty_db_stats st{};
@@ -761,15 +742,7 @@ int32_t lcty_db_build_locus(lcty_ctx* ctx, uint32_t n_seqs, const char* names, c
             if (!params->only_seqs) { kc.insert(kc.end(), counts + cnt_off[a], counts + cnt_off[a + 1]); kcoff.push_back(kc.size()); }
         }
         st.host_ms += now_ms() - t0;
-        uint64_t need = 0;
         std::vector<uint8_t> fasta, kmers, dists;
-        auto sized = [&](auto&& call, std::vector<uint8_t>& v) {
-            int32_t rc = call(nullptr, 0, &need);
-            if (rc != LCTY_OK) throw Error(rc, lcty_last_error());
-            v.resize(need);
-            rc = call(v.data(), need, &need);
-            if (rc != LCTY_OK) throw Error(rc, lcty_last_error());
-        };
         sized([&](uint8_t* o, uint64_t c, uint64_t* nd) { return lcty_fasta_write_text(m, knames.data(), ks.data(), koff.data(), reinterpret_cast<char*>(o), c, nd); }, fasta);
         lcty_db_check ck{};
         uint32_t warn = 0;
@@ -778,7 +751,7 @@ int32_t lcty_db_build_locus(lcty_ctx* ctx, uint32_t n_seqs, const char* names, c
                 ctx->activate();
                 if (m < 2) fail(LCTY_ERR_INVALID_DATA, "Less than two different haplotypes available");
                 std::vector<uint32_t> uniq(uint64_t(m) * (m - 1) / 2);
-                divergences(ctx, m, ks.data(), koff.data(), params->div_k, params->div_w, uniq.data(), nullptr, &ck, st);
+                divergences(ctx, check_db_haps(m, ks.data(), koff.data(), 2), ks.data(), koff.data(), params->div_k, params->div_w, uniq.data(), nullptr, &ck, st);
                 sized([&](uint8_t* o, uint64_t c, uint64_t* nd) { return lcty_distances_write(params->div_k, params->div_w, m, uniq.data(), o, c, nd); }, dists);
             }
             std::vector<uint16_t> offt(kc.size());
@@ -790,12 +763,14 @@ int32_t lcty_db_build_locus(lcty_ctx* ctx, uint32_t n_seqs, const char* names, c
             kmers = b1; kmers.insert(kmers.end(), b2.begin(), b2.end());                         // off-target first (add.rs:648-650)
         }
         st.total_ms = now_ms() - t0;
-        out->n_kept = m; out->warn_bits = warn; out->check = ck; out->stats = st;
-        out->fasta = to_malloc(fasta.data(), fasta.size()); out->fasta_len = fasta.size();
-        out->kmers = to_malloc(kmers.data(), kmers.size()); out->kmers_len = kmers.size();
-        out->distances = to_malloc(dists.data(), dists.size()); out->distances_len = dists.size();
-        out->discarded = to_malloc(disc.data(), disc.size()); out->discarded_len = disc.size();
-        out->kept = reinterpret_cast<uint32_t*>(to_malloc(kept.data(), 4 * kept.size()));
+        lcty_db_files o{}; Handoff h;
+        o.n_kept = m; o.warn_bits = warn; o.check = ck; o.stats = st;
+        o.fasta = h.copy(fasta); o.fasta_len = fasta.size();
+        o.kmers = h.copy(kmers); o.kmers_len = kmers.size();
+        o.distances = h.copy(dists); o.distances_len = dists.size();
+        o.discarded = h.bytes(disc); o.discarded_len = disc.size();
+        o.kept = h.copy(kept);
+        *out = o; h.commit();
     });
 }
 

@@ -434,10 +434,8 @@ int32_t lcty_io_read_file(const char* path, uint8_t** data, uint64_t* len) {
         else if (ends_with(p, ".lz4")) out = decode_lz4(raw, path);
         else if (ends_with(p, ".br")) out = decode_brotli(raw, path);
         else out.swap(raw);
-        uint8_t* buf = static_cast<uint8_t*>(malloc(out.size() ? out.size() : 1));
-        if (!buf) throw std::bad_alloc();
-        memcpy(buf, out.data(), out.size());
-        *data = buf; *len = out.size();
+        Handoff h;
+        *data = h.copy(out); *len = out.size(); h.commit();
     });
 }
 
@@ -1221,13 +1219,6 @@ size_t gt_index(Field format, const std::string& where) {
     fail(LCTY_ERR_INVALID_DATA, "Variant %s has no GT field", where.c_str());
 }
 
-template <typename T> T* vcf_malloc_copy(const std::vector<T>& v) {
-    T* out = static_cast<T*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
-    if (!out) throw std::bad_alloc();
-    if (!v.empty()) memcpy(out, v.data(), v.size() * sizeof(T));
-    return out;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1311,8 +1302,8 @@ void lcty_vcf_free(lcty_vcf* vcf) { delete vcf; }
 
 int32_t lcty_vcf_region(const lcty_vcf* vcf, const char* contig, uint32_t start, uint32_t end, const uint8_t* sample_used, lcty_vcf_records* out) {
     return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!vcf || !contig || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         const uint32_t S = vcf->view.n_samples, Hn = vcf->view.n_haps;
         uint32_t cix = LCTY_NONE_U32;
         for (uint32_t i = 0; i < vcf->contigs.size(); i++) if (vcf->contigs[i] == contig) cix = i;
@@ -1347,9 +1338,11 @@ int32_t lcty_vcf_region(const lcty_vcf* vcf, const char* contig, uint32_t start,
                 phased.push_back(ph ? 1 : 0);
             }
         }
-        out->n_recs = static_cast<uint32_t>(pos.size()); out->n_haps = Hn; out->n_samples = S; out->n_alleles = allele_off.size() - 1; out->pool_len = pool.size();
-        out->pos = vcf_malloc_copy(pos); out->ref_len = vcf_malloc_copy(rlen); out->rec_allele = vcf_malloc_copy(rec_allele);
-        out->allele_off = vcf_malloc_copy(allele_off); out->allele_bytes = vcf_malloc_copy(pool); out->gt = vcf_malloc_copy(gt); out->phased = vcf_malloc_copy(phased);
+        lcty_vcf_records o{}; Handoff h;
+        o.n_recs = static_cast<uint32_t>(pos.size()); o.n_haps = Hn; o.n_samples = S; o.n_alleles = allele_off.size() - 1; o.pool_len = pool.size();
+        o.pos = h.copy(pos); o.ref_len = h.copy(rlen); o.rec_allele = h.copy(rec_allele);
+        o.allele_off = h.copy(allele_off); o.allele_bytes = h.copy(pool); o.gt = h.copy(gt); o.phased = h.copy(phased);
+        *out = o; h.commit();
     });
 }
 

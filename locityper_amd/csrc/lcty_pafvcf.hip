@@ -494,23 +494,15 @@ void sync(lcty_ctx* ctx) { LCTY_HIP(hipStreamSynchronize(ctx->stream)); }
 #define LAUNCH(kernel, grid, ...) do { hipLaunchKernelGGL(kernel, dim3 grid, dim3(WG), 0, s, __VA_ARGS__); LCTY_HIP(hipGetLastError()); } while (0)
 
 struct DSeqs {
-    DevBuf<uint8_t> seqs; DevBuf<uint64_t> off;
-    uint32_t n = 0, ref_id = 0; uint64_t ref_len = 0, total = 0;
-    Seqs view() const { return Seqs{seqs.p, off.p, n, ref_id}; }
+    DevHaps d;
+    uint32_t n = 0, ref_id = 0; uint64_t ref_len = 0;
+    Seqs view() const { return Seqs{d.seqs.p, d.off.p, n, ref_id}; }
+    // 32-bit positions inside a haplotype, haplotype numbers that fit a grid dimension
     void upload(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* h_seqs, const uint64_t* seq_off, uint32_t ref) {
-        if (!n_seqs || !seq_off) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        if (n_seqs > MAX_HAPS) fail(LCTY_ERR_UNSUPPORTED, "%u haplotypes (at most %u)", n_seqs, MAX_HAPS);
+        const HapSet hs = check_haps(n_seqs, h_seqs, seq_off, HapLimits{1, MAX_HAPS, 0x7FFFFFF0ull});
         if (ref >= n_seqs) fail(LCTY_ERR_INVALID_INPUT, "reference haplotype %u of %u", ref, n_seqs);
-        if (seq_off[0] != 0) fail(LCTY_ERR_INVALID_INPUT, "seq_off does not start at 0");
-        for (uint32_t i = 0; i < n_seqs; i++) {
-            if (seq_off[i + 1] < seq_off[i]) fail(LCTY_ERR_INVALID_INPUT, "seq_off decreases at %u", i);
-            if (seq_off[i + 1] - seq_off[i] >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "haplotype %u has %llu bases (32-bit positions)", i,
-                                                                   static_cast<unsigned long long>(seq_off[i + 1] - seq_off[i]));
-        }
-        n = n_seqs; ref_id = ref; total = seq_off[n_seqs]; ref_len = seq_off[ref + 1] - seq_off[ref];
-        if (total && !h_seqs) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        seqs.alloc(std::max<uint64_t>(total, 1)); seqs.upload(h_seqs, total, ctx->stream);
-        off.alloc(uint64_t(n) + 1); off.upload(seq_off, uint64_t(n) + 1, ctx->stream);
+        n = n_seqs; ref_id = ref; ref_len = hs.len(ref);
+        d.upload(ctx, hs, h_seqs, seq_off, 0);
     }
 };
 
@@ -675,9 +667,9 @@ struct DSlots {
     }
 };
 
-// item 7: line lengths, a scan, every line at its offset. The text lands behind `prefix` in one malloc'ed buffer.
+// item 7: line lengths, a scan, every line at its offset. The text lands behind `prefix` in one block of h.
 char* text_dev(lcty_ctx* ctx, const DSeqs& S, const DTable& T, const uint32_t* r_start, const uint32_t* r_end, const DSlots& L, const char* chrom, uint32_t shift,
-               const std::string& prefix, uint64_t* len, uint64_t* n_lines) {
+               const std::string& prefix, Handoff& h, uint64_t* len, uint64_t* n_lines) {
     hipStream_t s = ctx->stream;
     const uint32_t R = T.n_ranges;
     const size_t chrom_len = strlen(chrom);
@@ -702,10 +694,10 @@ char* text_dev(lcty_ctx* ctx, const DSeqs& S, const DTable& T, const uint32_t* r
             LAUNCH(pafvcf_write_kernel, (R), in, S.view(), d_chrom.p, line_off.p, d_out.p);
         }
     }
-    char* out = static_cast<char*>(malloc(std::max<uint64_t>(prefix.size() + body, 1)));
-    if (!out) throw std::bad_alloc();
+    char* out = static_cast<char*>(h.raw(prefix.size() + body));
     memcpy(out, prefix.data(), prefix.size());
-    try { if (body) d_out.download(out + prefix.size(), body, s); sync(ctx); } catch (...) { free(out); throw; }
+    if (body) d_out.download(out + prefix.size(), body, s);
+    sync(ctx);
     *len = prefix.size() + body; *n_lines = lines;
     return out;
 }
@@ -795,13 +787,6 @@ Samples group_haplotypes(const std::vector<std::string>& names, const char* disc
     return out;
 }
 
-std::vector<std::string> split_blob(const char* names, uint32_t n) {
-    std::vector<std::string> out;
-    const char* p = names;
-    for (uint32_t i = 0; i < n; i++) { out.emplace_back(p); p += out.back().size() + 1; }
-    return out;
-}
-
 void free_out(lcty_pafvcf_out* o) {
     free(o->var_off); free(o->ref_start); free(o->ref_end); free(o->hap_start); free(o->hap_end); free(o->has_aln);
     free(o->unique_start); free(o->unique_end); free(o->merged_start); free(o->merged_end);
@@ -810,24 +795,24 @@ void free_out(lcty_pafvcf_out* o) {
     memset(o, 0, sizeof(*o));
 }
 
-void vars_to_host(lcty_ctx* ctx, const DSeqs& S, const DVars& V, lcty_pafvcf_out* out) {
+void vars_to_host(lcty_ctx* ctx, const DSeqs& S, const DVars& V, Handoff& h, lcty_pafvcf_out* out) {
     hipStream_t s = ctx->stream;
     std::vector<uint32_t> off(uint64_t(S.n) + 1);
     V.off.download(off.data(), off.size(), s);
-    out->ref_start = malloc_from(V.rs, V.n, s); out->ref_end = malloc_from(V.re, V.n, s);
-    out->hap_start = malloc_from(V.hs, V.n, s); out->hap_end = malloc_from(V.he, V.n, s);
-    out->has_aln = malloc_from(V.has, S.n, s);
+    out->ref_start = from(h, V.rs, V.n, s); out->ref_end = from(h, V.re, V.n, s);
+    out->hap_start = from(h, V.hs, V.n, s); out->hap_end = from(h, V.he, V.n, s);
+    out->has_aln = from(h, V.has, S.n, s);
     sync(ctx);
     std::vector<uint64_t> off64(off.begin(), off.end());
-    out->var_off = malloc_copy(off64.data(), off64.size());
+    out->var_off = h.copy(off64);
     out->n_seqs = S.n; out->n_variants = V.n;
     out->stats.n_variants = V.n; out->stats.n_missing = V.n_missing; out->stats.n_bad_len = V.n_bad_len; out->stats.n_shifted = V.n_shifted;
 }
 
-void ranges_to_host(lcty_ctx* ctx, const DRanges& R, lcty_pafvcf_out* out) {
+void ranges_to_host(lcty_ctx* ctx, const DRanges& R, Handoff& h, lcty_pafvcf_out* out) {
     hipStream_t s = ctx->stream;
-    out->unique_start = malloc_from(R.u_start, R.nu, s); out->unique_end = malloc_from(R.u_end, R.nu, s);
-    out->merged_start = malloc_from(R.m_start, R.nm, s); out->merged_end = malloc_from(R.m_end, R.nm, s);
+    out->unique_start = from(h, R.u_start, R.nu, s); out->unique_end = from(h, R.u_end, R.nu, s);
+    out->merged_start = from(h, R.m_start, R.nm, s); out->merged_end = from(h, R.m_end, R.nm, s);
     sync(ctx);
     out->n_unique = R.nu; out->n_merged = R.nm; out->stats.n_unique = R.nu; out->stats.n_merged = R.nm;
 }
@@ -864,15 +849,15 @@ void check_ranges(const DSeqs& S, uint64_t n_ranges, const uint32_t* r_start, co
                                                                 static_cast<unsigned long long>(r), r_start[r], r_end[r], static_cast<unsigned long long>(S.ref_len));
 }
 
-void table_to_host(lcty_ctx* ctx, const DSeqs& S, const DTable& T, lcty_pafvcf_out* out) {
+void table_to_host(lcty_ctx* ctx, const DSeqs& S, const DTable& T, Handoff& h, lcty_pafvcf_out* out) {
     hipStream_t s = ctx->stream;
     std::vector<uint32_t> aoff(uint64_t(T.n_ranges) + 1);
     T.aoff.download(aoff.data(), aoff.size(), s);
-    out->allele_ix = malloc_from(T.ix, uint64_t(T.n_ranges) * S.n, s); out->n_alleles = malloc_from(T.n_alleles, T.n_ranges, s);
-    out->allele_hap = malloc_from(T.a_hap, T.n_all, s); out->allele_start = malloc_from(T.a_start, T.n_all, s); out->allele_len = malloc_from(T.a_len, T.n_all, s);
+    out->allele_ix = from(h, T.ix, uint64_t(T.n_ranges) * S.n, s); out->n_alleles = from(h, T.n_alleles, T.n_ranges, s);
+    out->allele_hap = from(h, T.a_hap, T.n_all, s); out->allele_start = from(h, T.a_start, T.n_all, s); out->allele_len = from(h, T.a_len, T.n_all, s);
     sync(ctx);
     std::vector<uint64_t> aoff64(aoff.begin(), aoff.end());
-    out->allele_off = malloc_copy(aoff64.data(), aoff64.size());
+    out->allele_off = h.copy(aoff64);
     out->n_ranges = T.n_ranges; out->n_seqs = S.n;
 }
 
@@ -892,7 +877,7 @@ int32_t lcty_pafvcf_samples(uint32_t n_seqs, const char* names, const char* disc
                             uint32_t* n_slots, uint32_t* slot_hap, uint32_t* ref_id, uint32_t* warn_bits) {
     return guarded([&] {
         if (!names || !ref_hap || !n_samples || !names_len || !n_slots || !n_seqs) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const Samples S = group_haplotypes(split_blob(names, n_seqs), discarded, discarded_len, ref_hap);
+        const Samples S = group_haplotypes(split_names(names, n_seqs), discarded, discarded_len, ref_hap);
         std::string blob;
         for (const std::string& n : S.names) { blob += n; blob.push_back('\0'); }
         *n_samples = static_cast<uint32_t>(S.names.size()); *names_len = blob.size(); *n_slots = static_cast<uint32_t>(S.slot_hap.size());
@@ -910,25 +895,25 @@ int32_t lcty_pafvcf_samples(uint32_t n_seqs, const char* names, const char* disc
 
 int32_t lcty_pafvcf_variants(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref_id, uint64_t n_entries, const uint32_t* id1,
                              const uint32_t* id2, const uint64_t* cigar_off, const uint32_t* cigar, lcty_pafvcf_out* out) {
-    const int32_t rc = guarded([&] {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         ctx->activate();
         const double t0 = now_ms();
         DSeqs S; DVars V;
         S.upload(ctx, n_seqs, seqs, seq_off, ref_id);
         variants_dev(ctx, S, n_entries, id1, id2, cigar_off, cigar, V);
-        vars_to_host(ctx, S, V, out);
-        out->stats.variants_ms = out->stats.total_ms = now_ms() - t0;
+        lcty_pafvcf_out o{}; Handoff h;
+        vars_to_host(ctx, S, V, h, &o);
+        o.stats.variants_ms = o.stats.total_ms = now_ms() - t0;
+        *out = o; h.commit();
     });
-    if (rc != LCTY_OK && out) free_out(out);
-    return rc;
 }
 
 int32_t lcty_pafvcf_ranges(lcty_ctx* ctx, uint64_t n_variants, const uint32_t* ref_start, const uint32_t* ref_end, lcty_pafvcf_out* out) {
-    const int32_t rc = guarded([&] {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !out || (n_variants && (!ref_start || !ref_end))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         if (n_variants >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "%llu variants (32-bit offsets)", static_cast<unsigned long long>(n_variants));
         ctx->activate();
         const double t0 = now_ms();
@@ -939,19 +924,19 @@ int32_t lcty_pafvcf_ranges(lcty_ctx* ctx, uint64_t n_variants, const uint32_t* r
         rs.alloc(std::max(n, 1u)); re.alloc(std::max(n, 1u));
         rs.upload(ref_start, n, ctx->stream); re.upload(ref_end, n, ctx->stream);
         ranges_dev(ctx, n, rs, re, max_pos, R);
-        ranges_to_host(ctx, R, out);
-        out->stats.ranges_ms = out->stats.total_ms = now_ms() - t0;
+        lcty_pafvcf_out o{}; Handoff h;
+        ranges_to_host(ctx, R, h, &o);
+        o.stats.ranges_ms = o.stats.total_ms = now_ms() - t0;
+        *out = o; h.commit();
     });
-    if (rc != LCTY_OK && out) free_out(out);
-    return rc;
 }
 
 int32_t lcty_pafvcf_table(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref_id, const uint64_t* var_off,
                           const uint32_t* ref_start, const uint32_t* ref_end, const uint32_t* hap_start, const uint32_t* hap_end, const uint8_t* has_aln,
                           uint64_t n_ranges, const uint32_t* range_start, const uint32_t* range_end, lcty_pafvcf_out* out) {
-    const int32_t rc = guarded([&] {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         ctx->activate();
         const double t0 = now_ms();
         DSeqs S; DVars V; DTable T; DevBuf<uint32_t> r0, r1;
@@ -962,20 +947,20 @@ int32_t lcty_pafvcf_table(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, c
         r0.alloc(std::max(R, 1u)); r1.alloc(std::max(R, 1u));
         r0.upload(range_start, R, ctx->stream); r1.upload(range_end, R, ctx->stream);
         table_dev(ctx, S, V, R, r0.p, r1.p, T);
-        table_to_host(ctx, S, T, out);
-        out->stats.table_ms = out->stats.total_ms = now_ms() - t0;
+        lcty_pafvcf_out o{}; Handoff h;
+        table_to_host(ctx, S, T, h, &o);
+        o.stats.table_ms = o.stats.total_ms = now_ms() - t0;
+        *out = o; h.commit();
     });
-    if (rc != LCTY_OK && out) free_out(out);
-    return rc;
 }
 
 int32_t lcty_pafvcf_text(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, const uint64_t* seq_off, uint32_t ref_id, uint64_t n_ranges,
                          const uint32_t* range_start, const uint32_t* range_end, const int32_t* allele_ix, const uint32_t* n_alleles, const uint64_t* allele_off,
                          const uint32_t* allele_hap, const uint32_t* allele_start, const uint32_t* allele_len, uint32_t n_samples, const uint32_t* slot_off,
                          const uint32_t* slot_hap, const char* chrom, uint32_t shift, lcty_pafvcf_out* out) {
-    const int32_t rc = guarded([&] {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !out || !chrom) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         ctx->activate();
         const double t0 = now_ms();
         hipStream_t s = ctx->stream;
@@ -1005,22 +990,22 @@ int32_t lcty_pafvcf_text(lcty_ctx* ctx, uint32_t n_seqs, const uint8_t* seqs, co
         r0.alloc(std::max(R, 1u)); r1.alloc(std::max(R, 1u));
         r0.upload(range_start, R, s); r1.upload(range_end, R, s);
         L.upload(ctx, n_samples, slot_off, slot_hap, n_seqs);
-        out->merged = text_dev(ctx, S, T, r0.p, r1.p, L, chrom, shift, std::string(), &out->merged_len, &out->stats.n_lines_merged);
-        out->stats.merged_bytes = out->merged_len;
-        out->stats.text_ms = out->stats.total_ms = now_ms() - t0;
+        lcty_pafvcf_out o{}; Handoff h;
+        o.merged = text_dev(ctx, S, T, r0.p, r1.p, L, chrom, shift, std::string(), h, &o.merged_len, &o.stats.n_lines_merged);
+        o.stats.merged_bytes = o.merged_len;
+        o.stats.text_ms = o.stats.total_ms = now_ms() - t0;
+        *out = o; h.commit();
     });
-    if (rc != LCTY_OK && out) free_out(out);
-    return rc;
 }
 
 int32_t lcty_paf_to_vcf(lcty_ctx* ctx, uint32_t n_seqs, const char* names, const uint8_t* seqs, const uint64_t* seq_off, const char* discarded,
                         uint64_t discarded_len, const char* ref_hap, uint64_t n_entries, const uint32_t* id1, const uint32_t* id2, const uint64_t* cigar_off,
                         const uint32_t* cigar, const char* chrom, uint32_t region_start, uint32_t region_end, int32_t with_separate, lcty_pafvcf_out* out) {
-    const int32_t rc = guarded([&] {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !out || !names || !ref_hap || !n_seqs || !seq_off) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         const double t0 = now_ms();
-        const Samples G = group_haplotypes(split_blob(names, n_seqs), discarded, discarded_len, ref_hap);
+        const Samples G = group_haplotypes(split_names(names, n_seqs), discarded, discarded_len, ref_hap);
         const uint64_t ref_len = seq_off[G.ref_id + 1] - seq_off[G.ref_id];
         uint32_t shift = 0;
         if (chrom) {                                                    // convert_to_vcf 638-645
@@ -1043,6 +1028,7 @@ int32_t lcty_paf_to_vcf(lcty_ctx* ctx, uint32_t n_seqs, const char* names, const
         st.ranges_ms = now_ms() - t;
         st.n_variants = V.n; st.n_missing = V.n_missing; st.n_bad_len = V.n_bad_len; st.n_shifted = V.n_shifted; st.n_unique = R.nu; st.n_merged = R.nm;
         const std::string header = header_text(G.names);
+        lcty_pafvcf_out o{}; Handoff h;
         for (int pass = 0; pass < (with_separate ? 2 : 1); pass++) {
             DTable T;
             t = now_ms();
@@ -1050,16 +1036,15 @@ int32_t lcty_paf_to_vcf(lcty_ctx* ctx, uint32_t n_seqs, const char* names, const
             const uint32_t* r0 = pass ? R.u_start.p : R.m_start.p; const uint32_t* r1 = pass ? R.u_end.p : R.m_end.p;
             table_dev(ctx, S, V, n, r0, r1, T);
             st.table_ms += now_ms() - t; t = now_ms();
-            if (pass) { out->separate = text_dev(ctx, S, T, r0, r1, L, chrom, shift, header, &out->separate_len, &st.n_lines_separate); st.separate_bytes = out->separate_len; }
-            else { out->merged = text_dev(ctx, S, T, r0, r1, L, chrom, shift, header, &out->merged_len, &st.n_lines_merged); st.merged_bytes = out->merged_len; }
+            if (pass) { o.separate = text_dev(ctx, S, T, r0, r1, L, chrom, shift, header, h, &o.separate_len, &st.n_lines_separate); st.separate_bytes = o.separate_len; }
+            else { o.merged = text_dev(ctx, S, T, r0, r1, L, chrom, shift, header, h, &o.merged_len, &st.n_lines_merged); st.merged_bytes = o.merged_len; }
             st.text_ms += now_ms() - t;
         }
-        out->n_seqs = n_seqs; out->n_variants = V.n; out->n_unique = R.nu; out->n_merged = R.nm;
+        o.n_seqs = n_seqs; o.n_variants = V.n; o.n_unique = R.nu; o.n_merged = R.nm;
         st.total_ms = now_ms() - t0;
-        out->stats = st;
+        o.stats = st;
+        *out = o; h.commit();
     });
-    if (rc != LCTY_OK && out) free_out(out);
-    return rc;
 }
 
 void lcty_pafvcf_out_free(lcty_pafvcf_out* out) {

@@ -342,13 +342,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void boundary_best_kernel(uint32_t n_
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
 
-std::vector<std::string> split_blob(const char* names, uint32_t n) {
-    std::vector<std::string> out;
-    const char* p = names;
-    for (uint32_t i = 0; i < n; i++) { out.emplace_back(p); p += out.back().size() + 1; }
-    return out;
-}
-
 void sync(lcty_ctx* ctx) { LCTY_HIP(hipStreamSynchronize(ctx->stream)); }
 
 // find_best_boundary (add.rs:371-435). Returns whether a position was found; weights (may be null) receives the end - start final weights.
@@ -532,15 +525,13 @@ void free_out(lcty_panvcf_out* o) {
     memset(o, 0, sizeof(*o));
 }
 
-// filter_variants + reconstruct_sequences + the has_n filter of add_locus
+// filter_variants + reconstruct_sequences + the has_n filter of add_locus; the arrays of *out (zero on entry) belong to h
 void reconstruct(lcty_ctx* ctx, const char* contig, uint32_t ref_start, uint32_t ref_end, const uint8_t* ref_seq, const Records& r, const char* names,
-                 double unknown_frac, bool overlaps_allowed, lcty_panvcf_out* out) {
-    if (!ctx || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-    memset(out, 0, sizeof(*out));
+                 double unknown_frac, bool overlaps_allowed, Handoff& h, lcty_panvcf_out* out) {
     if (!ref_seq || !names) fail(LCTY_ERR_INVALID_INPUT, "null argument");
     if (ref_end <= ref_start) fail(LCTY_ERR_INVALID_INPUT, "empty interval %u-%u", ref_start, ref_end);
     check_records(r, true);
-    const std::vector<std::string> nm = split_blob(names, r.n_cols);
+    const std::vector<std::string> nm = split_names(names, r.n_cols);
     const uint32_t V = r.n, H = r.n_cols;
     const uint64_t ref_len = ref_end - ref_start;
     const uint64_t n_alleles = V ? r.rec_allele[V] : 0;
@@ -673,8 +664,7 @@ void reconstruct(lcty_ctx* ctx, const char* contig, uint32_t ref_start, uint32_t
     // (e) compaction
     const uint32_t K = static_cast<uint32_t>(keep.size());
     const uint64_t kept_total = new_off.back();
-    out->seqs = static_cast<uint8_t*>(malloc(std::max<uint64_t>(kept_total, 1)));        // the copy lands in the caller's buffer (released on failure by the entry point)
-    if (!out->seqs) throw std::bad_alloc();
+    out->seqs = static_cast<uint8_t*>(h.raw(kept_total));                               // the copy lands in the caller's buffer
     if (K == H) {
         d_out.download(out->seqs, kept_total, s);
     } else if (K) {
@@ -694,10 +684,10 @@ void reconstruct(lcty_ctx* ctx, const char* contig, uint32_t ref_start, uint32_t
     st.total_ms = now_ms() - t0;
 
     out->n_seqs = K; out->n_cols = H; out->total_overlaps = total_overlaps; out->stats = st;
-    out->seq_off = malloc_copy(new_off.data(), new_off.size());
-    out->names = malloc_copy(kept_names.data(), kept_names.size()); out->names_len = kept_names.size();
-    out->kept_cols = malloc_copy(keep.data(), keep.size());
-    out->col_unknown = malloc_copy(unk.data(), H); out->col_len = malloc_copy(col_len.data(), H); out->col_reason = malloc_copy(reason.data(), H);
+    out->seq_off = h.copy(new_off);
+    out->names = h.copy(kept_names.data(), kept_names.size()); out->names_len = kept_names.size();
+    out->kept_cols = h.copy(keep);
+    out->col_unknown = h.copy(unk); out->col_len = h.copy(col_len); out->col_reason = h.copy(reason);
 }
 
 }  // namespace
@@ -709,7 +699,7 @@ int32_t lcty_panvcf_names(uint32_t n_samples, const char* samples, const uint32_
                           uint32_t* n_left_out) {
     return guarded([&] {
         if (!ref_name || !n_cols || !names_len || (n_samples && (!samples || !ploidy)) || (n_leave_out && !leave_out)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const std::vector<std::string> sm = split_blob(samples, n_samples), lo = split_blob(leave_out, n_leave_out);
+        const std::vector<std::string> sm = split_names(samples, n_samples), lo = split_names(leave_out, n_leave_out);
         const std::unordered_set<std::string> leave(lo.begin(), lo.end());
         std::unordered_set<std::string> seen;
         std::vector<uint32_t> cs, ch; std::string blob;
@@ -751,12 +741,14 @@ int32_t lcty_panvcf_filter(lcty_ctx* ctx, uint32_t n_recs, uint32_t n_cols, cons
 int32_t lcty_panvcf_reconstruct(lcty_ctx* ctx, const char* contig, uint32_t ref_start, uint32_t ref_end, const uint8_t* ref_seq, uint32_t n_recs,
                                 const uint32_t* pos, const uint32_t* ref_len, const uint32_t* rec_allele, const uint64_t* allele_off, const uint8_t* allele_bytes,
                                 uint32_t n_cols, const int16_t* gt, const char* names, double unknown_frac, int32_t overlaps_allowed, lcty_panvcf_out* out) {
-    const int32_t rc = guarded([&] {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
+        if (!ctx || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        lcty_panvcf_out o{}; Handoff h;
         reconstruct(ctx, contig, ref_start, ref_end, ref_seq, Records{n_recs, pos, ref_len, rec_allele, allele_off, allele_bytes, n_cols, gt}, names, unknown_frac,
-                    overlaps_allowed != 0, out);
+                    overlaps_allowed != 0, h, &o);
+        *out = o; h.commit();
     });
-    if (rc != LCTY_OK && out) free_out(out);
-    return rc;
 }
 
 void lcty_panvcf_out_free(lcty_panvcf_out* out) {
@@ -785,9 +777,9 @@ int32_t lcty_db_expand_locus(lcty_ctx* ctx, const char* locus, uint32_t inner_st
 }
 
 int32_t lcty_db_locus_from_vcf(lcty_ctx* ctx, const lcty_locus_vcf_in* in, const lcty_db_params* params, lcty_locus_vcf_out* out) {
-    const int32_t rc = guarded([&] {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !in || !params || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         if (!in->locus || !in->contig || !in->win_seq || !in->names || !in->expansions || !in->n_expansions) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         if (!params->only_seqs && (!in->hap_counts || !in->hap_cnt_off))
             fail(LCTY_ERR_INVALID_INPUT, "the k-mer counts of the haplotypes are missing (or set only_seqs: the sequences alone)");
@@ -829,12 +821,11 @@ int32_t lcty_db_locus_from_vcf(lcty_ctx* ctx, const lcty_locus_vcf_in* in, const
         } else {
             sub.n = 0;
         }
-        lcty_panvcf_out rec{};
+        lcty_panvcf_out rec{}; Handoff h_rec;                               // the reconstruction: read here, never handed out
         const uint8_t* ref_seq = in->win_seq + (ex.start - win.start);
         const uint64_t ref_len = ex.end - ex.start;
         // allele_off of the run keeps its absolute offsets into the pool: the pool goes along whole
-        struct Guard { lcty_panvcf_out* o; ~Guard() { free_out(o); } } guard{&rec};
-        reconstruct(ctx, in->contig, ex.start, ex.end, ref_seq, sub, in->names, in->unknown_frac, in->overlaps_allowed != 0, &rec);
+        reconstruct(ctx, in->contig, ex.start, ex.end, ref_seq, sub, in->names, in->unknown_frac, in->overlaps_allowed != 0, h_rec, &rec);
         st.reconstruct_ms = rec.stats.total_ms; st.recon = rec.stats;
         st.n_kept_records = rec.n_kept_records; st.total_overlaps = rec.total_overlaps; st.n_unknown = rec.n_unknown; st.n_with_n = rec.n_with_n;
         st.n_haplotypes = rec.n_seqs;
@@ -852,21 +843,21 @@ int32_t lcty_db_locus_from_vcf(lcty_ctx* ctx, const lcty_locus_vcf_in* in, const
             const uint8_t* s = rec.seqs + rec.seq_off[a]; const uint64_t l = rec.seq_off[a + 1] - rec.seq_off[a];
             if (memcmp(s, s0, AFFIX) || memcmp(s + l - AFFIX, s0 + l0 - AFFIX, AFFIX)) { st.warn_bits |= LCTY_LOCUS_WARN_BOUNDARY_DIFFERS; break; }
         }
+        lcty_locus_vcf_out o{}; Handoff h;
+        // the names of the reconstructed haplotypes' columns, for the caller who maps files.kept back: kept indexes the surviving haplotypes
+        o.hap_cols = h.copy(rec.kept_cols, rec.n_seqs); o.n_hap_cols = rec.n_seqs;
+        const std::string bed = std::string(in->contig) + "\t" + std::to_string(ex.start) + "\t" + std::to_string(ex.end) + "\t" + in->locus + "\n";   // bed_fmt
+        o.ref_bed = h.copy(bed.data(), bed.size()); o.ref_bed_len = bed.size();
         const double tb = now_ms();
         const int32_t brc = lcty_db_build_locus(ctx, rec.n_seqs, rec.names, rec.seqs, rec.seq_off, ref_seq, ref_len, in->hap_counts, in->hap_cnt_off, in->k,
-                                                in->counter_bytes, params, &out->files);
+                                                in->counter_bytes, params, &o.files);          // the last thing that can fail: its files are not h's
         if (brc != LCTY_OK) throw Error(brc, lcty_last_error());
         st.build_ms = now_ms() - tb;
-        st.n_identical = rec.n_seqs - out->files.n_kept;
-        // the names of the reconstructed haplotypes' columns, for the caller who maps files.kept back: kept indexes the surviving haplotypes
-        out->hap_cols = malloc_copy(rec.kept_cols, rec.n_seqs); out->n_hap_cols = rec.n_seqs;
-        const std::string bed = std::string(in->contig) + "\t" + std::to_string(ex.start) + "\t" + std::to_string(ex.end) + "\t" + in->locus + "\n";   // bed_fmt
-        out->ref_bed = malloc_copy(bed.data(), bed.size()); out->ref_bed_len = bed.size();
+        st.n_identical = rec.n_seqs - o.files.n_kept;
         st.total_ms = now_ms() - t0;
-        out->stats = st;
+        o.stats = st;
+        *out = o; h.commit();
     });
-    if (rc != LCTY_OK && out) lcty_locus_vcf_out_free(out);
-    return rc;
 }
 
 void lcty_locus_vcf_out_free(lcty_locus_vcf_out* out) {

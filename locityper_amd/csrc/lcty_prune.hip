@@ -298,6 +298,8 @@ Cut cut_tree(uint32_t n, const std::vector<lcty_prune_step>& steps, double thres
     return c;
 }
 
+constexpr HapLimits kPruneHaps{1, UINT32_MAX, UINT64_MAX};                                              // the bases go to the FASTA text only: no kernel reads them
+
 void check_params(const lcty_prune_params* p) {
     if (!p) fail(LCTY_ERR_INVALID_INPUT, "null argument");
     if (!(p->threshold >= 0.0)) fail(LCTY_ERR_INVALID_INPUT, "Divergence threshold (%g) should be non-negative", p->threshold);
@@ -306,20 +308,12 @@ void check_params(const lcty_prune_params* p) {
     if (p->only_tree && p->skip_tree) fail(LCTY_ERR_INVALID_INPUT, "--skip-tree and --only-tree cannot be used together");
 }
 
-template <typename T>
-T* vec_malloc(const std::vector<T>& v) {
-    T* p = static_cast<T*>(malloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
-    if (!p) throw std::bad_alloc();
-    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
-
 void prune_out_free(lcty_prune_out* o) {
     free(o->steps); free(o->keep_ids); free(o->cluster_off); free(o->members); free(o->repr); free(o->acc);
     memset(o, 0, sizeof(*o));
 }
 
-void cluster(lcty_ctx* ctx, uint32_t n, const double* tri, const uint32_t* mult, const lcty_prune_params* prm, lcty_prune_out* out) {
+void cluster(lcty_ctx* ctx, uint32_t n, const double* tri, const uint32_t* mult, const lcty_prune_params* prm, Handoff& h, lcty_prune_out& o) {
     const double t_all = now_ms();
     lcty_prune_stats st{};
     std::vector<lcty_prune_step> steps(n - 1);
@@ -368,24 +362,12 @@ void cluster(lcty_ctx* ctx, uint32_t n, const double* tri, const uint32_t* mult,
     std::sort(keep.begin(), keep.end());
     st.host_ms += now_ms() - t0;
     st.total_ms = now_ms() - t_all;
-    lcty_prune_out o{};
     o.n = n; o.n_clusters = nc; o.threshold = c.threshold; o.epsilon = epsilon; o.stats = st;
-    try {
-        o.steps = vec_malloc(steps); o.keep_ids = vec_malloc(keep); o.cluster_off = vec_malloc(c.cluster_off); o.members = vec_malloc(c.members);
-        o.repr = vec_malloc(repr); o.acc = vec_malloc(acc);
-    } catch (...) { prune_out_free(&o); throw; }
-    *out = o;
+    o.steps = h.copy(steps); o.keep_ids = h.copy(keep); o.cluster_off = h.copy(c.cluster_off); o.members = h.copy(c.members);
+    o.repr = h.copy(repr); o.acc = h.copy(acc);
 }
 
 // ---- host: texts ----------------------------------------------------------------------------------------------------------------------
-
-std::vector<std::string> split_names0(const char* names, uint32_t n) {
-    if (!names) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-    std::vector<std::string> v;
-    const char* p = names;
-    for (uint32_t i = 0; i < n; i++) { v.emplace_back(p); p += v.back().size() + 1; }
-    return v;
-}
 
 std::unordered_map<std::string, uint32_t> name_ids(const std::vector<std::string>& names) {
     std::unordered_map<std::string, uint32_t> ids;
@@ -495,13 +477,6 @@ void texts(uint32_t n, const std::vector<std::string>& names, const std::vector<
     }
 }
 
-uint8_t* bytes_malloc(const void* p, uint64_t n) {
-    uint8_t* b = static_cast<uint8_t*>(malloc(n ? n : 1));
-    if (!b) throw std::bad_alloc();
-    if (n) memcpy(b, p, n);
-    return b;
-}
-
 // ---- host: divergences from the PAF (load_divergences, prune.rs:159-230) -------------------------------------------------------------------
 
 // str::parse::<f64>: [+-] then inf | infinity | nan (any case), or digits [. digits] [e [+-] digits] with a digit before the exponent
@@ -594,14 +569,6 @@ void paf_divergences(const uint8_t* text, uint64_t len, const std::vector<std::s
 
 void throw_rc(int32_t rc) { if (rc != LCTY_OK) throw Error(rc, lcty_last_error()); }
 
-template <typename F>
-void sized(F&& call, std::vector<uint8_t>& v) {
-    uint64_t need = 0;
-    throw_rc(call(nullptr, 0, &need));
-    v.resize(need);
-    throw_rc(call(v.data(), need, &need));
-}
-
 // one KmerCounts block at buf: thinned to `keep` and saved again; false when it does not match the haplotypes (KmerCounts::validate)
 bool thin_kmer_block(const uint8_t* buf, uint64_t len, const std::vector<uint32_t>& keep, const std::vector<uint64_t>& seq_len, uint64_t* consumed,
                      std::vector<uint8_t>& out) {
@@ -652,14 +619,14 @@ std::string prune_paf(const uint8_t* text, uint64_t len, const std::vector<std::
 // prune_files (471-518) below the copy branch: the files of the kept haplotypes into f
 void thin_files(uint32_t n, const std::vector<std::string>& nm, const uint8_t* seqs, const uint64_t* seq_off, const uint8_t* paf, uint64_t paf_len,
                 const uint8_t* kmers, uint64_t kmers_len, const uint8_t* distances, uint64_t distances_len, const std::vector<uint32_t>& keep,
-                lcty_prune_files& f) {
+                Handoff& h, lcty_prune_files& f) {
     std::string fa;
     for (uint32_t a : keep) {                                                                            // fastx::write_fasta: one line per sequence
         fa += ">" + nm[a] + "\n";
         fa.append(reinterpret_cast<const char*>(seqs) + seq_off[a], seq_off[a + 1] - seq_off[a]);
         fa += "\n";
     }
-    f.fasta = bytes_malloc(fa.data(), fa.size()); f.fasta_len = fa.size();
+    f.fasta = h.bytes(fa); f.fasta_len = fa.size();
     if (kmers && kmers_len) {                                                                            // 488-503: both blocks, or none
         std::vector<uint64_t> slen(n);
         for (uint32_t a = 0; a < n; a++) slen[a] = seq_off[a + 1] - seq_off[a];
@@ -667,7 +634,7 @@ void thin_files(uint32_t n, const std::vector<std::string>& nm, const uint8_t* s
         uint64_t used1 = 0, used2 = 0;
         bool ok = thin_kmer_block(kmers, kmers_len, keep, slen, &used1, blocks);
         ok = thin_kmer_block(kmers + used1, kmers_len - used1, keep, slen, &used2, blocks) && ok;
-        if (ok) { f.kmers = bytes_malloc(blocks.data(), blocks.size()); f.kmers_len = blocks.size(); }
+        if (ok) { f.kmers = h.copy(blocks); f.kmers_len = blocks.size(); }
         else f.warn_bits |= LCTY_PRUNE_WARN_KMERS;
     }
     if (distances && distances_len) {                                                                    // 505-513
@@ -681,10 +648,10 @@ void thin_files(uint32_t n, const std::vector<std::string>& nm, const uint8_t* s
         std::vector<uint8_t> db;
         sub.push_back(0);                                                                                // never read: a valid pointer for m = 1
         sized([&](uint8_t* o, uint64_t c, uint64_t* nd) { return lcty_distances_write(dk, dw, m, sub.data(), o, c, nd); }, db);
-        f.distances = bytes_malloc(db.data(), db.size()); f.distances_len = db.size();
+        f.distances = h.copy(db); f.distances_len = db.size();
     }
     const std::string pp = prune_paf(paf, paf_len, nm, keep);
-    f.paf = bytes_malloc(pp.data(), pp.size()); f.paf_len = pp.size();
+    f.paf = h.bytes(pp); f.paf_len = pp.size();
 }
 
 void prune_files_free(lcty_prune_files* f) {
@@ -745,12 +712,14 @@ int32_t lcty_prune_linkage(lcty_ctx* ctx, uint32_t n, const double* tri, lcty_pr
 
 int32_t lcty_prune_cluster(lcty_ctx* ctx, uint32_t n, const double* tri, const uint32_t* mult, const lcty_prune_params* params, lcty_prune_out* out) {
     return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         check_n(n);
         check_params(params);
         check_tri(n, tri);
-        cluster(ctx, n, tri, mult, params, out);
+        lcty_prune_out o{}; Handoff h;
+        cluster(ctx, n, tri, mult, params, h, o);
+        *out = o; h.commit();
     });
 }
 
@@ -761,19 +730,23 @@ void lcty_prune_out_free(lcty_prune_out* out) {
 int32_t lcty_prune_texts(uint32_t n, const char* names, const char* old_discarded, uint64_t old_len, const lcty_prune_out* res, uint8_t** newick,
                          uint64_t* newick_len, uint8_t** discarded, uint64_t* discarded_len) {
     return guarded([&] {
+        if (newick) *newick = nullptr;
+        if (newick_len) *newick_len = 0;
+        if (discarded) *discarded = nullptr;
+        if (discarded_len) *discarded_len = 0;
         if (!res || !newick || !newick_len || !discarded || !discarded_len) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         if (n < 1) fail(LCTY_ERR_INVALID_INPUT, "no haplotypes");
-        const std::vector<std::string> nm = split_names0(names, n);
+        const std::vector<std::string> nm = split_names(names, n);
         if (!old_discarded) old_len = 0;
         const std::vector<std::vector<std::string>> disc = discarded_by_contig(old_discarded, old_len, nm, nullptr);
         std::string nwk, lines;
         texts(n, nm, disc, res, &nwk, &lines);
         std::string all(old_discarded ? old_discarded : "", old_len);
         all += lines;
-        uint8_t* a = bytes_malloc(nwk.data(), nwk.size());
-        uint8_t* b;
-        try { b = bytes_malloc(all.data(), all.size()); } catch (...) { free(a); throw; }
+        Handoff h;
+        uint8_t* a = h.bytes(nwk); uint8_t* b = h.bytes(all);
         *newick = a; *newick_len = nwk.size(); *discarded = b; *discarded_len = all.size();
+        h.commit();
     });
 }
 
@@ -783,19 +756,17 @@ int32_t lcty_prune_thin(uint32_t n, const char* names, const uint8_t* seqs, cons
     return guarded([&] {
         if (!out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         memset(out, 0, sizeof(*out));
-        if (!seqs || !seq_off || !paf || !keep) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        if (n < 1 || n_keep < 1) fail(LCTY_ERR_INVALID_INPUT, "no haplotypes");
-        for (uint32_t a = 0; a < n; a++) if (seq_off[a + 1] < seq_off[a]) fail(LCTY_ERR_INVALID_INPUT, "seq_off is not ascending at %u", a);
+        if (!paf || !keep) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (n_keep < 1) fail(LCTY_ERR_INVALID_INPUT, "no haplotypes");
+        check_haps(n, seqs, seq_off, kPruneHaps);
         for (uint32_t t = 0; t < n_keep; t++)
             if (keep[t] >= n || (t && keep[t] <= keep[t - 1])) fail(LCTY_ERR_INVALID_INPUT, "keep must be ascending ids below %u", n);
-        const std::vector<std::string> nm = split_names0(names, n);
+        const std::vector<std::string> nm = split_names(names, n);
         const std::vector<uint32_t> kv(keep, keep + n_keep);
-        lcty_prune_files f{};
-        try {
-            f.keep = vec_malloc(kv); f.n_keep = n_keep;
-            thin_files(n, nm, seqs, seq_off, paf, paf_len, kmers, kmers_len, distances, distances_len, kv, f);
-        } catch (...) { prune_files_free(&f); throw; }
-        *out = f;
+        lcty_prune_files f{}; Handoff h;
+        f.keep = h.copy(kv); f.n_keep = n_keep;
+        thin_files(n, nm, seqs, seq_off, paf, paf_len, kmers, kmers_len, distances, distances_len, kv, h, f);
+        *out = f; h.commit();
     });
 }
 
@@ -803,48 +774,41 @@ int32_t lcty_db_prune_locus(lcty_ctx* ctx, uint32_t n, const char* names, const 
                             const uint8_t* kmers, uint64_t kmers_len, const uint8_t* distances, uint64_t distances_len, const char* discarded,
                             uint64_t discarded_len, const char* field, const lcty_prune_params* params, lcty_prune_files* out) {
     return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
         if (!ctx || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        memset(out, 0, sizeof(*out));
         check_params(params);
         if (n < 1) fail(LCTY_ERR_INVALID_DATA, "No haplotypes found");                                   // process_locus, 528-530
         check_n(n);
-        if (!seqs || !seq_off || !paf) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        for (uint32_t a = 0; a < n; a++) if (seq_off[a + 1] < seq_off[a]) fail(LCTY_ERR_INVALID_INPUT, "seq_off is not ascending at %u", a);
-        const std::vector<std::string> nm = split_names0(names, n);
-        lcty_prune_files f{};
-        lcty_prune_out res{};
-        try {
-            const double repl = params->n_clusters ? std::numeric_limits<double>::infinity() : 10.0 * params->threshold;   // 537
-            std::vector<double> tri(std::max<uint64_t>(tri_len(n), 1));
-            paf_divergences(paf, paf_len, nm, field, repl, tri.data(), &f.div);
-            if (params->skip_tree || !discarded) { discarded = nullptr; discarded_len = 0; }             // 542-547: not read with --skip-tree
-            const std::vector<std::vector<std::string>> disc = discarded_by_contig(discarded, discarded_len, nm, nullptr);
-            std::vector<uint32_t> mult(n);
-            for (uint32_t i = 0; i < n; i++) mult[i] = 1 + static_cast<uint32_t>(disc[i].size());
-            cluster(ctx, n, tri.data(), mult.data(), params, &res);
-            f.stats = res.stats; f.threshold = res.threshold;
-            std::string nwk, lines;
-            texts(n, nm, disc, &res, params->skip_tree ? nullptr : &nwk, &lines);
-            f.newick = bytes_malloc(nwk.data(), nwk.size()); f.newick_len = nwk.size();
-            const std::vector<uint32_t> keep(res.keep_ids, res.keep_ids + res.n_clusters);
-            f.keep = vec_malloc(keep); f.n_keep = res.n_clusters;
-            if (!params->only_tree) {
-                std::string all(discarded ? discarded : "", discarded_len);
-                all += lines;
-                f.discarded = bytes_malloc(all.data(), all.size()); f.discarded_len = all.size();
-                if (keep.size() == n) {
-                    f.unchanged = 1;                                                                     // copy_output_files, 475-478
-                } else {
-                    thin_files(n, nm, seqs, seq_off, paf, paf_len, kmers, kmers_len, distances, distances_len, keep, f);
-                }
+        if (!paf) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        check_haps(n, seqs, seq_off, kPruneHaps);
+        const std::vector<std::string> nm = split_names(names, n);
+        lcty_prune_files f{}; Handoff h;
+        lcty_prune_out res{}; Handoff h_res;                                                             // the clustering: used here, never handed out
+        const double repl = params->n_clusters ? std::numeric_limits<double>::infinity() : 10.0 * params->threshold;   // 537
+        std::vector<double> tri(std::max<uint64_t>(tri_len(n), 1));
+        paf_divergences(paf, paf_len, nm, field, repl, tri.data(), &f.div);
+        if (params->skip_tree || !discarded) { discarded = nullptr; discarded_len = 0; }             // 542-547: not read with --skip-tree
+        const std::vector<std::vector<std::string>> disc = discarded_by_contig(discarded, discarded_len, nm, nullptr);
+        std::vector<uint32_t> mult(n);
+        for (uint32_t i = 0; i < n; i++) mult[i] = 1 + static_cast<uint32_t>(disc[i].size());
+        cluster(ctx, n, tri.data(), mult.data(), params, h_res, res);
+        f.stats = res.stats; f.threshold = res.threshold;
+        std::string nwk, lines;
+        texts(n, nm, disc, &res, params->skip_tree ? nullptr : &nwk, &lines);
+        f.newick = h.bytes(nwk); f.newick_len = nwk.size();
+        const std::vector<uint32_t> keep(res.keep_ids, res.keep_ids + res.n_clusters);
+        f.keep = h.copy(keep); f.n_keep = res.n_clusters;
+        if (!params->only_tree) {
+            std::string all(discarded ? discarded : "", discarded_len);
+            all += lines;
+            f.discarded = h.bytes(all); f.discarded_len = all.size();
+            if (keep.size() == n) {
+                f.unchanged = 1;                                                                     // copy_output_files, 475-478
+            } else {
+                thin_files(n, nm, seqs, seq_off, paf, paf_len, kmers, kmers_len, distances, distances_len, keep, h, f);
             }
-        } catch (...) {
-            prune_out_free(&res);
-            prune_files_free(&f);
-            throw;
         }
-        prune_out_free(&res);
-        *out = f;
+        *out = f; h.commit();
     });
 }
 
