@@ -257,7 +257,9 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       LCTY_ERR_UNSUPPORTED naming this knob — it never takes another route);   "pafvcf_hash_bits"   bits kept of the hash of an
  *       allele's bytes in lcty_pafvcf_table (default 64; fewer: collisions, which the comparison of the bytes must reject);
  *       "pafvcf_table_mb"   megabytes the resident allele table (n_ranges x n_seqs x 4 bytes) of lcty_pafvcf_table / lcty_paf_to_vcf may
- *       take (default: a quarter of the free device memory; a larger table is LCTY_ERR_UNSUPPORTED naming this knob).
+ *       take (default: a quarter of the free device memory; a larger table is LCTY_ERR_UNSUPPORTED naming this knob);
+ *       "genome_max_bases"   positions (bases + one separator per contig) a resident genome may reach (default 2^32; lcty_genome_append
+ *       refuses a piece that reaches it with LCTY_ERR_UNSUPPORTED before it uploads anything).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -1628,6 +1630,53 @@ int32_t lcty_prune_thin(uint32_t n, const char* names, const uint8_t* seqs, cons
                         const uint8_t* kmers, uint64_t kmers_len, const uint8_t* distances, uint64_t distances_len, const uint32_t* keep,
                         uint32_t n_keep, lcty_prune_files* out);
 void    lcty_prune_files_free(lcty_prune_files* files);
+
+/* ---- a resident genome: its k-mer counts for a locus and its reference windows (lcty_genome.hip) ------------------
+ * Replaces JfKmerGetter::new / fetch (src/seq/counts.rs:258-369: `jellyfish query` against a whole-genome database, called for the
+ * flanks of expand_locus, command/add.rs:502; every haplotype plus the reference sequence, add.rs:633-636; the background region,
+ * command/preproc.rs:1373; the locus sequences of recruit, command/recruit.rs:540) and seq::fetch_seq + standardize
+ * (src/seq/mod.rs:26-38, 149). No database of every k-mer is built: a call counts the k-mers of ITS sequences in one pass over the
+ * genome, which stays on the device packed at 3 bits a base. Parity with the jellyfish binary is not pinned (there is none to run);
+ * the definition is the one below, restated in tests/pyref_kmer_count.py.
+ *   Genome: named contigs. A C G T a c g t are the bases (case folded); every other letter seq::standardize accepts (N and the IUPAC
+ *   codes, either case) is "not a base"; any other byte is LCTY_ERR_INVALID_DATA naming contig, position and byte, and the genome
+ *   is unusable from then on. A k-mer occurrence is k consecutive bases of one contig. count(x) = occurrences whose canonical form
+ *   (src/seq/kmers.rs:163-202) equals canonical(x).
+ * lcty_genome_append: one contig (continues == 0: `name` is its name), or the next piece of the contig that is open (continues != 0,
+ *   name ignored). Pieces of any length give the same genome as one piece. ASCII is uploaded as it is (at link rate from
+ *   lcty_host_alloc memory) and packed by a kernel. All positions, one separator per contig included, stay below 2^32 (32-bit
+ *   counters cannot wrap): more is LCTY_ERR_UNSUPPORTED before anything is uploaded (knob "genome_max_bases").
+ * lcty_genome_load_fasta: a FASTA file, plain or gzip / BGZF, multi-line, \n or \r\n; the name is the header up to the first blank
+ *   (src/seq/fastx.rs:417-419). Empty lines are skipped; sequence before the first header is LCTY_ERR_INVALID_DATA.
+ * lcty_genome_info / _contig: the contigs in order; name_buf (may be NULL) takes the 0-terminated name, cap its size.
+ * lcty_genome_fetch: out[end - start] = the window [start, end) of the contig (0-based) as fetch_seq + standardize leave it: capitals
+ *   A C G T, N for everything else. start >= end, end beyond the contig, an unknown name: LCTY_ERR_INVALID_INPUT.
+ * lcty_genome_kmer_counts: JfKmerGetter::fetch. Sequence i (seq_off[n_seqs + 1] into seqs, upper-case A C G T only) gets
+ *   max(len_i + 1 - k, 0) values at counts[cnt_off[i]..cnt_off[i + 1]); cnt_off[n_seqs + 1] is written, counts is the caller's
+ *   (cnt_off[n_seqs] values: sized from the lengths). A value is max(min(count, max_value), 1) with max_value = 65 535 for
+ *   counter_bytes >= 2, else 255 (counts.rs:297-303; the floor of 1: 354-355). A sequence with N: LCTY_ERR_RUNTIME "Cannot count
+ *   k-mers for sequence with Ns" (326-328); any other byte outside the four capitals: LCTY_ERR_INVALID_INPUT. k even:
+ *   LCTY_ERR_INVALID_DATA with the message of 284-286; 1 <= k <= 31 runs; 33 <= k <= 63: LCTY_ERR_UNSUPPORTED. counter_bytes outside
+ *   1..8: LCTY_ERR_INVALID_INPUT (292-295). Kernels, on the context's stream, workspace per call: byte check; the distinct canonical
+ *   k-mers of the query into an open-addressing table (load <= 0.5); the scan (a thread per LCTY_GENOME_SCAN_RUN k-mer starts of the
+ *   packed genome); the gather. Every count is exact. The genome is only read: calls on one genome come from one thread at a time. */
+#define LCTY_GENOME_SCAN_RUN 128u
+typedef struct lcty_genome lcty_genome;
+typedef struct lcty_genome_count_stats {
+    uint64_t n_query_kmers, n_distinct, table_slots;   /* values returned; distinct canonical k-mers among them; slots of the table */
+    uint64_t n_scanned, n_hits;                        /* genome positions (separators included) the scan went over; lookups that hit */
+    uint32_t scan_run, _pad0;                          /* LCTY_GENOME_SCAN_RUN */
+    double   table_ms, scan_ms, gather_ms, total_ms;   /* device events: check + table, scan, gather + download; host clock: the call */
+} lcty_genome_count_stats;
+int32_t lcty_genome_create(lcty_ctx* ctx, lcty_genome** out);
+void    lcty_genome_destroy(lcty_genome* genome);
+int32_t lcty_genome_append(lcty_genome* genome, const char* name, const uint8_t* bases, uint64_t len, int32_t continues);
+int32_t lcty_genome_load_fasta(lcty_ctx* ctx, const char* path, lcty_genome** out);
+int32_t lcty_genome_info(const lcty_genome* genome, uint32_t* n_contigs, uint64_t* n_bases);
+int32_t lcty_genome_contig(const lcty_genome* genome, uint32_t i, char* name_buf, uint64_t cap, uint64_t* len);
+int32_t lcty_genome_fetch(const lcty_genome* genome, const char* contig_name, uint64_t start, uint64_t end, uint8_t* out);
+int32_t lcty_genome_kmer_counts(const lcty_genome* genome, uint32_t k, uint32_t counter_bytes, uint32_t n_seqs, const uint8_t* seqs,
+                                const uint64_t* seq_off, uint16_t* counts, uint64_t* cnt_off, lcty_genome_count_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -88,6 +88,14 @@ SIGNATURES = {
     "lcty_db_prune_locus": (I32, [VP, U32, C.c_char_p, VP, VP, VP, U64, VP, U64, VP, U64, C.c_char_p, U64, C.c_char_p, P(PruneParams), P(PruneFiles)]),
     "lcty_prune_thin": (I32, [U32, C.c_char_p, VP, VP, VP, U64, VP, U64, VP, U64, VP, U32, P(PruneFiles)]),
     "lcty_prune_files_free": (None, [P(PruneFiles)]),
+    "lcty_genome_create": (I32, [VP, P(VP)]),
+    "lcty_genome_destroy": (None, [VP]),
+    "lcty_genome_append": (I32, [VP, C.c_char_p, VP, U64, I32]),
+    "lcty_genome_load_fasta": (I32, [VP, C.c_char_p, P(VP)]),
+    "lcty_genome_info": (I32, [VP, P(U32), P(U64)]),
+    "lcty_genome_contig": (I32, [VP, U32, C.c_char_p, U64, P(U64)]),
+    "lcty_genome_fetch": (I32, [VP, C.c_char_p, U64, U64, VP]),
+    "lcty_genome_kmer_counts": (I32, [VP, U32, U32, U32, VP, VP, VP, VP, P(GenomeCountStats)]),
     "lcty_last_error": (C.c_char_p, []),
     "lcty_version": (C.c_char_p, []),
     "lcty_device_count": (I32, []),

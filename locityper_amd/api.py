@@ -1715,3 +1715,71 @@ def prune_thin(names, seqs, seq_off, paf, keep, kmers=None, distances=None):
         return _prune_files_dict(f)
     finally:
         lib().lcty_prune_files_free(C.byref(f))
+
+
+# ---- a resident genome: k-mer counts and reference windows (lcty_genome.hip) ---------------------------------------------------------
+class Genome:
+    """JfKmerGetter (src/seq/counts.rs:258-369) without a Jellyfish database, and seq::fetch_seq: the genome packed on the device."""
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+        self._h = VP()
+        check(lib().lcty_genome_create(ctx._h, C.byref(self._h)))
+
+    @classmethod
+    def from_fasta(cls, ctx, path):
+        g = cls.__new__(cls)
+        g._ctx, g._h = ctx, VP()
+        check(lib().lcty_genome_load_fasta(ctx._h, str(path).encode(), C.byref(g._h)))
+        return g
+
+    def append(self, name, bases, continues=False):
+        """One contig, or (continues) the next piece of the contig that is open. bases: bytes or a u8 array of ASCII."""
+        b = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, dtype=np.uint8)
+        check(lib().lcty_genome_append(self._h, None if name is None else name.encode(), b.ctypes.data if len(b) else None, len(b), int(continues)))
+
+    def contigs(self):
+        """[(name, length)] in order."""
+        n, nb = U32(), U64()
+        check(lib().lcty_genome_info(self._h, C.byref(n), C.byref(nb)))
+        out = []
+        buf = C.create_string_buffer(1 << 16)
+        for i in range(n.value):
+            ln = U64()
+            check(lib().lcty_genome_contig(self._h, i, buf, len(buf), C.byref(ln)))
+            out.append((buf.value.decode(), int(ln.value)))
+        return out
+
+    def n_bases(self):
+        nb = U64()
+        check(lib().lcty_genome_info(self._h, None, C.byref(nb)))
+        return int(nb.value)
+
+    def fetch(self, contig, start, end):
+        """The window [start, end) of a contig as bytes: capitals A C G T, N for everything else."""
+        out = np.zeros(max(int(end) - int(start), 1), dtype=np.uint8)
+        check(lib().lcty_genome_fetch(self._h, contig.encode(), int(start), int(end), out.ctypes.data))
+        return out[:int(end) - int(start)].tobytes()
+
+    def kmer_counts(self, seqs, off, k, counter_bytes=2):
+        """JfKmerGetter::fetch: (counts u16, cnt_off u64[n + 1], stats dict) for the sequences seqs[off[i]:off[i + 1]]."""
+        sq, so = _haps(seqs, off)
+        n = len(so) - 1
+        n_values = int(sum(max(int(so[i + 1] - so[i]) + 1 - int(k), 0) for i in range(n)))
+        counts = np.zeros(max(n_values, 1), dtype=np.uint16)
+        cnt_off = np.zeros(n + 1, dtype=np.uint64)
+        st = cdefs.GenomeCountStats()
+        check(lib().lcty_genome_kmer_counts(self._h, k, counter_bytes, n, sq.ctypes.data, so.ctypes.data, counts.ctypes.data, cnt_off.ctypes.data,
+                                            C.byref(st)))
+        return counts[:n_values], cnt_off, st.as_dict()
+
+    def close(self):
+        if self._h:
+            lib().lcty_genome_destroy(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

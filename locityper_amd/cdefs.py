@@ -649,3 +649,16 @@ class Call(C.Structure):                 # lcty_call
     _fields_ = [("n_out", C.c_uint64), ("ixs", C.c_uint64 * MAX_RESULT), ("ln_probs", C.c_double * MAX_RESULT),
                 ("quality", C.c_double), ("unexpl_reads", C.c_uint32), ("warnings", C.c_uint32), ("n_good", C.c_uint64),
                 ("kept_after_filter", C.c_uint64)]
+
+
+# ---- a resident genome (lcty_genome.hip) ----
+GENOME_SCAN_RUN = 128            # LCTY_GENOME_SCAN_RUN: k-mer starts per thread of the scan kernel
+
+
+class GenomeCountStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_query_kmers", "n_distinct", "table_slots", "n_scanned", "n_hits")] + \
+               [("scan_run", C.c_uint32), ("_pad0", C.c_uint32)] + \
+               [(n, C.c_double) for n in ("table_ms", "scan_ms", "gather_ms", "total_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}

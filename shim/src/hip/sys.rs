@@ -21,6 +21,24 @@ pub const LCTY_SOLVER_EXACT: i32 = 2;
 /// Opaque handles.
 #[repr(C)] pub struct lcty_ctx { _private: [u8; 0] }
 #[repr(C)] pub struct lcty_locus { _private: [u8; 0] }
+#[repr(C)] pub struct lcty_genome { _private: [u8; 0] }
+
+/// `lcty_genome_count_stats`: what a call of `lcty_genome_kmer_counts` did.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lcty_genome_count_stats {
+    pub n_query_kmers: u64,
+    pub n_distinct: u64,
+    pub table_slots: u64,
+    pub n_scanned: u64,
+    pub n_hits: u64,
+    pub scan_run: u32,
+    pub _pad0: u32,
+    pub table_ms: f64,
+    pub scan_ms: f64,
+    pub gather_ms: f64,
+    pub total_ms: f64,
+}
 
 /// `lcty_solver`: the parameters of `Greedy` (stoch.rs:36-43), `SimAnneal` (stoch.rs:151-160) and of the exact solver.
 #[repr(C)]
@@ -75,4 +93,14 @@ extern "C" {
     pub fn lcty_rng_next_u64(state: *mut u64, out: *mut u64) -> i32;
     pub fn lcty_host_alloc(ctx: *mut lcty_ctx, bytes: u64, out: *mut *mut c_void) -> i32;
     pub fn lcty_host_free(p: *mut c_void);
+    // a resident genome: JfKmerGetter::new -> lcty_genome_load_fasta, fetch -> lcty_genome_kmer_counts, fetch_seq -> lcty_genome_fetch
+    pub fn lcty_genome_create(ctx: *mut lcty_ctx, out: *mut *mut lcty_genome) -> i32;
+    pub fn lcty_genome_destroy(genome: *mut lcty_genome);
+    pub fn lcty_genome_append(genome: *mut lcty_genome, name: *const c_char, bases: *const u8, len: u64, continues: i32) -> i32;
+    pub fn lcty_genome_load_fasta(ctx: *mut lcty_ctx, path: *const c_char, out: *mut *mut lcty_genome) -> i32;
+    pub fn lcty_genome_info(genome: *const lcty_genome, n_contigs: *mut u32, n_bases: *mut u64) -> i32;
+    pub fn lcty_genome_contig(genome: *const lcty_genome, i: u32, name_buf: *mut c_char, cap: u64, len: *mut u64) -> i32;
+    pub fn lcty_genome_fetch(genome: *const lcty_genome, contig_name: *const c_char, start: u64, end: u64, out: *mut u8) -> i32;
+    pub fn lcty_genome_kmer_counts(genome: *const lcty_genome, k: u32, counter_bytes: u32, n_seqs: u32, seqs: *const u8,
+        seq_off: *const u64, counts: *mut u16, cnt_off: *mut u64, stats: *mut lcty_genome_count_stats) -> i32;
 }
