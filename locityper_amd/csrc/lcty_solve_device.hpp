@@ -109,6 +109,8 @@ struct SolveView {
     double* parts;                  // [n_chains][4] aln_lik, depth_lik, solver iterations, accepted moves (diagnostics)
     uint32_t* overflow;             // set when a window got deeper than the depth table (the host widens it and repeats)
     double* dbg;                    // [wavefronts][8] clock cycles per phase of the greedy iteration (form 32 only)
+    uint32_t edge_trivial;          // 1: windows 0 and 1 of every chain of the launch have weight 0 — a location in those two only takes
+                                    // no depth gathers in the greedy loop; 0: no location is treated so
 };
 
 // a wave-uniform 64-bit value, told to the compiler as such (it then lives in scalar registers)

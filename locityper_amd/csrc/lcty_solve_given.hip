@@ -240,6 +240,7 @@ void solve_given(lcty_ctx* ctx, lcty_locus* loc, const lcty_depth_tables* T, con
     set_rec_list(V, R);
     V.ploidy = g->n_contigs ? g->n_contigs : 1; V.attempts = 1; V.solver = *solver; V.priors = nullptr;
     V.wstride = (W + 3) & ~3u;
+    V.edge_trivial = (W < 1 || g->window_weight[0] == 0.0) && (W < 2 || g->window_weight[1] == 0.0) ? 1u : 0u;      // the caller's weights, whatever they are
     if (!solver_lds_fits(V.wstride)) fail(LCTY_ERR_UNSUPPORTED, "%u windows per genotype: too many for the device solver", W);
     // the slot's depth table, wide enough for the deepest window: DistrCache (distr_cache.rs:61-75) of the locus, made on the device —
     // or the caller's rows (a power-of-two row stride; what lies behind a row's `width` is never read: deepest < width)

@@ -135,6 +135,7 @@ struct StageRunner {
         }
         V.ploidy = ploidy; V.attempts = attempts; V.solver = *solver;
         V.wstride = (2 + ploidy * loc->max_n_windows + 3) & ~3u;
+        V.edge_trivial = 1;                                                 // the initialisation kernels give windows 0 and 1 weight 0
         lds_init = init_chain_lds(V.wstride);
         if (!solver_lds_fits(V.wstride))
             fail(LCTY_ERR_UNSUPPORTED, "%u windows per genotype: too many for the device solver", V.wstride);

@@ -1046,6 +1046,14 @@ __device__ __forceinline__ void cand_loc(const RecBody& b, const GreedyExt& e, u
     *lp = l; *win = w;
 }
 
+// location k of a candidate for a k the compiler knows (k >= 3: the fourth)
+__device__ __forceinline__ void cand_loc_at(const RecBody& b, const GreedyExt& e, uint32_t k, double* lp, uint32_t* win) {
+    if (k == 0) { *lp = b.lp0; *win = b.win0; }
+    else if (k == 1) { *lp = b.lp1; *win = b.win1; }
+    else if (k == 2) { *lp = e.lp2; *win = e.win2; }
+    else { *lp = e.lp3; *win = e.win3; }
+}
+
 // With the weights in LDS a workgroup is two wavefronts that share the two tables (nothing else: after one barrier they run apart)
 template <uint32_t LPC, bool LW, uint32_t GREEDY_FORM = 0>
 __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveView V, const uint32_t n_chains) {
@@ -1115,10 +1123,12 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
     Xoshiro rng; rng.seed(V.seeds[chain]);
     uint64_t n_iter = 0, n_acc = 0;
     const double rel_contrib = V.depth_contrib / V.aln_contrib;
+    const uint32_t first_live = V.edge_trivial ? 2u : 0u;                        // the first window that can carry a distribution (SolveView::edge_trivial)
     double depth_mine = 0.0, aln_mine = 0.0;                                     // likelihood changes of the moves this lane applied
 
     bool done = nnt == 0 || !live_row;
     uint64_t phase[5] = {0, 0, 0, 0, 0}, sub[4] = {0, 0, 0, 0}, t_loop0 = 0;
+    [[maybe_unused]] uint64_t n_round1 = 0;                                      // (form 32) iterations of this wavefront with a round for the second alternative
     if (__any(!done)) {
         const uint32_t nnt1 = max(nnt, 1u);
         const uint64_t max_iter = max(static_cast<uint64_t>(100000), static_cast<uint64_t>(V.solver.plato_size) * 100);
@@ -1253,25 +1263,36 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
             if constexpr (TIMED) asm volatile("" :: "v"(w1), "v"(w2), "v"(cur_lp));
             subtick(0);
             // up to three alternatives per lane, all requested before any is used. The pair of the current location is the same
-            // for all of them: requested once; an alternative adds the pair of its own two windows.
+            // for all of them: requested once; an alternative adds the pair of its own two windows — when it has one to add: with
+            // V.edge_trivial an alternative in windows 0 and 1 only ("both mates unmapped") changes no window that carries a distribution,
+            // its two terms are 0.0 whatever the depths, and it takes no gathers. Alternative u >= 1 gets its round of depths, gathers and
+            // terms when one of the wavefront's candidates has a REAL one there (a window from first_live on): a read with three
+            // locations is nearly always two contigs and "unmapped", the last of them, and the wavefront then takes one round.
             constexpr uint32_t NA = GREEDY_INLINE_LOCS - 1;
             double lp_t[NA]; uint32_t win_t[NA], t_of[NA];
+            bool has_t[NA], real[NA];
             PairGather gc, ga[NA];
             bool cross[NA];
             C.request_pair(w1, w2, -1, gc);
             subtick(1);
 #pragma unroll
             for (uint32_t u = 0; u < NA; u++) {
+                // alternative u is location u, or u + 1 from the current location on: one select between two known registers
+                const bool up = u >= cur;
+                double lp_lo, lp_up; uint32_t win_lo, win_up;
+                cand_loc_at(b, EAu, u, &lp_lo, &win_lo); cand_loc_at(b, EAu, u + 1, &lp_up, &win_up);
+                t_of[u] = u + (up ? 1u : 0u);
+                has_t[u] = u < n_alt && !(deep && t_of[u] >= GREEDY_INLINE_LOCS);
+                lp_t[u] = up ? lp_up : lp_lo; win_t[u] = has_t[u] ? (up ? win_up : win_lo) : 0u;
+                real[u] = has_t[u] && ((win_t[u] & 0xFFFFu) >= first_live || (win_t[u] >> 16) >= first_live);
                 if (u == 1) subtick(2);
-                const bool has = u < n_alt && !(deep && u + (u >= cur ? 1u : 0u) >= GREEDY_INLINE_LOCS);
-                t_of[u] = u + (u >= cur ? 1u : 0u);
-                lp_t[u] = 0.0; win_t[u] = 0; cross[u] = false;
-                if (u == 0 || __any(has)) {
-                    if (has) cand_loc(b, EAu, t_of[u], &lp_t[u], &win_t[u]);
-                    const uint32_t a3 = has ? (win_t[u] & 0xFFFFu) : 0u, a4 = has ? (win_t[u] >> 16) : 0u;
+                cross[u] = false;
+                if (u == 0 || __any(real[u])) {
+                    const uint32_t a3 = real[u] ? (win_t[u] & 0xFFFFu) : 0u, a4 = real[u] ? (win_t[u] >> 16) : 0u;
                     C.request_pair(a3, a4, 1, ga[u]);
-                    // a window shared between the two pairs (windows 0 and 1 carry no distribution: sharing them changes nothing)
-                    cross[u] = has && ((a3 > 1 && (a3 == w1 || a3 == w2)) || (a4 > 1 && (a4 == w1 || a4 == w2)));
+                    // a window shared between the two pairs (windows that carry no distribution: sharing them changes nothing)
+                    cross[u] = real[u] && ((a3 >= first_live && (a3 == w1 || a3 == w2)) || (a4 >= first_live && (a4 == w1 || a4 == w2)));
+                    if constexpr (TIMED) { if (u == 1 && !done) n_round1++; }
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1287,22 +1308,29 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
             uint32_t deepest = 0;
             const double t1 = pair_term(gc, 0, &deepest);
             const double t12 = t1 + pair_term(gc, 1, &deepest);
+            // an alternative without gathers: both of its terms are 0.0, added as the others' are (-0.0 + 0.0 is 0.0, not -0.0)
+            const double dd_trivial = (t12 + 0.0) + 0.0;
 #pragma unroll
             for (uint32_t u = 0; u < NA; u++) {
-                const bool has = u < n_alt && !(deep && t_of[u] >= GREEDY_INLINE_LOCS);
-                if (u == 0 || __any(has)) {
-                    const double t3 = pair_term(ga[u], 0, &deepest);
-                    double dd = (t12 + t3) + pair_term(ga[u], 1, &deepest);
+                double dd = dd_trivial;
+                if (u == 0 || __any(real[u])) {
+                    uint32_t deep_u = 0;                                          // a round's look at window 0 for a lane with nothing to ask is no depth the chain reaches
+                    const double t3 = pair_term(ga[u], 0, &deep_u);
+                    double dd_g = (t12 + t3) + pair_term(ga[u], 1, &deep_u);
+                    deepest = max(deepest, real[u] ? deep_u : 0u);
                     if (__any(cross[u])) {
-                        if (cross[u]) dd = C.depth_lik_diff(w1, w2, win_t[u] & 0xFFFFu, win_t[u] >> 16);
+                        if (cross[u]) dd_g = C.depth_lik_diff(w1, w2, win_t[u] & 0xFFFFu, win_t[u] >> 16);
                     }
-                    const double improv = lp_t[u] + rel_contrib * dd;
-                    if (has && (u == 0 || improv > best_improv)) {
-                        best_improv = improv; new_assgn = t_of[u]; w3 = win_t[u] & 0xFFFFu; w4 = win_t[u] >> 16; lp_new = lp_t[u]; ddiff = dd;
-                    }
+                    dd = real[u] ? dd_g : dd;
+                }
+                const double improv = lp_t[u] + rel_contrib * dd;
+                if (has_t[u] && (u == 0 || improv > best_improv)) {
+                    best_improv = improv; new_assgn = t_of[u]; w3 = win_t[u] & 0xFFFFu; w4 = win_t[u] >> 16; lp_new = lp_t[u]; ddiff = dd;
                 }
             }
-            if (deepest > V.lut_depth - 1) atomicMax(V.overflow, 1u);            // every chain of the batch is repeated
+            // every chain of the batch is repeated (lanes without a candidate looked at window 0 for nothing: where a caller gives that window
+            // a weight, its depth minus two is no depth of the chain)
+            if (n_alt && deepest > V.lut_depth - 1) atomicMax(V.overflow, 1u);
             if (__any(deep)) {
                 // reads with more than four locations: the ones beyond the fourth from the chain's run, one at a time, in their place
                 // in the order (a read's alternatives are visited by ascending location; those in registers may come after these
@@ -1395,7 +1423,7 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
         if (lane == 0 && V.dbg) {
             double* d = V.dbg + (static_cast<size_t>(blockIdx.x) * WAVES + wave) * 12;
             for (int k = 0; k < 5; k++) d[k] = static_cast<double>(phase[k]);
-            d[5] = static_cast<double>(__builtin_amdgcn_s_memtime() - t_loop0); d[6] = static_cast<double>(n_iter); d[7] = 0.0;
+            d[5] = static_cast<double>(__builtin_amdgcn_s_memtime() - t_loop0); d[6] = static_cast<double>(n_iter); d[7] = static_cast<double>(n_round1);
             for (int k = 0; k < 4; k++) d[8 + k] = static_cast<double>(sub[k]);
         }
     }
@@ -2078,8 +2106,8 @@ void launch_greedy_chains(lcty_ctx* ctx, SolveView& V, uint32_t nch, hipStream_t
         LCTY_HIP(hipStreamSynchronize(stream));
         double sum[12] = {0}; size_t used = 0;
         for (size_t w = 0; w < n_waves; w++) if (d[12 * w + 6] > 0) { used++; for (int k = 0; k < 12; k++) sum[k] += d[12 * w + k] / d[12 * w + 6]; }
-        if (used) fprintf(stderr, "[lcty greedy phases] %zu wavefronts; clock ticks per iteration: candidates+requests %.0f (waiting for the further locations %.0f, current location %.0f, its pair %.0f, first alternative %.0f), ext+sample+record request %.0f, wait+score %.0f, row best %.0f, move %.0f; loop total %.0f\n",
-                          used, sum[0] / used, sum[11] / used, sum[8] / used, sum[9] / used, sum[10] / used, sum[1] / used, sum[2] / used, sum[3] / used, sum[4] / used, sum[5] / used);
+        if (used) fprintf(stderr, "[lcty greedy phases] %zu wavefronts; clock ticks per iteration: candidates+requests %.0f (waiting for the further locations %.0f, current location %.0f, its pair %.0f, first alternative %.0f), ext+sample+record request %.0f, wait+score %.0f, row best %.0f, move %.0f; loop total %.0f; a round for the second alternative in %.3f of the iterations\n",
+                          used, sum[0] / used, sum[11] / used, sum[8] / used, sum[9] / used, sum[10] / used, sum[1] / used, sum[2] / used, sum[3] / used, sum[4] / used, sum[5] / used, sum[7] / used);
     }
 }
 

@@ -1,7 +1,9 @@
 """Developer measurement: the solver stages of BASELINE configs[1] (1 M read pairs x 256 alleles) ALONE, once per knob setting:
-   python3 scripts/solve_probe.py [--diag] [--chains 5000] [--short] [--base-len 50000] name=value[,name=value...] ...
+   python3 scripts/solve_probe.py [--diag] [--lib FILE] [--save FILE] [--chains 5000] [--short] [--base-len 50000] name=value[,name=value...] ...
 For every setting: solve_init_kernel and greedy_loop_kernel times of the default greedy stage (5 000 chains, 100 000 iterations;
---short: plateau 1, the stage is its initialisation) and whether the per-chain likelihoods equal those of the first setting bit for bit."""
+--short: plateau 1, the stage is its initialisation) and whether the per-chain likelihoods equal those of the first setting bit for bit.
+--save FILE writes the per-chain likelihoods of the LAST setting as .npy: a run with --lib <another build of the library> and one
+without can then be compared bit for bit at full size (numpy.array_equal of the two files)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,6 +17,7 @@ def main():
     anneal = False                                    # --anneal: the annealing stage of the default scheme instead (20 genotypes x 20 attempts)
     settings = []
     sort_gts = False
+    save = None
     base_len = 50_000                                 # --base-len: shorter alleles = fewer windows per chain = more greedy wavefronts per CU
     i = 0
     while i < len(args):
@@ -25,6 +28,7 @@ def main():
         elif args[i] == "--diag":                                 # the developer build: knobs such as solve_stats, solve_greedy_form, solve_init_tiles exist there only
             from locityper_amd import _lib
             _lib.use_diag_build(); i += 1
+        elif args[i] == "--save": save = args[i + 1]; i += 2
         elif args[i] == "--short": short = True; i += 1
         elif args[i] == "--base-len": base_len = int(args[i + 1]); i += 2
         elif args[i] == "--sort-genotypes": sort_gts = True; i += 1      # the stage's genotypes in lexicographic order instead of by prefilter score
@@ -69,6 +73,9 @@ def main():
         print(f"{st}: {ch_} chains, {it_} iterations, {acc_} accepted; init {ctx.timing(api.K_SOLVE_INIT)[1]:.1f} ms, loop {ctx.timing(api.K_ANNEAL if anneal else api.K_SOLVE)[1]:.1f} ms, wall {1e3 * wall:.1f} ms, "
               f"likelihoods equal the first setting's: {bool(np.array_equal(l, first))} (largest relative difference {float(np.max(np.abs(l - first) / np.abs(first))):.3g})", flush=True)
         for k, _ in knobs: ctx.set_knob(k, -1)
+        last = l
+    if save:
+        with open(save, "wb") as f: np.save(f, last)
 
 
 main()
