@@ -923,7 +923,8 @@ struct Chain {
     // depth_lik_diff in two halves of two windows: the current location's pair (w1, w2: depths go down) is the same for every
     // alternative location of a read, so the greedy loop requests it once and each alternative's pair (w3, w4: depths go up) once.
     // Inside a pair the coincidence rule of assgn.rs:259-284 is applied as written (w2 == w1: -2 / 0; w4 == w3: +2 / 0); a window
-    // shared BETWEEN the pairs changes both halves — the caller detects that (rare) and takes depth_lik_diff instead.
+    // shared BETWEEN the pairs changes both halves — the caller detects that and corrects the sum (diff_with_shared_window in the greedy
+    // loop: from the gathered terms where every window changes by one at most, through depth_lik_diff otherwise).
     __device__ __forceinline__ void request_pair(uint32_t wa, uint32_t wb, int32_t dir, PairGather& g) const {
         const int32_t same = wb == wa;
         g.c[0] = dir * (1 + same); g.c[1] = same ? 0 : dir;
@@ -1306,8 +1307,21 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
             double best_improv = -INFINITY, lp_new = 0.0, ddiff = 0.0;
             uint32_t new_assgn = 0, w3 = 0, w4 = 0;
             uint32_t deepest = 0;
-            const double t1 = pair_term(gc, 0, &deepest);
-            const double t12 = t1 + pair_term(gc, 1, &deepest);
+            const double t1 = pair_term(gc, 0, &deepest), t2 = pair_term(gc, 1, &deepest);
+            const double t12 = t1 + t2;
+            // depth_lik_diff for an alternative (a3, a4) that shares a window with the current pair, from the terms t3, t4 of its own pair's
+            // gathers. With two different windows in each pair every window's depth changes by one at most: a shared window does not change at
+            // all (depth_lik_diff folds it into its first mention: c = 0 there and at the later one, both terms 0.0), the others change as they
+            // were gathered — the same four terms in the same order, from registers. Only a shared window next to a pair that lies in ONE
+            // window (a change by two against a change by one) needs table entries nobody asked for: those take the gathers of depth_lik_diff.
+            auto diff_with_shared_window = [&](uint32_t a3, uint32_t a4, double t3, double t4) -> double {
+                if (w1 != w2 && a3 != a4) {
+                    const double s1 = (a3 == w1 || a4 == w1) ? 0.0 : t1, s2 = (a3 == w2 || a4 == w2) ? 0.0 : t2;
+                    const double s3 = (a3 == w1 || a3 == w2) ? 0.0 : t3, s4 = (a4 == w1 || a4 == w2) ? 0.0 : t4;
+                    return ((s1 + s2) + s3) + s4;
+                }
+                return C.depth_lik_diff(w1, w2, a3, a4);
+            };
             // an alternative without gathers: both of its terms are 0.0, added as the others' are (-0.0 + 0.0 is 0.0, not -0.0)
             const double dd_trivial = (t12 + 0.0) + 0.0;
 #pragma unroll
@@ -1316,10 +1330,11 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
                 if (u == 0 || __any(real[u])) {
                     uint32_t deep_u = 0;                                          // a round's look at window 0 for a lane with nothing to ask is no depth the chain reaches
                     const double t3 = pair_term(ga[u], 0, &deep_u);
-                    double dd_g = (t12 + t3) + pair_term(ga[u], 1, &deep_u);
+                    const double t4 = pair_term(ga[u], 1, &deep_u);
+                    double dd_g = (t12 + t3) + t4;
                     deepest = max(deepest, real[u] ? deep_u : 0u);
                     if (__any(cross[u])) {
-                        if (cross[u]) dd_g = C.depth_lik_diff(w1, w2, win_t[u] & 0xFFFFu, win_t[u] >> 16);
+                        if (cross[u]) dd_g = diff_with_shared_window(win_t[u] & 0xFFFFu, win_t[u] >> 16, t3, t4);
                     }
                     dd = real[u] ? dd_g : dd;
                 }
@@ -1335,13 +1350,21 @@ __global__ __launch_bounds__(LW ? 128 : 64) void greedy_loop_kernel(const SolveV
                 // reads with more than four locations: the ones beyond the fourth from the chain's run, one at a time, in their place
                 // in the order (a read's alternatives are visited by ascending location; those in registers may come after these
                 // only when the current location is beyond the fourth — then none of the inline ones was skipped)
-                for (uint32_t u = 0; __any(deep && u < n_alt); u++) {
+                for (uint32_t u = NA; __any(deep && u < n_alt); u++) {            // (the alternatives below NA are the ones in registers)
                     const uint32_t t = u + (u >= cur ? 1u : 0u);
                     if (deep && u < n_alt && (u >= NA || t >= GREEDY_INLINE_LOCS)) {
                         double lp_u; uint32_t win_u;
                         rec_loc(b, extra, t, &lp_u, &win_u);
                         const uint32_t a3 = win_u & 0xFFFFu, a4 = win_u >> 16;
-                        const double dd = C.depth_lik_diff(w1, w2, a3, a4);
+                        // the current pair's terms are in registers: the alternative adds its own pair, as the inline ones do
+                        PairGather gu;
+                        C.request_pair(a3, a4, 1, gu);
+                        uint32_t deep_u = 0;
+                        const double t3 = pair_term(gu, 0, &deep_u), t4 = pair_term(gu, 1, &deep_u);
+                        double dd = (t12 + t3) + t4;
+                        if (deep_u > V.lut_depth - 1) atomicMax(V.overflow, 1u);
+                        if ((a3 >= first_live && (a3 == w1 || a3 == w2)) || (a4 >= first_live && (a4 == w1 || a4 == w2)))
+                            dd = diff_with_shared_window(a3, a4, t3, t4);
                         const double improv = lp_u + rel_contrib * dd;
                         // alternatives arrive in ascending u here as in the unrolled part: the inline ones have u < NA and t < 4
                         if (improv > best_improv) { best_improv = improv; new_assgn = t; w3 = a3; w4 = a4; lp_new = lp_u; ddiff = dd; }
