@@ -27,6 +27,7 @@
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
 #include "lcty_math.hpp"
+#include "lcty_scan.hpp"
 
 using namespace lcty;
 
@@ -37,11 +38,6 @@ constexpr uint32_t LONG_RECORD = 2048;       // query bases from which a record 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // device
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // 16 packed bases (2 bits each) starting at base `off`; the arrays carry one spare word at their end
 __device__ __forceinline__ uint32_t get16(const uint32_t* w, uint64_t off) {
     const uint64_t i = off >> 4;
@@ -75,7 +71,7 @@ __global__ void windows_kernel(const uint8_t* __restrict__ seq, uint32_t seq_len
     uint32_t gc = 0, low = 0;
     for (uint32_t i = start_ix + lane; i < end_ix; i += 64) { const uint8_t c = seq[i]; gc += (c == 'C') | (c == 'G'); }
     for (uint32_t i = start_ix + lane; i < end_ix2; i += 64) low += counts[i] <= 1;
-    gc = wave_sum(gc); low = wave_sum(low);
+    gc = wave_reduce(gc, AddOp{}); low = wave_reduce(low, AddOp{});
     if (lane == 0) { gc_out[wi] = gc; low_out[wi] = low; span_out[2 * wi] = end_ix - start_ix; span_out[2 * wi + 1] = end_ix2 - start_ix; }
 }
 
@@ -126,7 +122,7 @@ __device__ void count_record(const RecArgs& a, uint32_t r, uint32_t lane) {
             default: break;                                         // refused by the reader
         }
     }
-    const uint32_t eq = W > 1 ? wave_sum(eq_lane) : eq_lane;
+    const uint32_t eq = W > 1 ? wave_reduce(eq_lane, AddOp{}) : eq_lane;
     if (lane == 0) {
         m += eq; x -= eq;
         uint32_t* o = a.counts + 5ull * r;

@@ -44,11 +44,6 @@ constexpr uint32_t GR_BITS = 7 * GR_PLANES;
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ double wave_max_f64(double x) {
-    for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o));
-    return x;
-}
-
 // counters[0] columns handed out, [1] overflow of the column capacity, [2] residual rows, [3] largest weight (bits of the f64)
 template <uint32_t VPL>
 __global__ __launch_bounds__(256) void gram_levels_kernel(const double* __restrict__ M, uint64_t n_rows, uint32_t A, uint64_t k_cap, uint64_t kw,
@@ -81,7 +76,7 @@ __global__ __launch_bounds__(256) void gram_levels_kernel(const double* __restri
                 double cand = -INFINITY;
 #pragma unroll
                 for (uint32_t t = 0; t < VPL; t++) cand = fmax(cand, x[t] < prev ? x[t] : -INFINITY);
-                cand = wave_max_f64(cand);
+                cand = wave_reduce(cand, MaxOp{});
                 if (cand == -INFINITY) break;
                 if (k == lmax) { bad = true; break; }                          // one level too many (lmax <= 16)
                 if (lane == 0) lv[rr][k] = cand;

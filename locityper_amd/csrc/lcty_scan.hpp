@@ -1,5 +1,7 @@
-// lcty_scan.hpp — in-order scans, one definition each: of a wavefront (wave_scan_incl, every kernel that ranks or
-// places the items of its lanes), of one workgroup with any operation (launch_scan: sums and running maxima of lcty_panvcf.hip and
+// lcty_scan.hpp — in-order scans and the wavefront's reduction, one definition each: of a wavefront (wave_scan_incl,
+// every kernel that ranks or places the items of its lanes; wave_reduce, the minima, maxima and sums of lcty_score.hip, lcty_gram.hip
+// and lcty_bg.hip: their kernels compile to the same registers, occupancy and scratch through it, so none of those loops stays written
+// out), of one workgroup with any operation (launch_scan: sums and running maxima of lcty_panvcf.hip and
 // lcty_pafvcf.hip) and of any number of workgroups over 32-bit counts (exclusive_scan, ScanTotal: the radix sort of lcty_sort.hpp, the
 // run starts of lcty_map_index.hip, the offsets of lcty_pafvcf.hip; defined in lcty_sort.hip).
 // Two loops scan two values per step with one shuffle pair each and stay as they are written: the anchor ranks of
@@ -15,7 +17,15 @@ namespace lcty {
 constexpr int SCAN_THREADS = 1024;
 
 struct AddOp { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
-struct MaxOp { template <typename T> __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
+// doubles take fmax / fmin: a NaN loses to a number, as in the reference's f64::max / f64::min
+struct MaxOp {
+    template <typename T> __device__ T operator()(T a, T b) const { return a > b ? a : b; }
+    __device__ double operator()(double a, double b) const { return fmax(a, b); }
+};
+struct MinOp {
+    template <typename T> __device__ T operator()(T a, T b) const { return a < b ? a : b; }
+    __device__ double operator()(double a, double b) const { return fmin(a, b); }
+};
 
 // what a scan reads: element i of an array, widened where the sums need it
 struct LoadU32 { const uint32_t* p; __device__ uint32_t operator()(uint64_t i) const { return p[i]; } };
@@ -30,6 +40,13 @@ template <typename T, typename Op> __device__ inline T wave_scan_incl(T x, Op op
         const T y = __shfl_up(x, off);
         if (lane >= uint32_t(off)) x = op(y, x);
     }
+    return x;
+}
+
+// Reduction over the 64 lanes of the calling wavefront: EVERY lane gets op over all 64 values (a butterfly of xor shuffles; sums of
+// doubles are added in that order, the same in every lane). Every lane of the wavefront calls it.
+template <typename T, typename Op> __device__ inline T wave_reduce(T x, Op op) {
+    for (int off = WAVE / 2; off > 0; off >>= 1) x = op(x, __shfl_xor(x, off));
     return x;
 }
 

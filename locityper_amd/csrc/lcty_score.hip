@@ -45,22 +45,6 @@ static_assert(sizeof(Rec16) == 16, "Rec16 layout");
 struct __attribute__((packed, aligned(4))) W8 { uint32_t w[8]; };
 struct __attribute__((packed, aligned(4))) W4 { uint32_t w[4]; };
 
-__device__ inline uint32_t wave_min_u32(uint32_t v) {
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = min(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o)));
-    return v;
-}
-__device__ inline double wave_max_f64(double v) {
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ inline uint32_t wave_sum_u32(uint32_t v) {
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o));
-    return v;
-}
-__device__ inline double wave_sum_f64(double v) {
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // exclusive prefix sum across the wave; *total = wave sum
 __device__ inline uint32_t wave_excl_scan_u32(uint32_t v, int lane, uint32_t* total) {
     const uint32_t x = wave_scan_incl(v, AddOp{});
@@ -328,6 +312,10 @@ __device__ __forceinline__ AlnRef load_aln(const Rec16* rec, uint32_t idx, doubl
     return AlnRef{r.ln_prob - best_lik, r.start, r.end_rev & ~REV_BIT, idx, (r.end_rev & REV_BIT) != 0};   // normalize_probs, locs.rs:358-360
 }
 
+// an alignment lies in the central region of its contig (in_bounds, locs.rs:1008-1014); mid = Interval::middle (interv.rs:154-156)
+__device__ __forceinline__ bool in_bounds(uint32_t mid, uint32_t clen, uint32_t boundary) { return boundary <= mid && mid < clen - boundary; }
+__device__ __forceinline__ bool in_bounds(const AlnRef& a, uint32_t clen, uint32_t boundary) { return in_bounds((a.start + a.end) / 2, clen, boundary); }
+
 template <typename C, typename F> __device__ inline void enumerate_pairs(const C& c, F&& f);
 
 struct PairCtx {
@@ -406,7 +394,7 @@ struct SmallCtx {
 
 // General path, one (contig, end) group: copy the chain into `ord`, order by (ln_prob desc, record
 // index asc), drop later members of a 128-bp bin (locs.rs:321-342). Returns the kept count;
-// bit 31: some kept alignment lies in the central region (in_bounds, locs.rs:1008-1014).
+// bit 31: some kept alignment lies in the central region (in_bounds).
 __device__ __noinline__ uint32_t gather_sort_dedupe(const Rec16* rec, const uint16_t* nxt, uint32_t head, uint16_t* ord,
                                                     uint32_t boundary, uint32_t contig_len) {
     bool inb = false;
@@ -431,8 +419,7 @@ __device__ __noinline__ uint32_t gather_sort_dedupe(const Rec16* rec, const uint
         for (uint32_t u = 0; u < kept; u++) dup |= (rec[ord[u]].start >> 7) == bin;
         if (!dup) {
             ord[kept++] = v;
-            const uint32_t mid = (rec[v].start + (rec[v].end_rev & ~REV_BIT)) / 2;
-            if (boundary <= mid && mid < contig_len - boundary) inb = true;
+            if (in_bounds((rec[v].start + (rec[v].end_rev & ~REV_BIT)) / 2, contig_len, boundary)) inb = true;
         }
     }
     return kept | (inb ? 0x80000000u : 0u);
@@ -577,6 +564,279 @@ __device__ __forceinline__ void pair_barrier() {
     __syncthreads();
 }
 
+// ---- The rules of one read pair that every kernel form applies alike, stated once: both bodies below call them. ----
+
+// What the work on a pair starts from (locs.rs:502-510): its records, pair_meta (from the host), the mates' lengths, its row of the
+// matrix, and the mates' 2-bit words and N masks prefetched for K2 (lane l holds 64-bit word l and mask word l of each mate).
+struct PairHead {
+    uint64_t p;
+    const lcty_aln_rec* recs;
+    uint32_t j2, n_eff, split, len0, len1;
+    double* mrow;
+    bool regs_ok;                  // both mates fit the register path of the k-mer windows (k-mers of 32..63 bases take the general path)
+    uint64_t bw0, bw1;
+    uint32_t nm0, nm1;
+    __device__ __forceinline__ uint4 raw(uint32_t idx) const { return reinterpret_cast<const uint4*>(recs)[idx]; }
+    __device__ __forceinline__ uint4 raw_or_zero(uint32_t idx) const { return idx < n_eff ? raw(idx) : make_uint4(0, 0, 0, 0); }
+};
+
+__device__ __forceinline__ PairHead load_pair(const LocusView& L, const ReadsView& R, uint64_t p, bool paired, int lane) {
+    PairHead h;
+    h.p = p; h.recs = R.recs + R.aln_off[p];
+    const uint2 meta = R.pair_meta[p];                 // {index of the mate-2 primary (or n), records to look at}
+    h.j2 = meta.x; h.n_eff = meta.y;
+    h.split = min(h.j2, h.n_eff);
+    h.len0 = R.mate_len[2 * p]; h.len1 = paired ? R.mate_len[2 * p + 1] : 0u;
+    h.mrow = R.matrix + p * L.n_alleles;
+    h.regs_ok = h.len0 <= 2016 && h.len1 <= 2016 && L.k <= 31;
+    h.bw0 = h.bw1 = 0; h.nm0 = h.nm1 = 0;
+    if (h.regs_ok) {
+        const uint64_t off0 = R.mate_off[2 * p], off1 = R.mate_off[2 * p + 1];
+        if (static_cast<uint32_t>(lane) * 32u < h.len0) {
+            h.bw0 = (reinterpret_cast<const uint64_t*>(R.bases2) + (off0 >> 5))[lane];
+            h.nm0 = (R.nmask + (off0 >> 5))[lane];
+        }
+        if (static_cast<uint32_t>(lane) * 32u < h.len1) {
+            h.bw1 = (reinterpret_cast<const uint64_t*>(R.bases2) + (off1 >> 5))[lane];
+            h.nm1 = (R.nmask + (off1 >> 5))[lane];
+        }
+    }
+    return h;
+}
+
+// Thresholds of the two primaries (locs.rs:502-567): lane e < 2 scores the primary of read end e and looks up its edit thresholds
+// (EditDistCache, relaxed where the complexity around the alignment is poor: 529-536); every lane gets both ends' values. state: 1
+// examined-ok, 2 primary saved, 4 error. CNT: counted alignments (the lean kernels' form); else BAM records, `cig` = their CIGAR words.
+struct EndThresholds { uint32_t good, thr, passable, state; };
+struct PairThresholds {
+    EndThresholds e0, e1;
+    // a pair whose first primary was not pushed is rejected without looking further (locs.rs:539-543)
+    __device__ __forceinline__ bool look() const { return (e0.state & 3u) == 3u; }
+    __device__ __forceinline__ uint32_t passable(uint32_t e) const { return e ? e1.passable : e0.passable; }
+};
+
+template <bool CNT>
+__device__ __forceinline__ PairThresholds primary_thresholds(const LocusView& L, const PairHead& h, const uint32_t* cig, bool paired, int lane) {
+    EndThresholds my{0, NONE32, NONE32, 0};
+    if (lane < 2) {
+        const uint32_t e = lane;
+        const uint32_t pidx = e ? h.j2 : 0u;
+        const bool exists = e == 0 ? h.n_eff > 0 : (paired && h.j2 < h.n_eff);
+        if (e == 1 && !paired) {
+            my.state = 3;                                   // single-end: second end is vacuously fine
+        } else if (!exists) {
+            my.state = 4;                                   // expect("Cannot read any more records"), locs.rs:509
+        } else {
+            const uint4 praw = h.raw(pidx);
+            const lcty_aln_rec pr = h.recs[pidx];
+            const uint32_t read_len = e ? h.len1 : h.len0;
+            const uint32_t pflags = CNT ? ((praw.x >> 28 & 1u) ? LCTY_FLAG_REVERSE : 0u) | ((praw.x >> 29 & 1u) ? LCTY_FLAG_SECONDARY : 0u)
+                                          | ((praw.x >> 30 & 1u) ? LCTY_FLAG_UNMAPPED : 0u) : pr.flags;
+            const uint32_t pcontig = CNT ? (praw.y & 0xFFFFu) : pr.contig;
+            const bool is_primary = (pflags & (LCTY_FLAG_SECONDARY | LCTY_FLAG_SUPPL)) == 0;
+            if (read_len == 0 || !is_primary) my.state = 4;                 // locs.rs:511-517 / LaggedReader assert
+            else if (pflags & LCTY_FLAG_UNMAPPED) my.state = 0;             // locs.rs:520-523
+            else if ((!CNT && pr.n_cigar == 0) || pcontig >= L.n_alleles) my.state = 4;
+            else {
+                Scored sc;
+                if constexpr (CNT) sc = score_counted(L, praw);
+                else {
+                    const W8 w8 = *reinterpret_cast<const W8*>(cig + pr.cigar_rel);
+                    const OpCounts oc = count_ops(w8, cig + pr.cigar_rel, pr.n_cigar, true);
+                    sc = score_counts(L, oc, pr.pos, L.allele_len[pr.contig]);
+                }
+                if (sc.bad) my.state = 4;
+                else {
+                    const uint2 gp = L.edit_lut[min(read_len, L.edit_lut_size - 1)];
+                    uint32_t good = gp.x, passable = gp.y, thr = good;
+                    double compl_v = 1.0;
+                    if (L.short_reads) {                     // neighb_complexity, windows.rs:447-452, 696-698
+                        const uint32_t mid = (sc.start + sc.end) / 2;
+                        const uint32_t o = L.ci_off[pcontig];
+                        const uint32_t npos = L.ci_off[pcontig + 1] - o;
+                        const uint32_t i = min(mid > L.half_neighb ? mid - L.half_neighb : 0u, npos - 1);
+                        compl_v = static_cast<double>(L.compl_cnt[o + i]) * L.compl_mult;
+                    }
+                    if (compl_v <= L.poor_compl) {           // locs.rs:533-536
+                        thr = max(good, static_cast<uint32_t>(L.poor_compl_edit * static_cast<double>(read_len)));
+                        passable += thr - good;
+                    }
+                    my.good = good; my.thr = thr; my.passable = passable;
+                    my.state = 1u | (sc.edit <= passable ? 2u : 0u);
+                }
+            }
+        }
+    }
+    PairThresholds t;
+    t.e0 = EndThresholds{__shfl(my.good, 0), __shfl(my.thr, 0), __shfl(my.passable, 0), __shfl(my.state, 0)};
+    t.e1 = EndThresholds{__shfl(my.good, 1), __shfl(my.thr, 1), __shfl(my.passable, 1), __shfl(my.state, 1)};
+    return t;
+}
+
+// What pass 1 leaves of the records of a pair, per read end: the best edit distance and ln-probability, and how many records that are
+// not primaries were unusable (primaries are judged with the thresholds above): the lanes' values, reduced over the wavefront.
+// (The lanes keep their values in plain variables during pass 1: gathered in a struct there, the lean kernel spills.)
+struct Pass1 { uint32_t be0, be1, bad0, bad1; double bl0, bl1; };
+__device__ __forceinline__ Pass1 reduce_pass1(uint32_t be0, uint32_t be1, uint32_t bad0, uint32_t bad1, double bl0, double bl1) {
+    return Pass1{wave_reduce(be0, MinOp{}), wave_reduce(be1, MinOp{}), wave_reduce(bad0, AddOp{}), wave_reduce(bad1, AddOp{}),
+                 wave_reduce(bl0, MaxOp{}), wave_reduce(bl1, MaxOp{})};
+}
+
+// Acceptance of a pair after pass 1 and its edit-distance weight (locs.rs:565). End 1 is only looked at when end 0 is well mapped
+// (locs.rs:1125-1132), its secondaries only when its primary was pushed; invalid records raise the batch's error flag.
+struct Verdict { bool accepted; double weight; };
+__device__ __forceinline__ Verdict pair_verdict(const LocusView& L, const ReadsView& R, const PairHead& h, const PairThresholds& t,
+                                                const Pass1& b, bool paired, int lane) {
+    const bool look = t.look();
+    const bool wm0 = look && b.be0 <= (L.strict_subset ? t.e0.passable : t.e0.thr) && !b.bad0;
+    const bool saved1 = (t.e1.state & 3u) == 3u;
+    const bool err = (t.e0.state & 4u) || (look && b.bad0) || (wm0 && ((t.e1.state & 4u) || (saved1 && b.bad1)));
+    if (err && lane == 0) atomicMax(R.err_flag, static_cast<uint32_t>(LCTY_ERR_INVALID_DATA));
+    const bool wm1 = !paired || (saved1 && b.be1 <= (L.strict_subset ? t.e1.passable : t.e1.thr));
+    Verdict v{wm0 && wm1 && !err, 1.0};
+    if (v.accepted) {
+        v.weight *= b.be0 <= t.e0.good ? 1.0 : sqrt(static_cast<double>(t.e0.good) / static_cast<double>(b.be0));
+        if (paired) v.weight *= b.be1 <= t.e1.good ? 1.0 : sqrt(static_cast<double>(t.e1.good) / static_cast<double>(b.be1));
+    }
+    if (!v.accepted && lane == 0) R.recover_w[h.p] = -1.0;
+    return v;
+}
+
+// probability of the pair on a contig where it has no alignment (locs.rs:866; single-end: 908)
+__device__ __forceinline__ double unmapped_prob_of(const LocusView& L, double weight, bool paired) {
+    return paired ? weight * (2.0 * L.unmapped_penalty + L.insert_penalty) : weight * L.unmapped_penalty;
+}
+
+// the read weight from both mates' unique k-mers (locs.rs:968-1002); with it, the alignments a contig keeps (1268) and the unmapped probability
+struct KmerWeight { double weight, unmapped_prob; uint32_t max_alns; };
+__device__ __forceinline__ KmerWeight kmer_weight(const LocusView& L, double weight, uint32_t uk0, uint32_t uk1, bool paired) {
+    const uint32_t paired_count = (uk0 + uk1) & 0xFFFFu;
+    double kw = L.weight_interc + static_cast<double>(paired_count) * L.weight_mult;
+    kw = kw < 0.0 ? 0.0 : (kw > 1.0 ? 1.0 : kw);
+    weight *= kw;
+    const uint32_t max_alns = weight >= L.min_weight ? LCTY_MAX_USED_ALNS : LCTY_MAX_UNUSED_ALNS;
+    return KmerWeight{weight, unmapped_prob_of(L, weight, paired), max_alns};
+}
+
+// The verdict after pass 3a (locs.rs:1268-1285): a pair with no alignment in bounds on any contig is out of bounds, one whose best edit
+// distances are not good (best_edit_is_good, locs.rs:293-295) poorly mapped; either is not accepted. Alignment recovery looks at the
+// pairs in bounds (recover_w). any_inb: some lane saw one (the ballot is the caller's: inside, the two-slot kernel takes a register more).
+__device__ __forceinline__ uint8_t pair_status(const LocusView& L, const ReadsView& R, const PairHead& h, const PairThresholds& t,
+                                               const Pass1& b, bool any_inb, double weight, bool paired, int lane, bool* accepted) {
+    if (lane == 0) R.recover_w[h.p] = any_inb ? weight : -1.0;
+    const bool edit_good = b.be0 <= t.e0.thr && (!paired || b.be1 <= t.e1.thr);
+    if (!any_inb || !edit_good) *accepted = false;
+    return !any_inb ? LCTY_READ_OUT_OF_BOUNDS : !edit_good ? LCTY_READ_POORLY_MAPPED : weight >= L.min_weight ? LCTY_READ_GOOD : LCTY_READ_FEW_KMERS;
+}
+
+// A wavefront's share of the pair-alignment arena. The arena cursor is ONE word in memory: an atomic per read pair from every wavefront
+// of the device queues up at its L2 channel (2.4 of the kernel's 17.4 ms at 1 M pairs). A wavefront takes PA_CHUNK entries at a time and
+// hands them to its pairs (launches with at least PA_POOL_MIN_PAIRS pairs per wavefront; ReadsView::pa_chunk); the arena is addressed
+// through pa_off / pa_cnt only, and lcty_reads_create adds the room (an eighth + a chunk per wavefront).
+struct ArenaShare {
+    unsigned long long pool_at = 0, pool_left = 0;
+    // n entries can come from a share: this launch hands shares out, and n is at most an eighth of one
+    __device__ __forceinline__ bool shares(const ReadsView& R, uint32_t n) const { return R.pa_chunk != 0 && static_cast<uint64_t>(n) * 8 <= R.pa_chunk; }
+    // Where up to n entries may be written: the share's mark, after a new chunk if fewer are left (the rest, under an eighth of a chunk,
+    // stays unused). commit() takes what was written; what a pair that is not kept wrote is written over by the next pair.
+    __device__ __forceinline__ uint64_t upper_bound(const ReadsView& R, int lane, uint32_t n) {
+        if (n > pool_left) {
+            if (lane == 0) pool_at = atomicAdd(R.pa_count, static_cast<unsigned long long>(R.pa_chunk));
+            pool_at = __shfl(pool_at, 0);
+            pool_left = R.pa_chunk;
+        }
+        return pool_at;
+    }
+    __device__ __forceinline__ void commit(uint32_t n) { pool_at += n; pool_left -= n; }
+    // n entries for one pair: from the share, or (small launches, unusually large pairs) its own reservation. A run that ends beyond
+    // the arena raises the error flag and must not be written.
+    __device__ __forceinline__ uint64_t reserve(const ReadsView& R, int lane, uint32_t n) {
+        uint64_t base = 0;
+        if (shares(R, n)) {
+            base = upper_bound(R, lane, n);
+            commit(n);
+        } else {
+            if (lane == 0) base = atomicAdd(R.pa_count, static_cast<unsigned long long>(n));
+            base = __shfl(base, 0);
+        }
+        if (lane == 0 && base + n > R.pa_cap) atomicMax(R.err_flag, static_cast<uint32_t>(LCTY_ERR_RUNTIME));
+        return base;
+    }
+};
+
+// What a pair leaves behind. Rows of pairs that are not in AllAlignments::reads contribute 0.0 to every genotype score.
+__device__ __forceinline__ void store_pair(const LocusView& L, const ReadsView& R, const PairHead& h, int lane, uint8_t status, bool accepted,
+                                           double weight, double unmapped_prob, uint64_t pa_base, uint32_t total_cnt, uint32_t uk0, uint32_t uk1) {
+    if (status != LCTY_READ_GOOD)
+        for (uint32_t c = lane; c < L.n_alleles; c += WAVE) h.mrow[c] = 0.0;
+    if (lane == 0) {
+        const uint64_t p = h.p;
+        R.status[p] = status;
+        R.weight[p] = accepted ? weight : 0.0;
+        R.unmapped_prob[p] = accepted ? unmapped_prob : 0.0;
+        R.pa_off[p] = accepted ? pa_base : 0ull;
+        R.pa_cnt[p] = accepted ? total_cnt : 0u;
+        R.uniq_kmers[2 * p] = accepted ? static_cast<uint16_t>(uk0) : 0;
+        R.uniq_kmers[2 * p + 1] = accepted ? static_cast<uint16_t>(uk1) : 0;
+    }
+}
+
+// ---- LDS of the kernel forms: the host sizes the launch and the kernel finds its regions from the same struct (byte offsets). ----
+
+// General kernel. The saved alignments of a pair and their chains: rec [max_recs] Rec16 by record index, nxt [max_recs] 16-bit chain
+// links, order [max_recs] scratch of the general path, then kk1 kk2 cnt8 [A] bytes each (kept first / second-end alignments of the
+// general path, <= 10; emitted PairAlignments, <= 10, bit 7 = general path). Per-allele tables: head32 [A] {head(end 0) | head(end 1)
+// << 16}, alen [A] allele lengths, cursor [1]. LDS form: [rec | nxt | order | head32 | alen | cursor | kk1 kk2 cnt8], all in LDS.
+// BIG: LDS holds [head32 | cursor] only (4 B per allele, so that ten workgroups fit a CU at 4 096 alleles); [rec | nxt | order | kk1 kk2
+// cnt8] go to the workgroup's park in global memory, allele lengths come from L2.
+template <bool BIG>
+struct GeneralLayout {
+    uint32_t nxt, order, kk, park_bytes;         // in the park (BIG) or in LDS: rec is at 0
+    uint32_t head32, alen, cursor, lds_bytes;    // in LDS
+    __host__ __device__ GeneralLayout(uint32_t A, uint32_t max_recs) {
+        const uint32_t mr2 = (max_recs + 1) & ~1u;
+        nxt = max_recs * static_cast<uint32_t>(sizeof(Rec16));
+        order = nxt + mr2 * 2;
+        const uint32_t chains_end = order + mr2 * 2;
+        head32 = BIG ? 0 : chains_end; alen = BIG ? 0 : head32 + A * 4; cursor = alen + A * 4;
+        kk = BIG ? chains_end : cursor + 4;
+        park_bytes = BIG ? (kk + 3 * A + 255) & ~255u : 0;
+        lds_bytes = ((BIG ? cursor + 4 : kk + 3 * A) + 15) & ~15u;
+    }
+};
+
+// Lean kernels, per (contig, read end) of the pair. Plain: head [2A] the saved record's index, cnt8 [A] PairAlignments of the contig
+// (<= 3): 9 B per allele. KEEP: kept [2A] the saved alignment packed in 64 bits (pack_saved), kept_lp [2A] its ln-probability, cnt8 [A]:
+// 33 B per allele. TWO adds the second saved alignment of a group, where there is one: ovf_val [LEAN_OVF] packed values, ovf_n their
+// count (2 words), ovf_at [2A] the place of the group's second on that list.
+constexpr uint32_t LEAN_OVF = 64;             // second saved alignments of (contig, read end) groups a pair of the TWO form can hold
+template <bool KEEP, bool TWO>
+struct LeanLayout {
+    uint32_t head, kept, kept_lp, cnt8, ovf_val, ovf_n, ovf_at, lds_bytes;
+    __host__ __device__ explicit LeanLayout(uint32_t A) {
+        head = kept = 0;
+        kept_lp = 16 * A;
+        cnt8 = KEEP ? 32 * A : 8 * A;
+        ovf_val = (cnt8 + A + 7) & ~7u;
+        ovf_n = ovf_val + LEAN_OVF * 8;
+        ovf_at = ovf_n + 8;
+        lds_bytes = ((TWO ? ovf_at + 8 * A : cnt8 + A) + 15) & ~15u;
+    }
+};
+
+// The saved alignment of a (contig, read end) group as the KEEP forms hold it in LDS, 64 bits: start (28 bits, as in a counted record)
+// | strand << 28 | reference length (18 bits: three 16-bit counts) << 29 | record index (16 bits: the kernel is not launched on pairs of
+// 65 535 records or more) << 47. All ones = none. lp = the ln-probability that goes with it (normalised by the caller).
+constexpr unsigned long long NOT_KEPT = ~0ull;
+__device__ __forceinline__ unsigned long long pack_saved(uint32_t start, uint32_t end, bool rev, uint32_t idx) {
+    return static_cast<unsigned long long>(start) | static_cast<unsigned long long>(rev ? 1u : 0u) << 28 |
+           static_cast<unsigned long long>(end - start) << 29 | static_cast<unsigned long long>(idx) << 47;
+}
+__device__ __forceinline__ AlnRef unpack_saved(unsigned long long v, double lp) {
+    const uint32_t start = static_cast<uint32_t>(v) & 0x0FFFFFFFu;
+    return AlnRef{lp, start, start + (static_cast<uint32_t>(v >> 29) & 0x3FFFFu), static_cast<uint32_t>(v >> 47), ((v >> 28) & 1ull) != 0};
+}
+
 // EW = explicit region weights are set (lcty_locus_set_explicit_weights): the pair's weight is multiplied by
 // ContigInfos::explicit_read_weight over its PairAlignments (windows.rs:683-693; locs.rs:860, 903) before it scales them.
 // BIG = the saved alignments of a pair (16 B each + two 16-bit links) do not fit the LDS next to the per-allele tables (4 096
@@ -587,21 +847,17 @@ template <bool EW, bool BIG, bool CNT = false>
 __device__ __forceinline__ void score_reads_body(const LocusView& L, const ReadsView& R, const uint32_t max_recs) {
     extern __shared__ __align__(16) uint8_t smem[];
     const uint32_t A = L.n_alleles;
-    const uint32_t mr2 = (max_recs + 1) & ~1u;
-    // region sizes must match score_lds_bytes() / score_park_bytes()
+    const GeneralLayout<BIG> lay(A, max_recs);
     uint8_t* const park_base = BIG ? R.park + static_cast<uint64_t>(blockIdx.x) * R.park_stride : smem;
-    Rec16* rec = reinterpret_cast<Rec16*>(park_base);                         // [max_recs] saved alignments, by record index
-    uint16_t* nxt = reinterpret_cast<uint16_t*>(rec + max_recs);              // [max_recs] chain links
-    uint16_t* order = nxt + mr2;                                              // [max_recs] scratch of the general path
-    // LDS form: [rec | nxt | order | head32 | alen | cursor | kk1 kk2 cnt8]; BIG: LDS holds head32 + cursor only (4 B per allele, so
-    // that ten workgroups fit a CU at 4 096 alleles), the lane-private per-allele bytes go to the park, allele lengths come from L2
-    uint8_t* const tables = BIG ? smem : reinterpret_cast<uint8_t*>(order + mr2);
-    uint32_t* head32 = reinterpret_cast<uint32_t*>(tables);                   // [A] {head(end 0) | head(end 1) << 16}
-    uint32_t* alen_lds = head32 + A;                                          // [A] allele lengths (filled once per workgroup; not BIG)
-    uint32_t* scratch_cursor = BIG ? head32 + A : alen_lds + A;               // [1]
-    uint8_t* kk1 = BIG ? reinterpret_cast<uint8_t*>(order + mr2) : reinterpret_cast<uint8_t*>(scratch_cursor + 1);   // [A] general path: kept first-end alns (<= 10)
-    uint8_t* kk2 = kk1 + A;                                                   // [A]
-    uint8_t* cnt8 = kk2 + A;                                                  // [A] emitted PairAlignments (<= 10); bit 7 = general path
+    Rec16* rec = reinterpret_cast<Rec16*>(park_base);
+    uint16_t* nxt = reinterpret_cast<uint16_t*>(park_base + lay.nxt);
+    uint16_t* order = reinterpret_cast<uint16_t*>(park_base + lay.order);
+    uint32_t* head32 = reinterpret_cast<uint32_t*>(smem + lay.head32);
+    uint32_t* alen_lds = reinterpret_cast<uint32_t*>(smem + lay.alen);        // filled once per workgroup; not BIG
+    uint32_t* scratch_cursor = reinterpret_cast<uint32_t*>(smem + lay.cursor);
+    uint8_t* kk1 = park_base + lay.kk;
+    uint8_t* kk2 = kk1 + A;
+    uint8_t* cnt8 = kk2 + A;
     // SPLIT (counted alignments in LDS): the two chain heads of a contig in two words — head(end 0) in head32[c], head(end 1) in
     // head32[A + c], where the record form keeps the allele lengths (a counted alignment has its clipping applied: pass 1 does not
     // need them, pass 3 reads them from L2 along the contigs) — so that chaining a saved alignment is ONE LDS exchange instead of a
@@ -614,108 +870,32 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
     if constexpr (!BIG && !SPLIT) for (uint32_t i = lane; i < A; i += WAVE) alen_lds[i] = L.allele_len[i];
     __syncthreads();
 
-    unsigned long long pool_at = 0, pool_left = 0;          // this wavefront's share of the pair-alignment arena
+    ArenaShare arena;
     // all pairs of the batch, or the ones the lean kernel left (their indices and their number are on the device)
     const uint64_t n_todo = R.only_list ? static_cast<uint64_t>(*R.only_count) : R.n_pairs;
     for (uint64_t todo = blockIdx.x; todo < n_todo; todo += gridDim.x) {
         const uint64_t p = R.only_list ? R.only_list[todo] : todo;
-        const uint64_t a0 = R.aln_off[p];
         const uint32_t* cig = CNT ? nullptr : R.cigar + R.cigar_off[p];
-        const uint2 meta = R.pair_meta[p];                 // {index of the mate-2 primary (or n), records to look at}
-        const uint32_t j2 = meta.x, n_eff = meta.y;
-        const uint32_t split = min(j2, n_eff);
-        const uint32_t len0 = R.mate_len[2 * p], len1 = paired ? R.mate_len[2 * p + 1] : 0u;
-        double* mrow = R.matrix + p * A;
-        const lcty_aln_rec* recs = R.recs + a0;
-
-        // ---------------- prologue: prefetch read bases (consumed by K2) ----------------
-        const bool regs_ok = len0 <= 2016 && len1 <= 2016 && L.k <= 31;      // k-mers of 32..63 bases take the general path
-        uint64_t bw0 = 0, bw1 = 0;
-        uint32_t nm0 = 0, nm1 = 0;
-        if (regs_ok) {
-            const uint64_t off0 = R.mate_off[2 * p], off1 = R.mate_off[2 * p + 1];
-            if (static_cast<uint32_t>(lane) * 32u < len0) {
-                bw0 = (reinterpret_cast<const uint64_t*>(R.bases2) + (off0 >> 5))[lane];
-                nm0 = (R.nmask + (off0 >> 5))[lane];
-            }
-            if (static_cast<uint32_t>(lane) * 32u < len1) {
-                bw1 = (reinterpret_cast<const uint64_t*>(R.bases2) + (off1 >> 5))[lane];
-                nm1 = (R.nmask + (off1 >> 5))[lane];
-            }
-        }
+        // ---------------- prologue: the pair, its read bases prefetched (consumed by K2) ----------------
+        const PairHead h = load_pair(L, R, p, paired, lane);
+        const uint32_t j2 = h.j2, n_eff = h.n_eff, split = h.split;
+        double* mrow = h.mrow;
         for (uint32_t i = lane; i < (SPLIT ? 2 * A : A); i += WAVE) head32[i] = 0xFFFFFFFFu;
         if (lane == 0) *scratch_cursor = 0;
         // the records of the first group of pass 1 are requested now, so that they arrive while lanes 0 / 1 work out the
         // thresholds (two more dependent loads each)
         uint4 raw_first[GR];
 #pragma unroll
-        for (int g = 0; g < GR; g++) {
-            const uint32_t idx = g * WAVE + lane;
-            raw_first[g] = idx < n_eff ? reinterpret_cast<const uint4*>(recs)[idx] : make_uint4(0, 0, 0, 0);
-        }
+        for (int g = 0; g < GR; g++) raw_first[g] = h.raw_or_zero(g * WAVE + lane);
 
         // ---------------- thresholds (lanes 0 / 1 score the primaries) ----------------
-        // state: 1 examined-ok, 2 primary saved, 4 error
-        uint32_t my_good = 0, my_thr = NONE32, my_pass = NONE32, my_state = 0;
-        if (lane < 2) {
-            const uint32_t e = lane;
-            const uint32_t pidx = e ? j2 : 0u;
-            const bool exists = e == 0 ? n_eff > 0 : (paired && j2 < n_eff);
-            if (e == 1 && !paired) {
-                my_state = 3;                                   // single-end: second end is vacuously fine
-            } else if (!exists) {
-                my_state = 4;                                   // expect("Cannot read any more records"), locs.rs:509
-            } else {
-                const uint4 praw = reinterpret_cast<const uint4*>(recs)[pidx];
-                const lcty_aln_rec pr = recs[pidx];
-                const uint32_t read_len = e ? len1 : len0;
-                const uint32_t pflags = CNT ? ((praw.x >> 28 & 1u) ? LCTY_FLAG_REVERSE : 0u) | ((praw.x >> 29 & 1u) ? LCTY_FLAG_SECONDARY : 0u)
-                                              | ((praw.x >> 30 & 1u) ? LCTY_FLAG_UNMAPPED : 0u) : pr.flags;
-                const uint32_t pcontig = CNT ? (praw.y & 0xFFFFu) : pr.contig;
-                const bool is_primary = (pflags & (LCTY_FLAG_SECONDARY | LCTY_FLAG_SUPPL)) == 0;
-                if (read_len == 0 || !is_primary) my_state = 4;                 // locs.rs:511-517 / LaggedReader assert
-                else if (pflags & LCTY_FLAG_UNMAPPED) my_state = 0;             // locs.rs:520-523
-                else if ((!CNT && pr.n_cigar == 0) || pcontig >= A) my_state = 4;
-                else {
-                    Scored sc;
-                    if constexpr (CNT) sc = score_counted(L, praw);
-                    else {
-                        const W8 w8 = *reinterpret_cast<const W8*>(cig + pr.cigar_rel);
-                        const OpCounts oc = count_ops(w8, cig + pr.cigar_rel, pr.n_cigar, true);
-                        sc = score_counts(L, oc, pr.pos, L.allele_len[pr.contig]);
-                    }
-                    if (sc.bad) my_state = 4;
-                    else {
-                        const uint2 gp = L.edit_lut[min(read_len, L.edit_lut_size - 1)];
-                        uint32_t good = gp.x, passable = gp.y, thr = good;
-                        double compl_v = 1.0;
-                        if (L.short_reads) {                     // neighb_complexity, windows.rs:447-452, 696-698
-                            const uint32_t mid = (sc.start + sc.end) / 2;
-                            const uint32_t o = L.ci_off[pcontig];
-                            const uint32_t npos = L.ci_off[pcontig + 1] - o;
-                            const uint32_t i = min(mid > L.half_neighb ? mid - L.half_neighb : 0u, npos - 1);
-                            compl_v = static_cast<double>(L.compl_cnt[o + i]) * L.compl_mult;
-                        }
-                        if (compl_v <= L.poor_compl) {           // locs.rs:533-536
-                            thr = max(good, static_cast<uint32_t>(L.poor_compl_edit * static_cast<double>(read_len)));
-                            passable += thr - good;
-                        }
-                        my_good = good; my_thr = thr; my_pass = passable;
-                        my_state = 1u | (sc.edit <= passable ? 2u : 0u);
-                    }
-                }
-            }
-        }
-        const uint32_t good0 = __shfl(my_good, 0), thr0 = __shfl(my_thr, 0), pass0 = __shfl(my_pass, 0), st0 = __shfl(my_state, 0);
-        const uint32_t good1 = __shfl(my_good, 1), thr1 = __shfl(my_thr, 1), pass1 = __shfl(my_pass, 1), st1 = __shfl(my_state, 1);
+        const PairThresholds thr = primary_thresholds<CNT>(L, h, cig, paired, lane);
         pair_barrier<BIG>();      // head table initialised
 
         // ---------------- pass 1: records -> (best edit, best ln-prob), saved ones -> LDS chains ----------------
         uint32_t be0 = NONE32, be1 = NONE32, bad0 = 0, bad1 = 0;
-        double bl0 = -INFINITY, bl1 = -INFINITY;
-        // a pair whose first primary was not pushed is rejected without looking further (locs.rs:539-543)
-        const bool look = (st0 & 3u) == 3u;
-        for (uint32_t base = 0; look && base < n_eff; base += WAVE * GR) {
+        double lbl0 = -INFINITY, lbl1 = -INFINITY;
+        for (uint32_t base = 0; thr.look() && base < n_eff; base += WAVE * GR) {
             uint4 raw[GR];
             W8 cw[GR];
             uint32_t clen[GR];
@@ -723,7 +903,7 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
             for (int g = 0; g < GR; g++) {
                 const uint32_t idx = base + g * WAVE + lane;
                 if (base == 0) raw[g] = raw_first[g];
-                else raw[g] = idx < n_eff ? reinterpret_cast<const uint4*>(recs)[idx] : make_uint4(0, 0, 0, 0);
+                else raw[g] = h.raw_or_zero(idx);
             }
             if constexpr (!CNT) {
 #pragma unroll
@@ -757,11 +937,11 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
                     }
                     (void)pos;
                     if (sc.bad || cbad) {
-                        if (!primary) { if (e) bad1 = 1; else bad0 = 1; }   // primaries are judged by lanes 0/1 above
+                        if (!primary) { if (e) bad1 = 1; else bad0 = 1; }                     // primaries are judged by lanes 0/1 above
                     } else {
-                        if (e == 0) { be0 = min(be0, sc.edit); bl0 = fmax(bl0, sc.ln_prob); }
-                        else { be1 = min(be1, sc.edit); bl1 = fmax(bl1, sc.ln_prob); }
-                        if (sc.edit <= (e ? pass1 : pass0)) {              // save (locs.rs:314)
+                        if (e == 0) { be0 = min(be0, sc.edit); lbl0 = fmax(lbl0, sc.ln_prob); }
+                        else { be1 = min(be1, sc.edit); lbl1 = fmax(lbl1, sc.ln_prob); }
+                        if (sc.edit <= thr.passable(e)) {                  // save (locs.rs:314)
                             Rec16 r;
                             r.ln_prob = sc.ln_prob; r.start = sc.start;
                             r.end_rev = sc.end | ((bflags & LCTY_FLAG_REVERSE) ? REV_BIT : 0u);
@@ -784,34 +964,23 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
                 }
             }
         }
-        be0 = wave_min_u32(be0); be1 = wave_min_u32(be1);
-        bl0 = wave_max_f64(bl0); bl1 = wave_max_f64(bl1);
-        bad0 = wave_sum_u32(bad0); bad1 = wave_sum_u32(bad1);
+        const Pass1 best = reduce_pass1(be0, be1, bad0, bad1, lbl0, lbl1);
         pair_barrier<BIG>();
 
-        // end 1 is only looked at when end 0 is well mapped (locs.rs:1125-1132); its secondaries only when its
-        // primary was pushed
-        const bool wm0 = look && be0 <= (L.strict_subset ? pass0 : thr0) && !bad0;
-        const bool saved1 = (st1 & 3u) == 3u;
-        const bool err = (st0 & 4u) || (look && bad0) || (wm0 && ((st1 & 4u) || (saved1 && bad1)));
-        if (err && lane == 0) atomicMax(R.err_flag, static_cast<uint32_t>(LCTY_ERR_INVALID_DATA));
-        const bool wm1 = !paired || (saved1 && be1 <= (L.strict_subset ? pass1 : thr1));
-        bool accepted = wm0 && wm1 && !err;
-        double weight = 1.0;
-        if (accepted) {
-            weight *= be0 <= good0 ? 1.0 : sqrt(static_cast<double>(good0) / static_cast<double>(be0));      // locs.rs:565
-            if (paired) weight *= be1 <= good1 ? 1.0 : sqrt(static_cast<double>(good1) / static_cast<double>(be1));
-        }
+        const Verdict verdict = pair_verdict(L, R, h, thr, best, paired, lane);
+        bool accepted = verdict.accepted;
+        double weight = verdict.weight;
+        const double bl0 = best.bl0, bl1 = best.bl1;
         uint8_t status = LCTY_READ_POORLY_MAPPED;
         uint32_t total_cnt = 0, uk0 = 0, uk1 = 0;
         double unmapped_prob = 0.0;
         uint64_t pa_base = 0;
 
-        if (!accepted && lane == 0) R.recover_w[p] = -1.0;
         if (accepted) {
             // ---------------- K2: unique k-mers -> read weight (locs.rs:968-1002) ----------------
             // (evaluated after the in-bounds test in the reference; no side effects, order irrelevant)
-            if (regs_ok) pair_unique_kmers_regs(L.kset, L.kset_mask, L.undef_in_set, L.k, len0, len1, bw0, bw1, nm0, nm1, lane, &uk0, &uk1);
+            const uint32_t len0 = h.len0, len1 = h.len1;
+            if (h.regs_ok) pair_unique_kmers_regs(L.kset, L.kset_mask, L.undef_in_set, L.k, len0, len1, h.bw0, h.bw1, h.nm0, h.nm1, lane, &uk0, &uk1);
             else {
                 const uint64_t off0 = R.mate_off[2 * p], off1 = R.mate_off[2 * p + 1];
                 uk0 = mate_unique_kmers_global(L.kset, L.kset_mask, L.undef_in_set, L.k,
@@ -820,14 +989,10 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
                                                       reinterpret_cast<const uint64_t*>(R.bases2) + (off1 >> 5), R.nmask + (off1 >> 5), len1, lane)
                            : 0u;
             }
-            const uint32_t paired_count = (uk0 + uk1) & 0xFFFFu;
-            double kw = L.weight_interc + static_cast<double>(paired_count) * L.weight_mult;
-            kw = kw < 0.0 ? 0.0 : (kw > 1.0 ? 1.0 : kw);
-            weight *= kw;
-            const uint32_t max_alns = weight >= L.min_weight ? LCTY_MAX_USED_ALNS : LCTY_MAX_UNUSED_ALNS;   // locs.rs:1268
+            const KmerWeight kw = kmer_weight(L, weight, uk0, uk1, paired);
+            const uint32_t max_alns = kw.max_alns;
+            weight = kw.weight; unmapped_prob = kw.unmapped_prob;
             const double unm_ins_penalty = L.unmapped_penalty + L.insert_penalty;                         // locs.rs:816
-            unmapped_prob = paired ? weight * (2.0 * L.unmapped_penalty + L.insert_penalty)                // locs.rs:866
-                                   : weight * L.unmapped_penalty;                                          // locs.rs:908
 
             // ---------------- pass 3a: per contig best + kept count, matrix row ----------------
             bool inb = false;
@@ -844,8 +1009,8 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
                 if (c < A && !general) {
                     const Fast3 f = fast_candidates(ins, rec, h1, h2, bl0, bl1, unm_ins_penalty, paired);
                     const uint32_t clen = alen[c];
-                    if (f.has1) { const uint32_t mid = (f.a1.start + f.a1.end) / 2; inb |= L.boundary <= mid && mid < clen - L.boundary; }
-                    if (f.has2) { const uint32_t mid = (f.a2.start + f.a2.end) / 2; inb |= L.boundary <= mid && mid < clen - L.boundary; }
+                    if (f.has1) inb |= in_bounds(f.a1, clen, L.boundary);
+                    if (f.has2) inb |= in_bounds(f.a2, clen, L.boundary);
                     if (f.has1 || f.has2) res = fast_count(f, max_alns, L.prob_diff);
                     cnt8[c] = static_cast<uint8_t>(res.cnt);
                 }
@@ -876,33 +1041,12 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
                 }
             }
             const bool any_inb = __ballot(inb) != 0ull;
-            total_cnt = wave_sum_u32(total_cnt);
-            if (lane == 0) R.recover_w[p] = any_inb ? weight : -1.0;                         // alignment recovery looks at these pairs
-            const bool edit_good = be0 <= thr0 && (!paired || be1 <= thr1);                   // best_edit_is_good, locs.rs:293-295
-            if (!any_inb) { status = LCTY_READ_OUT_OF_BOUNDS; accepted = false; }
-            else if (!edit_good) { status = LCTY_READ_POORLY_MAPPED; accepted = false; }
-            else status = weight >= L.min_weight ? LCTY_READ_GOOD : LCTY_READ_FEW_KMERS;     // locs.rs:1277-1285 (EW: again below)
+            total_cnt = wave_reduce(total_cnt, AddOp{});
+            status = pair_status(L, R, h, thr, best, any_inb, weight, paired, lane, &accepted);     // EW: the weight's part of it again below
             pair_barrier<BIG>();
 
             if (accepted) {
-                // The arena cursor is ONE word in memory: an atomic per read pair from every wavefront of the device queues up at its
-                // L2 channel (2.4 of the kernel's 17.4 ms at 1 M pairs). A wavefront takes PA_CHUNK entries at a time and hands
-                // them to its pairs (launches with at least PA_POOL_MIN_PAIRS pairs per wavefront; ReadsView::pa_chunk); the arena is
-                // addressed through pa_off / pa_cnt only, and lcty_reads_create adds the room (an eighth + a chunk per wavefront).
-                if (R.pa_chunk == 0 || static_cast<uint64_t>(total_cnt) * 8 > R.pa_chunk) {
-                    // small launches and unusually large pairs: their own reservation (nothing of a chunk is left unused for them)
-                    if (lane == 0) pa_base = atomicAdd(R.pa_count, static_cast<unsigned long long>(total_cnt));
-                    pa_base = __shfl(pa_base, 0);
-                } else {
-                    if (total_cnt > pool_left) {                                  // what is left (< an eighth of a chunk) stays unused
-                        if (lane == 0) pool_at = atomicAdd(R.pa_count, static_cast<unsigned long long>(R.pa_chunk));
-                        pool_at = __shfl(pool_at, 0);
-                        pool_left = R.pa_chunk;
-                    }
-                    pa_base = pool_at;
-                    pool_at += total_cnt; pool_left -= total_cnt;
-                }
-                if (lane == 0 && pa_base + total_cnt > R.pa_cap) atomicMax(R.err_flag, static_cast<uint32_t>(LCTY_ERR_RUNTIME));
+                pa_base = arena.reserve(R, lane, total_cnt);
                 const bool room = pa_base + total_cnt <= R.pa_cap;
                 // ---------------- pass 3b: emit PairAlignments, contig-ascending ----------------
                 const double emit_weight = EW ? 1.0 : weight;
@@ -943,9 +1087,9 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
                 if constexpr (EW) {
                     // explicit_read_weight = mean over all PairAlignments of the pair (windows.rs:688-692); the sum is taken
                     // per lane and then across the wave (a different order of additions than upstream's serial loop)
-                    ew_sum = wave_sum_f64(ew_sum);
+                    ew_sum = wave_reduce(ew_sum, AddOp{});
                     weight = weight * (ew_sum / static_cast<double>(total_cnt));                       // locs.rs:860, 903
-                    unmapped_prob = paired ? weight * (2.0 * L.unmapped_penalty + L.insert_penalty) : weight * L.unmapped_penalty;
+                    unmapped_prob = unmapped_prob_of(L, weight, paired);
                     status = weight >= L.min_weight ? LCTY_READ_GOOD : LCTY_READ_FEW_KMERS;           // GrouppedAlignments::weight()
                     for (uint32_t c = lane; c < A; c += WAVE) {
                         const uint32_t ix = R.pa_idx[p * A + c];
@@ -960,18 +1104,7 @@ __device__ __forceinline__ void score_reads_body(const LocusView& L, const Reads
             }
         }
 
-        // rows of pairs that are not in AllAlignments::reads contribute 0.0 to every genotype score
-        if (status != LCTY_READ_GOOD)
-            for (uint32_t c = lane; c < A; c += WAVE) mrow[c] = 0.0;
-        if (lane == 0) {
-            R.status[p] = status;
-            R.weight[p] = accepted ? weight : 0.0;
-            R.unmapped_prob[p] = accepted ? unmapped_prob : 0.0;
-            R.pa_off[p] = accepted ? pa_base : 0ull;
-            R.pa_cnt[p] = accepted ? total_cnt : 0u;
-            R.uniq_kmers[2 * p] = accepted ? static_cast<uint16_t>(uk0) : 0;
-            R.uniq_kmers[2 * p + 1] = accepted ? static_cast<uint16_t>(uk1) : 0;
-        }
+        store_pair(L, R, h, lane, status, accepted, weight, unmapped_prob, pa_base, total_cnt, uk0, uk1);
         pair_barrier<BIG>();
     }
 }
@@ -992,7 +1125,6 @@ __device__ __forceinline__ AlnRef ref_from_counted(const LocusView& L, const uin
     return AlnRef{sc.ln_prob - best, sc.start, sc.end, idx, ((raw.x >> 28) & 1u) != 0};            // normalize_probs, locs.rs:358-360
 }
 
-constexpr uint32_t LEAN_OVF = 64;             // second saved alignments of (contig, read end) groups a pair of the TWO form can hold
 template <bool TIMED, bool KEEP, bool TWO = false>
 __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsView& R) {
     static_assert(!TWO || KEEP, "the two-slot form keeps the saved alignments' products in LDS");
@@ -1009,111 +1141,48 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
     };
     if constexpr (TIMED) t_prev = __builtin_amdgcn_s_memtime();
     const uint32_t A = L.n_alleles;
-    // KEEP (few alleles: 33 B of LDS per allele): what pass 1 computed of the saved alignment — its place, strand and index packed
-    // into 64 bits, its ln-probability — stays in LDS and pass 3 has it from there; otherwise (9 B per allele) pass 1 leaves the
-    // record's index and pass 3 reads and scores the record again.
-    uint32_t* head = reinterpret_cast<uint32_t*>(smem);                       // [2A]: saved record of (contig, end 0) | (contig, end 1)
-    unsigned long long* kept = reinterpret_cast<unsigned long long*>(smem);   // KEEP [2A]: start | rev << 28 | (end - start) << 29 | index << 47
-    double* kept_lp = reinterpret_cast<double*>(kept + 2 * A);                // KEEP [2A]
-    uint8_t* cnt8 = KEEP ? reinterpret_cast<uint8_t*>(kept_lp + 2 * A) : reinterpret_cast<uint8_t*>(head + 2 * A);   // [A] PairAlignments of the contig (<= 3)
-    // TWO: the second saved alignment of a (contig, read end) group, where there is one: a list of [LEAN_OVF] packed values with its count,
-    // and per group the place of its second on that list ([2A], LEAN_NONE: none) — an exchange on it tells a third alignment of a group
-    unsigned long long* ovf_val = reinterpret_cast<unsigned long long*>(smem + ((static_cast<size_t>(A) * 33 + 7) & ~static_cast<size_t>(7)));
-    uint32_t* ovf_n = reinterpret_cast<uint32_t*>(ovf_val + LEAN_OVF);
-    uint32_t* ovf_at = ovf_n + 2;
+    // KEEP (few alleles): what pass 1 computed of the saved alignment stays in LDS and pass 3 has it from there; otherwise pass 1
+    // leaves the record's index and pass 3 reads and scores the record again. TWO: an exchange on ovf_at tells a group's third alignment.
+    const LeanLayout<KEEP, TWO> lay(A);
+    uint32_t* head = reinterpret_cast<uint32_t*>(smem + lay.head);
+    unsigned long long* kept = reinterpret_cast<unsigned long long*>(smem + lay.kept);
+    double* kept_lp = reinterpret_cast<double*>(smem + lay.kept_lp);
+    uint8_t* cnt8 = smem + lay.cnt8;
+    unsigned long long* ovf_val = reinterpret_cast<unsigned long long*>(smem + lay.ovf_val);
+    uint32_t* ovf_n = reinterpret_cast<uint32_t*>(smem + lay.ovf_n);
+    uint32_t* ovf_at = reinterpret_cast<uint32_t*>(smem + lay.ovf_at);
     constexpr uint32_t LEAN_NONE = 0xFFFFFFFFu;
-    constexpr unsigned long long NOT_KEPT = ~0ull;
     const int lane = threadIdx.x;
     const bool paired = L.is_paired != 0;
     const InsLut ins{L.ins_lut, L.ins_lut_size, L.ins_n, L.ins_lnq, L.ins_lnpmf_const};
-    unsigned long long pool_at = 0, pool_left = 0;
+    ArenaShare arena;
     // TWO: the pairs the first lean launch left (only_list); what this form cannot take either goes on to defer_list
     const uint64_t n_todo = TWO ? static_cast<uint64_t>(*R.only_count) : R.n_pairs;
     for (uint64_t todo = blockIdx.x; todo < n_todo; todo += gridDim.x) {
         const uint64_t p = TWO ? R.only_list[todo] : todo;
-        const uint64_t a0 = R.aln_off[p];
-        const uint2 meta = R.pair_meta[p];
-        const uint32_t j2 = meta.x, n_eff = meta.y;
-        const uint32_t split = min(j2, n_eff);
-        const uint32_t len0 = R.mate_len[2 * p], len1 = paired ? R.mate_len[2 * p + 1] : 0u;
-        double* mrow = R.matrix + p * A;
-        const uint4* recs = reinterpret_cast<const uint4*>(R.recs + a0);
-        const bool regs_ok = len0 <= 2016 && len1 <= 2016;
-        uint64_t bw0 = 0, bw1 = 0;
-        uint32_t nm0 = 0, nm1 = 0;
-        if (regs_ok) {
-            const uint64_t off0 = R.mate_off[2 * p], off1 = R.mate_off[2 * p + 1];
-            if (static_cast<uint32_t>(lane) * 32u < len0) {
-                bw0 = (reinterpret_cast<const uint64_t*>(R.bases2) + (off0 >> 5))[lane];
-                nm0 = (R.nmask + (off0 >> 5))[lane];
-            }
-            if (static_cast<uint32_t>(lane) * 32u < len1) {
-                bw1 = (reinterpret_cast<const uint64_t*>(R.bases2) + (off1 >> 5))[lane];
-                nm1 = (R.nmask + (off1 >> 5))[lane];
-            }
-        }
+        const PairHead h = load_pair(L, R, p, paired, lane);
+        const uint32_t j2 = h.j2, n_eff = h.n_eff, split = h.split;
+        double* mrow = h.mrow;
         if constexpr (KEEP) { for (uint32_t i = lane; i < 2 * A; i += WAVE) { kept[i] = NOT_KEPT; if (TWO) ovf_at[i] = LEAN_NONE; } if (TWO && lane == 0) *ovf_n = 0; }
         else { for (uint32_t i = lane; i < 2 * A; i += WAVE) head[i] = 0xFFFFFFFFu; }
         uint4 raw_first[GR];
 #pragma unroll
-        for (int g = 0; g < GR; g++) {
-            const uint32_t idx = g * WAVE + lane;
-            raw_first[g] = idx < n_eff ? recs[idx] : make_uint4(0, 0, 0, 0);
-        }
-        // ---------------- thresholds (lanes 0 / 1 score the primaries): as in the general kernel ----------------
-        uint32_t my_good = 0, my_thr = NONE32, my_pass = NONE32, my_state = 0;
-        if (lane < 2) {
-            const uint32_t e = lane;
-            const uint32_t pidx = e ? j2 : 0u;
-            const bool exists = e == 0 ? n_eff > 0 : (paired && j2 < n_eff);
-            if (e == 1 && !paired) my_state = 3;
-            else if (!exists) my_state = 4;
-            else {
-                const uint4 praw = recs[pidx];
-                const uint32_t read_len = e ? len1 : len0;
-                const uint32_t pcontig = praw.y & 0xFFFFu;
-                const bool is_primary = ((praw.x >> 29) & 1u) == 0;
-                if (read_len == 0 || !is_primary) my_state = 4;
-                else if ((praw.x >> 30) & 1u) my_state = 0;
-                else if (pcontig >= A) my_state = 4;
-                else {
-                    const Scored sc = score_counted(L, praw);
-                    const uint2 gp = L.edit_lut[min(read_len, L.edit_lut_size - 1)];
-                    uint32_t good = gp.x, passable = gp.y, thr = good;
-                    double compl_v = 1.0;
-                    if (L.short_reads) {
-                        const uint32_t mid = (sc.start + sc.end) / 2;
-                        const uint32_t o = L.ci_off[pcontig];
-                        const uint32_t npos = L.ci_off[pcontig + 1] - o;
-                        const uint32_t i = min(mid > L.half_neighb ? mid - L.half_neighb : 0u, npos - 1);
-                        compl_v = static_cast<double>(L.compl_cnt[o + i]) * L.compl_mult;
-                    }
-                    if (compl_v <= L.poor_compl) {
-                        thr = max(good, static_cast<uint32_t>(L.poor_compl_edit * static_cast<double>(read_len)));
-                        passable += thr - good;
-                    }
-                    my_good = good; my_thr = thr; my_pass = passable;
-                    my_state = 1u | (sc.edit <= passable ? 2u : 0u);
-                }
-            }
-        }
-        const uint32_t good0 = __shfl(my_good, 0), thr0 = __shfl(my_thr, 0), pass0 = __shfl(my_pass, 0), st0 = __shfl(my_state, 0);
-        const uint32_t good1 = __shfl(my_good, 1), thr1 = __shfl(my_thr, 1), pass1 = __shfl(my_pass, 1), st1 = __shfl(my_state, 1);
+        for (int g = 0; g < GR; g++) raw_first[g] = h.raw_or_zero(g * WAVE + lane);
+        const PairThresholds thr = primary_thresholds<true>(L, h, nullptr, paired, lane);
         __syncthreads();          // head table initialised
         stamp(0);
 
         // ---------------- pass 1 ----------------
         uint32_t be0 = NONE32, be1 = NONE32, bad0 = 0, bad1 = 0;
-        double bl0 = -INFINITY, bl1 = -INFINITY;
+        double lbl0 = -INFINITY, lbl1 = -INFINITY;
         bool multi = false;
-        const bool look = (st0 & 3u) == 3u;
-        for (uint32_t base = 0; look && base < n_eff; base += WAVE * GR) {
+        for (uint32_t base = 0; thr.look() && base < n_eff; base += WAVE * GR) {
             uint4 raw[GR];
 #pragma unroll
             for (int g = 0; g < GR; g++) {
                 const uint32_t idx = base + g * WAVE + lane;
                 if (base == 0) raw[g] = raw_first[g];
-                else raw[g] = idx < n_eff ? recs[idx] : make_uint4(0, 0, 0, 0);
+                else raw[g] = h.raw_or_zero(idx);
             }
 #pragma unroll
             for (int g = 0; g < GR; g++) {
@@ -1127,14 +1196,11 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
                         if (!primary) { if (e) bad1 = 1; else bad0 = 1; }
                     } else {
                         const Scored sc = score_counted(L, raw[g]);
-                        if (e == 0) { be0 = min(be0, sc.edit); bl0 = fmax(bl0, sc.ln_prob); }
-                        else { be1 = min(be1, sc.edit); bl1 = fmax(bl1, sc.ln_prob); }
-                        if (sc.edit <= (e ? pass1 : pass0)) {                   // save (locs.rs:314)
+                        if (e == 0) { be0 = min(be0, sc.edit); lbl0 = fmax(lbl0, sc.ln_prob); }
+                        else { be1 = min(be1, sc.edit); lbl1 = fmax(lbl1, sc.ln_prob); }
+                        if (sc.edit <= thr.passable(e)) {                       // save (locs.rs:314)
                             if constexpr (KEEP) {
-                                // 28 + 1 + 18 (three 16-bit counts) + 16 bits (the kernel is not launched on pairs of 65535 records or more)
-                                const unsigned long long packed = static_cast<unsigned long long>(sc.start) | static_cast<unsigned long long>((raw[g].x >> 28) & 1u) << 28 |
-                                    static_cast<unsigned long long>(sc.end - sc.start) << 29 | static_cast<unsigned long long>(idx) << 47;
-                                const unsigned long long before = atomicExch(&kept[e * A + contig], packed);
+                                const unsigned long long before = atomicExch(&kept[e * A + contig], pack_saved(sc.start, sc.end, ((raw[g].x >> 28) & 1u) != 0, idx));
                                 if (before != NOT_KEPT) {
                                     if constexpr (TWO) {
                                         // the group's second saved alignment goes on the pair's list (which of the two stays in the slot is
@@ -1153,58 +1219,41 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
                 }
             }
         }
-        be0 = wave_min_u32(be0); be1 = wave_min_u32(be1);
-        bl0 = wave_max_f64(bl0); bl1 = wave_max_f64(bl1);
-        bad0 = wave_sum_u32(bad0); bad1 = wave_sum_u32(bad1);
+        const Pass1 best = reduce_pass1(be0, be1, bad0, bad1, lbl0, lbl1);
         __syncthreads();
         stamp(1);
-        if (!regs_ok || __ballot(multi) != 0ull) {
+        if (!h.regs_ok || __ballot(multi) != 0ull) {
             // not this kernel's pair: untouched, the general kernel takes it
             if (lane == 0) R.defer_list[atomicAdd(R.defer_count, 1u)] = static_cast<uint32_t>(p);
             continue;
         }
 
-        const bool wm0 = look && be0 <= (L.strict_subset ? pass0 : thr0) && !bad0;
-        const bool saved1 = (st1 & 3u) == 3u;
-        const bool err = (st0 & 4u) || (look && bad0) || (wm0 && ((st1 & 4u) || (saved1 && bad1)));
-        if (err && lane == 0) atomicMax(R.err_flag, static_cast<uint32_t>(LCTY_ERR_INVALID_DATA));
-        const bool wm1 = !paired || (saved1 && be1 <= (L.strict_subset ? pass1 : thr1));
-        bool accepted = wm0 && wm1 && !err;
-        double weight = 1.0;
-        if (accepted) {
-            weight *= be0 <= good0 ? 1.0 : sqrt(static_cast<double>(good0) / static_cast<double>(be0));      // locs.rs:565
-            if (paired) weight *= be1 <= good1 ? 1.0 : sqrt(static_cast<double>(good1) / static_cast<double>(be1));
-        }
+        const Verdict verdict = pair_verdict(L, R, h, thr, best, paired, lane);
+        bool accepted = verdict.accepted;
+        double weight = verdict.weight;
+        const double bl0 = best.bl0, bl1 = best.bl1;
         uint8_t status = LCTY_READ_POORLY_MAPPED;
         uint32_t total_cnt = 0, uk0 = 0, uk1 = 0;
         double unmapped_prob = 0.0;
         uint64_t pa_base = 0;
-        if (!accepted && lane == 0) R.recover_w[p] = -1.0;
         if (accepted) {
-            pair_unique_kmers_regs(L.kset, L.kset_mask, L.undef_in_set, L.k, len0, len1, bw0, bw1, nm0, nm1, lane, &uk0, &uk1);
+            pair_unique_kmers_regs(L.kset, L.kset_mask, L.undef_in_set, L.k, h.len0, h.len1, h.bw0, h.bw1, h.nm0, h.nm1, lane, &uk0, &uk1);
             stamp(2);
-            const uint32_t paired_count = (uk0 + uk1) & 0xFFFFu;
-            double kw = L.weight_interc + static_cast<double>(paired_count) * L.weight_mult;
-            kw = kw < 0.0 ? 0.0 : (kw > 1.0 ? 1.0 : kw);
-            weight *= kw;
-            const uint32_t max_alns = weight >= L.min_weight ? LCTY_MAX_USED_ALNS : LCTY_MAX_UNUSED_ALNS;
+            const KmerWeight kw = kmer_weight(L, weight, uk0, uk1, paired);
+            const uint32_t max_alns = kw.max_alns;
+            weight = kw.weight; unmapped_prob = kw.unmapped_prob;
             const double unm_ins_penalty = L.unmapped_penalty + L.insert_penalty;
-            unmapped_prob = paired ? weight * (2.0 * L.unmapped_penalty + L.insert_penalty) : weight * L.unmapped_penalty;
             const AlnRef none{0.0, 0, 0, NONE32, false};
             auto candidates = [&](uint32_t c) -> Fast3 {
                 if constexpr (KEEP) {
                     const unsigned long long k1 = kept[c], k2 = kept[A + c];
                     const bool has1 = k1 != NOT_KEPT, has2 = k2 != NOT_KEPT;
-                    auto ref = [](unsigned long long v, double lp) {
-                        const uint32_t start = static_cast<uint32_t>(v) & 0x0FFFFFFFu;
-                        return AlnRef{lp, start, start + (static_cast<uint32_t>(v >> 29) & 0x3FFFFu), static_cast<uint32_t>(v >> 47), ((v >> 28) & 1ull) != 0};
-                    };
-                    return fast_from_refs(ins, has1 ? ref(k1, kept_lp[c] - bl0) : none, has2 ? ref(k2, kept_lp[A + c] - bl1) : none,
+                    return fast_from_refs(ins, has1 ? unpack_saved(k1, kept_lp[c] - bl0) : none, has2 ? unpack_saved(k2, kept_lp[A + c] - bl1) : none,
                                           has1, has2, unm_ins_penalty, paired);
                 } else {
                     const uint32_t h1 = head[c], h2 = head[A + c];
                     const bool has1 = h1 != 0xFFFFFFFFu, has2 = h2 != 0xFFFFFFFFu;
-                    const uint4 r1 = recs[has1 ? h1 : 0u], r2 = recs[has2 ? h2 : 0u];      // L2: read in pass 1 a moment ago
+                    const uint4 r1 = h.raw(has1 ? h1 : 0u), r2 = h.raw(has2 ? h2 : 0u);    // L2: read in pass 1 a moment ago
                     return fast_from_refs(ins, has1 ? ref_from_counted(L, r1, h1, bl0) : none, has2 ? ref_from_counted(L, r2, h2, bl1) : none,
                                           has1, has2, unm_ins_penalty, paired);
                 }
@@ -1214,10 +1263,6 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
             SmallCtx sc;
             sc.ins = ins; sc.unm_ins_penalty = unm_ins_penalty; sc.paired = paired; sc.k1 = sc.k2 = 0;
             sc.a10 = sc.a11 = sc.a20 = sc.a21 = none;
-            auto packed_ref = [](unsigned long long v, double lp) {
-                const uint32_t start = static_cast<uint32_t>(v) & 0x0FFFFFFFu;
-                return AlnRef{lp, start, start + (static_cast<uint32_t>(v >> 29) & 0x3FFFFu), static_cast<uint32_t>(v >> 47), ((v >> 28) & 1ull) != 0};
-            };
             // the saved alignments of one group in the order of gather_sort_dedupe: ln_prob descending, record index ascending, the later
             // member of a 128-bp bin dropped (locs.rs:321-342); with two of them their ln-probabilities come from the records again
             struct Group { AlnRef r0, r1; uint32_t k; };
@@ -1228,12 +1273,12 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
                     if (m == NOT_KEPT) return g;
                     unsigned long long x = NOT_KEPT;
                     if constexpr (TWO) { const uint32_t at = ovf_at[key]; if (at != LEAN_NONE) x = ovf_val[at]; }
-                    if (x == NOT_KEPT) { g.r0 = packed_ref(m, kept_lp[key] - best); g.k = 1u; return g; }
+                    if (x == NOT_KEPT) { g.r0 = unpack_saved(m, kept_lp[key] - best); g.k = 1u; return g; }
                     const uint32_t i0 = static_cast<uint32_t>(m >> 47), i1 = static_cast<uint32_t>(x >> 47);
-                    const double l0 = score_counted(L, recs[i0]).ln_prob, l1 = score_counted(L, recs[i1]).ln_prob;
+                    const double l0 = score_counted(L, h.raw(i0)).ln_prob, l1 = score_counted(L, h.raw(i1)).ln_prob;
                     const bool m_first = l0 > l1 || (l0 == l1 && i0 < i1);
-                    g.r0 = packed_ref(m_first ? m : x, (m_first ? l0 : l1) - best);
-                    g.r1 = packed_ref(m_first ? x : m, (m_first ? l1 : l0) - best);
+                    g.r0 = unpack_saved(m_first ? m : x, (m_first ? l0 : l1) - best);
+                    g.r1 = unpack_saved(m_first ? x : m, (m_first ? l1 : l0) - best);
                     g.k = (g.r0.start >> 7) == (g.r1.start >> 7) ? 1u : 2u;
                 }
                 return g;
@@ -1259,15 +1304,10 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
                 else ub += __popcll(__ballot(c < A && (head[c] & head[A + c]) != 0xFFFFFFFFu));
             }
             ub *= 3;
-            const bool at_once = !TWO && R.pa_chunk != 0 && static_cast<uint64_t>(ub) * 8 <= R.pa_chunk;
+            const bool at_once = !TWO && arena.shares(R, ub);
             bool room = true;
             if (at_once) {
-                if (ub > pool_left) {
-                    if (lane == 0) pool_at = atomicAdd(R.pa_count, static_cast<unsigned long long>(R.pa_chunk));
-                    pool_at = __shfl(pool_at, 0);
-                    pool_left = R.pa_chunk;
-                }
-                pa_base = pool_at;
+                pa_base = arena.upper_bound(R, lane, ub);
                 room = pa_base + ub <= R.pa_cap;
             }
             stamp(3);
@@ -1283,12 +1323,12 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
                     const bool small = build(c, f);
                     const uint32_t clen = L.allele_len[c];
                     if (small) {
-                        for (uint32_t i = 0; i < sc.k1; i++) { const AlnRef a = sc.get1(i); const uint32_t mid = (a.start + a.end) / 2; inb |= L.boundary <= mid && mid < clen - L.boundary; }
-                        for (uint32_t j = 0; j < sc.k2; j++) { const AlnRef a = sc.get2(j); const uint32_t mid = (a.start + a.end) / 2; inb |= L.boundary <= mid && mid < clen - L.boundary; }
+                        for (uint32_t i = 0; i < sc.k1; i++) inb |= in_bounds(sc.get1(i), clen, L.boundary);
+                        for (uint32_t j = 0; j < sc.k2; j++) inb |= in_bounds(sc.get2(j), clen, L.boundary);
                         res = count_pairs(sc, max_alns, L.prob_diff);
                     } else {
-                        if (f.has1) { const uint32_t mid = (f.a1.start + f.a1.end) / 2; inb |= L.boundary <= mid && mid < clen - L.boundary; }
-                        if (f.has2) { const uint32_t mid = (f.a2.start + f.a2.end) / 2; inb |= L.boundary <= mid && mid < clen - L.boundary; }
+                        if (f.has1) inb |= in_bounds(f.a1, clen, L.boundary);
+                        if (f.has2) inb |= in_bounds(f.a2, clen, L.boundary);
                         if (f.has1 || f.has2) res = fast_count(f, max_alns, L.prob_diff);
                     }
                     cnt8[c] = static_cast<uint8_t>(res.cnt);
@@ -1305,30 +1345,13 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
             }
             stamp(4);
             const bool any_inb = __ballot(inb) != 0ull;
-            total_cnt = wave_sum_u32(total_cnt);
-            if (lane == 0) R.recover_w[p] = any_inb ? weight : -1.0;
-            const bool edit_good = be0 <= thr0 && (!paired || be1 <= thr1);
-            if (!any_inb) { status = LCTY_READ_OUT_OF_BOUNDS; accepted = false; }
-            else if (!edit_good) { status = LCTY_READ_POORLY_MAPPED; accepted = false; }
-            else status = weight >= L.min_weight ? LCTY_READ_GOOD : LCTY_READ_FEW_KMERS;
+            total_cnt = wave_reduce(total_cnt, AddOp{});
+            status = pair_status(L, R, h, thr, best, any_inb, weight, paired, lane, &accepted);
             if (accepted && at_once) {
-                // what a pair that is not kept wrote stays behind the share's mark and is written over by the next pair
                 if (!room && lane == 0) atomicMax(R.err_flag, static_cast<uint32_t>(LCTY_ERR_RUNTIME));
-                pool_at += total_cnt; pool_left -= total_cnt;
+                arena.commit(total_cnt);
             } else if (accepted) {
-                if (R.pa_chunk == 0 || static_cast<uint64_t>(total_cnt) * 8 > R.pa_chunk) {
-                    if (lane == 0) pa_base = atomicAdd(R.pa_count, static_cast<unsigned long long>(total_cnt));
-                    pa_base = __shfl(pa_base, 0);
-                } else {
-                    if (total_cnt > pool_left) {
-                        if (lane == 0) pool_at = atomicAdd(R.pa_count, static_cast<unsigned long long>(R.pa_chunk));
-                        pool_at = __shfl(pool_at, 0);
-                        pool_left = R.pa_chunk;
-                    }
-                    pa_base = pool_at;
-                    pool_at += total_cnt; pool_left -= total_cnt;
-                }
-                if (lane == 0 && pa_base + total_cnt > R.pa_cap) atomicMax(R.err_flag, static_cast<uint32_t>(LCTY_ERR_RUNTIME));
+                pa_base = arena.reserve(R, lane, total_cnt);
                 room = pa_base + total_cnt <= R.pa_cap;
                 // ---------------- pass 3b: every lane wrote its own cnt8 entries: no barrier in between ----------------
                 run = 0;
@@ -1348,17 +1371,7 @@ __device__ __forceinline__ void score_lean_body(const LocusView& L, const ReadsV
                 }
             }
         }
-        if (status != LCTY_READ_GOOD)
-            for (uint32_t c = lane; c < A; c += WAVE) mrow[c] = 0.0;
-        if (lane == 0) {
-            R.status[p] = status;
-            R.weight[p] = accepted ? weight : 0.0;
-            R.unmapped_prob[p] = accepted ? unmapped_prob : 0.0;
-            R.pa_off[p] = accepted ? pa_base : 0ull;
-            R.pa_cnt[p] = accepted ? total_cnt : 0u;
-            R.uniq_kmers[2 * p] = accepted ? static_cast<uint16_t>(uk0) : 0;
-            R.uniq_kmers[2 * p + 1] = accepted ? static_cast<uint16_t>(uk1) : 0;
-        }
+        store_pair(L, R, h, lane, status, accepted, weight, unmapped_prob, pa_base, total_cnt, uk0, uk1);
         __syncthreads();
         stamp(5);
         if constexpr (TIMED) tph[7] += 1;
@@ -1408,20 +1421,22 @@ __global__ __launch_bounds__(WAVE, 3) void score_counted_big_explicit_kernel(con
     score_reads_body<true, true, true>(L, R, max_recs);
 }
 
-static size_t score_lds_bytes(uint32_t max_recs, uint32_t A) {
-    const size_t mr2 = (max_recs + 1) & ~1u;
-    size_t b = static_cast<size_t>(max_recs) * sizeof(Rec16) + static_cast<size_t>(A) * 8 + 4;   // rec + head + alen + cursor
-    b += 2 * mr2 * sizeof(uint16_t) + static_cast<size_t>(3) * A;                                // nxt + order + kk1/kk2/cnt8
-    return (b + 15) & ~static_cast<size_t>(15);
-}
-
-// BIG variant: the parked alignments (global scratch per workgroup) and the per-allele tables (LDS)
-static size_t score_park_bytes(uint32_t max_recs, uint32_t A) {
-    const size_t mr2 = (max_recs + 1) & ~1u;
-    return (static_cast<size_t>(max_recs) * sizeof(Rec16) + 2 * mr2 * sizeof(uint16_t) + static_cast<size_t>(3) * A + 255) & ~static_cast<size_t>(255);
-}
-static size_t score_table_bytes(uint32_t A) {
-    return (static_cast<size_t>(A) * 4 + 4 + 15) & ~static_cast<size_t>(15);
+// One launch's shape: the dynamic-LDS attribute is raised where a workgroup needs more than 48 KB, the wavefronts of a CU are as
+// many as fit its LDS (at most `most_per_cu`), the grid covers every CU with them, and the wavefronts take the arena in chunks when
+// every one of them has pairs enough for that.
+// chunk-wise reservation abandons up to one partly used chunk per wavefront and LAUNCH: the arena's slack (lcty_reads_create) covers
+// PA_MAX_GRID wavefronts of one launch, so larger grids (parts with more CUs) and the many launches of a streaming batch reserve per pair
+struct ScoreLaunch { uint32_t grid, pa_chunk; };
+constexpr size_t SCORE_LDS_MAX = 160 * 1024;
+template <typename K>
+static ScoreLaunch score_launch(const lcty_reads* reads, uint64_t n_pairs, K kernel, size_t lds, size_t most_per_cu) {
+    if (lds > 48 * 1024)
+        LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    const uint32_t cus = static_cast<uint32_t>(reads->ctx->props.multiProcessorCount);
+    const uint32_t per_cu = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(most_per_cu, SCORE_LDS_MAX / lds)));
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(n_pairs, static_cast<uint64_t>(cus) * per_cu));
+    const bool pooled = reads->pa_pooled && !reads->streaming;
+    return ScoreLaunch{static_cast<uint32_t>(grid), pooled && grid <= PA_MAX_GRID && n_pairs / grid >= PA_POOL_MIN_PAIRS ? PA_CHUNK : 0u};
 }
 
 void launch_score_reads(lcty_reads* reads) {
@@ -1429,39 +1444,28 @@ void launch_score_reads(lcty_reads* reads) {
     const LocusView L = reads->locus->view();
     ReadsView R = reads->view();
     const uint32_t max_recs = std::max<uint32_t>(reads->max_recs_per_pair, 1);
-    size_t lds = score_lds_bytes(max_recs, L.n_alleles);
-    const size_t lds_max = 160 * 1024;
     if (max_recs >= 65535) fail(LCTY_ERR_UNSUPPORTED, "more than 65534 records in one read pair");
     // the saved alignments of a pair live in LDS when they fit; beyond that (thousands of alleles, an alignment on each) in a
     // per-workgroup scratch in global memory, only the per-allele tables in LDS
-    const bool big = lds > lds_max;
-    if (big) {
-        lds = score_table_bytes(L.n_alleles);
-        if (lds > lds_max)
-            fail(LCTY_ERR_UNSUPPORTED, "%u alleles need %zu B of LDS for the per-allele tables (> %zu): not supported by this build",
-                 L.n_alleles, lds, lds_max);
-    }
+    const GeneralLayout<false> in_lds(L.n_alleles, max_recs);
+    const GeneralLayout<true> parked(L.n_alleles, max_recs);
+    const bool big = in_lds.lds_bytes > SCORE_LDS_MAX;
+    const size_t lds = big ? parked.lds_bytes : in_lds.lds_bytes;
+    if (lds > SCORE_LDS_MAX)
+        fail(LCTY_ERR_UNSUPPORTED, "%u alleles need %zu B of LDS for the per-allele tables (> %zu): not supported by this build",
+             L.n_alleles, lds, SCORE_LDS_MAX);
     const bool explicit_weights = L.ew_val != nullptr;
     auto kernel = reads->counted
         ? (big ? (explicit_weights ? score_counted_big_explicit_kernel : score_counted_big_kernel)
                : (explicit_weights ? score_counted_explicit_kernel : score_counted_kernel))
         : (big ? (explicit_weights ? score_reads_big_explicit_kernel : score_reads_big_kernel)
                : (explicit_weights ? score_reads_explicit_kernel : score_reads_kernel));
-    if (lds > 48 * 1024)
-        LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
-    const uint32_t per_cu = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(12, lds_max / lds)));
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(R.n_pairs, static_cast<uint64_t>(cus) * per_cu));
+    const ScoreLaunch general = score_launch(reads, R.n_pairs, kernel, lds, 12);
     if (big) {
-        const size_t stride = score_park_bytes(max_recs, L.n_alleles);
-        reads->d_park.ensure(stride * grid);
-        R.park = reads->d_park.p; R.park_stride = stride;
+        reads->d_park.ensure(static_cast<size_t>(parked.park_bytes) * general.grid);
+        R.park = reads->d_park.p; R.park_stride = parked.park_bytes;
     }
-    // chunk-wise reservation abandons up to one partly used chunk per wavefront and LAUNCH: the arena's slack (lcty_reads_create) covers
-    // PA_MAX_GRID wavefronts of one launch, so larger grids (parts with more CUs) and the many launches of a streaming batch reserve per pair
-    const bool pooled = reads->pa_pooled && !reads->streaming;
-    R.pa_chunk = pooled && grid <= PA_MAX_GRID && R.n_pairs / grid >= PA_POOL_MIN_PAIRS ? PA_CHUNK : 0u;
+    R.pa_chunk = general.pa_chunk;
     // the arena cursor goes back to where the pairs on the device start (0 unless a streaming batch has dropped chunks)
     if (reads->raw_first == 0) reads->d_pa_count.zero(ctx->stream);
     else reads->d_pa_count.upload(&reads->pa_at_raw_first, 1, ctx->stream);
@@ -1477,8 +1481,8 @@ void launch_score_reads(lcty_reads* reads) {
     ctx->timed(LCTY_K_SCORE, [&] {
         if (lean) {
             // sixteen wavefronts per CU either way: with the saved alignments' products kept in LDS (33 B per allele) while that many fit
-            const bool keep = static_cast<size_t>(L.n_alleles) * 33 + 16 <= lds_max / 16 && ctx->knob("score_lean_keep", 1) != 0;
-            const size_t lean_lds = (static_cast<size_t>(L.n_alleles) * (keep ? 33 : 9) + 15) & ~static_cast<size_t>(15);
+            const bool keep = static_cast<size_t>(L.n_alleles) * 33 + 16 <= SCORE_LDS_MAX / 16 && ctx->knob("score_lean_keep", 1) != 0;
+            const size_t lean_lds = keep ? LeanLayout<true, false>(L.n_alleles).lds_bytes : LeanLayout<false, false>(L.n_alleles).lds_bytes;
             auto lean_kernel = keep ? score_counted_lean_keep_kernel : score_counted_lean_kernel;
 #ifdef LCTY_DIAG
             const bool timing = ctx->diag_knob("score_timing", 0) != 0;
@@ -1486,26 +1490,21 @@ void launch_score_reads(lcty_reads* reads) {
 #else
             constexpr bool timing = false;
 #endif
-            if (lean_lds > 48 * 1024)
-                LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lean_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lean_lds)));
-            const uint32_t lean_per_cu = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(16, lds_max / lean_lds)));
-            const uint64_t lean_grid = std::max<uint64_t>(1, std::min<uint64_t>(R.n_pairs, static_cast<uint64_t>(cus) * lean_per_cu));
-            ReadsView RL = R;
-            RL.pa_chunk = pooled && lean_grid <= PA_MAX_GRID && R.n_pairs / lean_grid >= PA_POOL_MIN_PAIRS ? PA_CHUNK : 0u;
+            const ScoreLaunch ll = score_launch(reads, R.n_pairs, lean_kernel, lean_lds, 16);
+            ReadsView RL = R; RL.pa_chunk = ll.pa_chunk;
             if (timing) {
                 // diagnostic: the timed build of the lean kernel; ticks (10 ns) per pair of a wavefront, phase by phase, on stderr
                 reads->d_score_dbg.ensure(8); reads->d_score_dbg.zero(ctx->stream);
                 RL.dbg = reads->d_score_dbg.p;
-                hipLaunchKernelGGL(lean_kernel, dim3(static_cast<uint32_t>(lean_grid)), dim3(WAVE), lean_lds, ctx->stream, L, RL);
+                hipLaunchKernelGGL(lean_kernel, dim3(ll.grid), dim3(WAVE), lean_lds, ctx->stream, L, RL);
                 unsigned long long t[8];
                 reads->d_score_dbg.download(t, 8, ctx->stream);
                 LCTY_HIP(hipStreamSynchronize(ctx->stream));
                 const double n = static_cast<double>(std::max<unsigned long long>(t[7], 1));
                 fprintf(stderr, "[lcty score] lean kernel, ticks per pair of a wavefront (%llu pairs, %llu wavefronts): records + thresholds %.0f, pass 1 %.0f, "
-                        "k-mers %.0f, arena share %.0f, pass 3 %.0f, tail %.0f\n", t[7], static_cast<unsigned long long>(lean_grid),
+                        "k-mers %.0f, arena share %.0f, pass 3 %.0f, tail %.0f\n", t[7], static_cast<unsigned long long>(ll.grid),
                         t[0] / n, t[1] / n, t[2] / n, t[3] / n, t[4] / n, t[5] / n);
-            } else hipLaunchKernelGGL(lean_kernel, dim3(static_cast<uint32_t>(lean_grid)), dim3(WAVE), lean_lds, ctx->stream, L, RL);
+            } else hipLaunchKernelGGL(lean_kernel, dim3(ll.grid), dim3(WAVE), lean_lds, ctx->stream, L, RL);
             R.only_list = R.defer_list; R.only_count = R.defer_count;
             R.pa_chunk = 0;                                                     // the few pairs left reserve their own entries
             if (keep && ctx->knob("score_lean_two", 1) != 0) {
@@ -1515,17 +1514,14 @@ void launch_score_reads(lcty_reads* reads) {
                 reads->d_defer_count2.zero(ctx->stream);
                 ReadsView R2 = R;
                 R2.defer_list = reads->d_defer_list2.p; R2.defer_count = reads->d_defer_count2.p;
-                const size_t two_lds = ((((static_cast<size_t>(L.n_alleles) * 33 + 7) & ~static_cast<size_t>(7)) + LEAN_OVF * 8 + 8 + static_cast<size_t>(L.n_alleles) * 8) + 15) & ~static_cast<size_t>(15);
-                if (two_lds > 48 * 1024)
-                    LCTY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_counted_lean_two_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 static_cast<int>(two_lds)));
-                const uint32_t two_per_cu = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(8, lds_max / two_lds)));    // two wavefronts per SIMD: 2 x 2 alignments per contig in registers
-                const uint64_t two_grid = std::max<uint64_t>(1, std::min<uint64_t>(R.n_pairs, static_cast<uint64_t>(cus) * two_per_cu));
-                hipLaunchKernelGGL(score_counted_lean_two_kernel, dim3(static_cast<uint32_t>(two_grid)), dim3(WAVE), two_lds, ctx->stream, L, R2);
+                const size_t two_lds = LeanLayout<true, true>(L.n_alleles).lds_bytes;
+                // two wavefronts per SIMD: 2 x 2 alignments per contig in registers
+                const ScoreLaunch tl = score_launch(reads, R.n_pairs, score_counted_lean_two_kernel, two_lds, 8);
+                hipLaunchKernelGGL(score_counted_lean_two_kernel, dim3(tl.grid), dim3(WAVE), two_lds, ctx->stream, L, R2);
                 R.only_list = R2.defer_list; R.only_count = R2.defer_count;
             }
         }
-        hipLaunchKernelGGL(kernel, dim3(static_cast<uint32_t>(grid)), dim3(WAVE), lds, ctx->stream, L, R, max_recs);
+        hipLaunchKernelGGL(kernel, dim3(general.grid), dim3(WAVE), lds, ctx->stream, L, R, max_recs);
     });
     LCTY_HIP(hipGetLastError());
 }

@@ -78,6 +78,39 @@ def test_counted_edge_cases_and_misuse(gpu_ctx):
     assert e.value.code == cdefs.ERR_INVALID_INPUT
 
 
+def test_lean_kernel_takes_arena_shares(gpu_ctx):
+    """The scoring kernels hand the pair-alignment arena out in chunks per wavefront only in large launches: a batch that can hold
+    65 536 pairs and at least 32 pairs for every wavefront of a grid of 16 per CU, at most 4 096 wavefronts (256 CUs). 32 x 4 096 pairs
+    reach it on every device that can: there the lean kernel decides where a pair's entries go before it looks at the contigs and
+    writes them in the same pass, and the general kernel takes shares as well. Both, and the flow without the two-slot form, must
+    give the same products; a slice is held against the oracle. (Synthesis of the 2 M records takes a quarter of a second.)"""
+    n_pairs, n_alleles, n_slice = 32 * 4096, 8, 2000
+    L = synth.SynthLocus(n_alleles, n_pairs, seed=5, base_len=10_000)
+    p = api.resolve_params(api.default_params(), L.bg)
+    loc = api.Locus(gpu_ctx, L.seqs, L.seq_off, L.counts, L.cnt_off, L.k, L.bg, p)
+    ch = L.reads(0, n_pairs)
+    try:
+        shares = api.AllAlignments.load(loc, ch, counted=True)                 # one batch, default knobs
+        gpu_ctx.set_knob("score_lean", 0)
+        general = api.AllAlignments.load(loc, ch, counted=True)
+        _same(shares, general)
+        gpu_ctx.set_knob("score_lean", -1); gpu_ctx.set_knob("score_lean_two", 0)
+        no_two = api.AllAlignments.load(loc, ch, counted=True)
+        _same(shares, no_two)
+    finally:
+        gpu_ctx.set_knob("score_lean", -1); gpu_ctx.set_knob("score_lean_two", -1)
+    oa = O.OracleLocus(L.seqs, L.seq_off, L.counts, L.cnt_off, L.k, L.bg, p).load(ch.slice(0, n_slice))
+    st, w, unm, uk = shares.status()
+    assert np.array_equal(st[:n_slice], oa.status) and np.array_equal(uk[:2 * n_slice], oa.uniq_kmers)
+    Mo = oa.best_aln_matrix()                                                   # the good pairs of the slice are the first columns
+    assert Mo.shape[1] == oa.n_good > 0 and np.abs(shares.best_aln_matrix()[:, :oa.n_good] - Mo).max() < 1e-9
+    # every entry a pair counts is reachable, and is an entry: nothing of a share that was left unused comes back
+    off, pa = shares.pair_alns()
+    assert int(off[-1]) == len(pa) == int(np.diff(off).sum()) and len(pa) > n_pairs
+    assert (pa["contig"] < n_alleles).all() and np.isfinite(pa["ln_prob"]).all()
+    assert np.array_equal(off[:n_slice + 1], oa.pa_off)
+
+
 def test_lean_kernel_equals_the_general_kernel(gpu_ctx):
     """Counted batches go through the lean scoring kernel (at most one saved alignment per contig and read end), the pairs it leaves
     through its two-slot form (a second saved alignment per contig and read end) and what that leaves through the general one (lcty_score.hip). The same batch with the knob "score_lean" 0 — the general kernel on every
