@@ -19,6 +19,7 @@
 #include "lcty_bitonic.hpp"
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
+#include "lcty_table.hpp"
 
 #include <algorithm>
 #include <thread>
@@ -135,28 +136,8 @@ __global__ __launch_bounds__(1024) void db_sort_kernel(uint64_t* __restrict__ ha
 }
 
 // ---- column index -----------------------------------------------------------------------------------------------------------------------
-// Open addressing over the distinct hashes; slot `cap` is reserved for the hash that equals the empty marker (a list can hold UNDEF:
-// k = w = 1 and a non-ACGT first base push it, kmers.rs:326-329).
-__device__ inline uint64_t tab_start(uint64_t h, uint64_t cap) { return (h * 0x9E3779B97F4A7C15ull) >> 20 & (cap - 1); }
-__device__ inline uint64_t tab_insert(unsigned long long* keys, uint64_t cap, uint64_t h) {
-    if (h == UNDEF64) return cap;
-    for (uint64_t s = tab_start(h, cap);; s = (s + 1) & (cap - 1)) {
-        const unsigned long long seen = keys[s];
-        if (seen == h) return s;
-        if (seen == UNDEF64) {
-            const unsigned long long old = atomicCAS(&keys[s], static_cast<unsigned long long>(UNDEF64), static_cast<unsigned long long>(h));
-            if (old == UNDEF64 || old == h) return s;
-        }
-    }
-}
-__device__ inline uint64_t tab_find(const unsigned long long* keys, uint64_t cap, uint64_t h) {      // cap + 1: not there
-    if (h == UNDEF64) return cap;
-    for (uint64_t s = tab_start(h, cap);; s = (s + 1) & (cap - 1)) {
-        const unsigned long long seen = keys[s];
-        if (seen == h) return s;
-        if (seen == UNDEF64) return cap + 1;
-    }
-}
+// A key table over the distinct hashes (lcty_table.hpp). A list can hold UNDEF (k = w = 1 and a non-ACGT first base push it,
+// kmers.rs:326-329), which equals the free marker and is never stored: its columns live in slot `cap`, one behind the table.
 __device__ inline uint64_t lower_bound_dev(const uint64_t* v, uint64_t n, uint64_t h) {
     uint64_t lo = 0, hi = n;
     while (lo < hi) {
@@ -168,7 +149,7 @@ __device__ inline uint64_t lower_bound_dev(const uint64_t* v, uint64_t n, uint64
 
 // the last entry of every run of equal hashes enters the hash with the length of its run: mult[slot] = max_a c_a[h]
 __global__ __launch_bounds__(256) void db_runs_kernel(const uint64_t* __restrict__ hashes, const uint64_t* __restrict__ min_off,
-                                                      unsigned long long* __restrict__ keys, uint32_t* __restrict__ mult, uint64_t cap) {
+                                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ mult, uint64_t cap) {
     const uint32_t a = blockIdx.x;
     const uint64_t* v = hashes + min_off[a];
     const uint64_t n = min_off[a + 1] - min_off[a];
@@ -176,7 +157,8 @@ __global__ __launch_bounds__(256) void db_runs_kernel(const uint64_t* __restrict
         const uint64_t h = v[i];
         if (i + 1 < n && v[i + 1] == h) continue;
         const uint64_t run = i - lower_bound_dev(v, n, h) + 1;
-        atomicMax(&mult[tab_insert(keys, cap, h)], static_cast<uint32_t>(run));
+        const uint64_t slot = h == UNDEF64 ? cap : keytable::claim<keytable::MulHash, UNDEF64>(keys, cap - 1, h).slot;
+        atomicMax(&mult[slot], static_cast<uint32_t>(run));
     }
 }
 __global__ __launch_bounds__(256) void db_bases_kernel(const uint32_t* __restrict__ mult, uint32_t* __restrict__ base, uint64_t n_slots,
@@ -186,14 +168,15 @@ __global__ __launch_bounds__(256) void db_bases_kernel(const uint32_t* __restric
 }
 // column of entry i of list a: base[hash] + its rank within its run
 __global__ __launch_bounds__(256) void db_cols_kernel(const uint64_t* __restrict__ hashes, const uint64_t* __restrict__ min_off,
-                                                      const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ base, uint64_t cap,
+                                                      const uint64_t* __restrict__ keys, const uint32_t* __restrict__ base, uint64_t cap,
                                                       uint32_t* __restrict__ col) {
     const uint32_t a = blockIdx.x;
     const uint64_t* v = hashes + min_off[a];
     const uint64_t n = min_off[a + 1] - min_off[a];
     for (uint64_t i = uint64_t(blockIdx.y) * 256 + threadIdx.x; i < n; i += uint64_t(gridDim.y) * 256) {
         const uint64_t h = v[i];
-        col[min_off[a] + i] = base[tab_find(keys, cap, h)] + static_cast<uint32_t>(i - lower_bound_dev(v, n, h));
+        const uint64_t slot = h == UNDEF64 ? cap : keytable::find<keytable::MulHash, UNDEF64>(keys, cap - 1, h).slot;      // db_runs_kernel claimed it
+        col[min_off[a] + i] = base[slot] + static_cast<uint32_t>(i - lower_bound_dev(v, n, h));
     }
 }
 // bits of the columns [c0, c1) of every row; B[n_pad][W] 64-bit words, W * 64 >= c1 - c0
@@ -253,17 +236,17 @@ __global__ __launch_bounds__(256) void db_gram_kernel(const uint64_t* __restrict
 
 // ---- off-target counts (k <= 31: 64-bit canonical k-mers; all-ones = a k-mer over a non-ACGT base, Kmer::UNDEF) -------------------------
 // the key of the tables is the value of canonical_kmer_ascii: min(fw, rv)
-__global__ __launch_bounds__(256) void db_ref_insert_kernel(const uint8_t* __restrict__ ref, uint64_t n_kmers, uint32_t k, unsigned long long* __restrict__ keys,
+__global__ __launch_bounds__(256) void db_ref_insert_kernel(const uint8_t* __restrict__ ref, uint64_t n_kmers, uint32_t k, uint64_t* __restrict__ keys,
                                                             uint32_t* __restrict__ first, uint32_t* __restrict__ occ, uint64_t cap) {
     const uint64_t p = uint64_t(blockIdx.x) * 256 + threadIdx.x;
     if (p >= n_kmers) return;
     uint64_t km;
     if (!canonical_kmer_ascii(ref, p, k, &km)) return;                                              // the map's UNDEF entry is max_value whatever happens (counts.rs:198, 202)
-    const uint64_t s = tab_insert(keys, cap, km);
+    const uint64_t s = keytable::claim<keytable::MulHash, UNDEF64>(keys, cap - 1, km).slot;      // a k-mer of k <= 31 bases is never all-ones
     atomicMin(&first[s], static_cast<uint32_t>(p));
     atomicAdd(&occ[s], 1u);
 }
-__global__ __launch_bounds__(256) void db_ref_value_kernel(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ first, const uint32_t* __restrict__ occ,
+__global__ __launch_bounds__(256) void db_ref_value_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ first, const uint32_t* __restrict__ occ,
                                                            uint64_t cap, const uint16_t* __restrict__ ref_counts, uint32_t max_value,
                                                            uint16_t* __restrict__ value, uint32_t* __restrict__ negatives) {
     const uint64_t s = uint64_t(blockIdx.x) * 256 + threadIdx.x;
@@ -273,7 +256,7 @@ __global__ __launch_bounds__(256) void db_ref_value_kernel(const unsigned long l
     if (f != max_value && m > f) *negatives = 1;
 }
 __global__ __launch_bounds__(256) void db_offt_kernel(const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ seq_off, const uint16_t* __restrict__ counts,
-                                                      const uint64_t* __restrict__ cnt_off, uint32_t k, const unsigned long long* __restrict__ keys,
+                                                      const uint64_t* __restrict__ cnt_off, uint32_t k, const uint64_t* __restrict__ keys,
                                                       const uint16_t* __restrict__ value, uint64_t cap, uint32_t max_value, uint16_t* __restrict__ out) {
     const uint32_t a = blockIdx.x;
     const uint8_t* s = seqs + seq_off[a];
@@ -283,16 +266,14 @@ __global__ __launch_bounds__(256) void db_offt_kernel(const uint8_t* __restrict_
         uint16_t v;
         if (!canonical_kmer_ascii(s, p, k, &km)) v = static_cast<uint16_t>(max_value);
         else {
-            const uint64_t slot = tab_find(keys, cap, km);
-            v = slot <= cap ? value[slot] : counts[cnt_off[a] + p];
+            const keytable::Probe at = keytable::find<keytable::MulHash, UNDEF64>(keys, cap - 1, km);
+            v = at.found ? value[at.slot] : counts[cnt_off[a] + p];
         }
         out[cnt_off[a] + p] = v;
     }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
-uint64_t pow2_at_least(uint64_t x) { uint64_t c = 1024; while (c < x) c <<= 1; return c; }
-
 // what the kernels here take: positions inside a sequence are 31 bits wide
 HapSet check_db_haps(uint32_t n, const uint8_t* seqs, const uint64_t* seq_off, uint32_t min_seqs) {
     return check_haps(n, seqs, seq_off, HapLimits{min_seqs, UINT32_MAX, 1ull << 31});
@@ -395,8 +376,8 @@ void divergences(lcty_ctx* ctx, const HapSet& hs, const uint8_t* seqs, const uin
     const uint64_t total = L.off[n], n_pairs = uint64_t(n) * (n - 1) / 2;
     double t0 = now_ms();
     // column index
-    const uint64_t cap = pow2_at_least(2 * std::max<uint64_t>(total, 1));
-    DevBuf<unsigned long long> keys; DevBuf<uint32_t> mult, base, col, n_cols;
+    const uint64_t cap = keytable::table_slots(total, 1, 1024);
+    DevBuf<uint64_t> keys; DevBuf<uint32_t> mult, base, col, n_cols;
     keys.alloc(cap + 1); mult.alloc(cap + 2); base.alloc(cap + 2); col.alloc(std::max<uint64_t>(total, 1)); n_cols.alloc(1);
     LCTY_HIP(hipMemsetAsync(keys.p, 0xFF, (cap + 1) * 8, s));
     mult.zero(s); base.zero(s); n_cols.zero(s);
@@ -561,9 +542,9 @@ void off_target(lcty_ctx* ctx, uint32_t n, const uint8_t* seqs, const uint64_t* 
         hipStream_t s = ctx->stream;
         uint64_t max_n = 0;
         for (uint32_t a = 0; a < n; a++) max_n = std::max(max_n, cnt_off[a + 1] - cnt_off[a]);
-        const uint64_t cap = pow2_at_least(2 * std::max<uint64_t>(n_ref, 1));
+        const uint64_t cap = keytable::table_slots(n_ref, 1, 1024);
         DevHaps d; DevBuf<uint8_t> d_ref; DevBuf<uint64_t> d_cnt_off; DevBuf<uint16_t> d_counts, d_out, d_ref_counts, d_value;
-        DevBuf<unsigned long long> keys; DevBuf<uint32_t> first, occ, d_neg;
+        DevBuf<uint64_t> keys; DevBuf<uint32_t> first, occ, d_neg;
         d_ref.alloc(std::max<uint64_t>(ref_len, 1)); d_cnt_off.alloc(n + 1);
         d_counts.alloc(std::max<uint64_t>(n_counts, 1)); d_out.alloc(std::max<uint64_t>(n_counts, 1)); d_ref_counts.alloc(std::max<uint64_t>(n_ref, 1));
         d_value.alloc(cap + 1); keys.alloc(cap + 1); first.alloc(cap + 1); occ.alloc(cap + 1); d_neg.alloc(1);

@@ -41,7 +41,7 @@ struct LocusView {
     double compl_mult;              // 1 / min(neighb+1-ck, 4^ck)
     uint32_t half_neighb;
     // UniqueKmers (src/model/locs.rs:915-1003)
-    const uint64_t* kset;           // open addressing, KSET_EMPTY = free
+    const uint64_t* kset;           // key table (lcty_table.hpp: MixHash, free = UNDEF64)
     uint64_t kset_mask;             // capacity - 1
     uint32_t undef_in_set;          // UNDEF was inserted (an allele window with N has count 0)
     double weight_mult, weight_interc;
@@ -102,28 +102,19 @@ struct ReadsView {
 };
 
 #ifdef __HIPCC__
-// ---- set probes. k-mers of 32..63 bases: the set is an open-addressing table of {lo, hi} pairs built on the host (lcty_locus_create),
-// free = {~0, ~0} ----
+// ---- set probe. k-mers of 32..63 bases: the set is an open-addressing table of {lo, hi} pairs built on the host (lcty_locus_create),
+// free = {~0, ~0}: another key type than that of lcty_table.hpp, which serves k <= 31 ----
 __host__ __device__ inline uint64_t kmer128_hash(uint64_t lo, uint64_t hi) { return mix64(lo ^ mix64(hi ^ 0x9E3779B97F4A7C15ull)); }
 __device__ inline bool kset128_contains(const uint64_t* kset, uint64_t mask, Kmer128 key) {
     uint64_t slot = kmer128_hash(key.lo, key.hi) & mask;
     while (true) {
         const uint64_t lo = kset[2 * slot], hi = kset[2 * slot + 1];
         if (lo == key.lo && hi == key.hi) return true;
-        if (lo == KSET_EMPTY && hi == KSET_EMPTY) return false;
+        if (lo == UNDEF64 && hi == UNDEF64) return false;
         slot = (slot + 1) & mask;
     }
 }
 
-__device__ inline bool kset_contains(const uint64_t* kset, uint64_t mask, uint64_t key) {
-    uint64_t slot = mix64(key) & mask;
-    while (true) {
-        const uint64_t v = kset[slot];
-        if (v == key) return true;
-        if (v == KSET_EMPTY) return false;
-        slot = (slot + 1) & mask;
-    }
-}
 #endif
 
 }  // namespace lcty

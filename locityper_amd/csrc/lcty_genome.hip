@@ -13,6 +13,7 @@
 #include "lcty_common.hpp"
 #include "lcty_lines.hpp"
 #include "lcty_seq.hpp"
+#include "lcty_table.hpp"
 
 using namespace lcty;
 
@@ -91,33 +92,10 @@ __device__ inline uint64_t query_kmer(const uint8_t* seqs, const uint64_t* seq_o
     return kmer;
 }
 
-__device__ inline void table_insert(uint64_t* keys, uint64_t mask, uint64_t key) {
-    uint64_t slot = mix64(key) & mask;
-    for (;;) {
-        const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&keys[slot]), static_cast<unsigned long long>(UNDEF64),
-                                                 static_cast<unsigned long long>(key));
-        if (old == UNDEF64 || old == key) return;
-        slot = (slot + 1) & mask;
-    }
-}
-
 __global__ void query_insert_kernel(const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ seq_off, const uint64_t* __restrict__ cnt_off,
                                     uint32_t n_seqs, uint32_t k, uint64_t n_values, uint64_t* keys, uint64_t mask) {
     for (uint64_t o = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; o < n_values; o += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-        table_insert(keys, mask, query_kmer(seqs, seq_off, cnt_off, n_seqs, k, o));
-}
-
-__global__ void table_count_kernel(const uint64_t* __restrict__ keys, uint64_t slots, unsigned long long* out) {
-    uint64_t local = 0;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < slots; i += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-        local += keys[i] != UNDEF64;
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off);
-    if ((threadIdx.x & 63u) == 0 && local) atomicAdd(out, static_cast<unsigned long long>(local));
-}
-
-__global__ void table_compact_kernel(const uint64_t* __restrict__ big, uint64_t big_slots, uint64_t* keys, uint64_t mask) {
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < big_slots; i += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-        if (big[i] != UNDEF64) table_insert(keys, mask, big[i]);
+        keytable::claim<keytable::MixHash, UNDEF64>(keys, mask, query_kmer(seqs, seq_off, cnt_off, n_seqs, k, o));
 }
 
 // ---- the scan (the hot path). A thread owns the RUN k-mer starts from s = RUN * its index on: it reads the 8 words of their bases,
@@ -125,8 +103,8 @@ __global__ void table_compact_kernel(const uint64_t* __restrict__ big, uint64_t 
 // them, and counts the valid bases since the last masked one — a k-mer ends at base i iff that count has reached k, so no k-mer that
 // starts before s, spans a masked base or reaches behind `n_pos` is ever looked up. The 16 lookups of a word are issued together
 // (16 loads in flight a lane), then resolved: the first slot holds the key (a hit), the free marker (a miss) or another key (the
-// probe goes on). MERGE: equal consecutive hits of a thread (a homopolymer, a tandem repeat of period 1) are
-// added as one atomic. ----
+// probe goes on): keytable::find of lcty_table.hpp in a batched form, which stays written out. MERGE: equal
+// consecutive hits of a thread (a homopolymer, a tandem repeat of period 1) are added as one atomic. ----
 template <bool MERGE>
 __global__ void __launch_bounds__(THREADS) genome_scan_kernel(const uint32_t* __restrict__ bases2, const uint32_t* __restrict__ nmask, uint64_t n_pos,
                                                              uint32_t k, const uint64_t* __restrict__ keys, uint32_t* counters, uint64_t mask,
@@ -170,13 +148,13 @@ __global__ void __launch_bounds__(THREADS) genome_scan_kernel(const uint32_t* __
                     if (valid >= k) ends |= 1u << j;
                 }
 #pragma unroll
-                for (uint32_t j = 0; j < 16; j++) first[j] = ((ends >> j) & 1u) ? keys[mix64(key[j]) & mask] : UNDEF64;
+                for (uint32_t j = 0; j < 16; j++) first[j] = ((ends >> j) & 1u) ? keys[keytable::home<keytable::MixHash>(key[j], mask)] : UNDEF64;
 #pragma unroll
                 for (uint32_t j = 0; j < 16; j++) {
                     uint64_t got = first[j];
                     if (got == UNDEF64) continue;                         // no k-mer ends here, or its first slot is free: a miss
-                    uint64_t slot = mix64(key[j]) & mask;
-                    while (got != key[j] && got != UNDEF64) { slot = (slot + 1) & mask; got = keys[slot]; }
+                    uint64_t slot = keytable::home<keytable::MixHash>(key[j], mask);
+                    while (got != key[j] && got != UNDEF64) { slot = keytable::step(slot, mask); got = keys[slot]; }
                     if (got != key[j]) continue;
                     hits++;
                     if (MERGE) {
@@ -201,16 +179,13 @@ __global__ void query_gather_kernel(const uint8_t* __restrict__ seqs, const uint
                                     const uint32_t* __restrict__ counters, uint64_t mask, uint32_t max_value, uint16_t* out) {
     for (uint64_t o = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; o < n_values; o += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
         const uint64_t key = query_kmer(seqs, seq_off, cnt_off, n_seqs, k, o);
-        uint64_t slot = mix64(key) & mask;
-        uint64_t probes = 0;                                             // every query k-mer is in the table: found before a free slot
-        while (keys[slot] != key && keys[slot] != UNDEF64 && probes++ <= mask) slot = (slot + 1) & mask;
-        const uint32_t c = keys[slot] == key ? counters[slot] : 0u;
+        const keytable::Probe p = keytable::find<keytable::MixHash, UNDEF64>(keys, mask, key);        // every query k-mer is in the table
+        const uint32_t c = p.found ? counters[p.slot] : 0u;
         out[o] = static_cast<uint16_t>(max(min(c, max_value), 1u));      // counts.rs:354-355
     }
 }
 
 uint32_t grid_for(uint64_t n) { return std::max(1u, std::min(blocks_of(n, THREADS), MAX_GRID)); }
-uint64_t pow2_at_least(uint64_t n) { uint64_t p = 64; while (p < n) p <<= 1; return p; }
 
 struct Contig { std::string name; uint64_t start, len; };
 
@@ -468,25 +443,25 @@ int32_t lcty_genome_kmer_counts(const lcty_genome* genome, uint32_t k, uint32_t 
         // stage 2: the table. Sized for every query k-mer being distinct, counted, and rebuilt at the size the distinct ones need.
         DevBuf<uint64_t> keys;
         DevBuf<uint32_t> counters;
-        uint64_t slots = pow2_at_least(2 * n_values);
+        uint64_t slots = keytable::table_slots(n_values, 1, 64);
         keys.alloc(slots);
         LCTY_HIP(hipMemsetAsync(keys.p, 0xFF, slots * sizeof(uint64_t), s));
         if (n_values) {
             hipLaunchKernelGGL(query_insert_kernel, dim3(grid_for(n_values)), dim3(THREADS), 0, s, d.seqs.p, d.off.p, d_cnt_off.p, n_seqs, k, n_values,
                                keys.p, slots - 1);
             LCTY_HIP(hipGetLastError());
-            hipLaunchKernelGGL(table_count_kernel, dim3(grid_for(slots)), dim3(THREADS), 0, s, keys.p, slots, d_word.p + 1);
+            hipLaunchKernelGGL(keytable::table_count_kernel<UNDEF64>, dim3(grid_for(slots)), dim3(THREADS), 0, s, keys.p, slots, d_word.p + 1);
             LCTY_HIP(hipGetLastError());
         }
         unsigned long long n_distinct = 0;
         d_word.download(&n_distinct, 1, s, 1);
         LCTY_HIP(hipStreamSynchronize(s));
-        const uint64_t small = pow2_at_least(2 * n_distinct);
+        const uint64_t small = keytable::table_slots(n_distinct, 1, 64);
         if (small < slots) {
             DevBuf<uint64_t> k2;
             k2.alloc(small);
             LCTY_HIP(hipMemsetAsync(k2.p, 0xFF, small * sizeof(uint64_t), s));
-            hipLaunchKernelGGL(table_compact_kernel, dim3(grid_for(slots)), dim3(THREADS), 0, s, keys.p, slots, k2.p, small - 1);
+            hipLaunchKernelGGL((keytable::table_compact_kernel<keytable::MixHash, UNDEF64>), dim3(grid_for(slots)), dim3(THREADS), 0, s, keys.p, slots, k2.p, small - 1);
             LCTY_HIP(hipGetLastError());
             LCTY_HIP(hipStreamSynchronize(s));
             keys = std::move(k2); slots = small;

@@ -1,5 +1,5 @@
 // lcty_locus.hip — per-locus preprocessing.
-//   K1  UniqueKmers::new (src/model/locs.rs:930-963): device hash set of locus-unique canonical k-mers
+//   K1  UniqueKmers::new (src/model/locs.rs:930-963): the locus-unique canonical k-mers as a key table (lcty_table.hpp)
 //   K3  ContigInfo::new  (src/model/windows.rs:362-424): GC / unique-k-mer / complexity moving windows
 //       (contig_info_kernel: thread per neighbourhood position, seen ck-mers as an LDS bit set)
 //   LUTs: InsertDistr (bg/insertsz.rs:195-208), DistrCache (model/distr_cache.rs:61-75),
@@ -9,6 +9,7 @@
 #include <memory>
 
 #include "lcty_objects.hpp"
+#include "lcty_table.hpp"
 
 namespace lcty {
 
@@ -17,17 +18,6 @@ namespace lcty {
 // restating kmers::kmers::<_, _, CANONICAL> (src/seq/kmers.rs:163-202) on the ASCII sequence.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t KSEG = 64;
-
-__device__ inline void kset_insert(uint64_t* table, uint64_t mask, uint64_t key) {
-    uint64_t slot = mix64(key) & mask;
-    while (true) {
-        const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[slot]),
-                                                 static_cast<unsigned long long>(KSET_EMPTY),
-                                                 static_cast<unsigned long long>(key));
-        if (old == KSET_EMPTY || old == key) return;
-        slot = (slot + 1) & mask;
-    }
-}
 
 __global__ void kset_build_kernel(const uint8_t* __restrict__ seqs, const uint64_t* __restrict__ seq_off,
                                   const uint16_t* __restrict__ counts, const uint64_t* __restrict__ cnt_off,
@@ -57,28 +47,11 @@ __global__ void kset_build_kernel(const uint8_t* __restrict__ seqs, const uint64
         if (i + 1 >= s + k) {
             const uint64_t pos = i + 1 - k;
             if (i >= reset) {
-                if (cnt[pos] == 0) kset_insert(table, mask, rv < fw ? rv : fw);
+                if (cnt[pos] == 0) keytable::claim<keytable::MixHash, UNDEF64>(table, mask, rv < fw ? rv : fw);
             } else if (cnt[pos] == 0) {
                 atomicOr(undef_flag, 1u);
             }
         }
-    }
-}
-
-__global__ void kset_count_kernel(const uint64_t* __restrict__ table, uint64_t cap, unsigned long long* out) {
-    uint64_t local = 0;
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < cap;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x)
-        local += table[i] != KSET_EMPTY;
-    for (int off = WAVE / 2; off > 0; off >>= 1) local += __shfl_down(local, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && local) atomicAdd(out, static_cast<unsigned long long>(local));
-}
-
-__global__ void kset_compact_kernel(const uint64_t* __restrict__ big, uint64_t big_cap, uint64_t* small, uint64_t small_mask) {
-    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < big_cap;
-         i += static_cast<uint64_t>(gridDim.x) * blockDim.x) {
-        const uint64_t key = big[i];
-        if (key != KSET_EMPTY) kset_insert(small, small_mask, key);
     }
 }
 
@@ -120,12 +93,6 @@ __global__ void explicit_window_kernel(const uint64_t* __restrict__ cum, const u
     const uint32_t start = i + left_padding;
     const double avg = static_cast<double>((c[start + window] - c[start]) / static_cast<uint64_t>(window)) / 4294967296.0;
     win_weight[o + i] = win_weight[o + i] * avg;
-}
-
-static uint64_t next_pow2(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -454,12 +421,13 @@ int32_t lcty_locus_create(lcty_ctx* ctx, uint32_t n_alleles, const uint8_t* seqs
             keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
             L->undef_in_set = undef ? 1u : 0u;
             L->n_unique = keys.size() + (undef ? 1 : 0);
-            L->kset_cap = next_pow2(std::max<uint64_t>(4 * keys.size(), 1024));
-            std::vector<uint64_t> table(2 * L->kset_cap, KSET_EMPTY);
+            L->kset_cap = keytable::table_slots(keys.size(), 2, 1024);
+            // {lo, hi} pairs, free = {~0, ~0}: another key type than lcty_table.hpp's, placed by its step (the keys are distinct: no compare)
+            std::vector<uint64_t> table(2 * L->kset_cap, UNDEF64);
             for (const u128 key : keys) {
                 const uint64_t lo = static_cast<uint64_t>(key), hi = static_cast<uint64_t>(key >> 64);
                 uint64_t slot = kmer128_hash(lo, hi) & (L->kset_cap - 1);
-                while (table[2 * slot] != KSET_EMPTY || table[2 * slot + 1] != KSET_EMPTY) slot = (slot + 1) & (L->kset_cap - 1);
+                while (table[2 * slot] != UNDEF64 || table[2 * slot + 1] != UNDEF64) slot = keytable::step(slot, L->kset_cap - 1);
                 table[2 * slot] = lo; table[2 * slot + 1] = hi;
             }
             L->d_kset.alloc(table.size()); L->d_kset.upload(table.data(), table.size(), s);
@@ -468,7 +436,7 @@ int32_t lcty_locus_create(lcty_ctx* ctx, uint32_t n_alleles, const uint8_t* seqs
         // ---- K1 (device) ----
         {
             DevBuf<uint64_t> d_big; DevBuf<uint32_t> d_flag; DevBuf<unsigned long long> d_n;
-            const uint64_t big_cap = next_pow2(std::max<uint64_t>(2 * total_cnt, 1024));      // at most one key per k-mer position
+            const uint64_t big_cap = keytable::table_slots(total_cnt, 1, 1024);      // at most one key per k-mer position
             d_big.alloc(big_cap);
             LCTY_HIP(hipMemsetAsync(d_big.p, 0xFF, big_cap * sizeof(uint64_t), s));
             d_flag.alloc(1); d_flag.zero(s);
@@ -479,17 +447,17 @@ int32_t lcty_locus_create(lcty_ctx* ctx, uint32_t n_alleles, const uint8_t* seqs
             dim3 grid((segs + threads - 1) / threads, n_alleles);
             hipLaunchKernelGGL(kset_build_kernel, grid, dim3(threads), 0, s, d_seqs.p, d_seq_off.p, d_counts.p,
                                d_cnt_off.p, k, d_big.p, big_cap - 1, d_flag.p);
-            hipLaunchKernelGGL(kset_count_kernel, dim3(1024), dim3(256), 0, s, d_big.p, big_cap, d_n.p);
+            hipLaunchKernelGGL(keytable::table_count_kernel<UNDEF64>, dim3(1024), dim3(256), 0, s, d_big.p, big_cap, d_n.p);
             unsigned long long n_distinct = 0; uint32_t flag = 0;
             LCTY_HIP(hipMemcpyAsync(&n_distinct, d_n.p, sizeof(n_distinct), hipMemcpyDeviceToHost, s));
             LCTY_HIP(hipMemcpyAsync(&flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, s));
             LCTY_HIP(hipStreamSynchronize(s));
             L->undef_in_set = flag;
             L->n_unique = n_distinct + (flag ? 1 : 0);
-            L->kset_cap = next_pow2(std::max<uint64_t>(4 * n_distinct, 1024));
+            L->kset_cap = keytable::table_slots(n_distinct, 2, 1024);
             L->d_kset.alloc(L->kset_cap);
             LCTY_HIP(hipMemsetAsync(L->d_kset.p, 0xFF, L->kset_cap * sizeof(uint64_t), s));
-            hipLaunchKernelGGL(kset_compact_kernel, dim3(1024), dim3(256), 0, s, d_big.p, big_cap, L->d_kset.p, L->kset_cap - 1);
+            hipLaunchKernelGGL((keytable::table_compact_kernel<keytable::MixHash, UNDEF64>), dim3(1024), dim3(256), 0, s, d_big.p, big_cap, L->d_kset.p, L->kset_cap - 1);
             LCTY_HIP(hipGetLastError());
             LCTY_HIP(hipStreamSynchronize(s));
         }

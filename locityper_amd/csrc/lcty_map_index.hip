@@ -6,8 +6,7 @@
 // mapping call of 2 048 long reads). Here: one thread per window writes (k-mer, place) — windows with a base other than ACGT get the
 // key ~0 and sort behind everything —, a stable radix sort by k-mer (below; the places were written in (allele, position) order and
 // stay so inside a run), heads of runs by comparison with the left neighbour, their starts by a prefix sum, and one thread per run
-// claims a slot (64-bit compare-and-swap on the key, linear probing). Which slot a k-mer ends up in depends on who gets there first;
-// what a lookup finds does not.
+// claims a slot of the key table (lcty_table.hpp).
 //
 // The sort (RadixSort, lcty_sort.hpp): least significant digit first, eight bits a pass, over the bytes a k-mer of this
 // k can differ in plus the top byte (where the key of a window without a k-mer differs from all of them). A pass is three steps over
@@ -40,7 +39,7 @@ __global__ __launch_bounds__(256) void index_pairs_kernel(const uint8_t* __restr
         uint64_t kmer;
         bool fwd;                                                    // fw <= rv: a palindrome's place counts as forward
         const bool ok = canonical_kmer_ascii(seqs + seq_off[basis[b]], i, k, &kmer, &fwd);
-        keys[w] = ok ? kmer : MAP_FREE;
+        keys[w] = ok ? kmer : UNDEF64;
         places[w] = (static_cast<uint64_t>(b) << 33) | (i << 1) | (fwd ? 1ull : 0ull);
         bad = ok ? 0u : 1u;
     }
@@ -61,18 +60,12 @@ __global__ __launch_bounds__(256) void index_starts_kernel(const uint32_t* __res
 }
 
 __global__ __launch_bounds__(256) void index_insert_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ run_start, uint32_t n_runs,
-                                                           uint32_t n_valid, MapSlot* __restrict__ table, uint64_t mask) {
+                                                           uint32_t n_valid, keytable::Slot* __restrict__ table, uint64_t mask) {
     const uint32_t r = blockIdx.x * 256 + threadIdx.x;
     if (r >= n_runs) return;
     const uint32_t start = run_start[r], end = r + 1 < n_runs ? run_start[r + 1] : n_valid;
     const uint64_t key = keys[start];
-    uint64_t h = fast_hash64(key) & mask;
-    for (;;) {
-        const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[h].key), static_cast<unsigned long long>(MAP_FREE),
-                                                 static_cast<unsigned long long>(key));
-        if (old == MAP_FREE) break;                                  // every k-mer has one run: nobody else asks for this key
-        h = (h + 1) & mask;
-    }
+    const uint64_t h = keytable::claim<keytable::FastHash, UNDEF64>(table, mask, key).slot;      // every k-mer has one run: nobody else asks for this key
     table[h].start = start; table[h].count = end - start;
 }
 
@@ -133,10 +126,9 @@ std::shared_ptr<MapIndex> build_map_index_device(lcty_locus* locus, const uint16
         hipLaunchKernelGGL(index_starts_kernel, dim3(blocks), dim3(256), 0, s, head.p, rank.p, static_cast<uint64_t>(n_valid), run_start.p);
         LCTY_HIP(hipGetLastError());
     }
-    uint64_t cap = 1024;
-    while (cap < 2 * static_cast<uint64_t>(n_runs)) cap <<= 1;
+    const uint64_t cap = keytable::table_slots(n_runs, 1, 1024);
     ix->table.alloc(cap);
-    LCTY_HIP(hipMemsetAsync(ix->table.p, 0xFF, cap * sizeof(MapSlot), s));          // key ~0 = free (start / count of a free slot are never read)
+    LCTY_HIP(hipMemsetAsync(ix->table.p, 0xFF, cap * sizeof(keytable::Slot), s));   // key ~0 = free (start / count of a free slot are never read)
     ix->mask = cap - 1;
     if (n_runs) {
         hipLaunchKernelGGL(index_insert_kernel, dim3((n_runs + 255) / 256), dim3(256), 0, s, keys_b.p, run_start.p, n_runs, n_valid, ix->table.p, ix->mask);

@@ -18,6 +18,7 @@
 #include <memory>
 
 #include "lcty_objects.hpp"
+#include "lcty_table.hpp"
 
 namespace lcty {
 
@@ -39,8 +40,6 @@ enum : uint32_t {
     MAPC_N = 8
 };
 
-struct MapSlot { uint64_t key; uint32_t start, count; };   // key MAP_FREE = free; the slot of a k-mer starts at fast_hash64(key) & mask
-
 __device__ __forceinline__ uint32_t base_at(const uint32_t* b2, uint64_t off, uint32_t i) {
     const uint64_t p = off + i;
     return (b2[p >> 4] >> (2 * (p & 15u))) & 3u;
@@ -51,7 +50,8 @@ __device__ __forceinline__ bool n_at(const uint32_t* nm, uint64_t off, uint32_t 
 }
 
 struct MapIndex {
-    DevBuf<MapSlot> table; DevBuf<uint64_t> entries; DevBuf<uint16_t> basis; DevBuf<uint32_t> scratch;
+    DevBuf<keytable::Slot> table;          // canonical k-mer -> its run of `entries` (lcty_table.hpp: FastHash, free = UNDEF64)
+    DevBuf<uint64_t> entries; DevBuf<uint16_t> basis; DevBuf<uint32_t> scratch;
     uint64_t mask = 0; uint32_t k = 0, n_basis = 0;
 };
 
@@ -73,7 +73,7 @@ struct MapRun {
 
 // what the kernels of both routes are given; MapView and LongView add their route's candidates and scratch
 struct MapViewCommon {
-    const MapSlot* table; uint64_t mask;
+    const keytable::Slot* table; uint64_t mask;
     const uint64_t* entries;               // basis index << 33 | position << 1 | forward-is-canonical
     const uint16_t* basis;                 // basis index -> allele
     uint32_t n_basis, k, stride, min_votes, max_occ, band;
@@ -116,9 +116,11 @@ __device__ __forceinline__ MapSeed map_seed_at(const MapViewCommon& V, uint64_t 
     MapSeed sd{sidx < n0 ? sidx * V.stride : span, 0u, 0u, false};
     if (window_has_n(V.nmask + (off >> 5), sd.pr, V.k)) return sd;
     const uint64_t canon = canonical_kmer_2bit(reinterpret_cast<const uint64_t*>(V.bases2 + (off >> 4)), sd.pr, V.k, &sd.read_fwd);
-    for (uint64_t h = fast_hash64(canon) & V.mask;; h = (h + 1) & V.mask) {
-        const MapSlot s = V.table[h];
-        if (s.key == MAP_FREE) break;
+    // keytable::find (lcty_table.hpp) written out: through the function the long route's kernels compile to other instructions, and
+    // their time left the parent's range on the slow side
+    for (uint64_t h = keytable::home<keytable::FastHash>(canon, V.mask);; h = keytable::step(h, V.mask)) {
+        const keytable::Slot s = V.table[h];
+        if (s.key == UNDEF64) break;
         if (s.key == canon) { sd.start = s.start; sd.count = s.count > V.max_occ ? 0u : min(s.count, per_seed); break; }      // a repetitive k-mer says nothing about the place
     }
     return sd;

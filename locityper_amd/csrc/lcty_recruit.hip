@@ -3,7 +3,7 @@
 //   src/math/frac.rs:50-93; the hash and the canonical minimizers of src/seq/kmers.rs are in lcty_seq.hpp.
 //
 // Targets are built on the host once (minimizers of the alleles, one entry per (minimizer, locus): direction bits, "rare");
-// the device holds an open-addressing table minimizer -> run of entries. recruit_kernel: one lane per read pair. A lane walks
+// the device holds a key table (lcty_table.hpp) minimizer -> run of entries. recruit_kernel: one lane per read pair. A lane walks
 // a mate base by base (rolling forward / reverse k-mer, hash, ring of the last w hashes in LDS, window minimum with the rescan
 // rule of the reference) and only WRITES its minimizers down (wavefront scratch, interleaved across the lanes); then all lanes
 // probe the table with their j-th minimizer together — the lanes find their minimizers at different bases, and a probe inside
@@ -16,17 +16,18 @@
 #include <unordered_map>
 
 #include "lcty_objects.hpp"
+#include "lcty_table.hpp"
 
 namespace lcty {
 
 constexpr uint32_t MAX_LOCI_PER_READ = 8;
 constexpr uint32_t READ_LENGTH_THRESH = 500;       // recruit.rs:35
 
-struct TableSlot { uint64_t key; uint32_t start, count; };      // key UNDEF64 = free (UNDEF is never a minimizer, kmers.rs:27-30)
+// the table: keytable::Slot, minimizer -> its run of `entries`; MixHash, free = UNDEF64 (UNDEF is never a minimizer, kmers.rs:27-30)
 // entry: locus | direction << 24 (bit 0 backward, bit 1 forward) | rare << 26
 
 struct RecruitView {
-    const TableSlot* table; uint64_t table_mask;
+    const keytable::Slot* table; uint64_t table_mask;
     const uint32_t* entries;
     uint32_t k, w, ring;                 // ring: power of two >= w
     uint32_t mf_num, mf_den;             // match_frac_short
@@ -99,11 +100,10 @@ __device__ inline uint32_t walk_minimizers(const RecruitView& V, const uint64_t*
 }
 
 // the run of entries of a minimizer: its slot of the table, or none (count 0)
-__device__ __forceinline__ TableSlot find_minimizer(const RecruitView& V, uint64_t minim) {
-    uint64_t slot = mix64(minim) & V.table_mask;
-    TableSlot ts = V.table[slot];
-    while (ts.key != UNDEF64 && ts.key != minim) { slot = (slot + 1) & V.table_mask; ts = V.table[slot]; }
-    if (ts.key != minim) ts.count = 0;
+__device__ __forceinline__ keytable::Slot find_minimizer(const RecruitView& V, uint64_t minim) {
+    const keytable::Probe at = keytable::find<keytable::MixHash, UNDEF64>(V.table, V.table_mask, minim);
+    keytable::Slot ts = V.table[at.slot];
+    if (!at.found) ts.count = 0;
     return ts;
 }
 
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64) void recruit_kernel(const RecruitView V) {
         for (uint32_t j = 0; j < MAX_LOCI_PER_READ; j++) { M.locus[j] = 0xFFFFFFFFu; M.first[j] = 0; M.second[j] = 0; }
         bool overflow = false;
         auto probe = [&](uint64_t minim, bool forward, bool second) {
-            const TableSlot ts = find_minimizer(V, minim);
+            const keytable::Slot ts = find_minimizer(V, minim);
             for (uint32_t q = 0; q < ts.count; q++) {
                 const uint32_t e = V.entries[ts.start + q];
                 const uint32_t locus = e & 0xFFFFFFu, direction = (e >> 24) & 3u, rare = (e >> 26) & 1u;
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(64) void recruit_single_kernel(const RecruitView V)
         for (uint32_t j = lane; j < total; j += 64) {
             const uint64_t minim = list_h[j];
             const bool forward = list_f[j] != 0;
-            const TableSlot ts = find_minimizer(V, minim);
+            const keytable::Slot ts = find_minimizer(V, minim);
             for (uint32_t q = 0; q < ts.count; q++) {
                 const uint32_t e = V.entries[ts.start + q];
                 const uint32_t locus = e & 0xFFFFFFu, direction = (e >> 24) & 3u, rare = (e >> 26) & 1u;
@@ -448,7 +448,7 @@ __global__ __launch_bounds__(64) void recruit_single_kernel(const RecruitView V)
                         const uint64_t minim = list_h[j];
                         const bool forward = list_f[j] != 0;
                         int64_t add[2] = {0, 0};
-                        const TableSlot ts = find_minimizer(V, minim);
+                        const keytable::Slot ts = find_minimizer(V, minim);
                         for (uint32_t q = 0; q < ts.count; q++) {
                                 const uint32_t e = V.entries[ts.start + q];
                                 if ((e & 0xFFFFFFu) != locus) continue;
@@ -496,7 +496,7 @@ struct lcty_targets {
     bool finalized = false;
     struct Entry { uint32_t locus; uint8_t direction, rare; };
     std::unordered_map<uint64_t, std::vector<Entry>> minim_to_loci;
-    DevBuf<TableSlot> d_table; DevBuf<uint32_t> d_entries, d_err;
+    DevBuf<keytable::Slot> d_table; DevBuf<uint32_t> d_entries, d_err;
     uint64_t table_mask = 0;
 };
 
@@ -600,14 +600,12 @@ int32_t lcty_targets_finalize(lcty_targets* t, uint64_t* n_minimizers) {
     return guarded([&] {
         if (!t) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         if (t->minim_to_loci.empty()) fail(LCTY_ERR_RUNTIME, "No minimizers for recruitment");       // recruit.rs:748
-        uint64_t cap = 64;
-        while (cap < 2 * t->minim_to_loci.size() + 2) cap <<= 1;
-        std::vector<TableSlot> table(cap, TableSlot{UNDEF64, 0, 0});
+        const uint64_t cap = keytable::table_slots(t->minim_to_loci.size() + 1, 1, 64);
+        std::vector<keytable::Slot> table(cap, keytable::Slot{UNDEF64, 0, 0});
         std::vector<uint32_t> entries;
         for (const auto& kv : t->minim_to_loci) {
-            uint64_t slot = mix64(kv.first) & (cap - 1);
-            while (table[slot].key != UNDEF64) slot = (slot + 1) & (cap - 1);
-            table[slot] = TableSlot{kv.first, static_cast<uint32_t>(entries.size()), static_cast<uint32_t>(kv.second.size())};
+            const uint64_t slot = keytable::claim<keytable::MixHash, UNDEF64>(table.data(), cap - 1, kv.first).slot;
+            table[slot] = keytable::Slot{kv.first, static_cast<uint32_t>(entries.size()), static_cast<uint32_t>(kv.second.size())};
             for (const auto& e : kv.second) entries.push_back(e.locus | (static_cast<uint32_t>(e.direction) << 24) | (static_cast<uint32_t>(e.rare) << 26));
         }
         lcty_ctx* ctx = t->ctx;

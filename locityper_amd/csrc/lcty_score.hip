@@ -27,6 +27,7 @@
 //  pass 1 is instruction-issue bound, not latency bound, once the loads are grouped.)
 #include "lcty_objects.hpp"
 #include "lcty_scan.hpp"
+#include "lcty_table.hpp"
 
 namespace lcty {
 
@@ -196,7 +197,7 @@ __device__ __noinline__ uint32_t mate_unique_kmers_global(const uint64_t* kset, 
                 if (window_has_n_wide(nm, q, k)) hit = undef_in_set != 0;
                 else hit = kset128_contains(kset, kset_mask, canonical_kmer_2bit128(w64, q, k));
             } else if (window_has_n(nm, q, k)) hit = undef_in_set != 0;  // UNDEF k-mer (kmers.rs:184-190)
-            else hit = kset_contains(kset, kset_mask, canonical_kmer_2bit(w64, q, k));
+            else hit = keytable::find<keytable::MixHash, UNDEF64>(kset, kset_mask, canonical_kmer_2bit(w64, q, k)).found;
         }
         walk.feed(__ballot(hit), base, k);
     }
@@ -254,8 +255,9 @@ __device__ __forceinline__ void pair_unique_kmers_regs(const uint64_t* kset, uin
             uint32_t nbits = (half ? nB : nA) >> sh1;
             if (sh1 + k > 32u) nbits |= (half ? nC : nB) << (32u - sh1);
             undef[j] = (nbits & ((1u << k) - 1u)) != 0u;  // window contains a non-ACGT base -> UNDEF (kmers.rs:184-190)
-            slot[j] = mix64(key[j]) & kset_mask;
+            slot[j] = keytable::home<keytable::MixHash>(key[j], kset_mask);
         }
+        // keytable::find (lcty_table.hpp) in a batched form, which stays written out.
         // The probes of all four items advance together, two slots of the table per step: a step costs one trip to the L2 whatever
         // the number of lanes and items still searching (one item after the other, one slot at a time, the four chains add up:
         // at a load of 1/4 the longest chain of 64 lanes is 4 or 5 slots).
@@ -270,14 +272,14 @@ __device__ __forceinline__ void pair_unique_kmers_regs(const uint64_t* kset, uin
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const bool go = (pend >> j) & 1u;
-                v0[j] = go ? kset[slot[j]] : KSET_EMPTY;
-                v1[j] = go ? kset[(slot[j] + 1) & kset_mask] : KSET_EMPTY;
+                v0[j] = go ? kset[slot[j]] : UNDEF64;
+                v1[j] = go ? kset[keytable::step(slot[j], kset_mask)] : UNDEF64;
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 if (!((pend >> j) & 1u)) continue;
-                const bool found = v0[j] == key[j] || (v0[j] != KSET_EMPTY && v1[j] == key[j]);
-                const bool ended = v0[j] == KSET_EMPTY || v1[j] == KSET_EMPTY;
+                const bool found = v0[j] == key[j] || (v0[j] != UNDEF64 && v1[j] == key[j]);
+                const bool ended = v0[j] == UNDEF64 || v1[j] == UNDEF64;
                 if (found) hits |= 1u << j;
                 if (found || ended) pend &= ~(1u << j);
                 else slot[j] = (slot[j] + 2) & kset_mask;

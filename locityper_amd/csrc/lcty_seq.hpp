@@ -10,9 +10,7 @@
 namespace lcty {
 
 constexpr uint64_t UNDEF64 = ~0ull;            // Kmer::UNDEF for u64 (src/seq/kmers.rs:45): the hash of a k-mer over a base that is not ACGT
-// never a valid canonical k-mer for k <= 31 and never a minimizer (kmers.rs:27-30), hence the free marker of the open-addressing tables
-constexpr uint64_t KSET_EMPTY = UNDEF64;       // UniqueKmers set (lcty_locus.hip)
-constexpr uint64_t MAP_FREE = UNDEF64;         // k-mer index of the basis alleles (lcty_map_index.hip)
+// never a valid canonical k-mer for k <= 31 and never a minimizer (kmers.rs:27-30), hence the free marker of the key tables (lcty_table.hpp)
 
 // A 0, C 1, G 2, T 3; anything else (N, IUPAC codes, lower case: the reference matches the four capitals only) is 4
 __host__ __device__ inline uint32_t base_enc(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
@@ -28,7 +26,7 @@ __host__ __device__ inline uint64_t fast_hash64(uint64_t x) {
     return x;
 }
 
-// the slot hash of the project's own open-addressing tables (not the reference's)
+// the slot hash of most of the project's own key tables (lcty_table.hpp: MixHash; not the reference's)
 __host__ __device__ inline uint64_t mix64(uint64_t x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
     x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;

@@ -17,6 +17,7 @@
 #include <thread>
 
 #include "lcty_objects.hpp"
+#include "lcty_table.hpp"
 #include "lcty_transfer_device.hpp"
 
 namespace lcty {
@@ -152,13 +153,9 @@ __device__ __forceinline__ uint64_t pos_key(uint32_t read_end, uint32_t contig, 
     return (static_cast<uint64_t>(read_end + 1) << 48) | (static_cast<uint64_t>(contig) << 32) | static_cast<uint64_t>(pos >> 7);
 }
 __device__ inline uint32_t hfind(const PairScratch& P, uint64_t key, bool* found) {
-    uint32_t h = static_cast<uint32_t>(mix64(key)) & (P.hcap - 1);
-    while (P.hkey[h] != 0) {
-        if (P.hkey[h] == key) { *found = true; return h; }
-        h = (h + 1) & (P.hcap - 1);
-    }
-    *found = false;
-    return h;
+    const keytable::Probe at = keytable::find<keytable::MixHash, 0ull>(P.hkey, P.hcap - 1, key);
+    *found = at.found;
+    return static_cast<uint32_t>(at.slot);
 }
 
 // PrelimAlignments state of the pair (single lane)
@@ -563,13 +560,9 @@ __global__ __launch_bounds__(64, WPS) void transfer_kernel(const LocusView L, co
                     bool found = false;
                     const uint64_t key = pos_key(e, target, na.start);
                     if (fresh) {
-                        h = static_cast<uint32_t>(mix64(key)) & (P.hcap - 1);
-                        for (;;) {
-                            const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&P.hkey[h]), 0ull, static_cast<unsigned long long>(key));
-                            if (old == 0ull) break;
-                            if (old == key) { found = true; existing = P.hval[h].x; break; }
-                            h = (h + 1) & (P.hcap - 1);
-                        }
+                        const keytable::Probe at = keytable::claim<keytable::MixHash, 0ull>(P.hkey, P.hcap - 1, key);
+                        h = static_cast<uint32_t>(at.slot); found = at.found;
+                        if (found) existing = P.hval[h].x;
                     }
                     const bool appends = save && (!found || existing == NOT_SAVED);
                     const unsigned long long app_mask = __ballot(appends);
@@ -907,8 +900,7 @@ int32_t lcty_recover_alignments(lcty_reads* reads, uint64_t* n_recovered) {
         uint64_t n_first = 0, would = 0;
         {
             const uint32_t cap_alns = reads->max_recs_per_pair + 1;
-            uint32_t hcap = 64;
-            while (hcap < 2 * cap_alns + 2) hcap <<= 1;
+            const uint32_t hcap = static_cast<uint32_t>(keytable::table_slots(uint64_t(cap_alns) + 1, 1, 64));
             Limits none; none.cigar_cap = 1; none.dp_dim = 0; none.dp_cells = 0;
             const size_t stride = pair_scratch_bytes(cap_alns, hcap, 1, 1, none);
             const uint32_t blocks = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>({R, max_blocks, scratch_budget / stride})));
@@ -961,8 +953,7 @@ int32_t lcty_recover_alignments(lcty_reads* reads, uint64_t* n_recovered) {
         for (int attempt = 0;; attempt++) {
             if (attempt > 12) fail(LCTY_ERR_RUNTIME, "alignment recovery: arenas keep overflowing");
             const uint32_t cap_alns = reads->max_recs_per_pair + cap_new;
-            uint32_t hcap = 64;
-            while (hcap < 2 * cap_alns + 2) hcap <<= 1;
+            const uint32_t hcap = static_cast<uint32_t>(keytable::table_slots(uint64_t(cap_alns) + 1, 1, 64));
             const uint64_t cap_words64 = static_cast<uint64_t>(cap_new) * words_per_new;
             const uint32_t cap_words = static_cast<uint32_t>(std::min<uint64_t>(cap_words64, 1u << 30));
             d_xrecs_bytes.ensure(arena_recs * sizeof(lcty_aln_rec)); d_xwords.ensure(arena_words);

@@ -95,6 +95,58 @@ def test_every_k_on_five_contigs(gpu_ctx, k):
     assert st["table_slots"] >= 2 * st["n_distinct"] and st["n_distinct"] <= st["n_query_kmers"]
 
 
+M64 = (1 << 64) - 1
+
+
+def _mix64(x):
+    """mix64 of lcty_seq.hpp: the slot hash of the query table"""
+    x ^= x >> 33; x = x * 0xff51afd7ed558ccd & M64
+    x ^= x >> 33; x = x * 0xc4ceb9fe1a85ec53 & M64
+    return x ^ x >> 33
+
+
+def _revcomp(s):
+    return s.translate(bytes.maketrans(b"ACGT", b"TGCA"))[::-1]
+
+
+def _canonical(s):
+    """the smaller of the k-mer and its reverse complement as 2-bit numbers, first base in the highest bits"""
+    value = lambda t: int("".join(str(b"ACGT".index(c)) for c in t), 4)
+    return min(value(s), value(_revcomp(s)))
+
+
+def test_claim_compact_and_find_where_a_chain_wraps(gpu_ctx):
+    """The key table of a call at its smallest (lcty_table.hpp): 18 distinct 15-mers, asked for 40 times each. The first table has
+    2 048 slots and hundreds of threads claim equal keys at once; the compacted one has 64, four keys whose home is its last slot (their
+    chain wraps to slot 0 and beyond) and two whose home is slot 0 (which the wrapped chain pushes on)."""
+    rng = np.random.default_rng(41)
+    k, last, first, others = 15, [], [], []
+    seen = set()
+    for _ in range(5_000):
+        s = _rand(rng, k)
+        c = _canonical(s)
+        if c in seen:
+            continue
+        home = _mix64(c) & 63
+        group = last if home == 63 and len(last) < 4 else first if home == 0 and len(first) < 2 else others if len(others) < 12 else None
+        if group is not None:
+            group.append(s); seen.add(c)
+        if (len(last), len(first), len(others)) == (4, 2, 12):
+            break
+    chosen = last + first + others
+    assert [_mix64(_canonical(s)) & 63 for s in chosen[:6]] == [63] * 4 + [0] * 2 and len(chosen) == len(seen) == 18
+    # occurrence j of k-mer i is its reverse complement when j is odd; an N between any two
+    times = [1 + i % 4 for i in range(len(chosen))]
+    contigs = [("c", b"N".join(s if j % 2 == 0 else _revcomp(s) for i, s in enumerate(chosen) for j in range(times[i])))]
+    seqs = chosen * 40
+    g = _genome(gpu_ctx, contigs)
+    got, st = _counts(g, seqs, k)
+    assert st["n_query_kmers"] == 720 and st["n_distinct"] == 18 and st["table_slots"] == 64
+    assert [int(x[0]) for x in got[:18]] == times
+    _same(got, R.kmer_counts(contigs, seqs, k))
+    g.close()
+
+
 def test_non_bases_split_and_lower_case_counts(gpu_ctx):
     rng = np.random.default_rng(11)
     k = 9
