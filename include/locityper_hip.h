@@ -259,7 +259,10 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       "pafvcf_table_mb"   megabytes the resident allele table (n_ranges x n_seqs x 4 bytes) of lcty_pafvcf_table / lcty_paf_to_vcf may
  *       take (default: a quarter of the free device memory; a larger table is LCTY_ERR_UNSUPPORTED naming this knob);
  *       "genome_max_bases"   positions (bases + one separator per contig) a resident genome may reach (default 2^32; lcty_genome_append
- *       refuses a piece that reaches it with LCTY_ERR_UNSUPPORTED before it uploads anything).
+ *       refuses a piece that reaches it with LCTY_ERR_UNSUPPORTED before it uploads anything);
+ *       "sample_bam_hash_bits"   bits kept of the hash of a read name in lcty_sample_bam_fetch (default 64; fewer: collisions, which the
+ *       comparison of the names must resolve);   "sample_bam_max_slice_bytes"   inflated bytes one lcty_sample_bam_fetch may take
+ *       (default 2^33; a larger slice is LCTY_ERR_UNSUPPORTED naming this knob, before anything is uploaded).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -557,6 +560,84 @@ int32_t lcty_fastx_writers_open(const char* const* paths, uint32_t n, lcty_fastx
 int32_t lcty_fastx_write_recruited(lcty_fastx* f, lcty_fastx_writers* writers, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci,
                                    uint64_t* n_written);
 int32_t lcty_fastx_writers_close(lcty_fastx_writers* writers);
+
+/* ---- a sample's reads from a coordinate-sorted, indexed BAM file: `locityper genotype -a sample.bam` ---------------
+ * recruit_to_targets (command/genotype.rs:872-907) -> create_fetch_targets / postprocess_targets (776-854) -> IndexedBamReader +
+ * PairedBamReader (seq/fastx.rs:577-874) -> Targets::recruit. The index, the file access and the inflation of the selected BGZF
+ * blocks are host code; the fetched slice becomes recruitable read pairs on the device (record filter, name pairing, unpacking
+ * with strand restore) and is recruited from there. The rules are restated index-free in tests/pyref_sample_bam.py.
+ * lcty_sample_bam_open: bam::IndexedReader::from_path / from_path_and_index (genotype.rs:886-890): the header, and the BAI index
+ *   at index_path, or else at path + ".bai", or else at path with ".bam" replaced by ".bai". A CSI index or a CRAM file is
+ *   LCTY_ERR_UNSUPPORTED, no index LCTY_ERR_INVALID_INPUT. Host code. lcty_sample_bam_contigs: ContigNames::from_bam_header (892):
+ *   name i = names + name_off[i], 0-terminated; the arrays belong to the handle.
+ * lcty_sample_bam_is_paired: identify_pairedness (857-867): flag 0x1 of the first record; a file without records is
+ *   LCTY_ERR_INVALID_DATA "Input BAM/CRAM file is empty".
+ * lcty_recruit_fetch_regions: postprocess_targets (776-797), host code: every interval padded (Interval::add_padding,
+ *   seq/interv.rs:74-77: start - padding saturating at 0, end + padding at most the contig's length), every contig SHORTER than
+ *   alt_contig_len appended whole, sorted by (tid, start, end), merged (Interval::merge, 232-247: the next interval joins the last
+ *   when last.end + merge_distance >= next.start). The reference uses merge_distance 1000, alt_contig_len 10 000 000 and padding =
+ *   min(ceil(quantile 0.999 of the insert size distribution), 10 000) + 100, or 1000 without one (genotype.rs:848-852); the padding
+ *   is the caller's. The out arrays hold n_in + n_contigs entries. tid >= n_contigs, start >= end: LCTY_ERR_INVALID_INPUT.
+ * lcty_sample_bam_plan: the chunks of virtual offsets a fetch of these regions reads, host code: reg2bins, chunks that end at or
+ *   before the linear index's offset of the region's first 16 kb window dropped, sorted, and chunks that touch, overlap or meet
+ *   in one BGZF block merged over all regions of the call; with_unmapped adds [largest chunk end of the index, end of file).
+ *   Up to chunk_cap chunks are written, *n_chunks is their number; *blocks_total (may be NULL) the BGZF blocks they span, read
+ *   from the file. Regions are (tid, start, end), sorted, strictly increasing and disjoint as postprocess_targets leaves them:
+ *   anything else is LCTY_ERR_INVALID_INPUT (the reference asserts, fastx.rs:770).
+ * lcty_sample_bam_fetch: IndexedBamReader (732-803) [+ PairedBamReader (805-874) with paired = 1; paired = -1 asks the file],
+ *   one call per sample. Region i gives the records with tid == tid_i, pos < end_i, endpos > start_i (endpos = pos + reference
+ *   length of the CIGAR, 0 for a record with flag 0x4, 0 counting as 1) in file order; one is kept iff (flag & 0x900) == 0 and
+ *   pos >= end_(i-1) when region i - 1 is on the same contig (587-611, 762-783). with_unmapped: then the primaries without
+ *   coordinate (tid < 0). whole_file != 0 (n_regions == 0, with_unmapped == 0): DirectBamReader (692-729), every primary of the
+ *   file, single-end only (paired: LCTY_ERR_UNSUPPORTED). A record's sequence is reversed and complemented when flag 0x10 is set;
+ *   every BAM code but A, C, G, T is "not ACGT". Pairs: per record of that stream as read_next (829-869) — a record without
+ *   0x40 / 0x80 is LCTY_ERR_INVALID_DATA "Expected paired-end reads, but read .. is unpaired"; a waiting record of the same name
+ *   with the same first-in-template flag is LCTY_ERR_INVALID_DATA "Found two primary alignments for .. for the same read end",
+ *   otherwise the two are a pair (mate 1 the one with 0x40), in the order of the records that complete them; a record nobody waits
+ *   for waits iff (tid as u32, pos as u64) <= (mtid as u32, mpos as u64), else it is discarded, as is whatever waits at the end.
+ *   A kept record without sequence: LCTY_ERR_INVALID_DATA "Primary alignment for read .. has no sequence". The first offending
+ *   record in file order decides. Beyond the reference: a record that leaves the fetched slice or is shorter than its fields, and
+ *   (tid, pos) running backwards inside the slice: LCTY_ERR_INVALID_DATA; a primary mapped record whose CIGAR is the `kSmN`
+ *   placeholder of a CG tag: LCTY_ERR_UNSUPPORTED with the read's name; an inflated slice above lcty_ctx_set_knob
+ *   "sample_bam_max_slice_bytes" (default 2^33): LCTY_ERR_UNSUPPORTED before anything is uploaded; 2^31 records or more:
+ *   LCTY_ERR_UNSUPPORTED. "sample_bam_hash_bits" (default 64) keeps that many bits of the hash of a read name: names are always
+ *   compared in full, the hash only brings candidates together. stats may be NULL.
+ * lcty_sample_reads_view: the reads as the sequence fields of a chunk, what lcty_fastx_next gives (single-end: every odd mate
+ *   absent), and per mate the ordinal of its record in the fetched stream (0xFFFFFFFF: absent); downloaded on first use, the
+ *   arrays belong to the handle. lcty_sample_reads_recruit: lcty_recruit on that view, from the device-resident arrays (paired as
+ *   fetched). lcty_sample_reads_write_recruited: BamRecord::write_to (633-668) to the writers of exactly the loci of the answer, both
+ *   mates one after the other: FASTA when the qualities are absent or start with 255, else FASTQ with q + 33, reversed for reverse
+ *   records. Not built: CRAM, CSI, several files, subsampling. */
+typedef struct lcty_sample_bam lcty_sample_bam;
+typedef struct lcty_sample_reads lcty_sample_reads;
+typedef struct lcty_sample_bam_stats {
+    uint64_t n_regions, n_chunks;                 /* as given; after merging */
+    uint64_t file_bytes, bytes_read;              /* size of the BAM file; compressed bytes read from it */
+    uint64_t blocks_inflated, bytes_inflated;     /* BGZF blocks of the chunks; their inflated size */
+    uint64_t records_walked, records_primary, records_kept;
+    uint64_t n_pairs, n_discarded;                /* paired: pairs made, kept records without a pair; single-end: reads, 0 */
+    double   ms_read, ms_inflate, ms_walk;        /* host: pread, inflate (at most 16 threads), the chain of record lengths */
+    double   ms_upload, ms_record, ms_pair, ms_unpack;   /* device, wall clock around each stage with its synchronisation */
+    double   ms_total;
+} lcty_sample_bam_stats;
+int32_t lcty_sample_bam_open(const char* path, const char* index_path, lcty_sample_bam** out);
+void    lcty_sample_bam_close(lcty_sample_bam* bam);
+int32_t lcty_sample_bam_contigs(const lcty_sample_bam* bam, uint32_t* n, const char** names, const uint64_t** name_off, const uint32_t** lengths);
+int32_t lcty_sample_bam_is_paired(lcty_sample_bam* bam, int32_t* paired);
+int32_t lcty_recruit_fetch_regions(uint32_t n_in, const uint32_t* tid, const uint32_t* start, const uint32_t* end, uint32_t n_contigs,
+                                   const uint32_t* contig_len, uint32_t padding, uint32_t alt_contig_len, uint32_t merge_distance,
+                                   uint32_t* out_tid, uint32_t* out_start, uint32_t* out_end, uint32_t* n_out);
+int32_t lcty_sample_bam_plan(lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
+                             int32_t with_unmapped, uint64_t chunk_cap, uint64_t* n_chunks, uint64_t* chunk_beg, uint64_t* chunk_end,
+                             uint64_t* blocks_total);
+int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start,
+                              const uint32_t* end, int32_t with_unmapped, int32_t whole_file, int32_t paired, lcty_sample_reads** reads,
+                              lcty_sample_bam_stats* stats);
+int32_t lcty_sample_reads_view(lcty_sample_reads* reads, lcty_reads_host* view, const uint32_t** src_record, int32_t* paired);
+int32_t lcty_sample_reads_recruit(lcty_targets* targets, lcty_sample_reads* reads, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci);
+int32_t lcty_sample_reads_write_recruited(lcty_sample_reads* reads, lcty_fastx_writers* writers, uint32_t max_out, const uint32_t* out_cnt,
+                                          const uint32_t* out_loci, uint64_t* n_written);
+void    lcty_sample_reads_free(lcty_sample_reads* reads);
 
 /* ---- candidate generation inside a locus (first slice) ----------------------------------------------------
  * The reference runs an external mapper per locus — strobealign -k 15 -N/-M min(25000, 4 x alleles) -S 0.5 --eqx for short

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -157,6 +157,17 @@ SIGNATURES = {
     "lcty_fastx_writers_open": (I32, [P(C.c_char_p), U32, P(VP)]),
     "lcty_fastx_write_recruited": (I32, [VP, VP, U32, VP, VP, P(U64)]),
     "lcty_fastx_writers_close": (I32, [VP]),
+    "lcty_sample_bam_open": (I32, [C.c_char_p, C.c_char_p, P(VP)]),
+    "lcty_sample_bam_close": (None, [VP]),
+    "lcty_sample_bam_contigs": (I32, [VP, P(U32), P(VP), P(VP), P(VP)]),
+    "lcty_sample_bam_is_paired": (I32, [VP, P(I32)]),
+    "lcty_recruit_fetch_regions": (I32, [U32, VP, VP, VP, U32, VP, U32, U32, U32, VP, VP, VP, P(U32)]),
+    "lcty_sample_bam_plan": (I32, [VP, U32, VP, VP, VP, I32, U64, P(U64), VP, VP, P(U64)]),
+    "lcty_sample_bam_fetch": (I32, [VP, VP, U32, VP, VP, VP, I32, I32, I32, P(VP), P(SampleBamStats)]),
+    "lcty_sample_reads_view": (I32, [VP, P(ReadsHost), P(VP), P(I32)]),
+    "lcty_sample_reads_recruit": (I32, [VP, VP, U32, VP, VP]),
+    "lcty_sample_reads_write_recruited": (I32, [VP, VP, U32, VP, VP, P(U64)]),
+    "lcty_sample_reads_free": (None, [VP]),
     "lcty_locus_depth_table": (I32, [VP, P(U32), VP]),
     "lcty_solver_default": (I32, [P(Solver), I32]),
     "lcty_chain_seeds": (I32, [U64, U64, VP]),

@@ -662,3 +662,12 @@ class GenomeCountStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
+
+
+class SampleBamStats(C.Structure):     # lcty_sample_bam_stats
+    _fields_ = [(n, C.c_uint64) for n in ("n_regions", "n_chunks", "file_bytes", "bytes_read", "blocks_inflated", "bytes_inflated", "records_walked",
+                                          "records_primary", "records_kept", "n_pairs", "n_discarded")] + \
+               [(n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_walk", "ms_upload", "ms_record", "ms_pair", "ms_unpack", "ms_total")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}

@@ -17,6 +17,7 @@
 #include "lcty_common.hpp"
 #include "lcty_lines.hpp"
 #include "lcty_seq.hpp"
+#include "lcty_writers.hpp"
 
 using namespace lcty;
 
@@ -73,18 +74,6 @@ struct lcty_fastx {
     std::vector<uint32_t> mate_len; std::vector<uint64_t> mate_off, zero_off;
     std::vector<uint32_t> bases2, nmask;
     uint64_t n = 0;
-};
-
-struct lcty_fastx_writers {
-    std::vector<gzFile> gz; std::vector<FILE*> plain; std::vector<std::string> paths;
-    ~lcty_fastx_writers() {
-        for (gzFile g : gz) if (g) gzclose(g);
-        for (FILE* f : plain) if (f) fclose(f);
-    }
-    void put(uint32_t i, const std::string& s) {
-        if (gz[i]) { if (gzwrite(gz[i], s.data(), static_cast<unsigned>(s.size())) != static_cast<int>(s.size())) fail(LCTY_ERR_RUNTIME, "write error on %s", paths[i].c_str()); }
-        else if (fwrite(s.data(), 1, s.size(), plain[i]) != s.size()) fail(LCTY_ERR_RUNTIME, "write error on %s", paths[i].c_str());
-    }
 };
 
 namespace {

@@ -187,6 +187,10 @@ struct DeviceRecords {
     uint32_t max_rec_cigar;
 };
 int32_t reads_append_device(lcty_reads* R, const lcty_reads_host* h, const DeviceRecords* dev);
+// lcty_recruit behind its upload (lcty_recruit.hip): the sequence fields of n pairs as device arrays + the host's copy of mate_len
+void recruit_device_view(lcty_targets* t, uint64_t n, const uint32_t* h_mate_len, const uint32_t* d_len, const uint64_t* d_off, const uint32_t* d_bases,
+                         const uint32_t* d_nm, int32_t paired, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci);
+lcty_ctx* targets_ctx(lcty_targets* t);
 
 // The rows of a stage's alleles of the location tables of several batches (shards of one locus' reads, in read order), laid
 // side by side into one table the solver kernels run on (lcty_solve_kernels.hip). The caller moves the packed rows between devices

@@ -534,6 +534,77 @@ void approximate_u16(double x, uint16_t* num, uint16_t* den) {
 
 }  // namespace
 
+namespace lcty {
+
+// lcty_recruit on reads that are on the device already (lcty_objects.hpp): the sequence fields of a chunk of n pairs as device
+// arrays, and the host's copy of mate_len, which sorts the reads between the two kernels. Work is issued on the context's stream
+// behind whatever filled the arrays; returns with out_cnt / out_loci on the host.
+void recruit_device_view(lcty_targets* t, uint64_t n, const uint32_t* h_mate_len, const uint32_t* d_len, const uint64_t* d_off, const uint32_t* d_bases,
+                         const uint32_t* d_nm, int32_t paired, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci) {
+    lcty_ctx* ctx = t->ctx;
+    hipStream_t s = ctx->stream;
+    DevBuf<uint32_t> d_cnt, d_loci;
+    d_cnt.alloc(n); d_loci.alloc(n * max_out);
+    t->d_err.zero(s);
+    RecruitView V{};
+    V.table = t->d_table.p; V.table_mask = t->table_mask; V.entries = t->d_entries.p;
+    V.k = t->prm.minimizer_k; V.w = t->prm.minimizer_w;
+    V.ring = 2; while (V.ring < V.w) V.ring <<= 1;
+    V.mf_num = t->mf_num; V.mf_den = t->mf_den;
+    V.n_pairs = n; V.mate_len = d_len; V.mate_off = d_off; V.bases2 = d_bases; V.nmask = d_nm;
+    V.paired = paired != 0; V.max_out = max_out; V.out_cnt = d_cnt.p; V.out_loci = d_loci.p; V.err = t->d_err.p;
+    const size_t lds_single = static_cast<size_t>(V.ring) * 64 * (8 + 8 + 4);
+    const size_t lds = std::max<size_t>(static_cast<size_t>(V.ring) * 8, static_cast<size_t>(V.w) * (8 + 8 + 4)) * 64;   // pair kernel: w slots per array
+    // single reads of more than 256 bases go to the wavefront-per-read kernel (short-read rule up to 500 bases, long-read rule beyond)
+    uint32_t max_len = 1, max_long = 0;
+    std::vector<uint32_t> long_list;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t l1 = h_mate_len[2 * i], l2 = paired ? h_mate_len[2 * i + 1] : 0u;
+        if (!paired && l1 > 256) { long_list.push_back(static_cast<uint32_t>(i)); max_long = std::max(max_long, l1); }
+        else max_len = std::max(max_len, std::max(l1, l2));
+    }
+    if (max_len > 256) fail(LCTY_ERR_UNSUPPORTED, "recruitment: a mate of %u bases in a read pair (the device kernel takes mates of up to 256 bases)", max_len);
+    if (n > 0xFFFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "recruitment: more than 2^32 reads in one call");
+    V.scratch_cap = max_len;                                                 // a mate has fewer minimizers than bases
+    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((n + 63) / 64, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16));
+    DevBuf<uint64_t> d_scratch, d_long_h; DevBuf<uint8_t> d_long_f, d_scratch_f; DevBuf<uint32_t> d_long_list;
+    d_scratch.alloc(static_cast<size_t>(blocks) * V.scratch_cap * 64); d_scratch_f.alloc(static_cast<size_t>(blocks) * V.scratch_cap * 64);
+    V.scratch = d_scratch.p; V.scratch_f = d_scratch_f.p;
+    V.match_frac = t->prm.match_frac;
+    // Params::new (recruit.rs:92-98)
+    V.stretch_minims = (2 * t->prm.match_length + (static_cast<uint32_t>(t->prm.minimizer_w) + 1) - 1) / (static_cast<uint32_t>(t->prm.minimizer_w) + 1);
+    V.stretch_score = static_cast<uint32_t>(std::ceil(std::max(static_cast<double>(V.stretch_minims) * (4.0 * t->prm.match_frac - 1.0), 3.0)));
+    ctx->timed(LCTY_K_RECRUIT, [&] {
+        hipLaunchKernelGGL(recruit_kernel, dim3(blocks), dim3(64), lds, s, V);
+    });
+    if (!long_list.empty()) {
+        V.n_long = static_cast<uint32_t>(long_list.size()); V.long_cap = max_long + 64;
+        const uint32_t lblocks = static_cast<uint32_t>(std::min<uint64_t>(long_list.size(), static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8));
+        d_long_list.alloc(long_list.size()); d_long_list.upload(long_list.data(), long_list.size(), s);
+        d_long_h.alloc(static_cast<size_t>(lblocks) * 2 * V.long_cap); d_long_f.alloc(static_cast<size_t>(lblocks) * 2 * V.long_cap);
+        V.long_list = d_long_list.p; V.long_h = d_long_h.p; V.long_f = d_long_f.p;
+        ctx->timed(LCTY_K_RECRUIT, [&] {
+            hipLaunchKernelGGL(recruit_single_kernel, dim3(lblocks), dim3(64), lds_single, s, V);
+        });
+    }
+    LCTY_HIP(hipGetLastError());
+    uint32_t err = 0;
+    t->d_err.download(&err, 1, s);
+    d_cnt.download(out_cnt, n, s); d_loci.download(out_loci, n * max_out, s);
+    LCTY_HIP(hipStreamSynchronize(s));
+    if (err == LCTY_ERR_UNSUPPORTED) fail(LCTY_ERR_UNSUPPORTED, "recruitment: a read matching minimizers of more than %u loci (%u for single reads beyond 256 bases)", MAX_LOCI_PER_READ, LONG_LOCI);
+    if (err == LCTY_ERR_INVALID_INPUT) fail(LCTY_ERR_INVALID_INPUT, "recruitment: max_out is smaller than the number of loci of a read");
+    if (err) fail(static_cast<int32_t>(err), "recruitment failed on the device");
+    for (uint64_t i = 0; i < n; i++) std::sort(out_loci + i * max_out, out_loci + i * max_out + out_cnt[i]);
+}
+
+lcty_ctx* targets_ctx(lcty_targets* t) {
+    if (!t->finalized) fail(LCTY_ERR_INVALID_INPUT, "lcty_targets_finalize has not been called");
+    return t->ctx;
+}
+
+}  // namespace lcty
+
 extern "C" {
 
 int32_t lcty_recruit_params_default(lcty_recruit_params* p, int32_t technology, int32_t is_paired) {
@@ -636,62 +707,13 @@ int32_t lcty_recruit(lcty_targets* t, const lcty_reads_host* h, int32_t paired, 
             if (h->mate_off[m] % 32) fail(LCTY_ERR_INVALID_INPUT, "mate offsets must be multiples of 32 bases");
             if (h->mate_off[m + 1] < h->mate_off[m] + h->mate_len[m]) fail(LCTY_ERR_INVALID_INPUT, "mate offsets overlap");
         }
-        DevBuf<uint32_t> d_len, d_bases, d_nm, d_cnt, d_loci; DevBuf<uint64_t> d_off;
+        // upload a host chunk ...
+        DevBuf<uint32_t> d_len, d_bases, d_nm; DevBuf<uint64_t> d_off;
         d_len.alloc(2 * n); d_off.alloc(2 * n + 1); d_bases.alloc(std::max<uint64_t>(nb / 16, 2)); d_nm.alloc(std::max<uint64_t>(nb / 32, 1));
-        d_cnt.alloc(n); d_loci.alloc(n * max_out);
         d_len.upload(h->mate_len, 2 * n, s); d_off.upload(h->mate_off, 2 * n + 1, s);
         d_bases.upload(h->bases2, nb / 16, s); d_nm.upload(h->nmask, nb / 32, s);
-        t->d_err.zero(s);
-        RecruitView V{};
-        V.table = t->d_table.p; V.table_mask = t->table_mask; V.entries = t->d_entries.p;
-        V.k = t->prm.minimizer_k; V.w = t->prm.minimizer_w;
-        V.ring = 2; while (V.ring < V.w) V.ring <<= 1;
-        V.mf_num = t->mf_num; V.mf_den = t->mf_den;
-        V.n_pairs = n; V.mate_len = d_len.p; V.mate_off = d_off.p; V.bases2 = d_bases.p; V.nmask = d_nm.p;
-        V.paired = paired != 0; V.max_out = max_out; V.out_cnt = d_cnt.p; V.out_loci = d_loci.p; V.err = t->d_err.p;
-        const size_t lds_single = static_cast<size_t>(V.ring) * 64 * (8 + 8 + 4);
-        const size_t lds = std::max<size_t>(static_cast<size_t>(V.ring) * 8, static_cast<size_t>(V.w) * (8 + 8 + 4)) * 64;   // pair kernel: w slots per array
-        // single reads of more than 256 bases go to the wavefront-per-read kernel (short-read rule up to 500 bases, long-read rule beyond)
-        uint32_t max_len = 1, max_long = 0;
-        std::vector<uint32_t> long_list;
-        for (uint64_t i = 0; i < n; i++) {
-            const uint32_t l1 = h->mate_len[2 * i], l2 = paired ? h->mate_len[2 * i + 1] : 0u;
-            if (!paired && l1 > 256) { long_list.push_back(static_cast<uint32_t>(i)); max_long = std::max(max_long, l1); }
-            else max_len = std::max(max_len, std::max(l1, l2));
-        }
-        if (max_len > 256) fail(LCTY_ERR_UNSUPPORTED, "recruitment: a mate of %u bases in a read pair (the device kernel takes mates of up to 256 bases)", max_len);
-        if (n > 0xFFFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "recruitment: more than 2^32 reads in one call");
-        V.scratch_cap = max_len;                                                 // a mate has fewer minimizers than bases
-        const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((n + 63) / 64, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16));
-        DevBuf<uint64_t> d_scratch, d_long_h; DevBuf<uint8_t> d_long_f, d_scratch_f; DevBuf<uint32_t> d_long_list;
-        d_scratch.alloc(static_cast<size_t>(blocks) * V.scratch_cap * 64); d_scratch_f.alloc(static_cast<size_t>(blocks) * V.scratch_cap * 64);
-        V.scratch = d_scratch.p; V.scratch_f = d_scratch_f.p;
-        V.match_frac = t->prm.match_frac;
-        // Params::new (recruit.rs:92-98)
-        V.stretch_minims = (2 * t->prm.match_length + (static_cast<uint32_t>(t->prm.minimizer_w) + 1) - 1) / (static_cast<uint32_t>(t->prm.minimizer_w) + 1);
-        V.stretch_score = static_cast<uint32_t>(std::ceil(std::max(static_cast<double>(V.stretch_minims) * (4.0 * t->prm.match_frac - 1.0), 3.0)));
-        ctx->timed(LCTY_K_RECRUIT, [&] {
-            hipLaunchKernelGGL(recruit_kernel, dim3(blocks), dim3(64), lds, s, V);
-        });
-        if (!long_list.empty()) {
-            V.n_long = static_cast<uint32_t>(long_list.size()); V.long_cap = max_long + 64;
-            const uint32_t lblocks = static_cast<uint32_t>(std::min<uint64_t>(long_list.size(), static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8));
-            d_long_list.alloc(long_list.size()); d_long_list.upload(long_list.data(), long_list.size(), s);
-            d_long_h.alloc(static_cast<size_t>(lblocks) * 2 * V.long_cap); d_long_f.alloc(static_cast<size_t>(lblocks) * 2 * V.long_cap);
-            V.long_list = d_long_list.p; V.long_h = d_long_h.p; V.long_f = d_long_f.p;
-            ctx->timed(LCTY_K_RECRUIT, [&] {
-                hipLaunchKernelGGL(recruit_single_kernel, dim3(lblocks), dim3(64), lds_single, s, V);
-            });
-        }
-        LCTY_HIP(hipGetLastError());
-        uint32_t err = 0;
-        t->d_err.download(&err, 1, s);
-        d_cnt.download(out_cnt, n, s); d_loci.download(out_loci, n * max_out, s);
-        LCTY_HIP(hipStreamSynchronize(s));
-        if (err == LCTY_ERR_UNSUPPORTED) fail(LCTY_ERR_UNSUPPORTED, "recruitment: a read matching minimizers of more than %u loci (%u for single reads beyond 256 bases)", MAX_LOCI_PER_READ, LONG_LOCI);
-        if (err == LCTY_ERR_INVALID_INPUT) fail(LCTY_ERR_INVALID_INPUT, "recruitment: max_out is smaller than the number of loci of a read");
-        if (err) fail(static_cast<int32_t>(err), "recruitment failed on the device");
-        for (uint64_t i = 0; i < n; i++) std::sort(out_loci + i * max_out, out_loci + i * max_out + out_cnt[i]);
+        // ... and run on the device view
+        recruit_device_view(t, n, h->mate_len, d_len.p, d_off.p, d_bases.p, d_nm.p, paired, max_out, out_cnt, out_loci);
     });
 }
 

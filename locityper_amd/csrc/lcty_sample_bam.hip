@@ -1,0 +1,933 @@
+// lcty_sample_bam.hip — a sample's reads from a coordinate-sorted, indexed BAM file, the input of `locityper genotype -a`:
+//   src/command/genotype.rs:776-797 postprocess_targets, 857-867 identify_pairedness, 872-907 recruit_to_targets
+//   src/seq/fastx.rs:577-673 BamRecord (read_from, write_to), 692-729 DirectBamReader, 732-803 IndexedBamReader, 805-874 PairedBamReader
+//   src/seq/interv.rs:74-77 add_padding, 232-247 merge
+// Host: the BAI index (SAM specification 5.2: bins -> chunks, the 16 kb linear index, the pseudo-bin 37450, n_no_coor), reg2bins, the
+// chunks of a call, pread of their byte ranges, inflation of their BGZF blocks into one page-locked buffer, the chain of record lengths.
+// Device, on the raw bytes of that buffer (records lie at any byte: every field is taken from two aligned dwords, ld32):
+//   record_kernel   a lane per record: fixed fields, reference length of the CIGAR (a CIGAR of more than 64 operations is summed by the
+//                   whole wavefront), the region / flag tests, the hash of the name, `curr <= mate`, the error classes
+//   exclusive_scan  over the kept flags -> the fetched stream in file order
+//   RadixSort       (hash of the name, stream ordinal): records of one hash side by side, in stream order
+//   pair_kernel     a lane per record: PairedBamReader's state machine replayed over the records of ITS name before it in the run of
+//                   its hash (names compared byte for byte), which says whether this record completes a pair and with whom
+//   exclusive_scan  over the completing records -> the pairs in the reference's order; assemble_kernel lays out the mates
+//   unpack_kernel   a lane per 32 bases of a mate: 4-bit codes -> bases2 / nmask, back to front and complemented for reverse records;
+//                   a lane writes whole words of its own only
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <zlib.h>
+
+#include <algorithm>
+#include <memory>
+#include <string>
+#include <system_error>
+#include <thread>
+#include <unordered_map>
+#include <vector>
+
+#include "lcty_objects.hpp"
+#include "lcty_scan.hpp"
+#include "lcty_sort.hpp"
+#include "lcty_writers.hpp"
+
+namespace lcty {
+
+constexpr uint64_t SLICE_PAD = 64;             // bytes behind the slice that the dword loads of a record's last bytes may touch
+constexpr uint32_t NONE32 = 0xFFFFFFFFu;
+// error classes, by rank at one record; (record ordinal << 8 | class) goes through atomicMin
+enum : uint32_t { E_SHORT = 1, E_UNSORTED = 2, E_CG = 3, E_NOSEQ = 4, E_UNPAIRED = 5, E_TWO_ENDS = 6 };
+constexpr uint32_t INFO_KEPT = 1u << 16, INFO_WAITS = 1u << 17;
+
+struct SampleView {
+    const uint32_t* raw;                        // the slice as dwords
+    const uint64_t* rec_off; uint32_t n_rec;    // byte offset of every record (of its block_size field)
+    const uint32_t* reg_tid; const uint32_t* reg_start; const uint32_t* reg_end; uint32_t n_reg;
+    int with_unmapped, whole_file;
+    uint64_t hash_mask;
+    uint32_t* info;                             // flag | INFO_*
+    uint64_t* hash;
+    uint32_t* kept;                             // 0 / 1
+    unsigned long long* err; uint32_t* n_primary;
+};
+
+// four bytes from byte `off` of the slice (the dword behind the last one is inside SLICE_PAD)
+__device__ __forceinline__ uint32_t ld32(const uint32_t* w, uint64_t off) {
+    const uint64_t i = off >> 2;
+    const uint64_t v = static_cast<uint64_t>(w[i]) | (static_cast<uint64_t>(w[i + 1]) << 32);
+    return static_cast<uint32_t>(v >> ((off & 3u) * 8u));
+}
+// reference bases of a CIGAR word: M, D, N, =, X
+__device__ __forceinline__ uint32_t cigar_ref_len(uint32_t w) { return ((0x18Du >> (w & 15u)) & 1u) ? (w >> 4) : 0u; }
+
+struct RecHead { int32_t tid, pos, mtid, mpos; uint32_t l_name, n_cigar, flag, l_seq, block; };
+__device__ __forceinline__ RecHead rec_head(const uint32_t* raw, uint64_t o) {
+    RecHead h;
+    h.block = ld32(raw, o); h.tid = static_cast<int32_t>(ld32(raw, o + 4)); h.pos = static_cast<int32_t>(ld32(raw, o + 8));
+    h.l_name = ld32(raw, o + 12) & 0xFFu;
+    const uint32_t nf = ld32(raw, o + 16);
+    h.n_cigar = nf & 0xFFFFu; h.flag = nf >> 16;
+    h.l_seq = ld32(raw, o + 20); h.mtid = static_cast<int32_t>(ld32(raw, o + 24)); h.mpos = static_cast<int32_t>(ld32(raw, o + 28));
+    return h;
+}
+__device__ __forceinline__ bool rec_fits(const RecHead& h) {
+    return 32ull + h.l_name + 4ull * h.n_cigar + (static_cast<uint64_t>(h.l_seq) + 1) / 2 + h.l_seq <= h.block;
+}
+// file order of two placed records; a record without coordinate (tid < 0) is behind every placed one
+__device__ __forceinline__ uint64_t sort_key(int32_t tid, int32_t pos) {
+    return tid < 0 ? ~0ull : (static_cast<uint64_t>(static_cast<uint32_t>(tid)) << 32) | static_cast<uint32_t>(pos + 1);
+}
+
+__global__ __launch_bounds__(256) void record_kernel(const SampleView V) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool valid = r < V.n_rec;
+    const uint64_t o = valid ? V.rec_off[r] : 0ull;
+    RecHead h{};
+    bool fits = false;
+    if (valid) { h = rec_head(V.raw, o); fits = rec_fits(h); }
+    const uint64_t cig = o + 36 + h.l_name;
+    // ---- reference length: up to 64 operations by the lane, more by the wavefront
+    unsigned long long rlen = 0;
+    const bool long_cigar = fits && h.n_cigar > 64u;
+    if (fits && !long_cigar) for (uint32_t j = 0; j < h.n_cigar; j++) rlen += cigar_ref_len(ld32(V.raw, cig + 4ull * j));
+    unsigned long long pending = __ballot(long_cigar);
+    while (pending) {
+        const int src = __ffsll(pending) - 1;
+        pending &= pending - 1;
+        const uint64_t c0 = __shfl(static_cast<unsigned long long>(cig), src);
+        const uint32_t nc = __shfl(h.n_cigar, src);
+        unsigned long long part = 0;
+        for (uint32_t j = lane; j < nc; j += 64u) part += cigar_ref_len(ld32(V.raw, c0 + 4ull * j));
+        part = wave_reduce(part, AddOp{});
+        if (static_cast<int>(lane) == src) rlen = part;
+    }
+    // ---- the tests
+    bool kept = false, primary = false;
+    uint32_t err = 0, info = 0;
+    if (valid && !fits) err = E_SHORT;
+    if (fits) {
+        primary = (h.flag & 0x900u) == 0;
+        if (V.whole_file) kept = primary;
+        else if (h.tid < 0) kept = primary && V.with_unmapped;
+        else {
+            if (h.flag & 4u) rlen = 0;
+            const int64_t endpos = static_cast<int64_t>(h.pos) + static_cast<int64_t>(rlen ? rlen : 1ull);    // bam_endpos
+            // the first region that ends behind pos (regions are sorted and disjoint): the only one the record can be taken by, since
+            // the regions before it end at or before pos and a later one on this contig would refuse pos < its min_start
+            uint32_t lo = 0, hi = V.n_reg;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) / 2;
+                const uint32_t t = V.reg_tid[mid];
+                const bool behind = t > static_cast<uint32_t>(h.tid) || (t == static_cast<uint32_t>(h.tid) && static_cast<int64_t>(V.reg_end[mid]) > h.pos);
+                if (behind) hi = mid; else lo = mid + 1;
+            }
+            const bool overlaps = lo < V.n_reg && V.reg_tid[lo] == static_cast<uint32_t>(h.tid) && static_cast<int64_t>(V.reg_start[lo]) < endpos;
+            kept = primary && overlaps;
+            if (primary && !(h.flag & 4u) && h.n_cigar == 2u && ld32(V.raw, cig) == ((h.l_seq << 4) | 4u) && (ld32(V.raw, cig + 4) & 15u) == 3u)
+                err = E_CG;
+        }
+        if (!err && kept && h.l_seq == 0) err = E_NOSEQ;                          // fastx.rs:599-602
+        if (!V.whole_file && r > 0) {
+            const uint64_t op = V.rec_off[r - 1];
+            const uint64_t before = sort_key(static_cast<int32_t>(ld32(V.raw, op + 4)), static_cast<int32_t>(ld32(V.raw, op + 8)));
+            if (before > sort_key(h.tid, h.pos) && (!err || err > E_UNSORTED)) err = E_UNSORTED;
+        }
+        const bool waits = static_cast<uint32_t>(h.tid) < static_cast<uint32_t>(h.mtid) ||
+                           (h.tid == h.mtid && static_cast<uint64_t>(static_cast<int64_t>(h.pos)) <= static_cast<uint64_t>(static_cast<int64_t>(h.mpos)));
+        info = h.flag | (kept ? INFO_KEPT : 0u) | (waits ? INFO_WAITS : 0u);
+        if (kept) {                                                              // FNV-1a over the name without its NUL, then mixed
+            uint64_t x = 0xcbf29ce484222325ull;
+            const uint32_t n = h.l_name ? h.l_name - 1 : 0u;
+            for (uint32_t j = 0; j < n; j += 4) {
+                uint32_t w = ld32(V.raw, o + 36 + j);
+                for (uint32_t b = 0; b < 4 && j + b < n; b++) { x = (x ^ (w & 0xFFu)) * 0x100000001b3ull; w >>= 8; }
+            }
+            V.hash[r] = mix64(x) & V.hash_mask;
+        }
+    }
+    if (valid) {
+        V.info[r] = info; V.kept[r] = kept ? 1u : 0u;
+        if (!kept) V.hash[r] = 0;
+        if (err) atomicMin(V.err, (static_cast<unsigned long long>(r) << 8) | err);
+    }
+    const unsigned long long prim = __ballot(primary);
+    if (lane == 0 && prim) atomicAdd(V.n_primary, static_cast<uint32_t>(__popcll(prim)));
+}
+
+// kept record r -> place scan[r] of the stream; the sort's input: (hash, stream ordinal)
+__global__ __launch_bounds__(256) void stream_kernel(uint32_t n_rec, const uint32_t* __restrict__ kept, const uint32_t* __restrict__ scan,
+                                                     const uint64_t* __restrict__ hash, uint32_t* __restrict__ stream, uint64_t* __restrict__ keys,
+                                                     uint64_t* __restrict__ vals) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_rec || !kept[r]) return;
+    const uint32_t s = scan[r];
+    stream[s] = r;
+    if (keys) { keys[s] = hash[r]; vals[s] = s; }
+}
+
+__device__ inline bool same_name(const uint32_t* raw, uint64_t oa, uint64_t ob) {
+    const uint32_t la = ld32(raw, oa + 12) & 0xFFu, lb = ld32(raw, ob + 12) & 0xFFu;
+    if (la != lb) return false;
+    for (uint32_t j = 0; j < la; j += 4) {
+        const uint32_t m = la - j >= 4 ? 0xFFFFFFFFu : (1u << (8 * (la - j))) - 1u;
+        if ((ld32(raw, oa + 36 + j) ^ ld32(raw, ob + 36 + j)) & m) return false;
+    }
+    return true;
+}
+
+// PairedBamReader::read_next (fastx.rs:829-869) for the record at place i of the sorted list: the records of its name before it, in
+// stream order, leave a record waiting or nobody; then this record completes a pair, waits, is discarded or is an error.
+__global__ __launch_bounds__(256) void pair_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ info,
+                                                   const uint32_t* __restrict__ stream, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ vals,
+                                                   uint32_t n, uint32_t* __restrict__ mate_of, uint32_t* __restrict__ completes, unsigned long long* err) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = keys[i];
+    uint32_t g = i;
+    while (g > 0 && keys[g - 1] == key) g--;
+    const uint32_t s = static_cast<uint32_t>(vals[i]), r = stream[s];
+    const uint64_t o = rec_off[r];
+    bool waiting = false, wait_first = false;
+    uint32_t wait_s = 0, mate = NONE32;
+    for (uint32_t t = g; t <= i; t++) {
+        const uint32_t st = static_cast<uint32_t>(vals[t]), rt = stream[st];
+        if (t < i && !same_name(raw, rec_off[rt], o)) continue;
+        const uint32_t inf = info[rt];
+        if ((inf & 0xC0u) == 0) {
+            if (t == i) atomicMin(err, (static_cast<unsigned long long>(r) << 8) | E_UNPAIRED);
+            continue;
+        }
+        const bool first = (inf & 0x40u) != 0;
+        if (waiting) {
+            if (first == wait_first) { if (t == i) atomicMin(err, (static_cast<unsigned long long>(r) << 8) | E_TWO_ENDS); }
+            else if (t == i) mate = wait_s;
+            waiting = false;                                                     // HashSet::take removed it either way
+        } else if (inf & INFO_WAITS) { waiting = true; wait_first = first; wait_s = st; }
+    }
+    mate_of[s] = mate; completes[s] = mate != NONE32 ? 1u : 0u;
+}
+
+// the mates of the output: src[m] = record of mate m (NONE32: absent), its length, and its length in units of 32 bases
+__global__ __launch_bounds__(256) void assemble_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ info,
+                                                       const uint32_t* __restrict__ stream, uint32_t n_stream, int paired, const uint32_t* __restrict__ mate_of,
+                                                       const uint32_t* __restrict__ pair_ix, uint32_t* __restrict__ src, uint32_t* __restrict__ src_stream,
+                                                       uint32_t* __restrict__ mate_len, uint32_t* __restrict__ units) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= n_stream) return;
+    uint32_t p = s, s1 = s, s2 = NONE32;
+    if (paired) {
+        if (mate_of[s] == NONE32) return;
+        p = pair_ix[s];
+        s2 = mate_of[s];
+        if (!(info[stream[s1]] & 0x40u)) { const uint32_t x = s1; s1 = s2; s2 = x; }     // mate 1 is the first in template
+    }
+    const uint32_t r1 = stream[s1], r2 = s2 != NONE32 ? stream[s2] : NONE32;
+    src_stream[2 * p] = s1; src_stream[2 * p + 1] = s2;
+    const uint32_t l1 = ld32(raw, rec_off[r1] + 20), l2 = r2 != NONE32 ? ld32(raw, rec_off[r2] + 20) : 0u;
+    src[2 * p] = r1; src[2 * p + 1] = r2;
+    mate_len[2 * p] = l1; mate_len[2 * p + 1] = l2;
+    units[2 * p] = l1 / 32u + ((l1 & 31u) ? 1u : 0u); units[2 * p + 1] = l2 / 32u + ((l2 & 31u) ? 1u : 0u);
+}
+__global__ __launch_bounds__(256) void offsets_kernel(const uint32_t* __restrict__ unit_off, uint64_t n, uint64_t* __restrict__ mate_off) {
+    const uint64_t m = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (m < n) mate_off[m] = 32ull * unit_off[m];
+}
+
+__device__ __forceinline__ uint32_t swap_nibbles(uint32_t x) { return ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu); }
+
+// unit u = 32 bases of one mate = one 64-bit word of bases2 and one word of nmask
+__global__ __launch_bounds__(256) void unpack_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ src,
+                                                     const uint32_t* __restrict__ unit_off, uint32_t n_mates, uint32_t n_units,
+                                                     uint64_t* __restrict__ bases2, uint32_t* __restrict__ nmask) {
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= n_units) return;
+    uint32_t lo_m = 0, hi_m = n_mates;                                           // the mate whose units hold u: last m with unit_off[m] <= u
+    while (hi_m - lo_m > 1) { const uint32_t mid = (lo_m + hi_m) / 2; if (unit_off[mid] <= u) lo_m = mid; else hi_m = mid; }
+    const uint32_t m = lo_m, q = u - unit_off[m];
+    const uint64_t o = rec_off[src[m]];
+    const uint32_t l_name = ld32(raw, o + 12) & 0xFFu, nf = ld32(raw, o + 16), L = ld32(raw, o + 20);
+    const bool reverse = ((nf >> 16) & 0x10u) != 0;
+    const uint32_t n = min(32u, L - 32u * q);
+    const uint32_t a = reverse ? L - 32u * q - n : 32u * q;                      // first base of the record this unit reads
+    const uint64_t b0 = o + 36 + l_name + 4ull * (nf & 0xFFFFu) + (a >> 1);
+    // 17 bytes at most; base a + t at bits 4 t of (lo, hi) once the nibbles of every byte are swapped and an odd start is shifted out
+    const uint32_t d0 = swap_nibbles(ld32(raw, b0)), d1 = swap_nibbles(ld32(raw, b0 + 4)), d2 = swap_nibbles(ld32(raw, b0 + 8)),
+                   d3 = swap_nibbles(ld32(raw, b0 + 12)), d4 = swap_nibbles(ld32(raw, b0 + 16));
+    uint64_t lo = d0 | (static_cast<uint64_t>(d1) << 32), hi = d2 | (static_cast<uint64_t>(d3) << 32);
+    if (a & 1u) { lo = (lo >> 4) | (hi << 60); hi = (hi >> 4) | (static_cast<uint64_t>(d4) << 60); }
+    uint64_t bases = 0; uint32_t mask = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < 32; t++) {
+        if (t < n) {
+            const uint32_t code = static_cast<uint32_t>((t < 16 ? lo >> (4 * t) : hi >> (4 * (t - 16))) & 15ull);
+            const uint32_t e = code == 1u ? 0u : code == 2u ? 1u : code == 4u ? 2u : code == 8u ? 3u : 4u;     // =ACMGRSVTWYHKDBN
+            const uint32_t at = reverse ? n - 1u - t : t;
+            if (e > 3u) mask |= 1u << at;
+            else bases |= static_cast<uint64_t>(reverse ? 3u - e : e) << (2u * at);
+        }
+    }
+    bases2[u] = bases; nmask[u] = mask;
+}
+
+// ---- host: BGZF by block, the header, the index ---------------------------------------------------------------------------------
+
+// the size of the BGZF block that starts at p (n bytes available, at least 18 needed); 0 = not a BGZF block
+static uint32_t bgzf_block_size(const uint8_t* p, size_t n) {
+    if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
+    const uint32_t xlen = p[10] | (p[11] << 8);
+    if (12 + xlen > n) return 0;
+    uint32_t bsize = 0;
+    for (size_t x = 12; x + 4 <= 12 + xlen;) {
+        const uint32_t slen = p[x + 2] | (p[x + 3] << 8);
+        if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen) bsize = (p[x + 4] | (p[x + 5] << 8)) + 1u;
+        x += 4 + slen;
+    }
+    return bsize < 12 + xlen + 8 ? 0 : bsize;
+}
+static void pread_all(int fd, void* buf, size_t n, uint64_t at, const char* path) {
+    uint8_t* p = static_cast<uint8_t*>(buf);
+    while (n) {
+        const ssize_t got = pread(fd, p, n, static_cast<off_t>(at));
+        if (got <= 0) fail(LCTY_ERR_RUNTIME, "read error on %s", path);
+        p += got; n -= static_cast<size_t>(got); at += static_cast<uint64_t>(got);
+    }
+}
+static void inflate_block(z_stream& zs, const uint8_t* in, uint32_t csize, uint8_t* out, uint32_t isize, const char* path) {
+    zs.next_in = const_cast<Bytef*>(in); zs.avail_in = csize;
+    zs.next_out = out; zs.avail_out = isize;
+    const int rc = inflate(&zs, Z_FINISH);
+    if (rc != Z_STREAM_END || zs.avail_out != 0) fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BGZF block (zlib %d)", path, rc);
+    if (inflateReset(&zs) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateReset");
+}
+
+// the blocks of a BGZF file one after the other, from its start: the header and the first record
+struct BgzfSerial {
+    int fd; uint64_t fsize; const char* path;
+    uint64_t coff = 0, next = 0;                 // the block in `data`, the one behind it
+    std::vector<uint8_t> data; size_t at = 0;
+    z_stream zs;
+    BgzfSerial(int fd_, uint64_t fsize_, const char* path_) : fd(fd_), fsize(fsize_), path(path_) {
+        memset(&zs, 0, sizeof(zs));
+        if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateInit2");
+    }
+    ~BgzfSerial() { inflateEnd(&zs); }
+    bool load() {                                // the next block that holds data; false at the end of the file
+        while (at == data.size()) {
+            if (next >= fsize) return false;
+            uint8_t buf[0x10000];
+            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(buf), fsize - next));
+            pread_all(fd, buf, n, next, path);
+            const uint32_t csize = bgzf_block_size(buf, n);
+            if (!csize || csize > n) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu", path, static_cast<unsigned long long>(next));
+            const uint32_t isize = buf[csize - 4] | (buf[csize - 3] << 8) | (buf[csize - 2] << 16) | (static_cast<uint32_t>(buf[csize - 1]) << 24);
+            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
+            data.resize(isize);
+            if (isize) inflate_block(zs, buf, csize, data.data(), isize, path); else if (inflateReset(&zs) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateReset");
+            coff = next; next += csize; at = 0;
+        }
+        return true;
+    }
+    bool read(void* out, size_t n) {             // false: the file ends first
+        uint8_t* p = static_cast<uint8_t*>(out);
+        while (n) {
+            if (!load()) return false;
+            const size_t take = std::min(n, data.size() - at);
+            memcpy(p, data.data() + at, take);
+            p += take; n -= take; at += take;
+        }
+        return true;
+    }
+    uint64_t tell() { return at == data.size() ? next << 16 : (coff << 16) | at; }
+};
+
+struct Chunk { uint64_t beg, end; };
+
+}  // namespace lcty
+
+using namespace lcty;
+
+struct lcty_sample_bam {
+    std::string path, index_path;
+    int fd = -1;
+    uint64_t fsize = 0;
+    std::vector<uint32_t> lengths; std::vector<uint64_t> name_off; std::string names;
+    uint64_t first_record = 0;                   // virtual offset behind the header
+    int paired = -1;                             // flag 0x1 of the first record; -1: not looked at yet, -2: no record
+    struct Ref { std::unordered_map<uint32_t, std::vector<Chunk>> bins; std::vector<uint64_t> linear; };
+    std::vector<Ref> refs;
+    uint64_t tail_start = 0;                     // largest chunk end of the index
+    uint64_t n_no_coor = 0; bool has_no_coor = false;
+    ~lcty_sample_bam() { if (fd >= 0) close(fd); }
+};
+
+struct lcty_sample_reads {
+    lcty_ctx* ctx = nullptr;
+    bool paired = false;
+    uint64_t n = 0;                              // pairs, or single reads
+    uint8_t* slice = nullptr;                    // page-locked: the inflated blocks of the call
+    std::vector<uint64_t> rec_off;
+    DevBuf<uint32_t> d_len, d_nm, d_src; DevBuf<uint64_t> d_off, d_bases;
+    uint64_t n_units = 0;
+    std::vector<uint32_t> h_len, h_src, h_src_stream, h_bases, h_nm;    // h_src: a mate's record among the records walked (rec_off); _stream: in the fetched stream
+    std::vector<uint64_t> h_off, zero_off;
+    bool have_bases = false;
+    ~lcty_sample_reads() { if (slice) (void)hipHostFree(slice); }
+};
+
+namespace {
+
+bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
+
+std::vector<uint8_t> read_file(const std::string& path) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", path.c_str());
+    std::vector<uint8_t> buf;
+    uint8_t chunk[1 << 16];
+    size_t n;
+    while ((n = fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) fail(LCTY_ERR_RUNTIME, "read error on %s", path.c_str());
+    return buf;
+}
+
+void load_bai(lcty_sample_bam* b) {
+    const std::vector<uint8_t> x = read_file(b->index_path);
+    const char* ip = b->index_path.c_str();
+    if (x.size() >= 4 && memcmp(x.data(), "CSI\1", 4) == 0) fail(LCTY_ERR_UNSUPPORTED, "%s is a CSI index (only BAI indices are read)", ip);
+    if (x.size() >= 2 && x[0] == 0x1f && x[1] == 0x8b) fail(LCTY_ERR_UNSUPPORTED, "%s is compressed: a CSI index? (only BAI indices are read)", ip);
+    if (x.size() < 8 || memcmp(x.data(), "BAI\1", 4) != 0) fail(LCTY_ERR_INVALID_DATA, "%s is not a BAI index", ip);
+    size_t at = 4;
+    auto need = [&](size_t n) { if (at + n > x.size()) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAI index", ip); };
+    auto u32 = [&]() { need(4); uint32_t v; memcpy(&v, x.data() + at, 4); at += 4; return v; };
+    auto u64 = [&]() { need(8); uint64_t v; memcpy(&v, x.data() + at, 8); at += 8; return v; };
+    const uint32_t n_ref = u32();
+    if (n_ref != b->lengths.size()) fail(LCTY_ERR_INVALID_DATA, "%s: the index has %u references, the BAM header %zu", ip, n_ref, b->lengths.size());
+    b->refs.resize(n_ref);
+    b->tail_start = b->first_record;
+    for (uint32_t r = 0; r < n_ref; r++) {
+        const uint32_t n_bin = u32();
+        for (uint32_t k = 0; k < n_bin; k++) {
+            const uint32_t bin = u32(), n_chunk = u32();
+            need(16ull * n_chunk);
+            std::vector<Chunk> cs(n_chunk);
+            for (uint32_t c = 0; c < n_chunk; c++) { cs[c].beg = u64(); cs[c].end = u64(); }
+            if (bin == 37450) { if (n_chunk) b->tail_start = std::max(b->tail_start, cs[0].end); continue; }      // pseudo-bin: file range, counts
+            for (const Chunk& c : cs) b->tail_start = std::max(b->tail_start, c.end);
+            b->refs[r].bins[bin] = std::move(cs);
+        }
+        const uint32_t n_intv = u32();
+        need(8ull * n_intv);
+        b->refs[r].linear.resize(n_intv);
+        for (uint32_t k = 0; k < n_intv; k++) b->refs[r].linear[k] = u64();
+    }
+    if (at + 8 <= x.size()) { b->n_no_coor = u64(); b->has_no_coor = true; }
+}
+
+void check_regions(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end) {
+    if (n && (!tid || !start || !end)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+    for (uint32_t i = 0; i < n; i++) {
+        if (tid[i] >= b->lengths.size()) fail(LCTY_ERR_INVALID_INPUT, "region %u: contig %u of %zu", i, tid[i], b->lengths.size());
+        if (start[i] >= end[i]) fail(LCTY_ERR_INVALID_INPUT, "region %u is empty (%u-%u)", i, start[i], end[i]);
+        if (i && (tid[i] < tid[i - 1] || (tid[i] == tid[i - 1] && start[i] < end[i - 1])))
+            fail(LCTY_ERR_INVALID_INPUT, "Cannot fetch reads from BAM file: regions must be sorted (region %u)", i);       // fastx.rs:770
+    }
+}
+
+// the chunks of a call: reg2bins (SAM specification 5.3), the linear index's cut, sorted and merged
+std::vector<Chunk> plan_chunks(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end, bool with_unmapped,
+                               bool whole_file) {
+    std::vector<Chunk> cs;
+    const uint64_t file_end = b->fsize << 16;
+    if (whole_file) { cs.push_back(Chunk{b->first_record, file_end}); return cs; }
+    for (uint32_t i = 0; i < n; i++) {
+        const lcty_sample_bam::Ref& R = b->refs[tid[i]];
+        const uint32_t beg = std::min(start[i], (1u << 29) - 1), e = std::min(end[i], 1u << 29) - 1;      // e: last base, inclusive
+        uint64_t min_off = 0;
+        if (!R.linear.empty()) min_off = R.linear[std::min<size_t>(beg >> 14, R.linear.size() - 1)];
+        auto take = [&](uint32_t bin) {
+            auto it = R.bins.find(bin);
+            if (it == R.bins.end()) return;
+            for (const Chunk& c : it->second) if (c.end > min_off && c.beg < c.end) cs.push_back(c);
+        };
+        take(0);
+        static const uint32_t first[5] = {1, 9, 73, 585, 4681}, shift[5] = {26, 23, 20, 17, 14};
+        for (int l = 0; l < 5; l++) for (uint32_t k = first[l] + (beg >> shift[l]); k <= first[l] + (e >> shift[l]); k++) take(k);
+    }
+    if (with_unmapped && b->tail_start < file_end) cs.push_back(Chunk{b->tail_start, file_end});
+    std::sort(cs.begin(), cs.end(), [](const Chunk& a, const Chunk& c) { return a.beg != c.beg ? a.beg < c.beg : a.end < c.end; });
+    std::vector<Chunk> merged;
+    for (const Chunk& c : cs) {
+        // touching, overlapping, or starting in the block the last one ends in: one chunk (the records between are walked and filtered)
+        if (!merged.empty() && (c.beg >> 16) <= (merged.back().end >> 16)) merged.back().end = std::max(merged.back().end, c.end);
+        else merged.push_back(c);
+    }
+    return merged;
+}
+
+// a chunk's blocks as they lie in the file
+struct Block { uint32_t csize, isize; uint64_t out_at; size_t in_at; };      // compressed size, inflated size, place in the slice, place in `comp`
+struct ChunkSpan { size_t first_block, n_blocks; uint64_t chain_beg, chain_end, span_end; };
+
+std::string record_name(const uint8_t* slice, uint64_t o) {
+    const uint32_t l = slice[o + 12];
+    std::string s(reinterpret_cast<const char*>(slice + o + 36), l ? l - 1 : 0);
+    const size_t z = s.find('\0');
+    if (z != std::string::npos) s.resize(z);
+    return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t lcty_sample_bam_open(const char* path, const char* index_path, lcty_sample_bam** out) {
+    return guarded([&] {
+        if (!path || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        *out = nullptr;
+        std::unique_ptr<lcty_sample_bam> b(new lcty_sample_bam());
+        b->path = path;
+        b->fd = open(path, O_RDONLY | O_CLOEXEC);
+        if (b->fd < 0) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", path);
+        struct stat st;
+        if (fstat(b->fd, &st) != 0) fail(LCTY_ERR_RUNTIME, "cannot stat %s", path);
+        b->fsize = static_cast<uint64_t>(st.st_size);
+        if (b->fsize >= (1ull << 48)) fail(LCTY_ERR_UNSUPPORTED, "%s: a file of 2^48 bytes or more", path);
+        uint8_t magic[4] = {0, 0, 0, 0};
+        if (b->fsize >= 4) pread_all(b->fd, magic, 4, 0, path);
+        if (memcmp(magic, "CRAM", 4) == 0) fail(LCTY_ERR_UNSUPPORTED, "%s is a CRAM file (only BAM files are read)", path);
+        // ---- the header (SAM specification 4.2)
+        BgzfSerial in(b->fd, b->fsize, path);
+        uint8_t head[8];
+        if (!in.read(head, 8) || memcmp(head, "BAM\1", 4) != 0) fail(LCTY_ERR_INVALID_DATA, "%s is not a BAM file", path);
+        uint32_t l_text; memcpy(&l_text, head + 4, 4);
+        std::vector<uint8_t> text(l_text);
+        uint32_t n_ref = 0;
+        if (!in.read(text.data(), l_text) || !in.read(&n_ref, 4)) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAM header", path);
+        for (uint32_t r = 0; r < n_ref; r++) {
+            uint32_t l_name = 0, l_ref = 0;
+            if (!in.read(&l_name, 4) || l_name == 0 || l_name > (1u << 20)) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAM header", path);
+            std::string nm(l_name, '\0');
+            if (!in.read(&nm[0], l_name) || !in.read(&l_ref, 4)) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAM header", path);
+            b->name_off.push_back(b->names.size());
+            b->names.append(nm.c_str()); b->names.push_back('\0');
+            b->lengths.push_back(l_ref);
+        }
+        b->name_off.push_back(b->names.size());
+        (void)in.load();
+        b->first_record = in.tell();
+        uint8_t rec[36];
+        if (in.read(rec, 36)) { uint16_t flag; memcpy(&flag, rec + 18, 2); b->paired = flag & 1; } else b->paired = -2;
+        // ---- the index
+        const std::string p = path;
+        if (index_path) b->index_path = index_path;
+        else if (file_exists(p + ".bai")) b->index_path = p + ".bai";
+        else if (p.size() > 4 && p.compare(p.size() - 4, 4, ".bam") == 0 && file_exists(p.substr(0, p.size() - 4) + ".bai")) b->index_path = p.substr(0, p.size() - 4) + ".bai";
+        else if (file_exists(p + ".csi")) fail(LCTY_ERR_UNSUPPORTED, "%s.csi is a CSI index (only BAI indices are read)", path);
+        else fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s.bai)", path, path);
+        if (!file_exists(b->index_path)) fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s)", path, b->index_path.c_str());
+        load_bai(b.get());
+        *out = b.release();
+    });
+}
+
+void lcty_sample_bam_close(lcty_sample_bam* bam) { delete bam; }
+
+int32_t lcty_sample_bam_contigs(const lcty_sample_bam* bam, uint32_t* n, const char** names, const uint64_t** name_off, const uint32_t** lengths) {
+    return guarded([&] {
+        if (!bam || !n) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        *n = static_cast<uint32_t>(bam->lengths.size());
+        if (names) *names = bam->names.c_str();
+        if (name_off) *name_off = bam->name_off.data();
+        if (lengths) *lengths = bam->lengths.data();
+    });
+}
+
+int32_t lcty_sample_bam_is_paired(lcty_sample_bam* bam, int32_t* paired) {
+    return guarded([&] {
+        if (!bam || !paired) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (bam->paired < 0) fail(LCTY_ERR_INVALID_DATA, "Input BAM/CRAM file is empty");              // genotype.rs:861
+        *paired = bam->paired;
+    });
+}
+
+int32_t lcty_recruit_fetch_regions(uint32_t n_in, const uint32_t* tid, const uint32_t* start, const uint32_t* end, uint32_t n_contigs,
+                                   const uint32_t* contig_len, uint32_t padding, uint32_t alt_contig_len, uint32_t merge_distance,
+                                   uint32_t* out_tid, uint32_t* out_start, uint32_t* out_end, uint32_t* n_out) {
+    return guarded([&] {
+        if ((n_in && (!tid || !start || !end)) || (n_contigs && !contig_len) || !out_tid || !out_start || !out_end || !n_out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        struct Iv { uint32_t tid, start, end; };
+        std::vector<Iv> v;
+        for (uint32_t i = 0; i < n_in; i++) {
+            if (tid[i] >= n_contigs) fail(LCTY_ERR_INVALID_INPUT, "interval %u: contig %u of %u", i, tid[i], n_contigs);
+            if (start[i] >= end[i]) fail(LCTY_ERR_INVALID_INPUT, "interval %u is empty (%u-%u)", i, start[i], end[i]);
+            // Interval::add_padding (interv.rs:74-77)
+            const uint64_t e = std::min<uint64_t>(static_cast<uint64_t>(end[i]) + padding, contig_len[tid[i]]);
+            v.push_back(Iv{tid[i], start[i] > padding ? start[i] - padding : 0u, static_cast<uint32_t>(e)});
+        }
+        for (uint32_t c = 0; c < n_contigs; c++) if (contig_len[c] < alt_contig_len) v.push_back(Iv{c, 0, contig_len[c]});
+        std::sort(v.begin(), v.end(), [](const Iv& a, const Iv& b) { return a.tid != b.tid ? a.tid < b.tid : a.start != b.start ? a.start < b.start : a.end < b.end; });
+        uint32_t m = 0;
+        for (const Iv& c : v) {                                                  // Interval::merge (interv.rs:232-247)
+            if (m && out_tid[m - 1] == c.tid && static_cast<uint64_t>(out_end[m - 1]) + merge_distance >= c.start) out_end[m - 1] = std::max(out_end[m - 1], c.end);
+            else { out_tid[m] = c.tid; out_start[m] = c.start; out_end[m] = c.end; m++; }
+        }
+        *n_out = m;
+    });
+}
+
+int32_t lcty_sample_bam_plan(lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
+                             int32_t with_unmapped, uint64_t chunk_cap, uint64_t* n_chunks, uint64_t* chunk_beg, uint64_t* chunk_end,
+                             uint64_t* blocks_total) {
+    return guarded([&] {
+        if (!bam || !n_chunks || (chunk_cap && (!chunk_beg || !chunk_end))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        check_regions(bam, n_regions, tid, start, end);
+        const std::vector<Chunk> cs = plan_chunks(bam, n_regions, tid, start, end, with_unmapped != 0, false);
+        *n_chunks = cs.size();
+        for (size_t i = 0; i < cs.size() && i < chunk_cap; i++) { chunk_beg[i] = cs[i].beg; chunk_end[i] = cs[i].end; }
+        if (blocks_total) {
+            uint64_t blocks = 0;
+            for (const Chunk& c : cs) {
+                uint64_t at = c.beg >> 16;
+                const uint64_t last = c.end >> 16;
+                while (at < bam->fsize && (at < last || (at == last && (c.end & 0xFFFF)))) {
+                    uint8_t hd[512];
+                    const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), bam->fsize - at));
+                    pread_all(bam->fd, hd, n, at, bam->path.c_str());
+                    const uint32_t csize = bgzf_block_size(hd, n);
+                    if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu", bam->path.c_str(), static_cast<unsigned long long>(at));
+                    blocks++; at += csize;
+                }
+            }
+            *blocks_total = blocks;
+        }
+    });
+}
+
+int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start,
+                              const uint32_t* end, int32_t with_unmapped, int32_t whole_file, int32_t paired, lcty_sample_reads** reads,
+                              lcty_sample_bam_stats* stats) {
+    if (reads) *reads = nullptr;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return guarded([&] {
+        if (!ctx || !bam || !reads) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        const double t_start = now_ms();
+        const char* path = bam->path.c_str();
+        if (whole_file && (n_regions || with_unmapped)) fail(LCTY_ERR_INVALID_INPUT, "whole_file goes without regions and without with_unmapped");
+        if (!whole_file && !n_regions && !with_unmapped) fail(LCTY_ERR_INVALID_INPUT, "nothing to fetch: no regions, no unmapped reads, not the whole file");
+        if (paired < 0) {
+            if (bam->paired < 0) fail(LCTY_ERR_INVALID_DATA, "Input BAM/CRAM file is empty");
+            paired = bam->paired;
+        }
+        if (paired && whole_file) fail(LCTY_ERR_UNSUPPORTED, "paired-end reads of a BAM file are read through its index: give the regions (fastx.rs:692-729 is single-end)");
+        check_regions(bam, n_regions, tid, start, end);
+        const int64_t hash_bits = ctx->knob("sample_bam_hash_bits", 64);
+        if (hash_bits > 64) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_hash_bits = %lld (0 .. 64)", static_cast<long long>(hash_bits));
+        const uint64_t hash_mask = hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1;
+        const uint64_t cap = static_cast<uint64_t>(ctx->knob("sample_bam_max_slice_bytes", 1ll << 33));
+        lcty_sample_bam_stats S{};
+        S.n_regions = n_regions; S.file_bytes = bam->fsize;
+        const std::vector<Chunk> cs = plan_chunks(bam, n_regions, tid, start, end, with_unmapped != 0, whole_file != 0);
+        S.n_chunks = cs.size();
+
+        // ---- the bytes of the chunks, split into blocks
+        double t0 = now_ms();
+        std::vector<uint8_t> comp;
+        std::vector<Block> blocks;
+        std::vector<ChunkSpan> spans;
+        uint64_t total = 0;
+        for (const Chunk& c : cs) {
+            const uint64_t cbeg = c.beg >> 16, cend = c.end >> 16;
+            const uint32_t uend = static_cast<uint32_t>(c.end & 0xFFFF);
+            if (cbeg >= bam->fsize) continue;
+            uint64_t rend = cend;                                              // ... and the block the chunk ends in, when it reaches into it
+            if (uend && cend < bam->fsize) {
+                uint8_t hd[512];
+                const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), bam->fsize - cend));
+                pread_all(bam->fd, hd, n, cend, path);
+                const uint32_t csize = bgzf_block_size(hd, n);
+                if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(cend));
+                rend = std::min<uint64_t>(bam->fsize, cend + csize);
+            }
+            rend = std::min<uint64_t>(rend, bam->fsize);
+            const size_t in0 = comp.size();
+            comp.resize(in0 + (rend - cbeg));
+            pread_all(bam->fd, comp.data() + in0, rend - cbeg, cbeg, path);
+            S.bytes_read += rend - cbeg;
+            ChunkSpan sp{blocks.size(), 0, total + (c.beg & 0xFFFF), 0, 0};
+            bool end_seen = false;
+            uint64_t at = cbeg;
+            while (at < rend && (at < cend || (at == cend && uend))) {
+                const uint8_t* p = comp.data() + in0 + (at - cbeg);
+                const uint32_t csize = bgzf_block_size(p, rend - at);
+                if (!csize || at + csize > rend) {
+                    if (at + 0x10000 >= bam->fsize) fail(LCTY_ERR_INVALID_DATA, "%s: truncated or corrupt BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
+                    fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(at));
+                }
+                const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
+                if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
+                if (at == cbeg && (c.beg & 0xFFFF) > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index starts behind its block", path);
+                if (at == cend) { if (uend > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index ends behind its block", path); sp.chain_end = total + uend; end_seen = true; }
+                blocks.push_back(Block{csize, isize, total, in0 + static_cast<size_t>(at - cbeg)});
+                total += isize; at += csize;
+            }
+            sp.n_blocks = blocks.size() - sp.first_block; sp.span_end = total;
+            if (!end_seen) sp.chain_end = total;
+            if (sp.n_blocks) spans.push_back(sp);
+        }
+        S.ms_read = now_ms() - t0;
+        S.blocks_inflated = blocks.size(); S.bytes_inflated = total;
+        if (total > cap)
+            fail(LCTY_ERR_UNSUPPORTED, "%s: the fetched slice has %llu bytes, more than %llu (knob sample_bam_max_slice_bytes)", path,
+                 static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
+
+        // ---- inflate: every block into its place of one page-locked buffer
+        ctx->activate();
+        hipStream_t s = ctx->stream;
+        std::unique_ptr<lcty_sample_reads> R(new lcty_sample_reads());
+        R->ctx = ctx; R->paired = paired != 0;
+        LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&R->slice), total + SLICE_PAD, hipHostMallocDefault));
+        memset(R->slice + total, 0, SLICE_PAD);
+        t0 = now_ms();
+        {
+            const uint32_t n_threads = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>({blocks.size() / 64 + 1, 16, std::thread::hardware_concurrency()})));
+            std::vector<std::string> failed(n_threads);
+            auto work = [&](uint32_t id) {
+                z_stream zs;
+                memset(&zs, 0, sizeof(zs));
+                if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) { failed[id] = "zlib: inflateInit2"; return; }
+                try {
+                    for (size_t k = id; k < blocks.size(); k += n_threads)
+                        if (blocks[k].isize) inflate_block(zs, comp.data() + blocks[k].in_at, blocks[k].csize, R->slice + blocks[k].out_at, blocks[k].isize, path);
+                } catch (const Error& e) { failed[id] = e.what(); }
+                inflateEnd(&zs);
+            };
+            std::vector<std::thread> th;
+            std::vector<uint32_t> here;
+            for (uint32_t id = 1; id < n_threads; id++) {
+                try { th.emplace_back(work, id); } catch (const std::system_error&) { here.push_back(id); }
+            }
+            work(0);
+            for (uint32_t id : here) work(id);
+            for (auto& x : th) x.join();
+            for (const std::string& f : failed) if (!f.empty()) fail(LCTY_ERR_INVALID_DATA, "%s", f.c_str());
+        }
+        S.ms_inflate = now_ms() - t0;
+        std::vector<uint8_t>().swap(comp);
+
+        // ---- the chain of record lengths
+        t0 = now_ms();
+        std::vector<uint64_t>& rec_off = R->rec_off;
+        for (const ChunkSpan& sp : spans) {
+            uint64_t p = sp.chain_beg;
+            while (p < sp.chain_end) {
+                uint32_t bs = 0;
+                if (p + 4 <= sp.span_end) memcpy(&bs, R->slice + p, 4);
+                if (p + 4 > sp.span_end || bs < 32 || p + 4 + bs > sp.span_end)
+                    fail(LCTY_ERR_INVALID_DATA, "%s: record %zu of the fetched slice is truncated, or its length (%u) leaves the slice", path, rec_off.size(), bs);
+                rec_off.push_back(p);
+                p += 4ull + bs;
+            }
+        }
+        const uint64_t n_rec = rec_off.size();
+        S.records_walked = n_rec;
+        S.ms_walk = now_ms() - t0;
+        if (n_rec >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "%s: %llu records in one fetch", path, static_cast<unsigned long long>(n_rec));
+
+        auto finish = [&]() {
+            S.ms_total = now_ms() - t_start;
+            if (stats) *stats = S;
+            *reads = R.release();
+        };
+        if (n_rec == 0) { R->zero_off.assign(1, 0); R->h_off.assign(1, 0); R->have_bases = true; R->h_bases.assign(2, 0); R->h_nm.assign(1, 0); finish(); return; }
+
+        // ---- upload, record kernel
+        t0 = now_ms();
+        DevBuf<uint8_t> d_raw; DevBuf<uint64_t> d_rec_off, d_hash; DevBuf<uint32_t> d_reg, d_info, d_kept, d_nprim; DevBuf<unsigned long long> d_err;
+        d_raw.alloc(total + SLICE_PAD); d_raw.upload(R->slice, total + SLICE_PAD, s);
+        d_rec_off.alloc(n_rec); d_rec_off.upload(rec_off.data(), n_rec, s);
+        std::vector<uint32_t> reg(3ull * std::max(n_regions, 1u), 0);
+        for (uint32_t i = 0; i < n_regions; i++) { reg[i] = tid[i]; reg[n_regions + i] = start[i]; reg[2ull * n_regions + i] = end[i]; }
+        d_reg.alloc(reg.size()); d_reg.upload(reg.data(), reg.size(), s);
+        d_info.alloc(n_rec); d_kept.alloc(n_rec); d_hash.alloc(n_rec); d_nprim.alloc(1); d_err.alloc(1);
+        d_nprim.zero(s);
+        LCTY_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), s));
+        LCTY_HIP(hipStreamSynchronize(s));
+        S.ms_upload = now_ms() - t0;
+        t0 = now_ms();
+        const uint32_t* raw = reinterpret_cast<const uint32_t*>(d_raw.p);
+        SampleView V{};
+        V.raw = raw; V.rec_off = d_rec_off.p; V.n_rec = static_cast<uint32_t>(n_rec);
+        V.reg_tid = d_reg.p; V.reg_start = d_reg.p + n_regions; V.reg_end = d_reg.p + 2ull * n_regions; V.n_reg = n_regions;
+        V.with_unmapped = with_unmapped != 0; V.whole_file = whole_file != 0; V.hash_mask = hash_mask;
+        V.info = d_info.p; V.hash = d_hash.p; V.kept = d_kept.p; V.err = d_err.p; V.n_primary = d_nprim.p;
+        hipLaunchKernelGGL(record_kernel, dim3(blocks_of(n_rec, 256)), dim3(256), 0, s, V);
+        LCTY_HIP(hipGetLastError());
+        ScanTotal scan;
+        DevBuf<uint32_t> d_scan, d_stream;
+        const uint32_t n_stream = scan.run(d_kept, d_scan, n_rec, ctx);
+        auto check_err = [&]() {
+            unsigned long long e = 0;
+            d_err.download(&e, 1, s);
+            LCTY_HIP(hipStreamSynchronize(s));
+            if (e == ~0ull) return;
+            const uint32_t cls = static_cast<uint32_t>(e & 0xFF);
+            const uint64_t r = e >> 8;
+            const uint64_t o = rec_off[r];
+            if (cls == E_SHORT) fail(LCTY_ERR_INVALID_DATA, "%s: record %llu of the fetched slice is shorter than its fields", path, static_cast<unsigned long long>(r));
+            const std::string name = record_name(R->slice, o);
+            if (cls == E_UNSORTED) fail(LCTY_ERR_INVALID_DATA, "%s: coordinates run backwards at read %s: the file is not sorted", path, name.c_str());
+            if (cls == E_CG) fail(LCTY_ERR_UNSUPPORTED, "%s: the CIGAR of read %s is kept in a CG tag (more than 65 535 operations)", path, name.c_str());
+            if (cls == E_NOSEQ) fail(LCTY_ERR_INVALID_DATA, "Primary alignment for read %s has no sequence", name.c_str());
+            if (cls == E_UNPAIRED) fail(LCTY_ERR_INVALID_DATA, "Expected paired-end reads, but read %s is unpaired", name.c_str());
+            if (cls == E_TWO_ENDS) fail(LCTY_ERR_INVALID_DATA, "Found two primary alignments for %s for the same read end", name.c_str());
+            fail(LCTY_ERR_RUNTIME, "%s: unknown device error %u", path, cls);
+        };
+        check_err();
+        uint32_t n_primary = 0;
+        d_nprim.download(&n_primary, 1, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+        S.records_primary = n_primary; S.records_kept = n_stream;
+        S.ms_record = now_ms() - t0;
+
+        // ---- the stream, and its pairs
+        t0 = now_ms();
+        d_stream.alloc(std::max<uint32_t>(n_stream, 1));
+        DevBuf<uint64_t> d_ka, d_va, d_kb, d_vb;
+        DevBuf<uint32_t> d_mate_of, d_completes, d_pair_ix;
+        if (paired) { d_ka.alloc(std::max<uint32_t>(n_stream, 1)); d_va.alloc(d_ka.n); d_kb.alloc(d_ka.n); d_vb.alloc(d_ka.n); }
+        hipLaunchKernelGGL(stream_kernel, dim3(blocks_of(n_rec, 256)), dim3(256), 0, s, static_cast<uint32_t>(n_rec), d_kept.p, d_scan.p, d_hash.p,
+                           d_stream.p, paired ? d_ka.p : nullptr, paired ? d_va.p : nullptr);
+        LCTY_HIP(hipGetLastError());
+        uint64_t n_out = n_stream;
+        RadixSort sorter;
+        if (paired && n_stream) {
+            std::vector<uint32_t> shifts;
+            for (uint32_t sh = 0; sh < static_cast<uint32_t>(std::max<int64_t>(hash_bits, 0)); sh += 8) shifts.push_back(sh);
+            int where = 0;
+            if (!shifts.empty()) where = sorter.run(d_ka.p, d_va.p, d_kb.p, d_vb.p, n_stream, shifts, s);
+            const uint64_t* keys = where ? d_kb.p : d_ka.p; const uint64_t* vals = where ? d_vb.p : d_va.p;
+            d_mate_of.alloc(n_stream); d_completes.alloc(n_stream);
+            hipLaunchKernelGGL(pair_kernel, dim3(blocks_of(n_stream, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_info.p, d_stream.p, keys, vals, n_stream,
+                               d_mate_of.p, d_completes.p, d_err.p);
+            LCTY_HIP(hipGetLastError());
+            n_out = scan.run(d_completes, d_pair_ix, n_stream, ctx);
+            check_err();
+        } else if (paired) n_out = 0;
+        S.n_pairs = n_out; S.n_discarded = paired ? n_stream - 2 * n_out : 0;
+        S.ms_pair = now_ms() - t0;
+
+        // ---- the mates and their bases
+        t0 = now_ms();
+        R->n = n_out;
+        R->zero_off.assign(n_out + 1, 0);
+        if (n_out == 0) { R->h_off.assign(1, 0); R->have_bases = true; R->h_bases.assign(2, 0); R->h_nm.assign(1, 0); finish(); return; }
+        DevBuf<uint32_t> d_units, d_unit_off, d_src_stream;
+        d_src_stream.alloc(2 * n_out);
+        R->d_src.alloc(2 * n_out); R->d_len.alloc(2 * n_out); d_units.alloc(2 * n_out); R->d_off.alloc(2 * n_out + 1);
+        hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n_stream, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_info.p, d_stream.p, n_stream, paired ? 1 : 0,
+                           d_mate_of.p, d_pair_ix.p, R->d_src.p, d_src_stream.p, R->d_len.p, d_units.p);
+        LCTY_HIP(hipGetLastError());
+        const uint32_t n_units = scan.run(d_units, d_unit_off, 2 * n_out, ctx);
+        R->n_units = n_units;
+        hipLaunchKernelGGL(offsets_kernel, dim3(blocks_of(2 * n_out + 1, 256)), dim3(256), 0, s, d_unit_off.p, 2 * n_out + 1, R->d_off.p);
+        R->d_bases.alloc(std::max<uint32_t>(n_units, 1)); R->d_nm.alloc(std::max<uint32_t>(n_units, 1));
+        R->d_bases.zero(s); R->d_nm.zero(s);
+        if (n_units)
+            hipLaunchKernelGGL(unpack_kernel, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, R->d_src.p, d_unit_off.p,
+                               static_cast<uint32_t>(2 * n_out), n_units, R->d_bases.p, R->d_nm.p);
+        LCTY_HIP(hipGetLastError());
+        R->h_len.resize(2 * n_out); R->h_src.resize(2 * n_out); R->h_off.resize(2 * n_out + 1);
+        R->h_src_stream.resize(2 * n_out); d_src_stream.download(R->h_src_stream.data(), 2 * n_out, s);
+        R->d_len.download(R->h_len.data(), 2 * n_out, s); R->d_src.download(R->h_src.data(), 2 * n_out, s); R->d_off.download(R->h_off.data(), 2 * n_out + 1, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+        S.ms_unpack = now_ms() - t0;
+        finish();
+    });
+}
+
+int32_t lcty_sample_reads_view(lcty_sample_reads* R, lcty_reads_host* view, const uint32_t** src_record, int32_t* paired) {
+    return guarded([&] {
+        if (!R || !view) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (!R->have_bases) {
+            R->ctx->activate();
+            hipStream_t s = R->ctx->stream;
+            R->h_bases.assign(2 * std::max<uint64_t>(R->n_units, 1), 0); R->h_nm.assign(std::max<uint64_t>(R->n_units, 1), 0);
+            if (R->n_units) {
+                LCTY_HIP(hipMemcpyAsync(R->h_bases.data(), R->d_bases.p, 8 * R->n_units, hipMemcpyDeviceToHost, s));
+                R->d_nm.download(R->h_nm.data(), R->n_units, s);
+                LCTY_HIP(hipStreamSynchronize(s));
+            }
+            R->have_bases = true;
+        }
+        memset(view, 0, sizeof(*view));
+        view->n_pairs = R->n;
+        view->mate_len = R->h_len.data(); view->mate_off = R->h_off.data(); view->bases2 = R->h_bases.data(); view->nmask = R->h_nm.data();
+        view->aln_off = R->zero_off.data(); view->cigar_off = R->zero_off.data();
+        if (src_record) *src_record = R->h_src_stream.data();
+        if (paired) *paired = R->paired ? 1 : 0;
+    });
+}
+
+int32_t lcty_sample_reads_recruit(lcty_targets* targets, lcty_sample_reads* R, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci) {
+    return guarded([&] {
+        if (!targets || !R || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        lcty_ctx* ctx = targets_ctx(targets);
+        if (ctx != R->ctx) fail(LCTY_ERR_INVALID_INPUT, "the targets and the reads belong to different contexts");
+        if (R->n == 0) return;
+        ctx->activate();
+        recruit_device_view(targets, R->n, R->h_len.data(), R->d_len.p, R->d_off.p, reinterpret_cast<const uint32_t*>(R->d_bases.p), R->d_nm.p, R->paired ? 1 : 0,
+                            max_out, out_cnt, out_loci);
+    });
+}
+
+int32_t lcty_sample_reads_write_recruited(lcty_sample_reads* R, lcty_fastx_writers* w, uint32_t max_out, const uint32_t* out_cnt,
+                                          const uint32_t* out_loci, uint64_t* n_written) {
+    return guarded([&] {
+        if (!R || !w || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        static const char CODES[] = "=ACMGRSVTWYHKDBN";
+        uint64_t written = 0;
+        std::string text;
+        for (uint64_t i = 0; i < R->n; i++) {
+            if (!out_cnt[i]) continue;
+            text.clear();
+            for (uint32_t e = 0; e < 2; e++) {                                   // BamRecord::write_to (fastx.rs:633-668), the mates one after the other
+                const uint32_t r = R->h_src[2 * i + e];
+                if (r == NONE32) continue;
+                const uint8_t* rec = R->slice + R->rec_off[r];
+                uint32_t l_seq; uint16_t n_cigar, flag;
+                memcpy(&n_cigar, rec + 16, 2); memcpy(&flag, rec + 18, 2); memcpy(&l_seq, rec + 20, 4);
+                const uint8_t* seq = rec + 36 + rec[12] + 4ull * n_cigar;
+                const uint8_t* qual = seq + (static_cast<uint64_t>(l_seq) + 1) / 2;
+                const bool reverse = (flag & 0x10) != 0, fasta = l_seq == 0 || qual[0] == 255;
+                text += fasta ? '>' : '@';
+                text += record_name(R->slice, R->rec_off[r]);
+                text += '\n';
+                for (uint32_t k = 0; k < l_seq; k++) {
+                    const uint32_t j = reverse ? l_seq - 1 - k : k;
+                    const char c = CODES[(seq[j >> 1] >> ((j & 1) ? 0 : 4)) & 15];
+                    // seq::complement_nt (seq/mod.rs:125-135): IUPAC codes become N ('=' panics there; N here)
+                    text += !reverse ? c : c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
+                }
+                text += '\n';
+                if (!fasta) {
+                    text += "+\n";
+                    for (uint32_t k = 0; k < l_seq; k++) text += static_cast<char>(qual[reverse ? l_seq - 1 - k : k] + 33);
+                    text += '\n';
+                }
+            }
+            for (uint32_t j = 0; j < std::min(out_cnt[i], max_out); j++) {
+                const uint32_t locus = out_loci[static_cast<size_t>(i) * max_out + j];
+                if (locus >= w->paths.size()) fail(LCTY_ERR_INVALID_INPUT, "record %llu is recruited to locus %u of %zu writers", static_cast<unsigned long long>(i), locus, w->paths.size());
+                w->put(locus, text);
+            }
+            written++;
+        }
+        if (n_written) *n_written = written;
+    });
+}
+
+void lcty_sample_reads_free(lcty_sample_reads* reads) { delete reads; }
+
+}  // extern "C"

@@ -265,6 +265,116 @@ class Fastx:
             pass
 
 
+def fetch_regions(tid, start, end, contig_len, padding, alt_contig_len=10_000_000, merge_distance=1000):
+    """lcty_recruit_fetch_regions (postprocess_targets): padded, short contigs added, sorted, merged -> (tid, start, end) arrays."""
+    tid, start, end = (np.ascontiguousarray(a, dtype=np.uint32) for a in (tid, start, end))
+    contig_len = np.ascontiguousarray(contig_len, dtype=np.uint32)
+    cap = len(tid) + len(contig_len)
+    out = [np.zeros(max(cap, 1), dtype=np.uint32) for _ in range(3)]
+    n = U32(0)
+    check(lib().lcty_recruit_fetch_regions(len(tid), tid.ctypes.data, start.ctypes.data, end.ctypes.data, len(contig_len), contig_len.ctypes.data,
+                                           padding, alt_contig_len, merge_distance, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, C.byref(n)))
+    return tuple(a[:n.value].copy() for a in out)
+
+
+def _regions(regions):
+    r = np.asarray(list(regions), dtype=np.uint32).reshape(-1, 3)
+    return tuple(np.ascontiguousarray(r[:, j]) for j in range(3))
+
+
+class SampleReads:
+    """lcty_sample_reads: the reads of one lcty_sample_bam_fetch, resident on the device."""
+
+    def __init__(self, handle, stats):
+        self._h, self.stats = handle, stats
+
+    def view(self):
+        """(cdefs.ReadsChunk of sequence fields, src_record [2 n] uint32, paired): copies."""
+        hs, src, paired = cdefs.ReadsHost(), VP(), C.c_int32(0)
+        check(lib().lcty_sample_reads_view(self._h, C.byref(hs), C.byref(src), C.byref(paired)))
+        n = int(hs.n_pairs)
+        def arr(ptr, count, dt):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(dt)), shape=(count,)).copy() if count else np.zeros(0, dtype=dt)
+        mate_off = arr(hs.mate_off, 2 * n + 1, C.c_uint64)
+        nb = int(mate_off[-1])
+        z = np.zeros(n + 1, dtype=np.uint64)
+        chunk = cdefs.ReadsChunk(arr(hs.mate_len, 2 * n, C.c_uint32), mate_off, arr(hs.bases2, max(nb // 16, 2), C.c_uint32),
+                                 arr(hs.nmask, max(nb // 32, 1), C.c_uint32), z, np.zeros(0, dtype=cdefs.ALN_REC_DTYPE), z, np.zeros(0, dtype=np.uint32))
+        return chunk, arr(src, 2 * n, C.c_uint32), bool(paired.value)
+
+    def recruit(self, targets, max_out=8):
+        n = self.stats["n_pairs"]
+        cnt = np.zeros(max(n, 1), dtype=np.uint32); loci = np.zeros(max(n, 1) * max_out, dtype=np.uint32)
+        check(lib().lcty_sample_reads_recruit(targets._h, self._h, max_out, cnt.ctypes.data, loci.ctypes.data))
+        return cnt[:n], loci.reshape(-1, max_out)[:n]
+
+    def write_recruited(self, writers, cnt, loci):
+        cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+        loci = np.ascontiguousarray(loci, dtype=np.uint32)
+        n = U64(0)
+        check(lib().lcty_sample_reads_write_recruited(self._h, writers._h, loci.shape[1], cnt.ctypes.data, loci.ctypes.data, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            lib().lcty_sample_reads_free(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SampleBam:
+    """lcty_sample_bam_*: a coordinate-sorted BAM file with its BAI index (`locityper genotype -a`)."""
+
+    def __init__(self, path, index_path=None):
+        self._h = VP()
+        check(lib().lcty_sample_bam_open(str(path).encode(), None if index_path is None else str(index_path).encode(), C.byref(self._h)))
+        n, names, noff, lens = U32(0), VP(), VP(), VP()
+        check(lib().lcty_sample_bam_contigs(self._h, C.byref(n), C.byref(names), C.byref(noff), C.byref(lens)))
+        n = n.value
+        off = np.ctypeslib.as_array(C.cast(noff, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        blob = C.string_at(names, int(off[-1])) if n else b""
+        self.contigs = [blob[int(off[i]):int(off[i + 1]) - 1].decode() for i in range(n)]
+        self.lengths = np.ctypeslib.as_array(C.cast(lens, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+
+    def is_paired(self):
+        p = C.c_int32(0)
+        check(lib().lcty_sample_bam_is_paired(self._h, C.byref(p)))
+        return bool(p.value)
+
+    def plan(self, regions, with_unmapped=False):
+        """-> (chunks [n][2] uint64 of virtual offsets, BGZF blocks they span)"""
+        t, s, e = _regions(regions)
+        n, blocks = U64(0), U64(0)
+        check(lib().lcty_sample_bam_plan(self._h, len(t), t.ctypes.data, s.ctypes.data, e.ctypes.data, int(with_unmapped), 0, C.byref(n), None, None, None))
+        beg = np.zeros(max(n.value, 1), dtype=np.uint64); end = np.zeros(max(n.value, 1), dtype=np.uint64)
+        check(lib().lcty_sample_bam_plan(self._h, len(t), t.ctypes.data, s.ctypes.data, e.ctypes.data, int(with_unmapped), len(beg), C.byref(n),
+                                         beg.ctypes.data, end.ctypes.data, C.byref(blocks)))
+        return np.stack([beg, end], axis=1)[:n.value], int(blocks.value)
+
+    def fetch(self, ctx, regions=(), with_unmapped=False, whole_file=False, paired=None):
+        t, s, e = _regions(regions)
+        h, st = VP(), cdefs.SampleBamStats()
+        check(lib().lcty_sample_bam_fetch(ctx._h, self._h, len(t), t.ctypes.data, s.ctypes.data, e.ctypes.data, int(with_unmapped), int(whole_file),
+                                          -1 if paired is None else int(paired), C.byref(h), C.byref(st)))
+        return SampleReads(h, st.as_dict())
+
+    def close(self):
+        if self._h:
+            lib().lcty_sample_bam_close(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FastxWriters:
     def __init__(self, paths):
         self._keep = [str(p).encode() for p in paths]
