@@ -10,8 +10,9 @@
 //
 // This is recruit_to_targets (src/command/genotype.rs:872-907) for an input given with `-a`. The padding of the regions is 1000, the
 // reference's value without an insert size distribution (genotype.rs:848-852), unless --padding says otherwise. Prints the stats of
-// the fetch as one JSON line. Build: see tests/test_gpu_sample_bam_example.py.
-//   ./recruit_bam -a sample.bam [-i index] -d DB/loci/<locus> [-d ...] [--bed FILE] [--padding N] [--alt-contig N] [--single|--paired] -o OUTDIR
+// the fetch as one JSON line. --inflate device inflates the BGZF blocks of the fetch on the device (knob "sample_bam_inflate";
+// default host: zlib). Build: see tests/test_gpu_sample_bam_example.py.
+//   ./recruit_bam -a sample.bam [-i index] -d DB/loci/<locus> [-d ...] [--bed FILE] [--padding N] [--alt-contig N] [--single|--paired] [--inflate host|device] -o OUTDIR
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -34,7 +35,7 @@ int main(int argc, char** argv) {
     std::string bam_path, index_path, bed, outdir;
     std::vector<std::string> dirs;
     uint32_t padding = 1000, alt_contig = 10000000;
-    int paired = -1;
+    int paired = -1, inflate_on_device = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -46,11 +47,16 @@ int main(int argc, char** argv) {
         else if (a == "--alt-contig") alt_contig = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--single") paired = 0;
         else if (a == "--paired") paired = 1;
+        else if (a == "--inflate") {
+            const std::string v = next();
+            if (v != "host" && v != "device") { std::fprintf(stderr, "--inflate takes host or device\n"); return 2; }
+            inflate_on_device = v == "device";
+        }
         else if (a == "-o") outdir = next();
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     if (bam_path.empty() || dirs.empty() || outdir.empty()) {
-        std::fprintf(stderr, "usage: recruit_bam -a sample.bam [-i index] -d DB/loci/<locus> [-d ...] [--bed FILE] [--padding N] [--alt-contig N] [--single|--paired] -o OUTDIR\n");
+        std::fprintf(stderr, "usage: recruit_bam -a sample.bam [-i index] -d DB/loci/<locus> [-d ...] [--bed FILE] [--padding N] [--alt-contig N] [--single|--paired] [--inflate host|device] -o OUTDIR\n");
         return 2;
     }
 
@@ -62,6 +68,7 @@ int main(int argc, char** argv) {
 
     lcty_ctx* ctx = nullptr;
     ok(lcty_ctx_create(0, &ctx), "lcty_ctx_create");
+    ok(lcty_ctx_set_knob(ctx, "sample_bam_inflate", inflate_on_device), "lcty_ctx_set_knob");
     lcty_recruit_params rp;
     ok(lcty_recruit_params_default(&rp, LCTY_TECH_ILLUMINA, paired), "lcty_recruit_params_default");
     lcty_targets* targets = nullptr;

@@ -262,7 +262,9 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       refuses a piece that reaches it with LCTY_ERR_UNSUPPORTED before it uploads anything);
  *       "sample_bam_hash_bits"   bits kept of the hash of a read name in lcty_sample_bam_fetch (default 64; fewer: collisions, which the
  *       comparison of the names must resolve);   "sample_bam_max_slice_bytes"   inflated bytes one lcty_sample_bam_fetch may take
- *       (default 2^33; a larger slice is LCTY_ERR_UNSUPPORTED naming this knob, before anything is uploaded).
+ *       (default 2^33; a larger slice is LCTY_ERR_UNSUPPORTED naming this knob, before anything is uploaded);
+ *       "sample_bam_inflate"   0 (default): lcty_sample_bam_fetch inflates its BGZF blocks with zlib on the host, 1: on the device
+ *       (lcty_bgzf_inflate's kernel, straight into the buffer the record kernel reads; any other value is LCTY_ERR_INVALID_INPUT).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -564,7 +566,7 @@ int32_t lcty_fastx_writers_close(lcty_fastx_writers* writers);
 /* ---- a sample's reads from a coordinate-sorted, indexed BAM file: `locityper genotype -a sample.bam` ---------------
  * recruit_to_targets (command/genotype.rs:872-907) -> create_fetch_targets / postprocess_targets (776-854) -> IndexedBamReader +
  * PairedBamReader (seq/fastx.rs:577-874) -> Targets::recruit. The index, the file access and the inflation of the selected BGZF
- * blocks are host code; the fetched slice becomes recruitable read pairs on the device (record filter, name pairing, unpacking
+ * blocks are host code (the inflation runs on the device with lcty_ctx_set_knob "sample_bam_inflate" 1); the fetched slice becomes recruitable read pairs on the device (record filter, name pairing, unpacking
  * with strand restore) and is recruited from there. The rules are restated index-free in tests/pyref_sample_bam.py.
  * lcty_sample_bam_open: bam::IndexedReader::from_path / from_path_and_index (genotype.rs:886-890): the header, and the BAI index
  *   at index_path, or else at path + ".bai", or else at path with ".bam" replaced by ".bai". A CSI index or a CRAM file is
@@ -618,6 +620,8 @@ typedef struct lcty_sample_bam_stats {
     uint64_t n_pairs, n_discarded;                /* paired: pairs made, kept records without a pair; single-end: reads, 0 */
     double   ms_read, ms_inflate, ms_walk;        /* host: pread, inflate (at most 16 threads), the chain of record lengths */
     double   ms_upload, ms_record, ms_pair, ms_unpack;   /* device, wall clock around each stage with its synchronisation */
+    /* with knob "sample_bam_inflate" 1: ms_inflate = upload of the compressed bytes + the inflate kernel + the copy of the slice back
+     * to the host, and ms_upload = what is still uploaded afterwards (record offsets, regions; the slice is on the device already) */
     double   ms_total;
 } lcty_sample_bam_stats;
 int32_t lcty_sample_bam_open(const char* path, const char* index_path, lcty_sample_bam** out);
@@ -638,6 +642,27 @@ int32_t lcty_sample_reads_recruit(lcty_targets* targets, lcty_sample_reads* read
 int32_t lcty_sample_reads_write_recruited(lcty_sample_reads* reads, lcty_fastx_writers* writers, uint32_t max_out, const uint32_t* out_cnt,
                                           const uint32_t* out_loci, uint64_t* n_written);
 void    lcty_sample_reads_free(lcty_sample_reads* reads);
+
+/* ---- BGZF blocks inflated on the device ------------------------------------------------------------------------------
+ * BGZF is the SAM specification's section 4.1: gzip members (RFC 1952) of at most 64 KB each, whose extra field holds the block's
+ * size and whose payload is a raw DEFLATE stream (RFC 1951) followed by CRC32 and ISIZE. No counterpart upstream: the reference reads
+ * BGZF through htslib, which inflates on the host.
+ * lcty_bgzf_inflate: comp holds whole BGZF blocks back to back (host memory); they are split as lcty_sample_bam_fetch splits them,
+ *   uploaded, inflated one wavefront per block, checked against their CRC32 and ISIZE on the device, and downloaded to out in
+ *   order. *out_len = the sum of the ISIZE fields, written whenever the headers parse; out == NULL only sizes. Blocks of ISIZE 0
+ *   (the end-of-file marker) are skipped. The decoder accepts exactly what zlib's inflate accepts (locityper_amd/csrc/
+ *   lcty_inflate.hpp states the rules; tests/test_bgzf_inflate_host.py holds it to zlib on the CPU). Bytes that are not a BGZF block at
+ *   some offset, or a block that says it inflates to more than 65 536 bytes: LCTY_ERR_INVALID_DATA naming the offset; out_cap below
+ *   *out_len: LCTY_ERR_INVALID_INPUT; a block the decoder refuses: LCTY_ERR_INVALID_DATA "corrupt BGZF block at offset N (class)",
+ *   the first one in input order. A block whose gzip FLG byte is not exactly 4 (FEXTRA alone, what every BAM writer sets) sends
+ *   the whole call through zlib on the host (ms_upload, ms_kernel, ms_download stay 0). stats may be NULL. */
+typedef struct lcty_bgzf_stats {
+    uint64_t n_blocks, bytes_in, bytes_out;       /* blocks, the EOF marker included; compressed bytes; inflated bytes */
+    double   ms_upload, ms_kernel, ms_download;   /* wall clock around each stage with its synchronisation */
+    double   ms_total;
+} lcty_bgzf_stats;
+int32_t lcty_bgzf_inflate(lcty_ctx* ctx, const uint8_t* comp, uint64_t n_comp, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
+                          lcty_bgzf_stats* stats);
 
 /* ---- candidate generation inside a locus (first slice) ----------------------------------------------------
  * The reference runs an external mapper per locus — strobealign -k 15 -N/-M min(25000, 4 x alleles) -S 0.5 --eqx for short

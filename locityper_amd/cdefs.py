@@ -664,6 +664,14 @@ class GenomeCountStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
 
 
+class BgzfStats(C.Structure):          # lcty_bgzf_stats
+    _fields_ = [(n, C.c_uint64) for n in ("n_blocks", "bytes_in", "bytes_out")] + \
+               [(n, C.c_double) for n in ("ms_upload", "ms_kernel", "ms_download", "ms_total")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SampleBamStats(C.Structure):     # lcty_sample_bam_stats
     _fields_ = [(n, C.c_uint64) for n in ("n_regions", "n_chunks", "file_bytes", "bytes_read", "blocks_inflated", "bytes_inflated", "records_walked",
                                           "records_primary", "records_kept", "n_pairs", "n_discarded")] + \

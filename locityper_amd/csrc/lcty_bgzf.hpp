@@ -1,5 +1,6 @@
-// lcty_bgzf.hpp — the BGZF writer (SAM specification, section 4.1): the one definition behind write_bam (lcty_bam.hip) and
-// lcty_io_write_bgzf (lcty_io.hip). Host code.
+// lcty_bgzf.hpp — BGZF (SAM specification, section 4.1), host code: the writer, the one definition behind write_bam (lcty_bam.hip)
+// and lcty_io_write_bgzf (lcty_io.hip); the split of a run of bytes into blocks (bgzf_block_size) and the two ways a list of blocks
+// is inflated: zlib on at most 16 threads (lcty_sample_bam.hip) and bgzf_inflate_kernel (lcty_inflate.hip).
 #pragma once
 
 #include <zlib.h>
@@ -62,5 +63,33 @@ struct BgzfOut {
         f = nullptr;
     }
 };
+
+// the size of the BGZF block that starts at p (n bytes available, at least 18 needed); 0 = not a BGZF block
+inline uint32_t bgzf_block_size(const uint8_t* p, size_t n) {
+    if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
+    const uint32_t xlen = p[10] | (p[11] << 8);
+    if (12 + xlen > n) return 0;
+    uint32_t bsize = 0;
+    for (size_t x = 12; x + 4 <= 12 + xlen;) {
+        const uint32_t slen = p[x + 2] | (p[x + 3] << 8);
+        if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen) bsize = (p[x + 4] | (p[x + 5] << 8)) + 1u;
+        x += 4 + slen;
+    }
+    return bsize < 12 + xlen + 8 ? 0 : bsize;
+}
+// of a block bgzf_block_size took: the bytes in front of its deflate stream when FLG is FEXTRA alone (what every BAM writer sets),
+// else 0: a name, a comment or a header CRC follow the extra field, and the block is zlib's
+inline uint32_t bgzf_plain_head(const uint8_t* p) { return p[3] == 4 ? 12u + (p[10] | (p[11] << 8)) : 0u; }
+
+// one block of a run: compressed size, inflated size (its last four bytes), its place in the output and in the compressed bytes,
+// the offset an error names, and bgzf_plain_head
+struct BgzfBlock { uint32_t csize, isize; uint64_t out_at; size_t in_at; uint64_t named_at; uint32_t head; };
+// every block with isize > 0 inflated to out + out_at by zlib, on at most 16 threads; a refused block is LCTY_ERR_INVALID_DATA
+// "corrupt BGZF block" with `what` in front (lcty_sample_bam.hip)
+void bgzf_inflate_host(const uint8_t* comp, const std::vector<BgzfBlock>& blocks, uint8_t* out, const char* what);
+// the same on the device, between device buffers, every block with its head > 0 (lcty_inflate.hip). The first refused block in
+// input order is LCTY_ERR_INVALID_DATA "<what>: corrupt BGZF block at offset <named_at> (<class>)". Synchronises s.
+void bgzf_inflate_device(lcty_ctx* ctx, const uint8_t* d_comp, uint64_t n_comp, const std::vector<BgzfBlock>& blocks, uint8_t* d_out,
+                         uint64_t n_out, hipStream_t s, const char* what);
 
 }  // namespace lcty

@@ -3,7 +3,8 @@
 //   src/seq/fastx.rs:577-673 BamRecord (read_from, write_to), 692-729 DirectBamReader, 732-803 IndexedBamReader, 805-874 PairedBamReader
 //   src/seq/interv.rs:74-77 add_padding, 232-247 merge
 // Host: the BAI index (SAM specification 5.2: bins -> chunks, the 16 kb linear index, the pseudo-bin 37450, n_no_coor), reg2bins, the
-// chunks of a call, pread of their byte ranges, inflation of their BGZF blocks into one page-locked buffer, the chain of record lengths.
+// chunks of a call, pread of their byte ranges, inflation of their BGZF blocks into one page-locked buffer (zlib, or with knob
+// "sample_bam_inflate" 1 bgzf_inflate_kernel of lcty_inflate.hip and a copy back), the chain of record lengths.
 // Device, on the raw bytes of that buffer (records lie at any byte: every field is taken from two aligned dwords, ld32):
 //   record_kernel   a lane per record: fixed fields, reference length of the CIGAR (a CIGAR of more than 64 operations is summed by the
 //                   whole wavefront), the region / flag tests, the hash of the name, `curr <= mate`, the error classes
@@ -27,6 +28,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "lcty_bgzf.hpp"
 #include "lcty_objects.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
@@ -272,19 +274,6 @@ __global__ __launch_bounds__(256) void unpack_kernel(const uint32_t* __restrict_
 
 // ---- host: BGZF by block, the header, the index ---------------------------------------------------------------------------------
 
-// the size of the BGZF block that starts at p (n bytes available, at least 18 needed); 0 = not a BGZF block
-static uint32_t bgzf_block_size(const uint8_t* p, size_t n) {
-    if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
-    const uint32_t xlen = p[10] | (p[11] << 8);
-    if (12 + xlen > n) return 0;
-    uint32_t bsize = 0;
-    for (size_t x = 12; x + 4 <= 12 + xlen;) {
-        const uint32_t slen = p[x + 2] | (p[x + 3] << 8);
-        if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen) bsize = (p[x + 4] | (p[x + 5] << 8)) + 1u;
-        x += 4 + slen;
-    }
-    return bsize < 12 + xlen + 8 ? 0 : bsize;
-}
 static void pread_all(int fd, void* buf, size_t n, uint64_t at, const char* path) {
     uint8_t* p = static_cast<uint8_t*>(buf);
     while (n) {
@@ -340,6 +329,30 @@ struct BgzfSerial {
     }
     uint64_t tell() { return at == data.size() ? next << 16 : (coff << 16) | at; }
 };
+
+void bgzf_inflate_host(const uint8_t* comp, const std::vector<BgzfBlock>& blocks, uint8_t* out, const char* path) {
+    const uint32_t n_threads = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>({blocks.size() / 64 + 1, 16, std::thread::hardware_concurrency()})));
+    std::vector<std::string> failed(n_threads);
+    auto work = [&](uint32_t id) {
+        z_stream zs;
+        memset(&zs, 0, sizeof(zs));
+        if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) { failed[id] = "zlib: inflateInit2"; return; }
+        try {
+            for (size_t k = id; k < blocks.size(); k += n_threads)
+                if (blocks[k].isize) inflate_block(zs, comp + blocks[k].in_at, blocks[k].csize, out + blocks[k].out_at, blocks[k].isize, path);
+        } catch (const Error& e) { failed[id] = e.what(); }
+        inflateEnd(&zs);
+    };
+    std::vector<std::thread> th;
+    std::vector<uint32_t> here;
+    for (uint32_t id = 1; id < n_threads; id++) {
+        try { th.emplace_back(work, id); } catch (const std::system_error&) { here.push_back(id); }
+    }
+    work(0);
+    for (uint32_t id : here) work(id);
+    for (auto& x : th) x.join();
+    for (const std::string& f : failed) if (!f.empty()) fail(LCTY_ERR_INVALID_DATA, "%s", f.c_str());
+}
 
 struct Chunk { uint64_t beg, end; };
 
@@ -467,7 +480,6 @@ std::vector<Chunk> plan_chunks(const lcty_sample_bam* b, uint32_t n, const uint3
 }
 
 // a chunk's blocks as they lie in the file
-struct Block { uint32_t csize, isize; uint64_t out_at; size_t in_at; };      // compressed size, inflated size, place in the slice, place in `comp`
 struct ChunkSpan { size_t first_block, n_blocks; uint64_t chain_beg, chain_end, span_end; };
 
 std::string record_name(const uint8_t* slice, uint64_t o) {
@@ -626,6 +638,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         if (hash_bits > 64) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_hash_bits = %lld (0 .. 64)", static_cast<long long>(hash_bits));
         const uint64_t hash_mask = hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1;
         const uint64_t cap = static_cast<uint64_t>(ctx->knob("sample_bam_max_slice_bytes", 1ll << 33));
+        if (ctx->knob("sample_bam_inflate", 0) > 1) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_inflate = %lld (0: host, 1: device)", static_cast<long long>(ctx->knob("sample_bam_inflate", 0)));
         lcty_sample_bam_stats S{};
         S.n_regions = n_regions; S.file_bytes = bam->fsize;
         const std::vector<Chunk> cs = plan_chunks(bam, n_regions, tid, start, end, with_unmapped != 0, whole_file != 0);
@@ -634,7 +647,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         // ---- the bytes of the chunks, split into blocks
         double t0 = now_ms();
         std::vector<uint8_t> comp;
-        std::vector<Block> blocks;
+        std::vector<BgzfBlock> blocks;
         std::vector<ChunkSpan> spans;
         uint64_t total = 0;
         for (const Chunk& c : cs) {
@@ -669,7 +682,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
                 if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
                 if (at == cbeg && (c.beg & 0xFFFF) > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index starts behind its block", path);
                 if (at == cend) { if (uend > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index ends behind its block", path); sp.chain_end = total + uend; end_seen = true; }
-                blocks.push_back(Block{csize, isize, total, in0 + static_cast<size_t>(at - cbeg)});
+                blocks.push_back(BgzfBlock{csize, isize, total, in0 + static_cast<size_t>(at - cbeg), at, bgzf_plain_head(p)});
                 total += isize; at += csize;
             }
             sp.n_blocks = blocks.size() - sp.first_block; sp.span_end = total;
@@ -690,29 +703,20 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&R->slice), total + SLICE_PAD, hipHostMallocDefault));
         memset(R->slice + total, 0, SLICE_PAD);
         t0 = now_ms();
-        {
-            const uint32_t n_threads = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>({blocks.size() / 64 + 1, 16, std::thread::hardware_concurrency()})));
-            std::vector<std::string> failed(n_threads);
-            auto work = [&](uint32_t id) {
-                z_stream zs;
-                memset(&zs, 0, sizeof(zs));
-                if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) { failed[id] = "zlib: inflateInit2"; return; }
-                try {
-                    for (size_t k = id; k < blocks.size(); k += n_threads)
-                        if (blocks[k].isize) inflate_block(zs, comp.data() + blocks[k].in_at, blocks[k].csize, R->slice + blocks[k].out_at, blocks[k].isize, path);
-                } catch (const Error& e) { failed[id] = e.what(); }
-                inflateEnd(&zs);
-            };
-            std::vector<std::thread> th;
-            std::vector<uint32_t> here;
-            for (uint32_t id = 1; id < n_threads; id++) {
-                try { th.emplace_back(work, id); } catch (const std::system_error&) { here.push_back(id); }
-            }
-            work(0);
-            for (uint32_t id : here) work(id);
-            for (auto& x : th) x.join();
-            for (const std::string& f : failed) if (!f.empty()) fail(LCTY_ERR_INVALID_DATA, "%s", f.c_str());
-        }
+        // knob "sample_bam_inflate" 1: on the device, straight into the buffer record_kernel reads, and from there to the page-locked
+        // slice for the walk and the writer; blocks with more in their gzip header than the extra field leave the call to zlib
+        bool on_device = ctx->knob("sample_bam_inflate", 0) == 1 && total > 0;
+        for (const BgzfBlock& b : blocks) if (b.isize && (!b.head || b.head + 8u > b.csize)) on_device = false;
+        DevBuf<uint8_t> d_raw;
+        if (on_device) {
+            DevBuf<uint8_t> d_comp;
+            d_comp.alloc(comp.size()); d_raw.alloc(total + SLICE_PAD);
+            d_comp.upload(comp.data(), comp.size(), s);
+            LCTY_HIP(hipMemsetAsync(d_raw.p + total, 0, SLICE_PAD, s));
+            bgzf_inflate_device(ctx, d_comp.p, comp.size(), blocks, d_raw.p, total, s, path);
+            d_raw.download(R->slice, total, s);
+            LCTY_HIP(hipStreamSynchronize(s));
+        } else bgzf_inflate_host(comp.data(), blocks, R->slice, path);
         S.ms_inflate = now_ms() - t0;
         std::vector<uint8_t>().swap(comp);
 
@@ -744,8 +748,8 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
 
         // ---- upload, record kernel
         t0 = now_ms();
-        DevBuf<uint8_t> d_raw; DevBuf<uint64_t> d_rec_off, d_hash; DevBuf<uint32_t> d_reg, d_info, d_kept, d_nprim; DevBuf<unsigned long long> d_err;
-        d_raw.alloc(total + SLICE_PAD); d_raw.upload(R->slice, total + SLICE_PAD, s);
+        DevBuf<uint64_t> d_rec_off, d_hash; DevBuf<uint32_t> d_reg, d_info, d_kept, d_nprim; DevBuf<unsigned long long> d_err;
+        if (!on_device) { d_raw.alloc(total + SLICE_PAD); d_raw.upload(R->slice, total + SLICE_PAD, s); }
         d_rec_off.alloc(n_rec); d_rec_off.upload(rec_off.data(), n_rec, s);
         std::vector<uint32_t> reg(3ull * std::max(n_regions, 1u), 0);
         for (uint32_t i = 0; i < n_regions; i++) { reg[i] = tid[i]; reg[n_regions + i] = start[i]; reg[2ull * n_regions + i] = end[i]; }

@@ -282,6 +282,21 @@ def _regions(regions):
     return tuple(np.ascontiguousarray(r[:, j]) for j in range(3))
 
 
+def bgzf_inflate(ctx, comp, out=None, size_only=False):
+    """lcty_bgzf_inflate: whole BGZF blocks back to back (bytes or a uint8 array) -> (the inflated bytes as a uint8 array, stats).
+    size_only: -> the inflated size, nothing is inflated. out: a uint8 array to inflate into (its size is the capacity given)."""
+    buf = np.frombuffer(comp, dtype=np.uint8) if isinstance(comp, (bytes, bytearray, memoryview)) else np.ascontiguousarray(comp, dtype=np.uint8)
+    n = U64(0)
+    check(lib().lcty_bgzf_inflate(ctx._h, buf.ctypes.data if len(buf) else None, len(buf), None, 0, C.byref(n), None))
+    if size_only:
+        return int(n.value)
+    if out is None:
+        out = np.empty(int(n.value), dtype=np.uint8)
+    st = cdefs.BgzfStats()
+    check(lib().lcty_bgzf_inflate(ctx._h, buf.ctypes.data if len(buf) else None, len(buf), out.ctypes.data if len(out) else None, len(out), C.byref(n), C.byref(st)))
+    return out[:int(n.value)], st.as_dict()
+
+
 class SampleReads:
     """lcty_sample_reads: the reads of one lcty_sample_bam_fetch, resident on the device."""
 

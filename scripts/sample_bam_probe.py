@@ -2,7 +2,8 @@
 indexed BAM file, a few hundred fetch regions with 30x of 100-base pairs inside them, foreign records between the regions that the index
 must skip, a share of pairs without coordinate. Synthetic, written with tests/pyref_sample_bam.
    python3 scripts/sample_bam_probe.py --make DIR [--regions 200] [--region-len 4000] [--unmapped 0.05] [--foreign 0.5]     (CPU only)
-   python3 scripts/sample_bam_probe.py DIR [--calls 5]
+   python3 scripts/sample_bam_probe.py DIR [--calls 5] [--inflate host|device]
+--inflate: knob "sample_bam_inflate" (host: zlib on at most 16 threads; device: bgzf_inflate_kernel).
 measure: the first call pays the allocations; one JSON line with the medians of the calls after it per stage (file read, inflate, walk,
 upload, record / pair / unpack stages, recruitment), and the same stages as serial loops in one host thread (numpy for the per-record
 tests, a dict for the pairing, one zlib stream), whose stream, pairs and discarded count must equal the library's."""
@@ -134,13 +135,14 @@ def host_serial(path, regions):
     return t, np.array(pairs, dtype=np.uint32).reshape(-1), discarded + len(waiting), len(stream)
 
 
-def measure(d, calls):
+def measure(d, calls, inflate):
     from locityper_amd import api, io as lio
     with open(os.path.join(d, "sample.pkl"), "rb") as f:
         meta = pickle.load(f)
     regions = meta["regions"]
     path = os.path.join(d, "sample.bam")
     ctx = api.Context(0)
+    ctx.set_knob("sample_bam_inflate", 1 if inflate == "device" else 0)
     rng = np.random.default_rng(1)
     gt = api.Targets(ctx, api.recruit_params(paired=True))
     alleles = [bytes(rng.choice(list(b"ACGT"), 20_000).astype(np.uint8)) for _ in range(4)]
@@ -166,7 +168,7 @@ def measure(d, calls):
     med = {k: (round(float(np.median([r[k] for r in rows])), 3) if k.startswith("ms_") else rows[-1][k]) for k in rows[0]}
     host_t, host_src, host_discarded, host_kept = host_serial(path, regions)
     equal = bool(np.array_equal(host_src, src)) and host_discarded == med["n_discarded"] and host_kept == med["records_kept"]
-    print(json.dumps(dict(records_in_file=meta["n_records"], calls=calls, device=med, host_one_thread={k: round(v, 3) for k, v in host_t.items()},
+    print(json.dumps(dict(records_in_file=meta["n_records"], calls=calls, inflate=inflate, device=med, host_one_thread={k: round(v, 3) for k, v in host_t.items()},
                           host_equals_device=equal)))
     if not equal:
         raise SystemExit("the host's stream or pairs differ from the library's")
@@ -181,8 +183,9 @@ if __name__ == "__main__":
     ap.add_argument("--unmapped", type=float, default=0.05)
     ap.add_argument("--foreign", type=float, default=0.5)
     ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--inflate", choices=("host", "device"), default="host")
     a = ap.parse_args()
     if a.make:
         make(a.dir, a.regions, a.region_len, a.unmapped, a.foreign)
     else:
-        measure(a.dir, a.calls)
+        measure(a.dir, a.calls, a.inflate)
