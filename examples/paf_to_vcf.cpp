@@ -2,14 +2,15 @@
 // C ABI, files in, files out:
 //
 //   paf_to_vcf -i DIR -r REF_HAP [args]
-//   paf_to_vcf -p PAF -f FASTA -r REF_HAP [-d FILE|auto|none] -o MERGED [SEPARATE] [-R auto|none|chrom:start-end|BED]
+//   paf_to_vcf -p PAF -f FASTA -r REF_HAP [-d FILE|auto|none] -o MERGED [SEPARATE] [-R auto|none|chrom:start-end|BED] [--deflate host|device]
 //
 //   -i DIR        DB/loci/<locus>/: unless given otherwise, -p = the first of haplotypes.paf.br, .gz, plain that exists, -f =
 //                 DIR/haplotypes.fa.gz, -o = DIR/haplotypes.vcf.gz
 //   -d            discarded_haplotypes.txt; auto (default) = the one beside the FASTA when it exists
 //   -R            the region the positions are shifted to; auto (default) = ref.bed beside the FASTA when it exists, none = the
 //                 reference haplotype's own coordinates. `chrom:start` alone, which panics in the reference, is an input error here.
-//   outputs that end in .gz are BGZF (lcty_io_write_bgzf), others plain; both are written under a temporary name and renamed
+//   outputs that end in .gz are BGZF (lcty_io_write_bgzf; with --deflate device lcty_io_write_bgzf_device: the same inflated bytes,
+//                 deflated on the device), others plain; both are written under a temporary name and renamed
 //
 //   (lcty_fasta_read, lcty_paf_read, lcty_io_read_file, lcty_paf_to_vcf)
 // Prints one JSON line with the counts and the per-stage milliseconds. Build: see tests/test_gpu_pafvcf_example.py.
@@ -81,9 +82,12 @@ static Region load_region(const std::string& s, const std::string& fasta) {
     return r;
 }
 
+static lcty_ctx* deflate_on = nullptr;                                  // --deflate device: the context whose device deflates the .gz outputs
+
 static void write_out(const std::string& path, const char* data, uint64_t len) {
     const std::string tmp = parent(path) + "/." + path.substr(path.rfind('/') == std::string::npos ? 0 : path.rfind('/') + 1) + "." + std::to_string(getpid()) + ".tmp";
-    if (ends_with(path, ".gz")) ok(lcty_io_write_bgzf(tmp.c_str(), reinterpret_cast<const uint8_t*>(data), len), tmp.c_str());
+    if (ends_with(path, ".gz") && deflate_on) ok(lcty_io_write_bgzf_device(deflate_on, tmp.c_str(), reinterpret_cast<const uint8_t*>(data), len, nullptr), tmp.c_str());
+    else if (ends_with(path, ".gz")) ok(lcty_io_write_bgzf(tmp.c_str(), reinterpret_cast<const uint8_t*>(data), len), tmp.c_str());
     else {
         std::ofstream out(tmp, std::ios::binary);
         out.write(data, static_cast<std::streamsize>(len));
@@ -94,7 +98,7 @@ static void write_out(const std::string& path, const char* data, uint64_t len) {
 }
 
 int main(int argc, char** argv) {
-    std::string input, paf, fasta, disc = "auto", merged, separate, ref_hap, region = "auto";
+    std::string input, paf, fasta, disc = "auto", merged, separate, ref_hap, region = "auto", deflate = "host";
     bool bad = argc < 2;
     for (int i = 1; i < argc && !bad; i++) {
         const std::string a = argv[i];
@@ -105,6 +109,7 @@ int main(int argc, char** argv) {
         else if (a == "-d" || a == "--discarded") value(&disc);
         else if (a == "-r" || a == "--ref-hap") value(&ref_hap);
         else if (a == "-R" || a == "--region") value(&region);
+        else if (a == "--deflate") value(&deflate);
         else if (a == "-o" || a == "--output") {
             value(&merged);
             if (i + 1 < argc && argv[i + 1][0] != '-') separate = argv[++i];
@@ -115,9 +120,9 @@ int main(int argc, char** argv) {
         if (fasta.empty()) fasta = input + "/haplotypes.fa.gz";
         if (merged.empty()) merged = input + "/haplotypes.vcf.gz";
     }
-    if (bad || paf.empty() || fasta.empty() || merged.empty() || ref_hap.empty()) {
+    if (bad || paf.empty() || fasta.empty() || merged.empty() || ref_hap.empty() || (deflate != "host" && deflate != "device")) {
         std::fprintf(stderr, "usage: paf_to_vcf -i DIR -r REF_HAP [args]\n"
-                             "       paf_to_vcf -p PAF -f FASTA -r REF_HAP [-d FILE|auto|none] -o MERGED [SEPARATE] [-R auto|none|chrom:start-end|BED]\n");
+                             "       paf_to_vcf -p PAF -f FASTA -r REF_HAP [-d FILE|auto|none] -o MERGED [SEPARATE] [-R auto|none|chrom:start-end|BED] [--deflate host|device]\n");
         return 2;
     }
     // the haplotypes and their alignments
@@ -147,14 +152,15 @@ int main(int argc, char** argv) {
     ok(lcty_paf_to_vcf(ctx, n, names.data(), seqs.data(), off.data(), reinterpret_cast<const char*>(disc_text), disc_len, ref_hap.c_str(), n_entries, id1.data(),
                        id2.data(), cigar_off.data(), cigar.data(), reg.given ? reg.chrom.c_str() : nullptr, reg.start, reg.end, separate.empty() ? 0 : 1, &out),
        "paf-vcf");
-    lcty_ctx_destroy(ctx);
     lcty_io_free(disc_text);
+    if (deflate == "device") deflate_on = ctx;
     const lcty_pafvcf_stats& st = out.stats;
     if (st.warn_bits & LCTY_PAFVCF_WARN_PRUNED) std::fprintf(stderr, "Haplotypes were previously pruned (~ for some lines), VCF will be inaccurate\n");
     if (st.warn_bits & LCTY_PAFVCF_WARN_REF_SUFFIX) std::fprintf(stderr, "Reference name %s has haplotype suffix; will keep it in the VCF file\n", ref_hap.c_str());
     if (st.n_missing) std::fprintf(stderr, "    %u / %u haplotype-reference alignments are missing\n", st.n_missing, n);
     write_out(merged, out.merged, out.merged_len);
     if (!separate.empty()) write_out(separate, out.separate, out.separate_len);
+    lcty_ctx_destroy(ctx);
     std::printf("{\"haplotypes\": %u, \"samples\": %u, \"entries\": %llu, \"missing\": %u, \"bad_len\": %u, \"variants\": %llu, \"shifted\": %llu, \"unique\": %llu, "
                 "\"merged\": %llu, \"lines_merged\": %llu, \"lines_separate\": %llu, \"merged_bytes\": %llu, \"separate_bytes\": %llu, \"warn_bits\": %u, "
                 "\"ms\": {\"upload\": %.3f, \"variants\": %.3f, \"ranges\": %.3f, \"table\": %.3f, \"text\": %.3f, \"total\": %.3f}}\n",

@@ -265,6 +265,11 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       (default 2^33; a larger slice is LCTY_ERR_UNSUPPORTED naming this knob, before anything is uploaded);
  *       "sample_bam_inflate"   0 (default): lcty_sample_bam_fetch inflates its BGZF blocks with zlib on the host, 1: on the device
  *       (lcty_bgzf_inflate's kernel, straight into the buffer the record kernel reads; any other value is LCTY_ERR_INVALID_INPUT).
+ *       "bgzf_deflate"   0 (default): lcty_write_bam deflates its BGZF blocks with zlib on the host as the records come, 1: it keeps the
+ *       stream and deflates it on the device when the file is closed (lcty_bgzf_deflate; the inflated bytes of the BAM and what its
+ *       index points at are the same, the deflate bytes differ); any other value, a negative one included, is refused by this call with
+ *       LCTY_ERR_INVALID_INPUT naming the knob;   "bgzf_deflate_max_bytes"   input bytes one slice of lcty_bgzf_deflate takes to the
+ *       device (default 256 MB; the output does not depend on it; below 0xff00, one block, lcty_bgzf_deflate is LCTY_ERR_INVALID_INPUT).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -663,6 +668,30 @@ typedef struct lcty_bgzf_stats {
 } lcty_bgzf_stats;
 int32_t lcty_bgzf_inflate(lcty_ctx* ctx, const uint8_t* comp, uint64_t n_comp, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
                           lcty_bgzf_stats* stats);
+
+/* ---- BGZF blocks deflated on the device -------------------------------------------------------------------------------
+ * The writing half of the section above. No counterpart upstream: htslib deflates on the host (bam::Writer, bgzf::Writer).
+ * lcty_bgzf_deflate: data (host memory) is cut every 0xff00 bytes, where lcty_io_write_bgzf and lcty_write_bam cut it, uploaded,
+ *   deflated one wavefront per block (locityper_amd/csrc/lcty_deflate.hpp: hash matches in groups of 64 positions, a greedy parse, and
+ *   the smallest of the stored, fixed and dynamic forms; tests/test_bgzf_deflate_host.py holds the same text to zlib's inflate on the
+ *   CPU), given the 18-byte header (FLG 4, the BC subfield) and the CRC32 / ISIZE trailer, packed back to back on the device and
+ *   downloaded to out. with_eof appends the 28-byte end-of-file marker. *out_len = the bytes written. block_off: NULL, or
+ *   ceil(len / 0xff00) + 1 offsets in out: the start of every data block, and the end of the last. The bytes depend on `data` alone,
+ *   not on the device, the grid or knob "bgzf_deflate_max_bytes" (the slice an input above it is processed in). len == 0 gives the
+ *   marker alone, or nothing. They are not zlib's bytes: any inflater gives `data` back.
+ *   out_cap is asked for up front, the exact size not being known: below lcty_bgzf_deflate_bound (a stored block takes n + 31 bytes)
+ *   the call is LCTY_ERR_INVALID_INPUT, as are null arguments and a slice knob below one block. stats may be NULL.
+ * lcty_io_write_bgzf_device: lcty_io_write_bgzf through lcty_bgzf_deflate: the same blocks of inflated bytes and the marker. */
+typedef struct lcty_bgzf_deflate_stats {
+    uint64_t n_blocks, bytes_in, bytes_out;      /* data blocks (EOF marker not counted); raw bytes; file bytes */
+    uint64_t n_stored, n_fixed, n_dynamic;       /* blocks by the form chosen */
+    double   ms_upload, ms_kernel, ms_download, ms_total;
+} lcty_bgzf_deflate_stats;
+uint64_t lcty_bgzf_deflate_bound(uint64_t len, int32_t with_eof);   /* len + 31 * ceil(len / 0xff00) + 28 * with_eof */
+int32_t  lcty_bgzf_deflate(lcty_ctx* ctx, const uint8_t* data, uint64_t len, int32_t with_eof, uint8_t* out, uint64_t out_cap,
+                           uint64_t* out_len, uint64_t* block_off /* NULL or ceil(len/0xff00)+1 compressed offsets */,
+                           lcty_bgzf_deflate_stats* stats);
+int32_t  lcty_io_write_bgzf_device(lcty_ctx* ctx, const char* path, const uint8_t* data, uint64_t len, lcty_bgzf_deflate_stats* stats);
 
 /* ---- candidate generation inside a locus (first slice) ----------------------------------------------------
  * The reference runs an external mapper per locus — strobealign -k 15 -N/-M min(25000, 4 x alleles) -S 0.5 --eqx for short

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats, BgzfDeflateStats
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -169,6 +169,9 @@ SIGNATURES = {
     "lcty_sample_reads_write_recruited": (I32, [VP, VP, U32, VP, VP, P(U64)]),
     "lcty_sample_reads_free": (None, [VP]),
     "lcty_bgzf_inflate": (I32, [VP, VP, U64, VP, U64, P(U64), P(BgzfStats)]),
+    "lcty_bgzf_deflate_bound": (U64, [U64, I32]),
+    "lcty_bgzf_deflate": (I32, [VP, VP, U64, I32, VP, U64, P(U64), VP, P(BgzfDeflateStats)]),
+    "lcty_io_write_bgzf_device": (I32, [VP, C.c_char_p, VP, U64, P(BgzfDeflateStats)]),
     "lcty_locus_depth_table": (I32, [VP, P(U32), VP]),
     "lcty_solver_default": (I32, [P(Solver), I32]),
     "lcty_chain_seeds": (I32, [U64, U64, VP]),

@@ -672,6 +672,14 @@ class BgzfStats(C.Structure):          # lcty_bgzf_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BgzfDeflateStats(C.Structure):   # lcty_bgzf_deflate_stats
+    _fields_ = [(n, C.c_uint64) for n in ("n_blocks", "bytes_in", "bytes_out", "n_stored", "n_fixed", "n_dynamic")] + \
+               [(n, C.c_double) for n in ("ms_upload", "ms_kernel", "ms_download", "ms_total")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SampleBamStats(C.Structure):     # lcty_sample_bam_stats
     _fields_ = [(n, C.c_uint64) for n in ("n_regions", "n_chunks", "file_bytes", "bytes_read", "blocks_inflated", "bytes_inflated", "records_walked",
                                           "records_primary", "records_kept", "n_pairs", "n_discarded")] + \

@@ -48,6 +48,7 @@ int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value) {
                                             "score_lean_keep", "score_lean_two", "queue_early_head", "db_chunk_cols", "basis_batch_words",
                                             "align_batch_pairs", "align_hash_bits", "align_dp_cells", "align_match_budget", "align_cigar_store_mb", "pafvcf_hash_bits", "pafvcf_table_mb",
                                             "genome_max_bases", "sample_bam_hash_bits", "sample_bam_max_slice_bytes", "sample_bam_inflate",
+                                            "bgzf_deflate", "bgzf_deflate_max_bytes",
 #ifdef LCTY_DIAG
                                             // the developer build (make DIAG=1): traces, in-kernel timing, kernel forms under measurement
                                             "solve_stats", "queue_trace", "map_trace", "exact_trace", "solve_greedy_form", "solve_anneal_timing", "score_timing",
@@ -57,6 +58,8 @@ int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value) {
         bool ok = false;
         for (const char* const* k = known; *k; k++) ok |= strcmp(*k, name) == 0;
         if (!ok) fail(LCTY_ERR_INVALID_INPUT, "unknown knob '%s'", name);
+        // a route, not a limit: 0 is its default, and no other value (a negative one included) means anything
+        if (strcmp(name, "bgzf_deflate") == 0 && value != 0 && value != 1) fail(LCTY_ERR_INVALID_INPUT, "bgzf_deflate = %lld (0: host, 1: device)", static_cast<long long>(value));
         if (value < 0) ctx->knobs.erase(name); else ctx->knobs[name] = value;
     });
 }

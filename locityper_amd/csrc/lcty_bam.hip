@@ -301,7 +301,9 @@ int32_t lcty_write_bam(const char* path, lcty_reads* reads, const lcty_reads_hos
         });
 
         // ---- the file
-        BgzfOut out(path);
+        // knob "bgzf_deflate" 1: the stream is kept, deflated on the device when the file is closed, and the index translated behind it
+        // (lcty_ctx_set_knob takes 0 and 1 only)
+        BgzfOut out(path, reads->ctx->knob("bgzf_deflate", 0) == 1 ? reads->ctx : nullptr);
         std::vector<uint8_t> buf;
         buf.insert(buf.end(), {'B', 'A', 'M', 1});
         put<uint32_t>(buf, static_cast<uint32_t>(text.size())); buf.insert(buf.end(), text.begin(), text.end());
@@ -373,6 +375,11 @@ int32_t lcty_write_bam(const char* path, lcty_reads* reads, const lcty_reads_hos
             } else n_no_coor++;
         }
         out.close();
+        for (RefIndex& ri : index) {                                    // the virtual offsets of a deflated-at-close file become final here
+            for (auto& b : ri.bins) for (auto& c : b.second) { c.first = out.final(c.first); c.second = out.final(c.second); }
+            for (uint64_t& v : ri.linear) if (v) v = out.final(v);
+            if (ri.n_mapped + ri.n_unmapped) { ri.off_beg = out.final(ri.off_beg); ri.off_end = out.final(ri.off_end); }
+        }
         // bam::index::build(.., Bai, ..) (bam.rs:410): magic, per reference {bins (+ the 37450 pseudo-bin), linear index}, n_no_coor
         {
             std::vector<uint8_t> bai;

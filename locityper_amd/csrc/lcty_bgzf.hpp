@@ -1,6 +1,7 @@
 // lcty_bgzf.hpp — BGZF (SAM specification, section 4.1), host code: the writer, the one definition behind write_bam (lcty_bam.hip)
 // and lcty_io_write_bgzf (lcty_io.hip); the split of a run of bytes into blocks (bgzf_block_size) and the two ways a list of blocks
-// is inflated: zlib on at most 16 threads (lcty_sample_bam.hip) and bgzf_inflate_kernel (lcty_inflate.hip).
+// is inflated: zlib on at most 16 threads (lcty_sample_bam.hip) and bgzf_inflate_kernel (lcty_inflate.hip). The writer either deflates
+// block by block with zlib as the bytes come, or keeps them and deflates them all on the device when it is closed (lcty_deflate.hip).
 #pragma once
 
 #include <zlib.h>
@@ -13,18 +14,32 @@
 
 namespace lcty {
 
+// len bytes as BGZF blocks of at most 0xff00 bytes take at most this many bytes (a stored block: 18 + 5 + n + 8), the end-of-file marker 28
+uint64_t bgzf_deflate_bound(uint64_t len, bool with_eof);
+// lcty_bgzf_deflate behind its argument checks (lcty_deflate.hip): data (host) cut every 0xff00 bytes, deflated on the device, packed and
+// downloaded to out; block_off (may be null): the offset in out of every block and of the end of the last. Synchronises the context's stream.
+void bgzf_deflate_device(lcty_ctx* ctx, const uint8_t* data, uint64_t len, bool with_eof, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
+                         uint64_t* block_off, lcty_bgzf_deflate_stats* stats);
+
 // BGZF: gzip members of at most 64 KB with the BC extra field; virtual offset = start of the block << 16 | offset inside it
 struct BgzfOut {
     FILE* f = nullptr;
     std::vector<uint8_t> block;
     uint64_t coff = 0;
-    explicit BgzfOut(const char* path) {
+    // on_device (a context, or null): the bytes are kept in `all` and deflated by one bgzf_deflate_device in close(). Until then tell()
+    // is provisional, block ordinal << 16 | offset inside it, which grows with the final offset and maps one to one: final() translates
+    // after close().
+    lcty_ctx* on_device = nullptr;
+    std::vector<uint8_t> all;
+    std::vector<uint64_t> block_off;
+    explicit BgzfOut(const char* path, lcty_ctx* device = nullptr) : on_device(device) {
         f = fopen(path, "wb");
         if (!f) fail(LCTY_ERR_INVALID_INPUT, "cannot create %s", path);
         block.reserve(0xff00);
     }
     ~BgzfOut() { if (f) fclose(f); }
-    uint64_t tell() const { return (coff << 16) | block.size(); }
+    uint64_t tell() const { return on_device ? ((all.size() / 0xff00) << 16) | (all.size() % 0xff00) : (coff << 16) | block.size(); }
+    uint64_t final(uint64_t v) const { return on_device ? (block_off[std::min<size_t>(v >> 16, block_off.size() - 1)] << 16) | (v & 0xffff) : v; }
     void flush() {
         uint8_t out[0x10000];
         z_stream zs;
@@ -49,6 +64,7 @@ struct BgzfOut {
     }
     void write(const void* p, size_t n) {
         const uint8_t* b = static_cast<const uint8_t*>(p);
+        if (on_device) { all.insert(all.end(), b, b + n); return; }
         while (n) {
             const size_t take = std::min<size_t>(n, 0xff00 - block.size());
             block.insert(block.end(), b, b + take);
@@ -57,6 +73,17 @@ struct BgzfOut {
         }
     }
     void close() {
+        if (on_device) {
+            std::vector<uint8_t> out(bgzf_deflate_bound(all.size(), true));
+            block_off.assign(all.size() / 0xff00 + 2, 0);                   // at least ceil(size / 0xff00) + 1
+            uint64_t n = 0;
+            bgzf_deflate_device(on_device, all.data(), all.size(), true, out.data(), out.size(), &n, block_off.data(), nullptr);
+            block_off.resize((all.size() + 0xff00 - 1) / 0xff00 + 1);
+            const bool bad = fwrite(out.data(), 1, n, f) != n;
+            if (fclose(f) != 0 || bad) { f = nullptr; fail(LCTY_ERR_RUNTIME, "write error"); }
+            f = nullptr;
+            return;
+        }
         if (!block.empty()) flush();
         flush();                                                            // the empty block that marks the end of a BGZF file
         if (fclose(f) != 0) { f = nullptr; fail(LCTY_ERR_RUNTIME, "write error"); }

@@ -234,10 +234,15 @@ struct lcty_ctx {
     // scratch above: before the solver stages size their workspace, and by lcty_ctx_trim.
     std::shared_ptr<void> map_scratch;
     std::mutex map_mutex;             // one lcty_reads_map_append at a time per context: its buffers are the context's
+    // Device buffers of lcty_bgzf_deflate (lcty_deflate.hip: a slice of input, the blocks' slots, the packed output, the tokens of the
+    // blocks in flight), kept from call to call and released with the buffers above.
+    std::shared_ptr<void> deflate_scratch;
+    std::mutex deflate_mutex;         // one lcty_bgzf_deflate at a time per context
     std::mutex scratch_mutex;
     void release_transfer_scratch() {
         std::lock_guard<std::mutex> g(scratch_mutex);
         map_scratch.reset();
+        deflate_scratch.reset();
         if (transfer_scratch.n) transfer_scratch.release();
         if (transfer_recs.n) transfer_recs.release();
         if (transfer_words.n) transfer_words.release();

@@ -19,6 +19,8 @@
 
 #include <cstdint>
 
+#include "lcty_crc.hpp"
+
 #ifdef __HIPCC__
 #define LCTY_INF_FN __device__ __forceinline__
 #else
@@ -53,9 +55,8 @@ inline const char* class_name(uint32_t c) {
     return c < N_CLASSES ? names[c] : "unknown";
 }
 
-constexpr uint32_t RING = 32768, WIN = 1024, WIN_CHUNK = 256, MAX_ISIZE = 65536, CRC_SHARES = 64;
+constexpr uint32_t RING = 32768, WIN = 1024, WIN_CHUNK = 256, MAX_ISIZE = 65536;
 constexpr uint32_t LIT_BITS = 10, DIST_BITS = 8, MAX_CODE = 15, MAX_LENS = 352;
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
 
 // one canonical Huffman code: a primary table over the next PB bits (symbol | length << 9, 0 = not there) and, for longer codes and
 // for the codes nobody has, the counts per length with the symbols in code order
@@ -69,30 +70,8 @@ struct State {
     uint32_t crc_tab[256];
 };
 
-// ---- CRC-32 (RFC 1952 8): the byte table, and the product / power of x modulo P that joins the CRCs of neighbouring shares -----------
-LCTY_INF_FN uint32_t crc_table_entry(uint32_t i) {
-    uint32_t c = i;
-    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ CRC_POLY : c >> 1;
-    return c;
-}
-// a * b modulo P, bit-reflected (bit 31 is x^0)
-LCTY_INF_FN uint32_t crc_mul(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int k = 0; k < 32; k++) {
-        if (a & (0x80000000u >> k)) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-// x^(8 n) modulo P
-LCTY_INF_FN uint32_t crc_xpow8(uint32_t n) {
-    uint32_t p = 0x80000000u, base = 0x00800000u;            // 1, x^8
-    for (int k = 0; k < 32; k++) {
-        if ((n >> k) & 1u) p = crc_mul(p, base);
-        base = crc_mul(base, base);
-    }
-    return p;
-}
+// ---- CRC-32 (lcty_crc.hpp: the byte table, crc_mul and crc_xpow8 that join the CRCs of neighbouring shares), over the ring ----------------
+using crc::CRC_SHARES; using crc::crc_mul; using crc::crc_table_entry; using crc::crc_xpow8;
 // what share `share` of CRC_SHARES adds to the register of the bytes [from, to) of the ring: the register of its own contiguous
 // bytes from 0, moved over the bytes behind it
 LCTY_INF_FN uint32_t crc_share(const State* st, uint32_t from, uint32_t to, uint32_t share) {

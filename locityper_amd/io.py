@@ -297,6 +297,28 @@ def bgzf_inflate(ctx, comp, out=None, size_only=False):
     return out[:int(n.value)], st.as_dict()
 
 
+def bgzf_deflate(ctx, data, with_eof=True, out_cap=None):
+    """lcty_bgzf_deflate: bytes or a uint8 array -> (the BGZF file's bytes as a uint8 array, block_off: the offset of every data block and
+    the end of the last, stats). out_cap: the capacity given instead of lcty_bgzf_deflate_bound."""
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    cap = int(lib().lcty_bgzf_deflate_bound(len(buf), 1 if with_eof else 0)) if out_cap is None else int(out_cap)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    off = np.zeros((len(buf) + 0xff00 - 1) // 0xff00 + 1, dtype=np.uint64)
+    n = U64(0)
+    st = cdefs.BgzfDeflateStats()
+    check(lib().lcty_bgzf_deflate(ctx._h, buf.ctypes.data if len(buf) else None, len(buf), 1 if with_eof else 0, out.ctypes.data, cap, C.byref(n),
+                                  off.ctypes.data, C.byref(st)))
+    return out[:int(n.value)], off, st.as_dict()
+
+
+def write_bgzf_device(ctx, path, data):
+    """lcty_io_write_bgzf_device: write_bgzf with the blocks deflated on the device -> stats"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    st = cdefs.BgzfDeflateStats()
+    check(lib().lcty_io_write_bgzf_device(ctx._h, str(path).encode(), buf.ctypes.data if len(buf) else None, len(buf), C.byref(st)))
+    return st.as_dict()
+
+
 class SampleReads:
     """lcty_sample_reads: the reads of one lcty_sample_bam_fetch, resident on the device."""
 

@@ -78,6 +78,22 @@ pub struct lcty_depth_tables {
     pub id: u64,
 }
 
+/// `lcty_bgzf_deflate_stats`: what a call of `lcty_bgzf_deflate` did.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lcty_bgzf_deflate_stats {
+    pub n_blocks: u64,
+    pub bytes_in: u64,
+    pub bytes_out: u64,
+    pub n_stored: u64,
+    pub n_fixed: u64,
+    pub n_dynamic: u64,
+    pub ms_upload: f64,
+    pub ms_kernel: f64,
+    pub ms_download: f64,
+    pub ms_total: f64,
+}
+
 extern "C" {
     pub fn lcty_last_error() -> *const c_char;
     pub fn lcty_device_count() -> i32;
@@ -103,4 +119,10 @@ extern "C" {
     pub fn lcty_genome_fetch(genome: *const lcty_genome, contig_name: *const c_char, start: u64, end: u64, out: *mut u8) -> i32;
     pub fn lcty_genome_kmer_counts(genome: *const lcty_genome, k: u32, counter_bytes: u32, n_seqs: u32, seqs: *const u8,
         seq_off: *const u64, counts: *mut u16, cnt_off: *mut u64, stats: *mut lcty_genome_count_stats) -> i32;
+    // BGZF blocks deflated on the device: bam::Writer / bgzf::Writer -> lcty_bgzf_deflate, lcty_io_write_bgzf_device
+    pub fn lcty_bgzf_deflate_bound(len: u64, with_eof: i32) -> u64;
+    pub fn lcty_bgzf_deflate(ctx: *mut lcty_ctx, data: *const u8, len: u64, with_eof: i32, out: *mut u8, out_cap: u64, out_len: *mut u64,
+        block_off: *mut u64, stats: *mut lcty_bgzf_deflate_stats) -> i32;
+    pub fn lcty_io_write_bgzf_device(ctx: *mut lcty_ctx, path: *const c_char, data: *const u8, len: u64,
+        stats: *mut lcty_bgzf_deflate_stats) -> i32;
 }
