@@ -8,10 +8,14 @@
 //                              the number of counts)
 //   <chr:start-end>            the background interval, 1-based inclusive as samtools writes it
 //   <tech>                     illumina | hifi | pacbio | ont
+//   --fetch [index_path]       optional, last: <bg.bam> is the sample's whole, coordinate-sorted BAM file with its BAI index
+//                              (<bg.bam>.bai unless given) and the region's records are read through the index
+//                                                                                           (lcty_sample_bam_open, lcty_bg_reads_fetch)
 //        -> lcty_bg_estimate (estimate_bg_distrs with `-a`, preproc.rs:1157-1192) -> lcty_bg_to_json
 //   <out_dir>/distr.gz         BgDistr as JSON                                              (lcty_io_write_gz)
 //
-// Build: see tests/test_gpu_bg_example.py.   ./estimate_bg <bg.bam> <padded.fa> <padded_kmer_counts.u16> <chr:start-end> <tech> <out_dir>
+// Build: see tests/test_gpu_bg_example.py.
+//   ./estimate_bg <bg.bam> <padded.fa> <padded_kmer_counts.u16> <chr:start-end> <tech> <out_dir> [--fetch [index_path]]
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -28,10 +32,12 @@ static void ok(int32_t rc, const char* what) {
 }
 
 int main(int argc, char** argv) {
-    if (argc != 7) {
-        std::fprintf(stderr, "usage: estimate_bg <bg.bam> <padded.fa> <padded_kmer_counts.u16> <chr:start-end> <tech> <out_dir>\n");
+    const bool fetch = argc >= 8 && std::strcmp(argv[7], "--fetch") == 0;
+    if (!(argc == 7 || (fetch && argc <= 9))) {
+        std::fprintf(stderr, "usage: estimate_bg <bg.bam> <padded.fa> <padded_kmer_counts.u16> <chr:start-end> <tech> <out_dir> [--fetch [index_path]]\n");
         return 2;
     }
+    const char* index_path = argc == 9 ? argv[8] : nullptr;
     const std::string bam = argv[1], fa = argv[2], counts_path = argv[3], region = argv[4], tech = argv[5], out_dir = argv[6];
 
     // chr:start-end (1-based, inclusive) -> [start, end); the padded interval as Interval::add_padding clips it at 0
@@ -71,7 +77,17 @@ int main(int argc, char** argv) {
     lcty_ctx* ctx = nullptr;
     ok(lcty_ctx_create(0, &ctx), "lcty_ctx_create");
     lcty_bg_reads* reads = nullptr;
-    ok(lcty_bg_reads_load(bam.c_str(), contig.c_str(), start, end, padded_start, padded_len, &params, &reads), "load_alns");
+    if (fetch) {
+        lcty_sample_bam* sample = nullptr;
+        lcty_sample_bam_stats st;
+        ok(lcty_sample_bam_open(bam.c_str(), index_path, &sample), "lcty_sample_bam_open");
+        ok(lcty_bg_reads_fetch(ctx, sample, contig.c_str(), start, end, padded_start, padded_len, &params, &reads, &st), "fetch + load_alns");
+        lcty_sample_bam_close(sample);
+        std::printf("fetched %llu of %llu bytes, %llu records walked, %llu kept\n", static_cast<unsigned long long>(st.bytes_read),
+                    static_cast<unsigned long long>(st.file_bytes), static_cast<unsigned long long>(st.records_walked),
+                    static_cast<unsigned long long>(st.records_kept));
+    } else
+        ok(lcty_bg_reads_load(bam.c_str(), contig.c_str(), start, end, padded_start, padded_len, &params, &reads), "load_alns");
     lcty_bg bg; double read_len = 0;
     ok(lcty_bg_estimate(ctx, reads, seq.data(), padded_start, padded_len, counts.data(), k, start, end, &params, &bg, &read_len, nullptr),
        "estimate_bg_distrs");

@@ -994,7 +994,8 @@ int32_t lcty_distances_parse(const uint8_t* buf, uint64_t len, uint32_t n_allele
 
 /* ---- background distributions of a sample (locityper preproc, existing alignments + a background region) ------------------------
  * estimate_bg_distrs (src/command/preproc.rs:1157-1192) with `-a`: the alignments of ONE background interval [start, end) of one
- * contig, read sequentially from a BAM file that holds them (a slice of the sample's BAM: no BAI fetch, no CRAM), the reference
+ * contig, read sequentially from a BAM file that holds them (a slice of the sample's BAM) or fetched through the index of the
+ * sample's whole BAM file (lcty_bg_reads_fetch; no CRAM), the reference
  * sequence of the interval +- 50 kb (BgRegion::new, preproc.rs:1357-1385) and the k-mer counts of that padded sequence (what
  * `jellyfish query` returns for it; the caller runs jellyfish). Out of scope: mapping reads (run_mapping, 918), --similar-dataset
  * (estimate_like, 1293), input subsampling (only the rate enters the depth fit), the region-less OpCounter::Unbounded path.
@@ -1006,6 +1007,21 @@ int32_t lcty_distances_parse(const uint8_t* buf, uint64_t len, uint32_t n_allele
  *   (group_mates, bg/insertsz.rs:25-37). Errors (LCTY_ERR_INVALID_DATA): paired and unpaired records mixed, no records, a read with
  *   two first (second) mates, SEQ length != CIGAR query length (the reference panics), an op other than M I D S = X (H, N, P: the
  *   reference panics in count_region_operations). Paired-end data with a technology other than Illumina -> LCTY_ERR_INVALID_INPUT.
+ * lcty_bg_reads_fetch: the same records and the same answer from the sample's whole, coordinate-sorted, indexed BAM file
+ *   (lcty_sample_bam_open): IndexedReader::fetch (preproc.rs:1174-1192) through the BAI index, load_alns (988-1028) and group_mates
+ *   (bg/insertsz.rs:25-37) on the device. The records read are those of lcty_sample_bam_fetch's front half for the one region
+ *   (tid of contig, start, end) without the unmapped tail: the chunks of the index, pread, the BGZF split, the inflate (knob
+ *   "sample_bam_inflate"), the host walk of record lengths. The view of the handle equals, field for field and word for word, the
+ *   one lcty_bg_reads_load gives for a file of the same records, and so do the status and the read an error names (the first
+ *   offending record in file order; a mapped record without a CIGAR is named here too). Beyond lcty_bg_reads_load, as
+ *   lcty_sample_bam_fetch: a record that leaves the fetched slice or is shorter than its fields, and (tid, pos) running backwards
+ *   inside the slice: LCTY_ERR_INVALID_DATA; a slice above "sample_bam_max_slice_bytes", 2^31 records or CIGAR operations or more:
+ *   LCTY_ERR_UNSUPPORTED. A contig that is not in the header, an interval outside the padded sequence: LCTY_ERR_INVALID_INPUT.
+ *   "sample_bam_hash_bits" keeps that many bits of the hash of a read name (names are always compared in full). The arrays of the
+ *   view are downloaded once and belong to the handle, which also keeps them on the device of `ctx`: lcty_bg_estimate on the same
+ *   context reads them there (no upload; the results are bit-identical either way). The handle must be freed before its context.
+ *   stats (may be NULL) as lcty_sample_bam_fetch fills it: ms_record the record stage with its scans, ms_pair the mates, ms_unpack
+ *   the CIGAR gather, the base unpack and the downloads; records_kept = n_records, n_pairs the full pairs, n_discarded 0.
  * lcty_bg_estimate: estimate_bg_from_paired / _unpaired (preproc.rs:1065-1155) -> lcty_bg + the mean read length (read_len_from_alns,
  *   1031-1037; SequencingInfo::new 304-322: out of the technology's range -> LCTY_ERR_INVALID_INPUT unless explicit_technology).
  *   padded_seq: upper-case A/C/G/T only (JfKmerGetter::fetch refuses Ns, seq/counts.rs:326-327: LCTY_ERR_INVALID_INPUT);
@@ -1089,6 +1105,9 @@ typedef struct lcty_bg_diag {
 void    lcty_bg_params_default(lcty_bg_params* params);
 int32_t lcty_bg_reads_load(const char* path, const char* contig, uint32_t start, uint32_t end, uint32_t padded_start, uint32_t padded_len,
                            const lcty_bg_params* params, lcty_bg_reads** out);
+int32_t lcty_bg_reads_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, const char* contig, uint32_t start, uint32_t end,
+                            uint32_t padded_start, uint32_t padded_len, const lcty_bg_params* params,
+                            lcty_bg_reads** out, lcty_sample_bam_stats* stats /* may be NULL */);
 int32_t lcty_bg_reads_view_get(const lcty_bg_reads* reads, lcty_bg_reads_view* view);
 void    lcty_bg_reads_free(lcty_bg_reads* reads);
 int32_t lcty_bg_diag_sizes(const lcty_bg_reads* reads, uint32_t region_start, uint32_t region_end, const lcty_bg_params* params,

@@ -26,6 +26,7 @@ P = C.POINTER
 SIGNATURES = {
     "lcty_bg_params_default": (None, [P(BgParams)]),
     "lcty_bg_reads_load": (I32, [C.c_char_p, C.c_char_p, U32, U32, U32, U32, P(BgParams), P(VP)]),
+    "lcty_bg_reads_fetch": (I32, [VP, VP, C.c_char_p, U32, U32, U32, U32, P(BgParams), P(VP), P(SampleBamStats)]),
     "lcty_bg_reads_view_get": (I32, [VP, P(BgReadsView)]),
     "lcty_bg_reads_free": (None, [VP]),
     "lcty_bg_diag_sizes": (I32, [VP, U32, U32, P(BgParams), P(U64), P(U64), P(U64)]),

@@ -884,11 +884,30 @@ def bg_params(technology=cdefs.TECH_ILLUMINA, **kw):
 
 
 class BgReads:
-    """lcty_bg_reads_load: the records of the background interval [start, end) of `contig` that load_alns keeps, as numpy arrays."""
+    """lcty_bg_reads_load: the records of the background interval [start, end) of `contig` that load_alns keeps, as numpy arrays.
+    BgReads.fetch: the same from the sample's indexed BAM file (lcty_bg_reads_fetch), with the stage times in `stats`."""
 
     def __init__(self, path, contig, start, end, padded_start, padded_len, params):
         self._h = VP()
+        self.stats = None
         check(lib().lcty_bg_reads_load(str(path).encode(), contig.encode(), start, end, padded_start, padded_len, C.byref(params), C.byref(self._h)))
+        self._take_view()
+
+    @classmethod
+    def fetch(cls, ctx, sample_bam, contig, start, end, padded_start, padded_len, params):
+        """sample_bam: io.SampleBam. The handle keeps its arrays on the device of ctx: estimate_bg on that context reads them there.
+        Close it before the context."""
+        self = cls.__new__(cls)
+        self._h = VP()
+        st = cdefs.SampleBamStats()
+        check(lib().lcty_bg_reads_fetch(ctx._h, sample_bam._h, contig.encode(), start, end, padded_start, padded_len, C.byref(params),
+                                        C.byref(self._h), C.byref(st)))
+        self.stats = st.as_dict()
+        self._ctx = ctx
+        self._take_view()
+        return self
+
+    def _take_view(self):
         v = cdefs.BgReadsView()
         check(lib().lcty_bg_reads_view_get(self._h, C.byref(v)))
         n = int(v.n_records)

@@ -24,6 +24,7 @@
 #include <numeric>
 #include <vector>
 
+#include "lcty_bg_reads.hpp"
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
 #include "lcty_math.hpp"
@@ -419,12 +420,20 @@ int32_t lcty_bg_estimate(lcty_ctx* ctx, const lcty_bg_reads* reads, const uint8_
         const uint64_t n_cig = v.cigar_off[n], n_bases = v.seq_off[n];
         DevBuf<uint32_t> d_pos, d_end, d_cig, d_b2, d_nm, d_list, d_rc, d_edit, d_rl, d_mid, d_win; DevBuf<uint64_t> d_coff, d_soff; DevBuf<uint8_t> d_flags;
         RecArgs A{};
-        A.pos = dev_copy(d_pos, v.pos, n, s); A.end = dev_copy(d_end, v.end, n, s);
-        A.cigar_off = dev_copy(d_coff, v.cigar_off, n + 1ull, s); A.cigar = dev_copy(d_cig, v.cigar, n_cig, s);
-        A.seq_off = dev_copy(d_soff, v.seq_off, n + 1ull, s);
-        A.bases2 = dev_copy(d_b2, v.bases2, n_bases / 16 + 2, s); A.nmask = dev_copy(d_nm, v.nmask, n_bases / 32 + 1, s);
+        // a handle of lcty_bg_reads_fetch on this context holds the eight arrays on the device already, equal to the view's word for word
+        const bool resident = reads->ctx == ctx;
+        const uint8_t* rec_flags;
+        if (resident) {
+            A.pos = reads->d_pos.p; A.end = reads->d_end.p; A.cigar_off = reads->d_cigar_off.p; A.cigar = reads->d_cigar.p;
+            A.seq_off = reads->d_seq_off.p; A.bases2 = reads->d_bases2.p; A.nmask = reads->d_nmask.p; rec_flags = reads->d_flags.p;
+        } else {
+            A.pos = dev_copy(d_pos, v.pos, n, s); A.end = dev_copy(d_end, v.end, n, s);
+            A.cigar_off = dev_copy(d_coff, v.cigar_off, n + 1ull, s); A.cigar = dev_copy(d_cig, v.cigar, n_cig, s);
+            A.seq_off = dev_copy(d_soff, v.seq_off, n + 1ull, s);
+            A.bases2 = dev_copy(d_b2, v.bases2, n_bases / 16 + 2, s); A.nmask = dev_copy(d_nm, v.nmask, n_bases / 32 + 1, s);
+            rec_flags = dev_copy(d_flags, v.flags, n, s);
+        }
         A.ref2 = dev_copy(d_ref2, ref2.data(), ref2.size(), s);
-        dev_copy(d_flags, v.flags, n, s);
         A.padded_start = padded_start; A.region_start = region_start; A.region_end = region_end;
         A.win_start = region_start + L.first_start; A.win_end = A.win_start + L.n_windows * L.window; A.window = L.window;
         d_rc.alloc(5ull * n); d_edit.alloc(n); d_rl.alloc(n); d_mid.alloc(n); d_win.alloc(n);
@@ -457,7 +466,7 @@ int32_t lcty_bg_estimate(lcty_ctx* ctx, const lcty_bg_reads* reads, const uint8_
             dev_copy(d_pf, pf.data(), np, s); dev_copy(d_ps, ps.data(), np, s);
             d_ins.alloc(np); d_same.alloc(np);
             E.rec(4, s);
-            hipLaunchKernelGGL(pairs_kernel, dim3((np + 255) / 256), dim3(256), 0, s, d_pos.p, d_end.p, d_flags.p, d_pf.p, d_ps.p, np, d_ins.p, d_same.p);
+            hipLaunchKernelGGL(pairs_kernel, dim3((np + 255) / 256), dim3(256), 0, s, A.pos, A.end, rec_flags, d_pf.p, d_ps.p, np, d_ins.p, d_same.p);
             LCTY_HIP(hipGetLastError());
             E.rec(5, s);
             d_ins.download(ins.data(), np, s); d_same.download(same.data(), np, s);
@@ -567,7 +576,7 @@ int32_t lcty_bg_estimate(lcty_ctx* ctx, const lcty_bg_reads* reads, const uint8_
             dev_copy(d_dl, dl.data(), dl.size(), s);
             E.rec(6, s);
             hipLaunchKernelGGL(depth_kernel, dim3((static_cast<uint32_t>(dl.size()) + 255) / 256), dim3(256), 0, s, d_dl.p,
-                               static_cast<uint32_t>(dl.size()), d_win.p, d_flags.p, d_depth.p);
+                               static_cast<uint32_t>(dl.size()), d_win.p, rec_flags, d_depth.p);
             LCTY_HIP(hipGetLastError());
             E.rec(7, s);
         }

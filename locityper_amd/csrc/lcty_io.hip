@@ -21,6 +21,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "lcty_bg_reads.hpp"
 #include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
@@ -978,12 +979,6 @@ int32_t lcty_fasta_write_text(uint32_t n_seqs, const char* names, const uint8_t*
 extern "C" {
 
 // ---- background reads: IndexedReader::fetch + load_alns of `preproc -a` (src/command/preproc.rs:988-1028, 1174-1192) --------------
-struct lcty_bg_reads {
-    std::vector<uint32_t> pos, end, qlen, mate; std::vector<uint8_t> flags;
-    std::vector<uint64_t> cigar_off, seq_off; std::vector<uint32_t> cigar, bases2, nmask;
-    lcty_bg_reads_view view{};
-};
-
 void lcty_bg_params_default(lcty_bg_params* p) {
     if (!p) return;
     memset(p, 0, sizeof(*p));

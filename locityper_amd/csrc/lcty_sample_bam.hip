@@ -15,6 +15,8 @@
 //   exclusive_scan  over the completing records -> the pairs in the reference's order; assemble_kernel lays out the mates
 //   unpack_kernel   a lane per 32 bases of a mate: 4-bit codes -> bases2 / nmask, back to front and complemented for reverse records;
 //                   a lane writes whole words of its own only
+// The record fields, the name hash and comparison, unpack_kernel and the front half of a fetch (fetch_slice) are shared with the
+// background route, lcty_bg_fetch.hip, through lcty_sample_bam_internal.hpp.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -30,14 +32,13 @@
 
 #include "lcty_bgzf.hpp"
 #include "lcty_objects.hpp"
+#include "lcty_sample_bam_internal.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
 #include "lcty_writers.hpp"
 
 namespace lcty {
 
-constexpr uint64_t SLICE_PAD = 64;             // bytes behind the slice that the dword loads of a record's last bytes may touch
-constexpr uint32_t NONE32 = 0xFFFFFFFFu;
 // error classes, by rank at one record; (record ordinal << 8 | class) goes through atomicMin
 enum : uint32_t { E_SHORT = 1, E_UNSORTED = 2, E_CG = 3, E_NOSEQ = 4, E_UNPAIRED = 5, E_TWO_ENDS = 6 };
 constexpr uint32_t INFO_KEPT = 1u << 16, INFO_WAITS = 1u << 17;
@@ -53,33 +54,6 @@ struct SampleView {
     uint32_t* kept;                             // 0 / 1
     unsigned long long* err; uint32_t* n_primary;
 };
-
-// four bytes from byte `off` of the slice (the dword behind the last one is inside SLICE_PAD)
-__device__ __forceinline__ uint32_t ld32(const uint32_t* w, uint64_t off) {
-    const uint64_t i = off >> 2;
-    const uint64_t v = static_cast<uint64_t>(w[i]) | (static_cast<uint64_t>(w[i + 1]) << 32);
-    return static_cast<uint32_t>(v >> ((off & 3u) * 8u));
-}
-// reference bases of a CIGAR word: M, D, N, =, X
-__device__ __forceinline__ uint32_t cigar_ref_len(uint32_t w) { return ((0x18Du >> (w & 15u)) & 1u) ? (w >> 4) : 0u; }
-
-struct RecHead { int32_t tid, pos, mtid, mpos; uint32_t l_name, n_cigar, flag, l_seq, block; };
-__device__ __forceinline__ RecHead rec_head(const uint32_t* raw, uint64_t o) {
-    RecHead h;
-    h.block = ld32(raw, o); h.tid = static_cast<int32_t>(ld32(raw, o + 4)); h.pos = static_cast<int32_t>(ld32(raw, o + 8));
-    h.l_name = ld32(raw, o + 12) & 0xFFu;
-    const uint32_t nf = ld32(raw, o + 16);
-    h.n_cigar = nf & 0xFFFFu; h.flag = nf >> 16;
-    h.l_seq = ld32(raw, o + 20); h.mtid = static_cast<int32_t>(ld32(raw, o + 24)); h.mpos = static_cast<int32_t>(ld32(raw, o + 28));
-    return h;
-}
-__device__ __forceinline__ bool rec_fits(const RecHead& h) {
-    return 32ull + h.l_name + 4ull * h.n_cigar + (static_cast<uint64_t>(h.l_seq) + 1) / 2 + h.l_seq <= h.block;
-}
-// file order of two placed records; a record without coordinate (tid < 0) is behind every placed one
-__device__ __forceinline__ uint64_t sort_key(int32_t tid, int32_t pos) {
-    return tid < 0 ? ~0ull : (static_cast<uint64_t>(static_cast<uint32_t>(tid)) << 32) | static_cast<uint32_t>(pos + 1);
-}
 
 __global__ __launch_bounds__(256) void record_kernel(const SampleView V) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
@@ -138,15 +112,7 @@ __global__ __launch_bounds__(256) void record_kernel(const SampleView V) {
         const bool waits = static_cast<uint32_t>(h.tid) < static_cast<uint32_t>(h.mtid) ||
                            (h.tid == h.mtid && static_cast<uint64_t>(static_cast<int64_t>(h.pos)) <= static_cast<uint64_t>(static_cast<int64_t>(h.mpos)));
         info = h.flag | (kept ? INFO_KEPT : 0u) | (waits ? INFO_WAITS : 0u);
-        if (kept) {                                                              // FNV-1a over the name without its NUL, then mixed
-            uint64_t x = 0xcbf29ce484222325ull;
-            const uint32_t n = h.l_name ? h.l_name - 1 : 0u;
-            for (uint32_t j = 0; j < n; j += 4) {
-                uint32_t w = ld32(V.raw, o + 36 + j);
-                for (uint32_t b = 0; b < 4 && j + b < n; b++) { x = (x ^ (w & 0xFFu)) * 0x100000001b3ull; w >>= 8; }
-            }
-            V.hash[r] = mix64(x) & V.hash_mask;
-        }
+        if (kept) V.hash[r] = name_hash(V.raw, o, h.l_name) & V.hash_mask;
     }
     if (valid) {
         V.info[r] = info; V.kept[r] = kept ? 1u : 0u;
@@ -166,16 +132,6 @@ __global__ __launch_bounds__(256) void stream_kernel(uint32_t n_rec, const uint3
     const uint32_t s = scan[r];
     stream[s] = r;
     if (keys) { keys[s] = hash[r]; vals[s] = s; }
-}
-
-__device__ inline bool same_name(const uint32_t* raw, uint64_t oa, uint64_t ob) {
-    const uint32_t la = ld32(raw, oa + 12) & 0xFFu, lb = ld32(raw, ob + 12) & 0xFFu;
-    if (la != lb) return false;
-    for (uint32_t j = 0; j < la; j += 4) {
-        const uint32_t m = la - j >= 4 ? 0xFFFFFFFFu : (1u << (8 * (la - j))) - 1u;
-        if ((ld32(raw, oa + 36 + j) ^ ld32(raw, ob + 36 + j)) & m) return false;
-    }
-    return true;
 }
 
 // PairedBamReader::read_next (fastx.rs:829-869) for the record at place i of the sorted list: the records of its name before it, in
@@ -234,42 +190,6 @@ __global__ __launch_bounds__(256) void assemble_kernel(const uint32_t* __restric
 __global__ __launch_bounds__(256) void offsets_kernel(const uint32_t* __restrict__ unit_off, uint64_t n, uint64_t* __restrict__ mate_off) {
     const uint64_t m = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
     if (m < n) mate_off[m] = 32ull * unit_off[m];
-}
-
-__device__ __forceinline__ uint32_t swap_nibbles(uint32_t x) { return ((x & 0x0F0F0F0Fu) << 4) | ((x >> 4) & 0x0F0F0F0Fu); }
-
-// unit u = 32 bases of one mate = one 64-bit word of bases2 and one word of nmask
-__global__ __launch_bounds__(256) void unpack_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ src,
-                                                     const uint32_t* __restrict__ unit_off, uint32_t n_mates, uint32_t n_units,
-                                                     uint64_t* __restrict__ bases2, uint32_t* __restrict__ nmask) {
-    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
-    if (u >= n_units) return;
-    uint32_t lo_m = 0, hi_m = n_mates;                                           // the mate whose units hold u: last m with unit_off[m] <= u
-    while (hi_m - lo_m > 1) { const uint32_t mid = (lo_m + hi_m) / 2; if (unit_off[mid] <= u) lo_m = mid; else hi_m = mid; }
-    const uint32_t m = lo_m, q = u - unit_off[m];
-    const uint64_t o = rec_off[src[m]];
-    const uint32_t l_name = ld32(raw, o + 12) & 0xFFu, nf = ld32(raw, o + 16), L = ld32(raw, o + 20);
-    const bool reverse = ((nf >> 16) & 0x10u) != 0;
-    const uint32_t n = min(32u, L - 32u * q);
-    const uint32_t a = reverse ? L - 32u * q - n : 32u * q;                      // first base of the record this unit reads
-    const uint64_t b0 = o + 36 + l_name + 4ull * (nf & 0xFFFFu) + (a >> 1);
-    // 17 bytes at most; base a + t at bits 4 t of (lo, hi) once the nibbles of every byte are swapped and an odd start is shifted out
-    const uint32_t d0 = swap_nibbles(ld32(raw, b0)), d1 = swap_nibbles(ld32(raw, b0 + 4)), d2 = swap_nibbles(ld32(raw, b0 + 8)),
-                   d3 = swap_nibbles(ld32(raw, b0 + 12)), d4 = swap_nibbles(ld32(raw, b0 + 16));
-    uint64_t lo = d0 | (static_cast<uint64_t>(d1) << 32), hi = d2 | (static_cast<uint64_t>(d3) << 32);
-    if (a & 1u) { lo = (lo >> 4) | (hi << 60); hi = (hi >> 4) | (static_cast<uint64_t>(d4) << 60); }
-    uint64_t bases = 0; uint32_t mask = 0;
-#pragma unroll
-    for (uint32_t t = 0; t < 32; t++) {
-        if (t < n) {
-            const uint32_t code = static_cast<uint32_t>((t < 16 ? lo >> (4 * t) : hi >> (4 * (t - 16))) & 15ull);
-            const uint32_t e = code == 1u ? 0u : code == 2u ? 1u : code == 4u ? 2u : code == 8u ? 3u : 4u;     // =ACMGRSVTWYHKDBN
-            const uint32_t at = reverse ? n - 1u - t : t;
-            if (e > 3u) mask |= 1u << at;
-            else bases |= static_cast<uint64_t>(reverse ? 3u - e : e) << (2u * at);
-        }
-    }
-    bases2[u] = bases; nmask[u] = mask;
 }
 
 // ---- host: BGZF by block, the header, the index ---------------------------------------------------------------------------------
@@ -354,38 +274,20 @@ void bgzf_inflate_host(const uint8_t* comp, const std::vector<BgzfBlock>& blocks
     for (const std::string& f : failed) if (!f.empty()) fail(LCTY_ERR_INVALID_DATA, "%s", f.c_str());
 }
 
-struct Chunk { uint64_t beg, end; };
-
 }  // namespace lcty
 
 using namespace lcty;
-
-struct lcty_sample_bam {
-    std::string path, index_path;
-    int fd = -1;
-    uint64_t fsize = 0;
-    std::vector<uint32_t> lengths; std::vector<uint64_t> name_off; std::string names;
-    uint64_t first_record = 0;                   // virtual offset behind the header
-    int paired = -1;                             // flag 0x1 of the first record; -1: not looked at yet, -2: no record
-    struct Ref { std::unordered_map<uint32_t, std::vector<Chunk>> bins; std::vector<uint64_t> linear; };
-    std::vector<Ref> refs;
-    uint64_t tail_start = 0;                     // largest chunk end of the index
-    uint64_t n_no_coor = 0; bool has_no_coor = false;
-    ~lcty_sample_bam() { if (fd >= 0) close(fd); }
-};
 
 struct lcty_sample_reads {
     lcty_ctx* ctx = nullptr;
     bool paired = false;
     uint64_t n = 0;                              // pairs, or single reads
-    uint8_t* slice = nullptr;                    // page-locked: the inflated blocks of the call
-    std::vector<uint64_t> rec_off;
+    FetchedSlice F;                              // the inflated blocks of the call and the records walked in them
     DevBuf<uint32_t> d_len, d_nm, d_src; DevBuf<uint64_t> d_off, d_bases;
     uint64_t n_units = 0;
     std::vector<uint32_t> h_len, h_src, h_src_stream, h_bases, h_nm;    // h_src: a mate's record among the records walked (rec_off); _stream: in the fetched stream
     std::vector<uint64_t> h_off, zero_off;
     bool have_bases = false;
-    ~lcty_sample_reads() { if (slice) (void)hipHostFree(slice); }
 };
 
 namespace {
@@ -438,16 +340,6 @@ void load_bai(lcty_sample_bam* b) {
     if (at + 8 <= x.size()) { b->n_no_coor = u64(); b->has_no_coor = true; }
 }
 
-void check_regions(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end) {
-    if (n && (!tid || !start || !end)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-    for (uint32_t i = 0; i < n; i++) {
-        if (tid[i] >= b->lengths.size()) fail(LCTY_ERR_INVALID_INPUT, "region %u: contig %u of %zu", i, tid[i], b->lengths.size());
-        if (start[i] >= end[i]) fail(LCTY_ERR_INVALID_INPUT, "region %u is empty (%u-%u)", i, start[i], end[i]);
-        if (i && (tid[i] < tid[i - 1] || (tid[i] == tid[i - 1] && start[i] < end[i - 1])))
-            fail(LCTY_ERR_INVALID_INPUT, "Cannot fetch reads from BAM file: regions must be sorted (region %u)", i);       // fastx.rs:770
-    }
-}
-
 // the chunks of a call: reg2bins (SAM specification 5.3), the linear index's cut, sorted and merged
 std::vector<Chunk> plan_chunks(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end, bool with_unmapped,
                                bool whole_file) {
@@ -482,6 +374,20 @@ std::vector<Chunk> plan_chunks(const lcty_sample_bam* b, uint32_t n, const uint3
 // a chunk's blocks as they lie in the file
 struct ChunkSpan { size_t first_block, n_blocks; uint64_t chain_beg, chain_end, span_end; };
 
+}  // namespace
+
+namespace lcty {
+
+void check_regions(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end) {
+    if (n && (!tid || !start || !end)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+    for (uint32_t i = 0; i < n; i++) {
+        if (tid[i] >= b->lengths.size()) fail(LCTY_ERR_INVALID_INPUT, "region %u: contig %u of %zu", i, tid[i], b->lengths.size());
+        if (start[i] >= end[i]) fail(LCTY_ERR_INVALID_INPUT, "region %u is empty (%u-%u)", i, start[i], end[i]);
+        if (i && (tid[i] < tid[i - 1] || (tid[i] == tid[i - 1] && start[i] < end[i - 1])))
+            fail(LCTY_ERR_INVALID_INPUT, "Cannot fetch reads from BAM file: regions must be sorted (region %u)", i);       // fastx.rs:770
+    }
+}
+
 std::string record_name(const uint8_t* slice, uint64_t o) {
     const uint32_t l = slice[o + 12];
     std::string s(reinterpret_cast<const char*>(slice + o + 36), l ? l - 1 : 0);
@@ -490,7 +396,111 @@ std::string record_name(const uint8_t* slice, uint64_t o) {
     return s;
 }
 
-}  // namespace
+bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
+                 bool with_unmapped, bool whole_file, FetchedSlice& F, DevBuf<uint8_t>& d_raw, lcty_sample_bam_stats& S) {
+    const char* path = bam->path.c_str();
+    const uint64_t cap = static_cast<uint64_t>(ctx->knob("sample_bam_max_slice_bytes", 1ll << 33));
+    if (ctx->knob("sample_bam_inflate", 0) > 1) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_inflate = %lld (0: host, 1: device)", static_cast<long long>(ctx->knob("sample_bam_inflate", 0)));
+    const std::vector<Chunk> cs = plan_chunks(bam, n_regions, tid, start, end, with_unmapped, whole_file);
+    S.n_chunks = cs.size();
+
+    // ---- the bytes of the chunks, split into blocks
+    double t0 = now_ms();
+    std::vector<uint8_t> comp;
+    std::vector<BgzfBlock> blocks;
+    std::vector<ChunkSpan> spans;
+    uint64_t total = 0;
+    for (const Chunk& c : cs) {
+        const uint64_t cbeg = c.beg >> 16, cend = c.end >> 16;
+        const uint32_t uend = static_cast<uint32_t>(c.end & 0xFFFF);
+        if (cbeg >= bam->fsize) continue;
+        uint64_t rend = cend;                                              // ... and the block the chunk ends in, when it reaches into it
+        if (uend && cend < bam->fsize) {
+            uint8_t hd[512];
+            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), bam->fsize - cend));
+            pread_all(bam->fd, hd, n, cend, path);
+            const uint32_t csize = bgzf_block_size(hd, n);
+            if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(cend));
+            rend = std::min<uint64_t>(bam->fsize, cend + csize);
+        }
+        rend = std::min<uint64_t>(rend, bam->fsize);
+        const size_t in0 = comp.size();
+        comp.resize(in0 + (rend - cbeg));
+        pread_all(bam->fd, comp.data() + in0, rend - cbeg, cbeg, path);
+        S.bytes_read += rend - cbeg;
+        ChunkSpan sp{blocks.size(), 0, total + (c.beg & 0xFFFF), 0, 0};
+        bool end_seen = false;
+        uint64_t at = cbeg;
+        while (at < rend && (at < cend || (at == cend && uend))) {
+            const uint8_t* p = comp.data() + in0 + (at - cbeg);
+            const uint32_t csize = bgzf_block_size(p, rend - at);
+            if (!csize || at + csize > rend) {
+                if (at + 0x10000 >= bam->fsize) fail(LCTY_ERR_INVALID_DATA, "%s: truncated or corrupt BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
+                fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(at));
+            }
+            const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
+            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
+            if (at == cbeg && (c.beg & 0xFFFF) > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index starts behind its block", path);
+            if (at == cend) { if (uend > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index ends behind its block", path); sp.chain_end = total + uend; end_seen = true; }
+            blocks.push_back(BgzfBlock{csize, isize, total, in0 + static_cast<size_t>(at - cbeg), at, bgzf_plain_head(p)});
+            total += isize; at += csize;
+        }
+        sp.n_blocks = blocks.size() - sp.first_block; sp.span_end = total;
+        if (!end_seen) sp.chain_end = total;
+        if (sp.n_blocks) spans.push_back(sp);
+    }
+    S.ms_read = now_ms() - t0;
+    S.blocks_inflated = blocks.size(); S.bytes_inflated = total;
+    if (total > cap)
+        fail(LCTY_ERR_UNSUPPORTED, "%s: the fetched slice has %llu bytes, more than %llu (knob sample_bam_max_slice_bytes)", path,
+             static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
+
+    // ---- inflate: every block into its place of one page-locked buffer
+    ctx->activate();
+    hipStream_t s = ctx->stream;
+    F.total = total;
+    LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&F.slice), total + SLICE_PAD, hipHostMallocDefault));
+    memset(F.slice + total, 0, SLICE_PAD);
+    t0 = now_ms();
+    // knob "sample_bam_inflate" 1: on the device, straight into the buffer record_kernel reads, and from there to the page-locked
+    // slice for the walk and the writer; blocks with more in their gzip header than the extra field leave the call to zlib
+    bool on_device = ctx->knob("sample_bam_inflate", 0) == 1 && total > 0;
+    for (const BgzfBlock& b : blocks) if (b.isize && (!b.head || b.head + 8u > b.csize)) on_device = false;
+    if (on_device) {
+        DevBuf<uint8_t> d_comp;
+        d_comp.alloc(comp.size()); d_raw.alloc(total + SLICE_PAD);
+        d_comp.upload(comp.data(), comp.size(), s);
+        LCTY_HIP(hipMemsetAsync(d_raw.p + total, 0, SLICE_PAD, s));
+        bgzf_inflate_device(ctx, d_comp.p, comp.size(), blocks, d_raw.p, total, s, path);
+        d_raw.download(F.slice, total, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+    } else bgzf_inflate_host(comp.data(), blocks, F.slice, path);
+    S.ms_inflate = now_ms() - t0;
+    std::vector<uint8_t>().swap(comp);
+
+    // ---- the chain of record lengths
+    t0 = now_ms();
+    std::vector<uint64_t>& rec_off = F.rec_off;
+    for (const ChunkSpan& sp : spans) {
+        uint64_t p = sp.chain_beg;
+        while (p < sp.chain_end) {
+            uint32_t bs = 0;
+            if (p + 4 <= sp.span_end) memcpy(&bs, F.slice + p, 4);
+            if (p + 4 > sp.span_end || bs < 32 || p + 4 + bs > sp.span_end)
+                fail(LCTY_ERR_INVALID_DATA, "%s: record %zu of the fetched slice is truncated, or its length (%u) leaves the slice", path, rec_off.size(), bs);
+            rec_off.push_back(p);
+            p += 4ull + bs;
+        }
+    }
+    const uint64_t n_rec = rec_off.size();
+    S.records_walked = n_rec;
+    S.ms_walk = now_ms() - t0;
+    if (n_rec >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "%s: %llu records in one fetch", path, static_cast<unsigned long long>(n_rec));
+
+    return on_device;
+}
+
+}  // namespace lcty
 
 extern "C" {
 
@@ -637,107 +647,18 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         const int64_t hash_bits = ctx->knob("sample_bam_hash_bits", 64);
         if (hash_bits > 64) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_hash_bits = %lld (0 .. 64)", static_cast<long long>(hash_bits));
         const uint64_t hash_mask = hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1;
-        const uint64_t cap = static_cast<uint64_t>(ctx->knob("sample_bam_max_slice_bytes", 1ll << 33));
-        if (ctx->knob("sample_bam_inflate", 0) > 1) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_inflate = %lld (0: host, 1: device)", static_cast<long long>(ctx->knob("sample_bam_inflate", 0)));
         lcty_sample_bam_stats S{};
         S.n_regions = n_regions; S.file_bytes = bam->fsize;
-        const std::vector<Chunk> cs = plan_chunks(bam, n_regions, tid, start, end, with_unmapped != 0, whole_file != 0);
-        S.n_chunks = cs.size();
-
-        // ---- the bytes of the chunks, split into blocks
-        double t0 = now_ms();
-        std::vector<uint8_t> comp;
-        std::vector<BgzfBlock> blocks;
-        std::vector<ChunkSpan> spans;
-        uint64_t total = 0;
-        for (const Chunk& c : cs) {
-            const uint64_t cbeg = c.beg >> 16, cend = c.end >> 16;
-            const uint32_t uend = static_cast<uint32_t>(c.end & 0xFFFF);
-            if (cbeg >= bam->fsize) continue;
-            uint64_t rend = cend;                                              // ... and the block the chunk ends in, when it reaches into it
-            if (uend && cend < bam->fsize) {
-                uint8_t hd[512];
-                const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), bam->fsize - cend));
-                pread_all(bam->fd, hd, n, cend, path);
-                const uint32_t csize = bgzf_block_size(hd, n);
-                if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(cend));
-                rend = std::min<uint64_t>(bam->fsize, cend + csize);
-            }
-            rend = std::min<uint64_t>(rend, bam->fsize);
-            const size_t in0 = comp.size();
-            comp.resize(in0 + (rend - cbeg));
-            pread_all(bam->fd, comp.data() + in0, rend - cbeg, cbeg, path);
-            S.bytes_read += rend - cbeg;
-            ChunkSpan sp{blocks.size(), 0, total + (c.beg & 0xFFFF), 0, 0};
-            bool end_seen = false;
-            uint64_t at = cbeg;
-            while (at < rend && (at < cend || (at == cend && uend))) {
-                const uint8_t* p = comp.data() + in0 + (at - cbeg);
-                const uint32_t csize = bgzf_block_size(p, rend - at);
-                if (!csize || at + csize > rend) {
-                    if (at + 0x10000 >= bam->fsize) fail(LCTY_ERR_INVALID_DATA, "%s: truncated or corrupt BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
-                    fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(at));
-                }
-                const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
-                if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
-                if (at == cbeg && (c.beg & 0xFFFF) > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index starts behind its block", path);
-                if (at == cend) { if (uend > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index ends behind its block", path); sp.chain_end = total + uend; end_seen = true; }
-                blocks.push_back(BgzfBlock{csize, isize, total, in0 + static_cast<size_t>(at - cbeg), at, bgzf_plain_head(p)});
-                total += isize; at += csize;
-            }
-            sp.n_blocks = blocks.size() - sp.first_block; sp.span_end = total;
-            if (!end_seen) sp.chain_end = total;
-            if (sp.n_blocks) spans.push_back(sp);
-        }
-        S.ms_read = now_ms() - t0;
-        S.blocks_inflated = blocks.size(); S.bytes_inflated = total;
-        if (total > cap)
-            fail(LCTY_ERR_UNSUPPORTED, "%s: the fetched slice has %llu bytes, more than %llu (knob sample_bam_max_slice_bytes)", path,
-                 static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
-
-        // ---- inflate: every block into its place of one page-locked buffer
-        ctx->activate();
-        hipStream_t s = ctx->stream;
+        // ---- the front half: chunks, pread, BGZF split, inflate, the chain of record lengths
         std::unique_ptr<lcty_sample_reads> R(new lcty_sample_reads());
         R->ctx = ctx; R->paired = paired != 0;
-        LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&R->slice), total + SLICE_PAD, hipHostMallocDefault));
-        memset(R->slice + total, 0, SLICE_PAD);
-        t0 = now_ms();
-        // knob "sample_bam_inflate" 1: on the device, straight into the buffer record_kernel reads, and from there to the page-locked
-        // slice for the walk and the writer; blocks with more in their gzip header than the extra field leave the call to zlib
-        bool on_device = ctx->knob("sample_bam_inflate", 0) == 1 && total > 0;
-        for (const BgzfBlock& b : blocks) if (b.isize && (!b.head || b.head + 8u > b.csize)) on_device = false;
         DevBuf<uint8_t> d_raw;
-        if (on_device) {
-            DevBuf<uint8_t> d_comp;
-            d_comp.alloc(comp.size()); d_raw.alloc(total + SLICE_PAD);
-            d_comp.upload(comp.data(), comp.size(), s);
-            LCTY_HIP(hipMemsetAsync(d_raw.p + total, 0, SLICE_PAD, s));
-            bgzf_inflate_device(ctx, d_comp.p, comp.size(), blocks, d_raw.p, total, s, path);
-            d_raw.download(R->slice, total, s);
-            LCTY_HIP(hipStreamSynchronize(s));
-        } else bgzf_inflate_host(comp.data(), blocks, R->slice, path);
-        S.ms_inflate = now_ms() - t0;
-        std::vector<uint8_t>().swap(comp);
-
-        // ---- the chain of record lengths
-        t0 = now_ms();
-        std::vector<uint64_t>& rec_off = R->rec_off;
-        for (const ChunkSpan& sp : spans) {
-            uint64_t p = sp.chain_beg;
-            while (p < sp.chain_end) {
-                uint32_t bs = 0;
-                if (p + 4 <= sp.span_end) memcpy(&bs, R->slice + p, 4);
-                if (p + 4 > sp.span_end || bs < 32 || p + 4 + bs > sp.span_end)
-                    fail(LCTY_ERR_INVALID_DATA, "%s: record %zu of the fetched slice is truncated, or its length (%u) leaves the slice", path, rec_off.size(), bs);
-                rec_off.push_back(p);
-                p += 4ull + bs;
-            }
-        }
+        const bool on_device = fetch_slice(ctx, bam, n_regions, tid, start, end, with_unmapped != 0, whole_file != 0, R->F, d_raw, S);
+        hipStream_t s = ctx->stream;
+        const uint64_t total = R->F.total;
+        const std::vector<uint64_t>& rec_off = R->F.rec_off;
         const uint64_t n_rec = rec_off.size();
-        S.records_walked = n_rec;
-        S.ms_walk = now_ms() - t0;
-        if (n_rec >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "%s: %llu records in one fetch", path, static_cast<unsigned long long>(n_rec));
+        double t0;
 
         auto finish = [&]() {
             S.ms_total = now_ms() - t_start;
@@ -749,7 +670,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         // ---- upload, record kernel
         t0 = now_ms();
         DevBuf<uint64_t> d_rec_off, d_hash; DevBuf<uint32_t> d_reg, d_info, d_kept, d_nprim; DevBuf<unsigned long long> d_err;
-        if (!on_device) { d_raw.alloc(total + SLICE_PAD); d_raw.upload(R->slice, total + SLICE_PAD, s); }
+        if (!on_device) { d_raw.alloc(total + SLICE_PAD); d_raw.upload(R->F.slice, total + SLICE_PAD, s); }
         d_rec_off.alloc(n_rec); d_rec_off.upload(rec_off.data(), n_rec, s);
         std::vector<uint32_t> reg(3ull * std::max(n_regions, 1u), 0);
         for (uint32_t i = 0; i < n_regions; i++) { reg[i] = tid[i]; reg[n_regions + i] = start[i]; reg[2ull * n_regions + i] = end[i]; }
@@ -780,7 +701,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
             const uint64_t r = e >> 8;
             const uint64_t o = rec_off[r];
             if (cls == E_SHORT) fail(LCTY_ERR_INVALID_DATA, "%s: record %llu of the fetched slice is shorter than its fields", path, static_cast<unsigned long long>(r));
-            const std::string name = record_name(R->slice, o);
+            const std::string name = record_name(R->F.slice, o);
             if (cls == E_UNSORTED) fail(LCTY_ERR_INVALID_DATA, "%s: coordinates run backwards at read %s: the file is not sorted", path, name.c_str());
             if (cls == E_CG) fail(LCTY_ERR_UNSUPPORTED, "%s: the CIGAR of read %s is kept in a CG tag (more than 65 535 operations)", path, name.c_str());
             if (cls == E_NOSEQ) fail(LCTY_ERR_INVALID_DATA, "Primary alignment for read %s has no sequence", name.c_str());
@@ -839,7 +760,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         R->d_bases.alloc(std::max<uint32_t>(n_units, 1)); R->d_nm.alloc(std::max<uint32_t>(n_units, 1));
         R->d_bases.zero(s); R->d_nm.zero(s);
         if (n_units)
-            hipLaunchKernelGGL(unpack_kernel, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, R->d_src.p, d_unit_off.p,
+            hipLaunchKernelGGL(unpack_kernel<true>, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, R->d_src.p, d_unit_off.p,
                                static_cast<uint32_t>(2 * n_out), n_units, R->d_bases.p, R->d_nm.p);
         LCTY_HIP(hipGetLastError());
         R->h_len.resize(2 * n_out); R->h_src.resize(2 * n_out); R->h_off.resize(2 * n_out + 1);
@@ -899,14 +820,14 @@ int32_t lcty_sample_reads_write_recruited(lcty_sample_reads* R, lcty_fastx_write
             for (uint32_t e = 0; e < 2; e++) {                                   // BamRecord::write_to (fastx.rs:633-668), the mates one after the other
                 const uint32_t r = R->h_src[2 * i + e];
                 if (r == NONE32) continue;
-                const uint8_t* rec = R->slice + R->rec_off[r];
+                const uint8_t* rec = R->F.slice + R->F.rec_off[r];
                 uint32_t l_seq; uint16_t n_cigar, flag;
                 memcpy(&n_cigar, rec + 16, 2); memcpy(&flag, rec + 18, 2); memcpy(&l_seq, rec + 20, 4);
                 const uint8_t* seq = rec + 36 + rec[12] + 4ull * n_cigar;
                 const uint8_t* qual = seq + (static_cast<uint64_t>(l_seq) + 1) / 2;
                 const bool reverse = (flag & 0x10) != 0, fasta = l_seq == 0 || qual[0] == 255;
                 text += fasta ? '>' : '@';
-                text += record_name(R->slice, R->rec_off[r]);
+                text += record_name(R->F.slice, R->F.rec_off[r]);
                 text += '\n';
                 for (uint32_t k = 0; k < l_seq; k++) {
                     const uint32_t j = reverse ? l_seq - 1 - k : k;
