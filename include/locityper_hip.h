@@ -239,7 +239,7 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       (default: from 512 alleles on);   "arena_cap_pct"   p: batches created afterwards (lcty_reads_create) get p % of the bound on their PairAlignment arena (two per
  *       record; one per (pair, allele) is the rule — an arena that is too small fails loudly);   "score_lean"   0: counted batches go through the general scoring kernel only (default 1: the lean kernel first, the general
  *       one on the pairs it leaves);   "score_lean_keep"   0: the lean kernel scores a saved record again in its last pass instead of
- *       keeping the first pass' products in LDS (what loci of more than 310 alleles get anyway);   "score_timing"   1: the lean kernel's
+ *       keeping the first pass' products in LDS (what loci of more than 309 alleles get anyway);   "score_timing"   1: the lean kernel's
  *       timed build, shader-clock ticks per phase on stderr;   "comm_fail_at"   k: the k-th status agreement of a multi-GPU call fails on this rank (tests of
  *       the error path of the exchanges);   "prefilter_gram_cols"   room for that many level columns per read (default 6; too few: the
  *       f64 kernel takes the batch);   "queue_early_head"   0: lcty_solve_queue makes the head of a locus after the chains of the locus before (default 1:
@@ -392,6 +392,26 @@ int32_t lcty_reads_n_pairs(const lcty_reads* reads, uint64_t* out);
  * and K8 the dense row of best_aln_matrix (1203-1212) — one fused launch.
  * Asynchronous on the context's stream.                                         */
 int32_t lcty_score_reads(lcty_reads* reads);
+
+/* Which scoring kernel took which pair in the last lcty_score_reads launch of the batch. A counted batch goes
+ * through the lean kernel (every (contig, read end) group holds at most one saved alignment), what it leaves through its two-slot
+ * form (a second saved alignment in a group, at most 64 such groups in a pair) and what that leaves through the general kernel;
+ * every other batch through the general kernel alone. n_lean + n_two + n_general == n_pairs, the pairs of that launch (of a
+ * streaming batch: the chunk on the device). route: NULL, or n_pairs bytes of the caller's, one LCTY_ROUTE_* per pair in input
+ * order (set it before the call; 0 pairs scored so far: untouched). Read-only; synchronises the context's stream. */
+#define LCTY_ROUTE_LEAN    0
+#define LCTY_ROUTE_TWO     1
+#define LCTY_ROUTE_GENERAL 2
+#define LCTY_LEAN_FORM_NONE  0   /* the lean kernel did not run: n_general == n_pairs */
+#define LCTY_LEAN_FORM_INDEX 1   /* pass 1 leaves the record's index, pass 3 scores the record again (more than 309 alleles) */
+#define LCTY_LEAN_FORM_KEEP  2   /* pass 1's products stay in LDS */
+typedef struct lcty_score_routes {
+    uint64_t n_pairs, n_lean, n_two, n_general;
+    int32_t  lean_form;      /* LCTY_LEAN_FORM_* */
+    int32_t  two_ran;        /* 1: the two-slot form ran between the lean and the general kernel */
+    uint8_t* route;          /* in: NULL or [n_pairs] */
+} lcty_score_routes;
+int32_t lcty_reads_score_routes(lcty_reads* reads, lcty_score_routes* out);
 
 /* per-pair products of load(): any pointer may be NULL */
 int32_t lcty_reads_get_status(lcty_reads* reads, uint8_t* status, double* weight,

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats, BgzfDeflateStats
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats, BgzfDeflateStats, ScoreRoutes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -119,6 +119,7 @@ SIGNATURES = {
     "lcty_reads_destroy": (None, [VP]),
     "lcty_reads_n_pairs": (I32, [VP, P(U64)]),
     "lcty_score_reads": (I32, [VP]),
+    "lcty_reads_score_routes": (I32, [VP, P(ScoreRoutes)]),
     "lcty_reads_get_status": (I32, [VP, VP, VP, VP, VP]),
     "lcty_reads_n_good": (I32, [VP, P(U64)]),
     "lcty_best_aln_matrix": (I32, [VP, VP]),

@@ -307,6 +307,18 @@ class AllAlignments:
         check(lib().lcty_reads_n_good(self._h, C.byref(n)))
         return int(n.value)
 
+    def score_routes(self):
+        """lcty_reads_score_routes: which scoring kernel took which pair in the last scoring launch. A dict of n_pairs, n_lean, n_two,
+        n_general (they sum to n_pairs), lean_form (cdefs.LEAN_FORM_*), two_ran and route, one cdefs.ROUTE_* per pair of that launch."""
+        route = np.full(self.n_pairs, 0xFF, dtype=np.uint8)
+        r = cdefs.ScoreRoutes()
+        r.route = route.ctypes.data if len(route) else None
+        check(lib().lcty_reads_score_routes(self._h, C.byref(r)))
+        out = {n: int(getattr(r, n)) for n in ("n_pairs", "n_lean", "n_two", "n_general", "lean_form")}
+        out["two_ran"] = bool(r.two_ran)
+        out["route"] = route[:out["n_pairs"]]
+        return out
+
     def status(self):
         n = self.n_pairs
         status = np.zeros(n, dtype=np.uint8)

@@ -664,6 +664,15 @@ class GenomeCountStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if not n.startswith("_")}
 
 
+ROUTE_LEAN, ROUTE_TWO, ROUTE_GENERAL = 0, 1, 2                      # LCTY_ROUTE_*: the scoring kernel that took a pair
+LEAN_FORM_NONE, LEAN_FORM_INDEX, LEAN_FORM_KEEP = 0, 1, 2           # LCTY_LEAN_FORM_*
+
+
+class ScoreRoutes(C.Structure):        # lcty_score_routes
+    _fields_ = [(n, C.c_uint64) for n in ("n_pairs", "n_lean", "n_two", "n_general")] + \
+               [("lean_form", C.c_int32), ("two_ran", C.c_int32), ("route", C.c_void_p)]
+
+
 class BgzfStats(C.Structure):          # lcty_bgzf_stats
     _fields_ = [(n, C.c_uint64) for n in ("n_blocks", "bytes_in", "bytes_out")] + \
                [(n, C.c_double) for n in ("ms_upload", "ms_kernel", "ms_download", "ms_total")]

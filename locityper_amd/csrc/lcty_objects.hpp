@@ -156,6 +156,10 @@ struct lcty_reads {
     lcty::DevBuf<unsigned int> d_defer_count;
     lcty::DevBuf<uint32_t> d_defer_list2;    // pairs the two-slot form of the lean kernel leaves to the general one
     lcty::DevBuf<unsigned int> d_defer_count2;
+    // what the last launch_score_reads launched (lcty_reads_score_routes): its pairs, LCTY_LEAN_FORM_*, whether the two-slot form ran
+    uint64_t routes_n_pairs = 0;
+    int32_t routes_lean_form = 0;
+    bool routes_two = false;
     lcty::DevBuf<unsigned long long> d_score_dbg;            // lcty_ctx_set_knob "score_timing"
     lcty::DevBuf<double> d_recover_w;        // per pair: read weight when the pair reaches recover_and_group_alignments, else -1
 

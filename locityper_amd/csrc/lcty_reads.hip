@@ -437,6 +437,7 @@ int32_t lcty_reads_reset(lcty_reads* R, lcty_locus* locus) {
         R->max_recs_per_pair = R->max_cigar_per_pair = R->max_cigar_per_rec = 0;
         R->scored = false; R->counted = false; R->raw_first = 0; R->pa_at_raw_first = 0;
         R->good_valid = false; R->loc_table_valid = false; R->n_scores = 0; R->n_good_cached = 0;
+        R->routes_n_pairs = 0; R->routes_lean_form = LCTY_LEAN_FORM_NONE; R->routes_two = false;
         R->ctx->activate();
         hipStream_t s = R->ctx->copy_stream();
         R->d_err.zero(s); R->d_pa_count.zero(s);
@@ -499,6 +500,39 @@ int32_t lcty_reads_n_good(lcty_reads* reads, uint64_t* out) {
         uint64_t g = 0;
         for (uint8_t v : status) g += v == LCTY_READ_GOOD;
         *out = g;
+    });
+}
+
+// which kernel took which pair in the last scoring launch: launch_score_reads noted its launches on the host, the two hand-off
+// lists and their counts are still on the device (lcty_score.hip)
+int32_t lcty_reads_score_routes(lcty_reads* reads, lcty_score_routes* out) {
+    return guarded([&] {
+        require_scored(reads);
+        if (!out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        hipStream_t s = reads->ctx->stream;
+        const uint64_t n = reads->routes_n_pairs;
+        const bool lean = reads->routes_lean_form != LCTY_LEAN_FORM_NONE && n > 0, two = lean && reads->routes_two;
+        unsigned int c1 = 0, c2 = 0;
+        if (lean) reads->d_defer_count.download(&c1, 1, s);
+        if (two) reads->d_defer_count2.download(&c2, 1, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+        if (c1 > n || c2 > c1) fail(LCTY_ERR_RUNTIME, "hand-off counts of the scoring kernels out of range (%u, %u of %llu pairs)", c1, c2,
+                                    static_cast<unsigned long long>(n));
+        out->n_pairs = n;
+        out->lean_form = n > 0 ? reads->routes_lean_form : LCTY_LEAN_FORM_NONE;
+        out->two_ran = two ? 1 : 0;
+        out->n_lean = lean ? n - c1 : 0;
+        out->n_two = two ? c1 - c2 : 0;
+        out->n_general = lean ? (two ? c2 : c1) : n;
+        if (out->route && n > 0) {
+            std::vector<uint32_t> l1(c1), l2(c2);
+            if (c1) reads->d_defer_list.download(l1.data(), c1, s);
+            if (c2) reads->d_defer_list2.download(l2.data(), c2, s);
+            LCTY_HIP(hipStreamSynchronize(s));
+            std::fill(out->route, out->route + n, static_cast<uint8_t>(lean ? LCTY_ROUTE_LEAN : LCTY_ROUTE_GENERAL));
+            for (uint32_t p : l1) { if (p >= n) fail(LCTY_ERR_RUNTIME, "a handed-off pair out of range"); out->route[p] = two ? LCTY_ROUTE_TWO : LCTY_ROUTE_GENERAL; }
+            for (uint32_t p : l2) { if (p >= n) fail(LCTY_ERR_RUNTIME, "a handed-off pair out of range"); out->route[p] = LCTY_ROUTE_GENERAL; }
+        }
     });
 }
 

@@ -1472,6 +1472,7 @@ void launch_score_reads(lcty_reads* reads) {
     if (reads->raw_first == 0) reads->d_pa_count.zero(ctx->stream);
     else reads->d_pa_count.upload(&reads->pa_at_raw_first, 1, ctx->stream);
     R.defer_list = nullptr; R.defer_count = nullptr; R.only_list = nullptr; R.only_count = nullptr;
+    reads->routes_n_pairs = R.n_pairs; reads->routes_lean_form = LCTY_LEAN_FORM_NONE; reads->routes_two = false;
     // Counted batches: the lean kernel first (at most one saved alignment per contig and read end: the rule), the general kernel
     // on the pairs it left. lcty_ctx_set_knob "score_lean" 0: the general kernel on everything.
     const bool lean = reads->counted && !big && !explicit_weights && L.k <= 31 && L.n_alleles <= 16000 && ctx->knob("score_lean", 1) != 0;
@@ -1486,6 +1487,7 @@ void launch_score_reads(lcty_reads* reads) {
             const bool keep = static_cast<size_t>(L.n_alleles) * 33 + 16 <= SCORE_LDS_MAX / 16 && ctx->knob("score_lean_keep", 1) != 0;
             const size_t lean_lds = keep ? LeanLayout<true, false>(L.n_alleles).lds_bytes : LeanLayout<false, false>(L.n_alleles).lds_bytes;
             auto lean_kernel = keep ? score_counted_lean_keep_kernel : score_counted_lean_kernel;
+            reads->routes_lean_form = keep ? LCTY_LEAN_FORM_KEEP : LCTY_LEAN_FORM_INDEX;
 #ifdef LCTY_DIAG
             const bool timing = ctx->diag_knob("score_timing", 0) != 0;
             if (timing) lean_kernel = keep ? score_counted_lean_keep_timed_kernel : score_counted_lean_timed_kernel;
@@ -1521,6 +1523,7 @@ void launch_score_reads(lcty_reads* reads) {
                 const ScoreLaunch tl = score_launch(reads, R.n_pairs, score_counted_lean_two_kernel, two_lds, 8);
                 hipLaunchKernelGGL(score_counted_lean_two_kernel, dim3(tl.grid), dim3(WAVE), two_lds, ctx->stream, L, R2);
                 R.only_list = R2.defer_list; R.only_count = R2.defer_count;
+                reads->routes_two = true;
             }
         }
         hipLaunchKernelGGL(kernel, dim3(general.grid), dim3(WAVE), lds, ctx->stream, L, R, max_recs);
