@@ -3,7 +3,7 @@
 //   <root>/DB/loci/<locus>/haplotypes.fa.gz      alleles                          (lcty_fasta_read)
 //   <root>/DB/loci/<locus>/kmers.bin.lz4 | .br   off-target k-mer counts          (lcty_io_read_file + lcty_kmer_counts_parse)
 //   <root>/PREPROC/distr.gz                      background distributions         (lcty_io_read_file + lcty_bg_from_json)
-//   <root>/OUT/loci/<locus>/aln.bam              the mapper's output              (lcty_bam_read)
+//   <root>/OUT/loci/<locus>/aln.bam              the mapper's output              (lcty_bam_read, or --bam device: lcty_bam_read_device)
 //   <root>/DB/loci/<locus>/haplotypes.paf[.gz]   optional: pairwise haplotype alignments (lcty_paf_read + lcty_locus_set_hap_alns +
 //                                                lcty_recover_alignments: the mapper saw the basis haplotypes only)
 //        -> lcty_locus_create, lcty_reads_create / append, lcty_score_reads, lcty_solve (default scheme)
@@ -11,11 +11,15 @@
 //   <root>/OUT/loci/<locus>/alns/00.bam (+ .bai) read placements on the call      (lcty_assignment_counts + lcty_write_bam)
 //
 // This is what analyze_locus (src/command/genotype.rs:1161-1260) does between the mapper and the output files, and the call sequence
-// INTEGRATION.md describes for the Rust side. Build: see tests/test_gpu_example.py.   ./genotype_dir <root> <locus> [seed]
+// INTEGRATION.md describes for the Rust side. Build: see tests/test_gpu_example.py.
+//   ./genotype_dir <root> <locus> [seed] [--bam host|device] [--no-out-bam]
+// --bam device: aln.bam is read on the device (lcty_bam_read_device) and appended from there (lcty_reads_append_bam); the table comes
+// back to the host (host_copy) only when alns/00.bam is written, which needs the caller's copy. Default: host, as before.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -28,9 +32,19 @@ static void ok(int32_t rc, const char* what) {
 static bool exists(const std::string& p) { FILE* f = std::fopen(p.c_str(), "rb"); if (f) std::fclose(f); return f != nullptr; }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: genotype_dir <root> <locus> [seed]\n"); return 2; }
-    const std::string root = argv[1], locus = argv[2];
-    const uint64_t seed = argc > 3 ? std::strtoull(argv[3], nullptr, 10) : 1;
+    bool bam_on_device = false, out_bam = true;
+    std::vector<const char*> pos;
+    for (int i = 1; i < argc; i++) {
+        if (!std::strcmp(argv[i], "--bam") && i + 1 < argc) {
+            const char* v = argv[++i];
+            if (std::strcmp(v, "host") && std::strcmp(v, "device")) { std::fprintf(stderr, "--bam host|device\n"); return 2; }
+            bam_on_device = !std::strcmp(v, "device");
+        } else if (!std::strcmp(argv[i], "--no-out-bam")) out_bam = false;
+        else pos.push_back(argv[i]);
+    }
+    if (pos.size() < 2) { std::fprintf(stderr, "usage: genotype_dir <root> <locus> [seed] [--bam host|device] [--no-out-bam]\n"); return 2; }
+    const std::string root = pos[0], locus = pos[1];
+    const uint64_t seed = pos.size() > 2 ? std::strtoull(pos[2], nullptr, 10) : 1;
     const std::string db = root + "/DB/loci/" + locus, outd = root + "/OUT/loci/" + locus;
 
     // background distributions
@@ -63,23 +77,26 @@ int main(int argc, char** argv) {
     lcty_io_free(buf);
 
     // the mapper's alignments
+    lcty_ctx* ctx = nullptr;
+    ok(lcty_ctx_create(0, &ctx), "context");
     lcty_bam_table* bam = nullptr;
-    ok(lcty_bam_read((outd + "/aln.bam").c_str(), names.data(), A, bg.is_paired, &bam), "aln.bam");
-    lcty_reads_host table; const uint64_t* name_off = nullptr; const char* read_names = nullptr; uint32_t n_refs = 0;
-    ok(lcty_bam_table_view(bam, &table, &name_off, &read_names, &n_refs), "bam view");
+    if (bam_on_device) ok(lcty_bam_read_device(ctx, (outd + "/aln.bam").c_str(), names.data(), A, bg.is_paired, out_bam, &bam, nullptr), "aln.bam (device)");
+    else ok(lcty_bam_read((outd + "/aln.bam").c_str(), names.data(), A, bg.is_paired, &bam), "aln.bam");
+    lcty_reads_host table{}; const uint64_t* name_off = nullptr; const char* read_names = nullptr; uint32_t n_refs = 0;
+    uint64_t R = 0, n_bases = 0, n_recs = 0, n_cigar = 0;
+    ok(lcty_bam_table_sizes(bam, &R, &n_bases, &n_recs, &n_cigar, &n_refs), "bam sizes");
+    if (!bam_on_device || out_bam) ok(lcty_bam_table_view(bam, &table, &name_off, &read_names, &n_refs), "bam view");
 
     lcty_params prm;
     lcty_params_default(&prm);
     prm.strict_subset = n_refs < A;                              // locs.rs:486
     ok(lcty_params_resolve(&prm, &bg), "params");
-    lcty_ctx* ctx = nullptr;
-    ok(lcty_ctx_create(0, &ctx), "context");
     lcty_locus* loc = nullptr;
     ok(lcty_locus_create(ctx, A, seqs.data(), seq_off.data(), counts.data(), cnt_off.data(), k, &bg, &prm, &loc), "locus");
-    const uint64_t R = table.n_pairs;
     lcty_reads* reads = nullptr;
-    ok(lcty_reads_create(loc, R, table.mate_off[2 * R], table.aln_off[R], table.cigar_off[R], &reads), "reads");
-    ok(lcty_reads_append(reads, &table), "append");
+    ok(lcty_reads_create(loc, R, n_bases, n_recs, n_cigar, &reads), "reads");
+    if (bam_on_device) ok(lcty_reads_append_bam(reads, bam, 0, R), "append (device)");
+    else ok(lcty_reads_append(reads, &table), "append");
     ok(lcty_score_reads(reads), "AllAlignments::load");
 
     // haplotypes.paf[.gz]: the mapper saw the basis haplotypes only; the alignments reach the other alleles through the pairwise
@@ -158,15 +175,17 @@ int main(int argc, char** argv) {
     uint64_t n_rec = 0;
     // after alignment recovery the batch's record table (the mapper's records + the transferred alignments) comes back from the device
     std::vector<uint64_t> m_aln_off, m_cig_off; std::vector<lcty_aln_rec> m_recs; std::vector<uint32_t> m_cigar;
-    if (recovered) {
+    if (recovered && out_bam) {
         m_aln_off.resize(R + 1); m_cig_off.resize(R + 1);
         ok(lcty_reads_get_records(reads, m_aln_off.data(), nullptr, 0, m_cig_off.data(), nullptr, 0), "records (size)");
         m_recs.resize(m_aln_off[R] + 1); m_cigar.resize(m_cig_off[R] + 1);
         ok(lcty_reads_get_records(reads, m_aln_off.data(), m_recs.data(), m_recs.size(), m_cig_off.data(), m_cigar.data(), m_cigar.size()), "records");
         table.aln_off = m_aln_off.data(); table.recs = m_recs.data(); table.cigar_off = m_cig_off.data(); table.cigar = m_cigar.data();
     }
-    ok(lcty_write_bam((outd + "/alns/00.bam").c_str(), reads, &table, name_off, read_names, nullptr, nullptr, names.data(), best, 2,
-                      static_cast<uint16_t>(attempts), read_off.data(), cnts.data(), &n_rec), "write_bam");
+    // qualities: lcty_bam_table_quals hands out the primary records' (pass them in place of the two NULLs to keep them in the output)
+    if (out_bam)
+        ok(lcty_write_bam((outd + "/alns/00.bam").c_str(), reads, &table, name_off, read_names, nullptr, nullptr, names.data(), best, 2,
+                          static_cast<uint16_t>(attempts), read_off.data(), cnts.data(), &n_rec), "write_bam");
 
     std::printf("genotype %s,%s quality %.1f reads %llu unexplained %u warnings %u bam_records %llu recovered %llu\n", names[best[0]], names[best[1]],
                 call.quality, static_cast<unsigned long long>(call.n_good), call.unexpl_reads, call.warnings, static_cast<unsigned long long>(n_rec),

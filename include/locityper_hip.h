@@ -270,6 +270,8 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       index points at are the same, the deflate bytes differ); any other value, a negative one included, is refused by this call with
  *       LCTY_ERR_INVALID_INPUT naming the knob;   "bgzf_deflate_max_bytes"   input bytes one slice of lcty_bgzf_deflate takes to the
  *       device (default 256 MB; the output does not depend on it; below 0xff00, one block, lcty_bgzf_deflate is LCTY_ERR_INVALID_INPUT).
+ *       "aln_bam_max_slice_bytes"   inflated bytes lcty_bam_read_device may take (default 2^33; a larger file is LCTY_ERR_UNSUPPORTED
+ *       naming this knob, before anything is allocated); its inflate follows "sample_bam_inflate".
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -993,6 +995,33 @@ typedef struct lcty_bam_table lcty_bam_table;
 int32_t lcty_bam_read(const char* path, const char* const* names, uint32_t n_alleles, int32_t paired, lcty_bam_table** out);
 int32_t lcty_bam_table_view(const lcty_bam_table* t, lcty_reads_host* view, const uint64_t** name_off, const char** name_blob, uint32_t* n_refs);
 void    lcty_bam_table_free(lcty_bam_table* t);
+/* The same file read on the device (src/model/locs.rs:405-461, 502-567, 1116-1150, as lcty_bam_read): the file is inflated into one
+ * slice (host pool, or the device with knob "sample_bam_inflate" 1), the header is parsed and the record lengths are walked on the
+ * host, everything else — fields, grouping, offsets, CIGAR words, names, qualities, bases — is made by kernels and stays resident on
+ * ctx's device with the handle. host_copy != 0: everything is downloaded once and lcty_bam_table_view gives the view lcty_bam_read
+ * gives for the file, word for word. host_copy == 0: only the per-pair arrays (mate_len, mate_off, aln_off, cigar_off, names) come
+ * back; lcty_bam_table_view then fails with LCTY_ERR_INVALID_INPUT. Errors: status and text of lcty_bam_read for the same file.
+ * A slice above knob "aln_bam_max_slice_bytes" (default 2^33), or 2^31 - 16 or more records, CIGAR words or 32-base units:
+ * LCTY_ERR_UNSUPPORTED. stats (may be NULL): sizes and the milliseconds of every stage. */
+typedef struct lcty_aln_bam_stats {
+    uint64_t bytes_read, bytes_inflated, blocks, records, pairs, bases, cigar_words;
+    double ms_read, ms_inflate, ms_walk, ms_record, ms_gather, ms_unpack, ms_download, ms_total;
+} lcty_aln_bam_stats;
+int32_t lcty_bam_read_device(lcty_ctx* ctx, const char* path, const char* const* names, uint32_t n_alleles, int32_t paired,
+                             int32_t host_copy, lcty_bam_table** out, lcty_aln_bam_stats* stats);
+/* What lcty_reads_create needs for the table of either reader (locs.rs:1116-1150): pairs, bases (mate_off[2 n_pairs]), records,
+ * CIGAR words, and the reference sequences of the header. Every output may be NULL. */
+int32_t lcty_bam_table_sizes(const lcty_bam_table* t, uint64_t* n_pairs, uint64_t* n_bases, uint64_t* n_recs, uint64_t* n_cigar,
+                             uint32_t* n_refs);
+/* What the handle of either reader holds and the view does not show (locs.rs:1116-1150 reads neither): qual_off[2 n_pairs + 1] into
+ * quals, the qualities of every mate as its primary record stores them (0xFF: absent), and mapq[n_recs]. A device handle needs
+ * host_copy: LCTY_ERR_INVALID_INPUT otherwise. Every output may be NULL. */
+int32_t lcty_bam_table_quals(const lcty_bam_table* t, const uint64_t** qual_off, const uint8_t** quals, const uint8_t** mapq);
+/* Pairs [first_pair, first_pair + n_pairs) of a handle of lcty_bam_read_device appended to a batch of the same context, as
+ * lcty_reads_append of the host view's sub-chunk would (locs.rs:502-567, 1116-1150): records, CIGAR words, bases and nmask go device to
+ * device, the host builds the rebased offsets of the range only. Another context, a handle of lcty_bam_read or a range outside the
+ * table: LCTY_ERR_INVALID_INPUT. */
+int32_t lcty_reads_append_bam(lcty_reads* reads, const lcty_bam_table* t, uint64_t first_pair, uint64_t n_pairs);
 /* DB/loci/<locus>/haplotypes.fa[.gz] (ContigSet::load, src/seq/contigs.rs:295-306): names up to the first blank (0-separated in
  * `names`), upper-cased sequences concatenated, seq_off[n_seqs + 1]. Called twice: with names = seqs = seq_off = NULL it returns the sizes. */
 int32_t lcty_fasta_read(const char* path, uint32_t* n_seqs, char* names, uint64_t* names_len, uint8_t* seqs, uint64_t* seqs_len, uint64_t* seq_off);

@@ -218,6 +218,10 @@ SIGNATURES = {
     "lcty_bam_read": (I32, [C.c_char_p, VP, U32, I32, P(VP)]),
     "lcty_bam_table_view": (I32, [VP, VP, P(VP), P(VP), P(U32)]),
     "lcty_bam_table_free": (None, [VP]),
+    "lcty_bam_read_device": (I32, [VP, C.c_char_p, VP, U32, I32, I32, P(VP), VP]),
+    "lcty_bam_table_sizes": (I32, [VP, P(U64), P(U64), P(U64), P(U64), P(U32)]),
+    "lcty_bam_table_quals": (I32, [VP, P(VP), P(VP), P(VP)]),
+    "lcty_reads_append_bam": (I32, [VP, VP, U64, U64]),
     "lcty_fasta_read": (I32, [C.c_char_p, P(U32), VP, P(U64), VP, P(U64), VP]),
     "lcty_paf_read": (I32, [C.c_char_p, P(C.c_char_p), U32, P(U64), VP, VP, VP, VP, VP, VP, P(U64), VP]),
     "lcty_distances_parse": (I32, [VP, U64, U32, P(U32), P(U32), VP]),

@@ -262,6 +262,14 @@ class AllAlignments:
             check(lib().lcty_reads_append(self._h, C.byref(hs)))
         self._scored = False
 
+    def append_bam(self, table, first=0, n=None):
+        """lcty_reads_append_bam: pairs [first, first + n) of an io.BamTable read on this batch's context (BamTable(.., ctx=ctx)),
+        device to device; n None: up to the table's last pair."""
+        if n is None:
+            n = table.n_pairs - first
+        check(lib().lcty_reads_append_bam(self._h, table._h, first, n))
+        self._scored = False
+
     def score(self):
         check(lib().lcty_score_reads(self._h))
         self._scored = True

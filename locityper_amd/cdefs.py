@@ -689,6 +689,14 @@ class BgzfDeflateStats(C.Structure):   # lcty_bgzf_deflate_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AlnBamStats(C.Structure):        # lcty_aln_bam_stats
+    _fields_ = [(n, C.c_uint64) for n in ("bytes_read", "bytes_inflated", "blocks", "records", "pairs", "bases", "cigar_words")] + \
+               [(n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_walk", "ms_record", "ms_gather", "ms_unpack", "ms_download", "ms_total")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SampleBamStats(C.Structure):     # lcty_sample_bam_stats
     _fields_ = [(n, C.c_uint64) for n in ("n_regions", "n_chunks", "file_bytes", "bytes_read", "blocks_inflated", "bytes_inflated", "records_walked",
                                           "records_primary", "records_kept", "n_pairs", "n_discarded")] + \

@@ -21,6 +21,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "lcty_aln_bam.hpp"
 #include "lcty_bg_reads.hpp"
 #include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
@@ -358,17 +359,6 @@ std::string json_str(const std::string& s) {
 }
 
 }  // namespace
-
-// aln.bam as the flat table of the boundary (+ what only file writers need: names, qualities)
-struct lcty_bam_table {
-    std::vector<uint32_t> mate_len; std::vector<uint64_t> mate_off; std::vector<uint32_t> bases2, nmask;
-    std::vector<uint64_t> aln_off; std::vector<lcty_aln_rec> recs; std::vector<uint64_t> cigar_off; std::vector<uint32_t> cigar;
-    std::vector<uint64_t> name_off; std::string names;
-    std::vector<uint8_t> quals; std::vector<uint64_t> qual_off;       // per mate, BAM orientation (0xFF: absent)
-    std::vector<uint8_t> mapq;                                        // per record
-    uint32_t n_refs = 0;
-    lcty_reads_host view{};
-};
 
 namespace {
 
@@ -710,6 +700,7 @@ int32_t lcty_bam_read(const char* path, const char* const* names, uint32_t n_all
 int32_t lcty_bam_table_view(const lcty_bam_table* t, lcty_reads_host* view, const uint64_t** name_off, const char** name_blob, uint32_t* n_refs) {
     return guarded([&] {
         if (!t || !view) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (!t->host_copy) fail(LCTY_ERR_INVALID_INPUT, "the table was read on the device without host_copy: there is no host view (lcty_bam_table_sizes, lcty_reads_append_bam)");
         *view = t->view;
         if (name_off) *name_off = t->name_off.data();
         if (name_blob) *name_blob = t->names.data();

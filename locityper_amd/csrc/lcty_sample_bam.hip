@@ -455,28 +455,7 @@ bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const 
         fail(LCTY_ERR_UNSUPPORTED, "%s: the fetched slice has %llu bytes, more than %llu (knob sample_bam_max_slice_bytes)", path,
              static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
 
-    // ---- inflate: every block into its place of one page-locked buffer
-    ctx->activate();
-    hipStream_t s = ctx->stream;
-    F.total = total;
-    LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&F.slice), total + SLICE_PAD, hipHostMallocDefault));
-    memset(F.slice + total, 0, SLICE_PAD);
-    t0 = now_ms();
-    // knob "sample_bam_inflate" 1: on the device, straight into the buffer record_kernel reads, and from there to the page-locked
-    // slice for the walk and the writer; blocks with more in their gzip header than the extra field leave the call to zlib
-    bool on_device = ctx->knob("sample_bam_inflate", 0) == 1 && total > 0;
-    for (const BgzfBlock& b : blocks) if (b.isize && (!b.head || b.head + 8u > b.csize)) on_device = false;
-    if (on_device) {
-        DevBuf<uint8_t> d_comp;
-        d_comp.alloc(comp.size()); d_raw.alloc(total + SLICE_PAD);
-        d_comp.upload(comp.data(), comp.size(), s);
-        LCTY_HIP(hipMemsetAsync(d_raw.p + total, 0, SLICE_PAD, s));
-        bgzf_inflate_device(ctx, d_comp.p, comp.size(), blocks, d_raw.p, total, s, path);
-        d_raw.download(F.slice, total, s);
-        LCTY_HIP(hipStreamSynchronize(s));
-    } else bgzf_inflate_host(comp.data(), blocks, F.slice, path);
-    S.ms_inflate = now_ms() - t0;
-    std::vector<uint8_t>().swap(comp);
+    const bool on_device = inflate_slice(ctx, comp, blocks, total, F, d_raw, path, S.ms_inflate);
 
     // ---- the chain of record lengths
     t0 = now_ms();
@@ -497,6 +476,33 @@ bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const 
     S.ms_walk = now_ms() - t0;
     if (n_rec >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "%s: %llu records in one fetch", path, static_cast<unsigned long long>(n_rec));
 
+    return on_device;
+}
+
+bool inflate_slice(lcty_ctx* ctx, std::vector<uint8_t>& comp, const std::vector<BgzfBlock>& blocks, uint64_t total, FetchedSlice& F,
+                   DevBuf<uint8_t>& d_raw, const char* path, double& ms_inflate) {
+    // ---- inflate: every block into its place of one page-locked buffer
+    ctx->activate();
+    hipStream_t s = ctx->stream;
+    F.total = total;
+    LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&F.slice), total + SLICE_PAD, hipHostMallocDefault));
+    memset(F.slice + total, 0, SLICE_PAD);
+    const double t0 = now_ms();
+    // knob "sample_bam_inflate" 1: on the device, straight into the buffer record_kernel reads, and from there to the page-locked
+    // slice for the walk and the writer; blocks with more in their gzip header than the extra field leave the call to zlib
+    bool on_device = ctx->knob("sample_bam_inflate", 0) == 1 && total > 0;
+    for (const BgzfBlock& b : blocks) if (b.isize && (!b.head || b.head + 8u > b.csize)) on_device = false;
+    if (on_device) {
+        DevBuf<uint8_t> d_comp;
+        d_comp.alloc(comp.size()); d_raw.alloc(total + SLICE_PAD);
+        d_comp.upload(comp.data(), comp.size(), s);
+        LCTY_HIP(hipMemsetAsync(d_raw.p + total, 0, SLICE_PAD, s));
+        bgzf_inflate_device(ctx, d_comp.p, comp.size(), blocks, d_raw.p, total, s, path);
+        d_raw.download(F.slice, total, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+    } else bgzf_inflate_host(comp.data(), blocks, F.slice, path);
+    ms_inflate = now_ms() - t0;
+    std::vector<uint8_t>().swap(comp);
     return on_device;
 }
 

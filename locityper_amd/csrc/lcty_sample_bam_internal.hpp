@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
 #include "lcty_device.hpp"
 
@@ -148,6 +149,11 @@ void check_regions(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, co
 // left alone and the caller uploads F.slice. Activates the context.
 bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
                  bool with_unmapped, bool whole_file, FetchedSlice& F, DevBuf<uint8_t>& d_raw, lcty_sample_bam_stats& S);
+// The inflate of fetch_slice on its own (lcty_aln_bam.hip reads a whole un-indexed file through it): `blocks` of `comp` into F.slice
+// (page-locked, total + SLICE_PAD bytes, allocated here), by zlib on the host pool or, with knob "sample_bam_inflate" 1 and plain
+// gzip headers, on the device: true, and d_raw holds the slice with its pad. comp is released. Activates the context.
+bool inflate_slice(lcty_ctx* ctx, std::vector<uint8_t>& comp, const std::vector<BgzfBlock>& blocks, uint64_t total, FetchedSlice& F,
+                   DevBuf<uint8_t>& d_raw, const char* path, double& ms_inflate);
 // the name of the record at byte o of a slice
 std::string record_name(const uint8_t* slice, uint64_t o);
 

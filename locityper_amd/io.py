@@ -1,5 +1,6 @@
 """ctypes wrappers of the file-format entry points of liblocityper_hip.so (lcty_io.hip): harness code for tests, bench and examples."""
 import ctypes as C
+import time
 
 import numpy as np
 
@@ -184,12 +185,45 @@ def write_bam(path, aa, chunk, names, allele_names, genotype, attempts, read_off
 
 
 class BamTable:
-    """lcty_bam_read: aln.bam as a ReadsChunk (+ read names)."""
+    """lcty_bam_read: aln.bam as a ReadsChunk (+ read names). ctx: the device route (lcty_bam_read_device) — the arrays are also
+    resident on the context's device, AllAlignments.append_bam appends them from there; with host_copy=False only the per-pair
+    arrays come back: no chunk, no quals(), but sizes(), names and append_bam."""
 
-    def __init__(self, path, names, paired=True):
+    def __init__(self, path, names, paired=True, ctx=None, host_copy=True):
         self._h = VP()
         nm = (C.c_char_p * len(names))(*[s.encode() for s in names])
-        check(lib().lcty_bam_read(str(path).encode(), nm, len(names), int(paired), C.byref(self._h)))
+        self.ctx, self.host_copy, self.stats = ctx, bool(host_copy) or ctx is None, None
+        t0 = time.perf_counter()
+        if ctx is None:
+            check(lib().lcty_bam_read(str(path).encode(), nm, len(names), int(paired), C.byref(self._h)))
+        else:
+            st = cdefs.AlnBamStats()
+            check(lib().lcty_bam_read_device(ctx._h, str(path).encode(), nm, len(names), int(paired), int(bool(host_copy)), C.byref(self._h), C.byref(st)))
+            self.stats = st.as_dict()
+        self.ms_native = 1e3 * (time.perf_counter() - t0)           # the library call alone, without the copies into numpy arrays below
+        self.n_pairs, self.n_bases, self.n_recs, self.n_cigar, self.n_refs = self.sizes()
+        self.view = self.chunk = self.names = None
+        if self.host_copy:
+            self._load_view()
+
+    def sizes(self):
+        """lcty_bam_table_sizes: (pairs, bases, records, CIGAR words, references of the header) — what AllAlignments needs."""
+        a, b, c, d, r = U64(), U64(), U64(), U64(), U32()
+        check(lib().lcty_bam_table_sizes(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(r)))
+        return int(a.value), int(b.value), int(c.value), int(d.value), int(r.value)
+
+    def quals(self):
+        """lcty_bam_table_quals: (qual_off[2 n_pairs + 1], quals as stored, MAPQ per record)."""
+        qo, q, mq = VP(), VP(), VP()
+        check(lib().lcty_bam_table_quals(self._h, C.byref(qo), C.byref(q), C.byref(mq)))
+        n = self.n_pairs
+
+        def arr(p, count, dt):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(dt)), (count,)).copy() if count else np.zeros(0, dtype=dt)
+        qual_off = arr(qo, 2 * n + 1, C.c_uint64)
+        return qual_off, arr(q, int(qual_off[-1]), C.c_uint8), arr(mq, self.n_recs, C.c_uint8)
+
+    def _load_view(self):
         view = cdefs.ReadsHost()
         noff, blob, nref = VP(), VP(), U32()
         check(lib().lcty_bam_table_view(self._h, C.byref(view), C.byref(noff), C.byref(blob), C.byref(nref)))
