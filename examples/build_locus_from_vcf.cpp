@@ -4,7 +4,7 @@
 //   <window.fa[.gz]>       the reference bases of ONE window of the contig that holds the flanks of every allowed expansion,
 //                          [start - E_max, min(end + E_max, contig length)); one record. --win-start gives its position (default 0),
 //                          --contig-len the length of the contig (default: the window's end)
-//   <pangenome.vcf[.gz]>   text VCF, phased GT                                                      (lcty_vcf_open, lcty_vcf_region)
+//   <pangenome.vcf[.gz]>   text VCF, phased GT, read whole                     (lcty_vcf_open, lcty_vcf_region; with --index see below)
 //   <window.counts[.br|.lz4]>  what `jellyfish query` returned for the k-mers of the window, one KmerCounts block of one contig
 //                          ("-" with -e 0: no expansion, no counts)                                  (lcty_kmer_counts_parse)
 //   <contig> <start> <end> <locus> <db_dir>     0-based, half-open  -> <db_dir>/loci/<locus>/
@@ -14,6 +14,9 @@
 //   --only-seqs            haplotypes.fa.gz and ref.bed alone
 //   -e A,B,C               allowed expansions (20000,50000,200000); -w moving window (500); -g reference name (GRCh38)
 //   --leave-out N1,N2      samples / haplotypes / the reference name to leave out; --ignore-overlaps; --unknown F (0.0001); --calc-div
+//   --index [PATH]         the VCF is BGZF with a tabix index (PATH, default <pangenome.vcf.gz>.tbi): only the chunks of the window are
+//                          read, inflated and parsed, on the device (lcty_vcf_indexed_open, lcty_vcf_indexed_fetch); --device-inflate
+//                          inflates them there too (knob "sample_bam_inflate"). The JSON line gains the fetch statistics.
 // The statistics of the step go to stdout as one JSON line.
 //
 // Build: see tests/test_gpu_panvcf_example.py.
@@ -66,7 +69,8 @@ static Counts read_counts(const std::string& path) {
 int main(int argc, char** argv) {
     std::vector<std::string> pos, leave_out;
     std::vector<uint32_t> expansions{20000, 50000, 200000};
-    std::string ref_name = "GRCh38", hap_counts_path;
+    std::string ref_name = "GRCh38", hap_counts_path, index_path;
+    bool indexed = false, device_inflate = false;
     uint32_t moving_window = 500, win_start = 0, contig_len = 0, k_arg = 25;
     double unknown = 0.0001;
     int32_t overlaps_allowed = 0;
@@ -86,13 +90,15 @@ int main(int argc, char** argv) {
         else if (a == "--only-seqs") prm.only_seqs = 1;
         else if (a == "--calc-div") prm.calc_div = 1;
         else if (a == "--win-start") win_start = static_cast<uint32_t>(std::strtoul(next().c_str(), nullptr, 10));
+        else if (a == "--index") { indexed = true; if (i + 1 < argc && std::strlen(argv[i + 1]) > 4 && !std::strcmp(argv[i + 1] + std::strlen(argv[i + 1]) - 4, ".tbi")) index_path = argv[++i]; }
+        else if (a == "--device-inflate") device_inflate = true;
         else if (a == "--contig-len") contig_len = static_cast<uint32_t>(std::strtoul(next().c_str(), nullptr, 10));
         else pos.push_back(a);
     }
     if (pos.size() != 8 || expansions.empty() || (hap_counts_path.empty() && !prm.only_seqs)) {
         std::fprintf(stderr, "usage: build_locus_from_vcf <window.fa> <pangenome.vcf> <window.counts|-> <contig> <start> <end> <locus> <db_dir> "
                              "(--hap-counts <counts.bin> | --only-seqs) [-e A,B,C] [-w W] [-g NAME] [-k K] [--leave-out N1,N2] [--ignore-overlaps] "
-                             "[--unknown F] [--calc-div] [--win-start N] [--contig-len N]\n");
+                             "[--unknown F] [--calc-div] [--win-start N] [--contig-len N] [--index [PATH.tbi]] [--device-inflate]\n");
         return 2;
     }
     const std::string contig = pos[3], locus = pos[6];
@@ -118,9 +124,14 @@ int main(int argc, char** argv) {
     if (pos[2] != "-" && wc.k != k) { std::fprintf(stderr, "the two count tables differ in k (%u, %u)\n", wc.k, k); return 1; }
 
     // the VCF: samples, retained columns, the records of the window, the matrix of the retained columns
-    lcty_vcf* vcf = nullptr; lcty_vcf_view view;
-    ok(lcty_vcf_open(pos[1].c_str(), &vcf), pos[1].c_str());
-    ok(lcty_vcf_view_get(vcf, &view), "vcf view");
+    lcty_vcf* vcf = nullptr; lcty_vcf_indexed* ivcf = nullptr; lcty_vcf_view view;
+    if (indexed) {
+        ok(lcty_vcf_indexed_open(pos[1].c_str(), index_path.empty() ? nullptr : index_path.c_str(), &ivcf), pos[1].c_str());
+        ok(lcty_vcf_indexed_view_get(ivcf, &view), "vcf view");
+    } else {
+        ok(lcty_vcf_open(pos[1].c_str(), &vcf), pos[1].c_str());
+        ok(lcty_vcf_view_get(vcf, &view), "vcf view");
+    }
     const std::string leave_blob = blob_of(leave_out);
     uint32_t n_cols = 0, n_left = 0; uint64_t names_len = 0;
     ok(lcty_panvcf_names(view.n_samples, view.samples, view.ploidy, ref_name.c_str(), static_cast<uint32_t>(leave_out.size()), leave_blob.c_str(), 0, &n_cols, nullptr,
@@ -130,8 +141,15 @@ int main(int argc, char** argv) {
                          col_sample.data(), col_hap.data(), names.data(), names.size(), &names_len, &n_left), "HaplotypeNames::new");
     std::vector<uint8_t> used(view.n_samples, 0);
     for (uint32_t c = 0; c < n_cols; c++) if (col_sample[c] != LCTY_NONE_U32) used[col_sample[c]] = 1;
+    lcty_ctx* ctx = nullptr;
+    ok(lcty_ctx_create(0, &ctx), "lcty_ctx_create");
     lcty_vcf_records recs;
-    ok(lcty_vcf_region(vcf, contig.c_str(), win_start, static_cast<uint32_t>(win_start + win_len), used.data(), &recs), "fetch");
+    lcty_vcf_fetch_stats fs;
+    std::memset(&fs, 0, sizeof(fs));
+    if (indexed) {
+        if (device_inflate) ok(lcty_ctx_set_knob(ctx, "sample_bam_inflate", 1), "knob");
+        ok(lcty_vcf_indexed_fetch(ctx, ivcf, contig.c_str(), win_start, static_cast<uint32_t>(win_start + win_len), used.data(), &recs, &fs), "fetch");
+    } else ok(lcty_vcf_region(vcf, contig.c_str(), win_start, static_cast<uint32_t>(win_start + win_len), used.data(), &recs), "fetch");
     std::vector<int16_t> gt(static_cast<size_t>(recs.n_recs) * n_cols + 1, 0);
     for (uint32_t v = 0; v < recs.n_recs; v++)
         for (uint32_t c = 0; c < n_cols; c++)
@@ -151,8 +169,6 @@ int main(int argc, char** argv) {
     in.unknown_frac = unknown; in.overlaps_allowed = overlaps_allowed;
     if (!prm.only_seqs) { in.hap_counts = hc.counts.data(); in.hap_cnt_off = hc.off.data(); }
 
-    lcty_ctx* ctx = nullptr;
-    ok(lcty_ctx_create(0, &ctx), "lcty_ctx_create");
     lcty_locus_vcf_out out;
     ok(lcty_db_locus_from_vcf(ctx, &in, &prm, &out), "add_locus");
     lcty_ctx_destroy(ctx);
@@ -172,13 +188,23 @@ int main(int argc, char** argv) {
     std::printf("{\"locus\":\"%s\",\"contig\":\"%s\",\"start\":%u,\"end\":%u,\"attempt\":%d,\"allowed_expansion\":%u,\"crop_bits\":%u,\"warn_bits\":%u,"
                 "\"columns\":%u,\"left_out\":%u,\"records\":%u,\"kept_records\":%llu,\"overlaps\":%llu,\"haplotypes\":%u,\"unknown\":%u,\"with_n\":%u,"
                 "\"identical\":%u,\"written\":%u,\"shortest\":%llu,\"filter_ms\":%.3f,\"expand_ms\":%.3f,\"reconstruct_ms\":%.3f,\"chain_ms\":%.3f,"
-                "\"scan_ms\":%.3f,\"gather_ms\":%.3f,\"build_ms\":%.3f,\"total_ms\":%.3f}\n",
+                "\"scan_ms\":%.3f,\"gather_ms\":%.3f,\"build_ms\":%.3f,\"total_ms\":%.3f",
                 locus.c_str(), contig.c_str(), s.start, s.end, s.attempt, s.allowed_expansion, s.crop_bits, s.warn_bits, s.n_cols, n_left, s.n_records,
                 static_cast<unsigned long long>(s.n_kept_records), static_cast<unsigned long long>(s.total_overlaps), s.n_haplotypes, s.n_unknown, s.n_with_n,
                 s.n_identical, out.files.n_kept, static_cast<unsigned long long>(s.shortest), s.filter_ms, s.expand_ms, s.reconstruct_ms, s.recon.chain_ms,
                 s.recon.scan_ms, s.recon.gather_ms, s.build_ms, s.total_ms);
+    if (indexed)
+        std::printf(",\"fetch\":{\"chunks\":%llu,\"file_bytes\":%llu,\"bytes_read\":%llu,\"blocks_inflated\":%llu,\"bytes_inflated\":%llu,\"lines_walked\":%llu,"
+                    "\"records_kept\":%llu,\"read_ms\":%.3f,\"inflate_ms\":%.3f,\"upload_ms\":%.3f,\"lines_ms\":%.3f,\"heads_ms\":%.3f,\"alleles_ms\":%.3f,"
+                    "\"gt_ms\":%.3f,\"download_ms\":%.3f,\"total_ms\":%.3f}",
+                    static_cast<unsigned long long>(fs.n_chunks), static_cast<unsigned long long>(fs.file_bytes), static_cast<unsigned long long>(fs.bytes_read),
+                    static_cast<unsigned long long>(fs.blocks_inflated), static_cast<unsigned long long>(fs.bytes_inflated), static_cast<unsigned long long>(fs.lines_walked),
+                    static_cast<unsigned long long>(fs.records_kept), fs.ms_read, fs.ms_inflate, fs.ms_upload, fs.ms_lines, fs.ms_heads, fs.ms_alleles, fs.ms_gt,
+                    fs.ms_download, fs.ms_total);
+    std::printf("}\n");
     lcty_locus_vcf_out_free(&out);
     lcty_vcf_records_free(&recs);
     lcty_vcf_free(vcf);
+    lcty_vcf_indexed_close(ivcf);
     return 0;
 }

@@ -272,6 +272,8 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       device (default 256 MB; the output does not depend on it; below 0xff00, one block, lcty_bgzf_deflate is LCTY_ERR_INVALID_INPUT).
  *       "aln_bam_max_slice_bytes"   inflated bytes lcty_bam_read_device may take (default 2^33; a larger file is LCTY_ERR_UNSUPPORTED
  *       naming this knob, before anything is allocated); its inflate follows "sample_bam_inflate".
+ *       "vcf_max_slice_bytes"   inflated bytes one lcty_vcf_indexed_fetch may take (default 2^33; a larger window is LCTY_ERR_UNSUPPORTED
+ *       naming this knob, before the slice is allocated or uploaded); its inflate follows "sample_bam_inflate".
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -1271,7 +1273,7 @@ void    lcty_db_files_free(lcty_db_files* files);
  * unique piece of the reference, every phased haplotype of the VCF is rebuilt over the new interval, and the sequences go to
  * lcty_db_build_locus unchanged. Integer and byte work, and one short f64 recipe that is followed to the bit. Positions are 0-based.
  *
- * lcty_vcf_open / _view_get / _region / _free (host): a text VCF — plain, gzip or BGZF, told by its first bytes; no index, no BCF (a
+ * lcty_vcf_open / _view_get / _region / _free (host): a text VCF — plain, gzip or BGZF, told by its first bytes; read whole, no BCF (a
  *   `.bcf` path is LCTY_ERR_UNSUPPORTED). open reads the sample names of the #CHROM line and the ploidies of the FIRST record
  *   (HaplotypeNames::new, panvcf.rs:85-91); a file without records is LCTY_ERR_INVALID_DATA as there. region returns the records htslib's
  *   fetch(start, end) returns — same contig, pos < end, pos + len(REF) > start, in file order; INFO/END is NOT looked at, a stated
@@ -1281,6 +1283,28 @@ void    lcty_db_files_free(lcty_db_files* files);
  *   is '|' (a haploid call has none: 1). sample_used (NULL: all) [n_samples]: for these samples a GT whose allele count differs from the
  *   first record's ploidy ("has ploidy ... (expected ...)", panvcf.rs:161-164) and a sample of ploidy > 1 whose last separator is '/'
  *   ("is unphased", 167-171) are LCTY_ERR_INVALID_DATA. A contig the file does not name gives no records.
+ * lcty_vcf_indexed_open / _view_get / _plan / _fetch / _close: the same records through the file's tabix index, what add_locus does with
+ *   its bcf::IndexedReader (add.rs:802): it fetches the two flanks of a locus (add.rs:496-499) and reconstruct_sequences the interval
+ *   (panvcf.rs, filter_variants), never the whole file. The file must be BGZF (a plain or plain-gzip file is LCTY_ERR_INVALID_INPUT: an
+ *   indexed file must be BGZF); the index is `.tbi` (index_path NULL: path + ".tbi"): a `.csi` index and a `.bcf` file are
+ *   LCTY_ERR_UNSUPPORTED, no index LCTY_ERR_INVALID_INPUT, an index whose format is not 2 (VCF), whose counts are negative or reach
+ *   beyond its bytes, whose names lack their terminators or one of whose chunks begins behind its end LCTY_ERR_INVALID_DATA naming the
+ *   index file. open (host) reads the index and only the head of the file — BGZF blocks from offset 0 until the #CHROM line and the
+ *   first record are complete — and fills the view of lcty_vcf_open (samples, the ploidies of the first record of the FILE, hap_off)
+ *   with n_records = 0: the file is not walked. Its errors (no #CHROM line, a record before it, no records) are lcty_vcf_open's.
+ *   plan (host): the chunks of [start, end) on contig by the rule of lcty_sample_bam_plan — the bins of the region without the chunks
+ *   that end at or before the linear index's offset of its first 16 kb window, sorted, merged where they touch, overlap or meet in one
+ *   BGZF block; chunk_cap / n_chunks / blocks_total as there. fetch (device; add.rs:496-499, panvcf.rs filter_variants): exactly the
+ *   arrays lcty_vcf_region returns for the same file and arguments (the same fetch rule; INFO/END is still not looked at; a contig
+ *   the index does not know gives no records), released with lcty_vcf_records_free. Only the chunks are read and inflated (knob
+ *   "sample_bam_inflate": 0 the host's zlib pool, 1 the device); line starts, record heads, the allele pool and the records x samples
+ *   GT matrix are made by kernels on the inflated text (lcty_vcf_fetch.hip). The first offending line in file order —
+ *   a record of the window with a wrong column count, no GT, an unparsable genotype, a ploidy mismatch or an unphased call of a used
+ *   sample, an allele index above 32767, or any line of the chunks that names the contig with a bad position — is handed to the line
+ *   functions of lcty_vcf_open / lcty_vcf_region: status and text are theirs. LCTY_ERR_UNSUPPORTED: a slice above knob
+ *   "vcf_max_slice_bytes" (default 2^33), 2^31 - 16 lines or more, a line of 2^32 bytes or more. Without a device (ctx NULL, none
+ *   visible) fetch is LCTY_ERR_RUNTIME: there is no CPU fallback. stats (may be NULL): chunks, bytes read and inflated, lines walked,
+ *   records kept, the milliseconds of each stage.
  * lcty_panvcf_names (host): HaplotypeNames::new (panvcf.rs:65-135) on samples (n_samples 0-terminated names) and their ploidies: the
  *   retained columns in order (shift_ix), the reference first (col_sample = LCTY_NONE_U32) unless leave_out (n_leave_out 0-terminated
  *   names) holds ref_name; a haplotype is `sample` for ploidy 1, else `sample.<hap_ix + 1>`; leave_out matches a sample or a haplotype.
@@ -1401,6 +1425,23 @@ int32_t lcty_vcf_view_get(const lcty_vcf* vcf, lcty_vcf_view* view);
 int32_t lcty_vcf_region(const lcty_vcf* vcf, const char* contig, uint32_t start, uint32_t end, const uint8_t* sample_used, lcty_vcf_records* out);
 void    lcty_vcf_records_free(lcty_vcf_records* records);
 void    lcty_vcf_free(lcty_vcf* vcf);
+/* the indexed reader (add.rs:496-499, 802; panvcf.rs filter_variants) */
+typedef struct lcty_vcf_indexed lcty_vcf_indexed;
+typedef struct lcty_vcf_fetch_stats {
+    uint64_t n_chunks, file_bytes, bytes_read, blocks_inflated, bytes_inflated;
+    uint64_t lines_walked, records_kept;
+    double ms_read, ms_inflate, ms_upload, ms_lines, ms_heads, ms_alleles, ms_gt, ms_download, ms_total;
+} lcty_vcf_fetch_stats;
+/* host; index_path NULL: path + ".tbi". The view's n_records is 0: the file is not walked (add.rs:802) */
+int32_t lcty_vcf_indexed_open(const char* path, const char* index_path, lcty_vcf_indexed** out);
+int32_t lcty_vcf_indexed_view_get(const lcty_vcf_indexed* vcf, lcty_vcf_view* view);
+/* host: the merged chunks of a window (add.rs:496-499: the flanks; panvcf.rs filter_variants: the interval) */
+int32_t lcty_vcf_indexed_plan(lcty_vcf_indexed* vcf, const char* contig, uint32_t start, uint32_t end, uint64_t chunk_cap,
+                              uint64_t* n_chunks, uint64_t* chunk_beg, uint64_t* chunk_end, uint64_t* blocks_total);
+/* device: the records of a window, the arrays of lcty_vcf_region (add.rs:496-499, panvcf.rs filter_variants) */
+int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char* contig, uint32_t start, uint32_t end,
+                               const uint8_t* sample_used, lcty_vcf_records* out, lcty_vcf_fetch_stats* stats);
+void    lcty_vcf_indexed_close(lcty_vcf_indexed* vcf);
 int32_t lcty_panvcf_names(uint32_t n_samples, const char* samples, const uint32_t* ploidy, const char* ref_name, uint32_t n_leave_out,
                           const char* leave_out, uint32_t cap_cols, uint32_t* n_cols, uint32_t* col_sample, uint32_t* col_hap, char* names,
                           uint64_t cap_names, uint64_t* names_len, uint32_t* n_left_out);

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats, BgzfDeflateStats, ScoreRoutes
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, VcfFetchStats, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats, BgzfDeflateStats, ScoreRoutes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -47,6 +47,11 @@ SIGNATURES = {
     "lcty_vcf_region": (I32, [VP, C.c_char_p, U32, U32, VP, P(VcfRecords)]),
     "lcty_vcf_records_free": (None, [P(VcfRecords)]),
     "lcty_vcf_free": (None, [VP]),
+    "lcty_vcf_indexed_open": (I32, [C.c_char_p, C.c_char_p, P(VP)]),
+    "lcty_vcf_indexed_view_get": (I32, [VP, P(VcfView)]),
+    "lcty_vcf_indexed_plan": (I32, [VP, C.c_char_p, U32, U32, U64, P(U64), VP, VP, P(U64)]),
+    "lcty_vcf_indexed_fetch": (I32, [VP, VP, C.c_char_p, U32, U32, VP, P(VcfRecords), P(VcfFetchStats)]),
+    "lcty_vcf_indexed_close": (None, [VP]),
     "lcty_panvcf_names": (I32, [U32, C.c_char_p, VP, C.c_char_p, U32, C.c_char_p, U32, P(U32), VP, VP, VP, U64, P(U64), P(U32)]),
     "lcty_panvcf_filter": (I32, [VP, U32, U32, VP, VP, P(U64)]),
     "lcty_panvcf_reconstruct": (I32, [VP, C.c_char_p, U32, U32, VP, U32, VP, VP, VP, VP, VP, U32, VP, C.c_char_p, D, I32, P(PanvcfOut)]),

@@ -149,6 +149,11 @@ class VcfRecords(C.Structure):
                 ("allele_bytes", C.c_void_p), ("gt", C.c_void_p), ("phased", C.c_void_p)]
 
 
+class VcfFetchStats(_Dictable):
+    _fields_ = [(n, C.c_uint64) for n in ("n_chunks", "file_bytes", "bytes_read", "blocks_inflated", "bytes_inflated", "lines_walked", "records_kept")] + \
+               [(n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_upload", "ms_lines", "ms_heads", "ms_alleles", "ms_gt", "ms_download", "ms_total")]
+
+
 class PanvcfStats(_Dictable):
     _fields_ = [(n, C.c_uint64) for n in ("bytes_h2d", "bytes_d2h", "n_segments", "out_bytes")] + \
                [(n, C.c_double) for n in ("upload_ms", "rows_ms", "chain_ms", "scan_ms", "gather_ms", "compact_ms", "total_ms")]

@@ -26,6 +26,7 @@
 #include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
+#include "lcty_vcf_index_parse.hpp"
 
 using namespace lcty;
 
@@ -1156,56 +1157,9 @@ struct lcty_vcf {
     lcty_vcf_view view{};
 };
 
-namespace {
-
-struct Field { const char* p; size_t n; };
-
-// the tab-separated fields of [begin, end)
-std::vector<Field> split_tabs(const uint8_t* text, uint64_t begin, uint64_t end) {
-    std::vector<Field> out;
-    uint64_t s = begin;
-    for (uint64_t i = begin; i <= end; i++)
-        if (i == end || text[i] == '\t') { out.push_back({reinterpret_cast<const char*>(text) + s, size_t(i - s)}); s = i + 1; }
-    return out;
-}
-
-// The GT subfield of one sample: allele indices (-1 for '.') and whether the separator before the last allele is '|' (a haploid call has
-// none and counts as phased). `which` = position of GT among the FORMAT keys.
-void parse_gt(Field sample, size_t which, std::vector<int32_t>& alleles, bool& phased, const std::string& where) {
-    const char* p = sample.p; const char* e = sample.p + sample.n;
-    for (size_t skip = 0; skip < which && p < e; skip++) { while (p < e && *p != ':') p++; if (p < e) p++; else { p = e; } }
-    const char* q = p;
-    while (q < e && *q != ':') q++;
-    alleles.clear(); phased = true;
-    if (p == q) { alleles.push_back(-1); return; }                     // a dropped trailing field: one missing allele
-    while (p < q) {
-        if (*p == '.') { alleles.push_back(-1); p++; }
-        else {
-            if (*p < '0' || *p > '9') fail(LCTY_ERR_INVALID_DATA, "Variant %s: cannot parse the genotype '%.*s'", where.c_str(), int(sample.n), sample.p);
-            int64_t v = 0;
-            while (p < q && *p >= '0' && *p <= '9') { v = v * 10 + (*p - '0'); if (v > 32767) fail(LCTY_ERR_UNSUPPORTED, "Variant %s: allele index above 32767", where.c_str()); p++; }
-            alleles.push_back(static_cast<int32_t>(v));
-        }
-        if (p < q) {
-            if (*p != '/' && *p != '|') fail(LCTY_ERR_INVALID_DATA, "Variant %s: cannot parse the genotype '%.*s'", where.c_str(), int(sample.n), sample.p);
-            phased = *p == '|';
-            p++;
-            if (p == q) fail(LCTY_ERR_INVALID_DATA, "Variant %s: cannot parse the genotype '%.*s'", where.c_str(), int(sample.n), sample.p);
-        }
-    }
-}
-
-size_t gt_index(Field format, const std::string& where) {
-    size_t ix = 0, s = 0;
-    for (size_t i = 0; i <= format.n; i++)
-        if (i == format.n || format.p[i] == ':') {
-            if (i - s == 2 && format.p[s] == 'G' && format.p[s + 1] == 'T') return ix;
-            ix++; s = i + 1;
-        }
-    fail(LCTY_ERR_INVALID_DATA, "Variant %s has no GT field", where.c_str());
-}
-
-}  // namespace
+// the line rules (split_tabs, parse_gt, gt_index, the head of a record, a record of a region) are in lcty_vcf_index_parse.hpp: the indexed
+// reader (lcty_vcf_fetch.hip) raises its errors through the same functions
+using namespace lcty::vcfidx;
 
 extern "C" {
 
@@ -1229,45 +1183,29 @@ int32_t lcty_vcf_open(const char* path, lcty_vcf** out) {
             if (le > b) {
                 if (t[b] == '#') {
                     if (le - b >= 6 && !memcmp(&t[b], "#CHROM", 6)) {
-                        const std::vector<Field> f = split_tabs(t.data(), b, le);
-                        if (f.size() < 8) fail(LCTY_ERR_INVALID_DATA, "%s: the #CHROM line has %zu columns", path, f.size());
-                        for (size_t i = 9; i < f.size(); i++) V->samples.emplace_back(f[i].p, f[i].n);
+                        parse_chrom_line(t.data(), b, le, path, V->samples);
                         have_header = true;
                     }
                 } else {
-                    if (!have_header) fail(LCTY_ERR_INVALID_DATA, "%s: a record comes before the #CHROM line", path);
-                    // CHROM, POS, ID, REF
-                    uint64_t c[4]; uint32_t nc = 0;
-                    for (uint64_t i = b; i < le && nc < 4; i++) if (t[i] == '\t') c[nc++] = i;
-                    if (nc < 4) fail(LCTY_ERR_INVALID_DATA, "%s: a record has fewer than five columns", path);
-                    const std::string chrom(reinterpret_cast<const char*>(&t[b]), c[0] - b);
-                    uint64_t pos = 0;
-                    if (c[1] == c[0] + 1) fail(LCTY_ERR_INVALID_DATA, "%s: a record of %s has no position", path, chrom.c_str());
-                    for (uint64_t i = c[0] + 1; i < c[1]; i++) {
-                        if (t[i] < '0' || t[i] > '9' || pos > 0xFFFFFFFFull) fail(LCTY_ERR_INVALID_DATA, "%s: bad position in a record of %s", path, chrom.c_str());
-                        pos = pos * 10 + (t[i] - '0');
-                    }
-                    if (pos < 1 || pos > 0xFFFFFFFFull) fail(LCTY_ERR_INVALID_DATA, "%s: bad position in a record of %s", path, chrom.c_str());
+                    if (!have_header) fail_record_before_header(path);
+                    const LineHead h = parse_line_head(t.data(), b, le, path);                                    // CHROM, POS, len(REF)
+                    const std::string& chrom = h.chrom;
                     auto it = contig_ix.find(chrom);
                     if (it == contig_ix.end()) { it = contig_ix.emplace(chrom, static_cast<uint32_t>(V->contigs.size())).first; V->contigs.push_back(chrom); }
-                    V->lines.push_back({b, le, it->second, static_cast<uint32_t>(pos - 1), static_cast<uint32_t>(c[3] - c[2] - 1)});
+                    V->lines.push_back({b, le, it->second, h.pos, h.ref_len});
                 }
             }
             b = e + 1;
         }
-        if (!have_header) fail(LCTY_ERR_INVALID_DATA, "%s has no #CHROM line", path);
-        if (V->lines.empty()) fail(LCTY_ERR_INVALID_DATA, "Input VCF file does not contain any records");          // panvcf.rs:85-86
+        if (!have_header) fail_no_header(path);
+        if (V->lines.empty()) fail_no_records();
         // the ploidies of the first record
         const uint32_t S = static_cast<uint32_t>(V->samples.size());
         V->ploidy.assign(S, 0); V->hap_off.assign(S + 1, 0);
         if (S) {
             const lcty_vcf::Line& l0 = V->lines[0];
             const std::string where = V->contigs[l0.contig] + ":" + std::to_string(uint64_t(l0.pos) + 1);
-            const std::vector<Field> f = split_tabs(t.data(), l0.begin, l0.end);
-            if (f.size() != 9 + size_t(S)) fail(LCTY_ERR_INVALID_DATA, "Variant %s has %zu columns (expected %u)", where.c_str(), f.size(), 9 + S);
-            const size_t which = gt_index(f[8], where);
-            std::vector<int32_t> al; bool ph;
-            for (uint32_t i = 0; i < S; i++) { parse_gt(f[9 + i], which, al, ph, where); V->ploidy[i] = static_cast<uint32_t>(al.size()); }
+            first_record_ploidy(t.data(), l0.begin, l0.end, where, S, V->ploidy);
         }
         for (uint32_t i = 0; i < S; i++) { V->hap_off[i + 1] = V->hap_off[i] + V->ploidy[i]; V->sample_blob += V->samples[i]; V->sample_blob.push_back('\0'); }
         V->view.n_samples = S; V->view.n_haps = V->hap_off[S]; V->view.n_records = V->lines.size();
@@ -1293,41 +1231,17 @@ int32_t lcty_vcf_region(const lcty_vcf* vcf, const char* contig, uint32_t start,
         const uint32_t S = vcf->view.n_samples, Hn = vcf->view.n_haps;
         uint32_t cix = LCTY_NONE_U32;
         for (uint32_t i = 0; i < vcf->contigs.size(); i++) if (vcf->contigs[i] == contig) cix = i;
-        std::vector<uint32_t> pos, rlen, rec_allele{0}; std::vector<uint64_t> allele_off{0}; std::vector<uint8_t> pool, phased; std::vector<int16_t> gt;
+        RecordArrays A;
         std::vector<int32_t> al;
         const uint8_t* t = vcf->text.data();
         for (const lcty_vcf::Line& l : vcf->lines) {
             if (l.contig != cix || !(l.pos < end && uint64_t(l.pos) + l.ref_len > start)) continue;          // htslib's fetch; INFO/END is not looked at
-            const std::string where = std::string(contig) + ":" + std::to_string(uint64_t(l.pos) + 1);       // format_var, panvcf.rs:187-193
-            const std::vector<Field> f = split_tabs(t, l.begin, l.end);
-            if (f.size() != (S ? 9 + size_t(S) : f.size()) || f.size() < 8) fail(LCTY_ERR_INVALID_DATA, "Variant %s has %zu columns (expected %u)", where.c_str(), f.size(), 9 + S);
-            pos.push_back(l.pos); rlen.push_back(l.ref_len);
-            pool.insert(pool.end(), f[3].p, f[3].p + f[3].n); allele_off.push_back(pool.size());
-            if (!(f[4].n == 1 && f[4].p[0] == '.')) {
-                size_t s = 0;
-                for (size_t i = 0; i <= f[4].n; i++)
-                    if (i == f[4].n || f[4].p[i] == ',') { pool.insert(pool.end(), f[4].p + s, f[4].p + i); allele_off.push_back(pool.size()); s = i + 1; }
-            }
-            rec_allele.push_back(static_cast<uint32_t>(allele_off.size() - 1));
-            if (!S) continue;
-            const size_t which = gt_index(f[8], where);
-            for (uint32_t i = 0; i < S; i++) {
-                bool ph = true;
-                parse_gt(f[9 + i], which, al, ph, where);
-                const uint32_t pl = vcf->ploidy[i];
-                const bool used = !sample_used || sample_used[i];
-                if (used && al.size() != pl)                                                                 // panvcf.rs:161-164
-                    fail(LCTY_ERR_INVALID_DATA, "Variant %s in sample %s has ploidy %zu (expected %u)", where.c_str(), vcf->samples[i].c_str(), al.size(), pl);
-                if (used && pl > 1 && !ph)                                                                   // panvcf.rs:167-171
-                    fail(LCTY_ERR_INVALID_DATA, "Variant %s is unphased in sample %s", where.c_str(), vcf->samples[i].c_str());
-                for (uint32_t h = 0; h < pl; h++) gt.push_back(h < al.size() ? static_cast<int16_t>(al[h]) : int16_t(-1));
-                phased.push_back(ph ? 1 : 0);
-            }
+            parse_record_line(t, l.begin, l.end, contig, l.pos, l.ref_len, S, vcf->ploidy.data(), vcf->samples, sample_used, A, al);
         }
         lcty_vcf_records o{}; Handoff h;
-        o.n_recs = static_cast<uint32_t>(pos.size()); o.n_haps = Hn; o.n_samples = S; o.n_alleles = allele_off.size() - 1; o.pool_len = pool.size();
-        o.pos = h.copy(pos); o.ref_len = h.copy(rlen); o.rec_allele = h.copy(rec_allele);
-        o.allele_off = h.copy(allele_off); o.allele_bytes = h.copy(pool); o.gt = h.copy(gt); o.phased = h.copy(phased);
+        o.n_recs = static_cast<uint32_t>(A.pos.size()); o.n_haps = Hn; o.n_samples = S; o.n_alleles = A.allele_off.size() - 1; o.pool_len = A.pool.size();
+        o.pos = h.copy(A.pos); o.ref_len = h.copy(A.rlen); o.rec_allele = h.copy(A.rec_allele);
+        o.allele_off = h.copy(A.allele_off); o.allele_bytes = h.copy(A.pool); o.gt = h.copy(A.gt); o.phased = h.copy(A.phased);
         *out = o; h.commit();
     });
 }

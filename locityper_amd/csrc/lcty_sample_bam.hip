@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void offsets_kernel(const uint32_t* __restrict
 
 // ---- host: BGZF by block, the header, the index ---------------------------------------------------------------------------------
 
-static void pread_all(int fd, void* buf, size_t n, uint64_t at, const char* path) {
+void pread_all(int fd, void* buf, size_t n, uint64_t at, const char* path) {
     uint8_t* p = static_cast<uint8_t*>(buf);
     while (n) {
         const ssize_t got = pread(fd, p, n, static_cast<off_t>(at));
@@ -202,53 +202,13 @@ static void pread_all(int fd, void* buf, size_t n, uint64_t at, const char* path
         p += got; n -= static_cast<size_t>(got); at += static_cast<uint64_t>(got);
     }
 }
-static void inflate_block(z_stream& zs, const uint8_t* in, uint32_t csize, uint8_t* out, uint32_t isize, const char* path) {
+void inflate_block(z_stream& zs, const uint8_t* in, uint32_t csize, uint8_t* out, uint32_t isize, const char* path) {
     zs.next_in = const_cast<Bytef*>(in); zs.avail_in = csize;
     zs.next_out = out; zs.avail_out = isize;
     const int rc = inflate(&zs, Z_FINISH);
     if (rc != Z_STREAM_END || zs.avail_out != 0) fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BGZF block (zlib %d)", path, rc);
     if (inflateReset(&zs) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateReset");
 }
-
-// the blocks of a BGZF file one after the other, from its start: the header and the first record
-struct BgzfSerial {
-    int fd; uint64_t fsize; const char* path;
-    uint64_t coff = 0, next = 0;                 // the block in `data`, the one behind it
-    std::vector<uint8_t> data; size_t at = 0;
-    z_stream zs;
-    BgzfSerial(int fd_, uint64_t fsize_, const char* path_) : fd(fd_), fsize(fsize_), path(path_) {
-        memset(&zs, 0, sizeof(zs));
-        if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateInit2");
-    }
-    ~BgzfSerial() { inflateEnd(&zs); }
-    bool load() {                                // the next block that holds data; false at the end of the file
-        while (at == data.size()) {
-            if (next >= fsize) return false;
-            uint8_t buf[0x10000];
-            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(buf), fsize - next));
-            pread_all(fd, buf, n, next, path);
-            const uint32_t csize = bgzf_block_size(buf, n);
-            if (!csize || csize > n) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu", path, static_cast<unsigned long long>(next));
-            const uint32_t isize = buf[csize - 4] | (buf[csize - 3] << 8) | (buf[csize - 2] << 16) | (static_cast<uint32_t>(buf[csize - 1]) << 24);
-            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
-            data.resize(isize);
-            if (isize) inflate_block(zs, buf, csize, data.data(), isize, path); else if (inflateReset(&zs) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateReset");
-            coff = next; next += csize; at = 0;
-        }
-        return true;
-    }
-    bool read(void* out, size_t n) {             // false: the file ends first
-        uint8_t* p = static_cast<uint8_t*>(out);
-        while (n) {
-            if (!load()) return false;
-            const size_t take = std::min(n, data.size() - at);
-            memcpy(p, data.data() + at, take);
-            p += take; n -= take; at += take;
-        }
-        return true;
-    }
-    uint64_t tell() { return at == data.size() ? next << 16 : (coff << 16) | at; }
-};
 
 void bgzf_inflate_host(const uint8_t* comp, const std::vector<BgzfBlock>& blocks, uint8_t* out, const char* path) {
     const uint32_t n_threads = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>({blocks.size() / 64 + 1, 16, std::thread::hardware_concurrency()})));
@@ -340,39 +300,17 @@ void load_bai(lcty_sample_bam* b) {
     if (at + 8 <= x.size()) { b->n_no_coor = u64(); b->has_no_coor = true; }
 }
 
-// the chunks of a call: reg2bins (SAM specification 5.3), the linear index's cut, sorted and merged
+// the chunks of a call: those of its regions (region_chunks) and the tail of the file, sorted and merged (merge_chunks,
+// lcty_vcf_index_parse.hpp: the rule the tabix index of lcty_vcf_fetch.hip follows too)
 std::vector<Chunk> plan_chunks(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end, bool with_unmapped,
                                bool whole_file) {
     std::vector<Chunk> cs;
     const uint64_t file_end = b->fsize << 16;
     if (whole_file) { cs.push_back(Chunk{b->first_record, file_end}); return cs; }
-    for (uint32_t i = 0; i < n; i++) {
-        const lcty_sample_bam::Ref& R = b->refs[tid[i]];
-        const uint32_t beg = std::min(start[i], (1u << 29) - 1), e = std::min(end[i], 1u << 29) - 1;      // e: last base, inclusive
-        uint64_t min_off = 0;
-        if (!R.linear.empty()) min_off = R.linear[std::min<size_t>(beg >> 14, R.linear.size() - 1)];
-        auto take = [&](uint32_t bin) {
-            auto it = R.bins.find(bin);
-            if (it == R.bins.end()) return;
-            for (const Chunk& c : it->second) if (c.end > min_off && c.beg < c.end) cs.push_back(c);
-        };
-        take(0);
-        static const uint32_t first[5] = {1, 9, 73, 585, 4681}, shift[5] = {26, 23, 20, 17, 14};
-        for (int l = 0; l < 5; l++) for (uint32_t k = first[l] + (beg >> shift[l]); k <= first[l] + (e >> shift[l]); k++) take(k);
-    }
+    for (uint32_t i = 0; i < n; i++) region_chunks(b->refs[tid[i]], start[i], end[i], cs);
     if (with_unmapped && b->tail_start < file_end) cs.push_back(Chunk{b->tail_start, file_end});
-    std::sort(cs.begin(), cs.end(), [](const Chunk& a, const Chunk& c) { return a.beg != c.beg ? a.beg < c.beg : a.end < c.end; });
-    std::vector<Chunk> merged;
-    for (const Chunk& c : cs) {
-        // touching, overlapping, or starting in the block the last one ends in: one chunk (the records between are walked and filtered)
-        if (!merged.empty() && (c.beg >> 16) <= (merged.back().end >> 16)) merged.back().end = std::max(merged.back().end, c.end);
-        else merged.push_back(c);
-    }
-    return merged;
+    return merge_chunks(cs);
 }
-
-// a chunk's blocks as they lie in the file
-struct ChunkSpan { size_t first_block, n_blocks; uint64_t chain_beg, chain_end, span_end; };
 
 }  // namespace
 
@@ -396,6 +334,66 @@ std::string record_name(const uint8_t* slice, uint64_t o) {
     return s;
 }
 
+void read_chunk_blocks(int fd, uint64_t fsize, const char* path, const std::vector<Chunk>& cs, std::vector<uint8_t>& comp, std::vector<BgzfBlock>& blocks,
+                       std::vector<ChunkSpan>& spans, uint64_t& total, uint64_t& bytes_read) {
+    for (const Chunk& c : cs) {
+        const uint64_t cbeg = c.beg >> 16, cend = c.end >> 16;
+        const uint32_t uend = static_cast<uint32_t>(c.end & 0xFFFF);
+        if (cbeg >= fsize) continue;
+        uint64_t rend = cend;                                              // ... and the block the chunk ends in, when it reaches into it
+        if (uend && cend < fsize) {
+            uint8_t hd[512];
+            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), fsize - cend));
+            pread_all(fd, hd, n, cend, path);
+            const uint32_t csize = bgzf_block_size(hd, n);
+            if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(cend));
+            rend = std::min<uint64_t>(fsize, cend + csize);
+        }
+        rend = std::min<uint64_t>(rend, fsize);
+        const size_t in0 = comp.size();
+        comp.resize(in0 + (rend - cbeg));
+        pread_all(fd, comp.data() + in0, rend - cbeg, cbeg, path);
+        bytes_read += rend - cbeg;
+        ChunkSpan sp{blocks.size(), 0, total + (c.beg & 0xFFFF), 0, 0};
+        bool end_seen = false;
+        uint64_t at = cbeg;
+        while (at < rend && (at < cend || (at == cend && uend))) {
+            const uint8_t* p = comp.data() + in0 + (at - cbeg);
+            const uint32_t csize = bgzf_block_size(p, rend - at);
+            if (!csize || at + csize > rend) {
+                if (at + 0x10000 >= fsize) fail(LCTY_ERR_INVALID_DATA, "%s: truncated or corrupt BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
+                fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(at));
+            }
+            const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
+            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
+            if (at == cbeg && (c.beg & 0xFFFF) > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index starts behind its block", path);
+            if (at == cend) { if (uend > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index ends behind its block", path); sp.chain_end = total + uend; end_seen = true; }
+            blocks.push_back(BgzfBlock{csize, isize, total, in0 + static_cast<size_t>(at - cbeg), at, bgzf_plain_head(p)});
+            total += isize; at += csize;
+        }
+        sp.n_blocks = blocks.size() - sp.first_block; sp.span_end = total;
+        if (!end_seen) sp.chain_end = total;
+        if (sp.n_blocks) spans.push_back(sp);
+    }
+}
+
+uint64_t count_chunk_blocks(int fd, uint64_t fsize, const char* path, const std::vector<Chunk>& cs) {
+    uint64_t blocks = 0;
+    for (const Chunk& c : cs) {
+        uint64_t at = c.beg >> 16;
+        const uint64_t last = c.end >> 16;
+        while (at < fsize && (at < last || (at == last && (c.end & 0xFFFF)))) {
+            uint8_t hd[512];
+            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), fsize - at));
+            pread_all(fd, hd, n, at, path);
+            const uint32_t csize = bgzf_block_size(hd, n);
+            if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
+            blocks++; at += csize;
+        }
+    }
+    return blocks;
+}
+
 bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
                  bool with_unmapped, bool whole_file, FetchedSlice& F, DevBuf<uint8_t>& d_raw, lcty_sample_bam_stats& S) {
     const char* path = bam->path.c_str();
@@ -410,45 +408,7 @@ bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const 
     std::vector<BgzfBlock> blocks;
     std::vector<ChunkSpan> spans;
     uint64_t total = 0;
-    for (const Chunk& c : cs) {
-        const uint64_t cbeg = c.beg >> 16, cend = c.end >> 16;
-        const uint32_t uend = static_cast<uint32_t>(c.end & 0xFFFF);
-        if (cbeg >= bam->fsize) continue;
-        uint64_t rend = cend;                                              // ... and the block the chunk ends in, when it reaches into it
-        if (uend && cend < bam->fsize) {
-            uint8_t hd[512];
-            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), bam->fsize - cend));
-            pread_all(bam->fd, hd, n, cend, path);
-            const uint32_t csize = bgzf_block_size(hd, n);
-            if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(cend));
-            rend = std::min<uint64_t>(bam->fsize, cend + csize);
-        }
-        rend = std::min<uint64_t>(rend, bam->fsize);
-        const size_t in0 = comp.size();
-        comp.resize(in0 + (rend - cbeg));
-        pread_all(bam->fd, comp.data() + in0, rend - cbeg, cbeg, path);
-        S.bytes_read += rend - cbeg;
-        ChunkSpan sp{blocks.size(), 0, total + (c.beg & 0xFFFF), 0, 0};
-        bool end_seen = false;
-        uint64_t at = cbeg;
-        while (at < rend && (at < cend || (at == cend && uend))) {
-            const uint8_t* p = comp.data() + in0 + (at - cbeg);
-            const uint32_t csize = bgzf_block_size(p, rend - at);
-            if (!csize || at + csize > rend) {
-                if (at + 0x10000 >= bam->fsize) fail(LCTY_ERR_INVALID_DATA, "%s: truncated or corrupt BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
-                fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(at));
-            }
-            const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
-            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
-            if (at == cbeg && (c.beg & 0xFFFF) > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index starts behind its block", path);
-            if (at == cend) { if (uend > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index ends behind its block", path); sp.chain_end = total + uend; end_seen = true; }
-            blocks.push_back(BgzfBlock{csize, isize, total, in0 + static_cast<size_t>(at - cbeg), at, bgzf_plain_head(p)});
-            total += isize; at += csize;
-        }
-        sp.n_blocks = blocks.size() - sp.first_block; sp.span_end = total;
-        if (!end_seen) sp.chain_end = total;
-        if (sp.n_blocks) spans.push_back(sp);
-    }
+    read_chunk_blocks(bam->fd, bam->fsize, path, cs, comp, blocks, spans, total, S.bytes_read);
     S.ms_read = now_ms() - t0;
     S.blocks_inflated = blocks.size(); S.bytes_inflated = total;
     if (total > cap)
@@ -615,20 +575,7 @@ int32_t lcty_sample_bam_plan(lcty_sample_bam* bam, uint32_t n_regions, const uin
         *n_chunks = cs.size();
         for (size_t i = 0; i < cs.size() && i < chunk_cap; i++) { chunk_beg[i] = cs[i].beg; chunk_end[i] = cs[i].end; }
         if (blocks_total) {
-            uint64_t blocks = 0;
-            for (const Chunk& c : cs) {
-                uint64_t at = c.beg >> 16;
-                const uint64_t last = c.end >> 16;
-                while (at < bam->fsize && (at < last || (at == last && (c.end & 0xFFFF)))) {
-                    uint8_t hd[512];
-                    const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), bam->fsize - at));
-                    pread_all(bam->fd, hd, n, at, bam->path.c_str());
-                    const uint32_t csize = bgzf_block_size(hd, n);
-                    if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu", bam->path.c_str(), static_cast<unsigned long long>(at));
-                    blocks++; at += csize;
-                }
-            }
-            *blocks_total = blocks;
+            *blocks_total = count_chunk_blocks(bam->fd, bam->fsize, bam->path.c_str(), cs);
         }
     });
 }

@@ -15,6 +15,7 @@
 #include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
 #include "lcty_device.hpp"
+#include "lcty_vcf_index_parse.hpp"
 
 namespace lcty {
 
@@ -109,8 +110,6 @@ __global__ __launch_bounds__(256) void unpack_kernel(const uint32_t* __restrict_
     bases2[u] = bases; nmask[u] = mask;
 }
 
-struct Chunk { uint64_t beg, end; };           // virtual offsets of the index
-
 // The front half of a fetch. slice: page-locked, `total` inflated bytes + SLICE_PAD zero bytes; rec_off: the byte of every record
 // walked (of its block_size field), in file order.
 struct FetchedSlice {
@@ -132,7 +131,7 @@ struct lcty_sample_bam {
     std::vector<uint32_t> lengths; std::vector<uint64_t> name_off; std::string names;
     uint64_t first_record = 0;                   // virtual offset behind the header
     int paired = -1;                             // flag 0x1 of the first record; -1: not looked at yet, -2: no record
-    struct Ref { std::unordered_map<uint32_t, std::vector<lcty::Chunk>> bins; std::vector<uint64_t> linear; };
+    using Ref = lcty::IndexRef;                  // bins -> chunks, the linear index (lcty_vcf_index_parse.hpp)
     std::vector<Ref> refs;
     uint64_t tail_start = 0;                     // largest chunk end of the index
     uint64_t n_no_coor = 0; bool has_no_coor = false;
@@ -140,6 +139,62 @@ struct lcty_sample_bam {
 };
 
 namespace lcty {
+
+// n bytes of the file from byte `at` (LCTY_ERR_RUNTIME "read error"), and one BGZF block through a stream opened with 16 + MAX_WBITS
+void pread_all(int fd, void* buf, size_t n, uint64_t at, const char* path);
+void inflate_block(z_stream& zs, const uint8_t* in, uint32_t csize, uint8_t* out, uint32_t isize, const char* path);
+
+// the blocks of a BGZF file one after the other, from its start: the header and the first record
+struct BgzfSerial {
+    int fd; uint64_t fsize; const char* path;
+    uint64_t coff = 0, next = 0;                 // the block in `data`, the one behind it
+    std::vector<uint8_t> data; size_t at = 0;
+    z_stream zs;
+    BgzfSerial(int fd_, uint64_t fsize_, const char* path_) : fd(fd_), fsize(fsize_), path(path_) {
+        memset(&zs, 0, sizeof(zs));
+        if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateInit2");
+    }
+    ~BgzfSerial() { inflateEnd(&zs); }
+    bool load() {                                // the next block that holds data; false at the end of the file
+        while (at == data.size()) {
+            if (next >= fsize) return false;
+            uint8_t buf[0x10000];
+            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(buf), fsize - next));
+            pread_all(fd, buf, n, next, path);
+            const uint32_t csize = bgzf_block_size(buf, n);
+            if (!csize || csize > n) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu", path, static_cast<unsigned long long>(next));
+            const uint32_t isize = buf[csize - 4] | (buf[csize - 3] << 8) | (buf[csize - 2] << 16) | (static_cast<uint32_t>(buf[csize - 1]) << 24);
+            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
+            data.resize(isize);
+            if (isize) inflate_block(zs, buf, csize, data.data(), isize, path); else if (inflateReset(&zs) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateReset");
+            coff = next; next += csize; at = 0;
+        }
+        return true;
+    }
+    bool read(void* out, size_t n) {             // false: the file ends first
+        uint8_t* p = static_cast<uint8_t*>(out);
+        while (n) {
+            if (!load()) return false;
+            const size_t take = std::min(n, data.size() - at);
+            memcpy(p, data.data() + at, take);
+            p += take; n -= take; at += take;
+        }
+        return true;
+    }
+    uint64_t tell() { return at == data.size() ? next << 16 : (coff << 16) | at; }
+};
+
+// a chunk's blocks as they lie in the file: blocks[first_block .. + n_blocks); of the inflated bytes the chunk's own are
+// [chain_beg, chain_end), the last block's end is span_end
+struct ChunkSpan { size_t first_block, n_blocks; uint64_t chain_beg, chain_end, span_end; };
+// pread of the byte ranges of the merged chunks cs and their split into BGZF blocks: comp grows by the bytes read, blocks by their
+// blocks (out_at from `total` on, which grows by their inflated sizes), spans by one entry per chunk that has blocks. A chunk that
+// does not start or end inside its block, or bytes that are no BGZF block, are LCTY_ERR_INVALID_DATA.
+void read_chunk_blocks(int fd, uint64_t fsize, const char* path, const std::vector<Chunk>& cs, std::vector<uint8_t>& comp, std::vector<BgzfBlock>& blocks,
+                       std::vector<ChunkSpan>& spans, uint64_t& total, uint64_t& bytes_read);
+
+// the BGZF blocks the merged chunks cs span, by the headers of the blocks alone (what the plan entry points report)
+uint64_t count_chunk_blocks(int fd, uint64_t fsize, const char* path, const std::vector<Chunk>& cs);
 
 // The regions of a call must be inside the file's contigs, non-empty, sorted and disjoint: LCTY_ERR_INVALID_INPUT otherwise.
 void check_regions(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end);

@@ -482,19 +482,76 @@ class Vcf:
         r = cdefs.VcfRecords()
         check(lib().lcty_vcf_region(self._h, contig.encode(), start, end, None if used is None else used.ctypes.data, C.byref(r)))
         try:
-            def arr(p, n, dt):
-                return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
-            n = int(r.n_recs)
-            return {"pos": arr(r.pos, n, np.uint32), "ref_len": arr(r.ref_len, n, np.uint32), "rec_allele": arr(r.rec_allele, n + 1, np.uint32),
-                    "allele_off": arr(r.allele_off, int(r.n_alleles) + 1, np.uint64), "allele_bytes": arr(r.allele_bytes, int(r.pool_len), np.uint8),
-                    "gt": arr(r.gt, n * int(r.n_haps), np.int16).reshape(n, int(r.n_haps)),
-                    "phased": arr(r.phased, n * int(r.n_samples), np.uint8).reshape(n, int(r.n_samples))}
+            return _records_dict(r)
         finally:
             lib().lcty_vcf_records_free(C.byref(r))
 
     def close(self):
         if self._h:
             lib().lcty_vcf_free(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _records_dict(r):
+    """The arrays of a lcty_vcf_records as a dict (the caller frees the struct)."""
+    def arr(p, n, dt):
+        return np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+    n = int(r.n_recs)
+    return {"pos": arr(r.pos, n, np.uint32), "ref_len": arr(r.ref_len, n, np.uint32), "rec_allele": arr(r.rec_allele, n + 1, np.uint32),
+            "allele_off": arr(r.allele_off, int(r.n_alleles) + 1, np.uint64), "allele_bytes": arr(r.allele_bytes, int(r.pool_len), np.uint8),
+            "gt": arr(r.gt, n * int(r.n_haps), np.int16).reshape(n, int(r.n_haps)),
+            "phased": arr(r.phased, n * int(r.n_samples), np.uint8).reshape(n, int(r.n_samples))}
+
+
+class VcfIndexed:
+    """lcty_vcf_indexed_*: a BGZF VCF with its tabix index (`locityper target -v`): only the chunks of a window are read, inflated and
+    parsed, on the device. samples, ploidy (of the first record of the file), hap_off as Vcf; stats: those of the last region()."""
+
+    def __init__(self, path, index_path=None, ctx=None):
+        self._h = VP()
+        self.ctx = ctx                               # the context of region(); open and plan are host work
+        check(lib().lcty_vcf_indexed_open(str(path).encode(), None if index_path is None else str(index_path).encode(), C.byref(self._h)))
+        v = cdefs.VcfView()
+        check(lib().lcty_vcf_indexed_view_get(self._h, C.byref(v)))
+        blob = C.string_at(v.samples, v.samples_len) if v.samples_len else b""
+        self.samples = [s.decode() for s in blob.split(b"\0")[:-1]]
+        self.ploidy = np.frombuffer(C.string_at(v.ploidy, 4 * v.n_samples), dtype=np.uint32).copy() if v.n_samples else np.zeros(0, np.uint32)
+        self.hap_off = np.frombuffer(C.string_at(v.hap_off, 4 * (v.n_samples + 1)), dtype=np.uint32).copy()
+        self.n_haps, self.n_records = int(v.n_haps), int(v.n_records)
+        self.stats = None
+
+    def plan(self, contig, start, end):
+        """-> (chunks [n][2] uint64 of virtual offsets, BGZF blocks they span)"""
+        n, blocks = U64(0), U64(0)
+        check(lib().lcty_vcf_indexed_plan(self._h, contig.encode(), start, end, 0, C.byref(n), None, None, None))
+        beg = np.zeros(max(n.value, 1), dtype=np.uint64); end_ = np.zeros(max(n.value, 1), dtype=np.uint64)
+        check(lib().lcty_vcf_indexed_plan(self._h, contig.encode(), start, end, len(beg), C.byref(n), beg.ctypes.data, end_.ctypes.data, C.byref(blocks)))
+        return np.stack([beg, end_], axis=1)[:n.value], int(blocks.value)
+
+    def region(self, contig, start, end, sample_used=None, ctx=None):
+        """lcty_vcf_indexed_fetch: the dict of Vcf.region for the same file and arguments, on the context given here or at construction."""
+        ctx = self.ctx if ctx is None else ctx
+        used = None if sample_used is None else np.ascontiguousarray(sample_used, dtype=np.uint8)
+        if used is not None and len(used) != len(self.samples):
+            raise ValueError("sample_used must have one entry per sample")
+        r, st = cdefs.VcfRecords(), cdefs.VcfFetchStats()
+        check(lib().lcty_vcf_indexed_fetch(None if ctx is None else ctx._h, self._h, contig.encode(), start, end, None if used is None else used.ctypes.data,
+                                           C.byref(r), C.byref(st)))
+        try:
+            self.stats = st.as_dict()
+            return _records_dict(r)
+        finally:
+            lib().lcty_vcf_records_free(C.byref(r))
+
+    def close(self):
+        if self._h:
+            lib().lcty_vcf_indexed_close(self._h)
             self._h = VP()
 
     def __del__(self):
