@@ -1,7 +1,7 @@
 // lcty_aln_bam.hip — a locus's aln.bam read on the device, straight into a batch: what lcty_bam_read (lcty_io.hip) does
 // record by record on the host — AllAlignments::load over the mapper's name-grouped file (src/model/locs.rs:405-461, 502-567,
 // 1116-1150) —, over the whole file as one slice:
-//   host   read, BGZF split, inflate (inflate_slice of lcty_sample_bam.hip: host pool, or the device with knob "sample_bam_inflate" 1),
+//   host   read, BGZF split, inflate (Slice::inflate of lcty_bgzf_read.hpp: host pool, or the device with knob "sample_bam_inflate" 1),
 //          the header and the chain of record lengths (lcty_aln_bam_parse.hpp)
 //   aln_record_kernel   a lane per walked record: head, rec_fits, primary or not, the lcty_aln_rec fields but cigar_rel, MAPQ, n_cigar,
 //                       the error classes of one record
@@ -11,9 +11,9 @@
 //   scans               units -> mate_off, l_seq -> qual_off, name lengths -> name_off
 //   aln_pair_kernel     a lane per record: cigar_rel (relative to its pair), the largest CIGAR of a record per pair
 //   aln_mate_kernel     a lane per primary: the per-mate and per-pair arrays of the table
-//   gathers             CIGAR words, name bytes, quality bytes dealt flat over the lanes; unpack_kernel<false> for SEQ as stored
+//   gathers             CIGAR words (cigar_gather_kernel), name bytes, quality bytes dealt flat over the lanes; unpack_kernel<false> for SEQ as stored
 // The grouping is a pure function of the primary flags: primary j starts a read (paired == 0), or starts a pair when j is even and is
-// its second end when j is odd. Errors: (record ordinal << 8 | class) through atomicMin, the first offending record in file order
+// its second end when j is odd. Errors: (record ordinal, class) through refuse (lcty_device.hpp), the first offending record in file order
 // decides and at one record the order of checks of the host loop; the host words the message from the slice.
 #include <algorithm>
 #include <memory>
@@ -22,9 +22,9 @@
 
 #include "lcty_aln_bam.hpp"
 #include "lcty_aln_bam_parse.hpp"
-#include "lcty_bgzf.hpp"
+#include "lcty_bam_record.hpp"
+#include "lcty_bgzf_read.hpp"
 #include "lcty_objects.hpp"
-#include "lcty_sample_bam_internal.hpp"
 #include "lcty_scan.hpp"
 
 namespace lcty {
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void aln_record_kernel(const AlnView V) {
     V.mapq[r] = static_cast<uint8_t>((ld32(V.raw, o + 12) >> 8) & 0xFFu);
     V.prim[r] = primary ? 1u : 0u;
     V.n_cigar[r] = fits ? h.n_cigar : 0u;
-    if (err) atomicMin(V.err, (static_cast<unsigned long long>(r) << 8) | err);
+    if (err) refuse(V.err, r, err);
 }
 
 __global__ __launch_bounds__(256) void aln_place_kernel(const uint32_t* __restrict__ prim, const uint32_t* __restrict__ prim_ord, uint32_t n_rec,
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void aln_primary_kernel(const uint32_t* __rest
     const bool second = paired && (j & 1u);
     if (second && fits) {
         const uint64_t of = rec_off[prim_rec[j - 1]];
-        if (rec_fits(rec_head(raw, of)) && !same_qname(raw, of, o)) atomicMin(err, (static_cast<unsigned long long>(r) << 8) | A_NO_SECOND_END);
+        if (rec_fits(rec_head(raw, of)) && !same_qname(raw, of, o)) refuse(err, r, A_NO_SECOND_END);
     }
     P.l_seq[j] = fits ? h.l_seq : 0u;
     P.units[j] = fits ? h.l_seq / 32u + ((h.l_seq & 31u) ? 1u : 0u) : 0u;
@@ -155,65 +155,33 @@ __global__ __launch_bounds__(256) void aln_mate_kernel(const uint32_t* __restric
     }
 }
 
-// CIGAR word w of the output: of the last record r with cigar_at[r] <= w
-__global__ __launch_bounds__(256) void aln_cigar_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ cigar_at,
-                                                        uint32_t n_rec, uint32_t n_words, uint32_t* __restrict__ cigar) {
-    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
-    if (w >= n_words) return;
-    uint32_t lo = 0, hi = n_rec;
-    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (cigar_at[mid] <= w) lo = mid; else hi = mid; }
-    const uint64_t o = rec_off[lo];
-    const uint32_t l_name = ld32(raw, o + 12) & 0xFFu;
-    cigar[w] = ld32(raw, o + 36 + l_name + 4ull * (w - cigar_at[lo]));
-}
-
 // byte b of the output: of the last primary j with at[j] <= b. QUAL: the qualities behind SEQ, else the name behind the fixed fields.
 template <bool QUAL>
 __global__ __launch_bounds__(256) void aln_bytes_kernel(const uint8_t* __restrict__ raw8, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ prim_rec,
                                                         const uint64_t* __restrict__ at, uint32_t n_prim, uint64_t n_bytes, uint8_t* __restrict__ out) {
     const uint64_t b = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
     if (b >= n_bytes) return;
-    uint32_t lo = 0, hi = n_prim;
-    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (at[mid] <= b) lo = mid; else hi = mid; }
-    const uint64_t o = rec_off[prim_rec[lo]];
+    const uint32_t j = flat_owner(at, n_prim, b);
+    const uint64_t o = rec_off[prim_rec[j]];
     uint64_t from = o + 36;
     if (QUAL) {
         const uint32_t* raw = reinterpret_cast<const uint32_t*>(raw8);
         const uint32_t l_name = ld32(raw, o + 12) & 0xFFu, n_cigar = ld32(raw, o + 16) & 0xFFFFu, l_seq = ld32(raw, o + 20);
         from += l_name + 4ull * n_cigar + (static_cast<uint64_t>(l_seq) + 1) / 2;
     }
-    out[b] = raw8[from + (b - at[lo])];
+    out[b] = raw8[from + (b - at[j])];
 }
 
 // the whole file, split into its BGZF blocks; false: not BGZF from end to end
-bool split_blocks(const std::vector<uint8_t>& comp, std::vector<BgzfBlock>& blocks, uint64_t& total) {
+bool whole_file_blocks(const std::vector<uint8_t>& comp, std::vector<BgzfBlock>& blocks, uint64_t& total) {
     blocks.clear(); total = 0;
     for (uint64_t at = 0; at < comp.size();) {
-        const uint8_t* p = comp.data() + at;
-        const uint32_t csize = bgzf_block_size(p, comp.size() - at);
-        if (!csize || at + csize > comp.size()) return false;
-        const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
-        if (isize > 0x10000) return false;
-        blocks.push_back(BgzfBlock{csize, isize, total, static_cast<size_t>(at), at, bgzf_plain_head(p)});
-        total += isize; at += csize;
+        BgzfHead h;
+        if (bgzf_head(comp.data() + at, comp.size() - at, h) != BGZF_OK) { blocks.clear(); return false; }
+        blocks.push_back(BgzfBlock{h.csize, h.isize, total, static_cast<size_t>(at), at, h.head});
+        total += h.isize; at += h.csize;
     }
     return true;
-}
-
-std::vector<uint8_t> read_whole(const char* path) {
-    FILE* f = fopen(path, "rb");
-    if (!f) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", path);
-    std::vector<uint8_t> buf;
-    bool bad = fseek(f, 0, SEEK_END) != 0;
-    const long size = bad ? -1 : ftell(f);
-    bad = bad || size < 0 || fseek(f, 0, SEEK_SET) != 0;
-    if (!bad) {
-        buf.resize(static_cast<size_t>(size));
-        bad = size > 0 && fread(buf.data(), 1, buf.size(), f) != buf.size();
-    }
-    fclose(f);
-    if (bad) fail(LCTY_ERR_RUNTIME, "read error on %s", path);
-    return buf;
 }
 
 }  // namespace
@@ -231,44 +199,32 @@ int32_t lcty_bam_read_device(lcty_ctx* ctx, const char* path, const char* const*
         *out = nullptr;
         const double t_start = now_ms();
         const int paired = paired_arg != 0;
-        const uint64_t cap = static_cast<uint64_t>(ctx->knob("aln_bam_max_slice_bytes", 1ll << 33));
-        if (ctx->knob("sample_bam_inflate", 0) > 1) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_inflate = %lld (0: host, 1: device)", static_cast<long long>(ctx->knob("sample_bam_inflate", 0)));
+        check_inflate_knob(ctx);
         lcty_aln_bam_stats S{};
 
         // ---- the bytes of the file, split into blocks, inflated into one page-locked slice
         double t0 = now_ms();
-        std::vector<uint8_t> comp = read_whole(path);
-        S.bytes_read = comp.size();
-        std::vector<BgzfBlock> blocks;
-        uint64_t total = 0;
-        const bool bgzf = split_blocks(comp, blocks, total);
+        Slice F;
+        F.comp = read_whole_file(path);
+        S.bytes_read = F.comp.size();
+        const bool bgzf = whole_file_blocks(F.comp, F.blocks, F.total);
         S.ms_read = now_ms() - t0;
-        FetchedSlice F;
-        DevBuf<uint8_t> d_raw;
-        bool on_device = false;
         if (bgzf) {
-            S.blocks = blocks.size(); S.bytes_inflated = total;
-            if (total > cap)
-                fail(LCTY_ERR_UNSUPPORTED, "%s: the file inflates to %llu bytes, more than %llu (knob aln_bam_max_slice_bytes)", path,
-                     static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
-            on_device = inflate_slice(ctx, comp, blocks, total, F, d_raw, path, S.ms_inflate);
+            S.blocks = F.blocks.size(); S.bytes_inflated = F.total;
+            check_slice_cap(ctx, path, F.total, "aln_bam_max_slice_bytes", "the file inflates to");
+            S.ms_inflate = F.inflate(ctx, path);
         } else {
             // gzip members that are not BGZF blocks: the serial inflate of the host reader, with its errors
-            std::vector<uint8_t>().swap(comp);
+            std::vector<uint8_t>().swap(F.comp);
             t0 = now_ms();
             uint8_t* data = nullptr; uint64_t len = 0;
             const int32_t rc = lcty_io_read_file(path, &data, &len);
             if (rc != LCTY_OK) throw Error(rc, lcty_last_error());
             struct Freed { uint8_t* p; ~Freed() { free(p); } } freed{data};
-            S.bytes_inflated = total = len;
-            if (total > cap)
-                fail(LCTY_ERR_UNSUPPORTED, "%s: the file inflates to %llu bytes, more than %llu (knob aln_bam_max_slice_bytes)", path,
-                     static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
-            ctx->activate();
-            F.total = total;
-            LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&F.slice), total + SLICE_PAD, hipHostMallocDefault));
-            if (total) memcpy(F.slice, data, total);
-            memset(F.slice + total, 0, SLICE_PAD);
+            S.bytes_inflated = len;
+            check_slice_cap(ctx, path, len, "aln_bam_max_slice_bytes", "the file inflates to");
+            F.alloc(ctx, len);
+            if (len) memcpy(F.slice, data, len);
             S.ms_inflate = now_ms() - t0;
         }
         hipStream_t s = ctx->stream;
@@ -303,16 +259,16 @@ int32_t lcty_bam_read_device(lcty_ctx* ctx, const char* path, const char* const*
         if (n_rec) {
             // ---- upload, the record stage
             t0 = now_ms();
-            DevBuf<uint64_t> d_rec_off; DevBuf<uint32_t> d_tid, d_prim, d_ncig; DevBuf<unsigned long long> d_err;
-            if (!on_device) { d_raw.alloc(F.total + SLICE_PAD); d_raw.upload(F.slice, F.total + SLICE_PAD, s); }
+            DevBuf<uint64_t> d_rec_off; DevBuf<uint32_t> d_tid, d_prim, d_ncig; ErrWord err;
+            const uint8_t* d_raw = F.device(s);
             d_rec_off.alloc(n_rec); d_rec_off.upload(rec_off.data(), n_rec, s);
             d_tid.alloc(std::max<size_t>(H.n_ref, 1)); d_tid.upload(H.tid2contig.data(), H.n_ref, s);
-            T->d_recs.alloc(n_rec); d_mapq.alloc(n_rec); d_prim.alloc(n_rec); d_ncig.alloc(n_rec); d_err.alloc(1);
-            LCTY_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), s));
-            const uint32_t* raw = reinterpret_cast<const uint32_t*>(d_raw.p);
+            T->d_recs.alloc(n_rec); d_mapq.alloc(n_rec); d_prim.alloc(n_rec); d_ncig.alloc(n_rec);
+            unsigned long long* d_err = err.reset(s);
+            const uint32_t* raw = reinterpret_cast<const uint32_t*>(d_raw);
             AlnView V{};
             V.raw = raw; V.rec_off = d_rec_off.p; V.n_rec = static_cast<uint32_t>(n_rec); V.tid2contig = d_tid.p; V.n_ref = H.n_ref;
-            V.recs = T->d_recs.p; V.mapq = d_mapq.p; V.prim = d_prim.p; V.n_cigar = d_ncig.p; V.err = d_err.p;
+            V.recs = T->d_recs.p; V.mapq = d_mapq.p; V.prim = d_prim.p; V.n_cigar = d_ncig.p; V.err = d_err;
             hipLaunchKernelGGL(aln_record_kernel, dim3(blocks_of(n_rec, 256)), dim3(256), 0, s, V);
             LCTY_HIP(hipGetLastError());
             ScanTotal scan;
@@ -328,15 +284,11 @@ int32_t lcty_bam_read_device(lcty_ctx* ctx, const char* path, const char* const*
             LCTY_HIP(hipGetLastError());
             if (n_prim)
                 hipLaunchKernelGGL(aln_primary_kernel, dim3(blocks_of(n_prim, 256)), dim3(256), 0, s, raw, d_rec_off.p, static_cast<uint32_t>(n_rec), d_prim_rec.p,
-                                   n_prim, paired, P, d_err.p);
+                                   n_prim, paired, P, d_err);
             LCTY_HIP(hipGetLastError());
             // ---- errors: of a record, of the walk behind the records, of the end of the file
-            unsigned long long e = 0;
-            d_err.download(&e, 1, s);
-            LCTY_HIP(hipStreamSynchronize(s));
-            if (e != ~0ull) {
-                const uint32_t cls = static_cast<uint32_t>(e & 0xFF);
-                const uint64_t r = e >> 8;
+            uint64_t r; uint32_t cls;
+            if (err.take(s, r, cls)) {
                 if (cls == A_CORRUPT) fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BAM record", path);
                 if (cls == A_FIRST_NOT_PRIMARY) fail(LCTY_ERR_INVALID_DATA, "First record in the BAM file is secondary/supplementary");
                 if (cls == A_NO_SECOND_END) fail(LCTY_ERR_INVALID_DATA, "Read %s does not have a second read end", last_primary_name(r).c_str());
@@ -373,15 +325,15 @@ int32_t lcty_bam_read_device(lcty_ctx* ctx, const char* path, const char* const*
             T->d_cigar.alloc(std::max<uint32_t>(n_words, 1));
             d_names.alloc(std::max<uint64_t>(n_name, 1)); d_quals.alloc(std::max<uint64_t>(n_qual, 1));
             if (n_words)
-                hipLaunchKernelGGL(aln_cigar_kernel, dim3(blocks_of(n_words, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_cigar_at.p, static_cast<uint32_t>(n_rec),
+                hipLaunchKernelGGL(cigar_gather_kernel<uint32_t>, dim3(blocks_of(n_words, 256)), dim3(256), 0, s, raw, d_rec_off.p, nullptr, d_cigar_at.p, static_cast<uint32_t>(n_rec),
                                    n_words, T->d_cigar.p);
             LCTY_HIP(hipGetLastError());
             if (n_name)
-                hipLaunchKernelGGL(aln_bytes_kernel<false>, dim3(blocks_of(n_name, 256)), dim3(256), 0, s, d_raw.p, d_rec_off.p, d_prim_rec.p, d_name_at.p, n_prim,
+                hipLaunchKernelGGL(aln_bytes_kernel<false>, dim3(blocks_of(n_name, 256)), dim3(256), 0, s, d_raw, d_rec_off.p, d_prim_rec.p, d_name_at.p, n_prim,
                                    n_name, d_names.p);
             LCTY_HIP(hipGetLastError());
             if (n_qual && host_copy)                                             // nothing on the device reads qualities: they exist for the caller
-                hipLaunchKernelGGL(aln_bytes_kernel<true>, dim3(blocks_of(n_qual, 256)), dim3(256), 0, s, d_raw.p, d_rec_off.p, d_prim_rec.p, d_qual_at.p, n_prim,
+                hipLaunchKernelGGL(aln_bytes_kernel<true>, dim3(blocks_of(n_qual, 256)), dim3(256), 0, s, d_raw, d_rec_off.p, d_prim_rec.p, d_qual_at.p, n_prim,
                                    n_qual, d_quals.p);
             LCTY_HIP(hipGetLastError());
             LCTY_HIP(hipStreamSynchronize(s));

@@ -22,6 +22,7 @@
 // tests/test_basis_host.py holds this against the walk itself (tests/pyref_basis.py), on designed CIGARs and on random ones.
 #include "lcty_common.hpp"
 #include "lcty_basis_search.hpp"
+#include "lcty_device.hpp"
 #include "lcty_seq.hpp"
 
 #include <algorithm>
@@ -40,15 +41,6 @@ __global__ __launch_bounds__(256) void basis_init_kernel(const uint64_t* __restr
     for (uint64_t r = win_off[a] + threadIdx.x; r < win_off[a + 1]; r += 256) bits[r * words + (a >> 5)] = 1u << (a & 31);
 }
 
-// last index r in [0, n) with C[r] <= x; the caller guarantees C[0] <= x
-__device__ inline uint32_t last_le(const uint32_t* C, uint32_t n, uint32_t x) {
-    uint32_t lo = 0, hi = n;                               // C[lo] <= x, C[hi] > x (hi == n: past the end)
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (C[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 // first index q in [0, n] with C[q] >= x; the caller guarantees C[n] >= x
 __device__ inline uint32_t first_ge(const uint32_t* C, uint32_t n, uint32_t x) {
     uint32_t lo = 0, hi = n;
@@ -59,7 +51,7 @@ __device__ inline uint32_t first_ge(const uint32_t* C, uint32_t n, uint32_t x) {
     return lo;
 }
 __device__ inline uint32_t edits_left_of(const uint32_t* C, const uint32_t* ED, uint32_t n, uint32_t x, uint32_t* run) {
-    const uint32_t r = last_le(C, n, x);
+    const uint32_t r = flat_owner(C, n, x);                // the caller guarantees C[0] <= x
     *run = r;
     return ED[r] + (ED[r + 1] != ED[r] ? x - C[r] : 0u);
 }

@@ -8,7 +8,7 @@
 //   exclusive_scan     over the kept flags, the CIGAR lengths and the 32-base units -> record order, cigar_off, seq_off
 //   bg_compact_kernel  the kept records side by side, and the sort's input (hash of the name, kept ordinal)
 //   RadixSort + bg_mate_kernel (paired data)   a lane per record walks the run of its hash, names compared byte for byte
-//   bg_cigar_kernel    the CIGAR words, dealt flat over the lanes;   unpack_kernel<false>   SEQ as it lies in the file
+//   cigar_gather_kernel   the CIGAR words, dealt flat over the lanes;   unpack_kernel<false>   SEQ as it lies in the file (lcty_bam_record.hpp)
 // The arrays stay on the device with the handle (lcty_bg_estimate on the same context reads them there) and are downloaded once.
 #include <algorithm>
 #include <memory>
@@ -16,15 +16,15 @@
 #include <vector>
 
 #include "lcty_bg_reads.hpp"
-#include "lcty_sample_bam_internal.hpp"
+#include "lcty_sample_bam.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
 
 namespace lcty {
 namespace {
 
-// error classes, by rank at one record; (record ordinal << 8 | class) goes through atomicMin: the first offending record in file
-// order decides, as in the loop of lcty_bg_reads_load
+// error classes, by rank at one record (refuse, lcty_device.hpp): the first offending record in file order decides, as in the loop
+// of lcty_bg_reads_load
 enum : uint32_t { B_SHORT = 1, B_UNSORTED = 2, B_NO_CIGAR = 3, B_BAD_OP = 4, B_QLEN = 5, B_MATES = 6 };
 enum : uint32_t { C_IGNORED = 0, C_WO_CIGAR = 1, C_UNPAIRED = 2, C_PAIRED = 3, C_PRIMARY = 4, N_COUNTS = 5 };
 
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void bg_record_kernel(const BgView V) {
         V.units[r] = kept ? h.l_seq / 32u + ((h.l_seq & 31u) ? 1u : 0u) : 0u;
         V.hash[r] = kept ? name_hash(V.raw, o, h.l_name) & V.hash_mask : 0ull;
         V.paired[r] = paired ? 1 : 0;
-        if (err) atomicMin(V.err, (static_cast<unsigned long long>(r) << 8) | err);
+        if (err) refuse(V.err, r, err);
     }
     const unsigned long long b_ign = __ballot(ignored), b_wo = __ballot(wo_cigar), b_un = __ballot(kept && !paired), b_pa = __ballot(kept && paired),
                              b_prim = __ballot(fits && (h.flag & 0x900u) == 0);
@@ -178,18 +178,6 @@ __global__ __launch_bounds__(256) void bg_compact_kernel(const BgView V, const u
     if (C.keys) { C.keys[k] = V.hash[r]; C.vals[k] = k; }
 }
 
-// CIGAR word j of the output: of the last record k with cigar_off32[k] <= j
-__global__ __launch_bounds__(256) void bg_cigar_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ src,
-                                                       const uint32_t* __restrict__ cigar_off32, uint32_t n_kept, uint32_t n_words, uint32_t* __restrict__ cigar) {
-    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= n_words) return;
-    uint32_t lo = 0, hi = n_kept;
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (cigar_off32[mid] <= j) lo = mid; else hi = mid; }
-    const uint64_t o = rec_off[src[lo]];
-    const uint32_t l_name = ld32(raw, o + 12) & 0xFFu;
-    cigar[j] = ld32(raw, o + 36 + l_name + 4ull * (j - cigar_off32[lo]));
-}
-
 // group_mates (bg/insertsz.rs:25-37) for the record at place i of the sorted list: the records of its hash lie side by side in kept
 // order. One of its name and its end before it: "several first / second mates" at this record (the smallest such record is the one
 // the host loop names). One of its name and the other end: its mate.
@@ -206,7 +194,7 @@ __global__ __launch_bounds__(256) void bg_mate_kernel(const uint32_t* __restrict
     for (uint32_t t = i; t > 0 && keys[t - 1] == key; t--) {
         const uint32_t st = static_cast<uint32_t>(vals[t - 1]);
         if (!same_name(raw, rec_off[src[st]], o)) continue;
-        if ((flags[st] & LCTY_BG_SECOND) == second) atomicMin(err, (static_cast<unsigned long long>(src[s]) << 8) | B_MATES);
+        if ((flags[st] & LCTY_BG_SECOND) == second) refuse(err, src[s], B_MATES);
         else m = st;
     }
     for (uint32_t t = i + 1; t < n && keys[t] == key; t++) {
@@ -229,7 +217,7 @@ int32_t lcty_bg_reads_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, const char* con
     return guarded([&] {
         if (!ctx || !bam || !contig || !params || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         const double t_start = now_ms();
-        const char* path = bam->path.c_str();
+        const char* path = bam->file.path.c_str();
         if (start >= end || padded_start > start || static_cast<uint64_t>(padded_start) + padded_len < end)
             fail(LCTY_ERR_INVALID_INPUT, "background interval [%u, %u) is not inside the padded sequence [%u, +%u)", start, end, padded_start, padded_len);
         uint32_t tid = NONE32;
@@ -241,12 +229,11 @@ int32_t lcty_bg_reads_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, const char* con
         const uint64_t hash_mask = hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1;
         const uint64_t padded_end = static_cast<uint64_t>(padded_start) + padded_len;
         lcty_sample_bam_stats S{};
-        S.n_regions = 1; S.file_bytes = bam->fsize;
+        S.n_regions = 1; S.file_bytes = bam->file.fsize;
 
         // ---- the front half of lcty_sample_bam_fetch for the one region, without the unmapped tail
-        FetchedSlice F;
-        DevBuf<uint8_t> d_raw;
-        const bool on_device = fetch_slice(ctx, bam, 1, &tid, &start, &end, false, false, F, d_raw, S);
+        Slice F;
+        fetch_slice(ctx, bam, 1, &tid, &start, &end, false, false, F, S);
         hipStream_t s = ctx->stream;
         const std::vector<uint64_t>& rec_off = F.rec_off;
         const uint64_t n_rec = rec_off.size();
@@ -255,32 +242,27 @@ int32_t lcty_bg_reads_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, const char* con
         // ---- upload, the record stage
         double t0 = now_ms();
         DevBuf<uint64_t> d_rec_off, d_hash; DevBuf<uint32_t> d_kept, d_pos, d_end, d_qlen, d_ncig, d_units, d_counts; DevBuf<uint8_t> d_flags, d_paired;
-        DevBuf<unsigned long long> d_err;
-        if (!on_device) { d_raw.alloc(F.total + SLICE_PAD); d_raw.upload(F.slice, F.total + SLICE_PAD, s); }
+        ErrWord err;
+        const uint32_t* raw = reinterpret_cast<const uint32_t*>(F.device(s));
         d_rec_off.alloc(n_rec); d_rec_off.upload(rec_off.data(), n_rec, s);
         d_kept.alloc(n_rec); d_pos.alloc(n_rec); d_end.alloc(n_rec); d_qlen.alloc(n_rec); d_ncig.alloc(n_rec); d_units.alloc(n_rec);
-        d_hash.alloc(n_rec); d_flags.alloc(n_rec); d_paired.alloc(n_rec); d_counts.alloc(N_COUNTS); d_err.alloc(1);
+        d_hash.alloc(n_rec); d_flags.alloc(n_rec); d_paired.alloc(n_rec); d_counts.alloc(N_COUNTS);
         d_counts.zero(s);
-        LCTY_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), s));
+        unsigned long long* d_err = err.reset(s);
         LCTY_HIP(hipStreamSynchronize(s));
         S.ms_upload = now_ms() - t0;
         t0 = now_ms();
-        const uint32_t* raw = reinterpret_cast<const uint32_t*>(d_raw.p);
         BgView V{};
         V.raw = raw; V.rec_off = d_rec_off.p; V.n_rec = static_cast<uint32_t>(n_rec);
         V.tid = static_cast<int32_t>(tid); V.start = start; V.end = end; V.padded_start = padded_start; V.padded_end = padded_end;
         V.min_mapq = params->min_mapq; V.max_clipping = params->max_clipping; V.hash_mask = hash_mask;
         V.kept = d_kept.p; V.pos = d_pos.p; V.endpos = d_end.p; V.qlen = d_qlen.p; V.flags = d_flags.p; V.n_cigar = d_ncig.p; V.units = d_units.p;
-        V.hash = d_hash.p; V.paired = d_paired.p; V.err = d_err.p; V.counts = d_counts.p;
+        V.hash = d_hash.p; V.paired = d_paired.p; V.err = d_err; V.counts = d_counts.p;
         hipLaunchKernelGGL(bg_record_kernel, dim3(blocks_of(n_rec, 256)), dim3(256), 0, s, V);
         LCTY_HIP(hipGetLastError());
         auto check_err = [&]() {
-            unsigned long long e = 0;
-            d_err.download(&e, 1, s);
-            LCTY_HIP(hipStreamSynchronize(s));
-            if (e == ~0ull) return;
-            const uint32_t cls = static_cast<uint32_t>(e & 0xFF);
-            const uint64_t r = e >> 8;
+            uint64_t r; uint32_t cls;
+            if (!err.take(s, r, cls)) return;
             const uint8_t* rec = F.slice + rec_off[r];
             if (cls == B_SHORT) fail(LCTY_ERR_INVALID_DATA, "%s: record %llu of the fetched slice is shorter than its fields", path, static_cast<unsigned long long>(r));
             const std::string name = record_name(F.slice, rec_off[r]);
@@ -356,7 +338,7 @@ int32_t lcty_bg_reads_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, const char* con
             const uint64_t* keys = where ? d_kb.p : d_ka.p; const uint64_t* vals = where ? d_vb.p : d_va.p;
             DevBuf<uint32_t> d_mate;
             d_mate.alloc(n);
-            hipLaunchKernelGGL(bg_mate_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_src.p, T->d_flags.p, keys, vals, n, d_mate.p, d_err.p);
+            hipLaunchKernelGGL(bg_mate_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_src.p, T->d_flags.p, keys, vals, n, d_mate.p, d_err);
             LCTY_HIP(hipGetLastError());
             check_err();
             d_mate.download(T->mate.data(), n, s);
@@ -370,7 +352,7 @@ int32_t lcty_bg_reads_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, const char* con
         T->d_bases2.alloc(2ull * n_units + 2); T->d_nmask.alloc(n_units + 1ull);
         T->d_bases2.zero(s); T->d_nmask.zero(s);
         if (n_words)
-            hipLaunchKernelGGL(bg_cigar_kernel, dim3(blocks_of(n_words, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_src.p, d_coff32.p, n, n_words, T->d_cigar.p);
+            hipLaunchKernelGGL(cigar_gather_kernel<uint32_t>, dim3(blocks_of(n_words, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_src.p, d_coff32.p, n, n_words, T->d_cigar.p);
         LCTY_HIP(hipGetLastError());
         if (n_units)
             hipLaunchKernelGGL(unpack_kernel<false>, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_src.p, d_unit_off.p, n, n_units,

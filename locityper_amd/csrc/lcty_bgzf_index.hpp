@@ -1,9 +1,9 @@
-// lcty_vcf_index_parse.hpp — the host passes of the indexed VCF reader (lcty_vcf_fetch.hip) and the pieces the two
-// VCF readers and the two index readers share. Standard library and lcty_host.hpp only, no HIP call and no zlib: the bytes come
-// inflated. scripts/vcf_index_probe_host.cpp runs all of it on the CPU alone.
+// lcty_bgzf_index.hpp — the indices of BGZF files and the host passes of the indexed VCF reader (lcty_vcf_fetch.hip):
+// the pieces the two index readers and the two VCF readers share. Standard library and lcty_host.hpp only, no HIP call, no zlib and
+// no file: the bytes come read and inflated. scripts/vcf_index_probe_host.cpp runs all of it on the CPU alone.
 //   the index    a bin / linear index (SAM specification 5.2, 5.3; the tabix format): IndexRef, the chunks of a region
-//                (region_chunks) and their merge (merge_chunks) — one definition for the BAI of lcty_sample_bam.hip and the TBI here —
-//                and the TBI parser (parse_tbi)
+//                (region_chunks) and their merge (merge_chunks) — one definition for the BAI of lcty_sample_bam.hip and the TBI of
+//                lcty_vcf_fetch.hip — and the two parsers (parse_bai, parse_tbi)
 //   the text     what lcty_vcf_open and lcty_vcf_region (lcty_io.hip) do with one line: the #CHROM line (parse_chrom_line), the head
 //                of a record (parse_line_head), the ploidies of the first record (first_record_ploidy), a record of a region
 //                (parse_record_line), with their statuses and message texts. The indexed reader calls the same functions, so what it
@@ -49,6 +49,45 @@ inline std::vector<Chunk> merge_chunks(std::vector<Chunk>& cs) {
         else merged.push_back(c);
     }
     return merged;
+}
+
+// x[0 .. n): the bytes of a .bai file of a BAM file whose header names n_refs_of_header references. tail_start: the largest chunk end
+// of the index (0 without chunks). The trailing n_no_coor is optional, bytes behind it are ignored.
+struct Bai {
+    std::vector<IndexRef> refs;
+    uint64_t tail_start = 0;
+    uint64_t n_no_coor = 0; bool has_no_coor = false;
+};
+inline Bai parse_bai(const uint8_t* x, size_t n, size_t n_refs_of_header, const char* ip) {
+    if (n >= 4 && memcmp(x, "CSI\1", 4) == 0) fail(LCTY_ERR_UNSUPPORTED, "%s is a CSI index (only BAI indices are read)", ip);
+    if (n >= 2 && x[0] == 0x1f && x[1] == 0x8b) fail(LCTY_ERR_UNSUPPORTED, "%s is compressed: a CSI index? (only BAI indices are read)", ip);
+    if (n < 8 || memcmp(x, "BAI\1", 4) != 0) fail(LCTY_ERR_INVALID_DATA, "%s is not a BAI index", ip);
+    size_t at = 4;
+    auto need = [&](size_t k) { if (k > n - at) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAI index", ip); };
+    auto u32 = [&]() { need(4); uint32_t v; memcpy(&v, x + at, 4); at += 4; return v; };
+    auto u64 = [&]() { need(8); uint64_t v; memcpy(&v, x + at, 8); at += 8; return v; };
+    const uint32_t n_ref = u32();
+    if (n_ref != n_refs_of_header) fail(LCTY_ERR_INVALID_DATA, "%s: the index has %u references, the BAM header %zu", ip, n_ref, n_refs_of_header);
+    Bai B;
+    B.refs.resize(n_ref);
+    for (uint32_t r = 0; r < n_ref; r++) {
+        const uint32_t n_bin = u32();
+        for (uint32_t k = 0; k < n_bin; k++) {
+            const uint32_t bin = u32(), n_chunk = u32();
+            need(16ull * n_chunk);
+            std::vector<Chunk> cs(n_chunk);
+            for (uint32_t c = 0; c < n_chunk; c++) { cs[c].beg = u64(); cs[c].end = u64(); }
+            if (bin == 37450) { if (n_chunk) B.tail_start = std::max(B.tail_start, cs[0].end); continue; }      // pseudo-bin: file range, counts
+            for (const Chunk& c : cs) B.tail_start = std::max(B.tail_start, c.end);
+            B.refs[r].bins[bin] = std::move(cs);
+        }
+        const uint32_t n_intv = u32();
+        need(8ull * n_intv);
+        B.refs[r].linear.resize(n_intv);
+        for (uint32_t k = 0; k < n_intv; k++) B.refs[r].linear[k] = u64();
+    }
+    if (n - at >= 8) { B.n_no_coor = u64(); B.has_no_coor = true; }
+    return B;
 }
 
 namespace vcfidx {

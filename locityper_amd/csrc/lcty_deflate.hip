@@ -9,6 +9,7 @@
 // every block to its place; one download follows. An input above knob "bgzf_deflate_max_bytes" goes slice by slice, whole blocks each:
 // a block's bytes do not depend on the blocks around it, so a seam changes nothing.
 #include "lcty_bgzf.hpp"
+#include "lcty_common.hpp"
 #include "lcty_deflate.hpp"
 #include "lcty_objects.hpp"
 #include "lcty_scan.hpp"

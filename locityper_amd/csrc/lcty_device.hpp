@@ -1,11 +1,13 @@
-// lcty_device.hpp — plain views passed by value to the gfx950 kernels, and the probes of the
-// UniqueKmers sets. The sequence primitives (base codes, hashes, k-mer extraction) are in lcty_seq.hpp.
+// lcty_device.hpp — plain views passed by value to the gfx950 kernels, the probes of the UniqueKmers sets, and two things many
+// kernels state: the error word (ErrWord, refuse) and the owner of a flat item (flat_owner). The sequence primitives (base codes,
+// hashes, k-mer extraction) are in lcty_seq.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "../../include/locityper_hip.h"
+#include "lcty_common.hpp"
 #include "lcty_seq.hpp"
 
 namespace lcty {
@@ -101,7 +103,38 @@ struct ReadsView {
     uint64_t park_stride;
 };
 
+// ---- the error word of a pipeline of kernels: (ordinal of the offending item << 8 | class of the error), the smallest wins, so
+// the first item in input order decides and at one item the class of lowest rank. All bits set: nobody refused anything.
+struct ErrWord {
+    DevBuf<unsigned long long> d;
+    unsigned long long* reset(hipStream_t s) {
+        d.ensure(1);
+        LCTY_HIP(hipMemsetAsync(d.p, 0xFF, sizeof(unsigned long long), s));
+        return d.p;
+    }
+    // what the kernels launched on s so far left (synchronises s); false: nothing
+    bool take(hipStream_t s, uint64_t& ordinal, uint32_t& cls) {
+        unsigned long long e = 0;
+        d.download(&e, 1, s);
+        LCTY_HIP(hipStreamSynchronize(s));
+        ordinal = e >> 8; cls = static_cast<uint32_t>(e & 0xFF);
+        return e != ~0ull;
+    }
+};
+
 #ifdef __HIPCC__
+__device__ __forceinline__ void refuse(unsigned long long* err, uint64_t ordinal, uint32_t cls) {
+    atomicMin(err, (static_cast<unsigned long long>(ordinal) << 8) | cls);
+}
+
+// the owner of flat item j: the last k in [0, n) with off[k] <= j (off ascending, off[0] <= j)
+template <typename O, typename J>
+__device__ __forceinline__ uint32_t flat_owner(const O* __restrict__ off, uint32_t n, J j) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] <= j) lo = mid; else hi = mid; }
+    return lo;
+}
+
 // ---- set probe. k-mers of 32..63 bases: the set is an open-addressing table of {lo, hi} pairs built on the host (lcty_locus_create),
 // free = {~0, ~0}: another key type than that of lcty_table.hpp, which serves k <= 31 ----
 __host__ __device__ inline uint64_t kmer128_hash(uint64_t lo, uint64_t hi) { return mix64(lo ^ mix64(hi ^ 0x9E3779B97F4A7C15ull)); }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "lcty_common.hpp"
+#include "lcty_device.hpp"
 #include "lcty_lines.hpp"
 #include "lcty_seq.hpp"
 #include "lcty_table.hpp"
@@ -82,13 +83,9 @@ __global__ void query_check_kernel(const uint8_t* __restrict__ seqs, uint64_t to
 
 // canonical k-mer of value o (every base is one of the four capitals: query_check_kernel has run)
 __device__ inline uint64_t query_kmer(const uint8_t* seqs, const uint64_t* seq_off, const uint64_t* cnt_off, uint32_t n_seqs, uint32_t k, uint64_t o) {
-    uint32_t lo = 0, hi = n_seqs;                                  // the last a with cnt_off[a] <= o
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (cnt_off[mid] <= o) lo = mid; else hi = mid;
-    }
+    const uint32_t a = flat_owner(cnt_off, n_seqs, o);
     uint64_t kmer;
-    canonical_kmer_ascii<uint64_t>(seqs, seq_off[lo] + (o - cnt_off[lo]), k, &kmer);
+    canonical_kmer_ascii<uint64_t>(seqs, seq_off[a] + (o - cnt_off[a]), k, &kmer);
     return kmer;
 }
 

@@ -7,7 +7,8 @@
 // blocks, the flush and the CRC. The output window is a ring of 32 KiB in LDS, the farthest distance of the format, flushed to the
 // block's place with byte stores of neighbouring lanes whenever the next symbol would overwrite a byte not yet flushed, and the CRC
 // of the flushed bytes is taken from the ring on the way. State is 38.4 KiB: four blocks in flight per compute unit.
-#include "lcty_bgzf.hpp"
+#include "lcty_bgzf_read.hpp"
+#include "lcty_device.hpp"
 #include "lcty_inflate.hpp"
 #include "lcty_objects.hpp"
 
@@ -24,7 +25,7 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
         if (k.in_at <= n_comp && k.n_in <= n_comp - k.in_at && k.out_at <= n_out && k.isize <= n_out - k.out_at)
             rc = inflate::inflate_block(&st, comp + k.in_at, k.n_in, out + k.out_at, k.isize, true, nullptr);
         // (block ordinal, class): the first refused block in input order decides, as record_kernel's errors do
-        if (rc != inflate::OK && threadIdx.x == 0) atomicMin(err, (static_cast<unsigned long long>(t) << 8) | rc);
+        if (rc != inflate::OK && threadIdx.x == 0) refuse(err, t, rc);
         __syncthreads();
     }
 }
@@ -42,20 +43,17 @@ void bgzf_inflate_device(lcty_ctx* ctx, const uint8_t* d_comp, uint64_t n_comp, 
     }
     if (tasks.empty()) return;
     if (tasks.size() >= (1ull << 32)) fail(LCTY_ERR_UNSUPPORTED, "%s: %zu BGZF blocks in one call", what, tasks.size());
-    DevBuf<InflateTask> d_tasks; DevBuf<unsigned long long> d_err;
+    DevBuf<InflateTask> d_tasks; ErrWord err;
     d_tasks.alloc(tasks.size()); d_tasks.upload(tasks.data(), tasks.size(), s);
-    d_err.alloc(1);
-    LCTY_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), s));
+    unsigned long long* d_err = err.reset(s);
     // four workgroups of 38.4 KiB fit the LDS of a compute unit
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(tasks.size(), 4ull * static_cast<uint32_t>(ctx->props.multiProcessorCount)));
-    hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid), dim3(64), 0, s, d_comp, n_comp, d_out, n_out, d_tasks.p, static_cast<uint32_t>(tasks.size()), d_err.p);
+    hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid), dim3(64), 0, s, d_comp, n_comp, d_out, n_out, d_tasks.p, static_cast<uint32_t>(tasks.size()), d_err);
     LCTY_HIP(hipGetLastError());
-    unsigned long long e = 0;
-    d_err.download(&e, 1, s);
-    LCTY_HIP(hipStreamSynchronize(s));
-    if (e == ~0ull) return;
-    const BgzfBlock& b = blocks[block_of[std::min<size_t>(e >> 8, block_of.size() - 1)]];
-    fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BGZF block at offset %llu (%s)", what, static_cast<unsigned long long>(b.named_at), inflate::class_name(static_cast<uint32_t>(e & 0xFF)));
+    uint64_t t; uint32_t cls;
+    if (!err.take(s, t, cls)) return;
+    const BgzfBlock& b = blocks[block_of[std::min<size_t>(t, block_of.size() - 1)]];
+    fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BGZF block at offset %llu (%s)", what, static_cast<unsigned long long>(b.named_at), inflate::class_name(cls));
 }
 
 }  // namespace lcty
@@ -72,15 +70,13 @@ int32_t lcty_bgzf_inflate(lcty_ctx* ctx, const uint8_t* comp, uint64_t n_comp, u
         uint64_t total = 0;
         bool plain = true;
         for (uint64_t at = 0; at < n_comp;) {
-            const uint8_t* p = comp + at;
-            const uint32_t csize = bgzf_block_size(p, n_comp - at);
-            if (!csize || csize > n_comp - at) fail(LCTY_ERR_INVALID_DATA, "not a BGZF block at offset %llu", static_cast<unsigned long long>(at));
-            const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
-            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "a BGZF block of %u bytes at offset %llu", isize, static_cast<unsigned long long>(at));
-            const uint32_t head = bgzf_plain_head(p);
-            if (isize && (!head || head + 8u > csize)) plain = false;
-            blocks.push_back(BgzfBlock{csize, isize, total, static_cast<size_t>(at), at, head});
-            total += isize; at += csize;
+            BgzfHead h;
+            const BgzfVerdict v = bgzf_head(comp + at, n_comp - at, h);
+            if (v == BGZF_NOT_A_BLOCK) fail(LCTY_ERR_INVALID_DATA, "not a BGZF block at offset %llu", static_cast<unsigned long long>(at));
+            if (v == BGZF_TOO_LARGE) fail(LCTY_ERR_INVALID_DATA, "a BGZF block of %u bytes at offset %llu", h.isize, static_cast<unsigned long long>(at));
+            if (h.isize && (!h.head || h.head + 8u > h.csize)) plain = false;
+            blocks.push_back(BgzfBlock{h.csize, h.isize, total, static_cast<size_t>(at), at, h.head});
+            total += h.isize; at += h.csize;
         }
         *out_len = total;
         if (!out) return;

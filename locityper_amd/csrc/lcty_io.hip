@@ -16,8 +16,6 @@
 #include <map>
 #include <memory>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -26,81 +24,26 @@
 #include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
 #include "lcty_seq.hpp"
-#include "lcty_vcf_index_parse.hpp"
+#include "lcty_bgzf_index.hpp"
 
 using namespace lcty;
 
 namespace {
 
-std::vector<uint8_t> slurp(const char* path) {
-    FILE* f = fopen(path, "rb");
-    if (!f) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", path);
-    std::vector<uint8_t> buf;
-    uint8_t chunk[1 << 16];
-    size_t n;
-    while ((n = fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    const bool bad = ferror(f) != 0;
-    fclose(f);
-    if (bad) fail(LCTY_ERR_RUNTIME, "read error on %s", path);
-    return buf;
-}
-
-bool ends_with(const std::string& s, const char* suffix) {
-    const size_t n = strlen(suffix);
-    return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
-}
-
 // BGZF (the blocks of a BAM / .bgz file: gzip members of <= 64 KB whose extra field "BC" holds the member's size): the members are
-// independent, so they inflate on the host's cores straight into their places (htslib does the same with its thread pool). Returns
-// false when the input is not BGZF from end to end (then the serial walk below takes it).
+// independent, so they inflate on the host's cores straight into their places (bgzf_inflate_host). Returns false when the input is
+// not BGZF from end to end (then the serial walk below takes it).
 bool inflate_bgzf(const std::vector<uint8_t>& in, const char* what, std::vector<uint8_t>& out) {
-    struct Block { size_t at, size, out_at; uint32_t isize; };
-    std::vector<Block> blocks;
-    size_t i = 0, total = 0;
-    while (i < in.size()) {
-        if (i + 18 > in.size() || in[i] != 0x1f || in[i + 1] != 0x8b || in[i + 2] != 8 || !(in[i + 3] & 4)) return false;
-        const uint32_t xlen = in[i + 10] | (in[i + 11] << 8);
-        if (i + 12 + xlen > in.size()) return false;
-        uint32_t bsize = 0;
-        for (size_t x = i + 12; x + 4 <= i + 12 + xlen;) {
-            const uint32_t slen = in[x + 2] | (in[x + 3] << 8);
-            if (in[x] == 'B' && in[x + 1] == 'C' && slen == 2 && x + 6 <= i + 12 + xlen) bsize = (in[x + 4] | (in[x + 5] << 8)) + 1u;
-            x += 4 + slen;
-        }
-        if (bsize < 12 + xlen + 8 || i + bsize > in.size()) return false;
-        const uint32_t isize = in[i + bsize - 4] | (in[i + bsize - 3] << 8) | (in[i + bsize - 2] << 16) | (static_cast<uint32_t>(in[i + bsize - 1]) << 24);
-        if (isize > 65536) return false;
-        blocks.push_back(Block{i, bsize, total, isize});
-        total += isize; i += bsize;
+    std::vector<BgzfBlock> blocks;
+    uint64_t total = 0;
+    for (size_t i = 0; i < in.size();) {
+        BgzfHead h;
+        if (bgzf_head(in.data() + i, in.size() - i, h) != BGZF_OK) return false;
+        blocks.push_back(BgzfBlock{h.csize, h.isize, total, i, i, h.head});
+        total += h.isize; i += h.csize;
     }
     out.resize(total);
-    const uint32_t n_threads = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>({blocks.size() / 64 + 1, 32, std::thread::hardware_concurrency()})));
-    std::vector<int> rc_of(n_threads, Z_OK);
-    auto work = [&](uint32_t tid) {
-        z_stream zs;
-        memset(&zs, 0, sizeof(zs));
-        if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) { rc_of[tid] = Z_MEM_ERROR; return; }
-        for (size_t b = tid; b < blocks.size(); b += n_threads) {
-            const Block& B = blocks[b];
-            zs.next_in = const_cast<Bytef*>(in.data() + B.at); zs.avail_in = static_cast<uInt>(B.size);
-            zs.next_out = out.data() + B.out_at; zs.avail_out = B.isize;
-            const int rc = inflate(&zs, Z_FINISH);
-            if (rc != Z_STREAM_END || zs.avail_out != 0) { rc_of[tid] = rc == Z_STREAM_END ? Z_DATA_ERROR : (rc == Z_OK ? Z_BUF_ERROR : rc); break; }
-            if (inflateReset(&zs) != Z_OK) { rc_of[tid] = Z_STREAM_ERROR; break; }
-        }
-        inflateEnd(&zs);
-    };
-    // a thread that cannot be started: its share is inflated here (every thread that did start is joined)
-    std::vector<std::thread> th;
-    std::vector<uint32_t> here;
-    for (uint32_t tid = 1; tid < n_threads; tid++) {
-        try { th.emplace_back(work, tid); }
-        catch (const std::system_error&) { here.push_back(tid); }
-    }
-    work(0);
-    for (uint32_t tid : here) work(tid);
-    for (auto& x : th) x.join();
-    for (int rc : rc_of) if (rc != Z_OK) fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BGZF block (zlib %d)", what, rc);
+    bgzf_inflate_host(in.data(), blocks, out.data(), what, 32);
     return true;
 }
 
@@ -419,12 +362,12 @@ extern "C" {
 int32_t lcty_io_read_file(const char* path, uint8_t** data, uint64_t* len) {
     return guarded([&] {
         if (!path || !data || !len) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        std::vector<uint8_t> raw = slurp(path);
+        std::vector<uint8_t> raw = read_whole_file(path);
         const std::string p(path);
         std::vector<uint8_t> out;
-        if (ends_with(p, ".gz") || ends_with(p, ".bgz") || ends_with(p, ".bam")) out = inflate_gzip(raw, path);
-        else if (ends_with(p, ".lz4")) out = decode_lz4(raw, path);
-        else if (ends_with(p, ".br")) out = decode_brotli(raw, path);
+        if (has_suffix(p, ".gz") || has_suffix(p, ".bgz") || has_suffix(p, ".bam")) out = inflate_gzip(raw, path);
+        else if (has_suffix(p, ".lz4")) out = decode_lz4(raw, path);
+        else if (has_suffix(p, ".br")) out = decode_brotli(raw, path);
         else out.swap(raw);
         Handoff h;
         *data = h.copy(out); *len = out.size(); h.commit();
@@ -596,7 +539,7 @@ int32_t lcty_res_to_json(const lcty_call* call, const uint16_t* genotypes, uint3
 int32_t lcty_bam_read(const char* path, const char* const* names, uint32_t n_alleles, int32_t paired, lcty_bam_table** out) {
     return guarded([&] {
         if (!path || !names || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const std::vector<uint8_t> b = inflate_gzip(slurp(path), path);
+        const std::vector<uint8_t> b = inflate_gzip(read_whole_file(path), path);
         size_t i = 0;
         // i <= b.size() always holds; n is compared with what is left, so no sum can wrap (l_text / l_name / block_size are 32-bit
         // words of the file: 0xFFFFFFFF + 4 must not pass as 3)
@@ -716,9 +659,9 @@ void lcty_bam_table_free(lcty_bam_table* t) { delete t; }
 int32_t lcty_fasta_read(const char* path, uint32_t* n_seqs, char* names, uint64_t* names_len, uint8_t* seqs, uint64_t* seqs_len, uint64_t* seq_off) {
     return guarded([&] {
         if (!path || !n_seqs || !names_len || !seqs_len) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        std::vector<uint8_t> raw = slurp(path);
+        std::vector<uint8_t> raw = read_whole_file(path);
         const std::string p(path);
-        const std::vector<uint8_t> text = (ends_with(p, ".gz") || ends_with(p, ".bgz")) ? inflate_gzip(raw, path) : raw;
+        const std::vector<uint8_t> text = (has_suffix(p, ".gz") || has_suffix(p, ".bgz")) ? inflate_gzip(raw, path) : raw;
         std::string nm; std::vector<uint8_t> sq; std::vector<uint64_t> off{0};
         uint32_t n = 0;
         size_t i = 0;
@@ -761,10 +704,10 @@ int32_t lcty_paf_read(const char* path, const char* const* names, uint32_t n_all
         if (!path || !names || !n_entries || !n_cigar) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         const bool fill = id1 != nullptr;
         if (fill && (!id2 || !n_matches || !aln_len || !cigar_off || !cigar)) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        std::vector<uint8_t> raw = slurp(path);
+        std::vector<uint8_t> raw = read_whole_file(path);
         const std::string p(path);
-        const std::vector<uint8_t> text = (ends_with(p, ".gz") || ends_with(p, ".bgz")) ? inflate_gzip(raw, path)
-                                          : ends_with(p, ".lz4") ? decode_lz4(raw, path) : ends_with(p, ".br") ? decode_brotli(raw, path) : raw;
+        const std::vector<uint8_t> text = (has_suffix(p, ".gz") || has_suffix(p, ".bgz")) ? inflate_gzip(raw, path)
+                                          : has_suffix(p, ".lz4") ? decode_lz4(raw, path) : has_suffix(p, ".br") ? decode_brotli(raw, path) : raw;
         std::unordered_map<std::string, uint32_t> ids;
         for (uint32_t a = 0; a < n_alleles; a++) {
             if (!names[a]) fail(LCTY_ERR_INVALID_INPUT, "null contig name");
@@ -988,7 +931,7 @@ int32_t lcty_bg_reads_load(const char* path, const char* contig, uint32_t start,
         if (!path || !contig || !params || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         if (start >= end || padded_start > start || static_cast<uint64_t>(padded_start) + padded_len < end)
             fail(LCTY_ERR_INVALID_INPUT, "background interval [%u, %u) is not inside the padded sequence [%u, +%u)", start, end, padded_start, padded_len);
-        const std::vector<uint8_t> b = inflate_gzip(slurp(path), path);
+        const std::vector<uint8_t> b = inflate_gzip(read_whole_file(path), path);
         size_t i = 0;
         auto need = [&](uint64_t n) { if (n > b.size() - i) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAM", path); };
         need(12);
@@ -1157,7 +1100,7 @@ struct lcty_vcf {
     lcty_vcf_view view{};
 };
 
-// the line rules (split_tabs, parse_gt, gt_index, the head of a record, a record of a region) are in lcty_vcf_index_parse.hpp: the indexed
+// the line rules (split_tabs, parse_gt, gt_index, the head of a record, a record of a region) are in lcty_bgzf_index.hpp: the indexed
 // reader (lcty_vcf_fetch.hip) raises its errors through the same functions
 using namespace lcty::vcfidx;
 
@@ -1168,9 +1111,9 @@ int32_t lcty_vcf_open(const char* path, lcty_vcf** out) {
         if (!path || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         *out = nullptr;
         const std::string p(path);
-        if (ends_with(p, ".bcf")) fail(LCTY_ERR_UNSUPPORTED, "%s: BCF is not read here, convert it to a text VCF", path);
+        if (has_suffix(p, ".bcf")) fail(LCTY_ERR_UNSUPPORTED, "%s: BCF is not read here, convert it to a text VCF", path);
         auto V = std::make_unique<lcty_vcf>();
-        std::vector<uint8_t> raw = slurp(path);
+        std::vector<uint8_t> raw = read_whole_file(path);
         if (raw.size() >= 2 && raw[0] == 0x1f && raw[1] == 0x8b) V->text = inflate_gzip(raw, path); else V->text.swap(raw);
         const std::vector<uint8_t>& t = V->text;
         bool have_header = false;

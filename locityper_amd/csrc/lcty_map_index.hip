@@ -32,9 +32,7 @@ __global__ __launch_bounds__(256) void index_pairs_kernel(const uint8_t* __restr
     const uint64_t w = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     uint32_t bad = 0;
     if (w < n_windows) {
-        uint32_t lo = 0, hi = n_basis;                               // the allele of this window
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (win_off[mid] <= w) lo = mid; else hi = mid; }
-        const uint32_t b = lo;
+        const uint32_t b = flat_owner(win_off, n_basis, w);          // the allele of this window
         const uint64_t i = w - win_off[b];
         uint64_t kmer;
         bool fwd;                                                    // fw <= rv: a palindrome's place counts as forward

@@ -15,31 +15,22 @@
 //   exclusive_scan  over the completing records -> the pairs in the reference's order; assemble_kernel lays out the mates
 //   unpack_kernel   a lane per 32 bases of a mate: 4-bit codes -> bases2 / nmask, back to front and complemented for reverse records;
 //                   a lane writes whole words of its own only
-// The record fields, the name hash and comparison, unpack_kernel and the front half of a fetch (fetch_slice) are shared with the
-// background route, lcty_bg_fetch.hip, through lcty_sample_bam_internal.hpp.
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <zlib.h>
-
+// The record on the device (lcty_bam_record.hpp) and the front half of a fetch (fetch_slice, lcty_sample_bam.hpp, over the slice of
+// lcty_bgzf_read.hpp) are shared with the background route, lcty_bg_fetch.hip.
 #include <algorithm>
 #include <memory>
 #include <string>
-#include <system_error>
-#include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "lcty_bgzf.hpp"
 #include "lcty_objects.hpp"
-#include "lcty_sample_bam_internal.hpp"
+#include "lcty_sample_bam.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
 #include "lcty_writers.hpp"
 
 namespace lcty {
 
-// error classes, by rank at one record; (record ordinal << 8 | class) goes through atomicMin
+// error classes, by rank at one record (refuse, lcty_device.hpp)
 enum : uint32_t { E_SHORT = 1, E_UNSORTED = 2, E_CG = 3, E_NOSEQ = 4, E_UNPAIRED = 5, E_TWO_ENDS = 6 };
 constexpr uint32_t INFO_KEPT = 1u << 16, INFO_WAITS = 1u << 17;
 
@@ -117,7 +108,7 @@ __global__ __launch_bounds__(256) void record_kernel(const SampleView V) {
     if (valid) {
         V.info[r] = info; V.kept[r] = kept ? 1u : 0u;
         if (!kept) V.hash[r] = 0;
-        if (err) atomicMin(V.err, (static_cast<unsigned long long>(r) << 8) | err);
+        if (err) refuse(V.err, r, err);
     }
     const unsigned long long prim = __ballot(primary);
     if (lane == 0 && prim) atomicAdd(V.n_primary, static_cast<uint32_t>(__popcll(prim)));
@@ -153,12 +144,12 @@ __global__ __launch_bounds__(256) void pair_kernel(const uint32_t* __restrict__ 
         if (t < i && !same_name(raw, rec_off[rt], o)) continue;
         const uint32_t inf = info[rt];
         if ((inf & 0xC0u) == 0) {
-            if (t == i) atomicMin(err, (static_cast<unsigned long long>(r) << 8) | E_UNPAIRED);
+            if (t == i) refuse(err, r, E_UNPAIRED);
             continue;
         }
         const bool first = (inf & 0x40u) != 0;
         if (waiting) {
-            if (first == wait_first) { if (t == i) atomicMin(err, (static_cast<unsigned long long>(r) << 8) | E_TWO_ENDS); }
+            if (first == wait_first) { if (t == i) refuse(err, r, E_TWO_ENDS); }
             else if (t == i) mate = wait_s;
             waiting = false;                                                     // HashSet::take removed it either way
         } else if (inf & INFO_WAITS) { waiting = true; wait_first = first; wait_s = st; }
@@ -192,48 +183,6 @@ __global__ __launch_bounds__(256) void offsets_kernel(const uint32_t* __restrict
     if (m < n) mate_off[m] = 32ull * unit_off[m];
 }
 
-// ---- host: BGZF by block, the header, the index ---------------------------------------------------------------------------------
-
-void pread_all(int fd, void* buf, size_t n, uint64_t at, const char* path) {
-    uint8_t* p = static_cast<uint8_t*>(buf);
-    while (n) {
-        const ssize_t got = pread(fd, p, n, static_cast<off_t>(at));
-        if (got <= 0) fail(LCTY_ERR_RUNTIME, "read error on %s", path);
-        p += got; n -= static_cast<size_t>(got); at += static_cast<uint64_t>(got);
-    }
-}
-void inflate_block(z_stream& zs, const uint8_t* in, uint32_t csize, uint8_t* out, uint32_t isize, const char* path) {
-    zs.next_in = const_cast<Bytef*>(in); zs.avail_in = csize;
-    zs.next_out = out; zs.avail_out = isize;
-    const int rc = inflate(&zs, Z_FINISH);
-    if (rc != Z_STREAM_END || zs.avail_out != 0) fail(LCTY_ERR_INVALID_DATA, "%s: corrupt BGZF block (zlib %d)", path, rc);
-    if (inflateReset(&zs) != Z_OK) fail(LCTY_ERR_RUNTIME, "zlib: inflateReset");
-}
-
-void bgzf_inflate_host(const uint8_t* comp, const std::vector<BgzfBlock>& blocks, uint8_t* out, const char* path) {
-    const uint32_t n_threads = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>({blocks.size() / 64 + 1, 16, std::thread::hardware_concurrency()})));
-    std::vector<std::string> failed(n_threads);
-    auto work = [&](uint32_t id) {
-        z_stream zs;
-        memset(&zs, 0, sizeof(zs));
-        if (inflateInit2(&zs, 16 + MAX_WBITS) != Z_OK) { failed[id] = "zlib: inflateInit2"; return; }
-        try {
-            for (size_t k = id; k < blocks.size(); k += n_threads)
-                if (blocks[k].isize) inflate_block(zs, comp + blocks[k].in_at, blocks[k].csize, out + blocks[k].out_at, blocks[k].isize, path);
-        } catch (const Error& e) { failed[id] = e.what(); }
-        inflateEnd(&zs);
-    };
-    std::vector<std::thread> th;
-    std::vector<uint32_t> here;
-    for (uint32_t id = 1; id < n_threads; id++) {
-        try { th.emplace_back(work, id); } catch (const std::system_error&) { here.push_back(id); }
-    }
-    work(0);
-    for (uint32_t id : here) work(id);
-    for (auto& x : th) x.join();
-    for (const std::string& f : failed) if (!f.empty()) fail(LCTY_ERR_INVALID_DATA, "%s", f.c_str());
-}
-
 }  // namespace lcty
 
 using namespace lcty;
@@ -242,7 +191,7 @@ struct lcty_sample_reads {
     lcty_ctx* ctx = nullptr;
     bool paired = false;
     uint64_t n = 0;                              // pairs, or single reads
-    FetchedSlice F;                              // the inflated blocks of the call and the records walked in them
+    Slice F;                                     // the inflated blocks of the call and the records walked in them
     DevBuf<uint32_t> d_len, d_nm, d_src; DevBuf<uint64_t> d_off, d_bases;
     uint64_t n_units = 0;
     std::vector<uint32_t> h_len, h_src, h_src_stream, h_bases, h_nm;    // h_src: a mate's record among the records walked (rec_off); _stream: in the fetched stream
@@ -252,60 +201,20 @@ struct lcty_sample_reads {
 
 namespace {
 
-bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-
-std::vector<uint8_t> read_file(const std::string& path) {
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", path.c_str());
-    std::vector<uint8_t> buf;
-    uint8_t chunk[1 << 16];
-    size_t n;
-    while ((n = fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    const bool bad = ferror(f) != 0;
-    fclose(f);
-    if (bad) fail(LCTY_ERR_RUNTIME, "read error on %s", path.c_str());
-    return buf;
-}
-
 void load_bai(lcty_sample_bam* b) {
-    const std::vector<uint8_t> x = read_file(b->index_path);
-    const char* ip = b->index_path.c_str();
-    if (x.size() >= 4 && memcmp(x.data(), "CSI\1", 4) == 0) fail(LCTY_ERR_UNSUPPORTED, "%s is a CSI index (only BAI indices are read)", ip);
-    if (x.size() >= 2 && x[0] == 0x1f && x[1] == 0x8b) fail(LCTY_ERR_UNSUPPORTED, "%s is compressed: a CSI index? (only BAI indices are read)", ip);
-    if (x.size() < 8 || memcmp(x.data(), "BAI\1", 4) != 0) fail(LCTY_ERR_INVALID_DATA, "%s is not a BAI index", ip);
-    size_t at = 4;
-    auto need = [&](size_t n) { if (at + n > x.size()) fail(LCTY_ERR_INVALID_DATA, "%s: truncated BAI index", ip); };
-    auto u32 = [&]() { need(4); uint32_t v; memcpy(&v, x.data() + at, 4); at += 4; return v; };
-    auto u64 = [&]() { need(8); uint64_t v; memcpy(&v, x.data() + at, 8); at += 8; return v; };
-    const uint32_t n_ref = u32();
-    if (n_ref != b->lengths.size()) fail(LCTY_ERR_INVALID_DATA, "%s: the index has %u references, the BAM header %zu", ip, n_ref, b->lengths.size());
-    b->refs.resize(n_ref);
-    b->tail_start = b->first_record;
-    for (uint32_t r = 0; r < n_ref; r++) {
-        const uint32_t n_bin = u32();
-        for (uint32_t k = 0; k < n_bin; k++) {
-            const uint32_t bin = u32(), n_chunk = u32();
-            need(16ull * n_chunk);
-            std::vector<Chunk> cs(n_chunk);
-            for (uint32_t c = 0; c < n_chunk; c++) { cs[c].beg = u64(); cs[c].end = u64(); }
-            if (bin == 37450) { if (n_chunk) b->tail_start = std::max(b->tail_start, cs[0].end); continue; }      // pseudo-bin: file range, counts
-            for (const Chunk& c : cs) b->tail_start = std::max(b->tail_start, c.end);
-            b->refs[r].bins[bin] = std::move(cs);
-        }
-        const uint32_t n_intv = u32();
-        need(8ull * n_intv);
-        b->refs[r].linear.resize(n_intv);
-        for (uint32_t k = 0; k < n_intv; k++) b->refs[r].linear[k] = u64();
-    }
-    if (at + 8 <= x.size()) { b->n_no_coor = u64(); b->has_no_coor = true; }
+    const std::vector<uint8_t> x = read_whole_file(b->index_path.c_str());
+    Bai B = parse_bai(x.data(), x.size(), b->lengths.size(), b->index_path.c_str());
+    b->refs = std::move(B.refs);
+    b->tail_start = std::max(b->first_record, B.tail_start);
+    b->n_no_coor = B.n_no_coor; b->has_no_coor = B.has_no_coor;
 }
 
 // the chunks of a call: those of its regions (region_chunks) and the tail of the file, sorted and merged (merge_chunks,
-// lcty_vcf_index_parse.hpp: the rule the tabix index of lcty_vcf_fetch.hip follows too)
+// lcty_bgzf_index.hpp: the rule the tabix index of lcty_vcf_fetch.hip follows too)
 std::vector<Chunk> plan_chunks(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, const uint32_t* start, const uint32_t* end, bool with_unmapped,
                                bool whole_file) {
     std::vector<Chunk> cs;
-    const uint64_t file_end = b->fsize << 16;
+    const uint64_t file_end = b->file.fsize << 16;
     if (whole_file) { cs.push_back(Chunk{b->first_record, file_end}); return cs; }
     for (uint32_t i = 0; i < n; i++) region_chunks(b->refs[tid[i]], start[i], end[i], cs);
     if (with_unmapped && b->tail_start < file_end) cs.push_back(Chunk{b->tail_start, file_end});
@@ -334,93 +243,18 @@ std::string record_name(const uint8_t* slice, uint64_t o) {
     return s;
 }
 
-void read_chunk_blocks(int fd, uint64_t fsize, const char* path, const std::vector<Chunk>& cs, std::vector<uint8_t>& comp, std::vector<BgzfBlock>& blocks,
-                       std::vector<ChunkSpan>& spans, uint64_t& total, uint64_t& bytes_read) {
-    for (const Chunk& c : cs) {
-        const uint64_t cbeg = c.beg >> 16, cend = c.end >> 16;
-        const uint32_t uend = static_cast<uint32_t>(c.end & 0xFFFF);
-        if (cbeg >= fsize) continue;
-        uint64_t rend = cend;                                              // ... and the block the chunk ends in, when it reaches into it
-        if (uend && cend < fsize) {
-            uint8_t hd[512];
-            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), fsize - cend));
-            pread_all(fd, hd, n, cend, path);
-            const uint32_t csize = bgzf_block_size(hd, n);
-            if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(cend));
-            rend = std::min<uint64_t>(fsize, cend + csize);
-        }
-        rend = std::min<uint64_t>(rend, fsize);
-        const size_t in0 = comp.size();
-        comp.resize(in0 + (rend - cbeg));
-        pread_all(fd, comp.data() + in0, rend - cbeg, cbeg, path);
-        bytes_read += rend - cbeg;
-        ChunkSpan sp{blocks.size(), 0, total + (c.beg & 0xFFFF), 0, 0};
-        bool end_seen = false;
-        uint64_t at = cbeg;
-        while (at < rend && (at < cend || (at == cend && uend))) {
-            const uint8_t* p = comp.data() + in0 + (at - cbeg);
-            const uint32_t csize = bgzf_block_size(p, rend - at);
-            if (!csize || at + csize > rend) {
-                if (at + 0x10000 >= fsize) fail(LCTY_ERR_INVALID_DATA, "%s: truncated or corrupt BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
-                fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu (an index of another file?)", path, static_cast<unsigned long long>(at));
-            }
-            const uint32_t isize = p[csize - 4] | (p[csize - 3] << 8) | (p[csize - 2] << 16) | (static_cast<uint32_t>(p[csize - 1]) << 24);
-            if (isize > 0x10000) fail(LCTY_ERR_INVALID_DATA, "%s: a BGZF block of %u bytes", path, isize);
-            if (at == cbeg && (c.beg & 0xFFFF) > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index starts behind its block", path);
-            if (at == cend) { if (uend > isize) fail(LCTY_ERR_INVALID_DATA, "%s: a chunk of the index ends behind its block", path); sp.chain_end = total + uend; end_seen = true; }
-            blocks.push_back(BgzfBlock{csize, isize, total, in0 + static_cast<size_t>(at - cbeg), at, bgzf_plain_head(p)});
-            total += isize; at += csize;
-        }
-        sp.n_blocks = blocks.size() - sp.first_block; sp.span_end = total;
-        if (!end_seen) sp.chain_end = total;
-        if (sp.n_blocks) spans.push_back(sp);
-    }
-}
-
-uint64_t count_chunk_blocks(int fd, uint64_t fsize, const char* path, const std::vector<Chunk>& cs) {
-    uint64_t blocks = 0;
-    for (const Chunk& c : cs) {
-        uint64_t at = c.beg >> 16;
-        const uint64_t last = c.end >> 16;
-        while (at < fsize && (at < last || (at == last && (c.end & 0xFFFF)))) {
-            uint8_t hd[512];
-            const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), fsize - at));
-            pread_all(fd, hd, n, at, path);
-            const uint32_t csize = bgzf_block_size(hd, n);
-            if (!csize) fail(LCTY_ERR_INVALID_DATA, "%s: not a BGZF block at offset %llu", path, static_cast<unsigned long long>(at));
-            blocks++; at += csize;
-        }
-    }
-    return blocks;
-}
-
-bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
-                 bool with_unmapped, bool whole_file, FetchedSlice& F, DevBuf<uint8_t>& d_raw, lcty_sample_bam_stats& S) {
-    const char* path = bam->path.c_str();
-    const uint64_t cap = static_cast<uint64_t>(ctx->knob("sample_bam_max_slice_bytes", 1ll << 33));
-    if (ctx->knob("sample_bam_inflate", 0) > 1) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_inflate = %lld (0: host, 1: device)", static_cast<long long>(ctx->knob("sample_bam_inflate", 0)));
-    const std::vector<Chunk> cs = plan_chunks(bam, n_regions, tid, start, end, with_unmapped, whole_file);
-    S.n_chunks = cs.size();
-
-    // ---- the bytes of the chunks, split into blocks
-    double t0 = now_ms();
-    std::vector<uint8_t> comp;
-    std::vector<BgzfBlock> blocks;
-    std::vector<ChunkSpan> spans;
-    uint64_t total = 0;
-    read_chunk_blocks(bam->fd, bam->fsize, path, cs, comp, blocks, spans, total, S.bytes_read);
-    S.ms_read = now_ms() - t0;
-    S.blocks_inflated = blocks.size(); S.bytes_inflated = total;
-    if (total > cap)
-        fail(LCTY_ERR_UNSUPPORTED, "%s: the fetched slice has %llu bytes, more than %llu (knob sample_bam_max_slice_bytes)", path,
-             static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
-
-    const bool on_device = inflate_slice(ctx, comp, blocks, total, F, d_raw, path, S.ms_inflate);
+void fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
+                 bool with_unmapped, bool whole_file, Slice& F, lcty_sample_bam_stats& S) {
+    const char* path = bam->file.path.c_str();
+    SliceStats T{};
+    F.read(ctx, bam->file, plan_chunks(bam, n_regions, tid, start, end, with_unmapped, whole_file), "sample_bam_max_slice_bytes", T);
+    T.ms_inflate = F.inflate(ctx, path);
+    T.put(S);
 
     // ---- the chain of record lengths
-    t0 = now_ms();
+    const double t0 = now_ms();
     std::vector<uint64_t>& rec_off = F.rec_off;
-    for (const ChunkSpan& sp : spans) {
+    for (const ChunkSpan& sp : F.spans) {
         uint64_t p = sp.chain_beg;
         while (p < sp.chain_end) {
             uint32_t bs = 0;
@@ -435,35 +269,6 @@ bool fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const 
     S.records_walked = n_rec;
     S.ms_walk = now_ms() - t0;
     if (n_rec >= 0x7FFFFFF0ull) fail(LCTY_ERR_UNSUPPORTED, "%s: %llu records in one fetch", path, static_cast<unsigned long long>(n_rec));
-
-    return on_device;
-}
-
-bool inflate_slice(lcty_ctx* ctx, std::vector<uint8_t>& comp, const std::vector<BgzfBlock>& blocks, uint64_t total, FetchedSlice& F,
-                   DevBuf<uint8_t>& d_raw, const char* path, double& ms_inflate) {
-    // ---- inflate: every block into its place of one page-locked buffer
-    ctx->activate();
-    hipStream_t s = ctx->stream;
-    F.total = total;
-    LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&F.slice), total + SLICE_PAD, hipHostMallocDefault));
-    memset(F.slice + total, 0, SLICE_PAD);
-    const double t0 = now_ms();
-    // knob "sample_bam_inflate" 1: on the device, straight into the buffer record_kernel reads, and from there to the page-locked
-    // slice for the walk and the writer; blocks with more in their gzip header than the extra field leave the call to zlib
-    bool on_device = ctx->knob("sample_bam_inflate", 0) == 1 && total > 0;
-    for (const BgzfBlock& b : blocks) if (b.isize && (!b.head || b.head + 8u > b.csize)) on_device = false;
-    if (on_device) {
-        DevBuf<uint8_t> d_comp;
-        d_comp.alloc(comp.size()); d_raw.alloc(total + SLICE_PAD);
-        d_comp.upload(comp.data(), comp.size(), s);
-        LCTY_HIP(hipMemsetAsync(d_raw.p + total, 0, SLICE_PAD, s));
-        bgzf_inflate_device(ctx, d_comp.p, comp.size(), blocks, d_raw.p, total, s, path);
-        d_raw.download(F.slice, total, s);
-        LCTY_HIP(hipStreamSynchronize(s));
-    } else bgzf_inflate_host(comp.data(), blocks, F.slice, path);
-    ms_inflate = now_ms() - t0;
-    std::vector<uint8_t>().swap(comp);
-    return on_device;
 }
 
 }  // namespace lcty
@@ -475,18 +280,12 @@ int32_t lcty_sample_bam_open(const char* path, const char* index_path, lcty_samp
         if (!path || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         *out = nullptr;
         std::unique_ptr<lcty_sample_bam> b(new lcty_sample_bam());
-        b->path = path;
-        b->fd = open(path, O_RDONLY | O_CLOEXEC);
-        if (b->fd < 0) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", path);
-        struct stat st;
-        if (fstat(b->fd, &st) != 0) fail(LCTY_ERR_RUNTIME, "cannot stat %s", path);
-        b->fsize = static_cast<uint64_t>(st.st_size);
-        if (b->fsize >= (1ull << 48)) fail(LCTY_ERR_UNSUPPORTED, "%s: a file of 2^48 bytes or more", path);
+        b->file.open(path);
         uint8_t magic[4] = {0, 0, 0, 0};
-        if (b->fsize >= 4) pread_all(b->fd, magic, 4, 0, path);
+        if (b->file.fsize >= 4) pread_all(b->file.fd, magic, 4, 0, path);
         if (memcmp(magic, "CRAM", 4) == 0) fail(LCTY_ERR_UNSUPPORTED, "%s is a CRAM file (only BAM files are read)", path);
         // ---- the header (SAM specification 4.2)
-        BgzfSerial in(b->fd, b->fsize, path);
+        BgzfSerial in(b->file.fd, b->file.fsize, path);
         uint8_t head[8];
         if (!in.read(head, 8) || memcmp(head, "BAM\1", 4) != 0) fail(LCTY_ERR_INVALID_DATA, "%s is not a BAM file", path);
         uint32_t l_text; memcpy(&l_text, head + 4, 4);
@@ -510,11 +309,11 @@ int32_t lcty_sample_bam_open(const char* path, const char* index_path, lcty_samp
         // ---- the index
         const std::string p = path;
         if (index_path) b->index_path = index_path;
-        else if (file_exists(p + ".bai")) b->index_path = p + ".bai";
-        else if (p.size() > 4 && p.compare(p.size() - 4, 4, ".bam") == 0 && file_exists(p.substr(0, p.size() - 4) + ".bai")) b->index_path = p.substr(0, p.size() - 4) + ".bai";
-        else if (file_exists(p + ".csi")) fail(LCTY_ERR_UNSUPPORTED, "%s.csi is a CSI index (only BAI indices are read)", path);
+        else if (is_regular_file(p + ".bai")) b->index_path = p + ".bai";
+        else if (p.size() > 4 && has_suffix(p, ".bam") && is_regular_file(p.substr(0, p.size() - 4) + ".bai")) b->index_path = p.substr(0, p.size() - 4) + ".bai";
+        else if (is_regular_file(p + ".csi")) fail(LCTY_ERR_UNSUPPORTED, "%s.csi is a CSI index (only BAI indices are read)", path);
         else fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s.bai)", path, path);
-        if (!file_exists(b->index_path)) fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s)", path, b->index_path.c_str());
+        if (!is_regular_file(b->index_path)) fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s)", path, b->index_path.c_str());
         load_bai(b.get());
         *out = b.release();
     });
@@ -571,12 +370,7 @@ int32_t lcty_sample_bam_plan(lcty_sample_bam* bam, uint32_t n_regions, const uin
     return guarded([&] {
         if (!bam || !n_chunks || (chunk_cap && (!chunk_beg || !chunk_end))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         check_regions(bam, n_regions, tid, start, end);
-        const std::vector<Chunk> cs = plan_chunks(bam, n_regions, tid, start, end, with_unmapped != 0, false);
-        *n_chunks = cs.size();
-        for (size_t i = 0; i < cs.size() && i < chunk_cap; i++) { chunk_beg[i] = cs[i].beg; chunk_end[i] = cs[i].end; }
-        if (blocks_total) {
-            *blocks_total = count_chunk_blocks(bam->fd, bam->fsize, bam->path.c_str(), cs);
-        }
+        report_plan(bam->file, plan_chunks(bam, n_regions, tid, start, end, with_unmapped != 0, false), chunk_cap, n_chunks, chunk_beg, chunk_end, blocks_total);
     });
 }
 
@@ -588,7 +382,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
     return guarded([&] {
         if (!ctx || !bam || !reads) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         const double t_start = now_ms();
-        const char* path = bam->path.c_str();
+        const char* path = bam->file.path.c_str();
         if (whole_file && (n_regions || with_unmapped)) fail(LCTY_ERR_INVALID_INPUT, "whole_file goes without regions and without with_unmapped");
         if (!whole_file && !n_regions && !with_unmapped) fail(LCTY_ERR_INVALID_INPUT, "nothing to fetch: no regions, no unmapped reads, not the whole file");
         if (paired < 0) {
@@ -601,19 +395,18 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         if (hash_bits > 64) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_hash_bits = %lld (0 .. 64)", static_cast<long long>(hash_bits));
         const uint64_t hash_mask = hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1;
         lcty_sample_bam_stats S{};
-        S.n_regions = n_regions; S.file_bytes = bam->fsize;
+        S.n_regions = n_regions; S.file_bytes = bam->file.fsize;
         // ---- the front half: chunks, pread, BGZF split, inflate, the chain of record lengths
         std::unique_ptr<lcty_sample_reads> R(new lcty_sample_reads());
         R->ctx = ctx; R->paired = paired != 0;
-        DevBuf<uint8_t> d_raw;
-        const bool on_device = fetch_slice(ctx, bam, n_regions, tid, start, end, with_unmapped != 0, whole_file != 0, R->F, d_raw, S);
+        fetch_slice(ctx, bam, n_regions, tid, start, end, with_unmapped != 0, whole_file != 0, R->F, S);
         hipStream_t s = ctx->stream;
-        const uint64_t total = R->F.total;
         const std::vector<uint64_t>& rec_off = R->F.rec_off;
         const uint64_t n_rec = rec_off.size();
         double t0;
 
         auto finish = [&]() {
+            R->F.release_device();                                               // the handle keeps the host's slice alone
             S.ms_total = now_ms() - t_start;
             if (stats) *stats = S;
             *reads = R.release();
@@ -622,36 +415,31 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
 
         // ---- upload, record kernel
         t0 = now_ms();
-        DevBuf<uint64_t> d_rec_off, d_hash; DevBuf<uint32_t> d_reg, d_info, d_kept, d_nprim; DevBuf<unsigned long long> d_err;
-        if (!on_device) { d_raw.alloc(total + SLICE_PAD); d_raw.upload(R->F.slice, total + SLICE_PAD, s); }
+        DevBuf<uint64_t> d_rec_off, d_hash; DevBuf<uint32_t> d_reg, d_info, d_kept, d_nprim; ErrWord err;
+        const uint32_t* raw = reinterpret_cast<const uint32_t*>(R->F.device(s));
         d_rec_off.alloc(n_rec); d_rec_off.upload(rec_off.data(), n_rec, s);
         std::vector<uint32_t> reg(3ull * std::max(n_regions, 1u), 0);
         for (uint32_t i = 0; i < n_regions; i++) { reg[i] = tid[i]; reg[n_regions + i] = start[i]; reg[2ull * n_regions + i] = end[i]; }
         d_reg.alloc(reg.size()); d_reg.upload(reg.data(), reg.size(), s);
-        d_info.alloc(n_rec); d_kept.alloc(n_rec); d_hash.alloc(n_rec); d_nprim.alloc(1); d_err.alloc(1);
+        d_info.alloc(n_rec); d_kept.alloc(n_rec); d_hash.alloc(n_rec); d_nprim.alloc(1);
         d_nprim.zero(s);
-        LCTY_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), s));
+        unsigned long long* d_err = err.reset(s);
         LCTY_HIP(hipStreamSynchronize(s));
         S.ms_upload = now_ms() - t0;
         t0 = now_ms();
-        const uint32_t* raw = reinterpret_cast<const uint32_t*>(d_raw.p);
         SampleView V{};
         V.raw = raw; V.rec_off = d_rec_off.p; V.n_rec = static_cast<uint32_t>(n_rec);
         V.reg_tid = d_reg.p; V.reg_start = d_reg.p + n_regions; V.reg_end = d_reg.p + 2ull * n_regions; V.n_reg = n_regions;
         V.with_unmapped = with_unmapped != 0; V.whole_file = whole_file != 0; V.hash_mask = hash_mask;
-        V.info = d_info.p; V.hash = d_hash.p; V.kept = d_kept.p; V.err = d_err.p; V.n_primary = d_nprim.p;
+        V.info = d_info.p; V.hash = d_hash.p; V.kept = d_kept.p; V.err = d_err; V.n_primary = d_nprim.p;
         hipLaunchKernelGGL(record_kernel, dim3(blocks_of(n_rec, 256)), dim3(256), 0, s, V);
         LCTY_HIP(hipGetLastError());
         ScanTotal scan;
         DevBuf<uint32_t> d_scan, d_stream;
         const uint32_t n_stream = scan.run(d_kept, d_scan, n_rec, ctx);
         auto check_err = [&]() {
-            unsigned long long e = 0;
-            d_err.download(&e, 1, s);
-            LCTY_HIP(hipStreamSynchronize(s));
-            if (e == ~0ull) return;
-            const uint32_t cls = static_cast<uint32_t>(e & 0xFF);
-            const uint64_t r = e >> 8;
+            uint64_t r; uint32_t cls;
+            if (!err.take(s, r, cls)) return;
             const uint64_t o = rec_off[r];
             if (cls == E_SHORT) fail(LCTY_ERR_INVALID_DATA, "%s: record %llu of the fetched slice is shorter than its fields", path, static_cast<unsigned long long>(r));
             const std::string name = record_name(R->F.slice, o);
@@ -688,7 +476,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
             const uint64_t* keys = where ? d_kb.p : d_ka.p; const uint64_t* vals = where ? d_vb.p : d_va.p;
             d_mate_of.alloc(n_stream); d_completes.alloc(n_stream);
             hipLaunchKernelGGL(pair_kernel, dim3(blocks_of(n_stream, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_info.p, d_stream.p, keys, vals, n_stream,
-                               d_mate_of.p, d_completes.p, d_err.p);
+                               d_mate_of.p, d_completes.p, d_err);
             LCTY_HIP(hipGetLastError());
             n_out = scan.run(d_completes, d_pair_ix, n_stream, ctx);
             check_err();

@@ -1,9 +1,9 @@
 // lcty_vcf_fetch.hip — a locus's window of an indexed pangenome VCF, the input of `locityper target -v`:
 //   src/command/add.rs:496-499 the two fetches of the flanks, 802 bcf::IndexedReader
 //   src/seq/panvcf.rs:85-91 HaplotypeNames::new, 149-184 filter_variants
-// Host: the tabix index and the lines of the file's head (lcty_vcf_index_parse.hpp), the chunks of the window, pread of their byte
-// ranges, the BGZF split and the inflate into one slice (read_chunk_blocks, inflate_slice of lcty_sample_bam.hip: zlib, or the device
-// with knob "sample_bam_inflate" 1). Device, on the text of that slice and one (begin, end) byte range per merged chunk:
+// Host: the tabix index and the lines of the file's head (lcty_bgzf_index.hpp), the chunks of the window, pread of their byte
+// ranges, the BGZF split and the inflate into one slice (Slice of lcty_bgzf_read.hpp: zlib, or the device with knob
+// "sample_bam_inflate" 1). Device, on the text of that slice and one (begin, end) byte range per merged chunk:
 //   line_kernel     16 bytes per lane: a line starts at the start of a range and behind every '\n' inside one; counted per workgroup,
 //                   scanned (exclusive_scan), then written in file order
 //   head_kernel     a wavefront per line: its end (without '\r'), the first nine tabs (256 bytes per step, a scan of the lanes' tab
@@ -13,26 +13,20 @@
 //   allele_kernel   a wavefront per record: REF and the ALT alleles into the pool, their offsets
 //   gt_kernel       a wavefront per record: the tabs behind the ninth column, 256 bytes per step; the lane that holds the tab in front
 //                   of sample i parses its GT subfield (the rules of parse_gt) and writes gt and phased; the column count
-// Every error — of a kept record, or a bad position in any line that names the contig — goes through one atomicMin of the line's
-// ordinal; the host then runs the line functions of lcty_vcf_region over that one line, so status and text are that reader's.
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
+// Every error — of a kept record, or a bad position in any line that names the contig — goes to the error word with the line's
+// ordinal (refuse, lcty_device.hpp); the host then runs the line functions of lcty_vcf_region over that one line, so status and text are that reader's.
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "lcty_bgzf.hpp"
+#include "lcty_bgzf_read.hpp"
 #include "lcty_objects.hpp"
-#include "lcty_sample_bam_internal.hpp"
 #include "lcty_scan.hpp"
-#include "lcty_vcf_index_parse.hpp"
 
 namespace lcty {
 
 constexpr uint32_t LINE_BYTES = 16, LINE_THREADS = 256;            // line_kernel: bytes per lane, lanes per workgroup
-enum : uint32_t { E_LONG = 1, E_LINE = 2 };                         // (line ordinal << 8 | class) goes through atomicMin
+enum : uint32_t { E_LONG = 1, E_LINE = 2 };                         // error classes of a line (refuse, lcty_device.hpp)
 
 // the merged chunks as byte ranges of the slice, sorted and disjoint
 struct Ranges { const uint64_t* beg; const uint64_t* end; uint32_t n; };
@@ -112,7 +106,7 @@ __global__ __launch_bounds__(WAVE) void head_kernel(const HeadView V) {
     if (!(next < rend) && le > b && raw[le - 1] == '\n') le--;
     if (le > b && raw[le - 1] == '\r') le--;
     if (le == b || raw[b] == '#') return;
-    auto refuse = [&](uint32_t cls) { if (lane == 0) atomicMin(V.err, (static_cast<unsigned long long>(l) << 8) | cls); };
+    auto refuse = [&](uint32_t cls) { if (lane == 0) lcty::refuse(V.err, l, cls); };
     if (le - b >= (1ull << 32)) { refuse(E_LONG); return; }
     // ---- the first nine tabs: 256 bytes per step, a dword per lane; nothing assumes they lie in the first step
     uint32_t nt = 0;
@@ -232,7 +226,7 @@ struct GtView {
     unsigned long long* err;
 };
 
-// The GT subfield of the sample field that starts at q (it ends at a tab or at le): parse_gt of lcty_vcf_index_parse.hpp and the two
+// The GT subfield of the sample field that starts at q (it ends at a tab or at le): parse_gt of lcty_bgzf_index.hpp and the two
 // checks of a used sample. Writes the ploidy[i] entries of gt and the entry of phased as the host reader does; false: an error.
 __device__ inline bool sample_field(const GtView& V, uint64_t k, uint32_t i, uint64_t q, uint64_t le, uint32_t which) {
     const uint8_t* raw = V.raw;
@@ -301,7 +295,7 @@ __global__ __launch_bounds__(WAVE) void gt_kernel(const GtView V) {
         seen += __shfl(incl, WAVE - 1);
     }
     if (seen != V.S) ok = false;                                               // 9 + S columns
-    if (__any(!ok) && lane == 0) atomicMin(V.err, (static_cast<unsigned long long>(V.rec_line[k]) << 8) | E_LINE);
+    if (__any(!ok) && lane == 0) refuse(V.err, V.rec_line[k], E_LINE);
 }
 
 }  // namespace lcty
@@ -309,56 +303,41 @@ __global__ __launch_bounds__(WAVE) void gt_kernel(const GtView V) {
 using namespace lcty;
 
 struct lcty_vcf_indexed {
-    std::string path, index_path;
-    int fd = -1;
-    uint64_t fsize = 0;
+    BgzfFile file;
+    std::string index_path;
     vcfidx::Tbi tbi;
     std::vector<std::string> samples;
     std::string sample_blob;
     std::vector<uint32_t> ploidy, hap_off;           // of the first record of the file; hap_off[n_samples + 1]
     lcty_vcf_view view{};
-    ~lcty_vcf_indexed() { if (fd >= 0) close(fd); }
 };
 
 namespace {
 
-bool is_file(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-bool has_suffix(const std::string& s, const char* suffix) {
-    const size_t n = strlen(suffix);
-    return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
-}
-
-struct Fd { int fd = -1; ~Fd() { if (fd >= 0) close(fd); } };
-
 // the .tbi file: BGZF, inflated by zlib block after block
 void load_tbi(lcty_vcf_indexed* v) {
     const char* ip = v->index_path.c_str();
-    Fd f;
-    f.fd = open(ip, O_RDONLY | O_CLOEXEC);
-    if (f.fd < 0) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", ip);
-    struct stat st;
-    if (fstat(f.fd, &st) != 0) fail(LCTY_ERR_RUNTIME, "cannot stat %s", ip);
-    const uint64_t size = static_cast<uint64_t>(st.st_size);
+    BgzfFile f;
+    f.open(ip);
     uint8_t magic[2] = {0, 0};
-    if (size >= 2) pread_all(f.fd, magic, 2, 0, ip);
+    if (f.fsize >= 2) pread_all(f.fd, magic, 2, 0, ip);
     if (magic[0] != 0x1f || magic[1] != 0x8b) fail(LCTY_ERR_INVALID_DATA, "%s is not a tabix index (it is not compressed)", ip);
-    BgzfSerial in(f.fd, size, ip);
+    BgzfSerial in(f.fd, f.fsize, ip);
     std::vector<uint8_t> x;
-    while (in.load()) { x.insert(x.end(), in.data.begin() + static_cast<ptrdiff_t>(in.at), in.data.end()); in.at = in.data.size(); }
+    while (in.append_block(x)) {}
     v->tbi = vcfidx::parse_tbi(x.data(), x.size(), ip);
 }
 
 // The head of the file: BGZF blocks from offset 0 until the #CHROM line and the first record are complete. The errors of
 // lcty_vcf_open, with its texts.
 void load_head(lcty_vcf_indexed* v) {
-    const char* path = v->path.c_str();
-    BgzfSerial in(v->fd, v->fsize, path);
+    const char* path = v->file.path.c_str();
+    BgzfSerial in(v->file.fd, v->file.fsize, path);
     std::vector<uint8_t> t;
     uint64_t b = 0, searched = 0;                    // the first line not looked at yet; no '\n' in [b, searched)
     bool have_header = false, have_record = false, eof = false;
     while (!have_record && !eof) {
-        if (in.load()) { t.insert(t.end(), in.data.begin() + static_cast<ptrdiff_t>(in.at), in.data.end()); in.at = in.data.size(); }
-        else eof = true;
+        eof = !in.append_block(t);
         while (!have_record) {
             uint64_t e = std::max(b, searched);
             while (e < t.size() && t[e] != '\n') e++;
@@ -402,24 +381,18 @@ int32_t lcty_vcf_indexed_open(const char* path, const char* index_path, lcty_vcf
         const std::string p(path);
         if (has_suffix(p, ".bcf")) fail(LCTY_ERR_UNSUPPORTED, "%s: BCF is not read here, convert it to a text VCF", path);
         std::unique_ptr<lcty_vcf_indexed> v(new lcty_vcf_indexed());
-        v->path = p;
         // ---- the index
         if (index_path) v->index_path = index_path;
-        else if (is_file(p + ".tbi")) v->index_path = p + ".tbi";
-        else if (is_file(p + ".csi")) fail(LCTY_ERR_UNSUPPORTED, "%s.csi is a CSI index (only tabix indices are read)", path);
+        else if (is_regular_file(p + ".tbi")) v->index_path = p + ".tbi";
+        else if (is_regular_file(p + ".csi")) fail(LCTY_ERR_UNSUPPORTED, "%s.csi is a CSI index (only tabix indices are read)", path);
         else fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s.tbi)", path, path);
         if (has_suffix(v->index_path, ".csi")) fail(LCTY_ERR_UNSUPPORTED, "%s is a CSI index (only tabix indices are read)", v->index_path.c_str());
-        if (!is_file(v->index_path)) fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s)", path, v->index_path.c_str());
+        if (!is_regular_file(v->index_path)) fail(LCTY_ERR_INVALID_INPUT, "no index for %s (%s)", path, v->index_path.c_str());
         // ---- the file
-        v->fd = open(path, O_RDONLY | O_CLOEXEC);
-        if (v->fd < 0) fail(LCTY_ERR_INVALID_INPUT, "cannot open %s", path);
-        struct stat st;
-        if (fstat(v->fd, &st) != 0) fail(LCTY_ERR_RUNTIME, "cannot stat %s", path);
-        v->fsize = static_cast<uint64_t>(st.st_size);
-        if (v->fsize >= (1ull << 48)) fail(LCTY_ERR_UNSUPPORTED, "%s: a file of 2^48 bytes or more", path);
+        v->file.open(path);
         uint8_t hd[64];
-        const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), v->fsize));
-        if (n) pread_all(v->fd, hd, n, 0, path);
+        const size_t n = static_cast<size_t>(std::min<uint64_t>(sizeof(hd), v->file.fsize));
+        if (n) pread_all(v->file.fd, hd, n, 0, path);
         if (!bgzf_block_size(hd, n)) fail(LCTY_ERR_INVALID_INPUT, "%s: an indexed file must be BGZF (bgzip); this one is plain text or plain gzip", path);
         load_tbi(v.get());
         load_head(v.get());
@@ -440,10 +413,7 @@ int32_t lcty_vcf_indexed_plan(lcty_vcf_indexed* vcf, const char* contig, uint32_
                               uint64_t* chunk_beg, uint64_t* chunk_end, uint64_t* blocks_total) {
     return guarded([&] {
         if (!vcf || !contig || !n_chunks || (chunk_cap && (!chunk_beg || !chunk_end))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const std::vector<Chunk> cs = vcfidx::plan(vcf->tbi, contig, start, end);
-        *n_chunks = cs.size();
-        for (size_t i = 0; i < cs.size() && i < chunk_cap; i++) { chunk_beg[i] = cs[i].beg; chunk_end[i] = cs[i].end; }
-        if (blocks_total) *blocks_total = count_chunk_blocks(vcf->fd, vcf->fsize, vcf->path.c_str(), cs);
+        report_plan(vcf->file, vcfidx::plan(vcf->tbi, contig, start, end), chunk_cap, n_chunks, chunk_beg, chunk_end, blocks_total);
     });
 }
 
@@ -458,12 +428,10 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
         }
         if (!vcf || !contig || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         const double t_start = now_ms();
-        const char* path = vcf->path.c_str();
+        const char* path = vcf->file.path.c_str();
         const uint32_t S = vcf->view.n_samples, Hn = vcf->view.n_haps;
-        const uint64_t cap = static_cast<uint64_t>(ctx->knob("vcf_max_slice_bytes", 1ll << 33));
-        if (ctx->knob("sample_bam_inflate", 0) > 1) fail(LCTY_ERR_INVALID_INPUT, "sample_bam_inflate = %lld (0: host, 1: device)", static_cast<long long>(ctx->knob("sample_bam_inflate", 0)));
         lcty_vcf_fetch_stats T{};
-        T.file_bytes = vcf->fsize;
+        T.file_bytes = vcf->file.fsize;
         lcty_vcf_records o{}; Handoff h;
         o.n_haps = Hn; o.n_samples = S;
         auto finish = [&]() {
@@ -480,33 +448,23 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
         };
 
         // ---- the chunks of the window, their bytes, their blocks
-        const std::vector<Chunk> cs = vcfidx::plan(vcf->tbi, contig, start, end);
-        T.n_chunks = cs.size();
-        double t0 = now_ms();
-        std::vector<uint8_t> comp;
-        std::vector<BgzfBlock> blocks;
-        std::vector<ChunkSpan> spans;
-        uint64_t total = 0;
-        read_chunk_blocks(vcf->fd, vcf->fsize, path, cs, comp, blocks, spans, total, T.bytes_read);
-        T.ms_read = now_ms() - t0;
-        T.blocks_inflated = blocks.size(); T.bytes_inflated = total;
-        if (total > cap)
-            fail(LCTY_ERR_UNSUPPORTED, "%s: the fetched slice has %llu bytes, more than %llu (knob vcf_max_slice_bytes)", path,
-                 static_cast<unsigned long long>(total), static_cast<unsigned long long>(cap));
+        Slice F;
+        SliceStats fs{};
+        F.read(ctx, vcf->file, vcfidx::plan(vcf->tbi, contig, start, end), "vcf_max_slice_bytes", fs);
+        fs.put(T);
+        const uint64_t total = F.total;
         std::vector<uint64_t> rbeg, rend;
-        for (const ChunkSpan& sp : spans) if (sp.chain_beg < sp.chain_end) { rbeg.push_back(sp.chain_beg); rend.push_back(sp.chain_end); }
-        if (rbeg.empty()) { empty(); return; }
+        for (const ChunkSpan& sp : F.spans) if (sp.chain_beg < sp.chain_end) { rbeg.push_back(sp.chain_beg); rend.push_back(sp.chain_end); }
+        if (rbeg.empty()) { empty(); return; }                                 // nothing of the window's own: nothing is inflated
 
-        FetchedSlice F;
-        DevBuf<uint8_t> d_raw;
-        const bool on_device = inflate_slice(ctx, comp, blocks, total, F, d_raw, path, T.ms_inflate);
+        T.ms_inflate = F.inflate(ctx, path);
         hipStream_t s = ctx->stream;
 
         // ---- upload
-        t0 = now_ms();
+        double t0 = now_ms();
         const uint32_t n_ranges = static_cast<uint32_t>(rbeg.size()), contig_len = static_cast<uint32_t>(strlen(contig));
-        DevBuf<uint64_t> d_rng; DevBuf<uint8_t> d_contig, d_used; DevBuf<uint32_t> d_ploidy, d_hap_off; DevBuf<unsigned long long> d_err;
-        if (!on_device) { d_raw.alloc(total + SLICE_PAD); d_raw.upload(F.slice, total + SLICE_PAD, s); }
+        DevBuf<uint64_t> d_rng; DevBuf<uint8_t> d_contig, d_used; DevBuf<uint32_t> d_ploidy, d_hap_off; ErrWord err;
+        const uint8_t* d_raw = F.device(s);
         std::vector<uint64_t> rng(rbeg);
         rng.insert(rng.end(), rend.begin(), rend.end());
         d_rng.alloc(rng.size()); d_rng.upload(rng.data(), rng.size(), s);
@@ -516,8 +474,7 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
             d_hap_off.alloc(S + 1); d_hap_off.upload(vcf->hap_off.data(), S + 1, s);
             if (sample_used) { d_used.alloc(S); d_used.upload(sample_used, S, s); }
         }
-        d_err.alloc(1);
-        LCTY_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), s));
+        unsigned long long* d_err = err.reset(s);
         LCTY_HIP(hipStreamSynchronize(s));
         T.ms_upload = now_ms() - t0;
 
@@ -527,7 +484,7 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
         const uint64_t n_wg = (total + LINE_BYTES * LINE_THREADS - 1) / (LINE_BYTES * LINE_THREADS);
         DevBuf<uint32_t> d_cnt, d_cnt_off;
         d_cnt.alloc(n_wg);
-        hipLaunchKernelGGL(line_kernel<false>, dim3(static_cast<uint32_t>(n_wg)), dim3(LINE_THREADS), 0, s, d_raw.p, total, R, d_cnt.p, nullptr, nullptr);
+        hipLaunchKernelGGL(line_kernel<false>, dim3(static_cast<uint32_t>(n_wg)), dim3(LINE_THREADS), 0, s, d_raw, total, R, d_cnt.p, nullptr, nullptr);
         LCTY_HIP(hipGetLastError());
         ScanTotal scan;
         const uint32_t n_lines = scan.run(d_cnt, d_cnt_off, n_wg, ctx);           // 2^31 - 16 lines or more: LCTY_ERR_UNSUPPORTED
@@ -535,7 +492,7 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
         if (n_lines == 0) { T.ms_lines = now_ms() - t0; empty(); return; }
         DevBuf<uint64_t> d_line;
         d_line.alloc(n_lines);
-        hipLaunchKernelGGL(line_kernel<true>, dim3(static_cast<uint32_t>(n_wg)), dim3(LINE_THREADS), 0, s, d_raw.p, total, R, nullptr, d_cnt_off.p, d_line.p);
+        hipLaunchKernelGGL(line_kernel<true>, dim3(static_cast<uint32_t>(n_wg)), dim3(LINE_THREADS), 0, s, d_raw, total, R, nullptr, d_cnt_off.p, d_line.p);
         LCTY_HIP(hipGetLastError());
         LCTY_HIP(hipStreamSynchronize(s));
         T.ms_lines = now_ms() - t0;
@@ -546,8 +503,8 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
         DevBuf<LineInfo> d_info;
         d_kept.alloc(n_lines); d_info.alloc(n_lines);
         HeadView HV{};
-        HV.raw = d_raw.p; HV.R = R; HV.line_start = d_line.p; HV.n_lines = n_lines; HV.contig = d_contig.p; HV.contig_len = contig_len;
-        HV.start = start; HV.end = end; HV.S = S; HV.kept = d_kept.p; HV.info = d_info.p; HV.err = d_err.p;
+        HV.raw = d_raw; HV.R = R; HV.line_start = d_line.p; HV.n_lines = n_lines; HV.contig = d_contig.p; HV.contig_len = contig_len;
+        HV.start = start; HV.end = end; HV.S = S; HV.kept = d_kept.p; HV.info = d_info.p; HV.err = d_err;
         hipLaunchKernelGGL(head_kernel, dim3(n_lines), dim3(WAVE), 0, s, HV);
         LCTY_HIP(hipGetLastError());
         const uint32_t n_recs = scan.run(d_kept, d_kept_off, n_lines, ctx);
@@ -574,7 +531,7 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
             d_byte_off.download(&pool_len, 1, s, n_recs);
             LCTY_HIP(hipStreamSynchronize(s));
             d_allele_off.alloc(n_alleles + 1); d_pool.alloc(std::max<uint64_t>(pool_len, 1));
-            hipLaunchKernelGGL(allele_kernel, dim3(n_recs), dim3(WAVE), 0, s, d_raw.p, n_recs, d_rec.p, d_rec_allele.p, d_byte_off.p, d_allele_off.p, d_pool.p);
+            hipLaunchKernelGGL(allele_kernel, dim3(n_recs), dim3(WAVE), 0, s, d_raw, n_recs, d_rec.p, d_rec_allele.p, d_byte_off.p, d_allele_off.p, d_pool.p);
             LCTY_HIP(hipGetLastError());
             LCTY_HIP(hipStreamSynchronize(s));
         }
@@ -587,20 +544,18 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
         if (n_recs && S) {
             d_gt.alloc(std::max<size_t>(n_gt, 1)); d_phased.alloc(n_ph);
             GtView GV{};
-            GV.raw = d_raw.p; GV.rec = d_rec.p; GV.rec_line = d_rec_line.p; GV.S = S; GV.n_haps = Hn;
+            GV.raw = d_raw; GV.rec = d_rec.p; GV.rec_line = d_rec_line.p; GV.S = S; GV.n_haps = Hn;
             GV.ploidy = d_ploidy.p; GV.hap_off = d_hap_off.p; GV.sample_used = sample_used ? d_used.p : nullptr;
-            GV.gt = d_gt.p; GV.phased = d_phased.p; GV.err = d_err.p;
+            GV.gt = d_gt.p; GV.phased = d_phased.p; GV.err = d_err;
             hipLaunchKernelGGL(gt_kernel, dim3(n_recs), dim3(WAVE), 0, s, GV);
             LCTY_HIP(hipGetLastError());
         }
-        unsigned long long e = 0;
-        d_err.download(&e, 1, s);
-        LCTY_HIP(hipStreamSynchronize(s));
+        uint64_t l; uint32_t cls;
+        const bool refused = err.take(s, l, cls);
         T.ms_gt = now_ms() - t0;
 
         // ---- the first offending line in file order, through the line functions of the host reader
-        if (e != ~0ull) {
-            const uint64_t l = e >> 8;
+        if (refused) {
             uint64_t b = 0;
             d_line.download(&b, 1, s, l);
             LCTY_HIP(hipStreamSynchronize(s));
@@ -609,7 +564,7 @@ int32_t lcty_vcf_indexed_fetch(lcty_ctx* ctx, lcty_vcf_indexed* vcf, const char*
             uint64_t le = b;
             while (le < range_end && F.slice[le] != '\n') le++;
             if (le > b && F.slice[le - 1] == '\r') le--;
-            if ((e & 0xFF) == E_LONG) fail(LCTY_ERR_UNSUPPORTED, "%s: a line of 2^32 bytes or more", path);
+            if (cls == E_LONG) fail(LCTY_ERR_UNSUPPORTED, "%s: a line of 2^32 bytes or more", path);
             const vcfidx::LineHead lh = vcfidx::parse_line_head(F.slice, b, le, path);
             vcfidx::RecordArrays A; std::vector<int32_t> al;
             if (lh.chrom == contig) vcfidx::parse_record_line(F.slice, b, le, contig, lh.pos, lh.ref_len, S, vcf->ploidy.data(), vcf->samples, sample_used, A, al);
