@@ -274,6 +274,9 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       naming this knob, before anything is allocated); its inflate follows "sample_bam_inflate".
  *       "vcf_max_slice_bytes"   inflated bytes one lcty_vcf_indexed_fetch may take (default 2^33; a larger window is LCTY_ERR_UNSUPPORTED
  *       naming this knob, before the slice is allocated or uploaded); its inflate follows "sample_bam_inflate".
+ *       "fastx_window_bytes"   bytes of text lcty_fastx_device_open's reader takes per file and window (default 2^28, at least 64: less is
+ *       LCTY_ERR_INVALID_INPUT; the records do not depend on it); a window without a complete record is doubled, up to
+ *       "fastx_window_limit"   (default and most 2^31 - 64: offsets inside a window are 32-bit; a record beyond it is LCTY_ERR_UNSUPPORTED).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -591,6 +594,43 @@ int32_t lcty_fastx_writers_open(const char* const* paths, uint32_t n, lcty_fastx
 int32_t lcty_fastx_write_recruited(lcty_fastx* f, lcty_fastx_writers* writers, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci,
                                    uint64_t* n_written);
 int32_t lcty_fastx_writers_close(lcty_fastx_writers* writers);
+
+/* ---- the same input parsed on the device ---------------------------------------------------------------------------
+ * The route beside lcty_fastx_open for `locityper genotype -i reads_1.fq.gz reads_2.fq.gz`: the host reads windows of text (knob
+ * "fastx_window_bytes" per file) into a page-locked slice — plain files by pread, BGZF files block by block through the inflate of
+ * lcty_sample_bam_fetch (knob "sample_bam_inflate" 1: on the device), any other gzip through zlib —, kernels find lines and records,
+ * lay the mates out and pack them, and recruitment reads them where they lie. Records, layout, packed words, status and message
+ * are those of lcty_fastx_next for the same files, with one exception: a file that mixes FASTA and FASTQ records (fastx.rs:410-414
+ * decides per record) is LCTY_ERR_UNSUPPORTED naming the record. The first offending record in input order decides.
+ * lcty_fastx_device_open: Reader::from_path (fastx.rs:298-317), PairedEndInterleaved (423-453), PairedEndReaders (461-498) as
+ *   lcty_fastx_open; nothing is read yet. .lz4 / .br: LCTY_ERR_UNSUPPORTED. lcty_fastx_device_is_paired: as lcty_fastx_is_paired.
+ * lcty_fastx_device_next: read_next (fastx.rs:396-415, 437-453, 480-498) for up to max_records records (pairs, when paired) of the
+ *   current window, resident on the device; *n = 0 at the end of the input; records of the window beyond max_records are carried
+ *   to the next call. Records in front of a refused one are handed out; the call that would begin with it fails. A record
+ *   that no window of "fastx_window_limit" bytes holds is LCTY_ERR_UNSUPPORTED naming knob "fastx_window_bytes". stats (may be
+ *   NULL): sums since the handle was opened.
+ * lcty_fastx_device_view: the chunk as lcty_fastx_next gives it, downloaded on first use; the arrays belong to the handle until
+ *   the next call of lcty_fastx_device_next.
+ * lcty_fastx_device_recruit: lcty_recruit (recruit.rs:1000-1030) on the chunk, from the device-resident arrays. The handle's
+ *   context must be the targets', else LCTY_ERR_INVALID_INPUT.
+ * lcty_fastx_device_write_recruited: write_fastq / write_fasta (fastx.rs:46-75, 262-272), the bytes lcty_fastx_write_recruited
+ *   writes for the chunk: the text comes from the page-locked slice and the downloaded rows, a FASTA sequence on one line. */
+typedef struct lcty_fastx_device lcty_fastx_device;
+typedef struct lcty_fastx_device_stats {
+    uint64_t bytes_read, bytes_inflated;          /* bytes read from the files; text that came out of a compressed container */
+    uint64_t windows, windows_enlarged, records;  /* windows parsed (both files); of them: doubled for want of a complete record; records handed out */
+    double   ms_read, ms_inflate;                 /* host: pread; zlib, or with "sample_bam_inflate" 1 upload + inflate kernel + copy back */
+    double   ms_upload, ms_lines, ms_records, ms_pack;   /* device, wall clock around each stage with its synchronisation */
+    double   ms_total;                            /* inside lcty_fastx_device_next */
+} lcty_fastx_device_stats;
+int32_t lcty_fastx_device_open(lcty_ctx* ctx, const char* path1, const char* path2, int32_t interleaved, lcty_fastx_device** out);
+void    lcty_fastx_device_close(lcty_fastx_device* f);
+int32_t lcty_fastx_device_is_paired(const lcty_fastx_device* f, int32_t* paired);
+int32_t lcty_fastx_device_next(lcty_fastx_device* f, uint64_t max_records, uint64_t* n, lcty_fastx_device_stats* stats);
+int32_t lcty_fastx_device_view(lcty_fastx_device* f, lcty_reads_host* view);
+int32_t lcty_fastx_device_recruit(lcty_targets* targets, lcty_fastx_device* f, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci);
+int32_t lcty_fastx_device_write_recruited(lcty_fastx_device* f, lcty_fastx_writers* writers, uint32_t max_out, const uint32_t* out_cnt,
+                                          const uint32_t* out_loci, uint64_t* n_written);
 
 /* ---- a sample's reads from a coordinate-sorted, indexed BAM file: `locityper genotype -a sample.bam` ---------------
  * recruit_to_targets (command/genotype.rs:872-907) -> create_fetch_targets / postprocess_targets (776-854) -> IndexedBamReader +

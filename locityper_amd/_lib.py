@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, VcfFetchStats, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats, BgzfDeflateStats, ScoreRoutes
+from .cdefs import AlignParams, AlignOut, AlignBackboneOut, AlignStats, AlignTrParams, AlignTrOut, AlignTrStats, BasisParams, BasisStats, Bg, BgParams, DbParams, DbCheck, DbStats, DbFiles, BgReadsView, BgDiag, Params, ReadsHost, PairAln, Solver, Stage, Call, GtAlnsView, DepthTables, PafDivStats, PruneParams, PruneStats, PruneOut, PruneFiles, VcfView, VcfRecords, VcfFetchStats, PanvcfOut, ExpandOut, LocusVcfIn, LocusVcfOut, PafvcfOut, GenomeCountStats, SampleBamStats, BgzfStats, BgzfDeflateStats, ScoreRoutes, FastxDeviceStats
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblocityper_hip.so")
@@ -164,6 +164,13 @@ SIGNATURES = {
     "lcty_fastx_writers_open": (I32, [P(C.c_char_p), U32, P(VP)]),
     "lcty_fastx_write_recruited": (I32, [VP, VP, U32, VP, VP, P(U64)]),
     "lcty_fastx_writers_close": (I32, [VP]),
+    "lcty_fastx_device_open": (I32, [VP, C.c_char_p, C.c_char_p, I32, P(VP)]),
+    "lcty_fastx_device_close": (None, [VP]),
+    "lcty_fastx_device_is_paired": (I32, [VP, P(I32)]),
+    "lcty_fastx_device_next": (I32, [VP, U64, P(U64), P(FastxDeviceStats)]),
+    "lcty_fastx_device_view": (I32, [VP, P(ReadsHost)]),
+    "lcty_fastx_device_recruit": (I32, [VP, VP, U32, VP, VP]),
+    "lcty_fastx_device_write_recruited": (I32, [VP, VP, U32, VP, VP, P(U64)]),
     "lcty_sample_bam_open": (I32, [C.c_char_p, C.c_char_p, P(VP)]),
     "lcty_sample_bam_close": (None, [VP]),
     "lcty_sample_bam_contigs": (I32, [VP, P(U32), P(VP), P(VP), P(VP)]),

@@ -709,3 +709,11 @@ class SampleBamStats(C.Structure):     # lcty_sample_bam_stats
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class FastxDeviceStats(C.Structure):   # lcty_fastx_device_stats
+    _fields_ = [(n, C.c_uint64) for n in ("bytes_read", "bytes_inflated", "windows", "windows_enlarged", "records")] + \
+               [(n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_upload", "ms_lines", "ms_records", "ms_pack", "ms_total")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}

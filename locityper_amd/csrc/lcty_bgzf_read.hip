@@ -112,8 +112,12 @@ void Slice::read(lcty_ctx* ctx, const BgzfFile& f, const std::vector<Chunk>& cs,
 
 void Slice::alloc(lcty_ctx* ctx, uint64_t n) {
     ctx->activate();
-    total = n;
-    LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&slice), total + SLICE_PAD, hipHostMallocDefault));
+    if (!slice || n > cap) {                                                // a slice that is used again keeps a buffer that is large enough
+        if (slice) { (void)hipHostFree(slice); slice = nullptr; }
+        LCTY_HIP(hipHostMalloc(reinterpret_cast<void**>(&slice), n + SLICE_PAD, hipHostMallocDefault));
+        cap = n;
+    }
+    total = n; on_device = false;
     memset(slice + total, 0, SLICE_PAD);
 }
 
@@ -127,7 +131,7 @@ double Slice::inflate(lcty_ctx* ctx, const char* path) {
     for (const BgzfBlock& b : blocks) if (b.isize && (!b.head || b.head + 8u > b.csize)) on_device = false;
     if (on_device) {
         DevBuf<uint8_t> d_comp;
-        d_comp.alloc(comp.size()); d_raw.alloc(total + SLICE_PAD);
+        d_comp.alloc(comp.size()); d_raw.ensure(total + SLICE_PAD);
         d_comp.upload(comp.data(), comp.size(), s);
         LCTY_HIP(hipMemsetAsync(d_raw.p + total, 0, SLICE_PAD, s));
         bgzf_inflate_device(ctx, d_comp.p, comp.size(), blocks, d_raw.p, total, s, path);
@@ -140,8 +144,14 @@ double Slice::inflate(lcty_ctx* ctx, const char* path) {
     return ms;
 }
 
+void Slice::put_front(const uint8_t* p, uint64_t n, hipStream_t s) {
+    if (n > total) fail(LCTY_ERR_RUNTIME, "slice overflow (%llu > %llu)", static_cast<unsigned long long>(n), static_cast<unsigned long long>(total));
+    memcpy(slice, p, n);
+    if (on_device && n) LCTY_HIP(hipMemcpyAsync(d_raw.p, slice, n, hipMemcpyHostToDevice, s));
+}
+
 const uint8_t* Slice::device(hipStream_t s) {
-    if (!on_device) { d_raw.alloc(total + SLICE_PAD); d_raw.upload(slice, total + SLICE_PAD, s); on_device = true; }
+    if (!on_device) { d_raw.ensure(total + SLICE_PAD); d_raw.upload(slice, total + SLICE_PAD, s); on_device = true; }
     return d_raw.p;
 }
 

@@ -81,16 +81,22 @@ struct Slice {
     // inflated into its place, by zlib on the host pool or, with knob "sample_bam_inflate" 1 and plain gzip headers, on the device;
     // then the device has the slice already. comp is released. Activates the context; returns the time of the inflate.
     double inflate(lcty_ctx* ctx, const char* path);
-    // the page-locked buffer alone, its pad zeroed, for `n` bytes the caller puts there. Activates the context.
+    // the page-locked buffer alone, its pad zeroed, for `n` bytes the caller puts there. Activates the context. A slice may be used
+    // again (a reader of windows, lcty_fastx_device.hip): alloc() and inflate() then keep the buffers of the last use where they are
+    // large enough, on the host and on the device.
     void alloc(lcty_ctx* ctx, uint64_t n);
     // the slice with its pad on the device, as dwords too: uploaded now unless the inflate ran there
     const uint8_t* device(hipStream_t s);
     void release_device() { d_raw.release(); }
+    // n bytes written over the front of the slice after alloc() or inflate() (a reader of windows carries the tail of the last one
+    // here, lcty_fastx_window.hpp), on the device as well when the inflate left the slice there. Asynchronous on s.
+    void put_front(const uint8_t* p, uint64_t n, hipStream_t s);
 
     std::vector<uint8_t> comp;                 // between read() and inflate(): the bytes read ...
     std::vector<BgzfBlock> blocks;             // ... and their blocks
 private:
     DevBuf<uint8_t> d_raw;
+    uint64_t cap = 0;                          // bytes the page-locked buffer holds in front of its pad
     bool on_device = false;
 };
 

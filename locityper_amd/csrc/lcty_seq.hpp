@@ -56,9 +56,15 @@ __host__ __device__ inline bool canonical_kmer_ascii(const uint8_t* s, uint64_t 
 
 // base `c` (ASCII) at position `at` of a packed read: two bits in bases2 (LSB first, 16 bases a word; 0 where the base is not ACGT),
 // one bit in nmask (32 bases a word) where it is not. Both arrays are zero before the first base is packed.
-inline void pack_base(uint32_t* bases2, uint32_t* nmask, uint64_t at, uint8_t c) {
+// base_bits: the two values of one base, for a packer that builds whole words in registers (pack_kernel of lcty_fastx_device.hip).
+__host__ __device__ inline void base_bits(uint8_t c, uint32_t& two, uint32_t& not_acgt) {
     const uint32_t e = base_enc(c);
-    if (e < 4u) bases2[at >> 4] |= e << (2 * (at & 15));
+    two = e < 4u ? e : 0u; not_acgt = e < 4u ? 0u : 1u;
+}
+inline void pack_base(uint32_t* bases2, uint32_t* nmask, uint64_t at, uint8_t c) {
+    uint32_t two, not_acgt;
+    base_bits(c, two, not_acgt);
+    if (!not_acgt) bases2[at >> 4] |= two << (2 * (at & 15));
     else nmask[at >> 5] |= 1u << (at & 31);
 }
 

@@ -299,6 +299,69 @@ class Fastx:
             pass
 
 
+class FastxDevice:
+    """lcty_fastx_device_*: the same input as Fastx, parsed and packed on the device. Windows of text follow the context's
+    knob "fastx_window_bytes"; stats holds the sums of lcty_fastx_device_stats after every call of next()."""
+
+    def __init__(self, ctx, path1, path2=None, interleaved=False):
+        self._h = VP()
+        self._ctx = ctx
+        self.stats = cdefs.FastxDeviceStats().as_dict()
+        self.n = 0
+        check(lib().lcty_fastx_device_open(ctx._h, str(path1).encode(), None if path2 is None else str(path2).encode(), int(interleaved), C.byref(self._h)))
+        p = C.c_int32(0)
+        check(lib().lcty_fastx_device_is_paired(self._h, C.byref(p)))
+        self.paired = bool(p.value)
+
+    def next(self, max_records=2 ** 62):
+        """The next chunk stays on the device: -> its number of records (pairs, when paired), 0 at the end of the input."""
+        n, st = U64(0), cdefs.FastxDeviceStats()
+        self.n = 0
+        try:
+            check(lib().lcty_fastx_device_next(self._h, max_records, C.byref(n), C.byref(st)))
+        finally:
+            self.stats = st.as_dict()
+        self.n = int(n.value)
+        return self.n
+
+    def view(self):
+        """The current chunk as a cdefs.ReadsChunk of sequence fields, as Fastx.next gives it: copies."""
+        hs = cdefs.ReadsHost()
+        check(lib().lcty_fastx_device_view(self._h, C.byref(hs)))
+        n = int(hs.n_pairs)
+        def arr(ptr, count, dt):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(dt)), shape=(count,)).copy()
+        mate_off = arr(hs.mate_off, 2 * n + 1, C.c_uint64)
+        nb = int(mate_off[-1])
+        z = np.zeros(n + 1, dtype=np.uint64)
+        return cdefs.ReadsChunk(arr(hs.mate_len, 2 * n, C.c_uint32) if n else np.zeros(0, dtype=np.uint32), mate_off, arr(hs.bases2, nb // 16 + 1, C.c_uint32),
+                                arr(hs.nmask, nb // 32 + 1, C.c_uint32), z, np.zeros(0, dtype=cdefs.ALN_REC_DTYPE), z, np.zeros(0, dtype=np.uint32))
+
+    def recruit(self, targets, max_out=8):
+        n = self.n
+        cnt = np.zeros(max(n, 1), dtype=np.uint32); loci = np.zeros(max(n, 1) * max_out, dtype=np.uint32)
+        check(lib().lcty_fastx_device_recruit(targets._h, self._h, max_out, cnt.ctypes.data, loci.ctypes.data))
+        return cnt[:n], loci.reshape(-1, max_out)[:n]
+
+    def write_recruited(self, writers, cnt, loci):
+        cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+        loci = np.ascontiguousarray(loci, dtype=np.uint32)
+        n = U64(0)
+        check(lib().lcty_fastx_device_write_recruited(self._h, writers._h, loci.shape[1], cnt.ctypes.data, loci.ctypes.data, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            lib().lcty_fastx_device_close(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def fetch_regions(tid, start, end, contig_len, padding, alt_contig_len=10_000_000, merge_distance=1000):
     """lcty_recruit_fetch_regions (postprocess_targets): padded, short contigs added, sorted, merged -> (tid, start, end) arrays."""
     tid, start, end = (np.ascontiguousarray(a, dtype=np.uint32) for a in (tid, start, end))
