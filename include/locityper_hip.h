@@ -277,6 +277,9 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       "fastx_window_bytes"   bytes of text lcty_fastx_device_open's reader takes per file and window (default 2^28, at least 64: less is
  *       LCTY_ERR_INVALID_INPUT; the records do not depend on it); a window without a complete record is doubled, up to
  *       "fastx_window_limit"   (default and most 2^31 - 64: offsets inside a window are 32-bit; a record beyond it is LCTY_ERR_UNSUPPORTED).
+ *       "recruit_blocks"   the most workgroups either launch of lcty_recruit starts (default: 16 per CU for read pairs and single reads
+ *       of up to 256 bases, 8 per CU for longer single reads; 0 counts as 1): with few workgroups each one takes many chunks of 64 pairs,
+ *       or many long reads, in turn; the loci of a read do not depend on it.
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);

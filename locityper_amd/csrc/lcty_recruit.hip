@@ -566,7 +566,10 @@ void recruit_device_view(lcty_targets* t, uint64_t n, const uint32_t* h_mate_len
     if (max_len > 256) fail(LCTY_ERR_UNSUPPORTED, "recruitment: a mate of %u bases in a read pair (the device kernel takes mates of up to 256 bases)", max_len);
     if (n > 0xFFFFFFFFull) fail(LCTY_ERR_UNSUPPORTED, "recruitment: more than 2^32 reads in one call");
     V.scratch_cap = max_len;                                                 // a mate has fewer minimizers than bases
-    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((n + 63) / 64, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16));
+    // lcty_ctx_set_knob "recruit_blocks": the most workgroups of either launch, so that a test with few reads reaches the later turns
+    // of the kernels' loops (what a workgroup carries from one chunk of pairs, or one long read, to the next)
+    const uint64_t blocks_cap = static_cast<uint64_t>(std::max<int64_t>(1, ctx->knob("recruit_blocks", INT64_MAX)));
+    const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>({(n + 63) / 64, static_cast<uint64_t>(ctx->props.multiProcessorCount) * 16, blocks_cap}));
     DevBuf<uint64_t> d_scratch, d_long_h; DevBuf<uint8_t> d_long_f, d_scratch_f; DevBuf<uint32_t> d_long_list;
     d_scratch.alloc(static_cast<size_t>(blocks) * V.scratch_cap * 64); d_scratch_f.alloc(static_cast<size_t>(blocks) * V.scratch_cap * 64);
     V.scratch = d_scratch.p; V.scratch_f = d_scratch_f.p;
@@ -579,7 +582,7 @@ void recruit_device_view(lcty_targets* t, uint64_t n, const uint32_t* h_mate_len
     });
     if (!long_list.empty()) {
         V.n_long = static_cast<uint32_t>(long_list.size()); V.long_cap = max_long + 64;
-        const uint32_t lblocks = static_cast<uint32_t>(std::min<uint64_t>(long_list.size(), static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8));
+        const uint32_t lblocks = static_cast<uint32_t>(std::min<uint64_t>({long_list.size(), static_cast<uint64_t>(ctx->props.multiProcessorCount) * 8, blocks_cap}));
         d_long_list.alloc(long_list.size()); d_long_list.upload(long_list.data(), long_list.size(), s);
         d_long_h.alloc(static_cast<size_t>(lblocks) * 2 * V.long_cap); d_long_f.alloc(static_cast<size_t>(lblocks) * 2 * V.long_cap);
         V.long_list = d_long_list.p; V.long_h = d_long_h.p; V.long_f = d_long_f.p;
