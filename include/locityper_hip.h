@@ -280,6 +280,11 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       "recruit_blocks"   the most workgroups either launch of lcty_recruit starts (default: 16 per CU for read pairs and single reads
  *       of up to 256 bases, 8 per CU for longer single reads; 0 counts as 1): with few workgroups each one takes many chunks of 64 pairs,
  *       or many long reads, in turn; the loci of a read do not depend on it.
+ *       "recruited_init_units"   32-base units the device arrays of a locus of an lcty_recruited set hold when they are first made
+ *       (default 4 096: 128 kb of bases, 48 KB; room for an eighth as many pairs beside them; 0 counts as 1); they double until an add fits,
+ *       device to device; the contents do not depend on it.   "recruited_max_bytes"   bytes the contents of an lcty_recruited set may
+ *       reach over all loci, 12 per unit and 32 per pair (default 2^36; an add beyond it is LCTY_ERR_UNSUPPORTED naming this knob,
+ *       before anything is copied; the capacity behind the contents is at most twice as large).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -811,6 +816,53 @@ int32_t lcty_map_reads(lcty_locus* locus, const lcty_reads_host* chunk, const lc
  * mapping (arenas and kernel scratch: tens of GB for long reads on many alleles) stay with the context from chunk to chunk; the solver
  * stages release them before they size their workspace, and so does lcty_ctx_trim. One mapping call at a time per context. */
 int32_t lcty_reads_map_append(lcty_reads* reads, const lcty_reads_host* chunk, const lcty_map_params* params);
+
+/* ---- the recruited reads of every locus, resident on the device, and the mapper fed from them ----------------------
+ * The reference writes the reads of a locus to `reads.fq`, runs an external mapper on that file and reads its `aln.bam`
+ * (command/genotype.rs:872-907, 962-1094). Here the recruited reads stay on the device in the layout the mapper reads, so that
+ * recruitment and mapping meet without a file and without the host: SURVEY.md 8(f) rank 2.
+ * lcty_recruited_create: an empty set over the loci of finalized targets (not finalized: LCTY_ERR_INVALID_INPUT); the targets outlive
+ *   the set. keep_names != 0: the name of every added pair is kept per locus, on the host. Qualities are not kept.
+ * lcty_recruited_add / _add_fastx / _add_sample: pair i of the chunk goes to exactly the loci out_loci[i * max_out .. + out_cnt[i]], the
+ *   host arrays lcty_recruit / lcty_fastx_device_recruit / lcty_sample_reads_recruit filled, with the meaning they have in
+ *   *_write_recruited. _add uploads a host chunk (only its sequence fields are read; `paired` is accepted for symmetry with lcty_recruit:
+ *   an absent mate has length 0 either way), _add_fastx takes the chunk of the last lcty_fastx_device_next and _add_sample the fetched
+ *   reads from where they lie on the device. Within a locus the pairs stand in input order — add after add, inside an add by i —, the
+ *   order of the records of the reads.fq the writers produce for the same calls. Every pair carries a source ordinal: its index i plus
+ *   the pairs of every earlier add of the set, recruited or not. The contents depend on the chunks and the answers alone (no atomics, no
+ *   dependence on the grid): two runs give the same bytes. The set, the source handle and the targets share one context, else
+ *   LCTY_ERR_INVALID_INPUT, as are out_cnt[i] > max_out and a locus beyond the targets'. 2^32 or more (locus, pair) entries or 2^31 or
+ *   more 32-base units in one add: LCTY_ERR_UNSUPPORTED. The contents of the whole set after the add — 12 bytes per 32-base unit and
+ *   32 bytes per pair, over all loci — above knob "recruited_max_bytes": LCTY_ERR_UNSUPPORTED naming the knob. All of this is decided
+ *   before anything is copied: a failed add leaves the set as it was. A locus's arrays grow geometrically from knob
+ *   "recruited_init_units", device to device.
+ * lcty_recruited_sizes: the pairs of a locus and the bases its units span (32 per unit). locus_ix beyond the targets' loci is
+ *   LCTY_ERR_INVALID_INPUT here and in every call below.
+ * lcty_recruited_view: the reads of a locus as the sequence fields of one chunk, bit for bit what selecting those pairs from the source
+ *   views (lcty_fastx_next / lcty_fastx_device_view / lcty_sample_reads_view) gives: the mates on consecutive 32-base units in the
+ *   source's order, padding bits as they were, an absent mate with mate_len 0 and no unit; aln_off / cigar_off are zeros.
+ *   src_ordinal (may be NULL): the ordinal of every pair. Downloaded on first use; the arrays belong to the set and hold until the
+ *   next add that reaches the locus.
+ * lcty_recruited_names: name i = names[name_off[i] .. name_off[i + 1]), one behind the other without terminators, as lcty_write_bam
+ *   takes them: a FASTA / FASTQ header up to the first blank, a BAM record's read name (the first read end's). LCTY_ERR_INVALID_INPUT without keep_names, and once lcty_recruited_add,
+ *   which has no names, has added a read.
+ * lcty_reads_map_append_recruited: lcty_reads_map_append on pairs [first_pair, first_pair + n_pairs) of the locus, read where they lie
+ *   (either route): same records, same bytes in the batch as for the host chunk of those pairs. A range that does not start at pair 0
+ *   takes the bases in place as well; only its offsets are rebased, on the host. n_pairs == 0 does nothing; a range past the locus's
+ *   pairs is LCTY_ERR_INVALID_INPUT, as is a batch of another context. */
+typedef struct lcty_recruited lcty_recruited;
+int32_t lcty_recruited_create(lcty_targets* targets, int32_t keep_names, lcty_recruited** out);
+void    lcty_recruited_destroy(lcty_recruited* set);
+int32_t lcty_recruited_add(lcty_recruited* set, const lcty_reads_host* chunk, int32_t paired, uint32_t max_out, const uint32_t* out_cnt,
+                           const uint32_t* out_loci);
+int32_t lcty_recruited_add_fastx(lcty_recruited* set, lcty_fastx_device* f, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci);
+int32_t lcty_recruited_add_sample(lcty_recruited* set, lcty_sample_reads* reads, uint32_t max_out, const uint32_t* out_cnt,
+                                  const uint32_t* out_loci);
+int32_t lcty_recruited_sizes(lcty_recruited* set, uint32_t locus_ix, uint64_t* n_pairs, uint64_t* n_bases);
+int32_t lcty_recruited_view(lcty_recruited* set, uint32_t locus_ix, lcty_reads_host* view, const uint64_t** src_ordinal);
+int32_t lcty_recruited_names(lcty_recruited* set, uint32_t locus_ix, const uint64_t** name_off, const char** names);
+int32_t lcty_reads_map_append_recruited(lcty_reads* reads, lcty_recruited* set, uint32_t locus_ix, uint64_t first_pair, uint64_t n_pairs,
+                                        const lcty_map_params* params);
 
 /* ---- solver stages (src/solvers/solve.rs:789-850, src/solvers/stoch.rs, src/model/assgn.rs) ----------------
  * The reference drives these stages from one Xoshiro256++ through rand ^0.10 adaptors that are not in its tree and

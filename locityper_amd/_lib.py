@@ -216,6 +216,15 @@ SIGNATURES = {
     "lcty_locus_build_map_index": (I32, [VP, VP, U32, U32]),
     "lcty_map_reads": (I32, [VP, VP, VP, VP, VP, U64, VP, VP, U64, VP, VP]),
     "lcty_reads_map_append": (I32, [VP, VP, VP]),
+    "lcty_recruited_create": (I32, [VP, I32, P(VP)]),
+    "lcty_recruited_destroy": (None, [VP]),
+    "lcty_recruited_add": (I32, [VP, VP, I32, U32, VP, VP]),
+    "lcty_recruited_add_fastx": (I32, [VP, VP, U32, VP, VP]),
+    "lcty_recruited_add_sample": (I32, [VP, VP, U32, VP, VP]),
+    "lcty_recruited_sizes": (I32, [VP, U32, P(U64), P(U64)]),
+    "lcty_recruited_view": (I32, [VP, U32, VP, P(VP)]),
+    "lcty_recruited_names": (I32, [VP, U32, P(VP), P(VP)]),
+    "lcty_reads_map_append_recruited": (I32, [VP, VP, U32, U64, U64, VP]),
     "lcty_ctx_trim": (I32, [VP]),
     "lcty_host_alloc": (I32, [VP, U64, P(VP)]),
     "lcty_host_free": (None, [VP]),

@@ -745,6 +745,15 @@ def map_append(aa, chunk, params):
     aa._scored = False
 
 
+def map_append_recruited(aa, rset, locus_ix, params, first_pair=0, n_pairs=None):
+    """lcty_reads_map_append_recruited: pairs [first_pair, first_pair + n_pairs) of locus `locus_ix` of the Recruited set, mapped from
+    where they lie on the device, the records straight into the batch `aa` (n_pairs None: to the end)."""
+    if n_pairs is None:
+        n_pairs = rset.sizes(locus_ix)[0] - first_pair
+    check(lib().lcty_reads_map_append_recruited(aa._h, rset._h, locus_ix, first_pair, n_pairs, C.byref(params)))
+    aa._scored = False
+
+
 def map_reads(locus, chunk, params):
     """lcty_map_reads: the read ends of `chunk` (its sequence fields) onto the basis alleles; returns a ReadsChunk with the found
     records, =/X/S CIGARs and the bases in BAM orientation — ready for AllAlignments.append."""
@@ -803,6 +812,87 @@ class Targets:
     def close(self):
         if self._h:
             lib().lcty_targets_destroy(self._h)
+            self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Recruited:
+    """lcty_recruited: the recruited reads of every locus of finalized Targets, resident on the device in the mapper's layout
+    (DESIGN.md 5v). add() takes a host ReadsChunk, add_fastx() the current chunk of an io.FastxDevice, add_sample() an io.SampleReads;
+    cnt / loci are the answers of the matching recruit()."""
+
+    def __init__(self, targets, keep_names=False):
+        self._h = VP()
+        self._targets = targets                        # the targets outlive the set
+        check(lib().lcty_recruited_create(targets._h, int(keep_names), C.byref(self._h)))
+
+    @staticmethod
+    def _answers(cnt, loci):
+        cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+        loci = np.ascontiguousarray(loci, dtype=np.uint32).reshape(len(cnt), -1) if len(cnt) else np.zeros((0, 1), dtype=np.uint32)
+        return cnt, np.ascontiguousarray(loci), max(loci.shape[1], 1)
+
+    def add(self, chunk, cnt, loci, paired=True):
+        cnt, loci, max_out = self._answers(cnt, loci)
+        assert len(cnt) == chunk.n_pairs
+        hs = chunk.host_struct()
+        check(lib().lcty_recruited_add(self._h, C.byref(hs), int(paired), max_out, cnt.ctypes.data, loci.ctypes.data))
+
+    def add_fastx(self, fastx_device, cnt, loci):
+        cnt, loci, max_out = self._answers(cnt, loci)
+        assert len(cnt) == fastx_device.n
+        check(lib().lcty_recruited_add_fastx(self._h, fastx_device._h, max_out, cnt.ctypes.data, loci.ctypes.data))
+
+    def add_sample(self, sample_reads, cnt, loci):
+        cnt, loci, max_out = self._answers(cnt, loci)
+        assert len(cnt) == sample_reads.stats["n_pairs"]
+        check(lib().lcty_recruited_add_sample(self._h, sample_reads._h, max_out, cnt.ctypes.data, loci.ctypes.data))
+
+    def sizes(self, locus_ix):
+        """(pairs, bases spanned by the units) of a locus."""
+        n, nb = U64(0), U64(0)
+        check(lib().lcty_recruited_sizes(self._h, locus_ix, C.byref(n), C.byref(nb)))
+        return int(n.value), int(nb.value)
+
+    def view(self, locus_ix):
+        """(cdefs.ReadsChunk of sequence fields, src_ordinal [n] uint64) of a locus: copies."""
+        hs, ordp = cdefs.ReadsHost(), VP()
+        check(lib().lcty_recruited_view(self._h, locus_ix, C.byref(hs), C.byref(ordp)))
+        n = int(hs.n_pairs)
+        def arr(ptr, count, dt):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(dt)), shape=(count,)).copy() if count else np.zeros(0, dtype=dt)
+        mate_off = arr(hs.mate_off, 2 * n + 1, C.c_uint64)
+        nb = int(mate_off[-1])
+        z = np.zeros(n + 1, dtype=np.uint64)
+        chunk = cdefs.ReadsChunk(arr(hs.mate_len, 2 * n, C.c_uint32), mate_off, arr(hs.bases2, nb // 16, C.c_uint32), arr(hs.nmask, nb // 32, C.c_uint32),
+                                 z, np.zeros(0, dtype=cdefs.ALN_REC_DTYPE), z, np.zeros(0, dtype=np.uint32))
+        return chunk, arr(ordp, n, C.c_uint64)
+
+    def names(self, locus_ix):
+        """The names of a locus's pairs, in its order (keep_names)."""
+        offp, namesp = VP(), VP()
+        check(lib().lcty_recruited_names(self._h, locus_ix, C.byref(offp), C.byref(namesp)))
+        n = self.sizes(locus_ix)[0]
+        off = np.ctypeslib.as_array(C.cast(offp, C.POINTER(C.c_uint64)), shape=(n + 1,))
+        blob = C.string_at(namesp, int(off[n]))
+        return [blob[int(off[i]):int(off[i + 1])].decode() for i in range(n)]
+
+    def names_raw(self, locus_ix):
+        """(name_off [n + 1] uint64, names bytes) as lcty_write_bam takes them: copies."""
+        offp, namesp = VP(), VP()
+        check(lib().lcty_recruited_names(self._h, locus_ix, C.byref(offp), C.byref(namesp)))
+        n = self.sizes(locus_ix)[0]
+        off = np.ctypeslib.as_array(C.cast(offp, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        return off, C.string_at(namesp, int(off[n]))
+
+    def close(self):
+        if self._h:
+            lib().lcty_recruited_destroy(self._h)
             self._h = VP()
 
     def __del__(self):

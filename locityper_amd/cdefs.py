@@ -711,6 +711,12 @@ class SampleBamStats(C.Structure):     # lcty_sample_bam_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# lcty_recruited: the bytes knob "recruited_max_bytes" counts per 32-base unit (a 64-bit word of bases, a 32-bit word of mask) and per
+# pair (two lengths, two offsets, an ordinal)
+RECRUITED_UNIT_BYTES = 12
+RECRUITED_PAIR_BYTES = 32
+
+
 class FastxDeviceStats(C.Structure):   # lcty_fastx_device_stats
     _fields_ = [(n, C.c_uint64) for n in ("bytes_read", "bytes_inflated", "windows", "windows_enlarged", "records")] + \
                [(n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_upload", "ms_lines", "ms_records", "ms_pack", "ms_total")]

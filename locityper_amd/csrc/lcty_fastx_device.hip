@@ -358,6 +358,19 @@ void emit(lcty_fastx_device* f) {
 
 }  // namespace
 
+namespace lcty {
+
+ResidentChunk fastx_device_chunk(lcty_fastx_device* f) {
+    return ResidentChunk{f->ctx, f->chunk.k, f->h_len.data(), f->d_len.p, f->d_off.p, f->d_bases.p, f->d_nm.p};
+}
+// the name lcty_fastx_device_write_recruited writes for unit i: the header of its first record up to the first blank
+std::string fastx_device_name(lcty_fastx_device* f, uint64_t i) {
+    const fastx::Chunk& c = f->chunk;
+    return f->st.name_of(f->st.f[c.file[0]], c.rec0[0] + c.stride * static_cast<uint32_t>(i));
+}
+
+}  // namespace lcty
+
 extern "C" {
 
 int32_t lcty_fastx_device_open(lcty_ctx* ctx, const char* path1, const char* path2, int32_t interleaved, lcty_fastx_device** out) {

@@ -415,9 +415,10 @@ int32_t lcty_locus_build_map_index(lcty_locus* locus, const uint16_t* basis, uin
 
 namespace {
 
-void run_map(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_params* params, uint64_t* aln_off, uint64_t* cigar_off, bool sizes_only,
+void run_map(lcty_locus* locus, const MapInput& given, const lcty_map_params* params, uint64_t* aln_off, uint64_t* cigar_off, bool sizes_only,
              MapRun& X) {
-    if (!locus || !chunk || !params || !aln_off || !cigar_off) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+    if (!locus || !params || !aln_off || !cigar_off) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+    MapInput in = given;
     auto ix = std::static_pointer_cast<MapIndex>(locus->map_index);
     if (!ix) fail(LCTY_ERR_INVALID_INPUT, "lcty_locus_build_map_index has not been called on this locus");
     if (params->k != ix->k) fail(LCTY_ERR_INVALID_INPUT, "the index was built for k = %u", ix->k);
@@ -427,14 +428,13 @@ void run_map(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_par
     lcty_ctx* ctx = locus->ctx;
     ctx->activate();
     hipStream_t s = ctx->stream;
-    const uint64_t n = chunk->n_pairs, n_mates = 2 * n;
+    const uint64_t n = in.n_pairs, n_mates = 2 * n;
     aln_off[0] = 0; cigar_off[0] = 0;
     if (n == 0) return;
-    const uint64_t nb = chunk->mate_off[n_mates];
     uint32_t max_len = 1;
     for (uint64_t m = 0; m < n_mates; m++) {
-        max_len = std::max(max_len, chunk->mate_len[m]);
-        if (chunk->mate_off[m] % 32) fail(LCTY_ERR_INVALID_INPUT, "mate offsets must be multiples of 32 bases");
+        max_len = std::max(max_len, in.mate_len[m]);
+        if (in.mate_off[m] % 32) fail(LCTY_ERR_INVALID_INPUT, "mate offsets must be multiples of 32 bases");
     }
     // the route: read ends of up to 256 bases on up to 32 basis alleles vote for diagonals (this file); anything else is chained
     // and aligned along the chain (lcty_map_long.hip)
@@ -444,22 +444,19 @@ void run_map(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_par
     if (!long_route) {
         if (ix->n_basis > MAP_MAX_BASIS) fail(LCTY_ERR_UNSUPPORTED, "up to %u basis alleles on the short route (the index has %u)", MAP_MAX_BASIS, ix->n_basis);
         for (uint64_t m = 0; m < n_mates; m++) {
-            if (chunk->mate_len[m] > MAP_MAX_LEN) fail(LCTY_ERR_UNSUPPORTED, "read ends of up to %u bases on the short route (this one: %u)", MAP_MAX_LEN, chunk->mate_len[m]);
-            if (map_seed_bound(chunk->mate_len[m], params->k, params->stride) > 64)
+            if (in.mate_len[m] > MAP_MAX_LEN) fail(LCTY_ERR_UNSUPPORTED, "read ends of up to %u bases on the short route (this one: %u)", MAP_MAX_LEN, in.mate_len[m]);
+            if (map_seed_bound(in.mate_len[m], params->k, params->stride) > 64)
                 fail(LCTY_ERR_UNSUPPORTED, "more than 64 seeds per read end: raise the stride");
         }
     }
-    X.d_len.ensure_slack(n_mates); X.d_len.upload(chunk->mate_len, n_mates, s);
-    X.d_off.ensure_slack(n_mates + 1); X.d_off.upload(chunk->mate_off, n_mates + 1, s);
-    X.d_b2.ensure_slack(std::max<uint64_t>(nb / 16, 1)); X.d_b2.upload(chunk->bases2, nb / 16, s);
-    X.d_nm.ensure_slack(std::max<uint64_t>(nb / 32, 1)); X.d_nm.upload(chunk->nmask, nb / 32, s);
+    map_upload(in, X, s);
     X.d_nrec.ensure_slack(n_mates); X.d_ncig.ensure_slack(n_mates);
     if (long_route) {
-        run_map_long(locus, chunk, params, *ix, max_len, aln_off, cigar_off, sizes_only, X);
+        run_map_long(locus, in, params, *ix, max_len, aln_off, cigar_off, sizes_only, X);
         return;
     }
     MapView V{};
-    fill_map_view(V, locus, *ix, params, X, n_mates, std::min<uint32_t>(64, 2 * ix->n_basis), sizeof(MapCand));
+    fill_map_view(V, locus, *ix, params, X, in, std::min<uint32_t>(64, 2 * ix->n_basis), sizeof(MapCand));
     const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
     const uint32_t n_wg = static_cast<uint32_t>(std::min<uint64_t>(n_mates, 16ull * cus));
     // kernel 1: the candidates that stay, and the list of those to be aligned with gaps
@@ -484,10 +481,15 @@ void run_map(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_par
         });
     }
     // kernel 3: sizes, then records
-    map_emit_two_pass(ctx, chunk, V, X, aln_off, cigar_off, sizes_only, [&](const MapView& view, bool write, uint32_t wgs) {
+    map_emit_two_pass(ctx, in, V, X, aln_off, cigar_off, sizes_only, [&](const MapView& view, bool write, uint32_t wgs) {
         if (write) hipLaunchKernelGGL(map_emit_kernel<true>, dim3(wgs), dim3(64), 0, s, view);
         else hipLaunchKernelGGL(map_emit_kernel<false>, dim3(wgs), dim3(64), 0, s, view);
     });
+}
+
+// a chunk of the C interface as the routes take it: everything from the host
+MapInput host_input(const lcty_reads_host* chunk) {
+    return MapInput{chunk->n_pairs, chunk->mate_len, chunk->mate_off, chunk->bases2, chunk->nmask, nullptr, nullptr, nullptr, nullptr};
 }
 
 }  // namespace
@@ -497,7 +499,8 @@ int32_t lcty_map_reads(lcty_locus* locus, const lcty_reads_host* chunk, const lc
     return guarded([&] {
         MapRun X;
         const bool sizes_only = !recs || !cigar || !bases2_out || !nmask_out;
-        run_map(locus, chunk, params, aln_off, cigar_off, sizes_only, X);
+        if (!chunk) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        run_map(locus, host_input(chunk), params, aln_off, cigar_off, sizes_only, X);
         if (sizes_only || !chunk->n_pairs) return;
         if (X.n_recs > cap_recs || X.n_cigar > cap_cigar)
             fail(LCTY_ERR_INVALID_INPUT, "room for %llu records and %llu CIGAR words is needed", (unsigned long long)X.n_recs, (unsigned long long)X.n_cigar);
@@ -513,34 +516,43 @@ int32_t lcty_map_reads(lcty_locus* locus, const lcty_reads_host* chunk, const lc
 int32_t lcty_reads_map_append(lcty_reads* reads, const lcty_reads_host* chunk, const lcty_map_params* params) {
     return guarded([&] {
         if (!reads || !chunk || !params) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const uint64_t n = chunk->n_pairs;
-        if (n == 0) return;
-        const bool trace = reads->ctx->diag_knob("map_trace", 0) != 0;
-        const double t_in = now_ms();
-        auto since = [&] { return now_ms() - t_in; };
-        // the device buffers of the mapping (arenas of CIGAR words and chains, scratch of the kernels: tens of GB for long reads on many
-        // alleles) stay with the context from chunk to chunk — a streaming loop does not allocate and release them per chunk — until the
-        // solver stages take the memory back (lcty_ctx::release_transfer_scratch) or lcty_ctx_trim is called
-        std::lock_guard<std::mutex> one_at_a_time(reads->ctx->map_mutex);
-        std::shared_ptr<MapRun> held;
-        {
-            std::lock_guard<std::mutex> lock(reads->ctx->scratch_mutex);
-            held = std::static_pointer_cast<MapRun>(reads->ctx->map_scratch);
-            if (!held) { held = std::make_shared<MapRun>(); reads->ctx->map_scratch = held; }
-        }
-        MapRun& X = *held;
-        std::vector<uint64_t> aln_off(n + 1), cigar_off(n + 1);
-        run_map(reads->locus, chunk, params, aln_off.data(), cigar_off.data(), false, X);
-        if (trace) fprintf(stderr, "[lcty map] mapped at %.3f ms of the call\n", since());
-        lcty_reads_host h = *chunk;
-        h.aln_off = aln_off.data(); h.cigar_off = cigar_off.data(); h.recs = nullptr; h.cigar = nullptr;
-        DeviceRecords dev{X.d_recs.p, X.d_cigar.p, X.d_ob2.p, X.d_onm.p, X.nrec.data(), X.max_rec_cigar};
-        const double t0 = now_ms();
-        const int32_t rc = reads_append_device(reads, &h, &dev);
-        if (reads->ctx->diag_knob("map_trace", 0))
-            fprintf(stderr, "[lcty map] append of the mapped chunk: %.3f ms\n", now_ms() - t0);
-        if (rc != LCTY_OK) fail(rc, "%s", lcty_last_error());
+        map_append_input(reads, host_input(chunk), params);
     });
 }
 
 }  // extern "C"
+
+namespace lcty {
+
+void map_append_input(lcty_reads* reads, const MapInput& in, const lcty_map_params* params) {
+    const uint64_t n = in.n_pairs;
+    if (n == 0) return;
+    const bool trace = reads->ctx->diag_knob("map_trace", 0) != 0;
+    const double t_in = now_ms();
+    auto since = [&] { return now_ms() - t_in; };
+    // the device buffers of the mapping (arenas of CIGAR words and chains, scratch of the kernels: tens of GB for long reads on many
+    // alleles) stay with the context from chunk to chunk — a streaming loop does not allocate and release them per chunk — until the
+    // solver stages take the memory back (lcty_ctx::release_transfer_scratch) or lcty_ctx_trim is called
+    std::lock_guard<std::mutex> one_at_a_time(reads->ctx->map_mutex);
+    std::shared_ptr<MapRun> held;
+    {
+        std::lock_guard<std::mutex> lock(reads->ctx->scratch_mutex);
+        held = std::static_pointer_cast<MapRun>(reads->ctx->map_scratch);
+        if (!held) { held = std::make_shared<MapRun>(); reads->ctx->map_scratch = held; }
+    }
+    MapRun& X = *held;
+    std::vector<uint64_t> aln_off(n + 1), cigar_off(n + 1);
+    run_map(reads->locus, in, params, aln_off.data(), cigar_off.data(), false, X);
+    if (trace) fprintf(stderr, "[lcty map] mapped at %.3f ms of the call\n", since());
+    lcty_reads_host h{};                                                        // the sequence layout and the offsets: all reads_append_device reads of it
+    h.n_pairs = n; h.mate_len = in.mate_len; h.mate_off = in.mate_off;
+    h.aln_off = aln_off.data(); h.cigar_off = cigar_off.data(); h.recs = nullptr; h.cigar = nullptr;
+    DeviceRecords dev{X.d_recs.p, X.d_cigar.p, X.d_ob2.p, X.d_onm.p, X.nrec.data(), X.max_rec_cigar};
+    const double t0 = now_ms();
+    const int32_t rc = reads_append_device(reads, &h, &dev);
+    if (reads->ctx->diag_knob("map_trace", 0))
+        fprintf(stderr, "[lcty map] append of the mapped chunk: %.3f ms\n", now_ms() - t0);
+    if (rc != LCTY_OK) fail(rc, "%s", lcty_last_error());
+}
+
+}  // namespace lcty

@@ -9,8 +9,9 @@
 //             (allele, strand) order), the others with score >= min_score follow it in slot order as secondary records, a read end
 //             without a candidate is an unmapped record; map_write_seq: SEQ and N mask reverse-complemented when the primary is on the
 //             reverse strand. A route supplies its candidates and their CIGAR words, nothing else;
-//   host      map_fill_arena (a kernel repeated until its arena held what it asked for) and map_emit_two_pass (sizes, prefix sums over
-//             the read ends, the reserve, the records).
+//   host      MapInput (the read ends of a call: from the host, uploaded, or where they lie on the device), map_fill_arena (a kernel
+//             repeated until its arena held what it asked for) and map_emit_two_pass (sizes, prefix sums over the read ends, the
+//             reserve, the records).
 #pragma once
 
 #include <algorithm>
@@ -57,6 +58,16 @@ struct MapIndex {
 
 // lcty_map_index.hip: the index of the given basis alleles, made on the device
 std::shared_ptr<MapIndex> build_map_index_device(lcty_locus* locus, const uint16_t* basis, uint32_t n_basis, uint32_t k);
+
+// The read ends of a call. The host always has the lengths and the offsets (the routes size their scratch and the prefix sums from
+// them). The four sequence arrays come from the host — bases2 / nmask, uploaded into the call's buffers with the lengths and offsets —
+// or lie on the device already and are used in place: d_mate_len, d_bases2, d_nmask, and d_mate_off unless the caller's offsets are
+// not the device's (a range of a longer chunk, rebased on the host: null, and mate_off is uploaded). map_upload fills in the null ones.
+struct MapInput {
+    uint64_t n_pairs; const uint32_t* mate_len; const uint64_t* mate_off;                                // host
+    const uint32_t* bases2; const uint32_t* nmask;                                                       // host, or
+    const uint32_t* d_mate_len; const uint64_t* d_mate_off; const uint32_t* d_bases2; const uint32_t* d_nmask;      // device
+};
 
 // both passes of a route; the records stay on the device, the offsets come to the host
 struct MapRun {
@@ -223,16 +234,26 @@ __device__ void map_emit_read_end(const typename Route::View& V, const uint64_t 
 }
 
 // ---- host
-// the view of a call over an uploaded chunk (X.d_len .. X.d_nm filled), with room for `slots` candidates of `cand_bytes` per read end
-inline void fill_map_view(MapViewCommon& V, lcty_locus* locus, const MapIndex& ix, const lcty_map_params* params, MapRun& X, uint64_t n_mates,
+// what of the input is not on the device yet goes into the call's buffers; afterwards every d_ field of `in` is set
+inline void map_upload(MapInput& in, MapRun& X, hipStream_t s) {
+    const uint64_t n_mates = 2 * in.n_pairs, nb = in.mate_off[n_mates];
+    if (!in.d_mate_len) { X.d_len.ensure_slack(n_mates); X.d_len.upload(in.mate_len, n_mates, s); in.d_mate_len = X.d_len.p; }
+    if (!in.d_mate_off) { X.d_off.ensure_slack(n_mates + 1); X.d_off.upload(in.mate_off, n_mates + 1, s); in.d_mate_off = X.d_off.p; }
+    if (!in.d_bases2) { X.d_b2.ensure_slack(std::max<uint64_t>(nb / 16, 1)); X.d_b2.upload(in.bases2, nb / 16, s); in.d_bases2 = X.d_b2.p; }
+    if (!in.d_nmask) { X.d_nm.ensure_slack(std::max<uint64_t>(nb / 32, 1)); X.d_nm.upload(in.nmask, nb / 32, s); in.d_nmask = X.d_nm.p; }
+}
+
+// the view of a call over an input that is on the device (map_upload), with room for `slots` candidates of `cand_bytes` per read end
+inline void fill_map_view(MapViewCommon& V, lcty_locus* locus, const MapIndex& ix, const lcty_map_params* params, MapRun& X, const MapInput& in,
                           uint32_t slots, size_t cand_bytes) {
+    const uint64_t n_mates = 2 * in.n_pairs;
     V.table = ix.table.p; V.mask = ix.mask; V.entries = ix.entries.p; V.basis = ix.basis.p; V.n_basis = ix.n_basis;
     V.k = params->k; V.stride = params->stride; V.min_votes = std::max<uint32_t>(params->min_votes, 1);
     V.max_occ = params->max_occ ? params->max_occ : 4 * ix.n_basis;
     V.match = params->match; V.mismatch = params->mismatch; V.end_bonus = params->end_bonus; V.min_score = params->min_score;
     V.band = params->band; V.gap_open = params->gap_open; V.gap_extend = params->gap_extend;
     V.seqs = locus->d_seqs.p; V.seq_off = locus->d_seq_off.p; V.allele_len = locus->d_allele_len.p;
-    V.n_mates = n_mates; V.mate_len = X.d_len.p; V.mate_off = X.d_off.p; V.bases2 = X.d_b2.p; V.nmask = X.d_nm.p;
+    V.n_mates = n_mates; V.mate_len = in.d_mate_len; V.mate_off = in.d_mate_off; V.bases2 = in.d_bases2; V.nmask = in.d_nmask;
     V.paired = locus->bg.is_paired;
     V.n_recs = X.d_nrec.p; V.n_cigar = X.d_ncig.p;
     V.slots = slots;
@@ -267,10 +288,10 @@ void map_fill_arena(hipStream_t s, MapRun& X, uint32_t* counters, uint64_t cap, 
 // give rec_at, cig_at, pair_cig and the caller's aln_off / cigar_off; the outputs are reserved and zeroed and their places put into V;
 // emit(V, true, workgroups) writes.
 template <class View, class Emit>
-void map_emit_two_pass(lcty_ctx* ctx, const lcty_reads_host* chunk, View& V, MapRun& X, uint64_t* aln_off, uint64_t* cigar_off, bool sizes_only,
+void map_emit_two_pass(lcty_ctx* ctx, const MapInput& in, View& V, MapRun& X, uint64_t* aln_off, uint64_t* cigar_off, bool sizes_only,
                        Emit&& emit) {
     hipStream_t s = ctx->stream;
-    const uint64_t n = chunk->n_pairs, n_mates = 2 * n, nb = chunk->mate_off[n_mates];
+    const uint64_t n = in.n_pairs, n_mates = 2 * n, nb = in.mate_off[n_mates];
     const uint32_t n_wg = static_cast<uint32_t>(std::min<uint64_t>(n_mates, 16ull * static_cast<uint32_t>(ctx->props.multiProcessorCount)));
     uint32_t counters[MAPC_HOST];
     ctx->timed(LCTY_K_MAP, [&] { emit(V, false, n_wg); }, s);
@@ -302,9 +323,11 @@ void map_emit_two_pass(lcty_ctx* ctx, const lcty_reads_host* chunk, View& V, Map
     LCTY_HIP(hipStreamSynchronize(s));                                          // rec_at & co. are host vectors of this frame
 }
 
-// lcty_map_long.hip: the long route over an uploaded chunk (X.d_len .. X.d_nm filled); leaves records, CIGAR words, re-oriented bases
+// lcty_map_long.hip: the long route over an input that is on the device (map_upload); leaves records, CIGAR words, re-oriented bases
 // and the per-read-end counts in X, the offsets in aln_off / cigar_off
-void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_params* params, const MapIndex& ix, uint32_t max_len,
+void run_map_long(lcty_locus* locus, const MapInput& in, const lcty_map_params* params, const MapIndex& ix, uint32_t max_len,
                   uint64_t* aln_off, uint64_t* cigar_off, bool sizes_only, MapRun& X);
+// lcty_map.hip: lcty_reads_map_append on any input (lcty_recruited.hip maps the resident reads of a locus through it)
+void map_append_input(lcty_reads* reads, const MapInput& in, const lcty_map_params* params);
 
 }  // namespace lcty

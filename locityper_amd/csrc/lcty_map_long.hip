@@ -629,12 +629,12 @@ __global__ __launch_bounds__(64) void map_long_emit_kernel(const LongView V) {
 
 }  // namespace
 
-void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_map_params* params, const MapIndex& ix, uint32_t max_len,
+void run_map_long(lcty_locus* locus, const MapInput& in, const lcty_map_params* params, const MapIndex& ix, uint32_t max_len,
                   uint64_t* aln_off, uint64_t* cigar_off, bool sizes_only, MapRun& X) {
     lcty_ctx* ctx = locus->ctx;
     hipStream_t s = ctx->stream;
-    const uint64_t n = chunk->n_pairs, n_mates = 2 * n;
-    const uint64_t nb = chunk->mate_off[n_mates];
+    const uint64_t n = in.n_pairs, n_mates = 2 * n;
+    const uint64_t nb = in.mate_off[n_mates];
     // lcty_ctx_set_knob "map_trace" 1: wall-clock marks of the phases of a call on stderr
     const bool trace = ctx->diag_knob("map_trace", 0) != 0;
     const double t_begin = now_ms();
@@ -651,7 +651,7 @@ void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_ma
     const uint32_t cus = static_cast<uint32_t>(ctx->props.multiProcessorCount);
     size_t free_b = 0, total_b = 0;
     LongView V{};
-    fill_map_view(V, locus, ix, params, X, n_mates, n_groups, sizeof(LongCand));
+    fill_map_view(V, locus, ix, params, X, in, n_groups, sizeof(LongCand));
     V.chain_gap = params->chain_gap; V.chain_skew = params->chain_skew; V.chain_back = params->chain_back;
     V.cands = reinterpret_cast<LongCand*>(X.d_cands.p);
     uint32_t counters[MAPC_HOST] = {};
@@ -669,7 +669,7 @@ void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_ma
         X.d_work.ensure_slack(n_mates * V.slots * (sizeof(LongWork) / sizeof(uint32_t)));
         V.work = reinterpret_cast<LongWork*>(X.d_work.p);
         uint64_t seeds_total = 0;
-        for (uint64_t m = 0; m < n_mates; m++) seeds_total += map_seed_bound(chunk->mate_len[m], params->k, params->stride);
+        for (uint64_t m = 0; m < n_mates; m++) seeds_total += map_seed_bound(in.mate_len[m], params->k, params->stride);
         // room for the chains of a chunk of noisy reads on every basis allele (every other seed an anchor), as far as the memory goes; the
         // kernel says how many entries it needed when that was not enough
         LCTY_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -717,7 +717,7 @@ void run_map_long(lcty_locus* locus, const lcty_reads_host* chunk, const lcty_ma
         V.ops = X.d_ops.p; V.ops_cap = 1;
     }
     // ---- kernel 3: sizes, then records
-    map_emit_two_pass(ctx, chunk, V, X, aln_off, cigar_off, sizes_only, [&](const LongView& view, bool write, uint32_t wgs) {
+    map_emit_two_pass(ctx, in, V, X, aln_off, cigar_off, sizes_only, [&](const LongView& view, bool write, uint32_t wgs) {
         if (write) hipLaunchKernelGGL(map_long_emit_kernel<true>, dim3(wgs), dim3(64), 0, s, view);
         else hipLaunchKernelGGL(map_long_emit_kernel<false>, dim3(wgs), dim3(64), 0, s, view);
     });

@@ -605,6 +605,7 @@ lcty_ctx* targets_ctx(lcty_targets* t) {
     if (!t->finalized) fail(LCTY_ERR_INVALID_INPUT, "lcty_targets_finalize has not been called");
     return t->ctx;
 }
+uint32_t targets_n_loci(const lcty_targets* t) { return t->n_loci; }
 
 }  // namespace lcty
 

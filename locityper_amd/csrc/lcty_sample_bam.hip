@@ -597,3 +597,16 @@ int32_t lcty_sample_reads_write_recruited(lcty_sample_reads* R, lcty_fastx_write
 void lcty_sample_reads_free(lcty_sample_reads* reads) { delete reads; }
 
 }  // extern "C"
+
+namespace lcty {
+
+ResidentChunk sample_reads_chunk(lcty_sample_reads* R) {
+    return ResidentChunk{R->ctx, R->n, R->h_len.data(), R->d_len.p, R->d_off.p, R->d_bases.p, R->d_nm.p};
+}
+// the name lcty_sample_reads_write_recruited writes for pair i: its first read end's
+std::string sample_reads_name(lcty_sample_reads* R, uint64_t i) {
+    const uint32_t r = R->h_src[2 * i] != NONE32 ? R->h_src[2 * i] : R->h_src[2 * i + 1];
+    return r == NONE32 ? std::string() : record_name(R->F.slice, R->F.rec_off[r]);
+}
+
+}  // namespace lcty

@@ -350,6 +350,10 @@ class FastxDevice:
         check(lib().lcty_fastx_device_write_recruited(self._h, writers._h, loci.shape[1], cnt.ctypes.data, loci.ctypes.data, C.byref(n)))
         return int(n.value)
 
+    def add_recruited(self, rset, cnt, loci):
+        """lcty_recruited_add_fastx: the current chunk into an api.Recruited set, device to device."""
+        rset.add_fastx(self, cnt, loci)
+
     def close(self):
         if self._h:
             lib().lcty_fastx_device_close(self._h)
@@ -448,6 +452,10 @@ class SampleReads:
         n = U64(0)
         check(lib().lcty_sample_reads_write_recruited(self._h, writers._h, loci.shape[1], cnt.ctypes.data, loci.ctypes.data, C.byref(n)))
         return int(n.value)
+
+    def add_recruited(self, rset, cnt, loci):
+        """lcty_recruited_add_sample: the fetched reads into an api.Recruited set, device to device."""
+        rset.add_sample(self, cnt, loci)
 
     def close(self):
         if self._h:
