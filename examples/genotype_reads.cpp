@@ -2,6 +2,8 @@
 // in between:
 //
 //   R1 [R2] | sample.bam + index                 the sample's reads (lcty_fastx_device_open | lcty_sample_bam_open + lcty_sample_bam_fetch)
+//   a.bam [b.bam ...] --no-index [-^]            the same from whole BAM files without an index, read front to back in windows
+//                                                (lcty_bam_stream_open, lcty_bam_stream_next; -^: name-grouped pairs)
 //   PREPROC/distr.gz                             background distributions         (lcty_io_read_file + lcty_bg_from_json)
 //   <locus dir>/haplotypes.fa.gz                 alleles                          (lcty_fasta_read)
 //   <locus dir>/kmers.bin.lz4 | .br              off-target k-mer counts          (lcty_io_read_file + lcty_kmer_counts_parse)
@@ -18,7 +20,7 @@
 // external mapper -> aln.bam closed. The loci are solved with lcty_solve, one after the other: lcty_solve_queue gives the same calls
 // entry by entry but does not hand out the per-genotype likelihoods res.json.gz holds. No lock or success files, no subsampling, no
 // CRAM. Prints one JSON line of stats. Build: see tests/test_gpu_genotype_reads_example.py.
-//   ./genotype_reads -i R1 [R2] [--interleaved] | -a sample.bam [-x index] -p PREPROC/distr.gz -d DB/loci/<locus> [-d ...] [--basis]
+//   ./genotype_reads -i R1 [R2] [--interleaved] | -a sample.bam [-x index] | -a a.bam [-a b.bam ...] --no-index [-^] -p PREPROC/distr.gz -d DB/loci/<locus> [-d ...] [--basis]
 //                    [--chunk N] [--map-chunk N] [--seed S] [--out-bam] [--padding N] [--alt-contig N] -o OUTDIR
 #include <sys/stat.h>
 
@@ -92,16 +94,17 @@ static void load_locus(Locus& L, bool use_basis) {
 
 int main(int argc, char** argv) {
     std::string bam_path, index_path, distr, outdir;
-    std::vector<std::string> inputs, dirs;
-    int interleaved = 0; bool use_basis = false, out_bam = false;
+    std::vector<std::string> inputs, dirs, bam_paths;
+    int interleaved = 0; bool use_basis = false, out_bam = false, no_index = false;
     uint64_t chunk = 1u << 20, map_chunk = 1u << 16, seed = 1;
     uint32_t padding = 1000, alt_contig = 10000000;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
         if (a == "-i") { inputs.push_back(next()); if (i + 1 < argc && argv[i + 1][0] != '-') inputs.push_back(argv[++i]); }
-        else if (a == "--interleaved") interleaved = 1;
-        else if (a == "-a") bam_path = next();
+        else if (a == "--interleaved" || a == "-^") interleaved = 1;
+        else if (a == "-a") { bam_path = next(); bam_paths.push_back(bam_path); }
+        else if (a == "--no-index") no_index = true;
         else if (a == "-x") index_path = next();
         else if (a == "-p") distr = next();
         else if (a == "-d") dirs.push_back(next());
@@ -115,8 +118,8 @@ int main(int argc, char** argv) {
         else if (a == "-o") outdir = next();
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
-    if ((inputs.empty() == bam_path.empty()) || inputs.size() > 2 || distr.empty() || dirs.empty() || outdir.empty() || !chunk || !map_chunk) {
-        std::fprintf(stderr, "usage: genotype_reads -i R1 [R2] [--interleaved] | -a sample.bam [-x index] -p PREPROC/distr.gz -d DB/loci/<locus> [-d ...] [--basis] "
+    if ((inputs.empty() == bam_path.empty()) || inputs.size() > 2 || (!no_index && bam_paths.size() > 1) || (no_index && bam_path.empty()) || distr.empty() || dirs.empty() || outdir.empty() || !chunk || !map_chunk) {
+        std::fprintf(stderr, "usage: genotype_reads -i R1 [R2] [--interleaved] | -a sample.bam [-x index] | -a a.bam [-a b.bam ...] --no-index [-^] -p PREPROC/distr.gz -d DB/loci/<locus> [-d ...] [--basis] "
                              "[--chunk N] [--map-chunk N] [--seed S] [--out-bam] [--padding N] [--alt-contig N] -o OUTDIR\n");
         return 2;
     }
@@ -128,6 +131,10 @@ int main(int argc, char** argv) {
     lcty_bg bg; double read_len = 0;
     ok(lcty_bg_from_json(reinterpret_cast<const char*>(buf), len, &bg, &read_len), "BgDistr::load");
     lcty_io_free(buf);
+    if (no_index && (interleaved != 0) != (bg.is_paired != 0)) {
+        std::fprintf(stderr, "%s: distr.gz was made from %s reads\n", interleaved ? "-^ reads pairs" : "without -^ every record is a read", bg.is_paired ? "paired" : "single-end");
+        return 2;
+    }
 
     lcty_ctx* ctx = nullptr;
     ok(lcty_ctx_create(0, &ctx), "lcty_ctx_create");
@@ -175,6 +182,28 @@ int main(int argc, char** argv) {
         }
         ms_parse = st.ms_total;
         lcty_fastx_device_close(f);
+    } else if (no_index) {
+        std::vector<const char*> paths;
+        for (const std::string& p : bam_paths) paths.push_back(p.c_str());
+        lcty_bam_stream* stream = nullptr;
+        ok(lcty_bam_stream_open(ctx, paths.data(), static_cast<uint32_t>(paths.size()), interleaved, &stream), "lcty_bam_stream_open");
+        lcty_bam_stream_stats st;
+        std::memset(&st, 0, sizeof(st));
+        for (;;) {
+            lcty_sample_reads* sr = nullptr;                                    // belongs to the stream: never freed here
+            uint64_t n = 0;
+            ok(lcty_bam_stream_next(stream, &sr, &n, &st), "lcty_bam_stream_next");
+            if (!n) break;
+            cnt.assign(n, 0); out_loci.assign(n * max_out, 0);
+            double t0 = now_ms();
+            ok(lcty_sample_reads_recruit(targets, sr, max_out, cnt.data(), out_loci.data()), "lcty_sample_reads_recruit");
+            ms_recruit += now_ms() - t0; t0 = now_ms();
+            ok(lcty_recruited_add_sample(set, sr, max_out, cnt.data(), out_loci.data()), "lcty_recruited_add_sample");
+            ms_scatter += now_ms() - t0;
+            n_reads += n;
+        }
+        ms_parse = st.ms_total;
+        lcty_bam_stream_close(stream);
     } else {
         lcty_sample_bam* bam = nullptr;
         ok(lcty_sample_bam_open(bam_path.c_str(), index_path.empty() ? nullptr : index_path.c_str(), &bam), "lcty_sample_bam_open");

@@ -13,6 +13,12 @@
 // the fetch as one JSON line. --inflate device inflates the BGZF blocks of the fetch on the device (knob "sample_bam_inflate";
 // default host: zlib). Build: see tests/test_gpu_sample_bam_example.py.
 //   ./recruit_bam -a sample.bam [-i index] -d DB/loci/<locus> [-d ...] [--bed FILE] [--padding N] [--alt-contig N] [--single|--paired] [--inflate host|device] -o OUTDIR
+//
+// With --no-index the files given with -a (one or several) are read front to back, without an index and without regions, as
+// `locityper recruit -a a.bam [-a b.bam] --no-index [-^]` reads them (DirectBamReader, src/seq/fastx.rs:692-729; -^ / --interleaved:
+// PairedEndInterleaved, 423-453): lcty_bam_stream_open, then per window lcty_bam_stream_next -> lcty_sample_reads_recruit ->
+// lcty_sample_reads_write_recruited into the same reads.fq files. Prints the stats of the stream as one JSON line.
+//   ./recruit_bam --no-index -a a.bam [-a b.bam ...] [-^|--interleaved] -d DB/loci/<locus> [-d ...] [--inflate host|device] -o OUTDIR
 #include <sys/stat.h>
 
 #include <cstdint>
@@ -31,15 +37,44 @@ static void ok(int32_t rc, const char* what) {
 }
 static bool exists(const std::string& p) { FILE* f = std::fopen(p.c_str(), "rb"); if (f) std::fclose(f); return f != nullptr; }
 
+// one locus of the targets: alleles and off-target counts as genotype_dir.cpp loads them; makes OUTDIR/<locus> and returns its reads.fq
+static std::string add_locus(lcty_targets* targets, const std::string& db, const std::string& outdir) {
+    uint32_t A = 0; uint64_t names_len = 0, seqs_len = 0;
+    const std::string fa = db + "/haplotypes.fa.gz";
+    ok(lcty_fasta_read(fa.c_str(), &A, nullptr, &names_len, nullptr, &seqs_len, nullptr), "haplotypes.fa.gz");
+    std::vector<char> name_blob(names_len); std::vector<uint8_t> seqs(seqs_len); std::vector<uint64_t> seq_off(A + 1);
+    ok(lcty_fasta_read(fa.c_str(), &A, name_blob.data(), &names_len, seqs.data(), &seqs_len, seq_off.data()), "haplotypes.fa.gz");
+    const std::string kp = exists(db + "/kmers.bin.lz4") ? db + "/kmers.bin.lz4" : db + "/kmers.bin.br";
+    uint8_t* buf = nullptr; uint64_t len = 0;
+    ok(lcty_io_read_file(kp.c_str(), &buf, &len), "kmers.bin");
+    uint32_t k = 0, n_c = 0; uint64_t consumed = 0;
+    ok(lcty_kmer_counts_parse(buf, len, &k, &n_c, nullptr, 0, nullptr, 0, &consumed), "KmerCounts::load (sizes)");
+    if (n_c != A) { std::fprintf(stderr, "kmers.bin has %u contigs, the FASTA %u\n", n_c, A); std::exit(1); }
+    std::vector<uint64_t> cnt_off(A + 1);
+    uint64_t n_counts = 0;
+    for (uint32_t a = 0; a < A; a++) n_counts += seq_off[a + 1] - seq_off[a] + 1 - k;
+    std::vector<uint16_t> counts(n_counts);
+    ok(lcty_kmer_counts_parse(buf, len, &k, &n_c, cnt_off.data(), A, counts.data(), n_counts, &consumed), "KmerCounts::load");
+    lcty_io_free(buf);
+    ok(lcty_targets_add_locus(targets, A, seqs.data(), seq_off.data(), counts.data(), cnt_off.data(), k, nullptr), "lcty_targets_add_locus");
+    std::string locus = db;
+    while (!locus.empty() && locus.back() == '/') locus.pop_back();
+    locus = locus.substr(locus.find_last_of('/') + 1);
+    mkdir((outdir + "/" + locus).c_str(), 0777);
+    return outdir + "/" + locus + "/reads.fq";
+}
+
 int main(int argc, char** argv) {
     std::string bam_path, index_path, bed, outdir;
-    std::vector<std::string> dirs;
+    std::vector<std::string> dirs, bam_paths;
     uint32_t padding = 1000, alt_contig = 10000000;
-    int paired = -1, inflate_on_device = 0;
+    int paired = -1, inflate_on_device = 0, no_index = 0, interleaved = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
-        if (a == "-a") bam_path = next();
+        if (a == "-a") { bam_path = next(); bam_paths.push_back(bam_path); }
+        else if (a == "--no-index") no_index = 1;
+        else if (a == "-^" || a == "--interleaved") interleaved = 1;
         else if (a == "-i") index_path = next();
         else if (a == "-d") dirs.push_back(next());
         else if (a == "--bed") bed = next();
@@ -59,6 +94,58 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: recruit_bam -a sample.bam [-i index] -d DB/loci/<locus> [-d ...] [--bed FILE] [--padding N] [--alt-contig N] [--single|--paired] [--inflate host|device] -o OUTDIR\n");
         return 2;
     }
+    if (!no_index && (bam_paths.size() > 1 || interleaved)) { std::fprintf(stderr, "several -a files and -^ go with --no-index\n"); return 2; }
+
+    if (no_index) {
+        lcty_ctx* ctx = nullptr;
+        ok(lcty_ctx_create(0, &ctx), "lcty_ctx_create");
+        ok(lcty_ctx_set_knob(ctx, "sample_bam_inflate", inflate_on_device), "lcty_ctx_set_knob");
+        lcty_recruit_params rp;
+        ok(lcty_recruit_params_default(&rp, LCTY_TECH_ILLUMINA, interleaved), "lcty_recruit_params_default");
+        lcty_targets* targets = nullptr;
+        ok(lcty_targets_create(ctx, &rp, &targets), "lcty_targets_create");
+        std::vector<std::string> out_paths;
+        mkdir(outdir.c_str(), 0777);
+        for (const std::string& db : dirs) out_paths.push_back(add_locus(targets, db, outdir));
+        ok(lcty_targets_finalize(targets, nullptr), "lcty_targets_finalize");
+        std::vector<const char*> paths, inputs;
+        for (const std::string& p : out_paths) paths.push_back(p.c_str());
+        for (const std::string& p : bam_paths) inputs.push_back(p.c_str());
+        lcty_fastx_writers* writers = nullptr;
+        ok(lcty_fastx_writers_open(paths.data(), static_cast<uint32_t>(paths.size()), &writers), "lcty_fastx_writers_open");
+        lcty_bam_stream* stream = nullptr;
+        ok(lcty_bam_stream_open(ctx, inputs.data(), static_cast<uint32_t>(inputs.size()), interleaved, &stream), "lcty_bam_stream_open");
+        lcty_bam_stream_stats st;
+        std::memset(&st, 0, sizeof(st));
+        const uint32_t max_out = 8;
+        std::vector<uint32_t> cnt, loci;
+        uint64_t recruited = 0;
+        for (;;) {
+            lcty_sample_reads* reads = nullptr;                                   // belongs to the stream: never freed here
+            uint64_t n = 0;
+            ok(lcty_bam_stream_next(stream, &reads, &n, &st), "lcty_bam_stream_next");
+            if (!n) break;
+            cnt.assign(n, 0); loci.assign(n * max_out, 0);
+            ok(lcty_sample_reads_recruit(targets, reads, max_out, cnt.data(), loci.data()), "lcty_sample_reads_recruit");
+            uint64_t n_written = 0;
+            ok(lcty_sample_reads_write_recruited(reads, writers, max_out, cnt.data(), loci.data(), &n_written), "lcty_sample_reads_write_recruited");
+            recruited += n_written;
+        }
+        ok(lcty_fastx_writers_close(writers), "lcty_fastx_writers_close");
+        std::printf("{\"interleaved\": %d, \"files\": %llu, \"file_bytes\": %llu, \"bytes_read\": %llu, \"blocks_inflated\": %llu, \"bytes_inflated\": %llu, "
+                    "\"windows\": %llu, \"windows_enlarged\": %llu, \"bytes_carried\": %llu, \"records_walked\": %llu, \"records_kept\": %llu, "
+                    "\"bases_kept\": %llu, \"reads\": %llu, \"recruited\": %llu, \"ms_read\": %.3f, \"ms_inflate\": %.3f, \"ms_walk\": %.3f, "
+                    "\"ms_upload\": %.3f, \"ms_record\": %.3f, \"ms_pair\": %.3f, \"ms_unpack\": %.3f, \"ms_total\": %.3f}\n",
+                    interleaved, (unsigned long long)st.files, (unsigned long long)st.file_bytes, (unsigned long long)st.bytes_read,
+                    (unsigned long long)st.blocks_inflated, (unsigned long long)st.bytes_inflated, (unsigned long long)st.windows,
+                    (unsigned long long)st.windows_enlarged, (unsigned long long)st.bytes_carried, (unsigned long long)st.records_walked,
+                    (unsigned long long)st.records_kept, (unsigned long long)st.bases_kept, (unsigned long long)st.reads, (unsigned long long)recruited,
+                    st.ms_read, st.ms_inflate, st.ms_walk, st.ms_upload, st.ms_record, st.ms_pair, st.ms_unpack, st.ms_total);
+        lcty_bam_stream_close(stream);
+        lcty_targets_destroy(targets);
+        lcty_ctx_destroy(ctx);
+        return 0;
+    }
 
     lcty_sample_bam* bam = nullptr;
     ok(lcty_sample_bam_open(bam_path.c_str(), index_path.empty() ? nullptr : index_path.c_str(), &bam), "lcty_sample_bam_open");
@@ -74,7 +161,7 @@ int main(int argc, char** argv) {
     lcty_targets* targets = nullptr;
     ok(lcty_targets_create(ctx, &rp, &targets), "lcty_targets_create");
 
-    // ---- the loci: alleles and off-target counts as genotype_dir.cpp loads them; their intervals
+    // ---- the loci (add_locus) and their intervals
     std::vector<uint32_t> tid, start, end;
     auto read_bed = [&](const std::string& path) {                             // load_recr_targets / Interval::parse_bed (genotype.rs:799-820)
         std::ifstream in(path);
@@ -93,30 +180,8 @@ int main(int argc, char** argv) {
     std::vector<std::string> out_paths;
     mkdir(outdir.c_str(), 0777);
     for (const std::string& db : dirs) {
-        uint32_t A = 0; uint64_t names_len = 0, seqs_len = 0;
-        const std::string fa = db + "/haplotypes.fa.gz";
-        ok(lcty_fasta_read(fa.c_str(), &A, nullptr, &names_len, nullptr, &seqs_len, nullptr), "haplotypes.fa.gz");
-        std::vector<char> name_blob(names_len); std::vector<uint8_t> seqs(seqs_len); std::vector<uint64_t> seq_off(A + 1);
-        ok(lcty_fasta_read(fa.c_str(), &A, name_blob.data(), &names_len, seqs.data(), &seqs_len, seq_off.data()), "haplotypes.fa.gz");
-        const std::string kp = exists(db + "/kmers.bin.lz4") ? db + "/kmers.bin.lz4" : db + "/kmers.bin.br";
-        uint8_t* buf = nullptr; uint64_t len = 0;
-        ok(lcty_io_read_file(kp.c_str(), &buf, &len), "kmers.bin");
-        uint32_t k = 0, n_c = 0; uint64_t consumed = 0;
-        ok(lcty_kmer_counts_parse(buf, len, &k, &n_c, nullptr, 0, nullptr, 0, &consumed), "KmerCounts::load (sizes)");
-        if (n_c != A) { std::fprintf(stderr, "kmers.bin has %u contigs, the FASTA %u\n", n_c, A); return 1; }
-        std::vector<uint64_t> cnt_off(A + 1);
-        uint64_t n_counts = 0;
-        for (uint32_t a = 0; a < A; a++) n_counts += seq_off[a + 1] - seq_off[a] + 1 - k;
-        std::vector<uint16_t> counts(n_counts);
-        ok(lcty_kmer_counts_parse(buf, len, &k, &n_c, cnt_off.data(), A, counts.data(), n_counts, &consumed), "KmerCounts::load");
-        lcty_io_free(buf);
-        ok(lcty_targets_add_locus(targets, A, seqs.data(), seq_off.data(), counts.data(), cnt_off.data(), k, nullptr), "lcty_targets_add_locus");
+        out_paths.push_back(add_locus(targets, db, outdir));
         if (bed.empty()) read_bed(db + "/ref.bed");
-        std::string locus = db;
-        while (!locus.empty() && locus.back() == '/') locus.pop_back();
-        locus = locus.substr(locus.find_last_of('/') + 1);
-        mkdir((outdir + "/" + locus).c_str(), 0777);
-        out_paths.push_back(outdir + "/" + locus + "/reads.fq");
     }
     if (!bed.empty()) read_bed(bed);
     ok(lcty_targets_finalize(targets, nullptr), "lcty_targets_finalize");

@@ -285,6 +285,10 @@ int32_t lcty_ctx_synchronize(lcty_ctx* ctx);
  *       device to device; the contents do not depend on it.   "recruited_max_bytes"   bytes the contents of an lcty_recruited set may
  *       reach over all loci, 12 per unit and 32 per pair (default 2^36; an add beyond it is LCTY_ERR_UNSUPPORTED naming this knob,
  *       before anything is copied; the capacity behind the contents is at most twice as large).
+ *       "bam_stream_window_bytes"   inflated bytes, the carried tail included, at which a window of lcty_bam_stream_next stops taking
+ *       BGZF blocks (default 2^28, at least 1: 0 is LCTY_ERR_INVALID_INPUT at lcty_bam_stream_open; the reads do not depend on it); a
+ *       window that completes no record is doubled, up to   "bam_stream_window_limit"   (default 2^33; a record beyond it is
+ *       LCTY_ERR_UNSUPPORTED naming this knob).
  * value < 0 restores the default; an unknown name is LCTY_ERR_INVALID_INPUT. None of them changes a result beyond the last bits of
  * an f64 sum (the order in which a chain's likelihood or a genotype's score is added up). */
 int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value);
@@ -719,6 +723,49 @@ int32_t lcty_sample_reads_recruit(lcty_targets* targets, lcty_sample_reads* read
 int32_t lcty_sample_reads_write_recruited(lcty_sample_reads* reads, lcty_fastx_writers* writers, uint32_t max_out, const uint32_t* out_cnt,
                                           const uint32_t* out_loci, uint64_t* n_written);
 void    lcty_sample_reads_free(lcty_sample_reads* reads);
+
+/* ---- Whole BAM files without an index, streamed through the device in windows --------------------------------------
+ * `locityper genotype|recruit -a reads.bam [-a ...] --no-index [-^]`: process_readers! (src/seq/fastx.rs:1029-1043) -> DirectBamReader
+ * (692-729), under PairedEndInterleaved (423-453) with -^. How unaligned BAM files (PacBio HiFi, ONT), name-collated paired files and
+ * several files given as one input arrive. The rules are restated in tests/pyref_bam_stream.py.
+ * lcty_bam_stream_open: DirectBamReader::new: every file is opened and its header read now; no index is looked for, the contigs are
+ *   ignored. n_paths == 0 or a null argument: LCTY_ERR_INVALID_INPUT; a path that cannot be opened: LCTY_ERR_INVALID_INPUT; a CRAM
+ *   file: LCTY_ERR_UNSUPPORTED; bytes that are not BGZF or not BAM (an empty file included): LCTY_ERR_INVALID_DATA "... is not a BAM
+ *   file"; a truncated header: LCTY_ERR_INVALID_DATA. Host code.
+ * lcty_bam_stream_next: one chunk per call, all reads of one window: whole BGZF blocks of the current file until the inflated bytes,
+ *   the tail carried from the last window included, reach knob "bam_stream_window_bytes" or the file ends (inflated on the host, or
+ *   with knob "sample_bam_inflate" 1 on the device); the chain of record lengths is walked on the host, everything else runs on the
+ *   device. The stream is the records of file 0, then file 1, ...; a record is kept iff (flag & 0x900) == 0, nothing else of it
+ *   matters; its sequence is reversed and complemented with flag 0x10, every code but A, C, G, T is "not ACGT". interleaved == 0: every
+ *   kept record is a read (mate 2 absent). interleaved: kept records 2 i and 2 i + 1 of the whole stream are mates 1 and 2 of pair i,
+ *   whatever their flags, any number of other records apart and in different files; their names a, b (without the NUL) must satisfy
+ *   len(a) == len(b) && (len(a) <= 3 || a[len - 3] == b[len - 3]) (equal_names_fast).
+ *   *n: the reads, or pairs, of the chunk; 0 only at the end of the last file (a window that completes no read makes the call go on
+ *   to the next window). *reads belongs to the stream: it is valid until the next lcty_bam_stream_next or lcty_bam_stream_close and is
+ *   NEVER passed to lcty_sample_reads_free. lcty_sample_reads_view, _recruit, _write_recruited and lcty_recruited_add_sample work on it
+ *   unchanged; src_record of the view is the ordinal among the kept records of the chunk's window, stats.first_kept + src_record the
+ *   ordinal among the kept records of the whole input.
+ *   Errors, LCTY_ERR_INVALID_DATA: a kept record without sequence ("Primary alignment for read <name> has no sequence"); a name
+ *   mismatch ("Interleaved input file(s) <paths> contains non matching first and second mate (<a> and <b>)"); a kept record left alone
+ *   at the end of the last file ("Odd number of records in an interleaved input file(s) <paths>"); a record shorter than its fields, or
+ *   one that leaves the end of its file (a record never continues in the next file), naming the file. LCTY_ERR_UNSUPPORTED: a window of
+ *   2^31 - 16 records or more; a record beyond knob "bam_stream_window_limit". The first offending record in input order decides (for a
+ *   mismatch the second mate): reads completed in front of it are handed out, by a call that returns LCTY_OK; the call that would begin
+ *   with the offending record fails, and so does every call after it. What was handed out does not depend on the window knob.
+ *   stats (may be NULL): sums since lcty_bam_stream_open, every record counted once, whatever the window (a window that ends in an
+ *   error counts the records in front of it); first_kept belongs to this chunk. */
+typedef struct lcty_bam_stream lcty_bam_stream;
+typedef struct lcty_bam_stream_stats {
+    uint64_t files, file_bytes, bytes_read, blocks_inflated, bytes_inflated;   /* sums since open */
+    uint64_t windows, windows_enlarged, bytes_carried;
+    uint64_t records_walked, records_primary, records_kept, bases_kept;        /* every record counted once, whatever the window */
+    uint64_t reads;            /* reads, or pairs, handed out */
+    uint64_t first_kept;       /* of THIS chunk: ordinal in the whole input of record 0 of its window's kept stream */
+    double   ms_read, ms_inflate, ms_walk, ms_upload, ms_record, ms_pair, ms_unpack, ms_total;
+} lcty_bam_stream_stats;
+int32_t lcty_bam_stream_open(lcty_ctx* ctx, const char* const* paths, uint32_t n_paths, int32_t interleaved, lcty_bam_stream** out);
+void    lcty_bam_stream_close(lcty_bam_stream* s);
+int32_t lcty_bam_stream_next(lcty_bam_stream* s, lcty_sample_reads** reads, uint64_t* n, lcty_bam_stream_stats* stats);
 
 /* ---- BGZF blocks inflated on the device ------------------------------------------------------------------------------
  * BGZF is the SAM specification's section 4.1: gzip members (RFC 1952) of at most 64 KB each, whose extra field holds the block's

@@ -711,6 +711,15 @@ class SampleBamStats(C.Structure):     # lcty_sample_bam_stats
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BamStreamStats(C.Structure):     # lcty_bam_stream_stats
+    _fields_ = [(n, C.c_uint64) for n in ("files", "file_bytes", "bytes_read", "blocks_inflated", "bytes_inflated", "windows", "windows_enlarged",
+                                          "bytes_carried", "records_walked", "records_primary", "records_kept", "bases_kept", "reads", "first_kept")] + \
+               [(n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_walk", "ms_upload", "ms_record", "ms_pair", "ms_unpack", "ms_total")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # lcty_recruited: the bytes knob "recruited_max_bytes" counts per 32-base unit (a 64-bit word of bases, a 32-bit word of mask) and per
 # pair (two lengths, two offsets, an ordinal)
 RECRUITED_UNIT_BYTES = 12

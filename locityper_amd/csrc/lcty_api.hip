@@ -49,7 +49,7 @@ int32_t lcty_ctx_set_knob(lcty_ctx* ctx, const char* name, int64_t value) {
                                             "align_batch_pairs", "align_hash_bits", "align_dp_cells", "align_match_budget", "align_cigar_store_mb", "pafvcf_hash_bits", "pafvcf_table_mb",
                                             "genome_max_bases", "sample_bam_hash_bits", "sample_bam_max_slice_bytes", "sample_bam_inflate",
                                             "bgzf_deflate", "bgzf_deflate_max_bytes", "aln_bam_max_slice_bytes", "vcf_max_slice_bytes", "fastx_window_bytes", "fastx_window_limit", "recruit_blocks",
-                                            "recruited_init_units", "recruited_max_bytes",
+                                            "recruited_init_units", "recruited_max_bytes", "bam_stream_window_bytes", "bam_stream_window_limit",
 #ifdef LCTY_DIAG
                                             // the developer build (make DIAG=1): traces, in-kernel timing, kernel forms under measurement
                                             "solve_stats", "queue_trace", "map_trace", "exact_trace", "solve_greedy_form", "solve_anneal_timing", "score_timing",

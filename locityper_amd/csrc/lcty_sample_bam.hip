@@ -13,6 +13,7 @@
 //   pair_kernel     a lane per record: PairedBamReader's state machine replayed over the records of ITS name before it in the run of
 //                   its hash (names compared byte for byte), which says whether this record completes a pair and with whom
 //   exclusive_scan  over the completing records -> the pairs in the reference's order; assemble_kernel lays out the mates
+//                   (stream_kernel, assemble_kernel and offsets_kernel: lcty_bam_layout.hpp, shared with lcty_bam_stream.hip)
 //   unpack_kernel   a lane per 32 bases of a mate: 4-bit codes -> bases2 / nmask, back to front and complemented for reverse records;
 //                   a lane writes whole words of its own only
 // The record on the device (lcty_bam_record.hpp) and the front half of a fetch (fetch_slice, lcty_sample_bam.hpp, over the slice of
@@ -22,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "lcty_bam_layout.hpp"
 #include "lcty_objects.hpp"
 #include "lcty_sample_bam.hpp"
 #include "lcty_scan.hpp"
@@ -114,17 +116,6 @@ __global__ __launch_bounds__(256) void record_kernel(const SampleView V) {
     if (lane == 0 && prim) atomicAdd(V.n_primary, static_cast<uint32_t>(__popcll(prim)));
 }
 
-// kept record r -> place scan[r] of the stream; the sort's input: (hash, stream ordinal)
-__global__ __launch_bounds__(256) void stream_kernel(uint32_t n_rec, const uint32_t* __restrict__ kept, const uint32_t* __restrict__ scan,
-                                                     const uint64_t* __restrict__ hash, uint32_t* __restrict__ stream, uint64_t* __restrict__ keys,
-                                                     uint64_t* __restrict__ vals) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r >= n_rec || !kept[r]) return;
-    const uint32_t s = scan[r];
-    stream[s] = r;
-    if (keys) { keys[s] = hash[r]; vals[s] = s; }
-}
-
 // PairedBamReader::read_next (fastx.rs:829-869) for the record at place i of the sorted list: the records of its name before it, in
 // stream order, leave a record waiting or nobody; then this record completes a pair, waits, is discarded or is an error.
 __global__ __launch_bounds__(256) void pair_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ info,
@@ -157,47 +148,9 @@ __global__ __launch_bounds__(256) void pair_kernel(const uint32_t* __restrict__ 
     mate_of[s] = mate; completes[s] = mate != NONE32 ? 1u : 0u;
 }
 
-// the mates of the output: src[m] = record of mate m (NONE32: absent), its length, and its length in units of 32 bases
-__global__ __launch_bounds__(256) void assemble_kernel(const uint32_t* __restrict__ raw, const uint64_t* __restrict__ rec_off, const uint32_t* __restrict__ info,
-                                                       const uint32_t* __restrict__ stream, uint32_t n_stream, int paired, const uint32_t* __restrict__ mate_of,
-                                                       const uint32_t* __restrict__ pair_ix, uint32_t* __restrict__ src, uint32_t* __restrict__ src_stream,
-                                                       uint32_t* __restrict__ mate_len, uint32_t* __restrict__ units) {
-    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-    if (s >= n_stream) return;
-    uint32_t p = s, s1 = s, s2 = NONE32;
-    if (paired) {
-        if (mate_of[s] == NONE32) return;
-        p = pair_ix[s];
-        s2 = mate_of[s];
-        if (!(info[stream[s1]] & 0x40u)) { const uint32_t x = s1; s1 = s2; s2 = x; }     // mate 1 is the first in template
-    }
-    const uint32_t r1 = stream[s1], r2 = s2 != NONE32 ? stream[s2] : NONE32;
-    src_stream[2 * p] = s1; src_stream[2 * p + 1] = s2;
-    const uint32_t l1 = ld32(raw, rec_off[r1] + 20), l2 = r2 != NONE32 ? ld32(raw, rec_off[r2] + 20) : 0u;
-    src[2 * p] = r1; src[2 * p + 1] = r2;
-    mate_len[2 * p] = l1; mate_len[2 * p + 1] = l2;
-    units[2 * p] = l1 / 32u + ((l1 & 31u) ? 1u : 0u); units[2 * p + 1] = l2 / 32u + ((l2 & 31u) ? 1u : 0u);
-}
-__global__ __launch_bounds__(256) void offsets_kernel(const uint32_t* __restrict__ unit_off, uint64_t n, uint64_t* __restrict__ mate_off) {
-    const uint64_t m = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
-    if (m < n) mate_off[m] = 32ull * unit_off[m];
-}
-
 }  // namespace lcty
 
 using namespace lcty;
-
-struct lcty_sample_reads {
-    lcty_ctx* ctx = nullptr;
-    bool paired = false;
-    uint64_t n = 0;                              // pairs, or single reads
-    Slice F;                                     // the inflated blocks of the call and the records walked in them
-    DevBuf<uint32_t> d_len, d_nm, d_src; DevBuf<uint64_t> d_off, d_bases;
-    uint64_t n_units = 0;
-    std::vector<uint32_t> h_len, h_src, h_src_stream, h_bases, h_nm;    // h_src: a mate's record among the records walked (rec_off); _stream: in the fetched stream
-    std::vector<uint64_t> h_off, zero_off;
-    bool have_bases = false;
-};
 
 namespace {
 

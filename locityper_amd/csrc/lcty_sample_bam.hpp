@@ -1,7 +1,9 @@
 // lcty_sample_bam.hpp — what the two readers of an indexed BAM file share: lcty_sample_bam.hip (`genotype -a`: the
 // reads of the target regions) and lcty_bg_fetch.hip (`preproc -a`: the alignments of the background region). The opened file with
 // its index, and the front half of a fetch of regions: their chunks, the slice (lcty_bgzf_read.hpp) and the chain of record lengths
-// (fetch_slice). The record on the device is in lcty_bam_record.hpp.
+// (fetch_slice). The record on the device is in lcty_bam_record.hpp. The reads a fetch leaves on the device (lcty_sample_reads) are
+// also what the reader of whole files in windows hands out chunk by chunk (lcty_bam_stream.hip), so that the consumers
+// of lcty_sample_bam.hip (view, recruit, write_recruited, lcty_recruited_add_sample) serve both.
 #pragma once
 
 #include <string>
@@ -19,6 +21,19 @@ struct lcty_sample_bam {
     std::vector<lcty::IndexRef> refs;            // bins -> chunks, the linear index (lcty_bgzf_index.hpp)
     uint64_t tail_start = 0;                     // largest chunk end of the index
     uint64_t n_no_coor = 0; bool has_no_coor = false;
+};
+
+// The reads of one fetch, or of one window of a stream of whole files (lcty_bam_stream.hip), resident on the device.
+struct lcty_sample_reads {
+    lcty_ctx* ctx = nullptr;
+    bool paired = false;
+    uint64_t n = 0;                              // pairs, or single reads
+    lcty::Slice F;                               // the inflated blocks of the call and the records walked in them
+    lcty::DevBuf<uint32_t> d_len, d_nm, d_src; lcty::DevBuf<uint64_t> d_off, d_bases;
+    uint64_t n_units = 0;
+    std::vector<uint32_t> h_len, h_src, h_src_stream, h_bases, h_nm;    // h_src: a mate's record among the records walked (rec_off); _stream: in the fetched stream
+    std::vector<uint64_t> h_off, zero_off;
+    bool have_bases = false;
 };
 
 namespace lcty {

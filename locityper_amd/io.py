@@ -1,5 +1,6 @@
 """ctypes wrappers of the file-format entry points of liblocityper_hip.so (lcty_io.hip): harness code for tests, bench and examples."""
 import ctypes as C
+import os
 import time
 
 import numpy as np
@@ -421,10 +422,11 @@ def write_bgzf_device(ctx, path, data):
 
 
 class SampleReads:
-    """lcty_sample_reads: the reads of one lcty_sample_bam_fetch, resident on the device."""
+    """lcty_sample_reads: the reads of one lcty_sample_bam_fetch, resident on the device; owned=False: the current chunk of a
+    BamStream, which belongs to the stream and is valid until its next next() or close()."""
 
-    def __init__(self, handle, stats):
-        self._h, self.stats = handle, stats
+    def __init__(self, handle, stats, owned=True):
+        self._h, self.stats, self._owned = handle, stats, owned
 
     def view(self):
         """(cdefs.ReadsChunk of sequence fields, src_record [2 n] uint32, paired): copies."""
@@ -458,8 +460,43 @@ class SampleReads:
         rset.add_sample(self, cnt, loci)
 
     def close(self):
-        if self._h:
+        if self._h and self._owned:
             lib().lcty_sample_reads_free(self._h)
+        self._h = VP()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BamStream:
+    """lcty_bam_stream_*: whole BAM files without an index, read front to back in windows (`locityper genotype -a a.bam [-a b.bam]
+    --no-index [-^]`). Windows follow the context's knob "bam_stream_window_bytes"."""
+
+    def __init__(self, ctx, paths, interleaved=False):
+        self._h = VP()
+        self._ctx = ctx
+        self.interleaved = bool(interleaved)
+        self.stats = cdefs.BamStreamStats().as_dict()
+        paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        check(lib().lcty_bam_stream_open(ctx._h, arr, len(paths), int(self.interleaved), C.byref(self._h)))
+
+    def next(self):
+        """-> (a SampleReads that belongs to the stream: the reads, or pairs, of the next window that completes any; stats, the sums of
+        lcty_bam_stream_stats). The reads' stats["n_pairs"] is 0 at the end of the last file."""
+        h, n, st = VP(), U64(0), cdefs.BamStreamStats()
+        try:
+            check(lib().lcty_bam_stream_next(self._h, C.byref(h), C.byref(n), C.byref(st)))
+        finally:
+            self.stats = st.as_dict()
+        return SampleReads(h, dict(self.stats, n_pairs=int(n.value)), owned=False), self.stats
+
+    def close(self):
+        if self._h:
+            lib().lcty_bam_stream_close(self._h)
             self._h = VP()
 
     def __del__(self):
