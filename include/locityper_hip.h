@@ -1577,6 +1577,15 @@ typedef struct lcty_vcf_fetch_stats {
 /* host; index_path NULL: path + ".tbi". The view's n_records is 0: the file is not walked (add.rs:802) */
 int32_t lcty_vcf_indexed_open(const char* path, const char* index_path, lcty_vcf_indexed** out);
 int32_t lcty_vcf_indexed_view_get(const lcty_vcf_indexed* vcf, lcty_vcf_view* view);
+/* host: the contigs of the file in the order of their indices (htslib's get_tid, extra/into_vcf.py:170): the ##contig lines of the head in
+ * file order with their length= (0: none given), then the names of the tabix index that no line declares, length 0, as htslib adds them.
+ * names: n_contigs 0-terminated names. The arrays are the reader's and live until lcty_vcf_indexed_close. */
+typedef struct lcty_vcf_contigs {
+    uint32_t n_contigs, _pad0;
+    const char* names; uint64_t names_len;
+    const uint64_t* length;
+} lcty_vcf_contigs;
+int32_t lcty_vcf_indexed_contigs(const lcty_vcf_indexed* vcf, lcty_vcf_contigs* out);
 /* host: the merged chunks of a window (add.rs:496-499: the flanks; panvcf.rs filter_variants: the interval) */
 int32_t lcty_vcf_indexed_plan(lcty_vcf_indexed* vcf, const char* contig, uint32_t start, uint32_t end, uint64_t chunk_cap,
                               uint64_t* n_chunks, uint64_t* chunk_beg, uint64_t* chunk_end, uint64_t* blocks_total);
@@ -1694,6 +1703,183 @@ void    lcty_pafvcf_out_free(lcty_pafvcf_out* out);
  * input bytes and the empty end-of-file block. The deflate bytes are zlib's at level 6; the inflated bytes are `data`. Host code; the
  * writer is the one behind lcty_write_bam. */
 int32_t lcty_io_write_bgzf(const char* path, const uint8_t* data, uint64_t len);
+
+/* ---- a cohort's genotypes as a phased VCF (extra/into_vcf.py, extra/into_csv.py) ----------------------------------------
+ * For every locus into_vcf.py takes the records of the locus's interval from a phased variants file and, for every sample, copies the
+ * GT of the predicted haplotypes into a phased call (process_locus, into_vcf.py:117-144). Here the window is the arrays of an
+ * lcty_vcf_records (lcty_vcf_region, lcty_vcf_indexed_fetch), the predictions are columns of its GT matrix, and the text of the file is
+ * made on the device. lcty_gtvcf_merge is merge_vcfs (167-196); the table between the two scripts is lcty_res_summary_read and
+ * lcty_predictions_csv_write / _read (into_csv.py:65-100, 125; load_predictions, into_vcf.py:18-44).
+ *
+ * lcty_res_summary_read (host): the top level of one res.json.gz as process_sample reads it (into_csv.py:73-96), through the JSON reader
+ *   of lcty_bg_from_json. state: LCTY_RES_MISSING when the file does not exist (the caller's `?` row, 74-77), LCTY_RES_NO_GENOTYPE when
+ *   it has no `genotype` key (`*`, 85-87), else LCTY_RES_CALLED with genotype = the comma-joined allele names (90), qual10 =
+ *   floor(10 quality) in double arithmetic as line 91 computes it (a call without a numeric quality is LCTY_ERR_INVALID_DATA, as
+ *   float(None) raises there), reads / unexpl = total_reads / unexpl_reads, which must be whole numbers, wdist5 = weight_dist as `:.5f`
+ *   rounds it (96: the text of %.5f, read back digit by digit), LCTY_GTVCF_ABSENT for an absent, null or NaN value (get_or_nan, 60-62),
+ *   warnings = the texts joined by `;`, `*` without the key (95). A file that is no gzip or no JSON object: LCTY_ERR_INVALID_DATA.
+ *   The two strings are released with lcty_res_summary_free. In every other state they are NULL and the numbers absent. A call that
+ *   fails leaves state LCTY_RES_UNKNOWN, which lcty_predictions_csv_write refuses: a corrupt file never becomes a `?` row.
+ * lcty_predictions_csv_write (host): the table of into_csv.py:125 and one row per (sample[i], locus[i], rows[i]) in the order given (96;
+ *   `?` and `*` rows end behind the genotype column as upstream's do): quality with one decimal and weight_dist with five
+ *   (lcty_gtvcf_fixed_print with pad; absent: `nan`), the counts as integers (absent: `nan`, what Python prints for get_or_nan's value).
+ *   A name or text with a tab or a newline: LCTY_ERR_INVALID_INPUT. A path that ends in .gz is written as gzip.
+ * lcty_predictions_csv_read (host): load_predictions (into_vcf.py:18-44) and common.read_csv: lines that start with `#` before the
+ *   column line are skipped, the columns are found by name (sample, locus, genotype required; quality, total_reads, unexpl_reads,
+ *   weight_dist, warnings optional: absent for every row), a row may end early (csv.DictReader gives None: absent). Per row, in file
+ *   order: the offsets of its sample, locus, genotype (`*` or `?`: no prediction, 26-27) and warnings in `text`, a pool of 0-terminated
+ *   strings, and the four numbers in fixed point, parsed from the decimal text by lcty_gtvcf_fixed_parse's rule and never through a
+ *   double (the counts with 0 decimals). samples_off[n_samples]: the distinct sample names, sorted bytewise (44). A sample and locus that
+ *   appear twice keep the later row upstream (42); here both rows are returned and the caller takes the last. Released with
+ *   lcty_predictions_free.
+ * lcty_gtvcf_columns (host): copy_genotype's rule (into_vcf.py:99-114), applied once per predicted allele and not once per record.
+ *   names: n_names 0-terminated allele names; cols[n_names]: the column of view's GT matrix each one reads. A name longer than 2 bytes
+ *   whose second-to-last byte is `.` or `_` (102): sample = the name without its last two bytes, haplotype = the last byte as a digit
+ *   (103-104), column = hap_off[sample] + digit - 1 (106). A name equal to genome_name (107): LCTY_GTVCF_REF, allele 0 in every record
+ *   (108). Any other name: a sample, which must have ploidy 1 (110-112), column hap_off[sample]. LCTY_ERR_INVALID_DATA naming the allele:
+ *   a sample the view does not have (upstream: KeyError), a last byte that is no digit, a digit above the sample's ploidy, a name without
+ *   suffix of a sample with ploidy above 1 (the assertion of 112), and the digit 0 — a stated difference: Python would index from the end.
+ * lcty_gtvcf_fixed_print / _parse (host): the numbers of the FORMAT fields are fixed point, value x 10^decimals as an integer (decimals
+ *   <= 18; quality: 1, floor(10 q) as into_csv.py:91; weight_dist: 5, as `:.5f` of line 96), LCTY_GTVCF_ABSENT for an absent or NaN
+ *   value. print, integer arithmetic only: the integer part, then the fraction without trailing zeros, no point when nothing follows
+ *   (273 tenths: 27.3, 270: 27, 123 units of 1e-5: 0.00123), absent `.`; with pad != 0 all the decimals as `:.1f` / `:.5f` write them
+ *   (into_csv.py:96), absent `nan`. A stated difference: htslib prints FORMAT floats with %g and loses digits. Called for the size
+ *   (out NULL) and then with a buffer; no terminator is written. parse: [+-]digits[.digits], digit by digit and never through a double;
+ *   digits behind the last decimal are dropped towards minus infinity; `nan` in any case and `NA` (parse_float, into_vcf.py:14-15) are
+ *   absent; anything else, or a value of more than 18 digits, is LCTY_ERR_INVALID_DATA.
+ * lcty_gtvcf_header (host): create_vcf_header (into_vcf.py:76-96) as pysam writes it: ##fileformat=VCFv4.2, the PASS filter htslib
+ *   gives every new header, one ##contig per contig (79-83; contig_len NULL or an entry 0: no length=), the seven ##FORMAT lines in
+ *   upstream's order and wording (84-93; GQ is declared and never written, as upstream never sets it), the #CHROM line with the samples
+ *   (94-95). contigs, samples: 0-terminated names. Called for the size and then with a buffer.
+ * lcty_tbi_write (host): the tabix index of a BGZF VCF, what pysam.tabix_index(preset='vcf') leaves beside it (into_vcf.py:143, 196);
+ *   the library's first index writer. contigs: n_contigs 0-terminated names, all listed in the index; per record contig_ix, pos
+ *   (0-based) and ref_len = len(REF), sorted by (contig_ix, pos), else LCTY_ERR_INVALID_INPUT; line_off[n_records + 1]: the offset of
+ *   every record line in the inflated text and of what follows the last (lcty_gtvcf_add_locus gives them); block_off[n_blocks + 1]: the
+ *   array of lcty_bgzf_deflate over that text. The virtual offset of text offset u is block_off[u / 0xff00] << 16 | u % 0xff00. Header:
+ *   format 2, columns 1 / 2 / 0, meta `#`, skip 0. A record lies in bin reg2bin(pos, pos + max(len(REF), 1)); the chunks of a bin that
+ *   touch are one; the linear index has a 16-kb window per entry, a window without a record takes the offset before it; the pseudo-bin
+ *   37450 holds the reference's file range and record count as htslib writes them; n_no_coor 0. The file itself is BGZF
+ *   (lcty_io_write_bgzf). A record that ends beyond 2^29 needs a CSI index: LCTY_ERR_UNSUPPORTED. BCF and CSI are not written.
+ * lcty_gtvcf_create: a set for the loci of one cohort, on ctx, which outlives it. samples: n_samples 0-terminated names in the order of
+ *   the output columns (load_predictions sorts them bytewise, into_vcf.py:44; the order is the caller's). field_mask: the features that
+ *   follow GT, LCTY_GTVCF_QUAL .. _WARN. LCTY_GTVCF_ALL is the default. Upstream's load_predictions tests `'qual' in row` and `'warn' in
+ *   row` (31, 39) against a table whose columns are `quality` and `warnings`, and so writes reads:unexpl:wdist alone: that is
+ *   LCTY_GTVCF_UPSTREAM. Bits beyond LCTY_GTVCF_ALL, a name that is empty or holds a tab or a newline: LCTY_ERR_INVALID_INPUT. More than
+ *   65 535 x 256 samples: LCTY_ERR_UNSUPPORTED. The set
+ *   keeps the names, the FORMAT key, the device scratch of its calls and, on the device, what lcty_gtvcf_merge needs of every locus
+ *   added: its records, 2 bytes per (record, predicted allele) and the feature text of every sample.
+ * lcty_gtvcf_add_locus (device): the file of one locus (process_locus, 117-144), header and one line per record:
+ *     chrom \t pos + 1 \t ID \t REF \t ALT[,ALT..] \t . \t . \t . \t FORMAT, then one field per sample (127-142).
+ *   in: the locus's name (one locus per name, else LCTY_ERR_INVALID_INPUT), the contig's index in the variants file (get_tid, 170)
+ *   and the interval [start, end) of ref.bed, which only the merge reads; chrom and the contig's length (0: unknown; 123-124; two loci
+ *   of one contig index with different names or lengths: LCTY_ERR_INVALID_INPUT); the arrays of an lcty_vcf_records with n_haps columns, gt negative = missing;
+ *   id_off[n_recs + 1] / id_bytes, the ID column (131) — NULL or an empty ID gives `.`; the fetch of lcty_vcf_indexed_fetch and
+ *   lcty_vcf_region do not keep that column, so a caller that has only their arrays writes `.`; pred_off[n_samples + 1] / pred_col[]:
+ *   per output sample the columns of its predicted alleles from lcty_gtvcf_columns (134-138), an empty range = no prediction (`*`, `?`
+ *   or a sample the table does not have for this locus: 135-136); qual10, reads, unexpl, wdist5 [n_samples]: the features in fixed
+ *   point, LCTY_GTVCF_ABSENT = absent (any of the four arrays NULL: absent for every sample); warn_off[n_samples + 1] / warn: the warning
+ *   texts (NULL or an empty text: absent). A record with one allele has ALT `.`. A sample with a prediction: its alleles joined by `|`
+ *   (139), `.` for a missing one (106, 113), then `:` and the value of every feature of field_mask, `.` for an absent one; a sample
+ *   without: the one byte `.`. Features of samples without a prediction are not read.
+ *   Kernels (lcty_gtvcf.hip), no host loop over records, samples or cells behind the check of the arguments: one lane per (record, slot)
+ *   gathers call = pred_col == LCTY_GTVCF_REF ? 0 : gt[rec][pred_col] into calls[n_recs][n_slots], consecutive lanes on consecutive
+ *   slots of one record; one lane per sample sizes and writes the feature text, which is the same in every record; a workgroup per
+ *   record sums the line's length, a 64-bit scan places the lines, and a workgroup per line writes it with a scan of the field widths
+ *   per 256 samples (the helpers of lcty_pafvcf.hip's text stage, lcty_text.hpp). The text is downloaded once.
+ *   out: text = header + lines, line_off[n_lines + 1] the offset of every record line in text and text_len behind the last (what a
+ *   tabix writer needs), calls[n_recs][n_slots] with in->want_calls (else NULL). Released with lcty_gtvcf_out_free.
+ *   LCTY_ERR_INVALID_INPUT: null arguments, offsets that decrease, a record without an allele, a column beyond n_haps.
+ *   LCTY_ERR_INVALID_DATA: a call that names an allele its record does not have; a warning text with a tab, a space, a newline or `:`
+ *   (naming the sample). LCTY_ERR_UNSUPPORTED: a line of 2^32 bytes or more, more than 255 predicted alleles in one sample, a warning
+ *   text above 65 535 bytes, more than 65 535 x 256 predicted alleles over all samples, 2^31 records, feature texts that may reach
+ *   2^31 bytes over all samples (94 bytes per predicted sample plus the warning texts). A failed call
+ *   leaves *out zeroed and the set as it was.
+ * lcty_gtvcf_merge (device): merge_vcfs (167-196) over all loci added so far: one file with every record once. The loci are taken in
+ *   the order (contig index, start, end) (176), whatever the order they were added in; a record's key is (contig index, pos, the tuple
+ *   of its allele strings) (181); the lines come out in the order of the keys (192), tuples compared as Python compares them: element
+ *   by element, bytewise, a proper prefix first. The header lists the contigs of the loci in index order with their lengths (169-172,
+ *   189). Records of one key are joined (merge_vars, 153-164). Upstream cannot execute that branch — it reads GQ, which is never set,
+ *   and qual, which its table never gives — so the rule is this library's own: per sample, the first record in the order of the loci
+ *   keeps its field; a later record replaces it iff the sample has a prediction there and either had none so far, or the GTs differ
+ *   and the later locus's quality in whole units (floor) is strictly larger; an absent quality is the lowest. ID, REF and ALT are the
+ *   first record's (upstream asserts equal IDs, 154). Kernels: a stable radix sort (lcty_sort.hpp) of contig << 32 | pos over all
+ *   records; one wavefront per run of equal (contig, pos), a lane per record, which ranks the run by allele bytes and marks the records
+ *   that open a key; one lane per (line, sample) for the join; the text kernels of lcty_gtvcf_add_locus, each sample's field read from
+ *   the record the join chose. out: text, line_off as above; the n_contigs names of the header (contigs, 0-terminated) and per line
+ *   line_contig, line_pos, line_ref_len. line_contig[i] is the place of the line's contig among `contigs` (0 .. n_contigs - 1), NOT
+ *   the index in the variants file, which may be sparse (loci on contigs 0, 6 and 21 give 0, 1, 2): contigs, line_contig, line_pos,
+ *   line_ref_len and line_off go to lcty_tbi_write as they are. contig_ix[n_contigs]: the variants file's index of every header
+ *   contig. stats: the sort, the runs and the join are merge_ms; n_joined: the records joined to another, upstream's "Merged N variants" (184, 187). A run of more than 64
+ *   records at one position: LCTY_ERR_UNSUPPORTED naming it. The set stays as it was; more loci may be added and merged again. */
+#define LCTY_GTVCF_REF      0xFFFFFFFFu   /* a column of lcty_gtvcf_columns: the reference genome itself, allele 0 everywhere */
+#define LCTY_GTVCF_ABSENT   INT64_MIN     /* a fixed-point feature that is absent or NaN */
+#define LCTY_GTVCF_QUAL     1u
+#define LCTY_GTVCF_READS    2u
+#define LCTY_GTVCF_UNEXPL   4u
+#define LCTY_GTVCF_WDIST    8u
+#define LCTY_GTVCF_WARN     16u
+#define LCTY_GTVCF_ALL      31u
+#define LCTY_GTVCF_UPSTREAM 14u           /* reads:unexpl:wdist, what into_vcf.py writes */
+typedef struct lcty_gtvcf lcty_gtvcf;
+typedef struct lcty_gtvcf_locus_in {
+    const char* locus; const char* chrom; uint64_t contig_len;
+    uint32_t contig_ix, start, end, _pad0;
+    uint32_t n_recs, n_haps;
+    const uint32_t* pos; const uint32_t* ref_len; const uint32_t* rec_allele; const uint64_t* allele_off; const uint8_t* allele_bytes; const int16_t* gt;
+    const uint64_t* id_off; const uint8_t* id_bytes;
+    const uint32_t* pred_off; const uint32_t* pred_col;
+    const int64_t* qual10; const int64_t* reads; const int64_t* unexpl; const int64_t* wdist5;
+    const uint64_t* warn_off; const char* warn;
+    int32_t want_calls, _pad1;
+} lcty_gtvcf_locus_in;
+typedef struct lcty_gtvcf_stats {
+    uint64_t n_records, n_samples, n_slots, n_predicted, header_bytes, text_bytes, bytes_h2d, bytes_d2h;
+    /* wall time per stage with the stream drained at its end */
+    double   upload_ms, cells_ms, merge_ms, widths_ms, write_ms, download_ms, total_ms;
+} lcty_gtvcf_stats;
+typedef struct lcty_gtvcf_out {
+    char* text; uint64_t text_len;
+    uint64_t* line_off; uint64_t n_lines;
+    int16_t* calls; uint64_t n_slots;                               /* lcty_gtvcf_add_locus with want_calls */
+    /* lcty_gtvcf_merge: per line the contig's index, pos and len(REF); the records joined to another; the contigs of the header */
+    uint32_t* line_contig; uint32_t* line_pos; uint32_t* line_ref_len; uint64_t n_joined;
+    char* contigs; uint64_t contigs_len; uint32_t n_contigs, _pad0;
+    uint32_t* contig_ix;
+    lcty_gtvcf_stats stats;
+} lcty_gtvcf_out;
+#define LCTY_RES_CALLED      0
+#define LCTY_RES_NO_GENOTYPE 1             /* the `*` row */
+#define LCTY_RES_MISSING     2             /* the `?` row */
+#define LCTY_RES_UNKNOWN     (-1)          /* what a failed lcty_res_summary_read leaves: no row may be written from it */
+typedef struct lcty_res_summary {
+    char* genotype; char* warnings;
+    int64_t qual10, reads, unexpl, wdist5;
+    int32_t state, _pad0;
+} lcty_res_summary;
+typedef struct lcty_predictions {
+    uint64_t n_rows;
+    char* text; uint64_t text_len;
+    uint64_t* sample_off; uint64_t* locus_off; uint64_t* genotype_off; uint64_t* warn_off;
+    int64_t* qual10; int64_t* reads; int64_t* unexpl; int64_t* wdist5;
+    uint64_t* samples_off; uint64_t n_samples;
+} lcty_predictions;
+int32_t lcty_res_summary_read(const char* path, lcty_res_summary* out);
+void    lcty_res_summary_free(lcty_res_summary* out);
+int32_t lcty_predictions_csv_write(const char* path, uint64_t n_rows, const char* const* sample, const char* const* locus, const lcty_res_summary* rows);
+int32_t lcty_predictions_csv_read(const char* path, lcty_predictions* out);
+void    lcty_predictions_free(lcty_predictions* out);
+int32_t lcty_gtvcf_columns(const lcty_vcf_view* view, const char* genome_name, uint32_t n_names, const char* names, uint32_t* cols);
+int32_t lcty_gtvcf_fixed_print(int64_t value, uint32_t decimals, int32_t pad, char* out, uint64_t cap, uint64_t* len);
+int32_t lcty_gtvcf_fixed_parse(const char* text, uint32_t decimals, int64_t* value);
+int32_t lcty_gtvcf_header(uint32_t n_contigs, const char* contigs, const uint64_t* contig_len, uint32_t n_samples, const char* samples,
+                          char* out, uint64_t cap, uint64_t* len);
+int32_t lcty_tbi_write(const char* path, uint32_t n_contigs, const char* contigs, uint64_t n_records, const uint32_t* contig_ix,
+                       const uint32_t* pos, const uint32_t* ref_len, const uint64_t* line_off, const uint64_t* block_off, uint64_t n_blocks);
+int32_t lcty_gtvcf_create(lcty_ctx* ctx, const char* samples, uint32_t n_samples, uint32_t field_mask, lcty_gtvcf** out);
+void    lcty_gtvcf_destroy(lcty_gtvcf* set);
+int32_t lcty_gtvcf_add_locus(lcty_gtvcf* set, const lcty_gtvcf_locus_in* in, lcty_gtvcf_out* out);
+int32_t lcty_gtvcf_merge(lcty_gtvcf* set, lcty_gtvcf_out* out);
+void    lcty_gtvcf_out_free(lcty_gtvcf_out* out);
 
 /* ---- basis haplotypes (locityper augment, the basis step: DB/loci/<locus>/haplotypes-basis[.TAG].fa.gz) ------------------------------
  * construct_dominant_set -> inner_construct_dominant_set -> Cigar::locally_similar -> find_dominating_set (src/command/augment.rs:258-396,

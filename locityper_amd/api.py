@@ -1474,6 +1474,212 @@ def paf_to_vcf(ctx, names, seqs, seq_off, entries, ref_hap, discarded=None, regi
         lib().lcty_pafvcf_out_free(C.byref(o))
 
 
+# ---- a cohort's genotypes as a phased VCF (extra/into_vcf.py; lcty_gtvcf.hip) --------------------------------------------------------
+def gtvcf_columns(samples, ploidy, genome_name, alleles):
+    """lcty_gtvcf_columns (copy_genotype's rule): the column of the GT matrix every predicted allele reads (cdefs.GTVCF_REF: the genome).
+    samples, ploidy: the variants file's (Vcf.view)."""
+    from .io import _names_blob
+    sb = _names_blob(samples)
+    pl = np.ascontiguousarray(ploidy, dtype=np.uint32)
+    off = np.zeros(len(pl) + 1, dtype=np.uint32)
+    np.cumsum(pl, out=off[1:])
+    buf = C.create_string_buffer(sb, len(sb) + 1)
+    view = cdefs.VcfView(len(pl), int(off[-1]), 0, C.cast(buf, C.c_void_p), len(sb), pl.ctypes.data, off.ctypes.data)
+    cols = np.zeros(max(len(alleles), 1), dtype=np.uint32)
+    g = genome_name.encode() if isinstance(genome_name, str) else bytes(genome_name)
+    check(lib().lcty_gtvcf_columns(C.byref(view), g, len(alleles), _names_blob(alleles), cols.ctypes.data))
+    return cols[:len(alleles)]
+
+
+def gtvcf_fixed_print(value, decimals, pad=False):
+    """lcty_gtvcf_fixed_print: a fixed-point value (cdefs.GTVCF_ABSENT: absent) as bytes."""
+    n = U64()
+    buf = C.create_string_buffer(64)
+    check(lib().lcty_gtvcf_fixed_print(int(value), decimals, int(pad), C.cast(buf, C.c_void_p), 64, C.byref(n)))
+    return buf.raw[:n.value]
+
+
+def gtvcf_fixed_parse(text, decimals):
+    """lcty_gtvcf_fixed_parse: decimal text -> value x 10^decimals (cdefs.GTVCF_ABSENT for nan / NA)."""
+    v = C.c_int64()
+    check(lib().lcty_gtvcf_fixed_parse(text.encode() if isinstance(text, str) else bytes(text), decimals, C.byref(v)))
+    return int(v.value)
+
+
+def gtvcf_header(contigs, samples):
+    """lcty_gtvcf_header: contigs = [(name, length or None)] -> the header's bytes."""
+    from .io import _names_blob
+    ln = np.array([0 if l is None else l for _, l in contigs] + [0], dtype=np.uint64)
+    cb, sb = _names_blob([c for c, _ in contigs]), _names_blob(samples)
+    n = U64()
+    check(lib().lcty_gtvcf_header(len(contigs), cb, ln.ctypes.data, len(samples), sb, None, 0, C.byref(n)))
+    buf = C.create_string_buffer(int(n.value) + 1)
+    check(lib().lcty_gtvcf_header(len(contigs), cb, ln.ctypes.data, len(samples), sb, C.cast(buf, C.c_void_p), n.value, C.byref(n)))
+    return buf.raw[:n.value]
+
+
+def tbi_write(path, contigs, contig_ix, pos, ref_len, line_off, block_off):
+    """lcty_tbi_write: the tabix index of a BGZF VCF whose text was cut every 0xff00 bytes (io.bgzf_deflate's block_off)."""
+    from .io import _names_blob
+    ci, ps, rl = (np.ascontiguousarray(a, dtype=np.uint32) for a in (contig_ix, pos, ref_len))
+    lo, bo = np.ascontiguousarray(line_off, dtype=np.uint64), np.ascontiguousarray(block_off, dtype=np.uint64)
+    if len(lo) != len(ps) + 1 or len(bo) < 1:
+        raise ValueError("line_off has one entry more than the records, block_off at least one")
+    check(lib().lcty_tbi_write(str(path).encode(), len(contigs), _names_blob(contigs), len(ps), ci.ctypes.data, ps.ctypes.data, rl.ctypes.data, lo.ctypes.data,
+                               bo.ctypes.data, len(bo) - 1))
+
+
+def res_summary_read(path):
+    """lcty_res_summary_read: the top level of a res.json.gz as into_csv.py reads it. A dict: state (cdefs.RES_CALLED / RES_NO_GENOTYPE /
+    RES_MISSING), genotype and warnings (bytes or None), qual10, reads, unexpl, wdist5 (int, None when absent)."""
+    o = cdefs.ResSummary()
+    check(lib().lcty_res_summary_read(str(path).encode(), C.byref(o)))
+    try:
+        num = {k: (None if getattr(o, k) == cdefs.GTVCF_ABSENT else int(getattr(o, k))) for k in ("qual10", "reads", "unexpl", "wdist5")}
+        return dict(state=int(o.state), genotype=C.string_at(o.genotype) if o.genotype else None,
+                    warnings=C.string_at(o.warnings) if o.warnings else None, **num)
+    finally:
+        lib().lcty_res_summary_free(C.byref(o))
+
+
+def predictions_csv_write(path, rows):
+    """lcty_predictions_csv_write: rows = [(sample, locus, summary)], summary a dict of res_summary_read."""
+    def b(x):
+        return x.encode() if isinstance(x, str) else bytes(x)
+    n = len(rows)
+    samples = (C.c_char_p * max(n, 1))(*[b(r[0]) for r in rows])
+    loci = (C.c_char_p * max(n, 1))(*[b(r[1]) for r in rows])
+    arr = (cdefs.ResSummary * max(n, 1))()
+    keep = []
+    for a, (_, _, s) in zip(arr, rows):
+        a.state = s["state"]
+        for k in ("qual10", "reads", "unexpl", "wdist5"):
+            setattr(a, k, cdefs.GTVCF_ABSENT if s.get(k) is None else s[k])
+        for k in ("genotype", "warnings"):
+            if s.get(k) is not None:
+                keep.append(C.create_string_buffer(b(s[k])))
+                setattr(a, k, C.cast(keep[-1], C.c_void_p))
+    check(lib().lcty_predictions_csv_write(str(path).encode(), n, C.cast(samples, C.c_void_p), C.cast(loci, C.c_void_p), C.cast(arr, C.c_void_p)))
+
+
+def predictions_csv_read(path):
+    """lcty_predictions_csv_read (load_predictions): a dict of samples (sorted bytewise) and rows = [dict(sample, locus, genotype, warnings,
+    qual10, reads, unexpl, wdist5)] in file order; genotype b"*" / b"?" = no prediction."""
+    o = cdefs.Predictions()
+    check(lib().lcty_predictions_csv_read(str(path).encode(), C.byref(o)))
+    try:
+        n = int(o.n_rows)
+        text = C.string_at(o.text, o.text_len)
+
+        def at(off):
+            return text[off:text.index(b"\0", off)]
+        cols = {k: _take(getattr(o, k), n, np.uint64) for k in ("sample_off", "locus_off", "genotype_off", "warn_off")}
+        nums = {k: _take(getattr(o, k), n, np.int64) for k in ("qual10", "reads", "unexpl", "wdist5")}
+        rows = []
+        for i in range(n):
+            r = dict(sample=at(int(cols["sample_off"][i])), locus=at(int(cols["locus_off"][i])), genotype=at(int(cols["genotype_off"][i])),
+                     warnings=at(int(cols["warn_off"][i])))
+            r.update({k: (None if int(v[i]) == cdefs.GTVCF_ABSENT else int(v[i])) for k, v in nums.items()})
+            rows.append(r)
+        return dict(samples=[at(int(x)) for x in _take(o.samples_off, int(o.n_samples), np.uint64)], rows=rows)
+    finally:
+        lib().lcty_predictions_free(C.byref(o))
+
+
+class GenotypeVcf:
+    """lcty_gtvcf_create / _add_locus / _destroy: the VCF files of a cohort's loci, samples in the order given."""
+
+    def __init__(self, ctx, samples, field_mask=cdefs.GTVCF_ALL):
+        from .io import _names_blob
+        self._h = C.c_void_p()
+        self.ctx, self.n_samples = ctx, len(samples)
+        check(lib().lcty_gtvcf_create(ctx._h, _names_blob(samples), len(samples), field_mask, C.byref(self._h)))
+
+    def add_locus(self, chrom, contig_len, recs, gt, preds, ids=None, feats=None, warns=None, want_calls=False, locus=None, contig_ix=0, start=0, end=0):
+        """recs: the dict of Vcf.region / VcfIndexed.fetch (pos, ref_len, rec_allele, allele_off, allele_bytes); gt [n_recs][n_haps] int16;
+        preds: per sample the columns of gtvcf_columns ([] = no prediction); ids: per record bytes or None; feats: {"qual10" | "reads" |
+        "unexpl" | "wdist5": per sample int or None}; warns: per sample bytes; locus (default: a running number), contig_ix, start, end:
+        the locus's name and place, for merge(). Returns a dict: text, line_off, calls (want_calls), stats."""
+        i = cdefs.GtvcfLocusIn()
+        keep = []
+        name = ("locus%d" % (getattr(self, "_n_added", 0) + 1)) if locus is None else locus
+        i.locus = name.encode() if isinstance(name, str) else bytes(name)
+        i.contig_ix, i.start, i.end = contig_ix, start, end
+
+        def arr(a, dtype, pad=1):
+            a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+            a = np.concatenate([a, np.zeros(pad, dtype=dtype)]) if pad else a
+            keep.append(a)
+            return a.ctypes.data
+
+        def csr(items):
+            off = np.zeros(len(items) + 1, dtype=np.uint64)
+            np.cumsum([len(x) for x in items], out=off[1:])
+            return off, np.frombuffer(b"".join(bytes(x) for x in items), dtype=np.uint8)
+
+        i.chrom = chrom.encode() if isinstance(chrom, str) else bytes(chrom)
+        i.contig_len = int(contig_len or 0)
+        pos = np.ascontiguousarray(recs["pos"], dtype=np.uint32)
+        g = np.ascontiguousarray(gt, dtype=np.int16)
+        if g.ndim != 2:
+            g = g.reshape(len(pos), -1) if len(pos) else g.reshape(0, 0)
+        if g.shape[0] != len(pos):
+            raise ValueError("gt has one row per record")
+        i.n_recs, i.n_haps = len(pos), g.shape[1]
+        i.pos, i.gt, i.ref_len = arr(pos, np.uint32), arr(g, np.int16), arr(recs["ref_len"], np.uint32)
+        i.rec_allele, i.allele_off = arr(recs["rec_allele"], np.uint32, 0), arr(recs["allele_off"], np.uint64, 0)
+        i.allele_bytes = arr(recs["allele_bytes"], np.uint8)
+        if ids is not None:
+            off, b = csr([x or b"" for x in ids])
+            i.id_off, i.id_bytes = arr(off, np.uint64, 0), arr(b, np.uint8)
+        if len(preds) != self.n_samples:
+            raise ValueError("one prediction per sample")
+        poff = np.zeros(self.n_samples + 1, dtype=np.uint32)
+        np.cumsum([len(p) for p in preds], out=poff[1:])
+        i.pred_off = arr(poff, np.uint32, 0)
+        i.pred_col = arr([c for p in preds for c in p], np.uint32)
+        for key, vals in (feats or {}).items():
+            setattr(i, key, arr([cdefs.GTVCF_ABSENT if v is None else v for v in vals], np.int64, 0))
+        if warns is not None:
+            off, b = csr(warns)
+            i.warn_off, i.warn = arr(off, np.uint64, 0), arr(b, np.uint8)
+        i.want_calls = int(want_calls)
+        o = cdefs.GtvcfOut()
+        check(lib().lcty_gtvcf_add_locus(self._h, C.byref(i), C.byref(o)))
+        self._n_added = getattr(self, "_n_added", 0) + 1
+        try:
+            out = {"text": C.string_at(o.text, o.text_len), "line_off": _take(o.line_off, int(o.n_lines) + 1, np.uint64), "stats": o.stats.as_dict()}
+            if want_calls:
+                out["calls"] = _take(o.calls, int(o.n_lines) * int(o.n_slots), np.int16).reshape(int(o.n_lines), int(o.n_slots))
+            return out
+        finally:
+            lib().lcty_gtvcf_out_free(C.byref(o))
+
+    def merge(self):
+        """lcty_gtvcf_merge over the loci added so far: a dict of text, line_off, contigs (names of the header), line_contig (every line's
+        place among `contigs`), line_pos, line_ref_len (what tbi_write takes), contig_ix (the variants file's index of every header contig),
+        n_joined, stats."""
+        o = cdefs.GtvcfOut()
+        check(lib().lcty_gtvcf_merge(self._h, C.byref(o)))
+        try:
+            n = int(o.n_lines)
+            return {"text": C.string_at(o.text, o.text_len), "line_off": _take(o.line_off, n + 1, np.uint64), "n_joined": int(o.n_joined),
+                    "contigs": C.string_at(o.contigs, o.contigs_len).split(b"\0")[:-1] if o.contigs_len else [],
+                    "line_contig": _take(o.line_contig, n, np.uint32), "line_pos": _take(o.line_pos, n, np.uint32),
+                    "line_ref_len": _take(o.line_ref_len, n, np.uint32), "contig_ix": _take(o.contig_ix, int(o.n_contigs), np.uint32),
+                    "stats": o.stats.as_dict()}
+        finally:
+            lib().lcty_gtvcf_out_free(C.byref(o))
+
+    def close(self):
+        if self._h:
+            lib().lcty_gtvcf_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
 def _leave_out_mask(n_alleles, leave_out):
     if leave_out is None or len(leave_out) == 0:
         return None

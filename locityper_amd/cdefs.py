@@ -184,6 +184,50 @@ class PafvcfOut(C.Structure):
                [("merged", C.c_void_p), ("merged_len", C.c_uint64), ("separate", C.c_void_p), ("separate_len", C.c_uint64), ("stats", PafvcfStats)]
 
 
+# ---- a cohort's genotypes as a phased VCF (lcty_gtvcf.hip) ----
+GTVCF_REF = 0xFFFFFFFF
+GTVCF_ABSENT = -(1 << 63)
+GTVCF_QUAL, GTVCF_READS, GTVCF_UNEXPL, GTVCF_WDIST, GTVCF_WARN = 1, 2, 4, 8, 16
+GTVCF_ALL, GTVCF_UPSTREAM = 31, 14
+
+
+class GtvcfLocusIn(C.Structure):
+    _fields_ = [("locus", C.c_char_p), ("chrom", C.c_char_p), ("contig_len", C.c_uint64), ("contig_ix", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32),
+                ("_pad0", C.c_uint32), ("n_recs", C.c_uint32), ("n_haps", C.c_uint32)] + \
+               [(n, C.c_void_p) for n in ("pos", "ref_len", "rec_allele", "allele_off", "allele_bytes", "gt", "id_off", "id_bytes", "pred_off", "pred_col", "qual10",
+                                          "reads", "unexpl", "wdist5", "warn_off", "warn")] + \
+               [("want_calls", C.c_int32), ("_pad1", C.c_int32)]
+
+
+class GtvcfStats(_Dictable):
+    _fields_ = [(n, C.c_uint64) for n in ("n_records", "n_samples", "n_slots", "n_predicted", "header_bytes", "text_bytes", "bytes_h2d", "bytes_d2h")] + \
+               [(n, C.c_double) for n in ("upload_ms", "cells_ms", "merge_ms", "widths_ms", "write_ms", "download_ms", "total_ms")]
+
+
+class GtvcfOut(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_len", C.c_uint64), ("line_off", C.c_void_p), ("n_lines", C.c_uint64), ("calls", C.c_void_p),
+                ("n_slots", C.c_uint64), ("line_contig", C.c_void_p), ("line_pos", C.c_void_p), ("line_ref_len", C.c_void_p), ("n_joined", C.c_uint64),
+                ("contigs", C.c_void_p), ("contigs_len", C.c_uint64), ("n_contigs", C.c_uint32), ("_pad0", C.c_uint32), ("contig_ix", C.c_void_p), ("stats", GtvcfStats)]
+
+
+RES_CALLED, RES_NO_GENOTYPE, RES_MISSING, RES_UNKNOWN = 0, 1, 2, -1
+
+
+class VcfContigs(C.Structure):
+    _fields_ = [("n_contigs", C.c_uint32), ("_pad0", C.c_uint32), ("names", C.c_void_p), ("names_len", C.c_uint64), ("length", C.c_void_p)]
+
+
+class ResSummary(C.Structure):
+    _fields_ = [("genotype", C.c_void_p), ("warnings", C.c_void_p)] + [(n, C.c_int64) for n in ("qual10", "reads", "unexpl", "wdist5")] + \
+               [("state", C.c_int32), ("_pad0", C.c_int32)]
+
+
+class Predictions(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("text", C.c_void_p), ("text_len", C.c_uint64)] + \
+               [(n, C.c_void_p) for n in ("sample_off", "locus_off", "genotype_off", "warn_off", "qual10", "reads", "unexpl", "wdist5", "samples_off")] + \
+               [("n_samples", C.c_uint64)]
+
+
 class ExpandOut(_Dictable):
     _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("attempt", C.c_int32), ("allowed_expansion", C.c_uint32), ("n_attempts", C.c_uint32),
                 ("crop_bits", C.c_uint32), ("total_ms", C.c_double)]

@@ -23,6 +23,7 @@
 #include "lcty_bg_reads.hpp"
 #include "lcty_bgzf.hpp"
 #include "lcty_common.hpp"
+#include "lcty_gtvcf_host.hpp"
 #include "lcty_seq.hpp"
 #include "lcty_bgzf_index.hpp"
 
@@ -529,6 +530,123 @@ int32_t lcty_res_to_json(const lcty_call* call, const uint16_t* genotypes, uint3
         if (out && cap >= *needed) memcpy(out, j.c_str(), j.size() + 1);
         else if (out) fail(LCTY_ERR_INVALID_INPUT, "output buffer too small (%llu < %llu)", static_cast<unsigned long long>(cap), static_cast<unsigned long long>(*needed));
     });
+}
+
+// The top level of a res.json.gz as process_sample reads it (extra/into_csv.py:73-96), numbers in the fixed point of lcty_gtvcf_*.
+int32_t lcty_res_summary_read(const char* path, lcty_res_summary* out) {
+    return guarded([&] {
+        if (out) { memset(out, 0, sizeof(*out)); out->qual10 = out->reads = out->unexpl = out->wdist5 = LCTY_GTVCF_ABSENT; out->state = LCTY_RES_UNKNOWN; }
+        if (!path || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        if (access(path, F_OK) != 0) { out->state = LCTY_RES_MISSING; return; }   // 74-77: the `?` row
+        const std::vector<uint8_t> raw = read_whole_file(path);
+        if (raw.size() < 2 || raw[0] != 0x1f || raw[1] != 0x8b) fail(LCTY_ERR_INVALID_DATA, "%s: not a gzip file", path);
+        const std::vector<uint8_t> text = inflate_gzip(raw, path);
+        JsonParser jp{reinterpret_cast<const char*>(text.data()), reinterpret_cast<const char*>(text.data()) + text.size(), text.size()};
+        const Json root = jp.value();
+        if (root.kind != Json::Obj) fail(LCTY_ERR_INVALID_DATA, "%s: not a JSON object", path);
+        const Json* gt = root.get("genotype");
+        if (!gt) { out->state = LCTY_RES_NO_GENOTYPE; return; }               // 85-87: the `*` row
+        if (gt->kind != Json::Str) fail(LCTY_ERR_INVALID_DATA, "%s: `genotype` is not a string", path);
+        // get_or_nan (60-62): a missing key or null is NaN
+        auto number = [&](const char* key) -> const Json* {
+            const Json* v = root.get(key);
+            if (!v || v->kind == Json::Null) return nullptr;
+            if (v->kind != Json::Num) fail(LCTY_ERR_INVALID_DATA, "%s: `%s` is not a number", path, key);
+            return std::isnan(v->num) ? nullptr : v;
+        };
+        auto in_range = [&](double x, const char* key) { if (!(std::fabs(x) < 9e17)) fail(LCTY_ERR_INVALID_DATA, "%s: `%s` = %g is out of range", path, key, x); };
+        const Json* q = root.get("quality");
+        if (!q || q->kind != Json::Num) fail(LCTY_ERR_INVALID_DATA, "%s: a genotype without a numeric `quality`", path);      // 91: float(None) raises
+        int64_t qual10 = LCTY_GTVCF_ABSENT;
+        if (!std::isnan(q->num)) { const double t = std::floor(10.0 * q->num); in_range(t, "quality"); qual10 = static_cast<int64_t>(t); }
+        auto count = [&](const char* key) -> int64_t {
+            const Json* v = number(key);
+            if (!v) return LCTY_GTVCF_ABSENT;
+            in_range(v->num, key);
+            if (v->num != std::floor(v->num)) fail(LCTY_ERR_INVALID_DATA, "%s: `%s` = %g is not a whole number", path, key, v->num);
+            return static_cast<int64_t>(v->num);
+        };
+        const int64_t reads = count("total_reads"), unexpl = count("unexpl_reads");
+        int64_t wdist5 = LCTY_GTVCF_ABSENT;
+        if (const Json* w = number("weight_dist")) {                          // 96: `:.5f`, the text read back digit by digit
+            in_range(w->num * 1e5, "weight_dist");
+            char buf[64];
+            snprintf(buf, sizeof(buf), "%.5f", w->num);
+            wdist5 = gtvcf::fixed_parse(buf, gtvcf::WDIST_DECIMALS);
+        }
+        std::string warnings = "*";                                           // 95: ';'.join(res.get('warnings', '*'))
+        if (const Json* w = root.get("warnings")) {
+            if (w->kind != Json::Arr) fail(LCTY_ERR_INVALID_DATA, "%s: `warnings` is not an array", path);
+            warnings.clear();
+            for (size_t i = 0; i < w->arr.size(); i++) {
+                if (w->arr[i].kind != Json::Str) fail(LCTY_ERR_INVALID_DATA, "%s: a warning is not a string", path);
+                if (i) warnings += ';';
+                warnings += w->arr[i].str;
+            }
+        }
+        Handoff h;
+        out->genotype = h.copy(gt->str.c_str(), gt->str.size() + 1);
+        out->warnings = h.copy(warnings.c_str(), warnings.size() + 1);
+        out->qual10 = qual10; out->reads = reads; out->unexpl = unexpl; out->wdist5 = wdist5; out->state = LCTY_RES_CALLED;
+        h.commit();
+    });
+}
+
+void lcty_res_summary_free(lcty_res_summary* out) {
+    if (!out) return;
+    free(out->genotype); free(out->warnings);
+    out->genotype = out->warnings = nullptr;
+}
+
+int32_t lcty_predictions_csv_write(const char* path, uint64_t n_rows, const char* const* sample, const char* const* locus, const lcty_res_summary* rows) {
+    return guarded([&] {
+        if (!path || (n_rows && (!sample || !locus || !rows))) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        const std::string text = gtvcf::predictions_csv_text(n_rows, sample, locus, rows);
+        if (has_suffix(path, ".gz")) {
+            const int32_t rc = lcty_io_write_gz(path, reinterpret_cast<const uint8_t*>(text.data()), text.size());
+            if (rc != LCTY_OK) throw Error(rc, lcty_last_error());
+            return;
+        }
+        FILE* f = fopen(path, "wb");
+        if (!f) fail(LCTY_ERR_INVALID_INPUT, "cannot create %s", path);
+        const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+        if (fclose(f) != 0 || !ok) fail(LCTY_ERR_RUNTIME, "write error on %s", path);
+    });
+}
+
+int32_t lcty_predictions_csv_read(const char* path, lcty_predictions* out) {
+    return guarded([&] {
+        if (out) memset(out, 0, sizeof(*out));
+        if (!path || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        std::vector<uint8_t> raw = read_whole_file(path);
+        if (raw.size() >= 2 && raw[0] == 0x1f && raw[1] == 0x8b) raw = inflate_gzip(raw, path);                              // common.open
+        const gtvcf::PredictionTable T = gtvcf::predictions_csv_parse(std::string(raw.begin(), raw.end()), path);
+        const size_t n = T.rows.size();
+        std::string pool;
+        auto keep = [&](const std::string& s) { const uint64_t at = pool.size(); pool += s; pool.push_back('\0'); return at; };
+        std::vector<uint64_t> so(n), lo(n), go(n), wo(n), names(T.samples.size());
+        std::vector<int64_t> q(n), r(n), u(n), w(n);
+        for (size_t i = 0; i < T.samples.size(); i++) names[i] = keep(T.samples[i]);
+        for (size_t i = 0; i < n; i++) {
+            const gtvcf::PredictionRow& R = T.rows[i];
+            so[i] = names[size_t(std::lower_bound(T.samples.begin(), T.samples.end(), R.sample) - T.samples.begin())];
+            lo[i] = keep(R.locus); go[i] = keep(R.genotype); wo[i] = keep(R.warnings);
+            q[i] = R.qual10; r[i] = R.reads; u[i] = R.unexpl; w[i] = R.wdist5;
+        }
+        Handoff h;
+        out->text = reinterpret_cast<char*>(h.bytes(pool)); out->text_len = pool.size();
+        out->sample_off = h.copy(so); out->locus_off = h.copy(lo); out->genotype_off = h.copy(go); out->warn_off = h.copy(wo);
+        out->qual10 = h.copy(q); out->reads = h.copy(r); out->unexpl = h.copy(u); out->wdist5 = h.copy(w);
+        out->samples_off = h.copy(names); out->n_samples = names.size(); out->n_rows = n;
+        h.commit();
+    });
+}
+
+void lcty_predictions_free(lcty_predictions* out) {
+    if (!out) return;
+    free(out->text); free(out->sample_off); free(out->locus_off); free(out->genotype_off); free(out->warn_off);
+    free(out->qual10); free(out->reads); free(out->unexpl); free(out->wdist5); free(out->samples_off);
+    memset(out, 0, sizeof(*out));
 }
 
 // The record stream of OUT/loci/<locus>/aln.bam (name-grouped, mates mapped as independent single-end reads, genotype.rs:975-977)

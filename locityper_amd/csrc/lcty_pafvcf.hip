@@ -15,6 +15,7 @@
 #include "lcty_device.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
+#include "lcty_text.hpp"
 
 namespace {
 
@@ -390,9 +391,7 @@ __global__ __launch_bounds__(WG) void pafvcf_assign_kernel(uint32_t n_seqs, uint
 
 // ---- device: text ---------------------------------------------------------------------------------------------------------------------
 
-__device__ inline uint32_t n_digits(uint64_t x) { uint32_t d = 1; while (x >= 10) { x /= 10; d++; } return d; }
-__device__ inline void put_digits(char* at, uint64_t x, uint32_t d) { for (uint32_t i = d; i-- > 0;) { at[i] = char('0' + x % 10); x /= 10; } }
-
+// digits, the workgroup's sum and the place of a thread's bytes: lcty_text.hpp
 struct TextIn {
     const uint32_t* r_start; const uint32_t* r_end; const int32_t* ix; const uint32_t* n_alleles; const uint32_t* aoff;
     const uint32_t* a_hap; const uint32_t* a_start; const uint32_t* a_len;
@@ -404,17 +403,6 @@ __device__ inline uint32_t cell_width(const TextIn& T, uint32_t r, uint32_t s, i
     const int32_t v = hap == NONE ? CELL_NONE : T.ix[uint64_t(r) * T.n_seqs + hap];
     *value = v;
     return 1 + (v < 0 ? 1u : n_digits(uint64_t(v)));                    // the separator and "." or the allele number
-}
-
-// sum over the workgroup; every thread gets it
-__device__ inline uint64_t block_sum(uint64_t x, uint64_t* part) {
-    for (int off = WAVE / 2; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    __syncthreads();
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = x;
-    __syncthreads();
-    uint64_t t = 0;
-    for (int w = 0; w < WG / WAVE; w++) t += part[w];
-    return t;
 }
 
 #define PAFVCF_TAIL "\t60\t.\t.\tGT"
@@ -433,7 +421,7 @@ __global__ __launch_bounds__(WG) void pafvcf_linelen_kernel(TextIn T, uint64_t* 
         mine += cell_width(T, r, s, &v);
         if (v >= int32_t(na)) atomicMin(&flags[F_BADCELL], r);           // a table that is not lcty_pafvcf_table's
     }
-    const uint64_t sum = block_sum(mine, part);
+    const uint64_t sum = block_sum<WG>(mine, part);
     if (threadIdx.x == 0) {
         const uint64_t len = T.chrom_len + 1 + n_digits(uint64_t(T.r_start[r]) + T.shift + 1) + 2 + 1 + (T.r_end[r] - T.r_start[r]) + sum + TAIL_LEN + 1;
         line_len[r] = len;
@@ -446,7 +434,7 @@ __global__ __launch_bounds__(WG) void pafvcf_linelen_kernel(TextIn T, uint64_t* 
 // a scan of their widths per 256 slots.
 __global__ __launch_bounds__(WG) void pafvcf_write_kernel(TextIn T, Seqs S, const char* __restrict__ chrom, const uint64_t* __restrict__ line_off, char* __restrict__ out) {
     __shared__ uint32_t wsum[WG / WAVE];
-    const uint32_t r = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const uint32_t r = blockIdx.x, tid = threadIdx.x;
     const uint64_t o0 = line_off[r], o1 = line_off[r + 1];
     if (o0 == o1) return;                                               // the whole workgroup leaves
     char* line = out + o0;
@@ -472,14 +460,10 @@ __global__ __launch_bounds__(WG) void pafvcf_write_kernel(TextIn T, Seqs S, cons
         const uint32_t s = s0 + tid;
         int32_t v = CELL_NONE;
         const uint32_t w = s < T.n_slots ? cell_width(T, r, s, &v) : 0u;
-        const uint32_t incl = wave_scan_incl(w, AddOp{});
-        __syncthreads();
-        if (lane == WAVE - 1) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t k = 0; k < WG / WAVE; k++) { if (k < wave) before += wsum[k]; all += wsum[k]; }
+        uint32_t all = 0;
+        const uint32_t before = block_place<WG>(w, wsum, &all);
         if (s < T.n_slots) {
-            char* c = line + at + before + incl - w;
+            char* c = line + at + before;
             c[0] = T.slot_first[s] ? '\t' : '|';
             if (v < 0) c[1] = '.'; else put_digits(c + 1, uint64_t(v), w - 1);
         }

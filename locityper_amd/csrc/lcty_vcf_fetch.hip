@@ -310,6 +310,7 @@ struct lcty_vcf_indexed {
     std::string sample_blob;
     std::vector<uint32_t> ploidy, hap_off;           // of the first record of the file; hap_off[n_samples + 1]
     lcty_vcf_view view{};
+    std::vector<std::string> contigs; std::vector<uint64_t> contig_len; std::string contig_blob;      // lcty_vcf_indexed_contigs
 };
 
 namespace {
@@ -326,6 +327,22 @@ void load_tbi(lcty_vcf_indexed* v) {
     std::vector<uint8_t> x;
     while (in.append_block(x)) {}
     v->tbi = vcfidx::parse_tbi(x.data(), x.size(), ip);
+}
+
+// one ##contig line behind `##contig=<`: ID=name and length=n among its comma-separated keys (a line without an ID is passed over)
+void note_contig(lcty_vcf_indexed* v, std::string body) {
+    if (!body.empty() && body.back() == '>') body.pop_back();
+    std::string id; uint64_t len = 0;
+    for (size_t at = 0; at <= body.size();) {
+        size_t e = body.find(',', at);
+        if (e == std::string::npos) e = body.size();
+        const std::string kv = body.substr(at, e - at);
+        if (kv.compare(0, 3, "ID=") == 0) id = kv.substr(3);
+        else if (kv.compare(0, 7, "length=") == 0) { len = 0; for (size_t i = 7; i < kv.size() && kv[i] >= '0' && kv[i] <= '9' && len < (uint64_t(1) << 60); i++) len = len * 10 + uint64_t(kv[i] - '0'); }
+        at = e + 1;
+    }
+    if (id.empty() || std::find(v->contigs.begin(), v->contigs.end(), id) != v->contigs.end()) return;
+    v->contigs.push_back(id); v->contig_len.push_back(len);
 }
 
 // The head of the file: BGZF blocks from offset 0 until the #CHROM line and the first record are complete. The errors of
@@ -348,6 +365,7 @@ void load_head(lcty_vcf_indexed* v) {
             if (le > b) {
                 if (t[b] == '#') {
                     if (le - b >= 6 && !memcmp(&t[b], "#CHROM", 6)) { vcfidx::parse_chrom_line(t.data(), b, le, path, v->samples); have_header = true; }
+                    else if (le - b >= 10 && !memcmp(&t[b], "##contig=<", 10)) note_contig(v, std::string(reinterpret_cast<const char*>(&t[b + 10]), le - b - 10));
                 } else {
                     if (!have_header) vcfidx::fail_record_before_header(path);
                     const vcfidx::LineHead h = vcfidx::parse_line_head(t.data(), b, le, path);
@@ -362,6 +380,9 @@ void load_head(lcty_vcf_indexed* v) {
     }
     if (!have_header) vcfidx::fail_no_header(path);
     if (!have_record) vcfidx::fail_no_records();
+    for (const std::string& name : v->tbi.names)
+        if (std::find(v->contigs.begin(), v->contigs.end(), name) == v->contigs.end()) { v->contigs.push_back(name); v->contig_len.push_back(0); }
+    for (const std::string& name : v->contigs) { v->contig_blob += name; v->contig_blob.push_back('\0'); }
     const uint32_t S = static_cast<uint32_t>(v->samples.size());
     v->hap_off.assign(S + 1, 0);
     for (uint32_t i = 0; i < S; i++) { v->hap_off[i + 1] = v->hap_off[i] + v->ploidy[i]; v->sample_blob += v->samples[i]; v->sample_blob.push_back('\0'); }
@@ -397,6 +418,14 @@ int32_t lcty_vcf_indexed_open(const char* path, const char* index_path, lcty_vcf
         load_tbi(v.get());
         load_head(v.get());
         *out = v.release();
+    });
+}
+
+int32_t lcty_vcf_indexed_contigs(const lcty_vcf_indexed* vcf, lcty_vcf_contigs* out) {
+    return guarded([&] {
+        if (!vcf || !out) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+        out->n_contigs = static_cast<uint32_t>(vcf->contigs.size()); out->_pad0 = 0;
+        out->names = vcf->contig_blob.data(); out->names_len = vcf->contig_blob.size(); out->length = vcf->contig_len.data();
     });
 }
 

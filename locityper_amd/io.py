@@ -634,6 +634,14 @@ class VcfIndexed:
         self.n_haps, self.n_records = int(v.n_haps), int(v.n_records)
         self.stats = None
 
+    def contigs(self):
+        """lcty_vcf_indexed_contigs: [(name, length or 0)] in the order of the file's contig indices."""
+        c = cdefs.VcfContigs()
+        check(lib().lcty_vcf_indexed_contigs(self._h, C.byref(c)))
+        names = C.string_at(c.names, c.names_len).split(b"\0")[:-1] if c.names_len else []
+        lens = np.frombuffer(C.string_at(c.length, 8 * c.n_contigs), dtype=np.uint64) if c.n_contigs else []
+        return [(n.decode(), int(l)) for n, l in zip(names, lens)]
+
     def plan(self, contig, start, end):
         """-> (chunks [n][2] uint64 of virtual offsets, BGZF blocks they span)"""
         n, blocks = U64(0), U64(0)
