@@ -1,7 +1,7 @@
 // lcty_bam_layout.hpp — from the kept records of a slice to the mates of the output, shared by the two readers of a sample's BAM file:
 // lcty_sample_bam.hip (indexed: pairs by name) and lcty_bam_stream.hip (whole files in windows: single reads, or interleaved pairs).
-// The kept records in file order (stream_kernel), the mates of every read with their lengths in units of 32 bases (assemble_kernel),
-// and their offsets (offsets_kernel); unpack_kernel of lcty_bam_record.hpp ends both.
+// The kept records in file order (stream_kernel) and the mates of every read with their lengths in units of 32 bases (assemble_kernel);
+// ReadChunk::place (lcty_read_chunk.hpp) makes the offsets of them, and unpack_kernel of lcty_bam_record.hpp ends both.
 #pragma once
 
 #include "lcty_bam_record.hpp"
@@ -48,10 +48,6 @@ static __global__ __launch_bounds__(256) void assemble_kernel(const uint32_t* __
     src[2 * p] = r1; src[2 * p + 1] = r2;
     mate_len[2 * p] = l1; mate_len[2 * p + 1] = l2;
     units[2 * p] = l1 / 32u + ((l1 & 31u) ? 1u : 0u); units[2 * p + 1] = l2 / 32u + ((l2 & 31u) ? 1u : 0u);
-}
-static __global__ __launch_bounds__(256) void offsets_kernel(const uint32_t* __restrict__ unit_off, uint64_t n, uint64_t* __restrict__ mate_off) {
-    const uint64_t m = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
-    if (m < n) mate_off[m] = 32ull * unit_off[m];
 }
 
 }  // namespace lcty

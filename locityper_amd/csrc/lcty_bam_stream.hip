@@ -11,8 +11,8 @@
 //   exclusive_scan        over the kept flags -> the window's stream (stream_kernel); a carried first mate is its record 0
 //   stream_pair_kernel    a lane per pair (places 2 i, 2 i + 1): equal_names_fast on the two names, refused at the second mate's
 //                         record; an odd last place is reported as waiting
-//   assemble_kernel, offsets_kernel (lcty_bam_layout.hpp), unpack_kernel<true> (lcty_bam_record.hpp): the mates and their bases, as
-//                         lcty_sample_bam_fetch lays them out
+//   assemble_kernel (lcty_bam_layout.hpp), ReadChunk::place (lcty_read_chunk.hpp), unpack_kernel<true> (lcty_bam_record.hpp): the mates
+//                         and their bases, as lcty_sample_bam_fetch lays them out, in one chunk whose buffers serve every window
 // Every lane writes words of its own only; the one atomic beside the count is the minimum of the error word: two runs give the same bytes.
 #include <memory>
 #include <string>
@@ -63,23 +63,19 @@ __global__ __launch_bounds__(256) void stream_pair_kernel(const uint32_t* __rest
 
 // ---- the executor of lcty_bam_stream_window.hpp on the device
 struct DevExec {
-    lcty_ctx* ctx = nullptr;
-    lcty_sample_reads R;                             // the current chunk; its slice F is the window, used again window after window
+    lcty_ctx* ctx;
+    lcty_sample_reads R;                             // the current chunk, its buffers and its slice F (the window) used again window after window
     DevBuf<uint64_t> d_rec_off;
-    DevBuf<uint32_t> d_kept, d_scan, d_stream, d_words, d_units, d_unit_off, d_src_stream;     // d_words: [0] primaries, [1] the waiting record
+    DevBuf<uint32_t> d_kept, d_scan, d_stream, d_words, d_units, d_src, d_src_stream;     // d_words: [0] primaries, [1] the waiting record
     ErrWord err; ScanTotal scan_total;
     const uint32_t* raw = nullptr;
     uint32_t n_rec = 0, n_stream = 0;
     double ms_upload = 0, ms_record = 0, ms_pair = 0, ms_unpack = 0;
+    explicit DevExec(lcty_ctx* c) : ctx(c), R(c, ReadChunk::Buffers::Reused) {}
 
-    void clear_chunk() {
-        R.n = 0; R.n_units = 0; R.have_bases = true;
-        R.h_len.clear(); R.h_src.clear(); R.h_src_stream.clear();
-        R.h_off.assign(1, 0); R.zero_off.assign(1, 0); R.h_bases.assign(2, 0); R.h_nm.assign(1, 0);
-    }
-    uint8_t* alloc(uint64_t n) { clear_chunk(); R.F.alloc(ctx, n); return R.F.slice; }
+    uint8_t* alloc(uint64_t n) { R.clear(); R.F.alloc(ctx, n); return R.F.slice; }
     uint8_t* inflate(std::vector<uint8_t>& comp, std::vector<BgzfBlock>& blocks, uint64_t total, const char* path) {
-        clear_chunk();
+        R.clear();
         check_inflate_knob(ctx);
         R.F.comp.swap(comp); R.F.blocks.swap(blocks); R.F.total = total;
         R.F.inflate(ctx, path);
@@ -142,31 +138,22 @@ struct DevExec {
         hipStream_t s = ctx->stream;
         const double t0 = now_ms();
         const uint64_t M = 2ull * n_out;
-        R.n = n_out; R.have_bases = false;
-        R.zero_off.assign(n_out + 1ull, 0);
-        d_src_stream.ensure_slack(M); R.d_src.ensure_slack(M); R.d_len.ensure_slack(M); d_units.alloc(M); R.d_off.ensure_slack(M + 1);
+        ReadChunk& C = R.chunk; C.reserve_mates(n_out);
+        d_src_stream.ensure_slack(M); d_src.ensure_slack(M); d_units.alloc(M);
         hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n_lim, 256)), dim3(256), 0, s, raw, d_rec_off.p, static_cast<const uint32_t*>(nullptr), d_stream.p, n_lim,
-                           interleaved ? MATES_INTERLEAVED : MATES_SINGLE, static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr), R.d_src.p,
-                           d_src_stream.p, R.d_len.p, d_units.p);
+                           interleaved ? MATES_INTERLEAVED : MATES_SINGLE, static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr), d_src.p,
+                           d_src_stream.p, C.d_len.p, d_units.p);
         LCTY_HIP(hipGetLastError());
-        const uint32_t n_units = scan_total.run(d_units, d_unit_off, M, ctx);
-        R.n_units = n_units;
-        hipLaunchKernelGGL(offsets_kernel, dim3(blocks_of(M + 1, 256)), dim3(256), 0, s, d_unit_off.p, M + 1, R.d_off.p);
-        LCTY_HIP(hipGetLastError());
-        // two words of zeros behind the last unit: the k-mer windows of the recruitment kernels read one word ahead
-        R.d_bases.ensure_slack(n_units + 2ull); R.d_nm.ensure_slack(n_units + 2ull);
-        LCTY_HIP(hipMemsetAsync(R.d_bases.p + n_units, 0, 2 * sizeof(uint64_t), s));
-        LCTY_HIP(hipMemsetAsync(R.d_nm.p + n_units, 0, 2 * sizeof(uint32_t), s));
+        const uint32_t n_units = C.place(d_units, M, scan_total);
         if (n_units)
-            hipLaunchKernelGGL(unpack_kernel<true>, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, R.d_src.p, d_unit_off.p, static_cast<uint32_t>(M),
-                               n_units, R.d_bases.p, R.d_nm.p);
+            hipLaunchKernelGGL(unpack_kernel<true>, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_src.p, C.d_unit_off.p, static_cast<uint32_t>(M),
+                               n_units, C.d_bases.p, C.d_nm.p);
         LCTY_HIP(hipGetLastError());
-        R.h_len.resize(M); R.h_src.resize(M); R.h_src_stream.resize(M); R.h_off.resize(M + 1);
-        d_src_stream.download(R.h_src_stream.data(), M, s);
-        R.d_len.download(R.h_len.data(), M, s); R.d_src.download(R.h_src.data(), M, s); R.d_off.download(R.h_off.data(), M + 1, s);
+        R.h_src.resize(M); R.h_src_stream.resize(M);
+        d_src_stream.download(R.h_src_stream.data(), M, s); d_src.download(R.h_src.data(), M, s);
         LCTY_HIP(hipStreamSynchronize(s));
         uint64_t bases = 0;
-        for (uint32_t l : R.h_len) bases += l;
+        for (uint64_t m = 0; m < M; m++) bases += C.h_len[m];
         ms_unpack += now_ms() - t0;
         return bases;
     }
@@ -179,7 +166,7 @@ struct lcty_bam_stream {
     DevExec exec;
     bs::Stream<DevExec> st;
     double ms_total = 0;
-    explicit lcty_bam_stream(lcty_ctx* c) : ctx(c), st(exec) { exec.ctx = c; exec.R.ctx = c; exec.clear_chunk(); }
+    explicit lcty_bam_stream(lcty_ctx* c) : ctx(c), exec(c), st(exec) {}
 };
 
 namespace {
@@ -205,7 +192,7 @@ int32_t lcty_bam_stream_open(lcty_ctx* ctx, const char* const* paths, uint32_t n
         if (n_paths == 0) fail(LCTY_ERR_INVALID_INPUT, "no input file");
         check_inflate_knob(ctx);
         std::unique_ptr<lcty_bam_stream> b(new lcty_bam_stream(ctx));
-        b->exec.R.paired = interleaved != 0;
+        b->exec.R.chunk.paired = interleaved != 0;
         b->st.open(paths, n_paths, interleaved != 0, ctx->knob("bam_stream_window_bytes", static_cast<int64_t>(bs::WINDOW_DEFAULT)),
                    ctx->knob("bam_stream_window_limit", static_cast<int64_t>(bs::LIMIT_DEFAULT)));
         *out = b.release();
@@ -221,13 +208,13 @@ int32_t lcty_bam_stream_next(lcty_bam_stream* b, lcty_sample_reads** reads, uint
         if (!b || !reads || !n) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         const double t0 = now_ms();
         b->ctx->activate();
-        b->exec.clear_chunk();
+        b->exec.R.clear();
         try {
             const bs::Chunk c = b->st.next();
-            if (!c.n) b->exec.clear_chunk();
+            if (!c.n) b->exec.R.clear();
             *n = c.n;
         } catch (...) {
-            b->exec.clear_chunk();
+            b->exec.R.clear();
             b->ms_total += now_ms() - t0;
             if (stats) fill_stats(b, stats);
             throw;

@@ -198,19 +198,9 @@ int32_t lcty_fastx_write_recruited(lcty_fastx* f, lcty_fastx_writers* w, uint32_
     return guarded([&] {
         if (!f || !w || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         const size_t per = f->paired ? 2 : 1;
-        uint64_t written = 0;
-        std::string text;
-        for (uint64_t i = 0; i < f->n; i++) {
-            if (!out_cnt[i]) continue;
-            text.clear();
+        const uint64_t written = write_recruited_units(w, f->n, max_out, out_cnt, out_loci, [&](uint64_t i, std::string& text) {
             for (size_t e = 0; e < per; e++) record_text(f->recs[i * per + e], text);       // [T; 2]::write_to: the mates one after the other
-            for (uint32_t j = 0; j < std::min(out_cnt[i], max_out); j++) {
-                const uint32_t locus = out_loci[static_cast<size_t>(i) * max_out + j];
-                if (locus >= w->paths.size()) fail(LCTY_ERR_INVALID_INPUT, "record %llu is recruited to locus %u of %zu writers", static_cast<unsigned long long>(i), locus, w->paths.size());
-                w->put(locus, text);
-            }
-            written++;
-        }
+        });
         if (n_written) *n_written = written;
     });
 }

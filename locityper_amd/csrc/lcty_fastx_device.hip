@@ -4,12 +4,12 @@
 //   lines     the positions of its '\n' bytes, compacted in order (nl_count_kernel, exclusive scan, nl_place_kernel)
 //   records   a 16-byte row and a class per record by the rules of lcty_fastx_parse.hpp, the smallest (record, class) in one word
 //             (fastq_record_kernel; FASTA: fasta_line_kernel, two scans, fasta_header_kernel, fasta_record_kernel; names_kernel for pairs)
-// and of the records of one call
-//   layout    mate_len and, by a scan of the lengths rounded up to 32 bases, mate_off: the layout of pack() in lcty_fastx.hip
+// and of the records of one call a chunk of reads resident on the device (ReadChunk, lcty_read_chunk.hpp), used again call after call:
+//   layout    mate_len and every mate's units of 32 bases (layout_kernel); ReadChunk::place makes mate_off of them: the layout of
+//             pack() in lcty_fastx.hip
 //   pack      bases2 / nmask through base_bits (lcty_seq.hpp), one lane per 32 bases of a mate: it owns one nmask word and two
 //             bases2 words and writes them whole, so nothing is zeroed first and no two lanes meet (pack_kernel)
-// which lcty_fastx_device_recruit hands to recruit_device_view as they lie. No kernel uses LDS; none depends on timing: the
-// only atomic is the minimum of the error word.
+// which view, recruit and lcty_recruited_add_fastx take as it lies. No kernel uses LDS or depends on timing: the only atomic is the error word's minimum.
 #include <memory>
 #include <string>
 #include <vector>
@@ -19,7 +19,7 @@
 #include "lcty_device.hpp"
 #include "lcty_fastx_parse.hpp"
 #include "lcty_fastx_window.hpp"
-#include "lcty_objects.hpp"
+#include "lcty_read_chunk.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_seq.hpp"
 #include "lcty_writers.hpp"
@@ -112,10 +112,6 @@ __global__ __launch_bounds__(THREADS) void layout_kernel(ChunkView V, uint32_t* 
     const uint32_t e = m & 1u, i = m >> 1;
     const uint32_t len = e < V.per ? V.src[e].rows[V.src[e].rec0 + V.stride * i].len : 0u;
     mate_len[m] = len; units[m] = (len + 31) / 32;
-}
-__global__ __launch_bounds__(THREADS) void offsets_kernel(const uint32_t* __restrict__ unit_off, uint32_t n, uint64_t* __restrict__ mate_off) {
-    const uint32_t m = blockIdx.x * THREADS + threadIdx.x;
-    if (m < n) mate_off[m] = 32ull * unit_off[m];
 }
 // One lane per 32 bases. FASTQ: the bases are one run of bytes, read as nine dwords around them. FASTA: a unit may span lines; its
 // owner gathers the bytes from them (no lane writes a word another lane writes, so no atomic OR and no zeroed output are needed).
@@ -304,13 +300,10 @@ struct lcty_fastx_device {
     DevExec exec;
     fastx::Stream<DevExec> st;
     fastx::Chunk chunk;
-    // the current chunk on the device, and on the host what was asked for
-    DevBuf<uint32_t> d_len, d_units, d_unit_off, d_nm; DevBuf<uint64_t> d_off, d_bases;
-    uint32_t n_units = 0;
-    std::vector<uint32_t> h_len, h_bases, h_nm; std::vector<uint64_t> h_off, zero_off;
-    bool have_view = false;
+    ReadChunk reads;                          // the current chunk on the device
+    DevBuf<uint32_t> d_units;
     double ms_pack = 0, ms_total = 0;
-    explicit lcty_fastx_device(lcty_ctx* c) : ctx(c), st(exec) { exec.ctx = c; }
+    explicit lcty_fastx_device(lcty_ctx* c) : ctx(c), st(exec), reads(c, ReadChunk::Buffers::Reused) { exec.ctx = c; }
 };
 
 namespace {
@@ -325,11 +318,10 @@ void fill_stats(const lcty_fastx_device* f, lcty_fastx_device_stats* S) {
 // layout and pack of the chunk the stream just handed out
 void emit(lcty_fastx_device* f) {
     const fastx::Chunk& c = f->chunk;
-    lcty_ctx* ctx = f->ctx;
-    hipStream_t s = ctx->stream;
+    hipStream_t s = f->ctx->stream;
     const uint32_t k = c.k, M = 2 * k;
-    f->have_view = false; f->n_units = 0;
-    f->h_len.assign(M, 0);
+    ReadChunk& R = f->reads;
+    R.clear(); R.paired = f->st.paired;
     if (!k) return;
     if (k >= (1u << 30)) fail(LCTY_ERR_UNSUPPORTED, "more than 2^30 records in one call");
     const double t0 = now_ms();
@@ -339,19 +331,12 @@ void emit(lcty_fastx_device* f) {
         const DevExec::FileDev& F = f->exec.fd[c.file[e]];
         V.src[e] = MateSrc{F.text, F.rows.p, F.cum.p, c.rec0[e], F.n_lines, F.n_nl, F.n, F.nl.p, F.fasta};
     }
-    f->d_len.alloc(M); f->d_units.alloc(M); f->d_off.alloc(M + 1);
-    hipLaunchKernelGGL(layout_kernel, dim3(blocks_of(M, THREADS)), dim3(THREADS), 0, s, V, f->d_len.p, f->d_units.p);
+    R.reserve_mates(k); f->d_units.ensure_slack(M);
+    hipLaunchKernelGGL(layout_kernel, dim3(blocks_of(M, THREADS)), dim3(THREADS), 0, s, V, R.d_len.p, f->d_units.p);
     LCTY_HIP(hipGetLastError());
-    const uint32_t n_units = f->exec.scan.run(f->d_units, f->d_unit_off, M, ctx);
-    f->n_units = n_units;
-    hipLaunchKernelGGL(offsets_kernel, dim3(blocks_of(M + 1, THREADS)), dim3(THREADS), 0, s, f->d_unit_off.p, M + 1, f->d_off.p);
-    // two words of zeros behind the last unit: the k-mer windows of the recruitment kernels read one word ahead
-    f->d_bases.alloc(n_units + 2ull); f->d_nm.alloc(n_units + 2ull);
-    LCTY_HIP(hipMemsetAsync(f->d_bases.p + n_units, 0, 2 * sizeof(uint64_t), s));
-    LCTY_HIP(hipMemsetAsync(f->d_nm.p + n_units, 0, 2 * sizeof(uint32_t), s));
-    if (n_units) hipLaunchKernelGGL(pack_kernel, dim3(blocks_of(n_units, THREADS)), dim3(THREADS), 0, s, V, f->d_unit_off.p, n_units, f->d_bases.p, f->d_nm.p);
+    const uint32_t n_units = R.place(f->d_units, M, f->exec.scan);
+    if (n_units) hipLaunchKernelGGL(pack_kernel, dim3(blocks_of(n_units, THREADS)), dim3(THREADS), 0, s, V, R.d_unit_off.p, n_units, R.d_bases.p, R.d_nm.p);
     LCTY_HIP(hipGetLastError());
-    f->d_len.download(f->h_len.data(), M, s);
     LCTY_HIP(hipStreamSynchronize(s));
     f->ms_pack += now_ms() - t0;
 }
@@ -360,9 +345,7 @@ void emit(lcty_fastx_device* f) {
 
 namespace lcty {
 
-ResidentChunk fastx_device_chunk(lcty_fastx_device* f) {
-    return ResidentChunk{f->ctx, f->chunk.k, f->h_len.data(), f->d_len.p, f->d_off.p, f->d_bases.p, f->d_nm.p};
-}
+const ReadChunk& fastx_device_reads(const lcty_fastx_device* f) { return f->reads; }
 // the name lcty_fastx_device_write_recruited writes for unit i: the header of its first record up to the first blank
 std::string fastx_device_name(lcty_fastx_device* f, uint64_t i) {
     const fastx::Chunk& c = f->chunk;
@@ -401,12 +384,13 @@ int32_t lcty_fastx_device_next(lcty_fastx_device* f, uint64_t max_records, uint6
         const double t0 = now_ms();
         f->ctx->activate();
         f->chunk = fastx::Chunk();
-        f->have_view = false; f->n_units = 0; f->h_len.clear();
+        f->reads.clear();
         try {
             f->chunk = f->st.next(max_records);
             emit(f);
         } catch (...) {
             f->chunk = fastx::Chunk();
+            f->reads.clear();
             f->ms_total += now_ms() - t0;
             if (stats) fill_stats(f, stats);
             throw;
@@ -420,38 +404,14 @@ int32_t lcty_fastx_device_next(lcty_fastx_device* f, uint64_t max_records, uint6
 int32_t lcty_fastx_device_view(lcty_fastx_device* f, lcty_reads_host* view) {
     return guarded([&] {
         if (!f || !view) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const uint32_t k = f->chunk.k, M = 2 * k;
-        if (!f->have_view) {
-            f->ctx->activate();
-            hipStream_t s = f->ctx->stream;
-            f->h_off.assign(M + 1ull, 0); f->zero_off.assign(k + 1ull, 0);
-            f->h_bases.assign(2ull * f->n_units + 2, 0); f->h_nm.assign(f->n_units + 1ull, 0);
-            if (k) {
-                f->d_off.download(f->h_off.data(), M + 1ull, s);
-                if (f->n_units) {
-                    LCTY_HIP(hipMemcpyAsync(f->h_bases.data(), f->d_bases.p, 8ull * f->n_units, hipMemcpyDeviceToHost, s));
-                    f->d_nm.download(f->h_nm.data(), f->n_units, s);
-                }
-                LCTY_HIP(hipStreamSynchronize(s));
-            }
-            f->have_view = true;
-        }
-        memset(view, 0, sizeof(*view));
-        view->n_pairs = k;
-        view->mate_len = f->h_len.data(); view->mate_off = f->h_off.data(); view->bases2 = f->h_bases.data(); view->nmask = f->h_nm.data();
-        view->aln_off = f->zero_off.data(); view->cigar_off = f->zero_off.data();
+        f->reads.view(view);
     });
 }
 
 int32_t lcty_fastx_device_recruit(lcty_targets* targets, lcty_fastx_device* f, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci) {
     return guarded([&] {
         if (!targets || !f || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        lcty_ctx* ctx = targets_ctx(targets);
-        if (ctx != f->ctx) fail(LCTY_ERR_INVALID_INPUT, "the targets and the reads belong to different contexts");
-        if (f->chunk.k == 0) return;
-        ctx->activate();
-        recruit_device_view(targets, f->chunk.k, f->h_len.data(), f->d_len.p, f->d_off.p, reinterpret_cast<const uint32_t*>(f->d_bases.p), f->d_nm.p,
-                            f->st.paired ? 1 : 0, max_out, out_cnt, out_loci);
+        f->reads.recruit(targets, max_out, out_cnt, out_loci);
     });
 }
 
@@ -460,19 +420,9 @@ int32_t lcty_fastx_device_write_recruited(lcty_fastx_device* f, lcty_fastx_write
     return guarded([&] {
         if (!f || !w || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         const fastx::Chunk& c = f->chunk;
-        uint64_t written = 0;
-        std::string text;
-        for (uint32_t i = 0; i < c.k; i++) {
-            if (!out_cnt[i]) continue;
-            text.clear();
-            for (int e = 0; e < c.per; e++) f->st.record_text(f->st.f[c.file[e]], c.rec0[e] + c.stride * i, text);       // [T; 2]::write_to: the mates one after the other
-            for (uint32_t j = 0; j < std::min(out_cnt[i], max_out); j++) {
-                const uint32_t locus = out_loci[static_cast<size_t>(i) * max_out + j];
-                if (locus >= w->paths.size()) fail(LCTY_ERR_INVALID_INPUT, "record %llu is recruited to locus %u of %zu writers", static_cast<unsigned long long>(i), locus, w->paths.size());
-                w->put(locus, text);
-            }
-            written++;
-        }
+        const uint64_t written = write_recruited_units(w, c.k, max_out, out_cnt, out_loci, [&](uint64_t i, std::string& text) {
+            for (int e = 0; e < c.per; e++) f->st.record_text(f->st.f[c.file[e]], c.rec0[e] + c.stride * static_cast<uint32_t>(i), text);      // [T; 2]::write_to: the mates one after the other
+        });
         if (n_written) *n_written = written;
     });
 }

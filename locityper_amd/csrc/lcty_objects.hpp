@@ -191,21 +191,11 @@ struct DeviceRecords {
     uint32_t max_rec_cigar;
 };
 int32_t reads_append_device(lcty_reads* R, const lcty_reads_host* h, const DeviceRecords* dev);
-// lcty_recruit behind its upload (lcty_recruit.hip): the sequence fields of n pairs as device arrays + the host's copy of mate_len
+// lcty_recruit behind its upload (lcty_recruit.hip; ReadChunk::recruit): the sequence fields of n pairs as device arrays + the host's copy of mate_len
 void recruit_device_view(lcty_targets* t, uint64_t n, const uint32_t* h_mate_len, const uint32_t* d_len, const uint64_t* d_off, const uint32_t* d_bases,
                          const uint32_t* d_nm, int32_t paired, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci);
 lcty_ctx* targets_ctx(lcty_targets* t);
 uint32_t targets_n_loci(const lcty_targets* t);
-// The chunk a source handle holds, where it lies (lcty_recruited.hip scatters it from there): the sequence fields on the device, the
-// host's copy of mate_len, and the name of pair i as the handle's write_recruited writes it (its first read end's).
-struct ResidentChunk {
-    lcty_ctx* ctx; uint64_t n;
-    const uint32_t* h_len; const uint32_t* d_len; const uint64_t* d_off; const uint64_t* d_bases; const uint32_t* d_nm;
-};
-ResidentChunk fastx_device_chunk(lcty_fastx_device* f);                          // lcty_fastx_device.hip: the chunk of the last lcty_fastx_device_next
-std::string fastx_device_name(lcty_fastx_device* f, uint64_t i);
-ResidentChunk sample_reads_chunk(lcty_sample_reads* r);                          // lcty_sample_bam.hip: the fetched reads
-std::string sample_reads_name(lcty_sample_reads* r, uint64_t i);
 
 // The rows of a stage's alleles of the location tables of several batches (shards of one locus' reads, in read order), laid
 // side by side into one table the solver kernels run on (lcty_solve_kernels.hip). The caller moves the packed rows between devices

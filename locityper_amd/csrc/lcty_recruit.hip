@@ -16,6 +16,7 @@
 #include <unordered_map>
 
 #include "lcty_objects.hpp"
+#include "lcty_read_chunk.hpp"
 #include "lcty_table.hpp"
 
 namespace lcty {
@@ -536,8 +537,8 @@ void approximate_u16(double x, uint16_t* num, uint16_t* den) {
 
 namespace lcty {
 
-// lcty_recruit on reads that are on the device already (lcty_objects.hpp): the sequence fields of a chunk of n pairs as device
-// arrays, and the host's copy of mate_len, which sorts the reads between the two kernels. Work is issued on the context's stream
+// lcty_recruit on reads that are on the device already (ReadChunk::recruit, lcty_read_chunk.hpp): the sequence fields of a chunk of n
+// pairs as device arrays, and the host's copy of mate_len, which sorts the reads between the two kernels. Work is issued on the context's stream
 // behind whatever filled the arrays; returns with out_cnt / out_loci on the host.
 void recruit_device_view(lcty_targets* t, uint64_t n, const uint32_t* h_mate_len, const uint32_t* d_len, const uint64_t* d_off, const uint32_t* d_bases,
                          const uint32_t* d_nm, int32_t paired, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci) {
@@ -699,25 +700,12 @@ int32_t lcty_targets_finalize(lcty_targets* t, uint64_t* n_minimizers) {
 int32_t lcty_recruit(lcty_targets* t, const lcty_reads_host* h, int32_t paired, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci) {
     return guarded([&] {
         if (!t || !h || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        if (!t->finalized) fail(LCTY_ERR_INVALID_INPUT, "lcty_targets_finalize has not been called");
-        const uint64_t n = h->n_pairs;
-        if (n == 0) return;
-        if (!h->mate_len || !h->mate_off || !h->bases2 || !h->nmask) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        lcty_ctx* ctx = t->ctx;
+        lcty_ctx* ctx = targets_ctx(t);
         ctx->activate();
-        hipStream_t s = ctx->stream;
-        const uint64_t nb = h->mate_off[2 * n];
-        for (uint64_t m = 0; m < 2 * n; m++) {
-            if (h->mate_off[m] % 32) fail(LCTY_ERR_INVALID_INPUT, "mate offsets must be multiples of 32 bases");
-            if (h->mate_off[m + 1] < h->mate_off[m] + h->mate_len[m]) fail(LCTY_ERR_INVALID_INPUT, "mate offsets overlap");
-        }
-        // upload a host chunk ...
-        DevBuf<uint32_t> d_len, d_bases, d_nm; DevBuf<uint64_t> d_off;
-        d_len.alloc(2 * n); d_off.alloc(2 * n + 1); d_bases.alloc(std::max<uint64_t>(nb / 16, 2)); d_nm.alloc(std::max<uint64_t>(nb / 32, 1));
-        d_len.upload(h->mate_len, 2 * n, s); d_off.upload(h->mate_off, 2 * n + 1, s);
-        d_bases.upload(h->bases2, nb / 16, s); d_nm.upload(h->nmask, nb / 32, s);
-        // ... and run on the device view
-        recruit_device_view(t, n, h->mate_len, d_len.p, d_off.p, d_bases.p, d_nm.p, paired, max_out, out_cnt, out_loci);
+        ReadChunk c(ctx, ReadChunk::Buffers::OneShot);                          // recruit_device_view ends with the stream synchronised
+        c.paired = paired != 0;
+        c.upload(h);
+        c.recruit(t, max_out, out_cnt, out_loci);
     });
 }
 

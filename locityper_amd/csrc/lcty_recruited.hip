@@ -1,7 +1,7 @@
 // lcty_recruited.hip — a resident set of recruited reads: for every locus of a finalized lcty_targets the reads recruited
 // to it so far, on the device, as the sequence fields of one chunk — what the in-locus mapper reads (lcty_map.hip) — plus a source
-// ordinal per pair. An add scatters a chunk (a host chunk uploaded, or the arrays of lcty_fastx_device / lcty_sample_reads where they
-// lie) by the answers of recruitment:
+// ordinal per pair. An add scatters a chunk of reads resident on the device (ReadChunk, lcty_read_chunk.hpp: a host chunk uploaded, or
+// the chunk of a lcty_fastx_device / lcty_sample_reads where it lies) by the answers of recruitment:
 //   entries   (locus, pair) for every locus of every pair, in input order (entry_kernel behind an exclusive_scan of out_cnt),
 //             brought into locus order by the stable radix sort of lcty_sort.hpp on the bytes of the locus;
 //   places    exclusive_scan (lcty_scan.hpp) of the entries' unit counts: a locus's entries are one run, so entry e of locus l goes to
@@ -14,7 +14,9 @@
 #include <functional>
 
 #include "lcty_map_internal.hpp"
+#include "lcty_read_chunk.hpp"
 #include "lcty_recruited_host.hpp"
+#include "lcty_sample_bam.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
 
@@ -25,8 +27,8 @@ namespace {
 
 // the arrays of one locus on the device; the capacities are LocusBook's
 struct LocusDev {
-    DevBuf<uint64_t> bases, off, ord;         // [cap_units + 2] (two words of zeros follow the last unit, as in the sources), [2 cap_pairs + 1], [cap_pairs]
-    DevBuf<uint32_t> nm, len;                 // [cap_units + 2], [2 cap_pairs]
+    DevBuf<uint64_t> bases, off, ord;         // [cap_units + CHUNK_PAD_UNITS] (zeros follow the last unit, as in a ReadChunk), [2 cap_pairs + 1], [cap_pairs]
+    DevBuf<uint32_t> nm, len;                 // [cap_units + CHUNK_PAD_UNITS], [2 cap_pairs]
 };
 
 // where a locus's share of an add goes
@@ -94,13 +96,7 @@ __global__ __launch_bounds__(256) void scatter_kernel(const ScatterView V) {
     }
 }
 
-// the sequence fields of a chunk on the device and the host's copy of its lengths
-struct Source {
-    uint64_t n = 0;
-    const uint32_t* h_len = nullptr;
-    const uint32_t* d_len = nullptr; const uint64_t* d_off = nullptr; const uint64_t* d_bases = nullptr; const uint32_t* d_nm = nullptr;
-    std::function<std::string(uint64_t)> name;       // of pair i; empty: the source has no names
-};
+using NameFn = std::function<std::string(uint64_t)>;      // the name of pair i of a chunk; empty: the source has no names
 
 }  // namespace
 
@@ -132,7 +128,7 @@ void reserve(lcty_recruited* S, size_t l, uint64_t pairs, uint64_t units, uint64
     const uint64_t cap_pairs = recruited::grown(b.cap_pairs, pairs, std::max<uint64_t>(init_units / 8, 1));
     if (cap_units != b.cap_units || !d.bases.p) {
         DevBuf<uint64_t> bases; DevBuf<uint32_t> nm;
-        bases.alloc(cap_units + 2); nm.alloc(cap_units + 2);
+        bases.alloc(cap_units + CHUNK_PAD_UNITS); nm.alloc(cap_units + CHUNK_PAD_UNITS);
         bases.zero(s); nm.zero(s);
         if (b.n_units) {
             LCTY_HIP(hipMemcpyAsync(bases.p, d.bases.p, b.n_units * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
@@ -157,7 +153,7 @@ void reserve(lcty_recruited* S, size_t l, uint64_t pairs, uint64_t units, uint64
     }
 }
 
-void add_source(lcty_recruited* S, const Source& src, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci) {
+void add_chunk(lcty_recruited* S, const ReadChunk& src, const NameFn& name, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci) {
     lcty_ctx* ctx = S->ctx;
     hipStream_t s = ctx->stream;
     const uint64_t n = src.n;
@@ -166,7 +162,8 @@ void add_source(lcty_recruited* S, const Source& src, uint32_t max_out, const ui
     const uint64_t max_bytes = static_cast<uint64_t>(ctx->knob("recruited_max_bytes", static_cast<int64_t>(recruited::MAX_BYTES_DEFAULT)));
     const uint64_t init_units = static_cast<uint64_t>(std::max<int64_t>(1, ctx->knob("recruited_init_units", static_cast<int64_t>(recruited::INIT_UNITS_DEFAULT))));
     // ---- the plan: every check is made here, before anything is copied
-    const recruited::Plan P = recruited::plan_add(S->books, n, src.h_len, max_out, out_cnt, out_loci, max_bytes);
+    const uint32_t* h_len = src.h_len;
+    const recruited::Plan P = recruited::plan_add(S->books, n, h_len, max_out, out_cnt, out_loci, max_bytes);
     const size_t n_loci = S->books.size();
     if (P.n_entries) {
         const uint32_t n_entries = static_cast<uint32_t>(P.n_entries), n_units = static_cast<uint32_t>(P.n_units);
@@ -197,20 +194,19 @@ void add_source(lcty_recruited* S, const Source& src, uint32_t max_out, const ui
         const uint64_t* key = where ? S->key_b.p : S->key_a.p; const uint64_t* val = where ? S->val_b.p : S->val_a.p;
         // ---- places
         S->units.ensure_slack(n_entries); S->unit_at.ensure_slack(n_entries);
-        hipLaunchKernelGGL(entry_units_kernel, dim3(blocks_of(n_entries, 256)), dim3(256), 0, s, n_entries, val, src.d_len, S->units.p);
+        hipLaunchKernelGGL(entry_units_kernel, dim3(blocks_of(n_entries, 256)), dim3(256), 0, s, n_entries, val, src.d_len.p, S->units.p);
         LCTY_HIP(hipGetLastError());
         exclusive_scan(S->units.p, S->unit_at.p, n_entries, S->scan_tmp.p, s);
         // ---- the copy
-        ScatterView V{src.d_len, src.d_off, src.d_bases, src.d_nm, key, val, S->unit_at.p, n_entries, n_units,
+        ScatterView V{src.d_len.p, src.d_off.p, src.d_bases.p, src.d_nm.p, key, val, S->unit_at.p, n_entries, n_units,
                       reinterpret_cast<const LocusDst*>(S->d_dst.p), S->n_seen};
         hipLaunchKernelGGL(scatter_kernel, dim3(blocks_of(std::max(n_entries, n_units), 256)), dim3(256), 0, s, V);
         LCTY_HIP(hipGetLastError());
         LCTY_HIP(hipStreamSynchronize(s));                                       // dst and the caller's answers are host memory of this call
     }
     // ---- the host's side: nothing below fails for a reason of the input
-    const bool named = S->keep_names && static_cast<bool>(src.name);
-    if (named) recruited::commit_add(S->books, P, n, src.h_len, max_out, out_cnt, out_loci, &src.name);
-    else recruited::commit_add(S->books, P, n, src.h_len, max_out, out_cnt, out_loci, static_cast<const std::function<std::string(uint64_t)>*>(nullptr));
+    const bool named = S->keep_names && static_cast<bool>(name);
+    recruited::commit_add(S->books, P, n, h_len, max_out, out_cnt, out_loci, named ? &name : static_cast<const NameFn*>(nullptr));
     if (!named && P.n_entries) S->any_unnamed = true;
     for (size_t l = 0; l < n_loci; l++) if (P.add_pairs[l]) S->views[l].valid = false;
     S->n_seen += n;
@@ -218,6 +214,15 @@ void add_source(lcty_recruited* S, const Source& src, uint32_t max_out, const ui
 
 void check_answers(const lcty_recruited* S, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci) {
     if (!S || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+}
+
+// the chunk a source handle holds, scattered from where it lies (null: the handle was null)
+void add_resident(lcty_recruited* S, const ReadChunk* c, const NameFn& name, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci) {
+    check_answers(S, max_out, out_cnt, out_loci);
+    if (!c) fail(LCTY_ERR_INVALID_INPUT, "null argument");
+    if (c->ctx != S->ctx) fail(LCTY_ERR_INVALID_INPUT, "the set and the reads belong to different contexts");
+    S->ctx->activate();
+    add_chunk(S, *c, name, max_out, out_cnt, out_loci);
 }
 
 LocusBook& book_of(lcty_recruited* S, uint32_t locus_ix) {
@@ -248,49 +253,21 @@ void lcty_recruited_destroy(lcty_recruited* set) { delete set; }
 int32_t lcty_recruited_add(lcty_recruited* set, const lcty_reads_host* h, int32_t paired, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci) {
     return guarded([&] {
         check_answers(set, max_out, out_cnt, out_loci);
-        if (!h) fail(LCTY_ERR_INVALID_INPUT, "null argument");
         (void)paired;                                                            // an absent mate has length 0 either way
-        const uint64_t n = h->n_pairs;
-        if (n == 0) return;
-        if (!h->mate_len || !h->mate_off || !h->bases2 || !h->nmask) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        for (uint64_t m = 0; m < 2 * n; m++) {
-            if (h->mate_off[m] % 32) fail(LCTY_ERR_INVALID_INPUT, "mate offsets must be multiples of 32 bases");
-            if (h->mate_off[m + 1] < h->mate_off[m] + h->mate_len[m]) fail(LCTY_ERR_INVALID_INPUT, "mate offsets overlap");
-        }
-        lcty_ctx* ctx = set->ctx;
-        ctx->activate();
-        hipStream_t s = ctx->stream;
-        const uint64_t nu = h->mate_off[2 * n] / 32;
-        DevBuf<uint32_t> d_len, d_nm; DevBuf<uint64_t> d_off, d_bases;
-        d_len.alloc(2 * n); d_off.alloc(2 * n + 1); d_bases.alloc(std::max<uint64_t>(nu, 1)); d_nm.alloc(std::max<uint64_t>(nu, 1));
-        d_len.upload(h->mate_len, 2 * n, s); d_off.upload(h->mate_off, 2 * n + 1, s);
-        if (nu) LCTY_HIP(hipMemcpyAsync(d_bases.p, h->bases2, nu * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        d_nm.upload(h->nmask, nu, s);
-        struct Done { hipStream_t s; ~Done() { (void)hipStreamSynchronize(s); } } done{s};      // the copies read the caller's chunk
-        add_source(set, Source{n, h->mate_len, d_len.p, d_off.p, d_bases.p, d_nm.p, {}}, max_out, out_cnt, out_loci);
+        set->ctx->activate();
+        ReadChunk c(set->ctx, ReadChunk::Buffers::OneShot);
+        struct Done { hipStream_t s; ~Done() { (void)hipStreamSynchronize(s); } } done{set->ctx->stream};      // the copies read the caller's chunk
+        c.upload(h);
+        add_chunk(set, c, NameFn(), max_out, out_cnt, out_loci);
     });
 }
 
 int32_t lcty_recruited_add_fastx(lcty_recruited* set, lcty_fastx_device* f, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci) {
-    return guarded([&] {
-        check_answers(set, max_out, out_cnt, out_loci);
-        if (!f) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const ResidentChunk c = fastx_device_chunk(f);
-        if (c.ctx != set->ctx) fail(LCTY_ERR_INVALID_INPUT, "the set and the reads belong to different contexts");
-        set->ctx->activate();
-        add_source(set, Source{c.n, c.h_len, c.d_len, c.d_off, c.d_bases, c.d_nm, [f](uint64_t i) { return fastx_device_name(f, i); }}, max_out, out_cnt, out_loci);
-    });
+    return guarded([&] { add_resident(set, f ? &fastx_device_reads(f) : nullptr, [f](uint64_t i) { return fastx_device_name(f, i); }, max_out, out_cnt, out_loci); });
 }
 
 int32_t lcty_recruited_add_sample(lcty_recruited* set, lcty_sample_reads* r, uint32_t max_out, const uint32_t* out_cnt, const uint32_t* out_loci) {
-    return guarded([&] {
-        check_answers(set, max_out, out_cnt, out_loci);
-        if (!r) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        const ResidentChunk c = sample_reads_chunk(r);
-        if (c.ctx != set->ctx) fail(LCTY_ERR_INVALID_INPUT, "the set and the reads belong to different contexts");
-        set->ctx->activate();
-        add_source(set, Source{c.n, c.h_len, c.d_len, c.d_off, c.d_bases, c.d_nm, [r](uint64_t i) { return sample_reads_name(r, i); }}, max_out, out_cnt, out_loci);
-    });
+    return guarded([&] { add_resident(set, r ? &r->chunk : nullptr, [r](uint64_t i) { return sample_reads_name(r, i); }, max_out, out_cnt, out_loci); });
 }
 
 int32_t lcty_recruited_sizes(lcty_recruited* set, uint32_t locus_ix, uint64_t* n_pairs, uint64_t* n_bases) {

@@ -12,8 +12,9 @@
 //   RadixSort       (hash of the name, stream ordinal): records of one hash side by side, in stream order
 //   pair_kernel     a lane per record: PairedBamReader's state machine replayed over the records of ITS name before it in the run of
 //                   its hash (names compared byte for byte), which says whether this record completes a pair and with whom
-//   exclusive_scan  over the completing records -> the pairs in the reference's order; assemble_kernel lays out the mates
-//                   (stream_kernel, assemble_kernel and offsets_kernel: lcty_bam_layout.hpp, shared with lcty_bam_stream.hip)
+//   exclusive_scan  over the completing records -> the pairs in the reference's order; assemble_kernel gives every mate its record,
+//                   length and units (stream_kernel, assemble_kernel: lcty_bam_layout.hpp, shared with lcty_bam_stream.hip), and
+//                   ReadChunk::place (lcty_read_chunk.hpp) lays the mates out: the chunk the handle keeps, sized once
 //   unpack_kernel   a lane per 32 bases of a mate: 4-bit codes -> bases2 / nmask, back to front and complemented for reverse records;
 //                   a lane writes whole words of its own only
 // The record on the device (lcty_bam_record.hpp) and the front half of a fetch (fetch_slice, lcty_sample_bam.hpp, over the slice of
@@ -24,11 +25,9 @@
 #include <vector>
 
 #include "lcty_bam_layout.hpp"
-#include "lcty_objects.hpp"
 #include "lcty_sample_bam.hpp"
 #include "lcty_scan.hpp"
 #include "lcty_sort.hpp"
-#include "lcty_writers.hpp"
 
 namespace lcty {
 
@@ -188,14 +187,6 @@ void check_regions(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, co
     }
 }
 
-std::string record_name(const uint8_t* slice, uint64_t o) {
-    const uint32_t l = slice[o + 12];
-    std::string s(reinterpret_cast<const char*>(slice + o + 36), l ? l - 1 : 0);
-    const size_t z = s.find('\0');
-    if (z != std::string::npos) s.resize(z);
-    return s;
-}
-
 void fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
                  bool with_unmapped, bool whole_file, Slice& F, lcty_sample_bam_stats& S) {
     const char* path = bam->file.path.c_str();
@@ -350,8 +341,8 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
         lcty_sample_bam_stats S{};
         S.n_regions = n_regions; S.file_bytes = bam->file.fsize;
         // ---- the front half: chunks, pread, BGZF split, inflate, the chain of record lengths
-        std::unique_ptr<lcty_sample_reads> R(new lcty_sample_reads());
-        R->ctx = ctx; R->paired = paired != 0;
+        std::unique_ptr<lcty_sample_reads> R(new lcty_sample_reads(ctx, ReadChunk::Buffers::OneShot));
+        ReadChunk& C = R->chunk; C.paired = paired != 0;
         fetch_slice(ctx, bam, n_regions, tid, start, end, with_unmapped != 0, whole_file != 0, R->F, S);
         hipStream_t s = ctx->stream;
         const std::vector<uint64_t>& rec_off = R->F.rec_off;
@@ -364,7 +355,7 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
             if (stats) *stats = S;
             *reads = R.release();
         };
-        if (n_rec == 0) { R->zero_off.assign(1, 0); R->h_off.assign(1, 0); R->have_bases = true; R->h_bases.assign(2, 0); R->h_nm.assign(1, 0); finish(); return; }
+        if (n_rec == 0) { finish(); return; }                                    // the empty chunk
 
         // ---- upload, record kernel
         t0 = now_ms();
@@ -439,28 +430,22 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
 
         // ---- the mates and their bases
         t0 = now_ms();
-        R->n = n_out;
-        R->zero_off.assign(n_out + 1, 0);
-        if (n_out == 0) { R->h_off.assign(1, 0); R->have_bases = true; R->h_bases.assign(2, 0); R->h_nm.assign(1, 0); finish(); return; }
-        DevBuf<uint32_t> d_units, d_unit_off, d_src_stream;
-        d_src_stream.alloc(2 * n_out);
-        R->d_src.alloc(2 * n_out); R->d_len.alloc(2 * n_out); d_units.alloc(2 * n_out); R->d_off.alloc(2 * n_out + 1);
+        if (n_out == 0) { finish(); return; }
+        DevBuf<uint32_t> d_units, d_src, d_src_stream;
+        C.reserve_mates(n_out);
+        d_src_stream.alloc(2 * n_out); d_src.alloc(2 * n_out); d_units.alloc(2 * n_out);
         hipLaunchKernelGGL(assemble_kernel, dim3(blocks_of(n_stream, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_info.p, d_stream.p, n_stream, paired ? 1 : 0,
-                           d_mate_of.p, d_pair_ix.p, R->d_src.p, d_src_stream.p, R->d_len.p, d_units.p);
+                           d_mate_of.p, d_pair_ix.p, d_src.p, d_src_stream.p, C.d_len.p, d_units.p);
         LCTY_HIP(hipGetLastError());
-        const uint32_t n_units = scan.run(d_units, d_unit_off, 2 * n_out, ctx);
-        R->n_units = n_units;
-        hipLaunchKernelGGL(offsets_kernel, dim3(blocks_of(2 * n_out + 1, 256)), dim3(256), 0, s, d_unit_off.p, 2 * n_out + 1, R->d_off.p);
-        R->d_bases.alloc(std::max<uint32_t>(n_units, 1)); R->d_nm.alloc(std::max<uint32_t>(n_units, 1));
-        R->d_bases.zero(s); R->d_nm.zero(s);
+        const uint32_t n_units = C.place(d_units, 2 * n_out, scan);
         if (n_units)
-            hipLaunchKernelGGL(unpack_kernel<true>, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, R->d_src.p, d_unit_off.p,
-                               static_cast<uint32_t>(2 * n_out), n_units, R->d_bases.p, R->d_nm.p);
+            hipLaunchKernelGGL(unpack_kernel<true>, dim3(blocks_of(n_units, 256)), dim3(256), 0, s, raw, d_rec_off.p, d_src.p, C.d_unit_off.p,
+                               static_cast<uint32_t>(2 * n_out), n_units, C.d_bases.p, C.d_nm.p);
         LCTY_HIP(hipGetLastError());
-        R->h_len.resize(2 * n_out); R->h_src.resize(2 * n_out); R->h_off.resize(2 * n_out + 1);
-        R->h_src_stream.resize(2 * n_out); d_src_stream.download(R->h_src_stream.data(), 2 * n_out, s);
-        R->d_len.download(R->h_len.data(), 2 * n_out, s); R->d_src.download(R->h_src.data(), 2 * n_out, s); R->d_off.download(R->h_off.data(), 2 * n_out + 1, s);
+        R->h_src.resize(2 * n_out); R->h_src_stream.resize(2 * n_out);
+        d_src_stream.download(R->h_src_stream.data(), 2 * n_out, s); d_src.download(R->h_src.data(), 2 * n_out, s);
         LCTY_HIP(hipStreamSynchronize(s));
+        C.d_unit_off.release();                                                  // nothing reads it behind the unpack: the handle keeps the chunk alone
         S.ms_unpack = now_ms() - t0;
         finish();
     });
@@ -469,35 +454,16 @@ int32_t lcty_sample_bam_fetch(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_re
 int32_t lcty_sample_reads_view(lcty_sample_reads* R, lcty_reads_host* view, const uint32_t** src_record, int32_t* paired) {
     return guarded([&] {
         if (!R || !view) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        if (!R->have_bases) {
-            R->ctx->activate();
-            hipStream_t s = R->ctx->stream;
-            R->h_bases.assign(2 * std::max<uint64_t>(R->n_units, 1), 0); R->h_nm.assign(std::max<uint64_t>(R->n_units, 1), 0);
-            if (R->n_units) {
-                LCTY_HIP(hipMemcpyAsync(R->h_bases.data(), R->d_bases.p, 8 * R->n_units, hipMemcpyDeviceToHost, s));
-                R->d_nm.download(R->h_nm.data(), R->n_units, s);
-                LCTY_HIP(hipStreamSynchronize(s));
-            }
-            R->have_bases = true;
-        }
-        memset(view, 0, sizeof(*view));
-        view->n_pairs = R->n;
-        view->mate_len = R->h_len.data(); view->mate_off = R->h_off.data(); view->bases2 = R->h_bases.data(); view->nmask = R->h_nm.data();
-        view->aln_off = R->zero_off.data(); view->cigar_off = R->zero_off.data();
+        R->chunk.view(view);
         if (src_record) *src_record = R->h_src_stream.data();
-        if (paired) *paired = R->paired ? 1 : 0;
+        if (paired) *paired = R->chunk.paired ? 1 : 0;
     });
 }
 
 int32_t lcty_sample_reads_recruit(lcty_targets* targets, lcty_sample_reads* R, uint32_t max_out, uint32_t* out_cnt, uint32_t* out_loci) {
     return guarded([&] {
         if (!targets || !R || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        lcty_ctx* ctx = targets_ctx(targets);
-        if (ctx != R->ctx) fail(LCTY_ERR_INVALID_INPUT, "the targets and the reads belong to different contexts");
-        if (R->n == 0) return;
-        ctx->activate();
-        recruit_device_view(targets, R->n, R->h_len.data(), R->d_len.p, R->d_off.p, reinterpret_cast<const uint32_t*>(R->d_bases.p), R->d_nm.p, R->paired ? 1 : 0,
-                            max_out, out_cnt, out_loci);
+        R->chunk.recruit(targets, max_out, out_cnt, out_loci);
     });
 }
 
@@ -505,44 +471,12 @@ int32_t lcty_sample_reads_write_recruited(lcty_sample_reads* R, lcty_fastx_write
                                           const uint32_t* out_loci, uint64_t* n_written) {
     return guarded([&] {
         if (!R || !w || !out_cnt || !out_loci || max_out == 0) fail(LCTY_ERR_INVALID_INPUT, "null argument");
-        static const char CODES[] = "=ACMGRSVTWYHKDBN";
-        uint64_t written = 0;
-        std::string text;
-        for (uint64_t i = 0; i < R->n; i++) {
-            if (!out_cnt[i]) continue;
-            text.clear();
-            for (uint32_t e = 0; e < 2; e++) {                                   // BamRecord::write_to (fastx.rs:633-668), the mates one after the other
+        const uint64_t written = write_recruited_units(w, R->chunk.n, max_out, out_cnt, out_loci, [&](uint64_t i, std::string& text) {
+            for (uint32_t e = 0; e < 2; e++) {                                   // the mates one after the other
                 const uint32_t r = R->h_src[2 * i + e];
-                if (r == NONE32) continue;
-                const uint8_t* rec = R->F.slice + R->F.rec_off[r];
-                uint32_t l_seq; uint16_t n_cigar, flag;
-                memcpy(&n_cigar, rec + 16, 2); memcpy(&flag, rec + 18, 2); memcpy(&l_seq, rec + 20, 4);
-                const uint8_t* seq = rec + 36 + rec[12] + 4ull * n_cigar;
-                const uint8_t* qual = seq + (static_cast<uint64_t>(l_seq) + 1) / 2;
-                const bool reverse = (flag & 0x10) != 0, fasta = l_seq == 0 || qual[0] == 255;
-                text += fasta ? '>' : '@';
-                text += record_name(R->F.slice, R->F.rec_off[r]);
-                text += '\n';
-                for (uint32_t k = 0; k < l_seq; k++) {
-                    const uint32_t j = reverse ? l_seq - 1 - k : k;
-                    const char c = CODES[(seq[j >> 1] >> ((j & 1) ? 0 : 4)) & 15];
-                    // seq::complement_nt (seq/mod.rs:125-135): IUPAC codes become N ('=' panics there; N here)
-                    text += !reverse ? c : c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N';
-                }
-                text += '\n';
-                if (!fasta) {
-                    text += "+\n";
-                    for (uint32_t k = 0; k < l_seq; k++) text += static_cast<char>(qual[reverse ? l_seq - 1 - k : k] + 33);
-                    text += '\n';
-                }
+                if (r != NONE32) bam_record_text(R->F.slice, R->F.rec_off[r], text);
             }
-            for (uint32_t j = 0; j < std::min(out_cnt[i], max_out); j++) {
-                const uint32_t locus = out_loci[static_cast<size_t>(i) * max_out + j];
-                if (locus >= w->paths.size()) fail(LCTY_ERR_INVALID_INPUT, "record %llu is recruited to locus %u of %zu writers", static_cast<unsigned long long>(i), locus, w->paths.size());
-                w->put(locus, text);
-            }
-            written++;
-        }
+        });
         if (n_written) *n_written = written;
     });
 }
@@ -553,9 +487,6 @@ void lcty_sample_reads_free(lcty_sample_reads* reads) { delete reads; }
 
 namespace lcty {
 
-ResidentChunk sample_reads_chunk(lcty_sample_reads* R) {
-    return ResidentChunk{R->ctx, R->n, R->h_len.data(), R->d_len.p, R->d_off.p, R->d_bases.p, R->d_nm.p};
-}
 // the name lcty_sample_reads_write_recruited writes for pair i: its first read end's
 std::string sample_reads_name(lcty_sample_reads* R, uint64_t i) {
     const uint32_t r = R->h_src[2 * i] != NONE32 ? R->h_src[2 * i] : R->h_src[2 * i + 1];

@@ -11,6 +11,8 @@
 
 #include "lcty_bam_record.hpp"
 #include "lcty_bgzf_read.hpp"
+#include "lcty_read_chunk.hpp"
+#include "lcty_writers.hpp"
 
 struct lcty_sample_bam {
     lcty::BgzfFile file;
@@ -23,17 +25,14 @@ struct lcty_sample_bam {
     uint64_t n_no_coor = 0; bool has_no_coor = false;
 };
 
-// The reads of one fetch, or of one window of a stream of whole files (lcty_bam_stream.hip), resident on the device.
+// The reads of one fetch, or of one window of a stream of whole files (lcty_bam_stream.hip), resident on the device: the chunk
+// (lcty_read_chunk.hpp) and what the records are written from.
 struct lcty_sample_reads {
-    lcty_ctx* ctx = nullptr;
-    bool paired = false;
-    uint64_t n = 0;                              // pairs, or single reads
+    lcty::ReadChunk chunk;
     lcty::Slice F;                               // the inflated blocks of the call and the records walked in them
-    lcty::DevBuf<uint32_t> d_len, d_nm, d_src; lcty::DevBuf<uint64_t> d_off, d_bases;
-    uint64_t n_units = 0;
-    std::vector<uint32_t> h_len, h_src, h_src_stream, h_bases, h_nm;    // h_src: a mate's record among the records walked (rec_off); _stream: in the fetched stream
-    std::vector<uint64_t> h_off, zero_off;
-    bool have_bases = false;
+    std::vector<uint32_t> h_src, h_src_stream;   // h_src: a mate's record among the records walked (rec_off); _stream: in the fetched stream
+    lcty_sample_reads(lcty_ctx* ctx, lcty::ReadChunk::Buffers b) : chunk(ctx, b) {}
+    void clear() { chunk.clear(); h_src.clear(); h_src_stream.clear(); }
 };
 
 namespace lcty {
@@ -44,7 +43,5 @@ void check_regions(const lcty_sample_bam* b, uint32_t n, const uint32_t* tid, co
 // record lengths of one call, with the errors lcty_sample_bam_fetch documents for them. Fills F and the fields of S up to ms_walk.
 void fetch_slice(lcty_ctx* ctx, lcty_sample_bam* bam, uint32_t n_regions, const uint32_t* tid, const uint32_t* start, const uint32_t* end,
                  bool with_unmapped, bool whole_file, Slice& F, lcty_sample_bam_stats& S);
-// the name of the record at byte o of a slice
-std::string record_name(const uint8_t* slice, uint64_t o);
 
 }  // namespace lcty
